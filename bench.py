@@ -28,8 +28,11 @@ After the timed region rank 0 adds, at N=1: the dominant kernel's roofline figur
 (HIP events on the engine's stream), the CPU oracle timed on one host core, and an
 end-to-end run of the C CLI through files (BAM + GTF in, GTF / detail / summary / bed
 out) on the same 10 M reads (--no-e2e skips it).
+--dump-outputs DIR writes what the last timed step computed (per-read results, and
+the accepted list when the step makes it) as DIR/<name>.npy, so that two builds can
+be compared output for output on the same seeded inputs.
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
 """
 from __future__ import annotations
@@ -480,6 +483,51 @@ def c_route_leg(world: int, dev_map, args, capi, workload, dev_index: int):
     return out
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+DUMP_SAMPLE_READS = 1 << 17
+
+
+def _dump_records(np, sel, read_index, info, ref_tx, ex_off, ex_start, ex_end, ex_flag):
+    """Records `sel` of a result set (one row per record, its exons at ex_off[i] .. ex_off[i + 1]) with their exons, record by record."""
+    lo, hi = ex_off[:-1][sel], ex_off[1:][sel]
+    n_ex = hi - lo
+    first = np.cumsum(n_ex) - n_ex
+    ex = np.arange(int(n_ex.sum()), dtype=np.int64) + np.repeat(lo - first, n_ex)
+    return {"read_index": read_index[sel], "info": info[sel], "ref_tx": ref_tx[sel], "ex_off": lo, "n_exons": n_ex,
+            "ex_start": ex_start[ex], "ex_end": ex_end[ex], "ex_flag": ex_flag[ex]}
+
+
+def dump_outputs(directory, eng, with_accepted: bool, first_read_index: int, prefix: str = "", limit: int = DUMP_LIMIT_BYTES):
+    """--dump-outputs: what the last step left for its caller (l2r_download's per-read results; l2r_download_accepted's list when the step
+    made it) as <directory>/<prefix><name>.npy in float64, which holds every int32 / uint32 / int64 value exactly.  ex_off is where a
+    read's exons start in the caller's arrays.  Beyond `limit` bytes the reads are a sample: the first k of a permutation seeded with 0
+    that depends on the read count alone, k = DUMP_SAMPLE_READS halved until the files fit -- two builds that compute the same results
+    dump the same reads."""
+    import numpy as np
+    got = eng.download()
+    n = int(got.info.shape[0])
+    acc = eng.download_accepted() if with_accepted else None
+    order = np.random.default_rng(0).permutation(n) if n > DUMP_SAMPLE_READS else np.arange(n)
+    k = min(n, DUMP_SAMPLE_READS)
+    while True:
+        sel = np.zeros(n, bool)
+        sel[order[:k]] = True
+        arrays = _dump_records(np, sel, np.arange(n, dtype=np.int64) + first_read_index, got.info, got.ref_tx, got.ex_off, got.ex_start,
+                               got.ex_end, got.ex_flag)
+        if acc is not None:
+            a_read = acc.read_index
+            a = _dump_records(np, sel[a_read - first_read_index], a_read, acc.rec["info"], acc.rec["ref_tx"], acc.ex_off, acc.ex_start,
+                              acc.ex_end, acc.ex_flag)
+            arrays.update({"accepted_" + name: v for name, v in a.items()})
+        if sum(8 * v.size for v in arrays.values()) <= limit or k == 1:
+            break
+        k //= 2
+    os.makedirs(directory, exist_ok=True)
+    for name, v in arrays.items():
+        np.save(os.path.join(directory, prefix + name + ".npy"), v.astype(np.float64))
+    return {"dir": directory, "reads": n, "sampled_reads": k, "files": len(arrays)}
+
+
 def launcher_argv(args, port: int):
     """The command `bench.py --gpus N` starts when no launcher has set WORLD_SIZE: the shape the driver uses itself."""
     passed = [a for a in sys.argv[1:] if a != "--dry-launch"]
@@ -538,7 +586,12 @@ def main():
     ap.add_argument("--no-c-route", action="store_true", help="N > 1: skip the C CLI's own multi-GPU run (L2R_GPUS=N) behind the process group")
     ap.add_argument("--c-route-reads", type=int, default=1_000_000, help="N > 1: reads of the C route's leg")
     ap.add_argument("--dry-launch", action="store_true", help="print the launcher command a plain `bench.py --gpus N` would start, and exit")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (float64; a fixed sample of the reads "
+                         "beyond 64 MB; at N > 1 every rank writes rank<k>.<name>.npy)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     rank = int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -662,6 +715,10 @@ def main():
     # `roofline.frac` -- a read set is classified in a stream of such steps, on the clock the chip settles at.
     dt_cold, _ = timed_region(args.steps, args.warmup, gather_headline)
     dt, last = timed_region(args.steps, args.warmup, gather_headline)
+    dumped = None
+    if args.dump_outputs:
+        dumped = dump_outputs(args.dump_outputs, eng, gather_headline or args.accepted, rank * reads.n,
+                              prefix="rank%d." % rank if world > 1 else "", limit=DUMP_LIMIT_BYTES // world)
 
     n_r, n_x, n_acc, n_acc_x = eng.sizes()
     per_rank = [[reads.n, n_x, n_acc, n_acc_x]]
@@ -840,6 +897,8 @@ def main():
             "cpu_baseline": cpu,
             "e2e": e2e,
         }
+        if dumped is not None:
+            out["dumped_outputs"] = dumped
     if world > 1:
         dist.barrier()
         dist.destroy_process_group()

@@ -45,6 +45,11 @@ def test_a_world_that_does_not_match_gpus_is_refused():
     assert r.returncode == 2
 
 
+def test_no_timed_steps_is_refused():
+    r = subprocess.run([sys.executable, BENCH, "--steps", "0"], env=_env(), stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=120)
+    assert r.returncode == 2 and b"--steps" in r.stderr
+
+
 def test_fast_junction_table_is_the_generators(oracle):
     from lr2rmats_amd import synth
     anno = synth.make_annotation(12000, 11); af = anno.in_file_order()
@@ -60,6 +65,41 @@ def test_fast_junction_table_is_the_generators(oracle):
     key = (c.tid.astype(np.int64) << 56) | (c.don.astype(np.int64) << 25) | (c.acc - c.don)
     assert np.all(np.diff(key) > 0)                                                # sorted by (tid, don, acc), no duplicates
 
+
+
+def test_dump_outputs_sample_fits_the_limit(tmp_path):
+    """`--dump-outputs` beyond its size limit: the reads are a prefix of a permutation seeded by the read count alone, halved until the
+    files fit, each with its exons; the arrays are the caller's own values in float64."""
+    import bench
+    from lr2rmats_amd import capi
+    rng = np.random.default_rng(5)
+    n = 200_000
+    off = np.zeros(n + 1, np.int64)
+    off[1:] = np.cumsum(rng.integers(1, 12, n))
+    x = int(off[-1])
+    res = capi.Result(off, rng.integers(0, 2**31 - 1, x).astype(np.int32), rng.integers(0, 2**31 - 1, x).astype(np.int32),
+                      rng.integers(0, 256, x).astype(np.uint8), rng.integers(0, 2**32, n).astype(np.uint32), rng.integers(-1, 2**31 - 1, n).astype(np.int32))
+
+    class Eng:
+        def download(self):
+            return res
+    d = str(tmp_path / "d")
+    info = bench.dump_outputs(d, Eng(), False, 0, limit=8 << 20)
+    names = sorted(os.listdir(d))
+    assert sum(os.path.getsize(os.path.join(d, f)) for f in names) <= 8 << 20
+    dump = {f[:-4]: np.load(os.path.join(d, f)) for f in names}
+    assert set(dump) == {"read_index", "info", "ref_tx", "ex_off", "n_exons", "ex_start", "ex_end", "ex_flag"}
+    k = info["sampled_reads"]
+    assert k < bench.DUMP_SAMPLE_READS and info["reads"] == n
+    ri = np.sort(np.random.default_rng(0).permutation(n)[:k])
+    np.testing.assert_array_equal(dump["read_index"], ri)
+    for name in ("info", "ref_tx"):
+        assert dump[name].dtype == np.float64
+        np.testing.assert_array_equal(dump[name], getattr(res, name)[ri])
+    np.testing.assert_array_equal(dump["ex_off"], off[ri])
+    ex = np.concatenate([np.arange(off[i], off[i + 1]) for i in ri])
+    for name in ("ex_start", "ex_end", "ex_flag"):
+        np.testing.assert_array_equal(dump[name], getattr(res, name)[ex])
 
 @pytest.mark.gpu
 def test_self_launched_world_of_two_on_one_gpu():
@@ -112,3 +152,38 @@ def test_one_gpu_line_has_the_contract_fields():
         assert k in cb, k
     assert cb["kind"] == "port" and cb["cores"] == 1 and cb["value"] > 0 and cb["parity_on_sample"] is True
     assert d["second_pass"]["ms_per_step"] > 0 and d["with_accepted"]["ms_per_step"] > 0
+
+
+@pytest.mark.gpu
+def test_dump_outputs_are_the_last_steps_results(oracle, tmp_path):
+    """`--dump-outputs DIR`: the per-read results and the accepted list of the timed path's last step as float64 .npy files, every read of
+    a small workload (below the size limit nothing is sampled), bit for bit what the oracle computes on the same seeded inputs."""
+    from lr2rmats_amd import capi, workload
+    from tests import util
+    d = str(tmp_path / "dump")
+    r = subprocess.run([sys.executable, BENCH, "--steps", "2", "--warmup", "1", "--config", "cfg2", "--reads", "60000", "--accepted", "--no-cpu",
+                        "--no-gencode", "--no-e2e", "--no-second-pass", "--dump-outputs", d], env=_env(), stdout=subprocess.PIPE,
+                       stderr=subprocess.PIPE, timeout=900)
+    assert r.returncode == 0, r.stderr.decode()[-2000:]
+    line = json.loads(r.stdout.decode().strip().splitlines()[-1])
+    assert line["steps"] == 2 and line["dumped_outputs"]["reads"] == line["dumped_outputs"]["sampled_reads"] == 60000
+    names = sorted(os.listdir(d))
+    assert sum(os.path.getsize(os.path.join(d, f)) for f in names) <= 64 << 20
+    dump = {f[:-4]: np.load(os.path.join(d, f)) for f in names}
+    assert all(v.dtype == np.float64 for v in dump.values())
+    cfg = dict(workload.CONFIGS["cfg2"], n_reads=60000)
+    af, reads = workload.make_rank_workload(cfg, 0, 1)
+    want = util.oracle_run(oracle, af, reads, oracle.default_params(full_level=3))
+    np.testing.assert_array_equal(dump["read_index"], np.arange(reads.n))
+    ex_off = np.append(dump["ex_off"], dump["ex_off"][-1] + dump["n_exons"][-1]).astype(np.int64)
+    got = capi.Result(ex_off, dump["ex_start"].astype(np.int32), dump["ex_end"].astype(np.int32), dump["ex_flag"].astype(np.uint8),
+                      dump["info"].astype(np.uint32), dump["ref_tx"].astype(np.int32))
+    util.assert_same_result(got, want, 0, 0)
+    acc = np.flatnonzero(got.info & 128)
+    assert acc.size > 0
+    np.testing.assert_array_equal(dump["accepted_read_index"], acc)
+    np.testing.assert_array_equal(dump["accepted_info"], dump["info"][acc])
+    np.testing.assert_array_equal(dump["accepted_n_exons"], dump["n_exons"][acc])
+    ex = np.concatenate([np.arange(got.ex_off[i], got.ex_off[i + 1]) for i in acc])
+    for k in ("ex_start", "ex_end", "ex_flag"):
+        np.testing.assert_array_equal(dump["accepted_" + k], dump[k][ex])
