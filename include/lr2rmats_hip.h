@@ -262,8 +262,11 @@ void         l2r_xchg_destroy(l2r_xchg *x);
  *   several entries, [2] annotation transcripts the mask kernels take, [3] tiles, [4..11] tiles by the reason their descriptor
  *   is not on the 32-bit masks (0 = it is), [12] tiles of the 64-bit-mask kernel, [13] runs that l2r_sync did again on the slab pipeline
  *   because a tile of k_tile had waited in vain for the exon counts in front of it, [14] entries of the chunked kernel's list that k_tile_chunk
- *   declined in the last run (its staging caps), [15] tiles handed to the chunked kernel late (a key in several entries); n = words of out
- *   (4, 12, 13, 14 or 16).
+ *   declined in the last run (its staging caps), [15] tiles handed to the chunked kernel late (a key in several entries); the last run's
+ *   tile descriptors (slab / tile pipeline; classic: 24 and 25 only): [16..20] tiles of the chunked kernels by the END entries of their
+ *   dictionary slices (<= 256, <= 512, <= 768, <= 1024, more), [21] / [22] ... with more than 128 / 256 START entries, [23] all of
+ *   them, [24] / [25] the largest START / END slice of any tile, [26] tiles k_tile_chunk took from their CIGARs (TD_CDIRECT);
+ *   n = words of out (4, 12, 13, 14, 16, 24 or 27).
  * l2r_debug_stamps: with L2R_STAMPS=1 in the environment at l2r_upload_reads, per-phase cycle sums of the classification kernel
  *   (and clears them); zeros otherwise.
  * l2r_debug_tile_times: with L2R_STAMPS=1, one-kernel tile path: four words per tile -- the chip's 100 MHz clock at the tile's start

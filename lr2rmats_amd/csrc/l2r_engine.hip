@@ -1478,6 +1478,7 @@ int l2r_debug_counters(l2r_ctx *c, long long *out, int n)
     out[0] = redo; out[1] = c->n_wide; out[2] = c->n_compact; out[3] = c->n_tiles;
     if (n >= 12) for (int k = 0; k < 8; ++k) out[4 + k] = 0;
     if (n >= 13) out[12] = 0;
+    for (int k = 16; k < std::min(n, 27); ++k) out[k] = 0;         // (the descriptor words below: 0 where no run left descriptors)
     if (n >= 14) out[13] = c->n_lb_fallback;              // runs done again on the slab pipeline because k_tile's look-back starved
     if (n >= 16) {                                        // one-kernel tile path, last run: entries of chunk_list k_tile_chunk declined, tiles handed to the chunked kernel late
         out[14] = 0; out[15] = 0;
@@ -1492,8 +1493,11 @@ int l2r_debug_counters(l2r_ctx *c, long long *out, int n)
         std::vector<TileWin> w((size_t)c->n_tiles);
         HIP_TRY(hipMemcpyAsync(w.data(), c->tw.p, w.size() * sizeof(TileWin), hipMemcpyDeviceToHost, c->stream));
         HIP_TRY(hipStreamSynchronize(c->stream));
-        if (n >= 24) for (int k = 16; k < 24; ++k) out[k] = 0;
         for (const TileWin &t : w) {
+            if (n >= 27) {                                  // largest dictionary slices of any tile, tiles k_tile_chunk took (k_describe_scan<true>)
+                out[24] = std::max<long long>(out[24], t.d.st_nk); out[25] = std::max<long long>(out[25], t.d.en_nk);
+                if (t.d.flags & TD_CDIRECT) out[26]++;
+            }
             if (n >= 24) {                                  // tiles of the chunked kernel by the END entries of their dictionary slices (<= 256, 512, 768, 1024, more), START entries beyond 128 / 256, all of them
                 const uint32_t why = (t.d.flags >> 8) & 7u;
                 if ((t.d.flags & TD_CHUNK) || (!(t.d.flags & (TD_FAST | TD_WIDE)) && (why == 4u || why == 3u))) {
@@ -1510,7 +1514,10 @@ int l2r_debug_counters(l2r_ctx *c, long long *out, int n)
         std::vector<TileDesc> d((size_t)c->n_tiles);
         HIP_TRY(hipMemcpyAsync(d.data(), c->desc.p, d.size() * sizeof(TileDesc), hipMemcpyDeviceToHost, c->stream));
         HIP_TRY(hipStreamSynchronize(c->stream));
-        for (const TileDesc &t : d) out[4 + ((t.flags >> 8) & 7u)]++;
+        for (const TileDesc &t : d) {
+            out[4 + ((t.flags >> 8) & 7u)]++;
+            if (n >= 27) { out[24] = std::max<long long>(out[24], t.st_nk); out[25] = std::max<long long>(out[25], t.en_nk); }
+        }
     }
     return 0;
 }

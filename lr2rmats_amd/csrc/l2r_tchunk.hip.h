@@ -44,6 +44,7 @@ constexpr int TC_TRIPS = 256;                            // stretches of 63 tran
 constexpr int TC_CHUNKS = 64;                            // ... and the ones with members a tile may have (4 k members)
 constexpr int TC_DIR_N = DIR_CAP + 4;                    // directory words per dictionary (bucket b's first entry, two closing words)
 static_assert(TC_ST_CAP <= 512 && TC_EN_CAP <= 512, "9-bit entry numbers in a lookup word");
+static_assert(TC_ST_CAP - 1 <= 511 && TC_EN_CAP - 1 <= 511, "the zero slot (entry number st_nk / en_nk, below the cap: tile_chunk_direct) in 9 bits");
 // A position's lookup word (s_R): START half in bits 0-13, END half in bits 14-27 -- first part (9 bits) | parts (4 bits) << 9 | "the pair
 // matches" << 13 --, the exon's novel flags still standing in bits 28-31 (F_EXON | F_DON | F_ACC | F_JUNC).
 constexpr int TC_HALF_BITS = 14, TC_F_SHIFT = 28;

@@ -56,8 +56,9 @@ def pipeline(request, monkeypatch):
     return request.param
 
 
-def _run(oracle, af, reads, counters=None, sj=None, **kw):
-    want = util.oracle_run(oracle, af, reads, oracle.default_params(**kw), sj)
+def _run(oracle, af, reads, counters=None, sj=None, words=None, want=None, **kw):
+    if want is None:                            # (want: the oracle's result for these inputs and parameters, when the caller has it)
+        want = util.oracle_run(oracle, af, reads, oracle.default_params(**kw), sj)
     eng = capi.Engine(0)
     try:
         eng.set_annotation(af.tx_tid, af.tx_start, af.tx_end, af.tx_rev, af.tx_ex_off, af.ex_start, af.ex_end)
@@ -81,6 +82,13 @@ def _run(oracle, af, reads, counters=None, sj=None, **kw):
             lib.l2r_debug_counters.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
             lib.l2r_debug_counters(eng.ctx, cnt, 13)
             counters[:] = list(cnt)[:4] + [cnt[12]]      # (... , tiles the 64-member kernel took)
+        if words is not None:                   # every word l2r_debug_counters has (include/lr2rmats_hip.h)
+            import ctypes as C
+            lib = capi.load_library()
+            cnt = (C.c_longlong * 27)()
+            lib.l2r_debug_counters.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
+            assert lib.l2r_debug_counters(eng.ctx, cnt, 27) == 0
+            words[:] = list(cnt)
     finally:
         eng.close()
     util.assert_same_result(got, want, 0 if sj is None else len(sj[0]), kw.get("split_trans", 0))
