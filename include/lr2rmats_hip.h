@@ -267,7 +267,7 @@ void         l2r_xchg_destroy(l2r_xchg *x);
  *   dictionary slices (<= 256, <= 512, <= 768, <= 1024, more), [21] / [22] ... with more than 128 / 256 START entries, [23] all of
  *   them, [24] / [25] the largest START / END slice of any tile, [26] tiles k_tile_chunk took from their CIGARs (TD_CDIRECT);
  *   n = words of out (4, 12, 13, 14, 16, 24 or 27).
- * l2r_debug_stamps: with L2R_STAMPS=1 in the environment at l2r_upload_reads, per-phase cycle sums of the classification kernel
+ * l2r_debug_stamps: with L2R_STAMPS=1 in the environment at l2r_create, per-phase cycle sums of the classification kernel
  *   (and clears them); zeros otherwise.
  * l2r_debug_tile_times: with L2R_STAMPS=1, one-kernel tile path: four words per tile -- the chip's 100 MHz clock at the tile's start
  *   << 3 | its XCD, at the publication of its exon count, at the begin and the end of its wait for the counts in front. */

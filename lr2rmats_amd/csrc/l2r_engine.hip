@@ -12,6 +12,7 @@
 #include <algorithm>
 #include <string>
 #include <thread>
+#include <type_traits>
 #include <utility>
 #include <vector>
 
@@ -46,6 +47,10 @@ template <typename T>
 struct DevBuf {
     T *p = nullptr;
     size_t cap = 0;     // elements
+    DevBuf() = default;
+    DevBuf(const DevBuf &) = delete;
+    DevBuf &operator=(const DevBuf &) = delete;
+    ~DevBuf() { release(); }
     int ensure(size_t n)
     {
         if (n <= cap && p) return 0;
@@ -62,6 +67,10 @@ struct DevBuf {
     void release() { if (p) (void)hipFree(p); p = nullptr; cap = 0; }
 };
 
+// The three kernel pipelines: classic (l2r_kernels.hip.h, two walks), slab (l2r_slab.hip.h, one walk, two kernels), tile (l2r_tile.hip.h,
+// one kernel per tile).  The upload says which of them its layout allows, choose_pipeline which one a launch takes.
+enum class Pipeline { classic, slab, tile };
+
 struct l2r_ctx {
     int device = 0;
     int fast_grid = 0;
@@ -69,10 +78,10 @@ struct l2r_ctx {
     int n_cu = 256, wg_per_cu = 4;          // persistent grid of k_classify_fast (L2R_WG_PER_CU overrides)
     int ablate = 0;                         // diagnostics, L2R_ABLATE (read once, at l2r_create)
     int64_t seg_max = SEG_MAX;              // tiles up to which the segmented scans are used (l2r_kernels.hip.h); L2R_SEG_MAX
-    int want_pipeline = 2;                  // L2R_PIPELINE: classic (0: l2r_kernels.hip.h, two walks), slab (1: l2r_slab.hip.h, one walk, two kernels), tile (2, default: l2r_tile.hip.h, one kernel per tile where the input allows it, else slab)
+    Pipeline want_pipe = Pipeline::tile;    // L2R_PIPELINE (see Pipeline); the default takes the tile path where the input allows it, else slab
     bool many_exon_reads = false;           // the upload's sample: more than 0.5 % of the reads have more exons than a slab has rows
     bool slab_ok = false;                   // the current upload can run the slab pipeline: coordinate-sorted records, short CIGARs, its slab layout fits
-    bool slab = false;                      // ... and the last launch did (the parameters have a say: launch_all)
+    Pipeline pipe = Pipeline::classic;      // ... what the last launch took (the parameters have a say: choose_pipeline)
     bool lists_heavy = false;                           // ... or most tiles went to them (an isoform-rich annotation): k_tile would only walk for them, which k_walk_slab does faster -- later runs take the slab pipeline
     bool redo_empty = false;                            // ... and nothing to the generic kernel either: every read had its junction check in k_tile, k_validate_sj has nothing to do
     bool wide_direct = true;                            // L2R_WIDE_DIRECT=0: the exact 64-bit-mask tiles keep the slab form and k_probe_slab_wide (k_tile's WIDE instance, l2r_tile.hip.h)
@@ -87,12 +96,11 @@ struct l2r_ctx {
     uint32_t lc_flip = 0;                               // ... and which of the two blocks of list counters (SlabArgs::list_cnt / list_cnt_next)
     uint32_t lb_flip = 0;                               // which of the two lb_sup arrays the next run of the tile path uses (l2r_slab.hip.h SlabArgs::lb_sup)
     bool lists_known = false, lists_empty = false;      // one-kernel tile path: a completed run of these inputs and parameters left nothing to k_probe_slab / _wide / _chunked (l2r_sync looks): their launches are skipped until something changes
-    bool tile = false;                      // ... with the one-kernel tile path (l2r_tile.hip.h: short CIGARs, -e >= 1)
     DevBuf<unsigned long long> lb_tile, lb_blk, lb_sup;     // one-kernel tile path: the tiles' exon counts on their way to the later tiles' first slots
     DevBuf<uint32_t> fb_list;                               //                       the tiles it leaves to k_probe_slab
     DevBuf<uint16_t> sum_nn;                                //                       the records' N operations (l2r_reads::cig_summary) for k_tile_index<true>
     bool env_tile_anyway = false, env_launch_all = false;   // L2R_TILE_ANYWAY / L2R_LAUNCH_ALL (diagnostics), read once at l2r_create
-    int64_t inexact_tiles = -1;                             //                       tiles that are not exact under the parameters now set (-1: not counted yet; drop_graph forgets it)
+    int64_t inexact_tiles = -1;                             //                       tiles that are not exact under the parameters now set (-1: not counted yet; forget_list_state forgets it)
     bool tile_starved = false;                              //                       a tile of k_tile has waited in vain for the counts in front of it (or the device cannot hold the workgroups its look-back needs): the slab pipeline from then on
     int64_t n_lb_fallback = 0;                              //                       ... runs that were done again on the slab pipeline for that reason (l2r_debug_counters)
     bool have_index = false;                                //                       the current upload has its tile index (slot records, op statistics)
@@ -119,6 +127,7 @@ struct l2r_ctx {
     hipStream_t side[2] = {nullptr, nullptr};
     hipEvent_t ev_fork = nullptr, ev_join[2] = {nullptr, nullptr};
     bool side_on = true;
+    bool env_stamps = false;                // L2R_STAMPS (diagnostics): the next upload makes the `stamps` buffer
     l2r_params prm;
     // annotation
     int64_t n_tx = 0, n_anno_exon = 0;
@@ -180,20 +189,17 @@ struct l2r_ctx {
     DevBuf<int32_t> acc_start, acc_end;
     DevBuf<uint8_t> acc_flag;
     bool ran = false;
-    hipGraphExec_t graph = nullptr;         // the launch sequence of l2r_run, captured once per (inputs, parameters)
-    bool graph_valid = false;
     bool check_stages = false;              // L2R_CHECK
     DevBuf<unsigned long long> stamps;      // diagnostics, L2R_STAMPS=1
     uint32_t h_totals[3] = {0, 0, 0};
     bool totals_valid = false;
 };
 
-static void drop_graph(l2r_ctx *c)
+// What completed runs have shown about the tile path's lists and the inexact tiles: forgotten wherever inputs, parameters or outputs change
+static void forget_list_state(l2r_ctx *c)
 {
-    c->lists_known = false; c->lists_empty = false; c->redo_empty = false; c->lists_heavy = false;     // (called wherever inputs, parameters or outputs change)
+    c->lists_known = false; c->lists_empty = false; c->redo_empty = false; c->lists_heavy = false;
     c->inexact_tiles = -1;
-    if (c->graph) { (void)hipGraphExecDestroy(c->graph); c->graph = nullptr; }
-    c->graph_valid = false;
 }
 
 static DevParams dev_params(const l2r_ctx *c)
@@ -205,6 +211,25 @@ static DevParams dev_params(const l2r_ctx *c)
     p.n_tx = (int32_t)c->n_tx; p.n_sj = (int32_t)c->n_sj; p.reads_per_tile = c->reads_per_tile;
     p.ablate = c->ablate; p.want = (int32_t)c->want;
     return p;
+}
+
+// p.full_level (1 .. 5; anything else is 0: src/update_gtf.c:629-696, no evidence is gathered, full = lfull && rfull = 0) as a
+// compile-time constant for the kernels' level parameter, and a run-time flag as a compile-time bool: f(constant)
+template <typename F> static void with_level(int level, F &&f)
+{
+    switch (level) {
+    case 1: f(std::integral_constant<int, 1>()); break;
+    case 2: f(std::integral_constant<int, 2>()); break;
+    case 3: f(std::integral_constant<int, 3>()); break;
+    case 4: f(std::integral_constant<int, 4>()); break;
+    case 5: f(std::integral_constant<int, 5>()); break;
+    default: f(std::integral_constant<int, 0>()); break;
+    }
+}
+template <typename F> static void with_flag(bool on, F &&f)
+{
+    if (on) f(std::true_type());
+    else f(std::false_type());
 }
 
 static inline int64_t host_key(int32_t tid, int32_t x) { return ((int64_t)(tid + 1) << 32) | (uint32_t)x; }
@@ -235,12 +260,10 @@ l2r_ctx *l2r_create(int device)
     }
     int prio_lo = 0, prio_hi = 0;
     (void)hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi);      // (lowest, highest)
-    const char *sp = getenv("L2R_SIDE_PRIO");
     // (the side streams carry the long-lived workgroups: highest priority, so that they are on their way early and the plain instance's short ones
-    //  fill in -- measured on cfg3_gencode: lowest 0.665, default 0.660, highest 0.658 ms: the dispatcher hardly cares.  L2R_SIDE_PRIO: 0 default, < 0 lowest)
-    const int side_prio = !sp ? prio_hi : (atoi(sp) == 0 ? 0 : (atoi(sp) > 0 ? prio_hi : prio_lo));
+    //  fill in -- measured on cfg3_gencode: lowest 0.665, default 0.660, highest 0.658 ms: the dispatcher hardly cares)
     for (int k = 0; k < 2; ++k)
-        if (((e = hipStreamCreateWithPriority(&c->side[k], hipStreamNonBlocking, side_prio)) != hipSuccess &&
+        if (((e = hipStreamCreateWithPriority(&c->side[k], hipStreamNonBlocking, prio_hi)) != hipSuccess &&
              ((void)hipGetLastError(), e = hipStreamCreateWithFlags(&c->side[k], hipStreamNonBlocking)) != hipSuccess) ||      // (a runtime without stream priorities: a plain stream does)
             (e = hipEventCreateWithFlags(&c->ev_join[k], hipEventDisableTiming)) != hipSuccess) {
             fail(-2, "[l2r_create] side stream: %s", hipGetErrorString(e)); l2r_destroy(c); return nullptr;
@@ -269,8 +292,9 @@ l2r_ctx *l2r_create(int device)
         if (e) c->chunk_direct = atoi(e) != 0;
         e = getenv("L2R_SIDE");
         if (e) c->side_on = atoi(e) != 0;
+        c->env_stamps = getenv("L2R_STAMPS") != nullptr;
         e = getenv("L2R_PIPELINE");
-        if (e) { c->want_pipeline = !strcmp(e, "classic") ? 0 : !strcmp(e, "slab") ? 1 : 2; c->pipeline_forced = true; }
+        if (e) { c->want_pipe = !strcmp(e, "classic") ? Pipeline::classic : !strcmp(e, "slab") ? Pipeline::slab : Pipeline::tile; c->pipeline_forced = true; }
         {   // k_tile's look-back: a tile may wait for one whose workgroup comes up to 8 * TILE_GROUP - 1 block indices later (fused_tile), so
             // that many workgroups + 1 have to be resident together -- guaranteed nowhere; checked here (small or partitioned devices, CU
             // masks): a device that cannot hold them takes the slab pipeline from the start
@@ -285,20 +309,7 @@ l2r_ctx *l2r_create(int device)
 void l2r_destroy(l2r_ctx *c)
 {
     if (!c) return;
-    (void)hipSetDevice(c->device);
-    c->hdr.release(); c->anno_ex.release(); c->anno_key.release();
-    c->sk_st.release(); c->sk_en.release(); c->sd_st.release(); c->sd_en.release(); c->sr_st.release(); c->tid_base.release();
-    c->key_dir.release(); c->kb_base.release(); c->j0.release();
-    c->sj_tid.release(); c->sj_don.release(); c->sj_acc.release(); c->sj_uniq.release(); c->sj_multi.release(); c->sj_key.release(); c->sj_cbase.release(); c->sj_cdir.release(); c->sj_dbase.release(); c->sj_ddir.release(); c->sj_row.release();
-    c->r_tid.release(); c->r_pos.release(); c->r_rev.release(); c->cig_off.release(); c->cig.release();
-    c->win_start.release(); c->sj_cursor.release();
-    c->local.release(); c->order.release(); c->redo.release(); c->desc.release(); c->win_hdr.release(); c->tile_first.release(); c->walked.release(); c->stamps.release(); c->tile_base.release(); c->ex_off.release(); c->info.release(); c->tile_acc.release(); c->tile_acc_ex.release(); c->tile_acc_at.release(); c->tile_acc_ex_at.release(); c->tile_chunk.release(); c->tile_rchunk.release(); c->totals.release();
-    c->ex_start.release(); c->ex_end.release(); c->ref_tx.release(); c->ex_flag.release();
-    c->tile_total.release(); c->tile_xbase.release(); c->tile_rec.release(); c->cig_off32.release(); c->s_pl.release(); c->tile_span.release(); c->tile_sbase.release(); c->ovf_cursor.release(); c->tw64.release(); c->wide_list.release(); c->chunk_list.release(); c->list_cnt.release(); c->tile_flags.release();
-    c->lb_tile.release(); c->lb_blk.release(); c->lb_sup.release(); c->fb_list.release(); c->tile_stat.release(); c->sup_stat.release(); c->slot_rec.release(); c->sum_nn.release();
-    c->slab_row.release(); c->dense_start.release(); c->dense_end.release(); c->s_pre.release(); c->s_loc.release(); c->tw.release();
-    c->acc_rec.release(); c->acc_ex_off.release(); c->acc_start.release(); c->acc_end.release(); c->acc_flag.release();
-    drop_graph(c);
+    (void)hipSetDevice(c->device);                      // (the device buffers go with `delete c`)
     for (int k = 0; k < 2; ++k) { if (c->side[k]) (void)hipStreamDestroy(c->side[k]); if (c->ev_join[k]) (void)hipEventDestroy(c->ev_join[k]); }
     if (c->ev_fork) (void)hipEventDestroy(c->ev_fork);
     if (c->stream) (void)hipStreamDestroy(c->stream);
@@ -317,7 +328,7 @@ int l2r_set_outputs(l2r_ctx *c, unsigned want)
     // The per-read result arrays are always produced on the device (the junction check and the redo list read them);
     // what the flag saves is the compaction of the accepted list (kernel work, 16 + 9n bytes per accepted read).
     c->want = want;
-    c->ran = false; drop_graph(c);
+    c->ran = false; forget_list_state(c);
     return 0;
 }
 
@@ -325,7 +336,7 @@ int l2r_set_params(l2r_ctx *c, const l2r_params *prm)
 {
     if (!c || !prm) return fail(-1, "[l2r_set_params] null argument");
     c->prm = *prm;
-    c->ran = false; drop_graph(c);
+    c->ran = false; forget_list_state(c);
     return 0;
 }
 
@@ -686,7 +697,7 @@ int l2r_set_annotation(l2r_ctx *c, const l2r_annotation *a)
     c->seq = l2r_ctx::Stream();
     c->n_compact = t.n_compact; c->n_wide = t.n_wide; c->n_tid_dir = t.n_tid_dir; c->n_tid_key = t.n_tid_key;
     c->n_tx = a->n_tx; c->n_anno_exon = a->n_exon;
-    c->have_win = false; c->ran = false; drop_graph(c);
+    c->have_win = false; c->ran = false; forget_list_state(c);
     return 0;
 }
 
@@ -694,7 +705,7 @@ int l2r_set_junctions(l2r_ctx *c, const l2r_junctions *s)
 {
     if (!c) return fail(-1, "[l2r_set_junctions] null context");
     HIP_TRY(hipSetDevice(c->device));
-    c->ran = false; drop_graph(c);
+    c->ran = false; forget_list_state(c);
     if (!s || s->n == 0) { c->n_sj = 0; c->h_sj_key_raw.clear(); c->h_sj_key_pm.clear(); c->seq = l2r_ctx::Stream(); return 0; }
     if (s->n < 0 || s->n > 0x7ffffff0LL) return fail(-1, "[l2r_set_junctions] size out of range");
     const int64_t n = s->n;
@@ -789,10 +800,11 @@ int l2r_upload_reads(l2r_ctx *c, const l2r_reads *r)
     if (!sorted || c->n_sj > 0) { c->h_tid.assign(r->tid, r->tid + N); c->h_pos.assign(r->pos, r->pos + N); }
     else { c->h_tid.clear(); c->h_pos.clear(); }
 
+    c->wide_cigar = N > 0 && (double)r->n_cigar / (double)N > 32.0;
     // tile size: keep the expected exons of a tile inside the LDS staging area.
     // Estimate exons/read from a sample of the CIGARs (ops that can start an exon).
-    int rpt = TILE_THREADS;
     c->many_exon_reads = false;
+    double est = 1.0;
     if (N) {
         const int64_t sample = N < 4096 ? N : 4096;
         const int64_t step = N / sample;
@@ -810,51 +822,57 @@ int l2r_upload_reads(l2r_ctx *c, const l2r_reads *r)
         // (k_walk_slab_long hands a read beyond SLAB_ROWS exons to the generic kernel, the classic kernels keep it on the mask path: an
         //  input where such reads are more than a rarity stays with them)
         c->many_exon_reads = many * 200 > sample;
-        const double est = cuts / (double)sample + 1.0;
-        // (long CIGARs on the slab pipeline: the probe kernels stage SLAB_POS_CAP positions per tile)
-        const bool slab_long = c->want_pipeline > 0 && sorted && (double)r->n_cigar / (double)N > 32.0 && !getenv("L2R_NO_SLAB_LONG") && !c->many_exon_reads;
-        while (rpt > 32 && est * rpt * 1.25 > (double)(slab_long ? SLAB_POS_CAP : LDS_EXON_CAP)) rpt >>= 1;
-        // ... and keep the genomic span of a tile inside the staged bucket directory (DIR_CAP buckets of 512 bp):
-        // sparse input (few reads per locus) makes 256 consecutive reads span many genes, and a tile that does not
-        // fit goes to the generic kernel read by read (~30x the cost).  Sample windows of the sorted input, take for
-        // every candidate size the share of windows that would not fit, and pick the cheapest size.
-        // (The slab pipeline's tiles are cut by span one by one, below: a sparse stretch makes ITS tiles small, not every tile of the
-        //  upload -- an annotation with a few isoform-rich loci and long sparse stretches got 128-read tiles throughout, twice the tiles.)
-        const bool span_cut_tiles = c->want_pipeline > 0 && sorted && ((double)r->n_cigar / (double)N <= 32.0 || slab_long);
-        if (sorted && N >= 2 * TILE_THREADS && !span_cut_tiles) {
-            const int64_t n_win = std::min<int64_t>(N / TILE_THREADS, 384);
-            const int64_t wstep = (N / TILE_THREADS) / n_win;
-            const int64_t limit = (int64_t)(DIR_CAP - 8) << SITE_SHIFT;
-            int64_t bad[4] = {0, 0, 0, 0};                 // sizes 256, 128, 64, 32
-            for (int64_t w = 0; w < n_win; ++w) {
-                const int64_t i0 = w * wstep * TILE_THREADS;
-                int64_t hi = 0;
-                int size_idx = 3, next_mark = 32;
-                for (int64_t q = 0; q < TILE_THREADS && i0 + q < N; ++q) {
-                    const int64_t i = i0 + q;
-                    if (r->tid[i] != r->tid[i0]) break;
-                    int64_t end = r->pos[i];
-                    for (int64_t k = r->cig_off[i]; k < r->cig_off[i + 1]; ++k) if ((0x18du >> (r->cig[k] & 15u)) & 1u) end += r->cig[k] >> 4;
-                    hi = std::max(hi, end - r->pos[i0]);
-                    if (q + 1 == next_mark) {              // the first 32 / 64 / 128 / 256 reads of the window
-                        if (hi > limit) { for (int z = 0; z <= size_idx; ++z) bad[z]++; break; }   // this size and every larger one
-                        --size_idx; next_mark <<= 1;
-                    }
+        est = cuts / (double)sample + 1.0;
+    }
+    // What this upload's layout allows, decided once: the slab pipeline takes coordinate-sorted records; with long CIGARs
+    // (k_walk_slab_long) only where reads beyond SLAB_ROWS exons are a rarity.  Its tiles are cut by span and get the slab layout.
+    const bool slab_wanted = c->want_pipe != Pipeline::classic && sorted;
+    const bool slab_tiles = slab_wanted && !c->wide_cigar;                               // short CIGARs (k_walk_slab)
+    const bool slab_long = slab_wanted && c->wide_cigar && !c->many_exon_reads;          // long CIGARs (k_walk_slab_long)
+    const bool slab_layout = slab_tiles || slab_long;                                    // -> slab_ok
+    // ... and the tile index (k_tile_index) that the one-kernel tile path needs: not for an upload that ONE run follows (l2r_classify)
+    const bool make_index = c->want_pipe == Pipeline::tile && !c->wide_cigar && !(c->one_shot_upload && !c->env_tile_anyway && !c->pipeline_forced);
+    int rpt = TILE_THREADS;
+    // (long CIGARs on the slab pipeline: the probe kernels stage SLAB_POS_CAP positions per tile)
+    if (N) while (rpt > 32 && est * rpt * 1.25 > (double)(slab_long ? SLAB_POS_CAP : LDS_EXON_CAP)) rpt >>= 1;
+    // ... and keep the genomic span of a tile inside the staged bucket directory (DIR_CAP buckets of 512 bp):
+    // sparse input (few reads per locus) makes 256 consecutive reads span many genes, and a tile that does not
+    // fit goes to the generic kernel read by read (~30x the cost).  Sample windows of the sorted input, take for
+    // every candidate size the share of windows that would not fit, and pick the cheapest size.
+    // (The slab pipeline's tiles are cut by span one by one, below: a sparse stretch makes ITS tiles small, not every tile of the
+    //  upload -- an annotation with a few isoform-rich loci and long sparse stretches got 128-read tiles throughout, twice the tiles.)
+    if (sorted && N >= 2 * TILE_THREADS && !slab_layout) {
+        const int64_t n_win = std::min<int64_t>(N / TILE_THREADS, 384);
+        const int64_t wstep = (N / TILE_THREADS) / n_win;
+        const int64_t limit = (int64_t)(DIR_CAP - 8) << SITE_SHIFT;
+        int64_t bad[4] = {0, 0, 0, 0};                 // sizes 256, 128, 64, 32
+        for (int64_t w = 0; w < n_win; ++w) {
+            const int64_t i0 = w * wstep * TILE_THREADS;
+            int64_t hi = 0;
+            int size_idx = 3, next_mark = 32;
+            for (int64_t q = 0; q < TILE_THREADS && i0 + q < N; ++q) {
+                const int64_t i = i0 + q;
+                if (r->tid[i] != r->tid[i0]) break;
+                int64_t end = r->pos[i];
+                for (int64_t k = r->cig_off[i]; k < r->cig_off[i + 1]; ++k) if ((0x18du >> (r->cig[k] & 15u)) & 1u) end += r->cig[k] >> 4;
+                hi = std::max(hi, end - r->pos[i0]);
+                if (q + 1 == next_mark) {              // the first 32 / 64 / 128 / 256 reads of the window
+                    if (hi > limit) { for (int z = 0; z <= size_idx; ++z) bad[z]++; break; }   // this size and every larger one
+                    --size_idx; next_mark <<= 1;
                 }
             }
-            double best = 1e300; int best_rpt = rpt;
-            for (int z = 0; z < 4; ++z) {
-                const int cand = TILE_THREADS >> z;
-                if (cand > rpt) continue;
-                const double f = (double)bad[z] / (double)n_win;
-                const double cost = (1.0 - f) * (z == 0 ? 1.0 : z == 1 ? 1.6 : z == 2 ? 2.6 : 4.5) + 30.0 * f;
-                if (cost < best - 1e-9) { best = cost; best_rpt = cand; }
-            }
-            rpt = best_rpt;
         }
+        double best = 1e300; int best_rpt = rpt;
+        for (int z = 0; z < 4; ++z) {
+            const int cand = TILE_THREADS >> z;
+            if (cand > rpt) continue;
+            const double f = (double)bad[z] / (double)n_win;
+            const double cost = (1.0 - f) * (z == 0 ? 1.0 : z == 1 ? 1.6 : z == 2 ? 2.6 : 4.5) + 30.0 * f;
+            if (cost < best - 1e-9) { best = cost; best_rpt = cand; }
+        }
+        rpt = best_rpt;
     }
     c->reads_per_tile = rpt;
-    c->wide_cigar = N > 0 && (double)r->n_cigar / (double)N > 32.0;
     // Tiles: runs of up to rpt consecutive reads; for sorted input a tile also ends where the chromosome changes, so
     // that every read of a tile can use the tile's dictionary slices (unsorted input: plain runs, the reads that are
     // not on the chromosome of their tile's first read take the generic kernel).
@@ -862,8 +880,6 @@ int l2r_upload_reads(l2r_ctx *c, const l2r_reads *r)
     tile_first.reserve((size_t)(N / rpt + 64));
     // (slab pipeline: a tile's exons are staged by position in LDS on their way out, l2r_slab.hip.h SLAB_POS_CAP: a tile also ends
     //  where the exon bounds of its reads -- from the CIGAR lengths -- would exceed that, so no read of it is left outside)
-    const bool slab_long_tiles = c->want_pipeline > 0 && sorted && c->wide_cigar && !getenv("L2R_NO_SLAB_LONG") && !c->many_exon_reads;      // (k_walk_slab_long: tiles of rpt reads, cut by span like the slab's)
-    const bool slab_tiles = c->want_pipeline > 0 && sorted && !c->wide_cigar;
     uint64_t pos_sum = 0;
     for (int64_t i = 0, start = 0; i <= N; ++i) {
         if (i == N) { if (i > start) tile_first.push_back((uint32_t)start); break; }
@@ -872,7 +888,7 @@ int l2r_upload_reads(l2r_ctx *c, const l2r_reads *r)
         //  first base, and any tile's dictionary slices cover 196 kb -- sparse stretches give small tiles instead of tiles for the
         //  generic kernel; the classic pipeline, whose tiles own 24 KB of hand-over buffer each, keeps at least 8 reads per tile)
         if (i - start == rpt || (sorted && r->tid[i] != r->tid[start]) || (i > start && pos_sum + need > (uint64_t)TILE_POS_CAP) ||
-            (sorted && i > start && (int64_t)r->pos[i] - (int64_t)r->pos[start] >= (int64_t)SLAB_TILE_SPAN && (slab_tiles || slab_long_tiles || i - start >= 8))) { tile_first.push_back((uint32_t)start); start = i; pos_sum = 0; }
+            (sorted && i > start && (int64_t)r->pos[i] - (int64_t)r->pos[start] >= (int64_t)SLAB_TILE_SPAN && (slab_layout || i - start >= 8))) { tile_first.push_back((uint32_t)start); start = i; pos_sum = 0; }
         pos_sum += need;
     }
     c->n_tiles = (int64_t)tile_first.size();
@@ -914,8 +930,8 @@ int l2r_upload_reads(l2r_ctx *c, const l2r_reads *r)
         c->acc_rec.ensure((size_t)N) || c->acc_ex_off.ensure((size_t)N) ||
         c->acc_start.ensure(exb) || c->acc_end.ensure(exb) || c->acc_flag.ensure(exb) || (c->wide_cigar && c->walked.ensure((size_t)(c->n_tiles + 1) * LDS_EXON_CAP))) return -2;
     c->ex_cap = (int64_t)exb;
-    c->slab_ok = false; c->slab = false;
-    if (c->want_pipeline > 0 && sorted && (!c->wide_cigar || (!getenv("L2R_NO_SLAB_LONG") && !c->many_exon_reads))) {
+    c->slab_ok = false; c->pipe = Pipeline::classic;
+    if (slab_layout) {
         // the slab layout (l2r_slab.hip.h): per tile as many rows of 256 elements as its longest read can have exons (bound from
         // the CIGAR lengths); reads beyond SLAB_ROWS rows are outliers and get a run of the dense area
         const size_t T = (size_t)c->n_tiles;
@@ -972,7 +988,7 @@ int l2r_upload_reads(l2r_ctx *c, const l2r_reads *r)
             // ... and an index of its CIGAR operations from which a run knows the tile's exon count unless a threshold is borderline in it
             c->h_tile_stat.assign(T, TileStat{0, INT32_MAX, 0, INT32_MAX});
             c->index_ms = 0.0f; c->have_index = false;
-            if (T && !c->wide_cigar && c->want_pipeline >= 2 && !(c->one_shot_upload && !c->env_tile_anyway && !c->pipeline_forced)) {
+            if (T && make_index) {
                 c->have_index = true;
                 struct Ev { hipEvent_t a = nullptr, b = nullptr; ~Ev() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); } } ev;
                 HIP_TRY(hipEventCreate(&ev.a)); HIP_TRY(hipEventCreate(&ev.b));
@@ -1030,13 +1046,13 @@ int l2r_upload_reads(l2r_ctx *c, const l2r_reads *r)
         }
     }
     HIP_TRY(hipStreamSynchronize(c->stream));
-    if (getenv("L2R_STAMPS") && !c->stamps.p) {
+    if (c->env_stamps && !c->stamps.p) {
         if (c->stamps.ensure(1024 * 8 + 16)) return -2;
         HIP_TRY(hipMemsetAsync(c->stamps.p, 0, (1024 * 8 + 16) * 8, c->stream));
         HIP_TRY(hipStreamSynchronize(c->stream));
     }
     c->n_reads = N; c->n_cigar = r->n_cigar; c->first_read = r->first_read_index;
-    c->ran = false; c->totals_valid = false; drop_graph(c);
+    c->ran = false; c->totals_valid = false; forget_list_state(c);
     if (sorted) {
         // the annotation cursor after a sorted prefix is the prefix function of its last record
         if (N) {
@@ -1120,27 +1136,42 @@ static int prepare_unsorted_sj_cursor(l2r_ctx *c)
 
 enum { ST_PASS_A = 0, ST_SCAN1, ST_FAST, ST_GENERIC, ST_SJ, ST_SCAN2, ST_GATHER, ST_N };
 
-#define launch_fast_level(L, fa, grid, s) if (c->wide_cigar) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_classify_fast<L, true>), dim3(grid), dim3(TILE_THREADS), 0, s, fa, c->n_tiles, (const TileDesc *)c->desc.p, (const uint32_t *)c->tile_base.p, (const int64_t *)c->cig_off.p, (const uint8_t *)c->order.p, (const uint32_t *)c->tile_first.p); \
-    else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_classify_fast<L, false>), dim3(grid), dim3(TILE_THREADS), 0, s, fa, c->n_tiles, (const TileDesc *)c->desc.p, (const uint32_t *)c->tile_base.p, (const int64_t *)c->cig_off.p, (const uint8_t *)c->order.p, (const uint32_t *)c->tile_first.p)
-
-static int launch_all(l2r_ctx *c, hipEvent_t *ev /* ST_N + 1 events or null */)
+// Which pipeline the next launch takes: what the upload allows (slab_ok, have_index), the parameters, and what earlier runs of the
+// same upload and parameters have shown (inexact tiles, lists_heavy, a starved look-back)
+static Pipeline choose_pipeline(l2r_ctx *c, const DevParams &p)
 {
-    const DevParams p = dev_params(c);
-    const int64_t N = c->n_reads;
-    hipStream_t s = c->stream;
-    const unsigned gt = (unsigned)(c->n_tiles ? c->n_tiles : 1), g256 = (unsigned)(c->n_tiles256 ? c->n_tiles256 : 1);
-    const int32_t *j0 = c->sorted ? (const int32_t *)c->j0.p : (const int32_t *)c->win_start.p;
-    // L2R_CHECK=1 (diagnostics): wait for the device at every stage boundary, so that a kernel fault is reported with the stage it
-    // happened in instead of at the next synchronisation of the caller
-    static const char *const stage_name[ST_N + 1] = {"(start)", "pass A / order", "scan / walk", "classification", "generic", "junction check", "accepted scan", "accepted gather"};
-#define MARK(i) do { if (ev) HIP_TRY(hipEventRecord(ev[i], s)); \
-        if (c->check_stages) { const hipError_t e_ = hipStreamSynchronize(s); \
-            if (e_ != hipSuccess) return fail(-2, "[launch_all] device error behind stage \"%s\": %s", stage_name[(i) <= ST_N ? (i) : 0], hipGetErrorString(e_)); } } while (0)
-    MARK(ST_PASS_A);
-    const CursorDir cd{c->anno_key.p, c->key_dir.p, c->kb_base.p, c->n_tid_key, (int32_t)c->n_tx};
-    const SiteTabs tabs{{c->sk_st.p, c->sd_st.p, c->sr_st.p}, {c->sk_en.p, c->sd_en.p, nullptr}, c->tid_base.p, c->n_tid_dir};
+    // the slab pipeline wants the straight-line walk: thresholds that fit a CIGAR word (else: the classic kernels)
+    if (!(c->slab_ok && p.min_intron >= 0 && p.min_intron < (1 << 28) && p.max_delet >= -1 && p.max_delet < (1 << 28) - 1 &&
+          (!c->wide_cigar || p.min_exon >= 1)))           // (k_walk_slab_long has no -e < 1 form: the classic kernels take that)
+        return Pipeline::classic;
+    // the one-kernel tile path: short CIGARs whose exon counts the CIGAR lengths bound (-e >= 1)
+    if (c->want_pipe != Pipeline::tile || c->wide_cigar || p.min_exon < 1 || !(c->have_index || c->n_tiles == 0) || c->tile_starved)
+        return Pipeline::slab;
+    // A tile whose exon count the first kernel cannot derive from the upload's index (a threshold is borderline in it) publishes it
+    // from k_tile, and every later tile's write-out waits for it: fine for a few, a convoy for many (measured: 3 x the kernel when
+    // every tile does) -- such a run takes the two-kernel path.
+    if (c->inexact_tiles < 0) {     // (depends on the upload and the parameters alone: counted once, forgotten with them -- forget_list_state)
+        int64_t inexact = 0;
+        for (const TileStat &st : c->h_tile_stat) inexact += tile_exact(st, p.min_exon, p.min_intron, p.max_delet) ? 0 : 1;
+        c->inexact_tiles = inexact;
+    }
+    if (c->inexact_tiles * 50 > c->n_tiles + 800 && !c->env_tile_anyway) return Pipeline::slab;
+    // (measured: cfg3_iso40 -- every tile wide or chunked -- 1.34 ms on this path against 1.26 on the slab pipeline)
+    if (c->lists_known && c->lists_heavy && !c->env_tile_anyway) return Pipeline::slab;
+    return Pipeline::tile;
+}
+
+// The stage boundaries of a launch: per-stage events (l2r_run_timed); L2R_CHECK=1 (diagnostics): wait for the device at every one, so
+// that a kernel fault is reported with the stage it happened in instead of at the next synchronisation of the caller
+static const char *const stage_name[ST_N + 1] = {"(start)", "pass A / order", "scan / walk", "classification", "generic", "junction check", "accepted scan", "accepted gather"};
+#define MARK(i) do { if (ev) HIP_TRY(hipEventRecord(ev[i], c->stream)); \
+        if (c->check_stages) { const hipError_t e_ = hipStreamSynchronize(c->stream); \
+            if (e_ != hipSuccess) return fail(-2, "[launch_all] device error behind stage \"%s\": %s", stage_name[i], hipGetErrorString(e_)); } } while (0)
+
+static FastArgs fast_args(const l2r_ctx *c, const DevParams &p, const SiteTabs &tabs, const int32_t *j0)
+{
     FastArgs fa;
-    fa.n_reads = N; fa.r_tid = c->r_tid.p; fa.r_pos = c->r_pos.p; fa.r_rev = c->r_rev.p; fa.cig_off = c->cig_off.p; fa.cig = c->cig.p;
+    fa.n_reads = c->n_reads; fa.r_tid = c->r_tid.p; fa.r_pos = c->r_pos.p; fa.r_rev = c->r_rev.p; fa.cig_off = c->cig_off.p; fa.cig = c->cig.p;
     fa.walked = c->walked.p; fa.local = c->local.p; fa.order = c->order.p; fa.tile_base = c->tile_base.p; fa.j0 = j0; fa.desc = c->desc.p; fa.win_hdr = c->win_hdr.p;
     fa.hdr = c->hdr.p; fa.st = tabs.st; fa.en = tabs.en;
     fa.ex_off = c->ex_off.p; fa.ex_start = c->ex_start.p; fa.ex_end = c->ex_end.p; fa.ex_flag = c->ex_flag.p; fa.info = c->info.p; fa.ref_tx = c->ref_tx.p;
@@ -1148,267 +1179,229 @@ static int launch_all(l2r_ctx *c, hipEvent_t *ev /* ST_N + 1 events or null */)
     fa.tile_chunk = c->tile_chunk.p; fa.tile_rchunk = c->tile_rchunk.p; fa.chunk_cursor = (unsigned long long *)(c->totals.p + 4);
     fa.acc_start = c->acc_start.p; fa.acc_end = c->acc_end.p; fa.acc_flag = c->acc_flag.p; fa.acc_rec = (AccRec *)c->acc_rec.p; fa.acc_ex_off = c->acc_ex_off.p; fa.first_read = c->first_read;
     fa.stamps = c->stamps.p; fa.p = p;
-    // persistent grid: a few workgroups per CU walk over the tiles (l2r_kernels.hip.h)
-    unsigned gp = (unsigned)std::min<int64_t>(c->n_tiles ? c->n_tiles : 1, (int64_t)c->n_cu * c->wg_per_cu);
-    if (c->fast_grid > 0) gp = (unsigned)std::min<int64_t>(gp, c->fast_grid);           // L2R_FAST_GRID: tests force many tiles per workgroup
-    // the slab pipeline wants the straight-line walk: thresholds that fit a CIGAR word (else: the classic kernels)
-    c->slab = c->slab_ok && p.min_intron >= 0 && p.min_intron < (1 << 28) && p.max_delet >= -1 && p.max_delet < (1 << 28) - 1 &&
-              (!c->wide_cigar || p.min_exon >= 1);           // (k_walk_slab_long has no -e < 1 form: the classic kernels take that)
-    // the one-kernel tile path: short CIGARs whose exon counts the CIGAR lengths bound (-e >= 1)
-    c->tile = c->slab && c->want_pipeline >= 2 && !c->wide_cigar && p.min_exon >= 1 && (c->have_index || c->n_tiles == 0) && !c->tile_starved;
-    if (c->tile) {
-        // A tile whose exon count the first kernel cannot derive from the upload's index (a threshold is borderline in it) publishes it
-        // from k_tile, and every later tile's write-out waits for it: fine for a few, a convoy for many (measured: 3 x the kernel when
-        // every tile does) -- such a run takes the two-kernel path.
-        if (c->inexact_tiles < 0) {     // (depends on the upload and the parameters alone: counted once, forgotten with them -- drop_graph)
-            int64_t inexact = 0;
-            for (const TileStat &st : c->h_tile_stat) inexact += tile_exact(st, p.min_exon, p.min_intron, p.max_delet) ? 0 : 1;
-            c->inexact_tiles = inexact;
-        }
-        if (c->inexact_tiles * 50 > c->n_tiles + 800 && !c->env_tile_anyway) c->tile = false;
-        // (measured: cfg3_iso40 -- every tile wide or chunked -- 1.34 ms on this path against 1.26 on the slab pipeline)
-        if (c->lists_known && c->lists_heavy && !c->env_tile_anyway) c->tile = false;
-    }
-    if (c->slab) {
-        // ---- two light kernels at full occupancy: the walk (exons into the tiles' slabs, read-order places, descriptors), a scan of
-        //      the tiles' exon counts, then the probes, which write the read-order results (l2r_slab.hip.h).  Every launch does all
-        //      of it: nothing is kept from an earlier run of the same upload.
-        bool skip_lists = false;
-        SlabArgs sa;
-        sa.g.f = fa; sa.g.cd = cd; sa.g.tid_base = c->tid_base.p; sa.g.n_tid_dir = c->n_tid_dir; sa.g.tile_total = c->tile_total.p;
-        sa.tile_sbase = c->tile_sbase.p; sa.slab_row = c->slab_row.p;
-        sa.dense_start = c->dense_start.p; sa.dense_end = c->dense_end.p; sa.ovf_cursor = c->ovf_cursor.p;
-        sa.pl = c->s_pl.p; sa.pre_x = c->s_pre.p; sa.loc_x = c->s_loc.p; sa.cig_off32 = c->cig_off32.p; sa.tw = c->tw.p; sa.span = (TileSpan *)c->tile_span.p;
-        sa.n_tiles = (uint32_t)c->n_tiles;
-        const unsigned gx = 8u * (unsigned)std::max<int64_t>((c->n_tiles + 7) / 8, 1);      // (l2r_slab.hip.h xcd_tile; an empty upload still launches)
-        sa.tw64 = (c->ablate & 4) ? nullptr : c->tw64.p;
-        sa.chunk_on = (c->ablate & 32) ? 0u : 1u;          // (L2R_ABLATE bit 2: no 64-member windows, bit 5: no chunked windows)
-        sa.wide_list = c->wide_list.p; sa.chunk_list = c->chunk_list.p; sa.list_cnt = c->list_cnt.p; sa.list_cnt_next = nullptr; sa.tile_flags = c->tile_flags.p;
-        {   const size_t sup_words = (size_t)(c->n_tiles >> LB_SUP_SHIFT) + 64;
-            sa.lb_sup = c->lb_sup.p ? c->lb_sup.p + (c->lb_flip ? sup_words : 0) : nullptr;
-            sa.lb_sup_next = c->lb_sup.p ? c->lb_sup.p + (c->lb_flip ? 0 : sup_words) : nullptr;
-            sa.n_sup = (uint32_t)(c->n_tiles >> LB_SUP_SHIFT) + 1u; }
-        sa.lb_tile = c->lb_tile.p; sa.lb_blk = c->lb_blk.p; sa.lb_err = c->totals.p + 6; sa.fb_list = c->fb_list.p; sa.exon_total = c->totals.p + 0; sa.tile_stat = c->tile_stat.p; sa.sup_stat = c->sup_stat.p;
-        sa.sj = SjDir{CursorDir{c->sj_key.p, c->sj_cdir.p, c->sj_cbase.p, c->sj_ntid, (int32_t)c->n_sj}, c->sj_ddir.p, c->sj_dbase.p, c->sj_ntid, c->sj_row.p};
-        sa.has_wide_keys = c->n_wide > 0 ? 1u : 0u;
-        sa.wide_direct_on = (c->tile && c->wide_direct && c->tw64.p && !(c->ablate & 4)) ? 1u : 0u;
-        sa.chunk_direct_on = (c->tile && c->chunk_direct && sa.chunk_on) ? 1u : 0u;
-        // (with the accepted list wanted and no junction table to decide later, the tiles leave their accepted chunks themselves)
-        const bool probe_acc = (c->want & L2R_WANT_ACCEPTED) && (c->n_sj == 0 || c->tile);      // (k_tile decides acceptance itself, junction table or not)
-#define launch_probe_k(L, A, D, LIST, G) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_probe_slab<L, A, D, LIST>), dim3(G), dim3(TILE_THREADS), 0, s, sa, (const TileSpan *)c->tile_span.p, \
-            (const TileWin *)c->tw.p, (const uint32_t *)c->tile_xbase.p, (const uint32_t *)c->fb_list.p)
-        // (the tiles k_tile left in slab form leave no accepted chunks themselves: they stay k_gather_accepted's -- half the instantiations)
-#define launch_probe_level(L, LIST, G) do { if (p.ss_dis > 0) { if (probe_acc && !LIST) launch_probe_k(L, !LIST, true, LIST, G); else launch_probe_k(L, false, true, LIST, G); } \
-                                   else { if (probe_acc && !LIST) launch_probe_k(L, !LIST, false, LIST, G); else launch_probe_k(L, false, false, LIST, G); } } while (0)
-#define launch_probe(LIST, G) do { switch (p.full_level) { \
-        case 1: launch_probe_level(1, LIST, G); break; case 2: launch_probe_level(2, LIST, G); break; case 3: launch_probe_level(3, LIST, G); break; \
-        case 4: launch_probe_level(4, LIST, G); break; case 5: launch_probe_level(5, LIST, G); break; default: launch_probe_level(0, LIST, G); break; } } while (0)
-        if (c->tile) {
-            if (!c->prev_run_tile) { HIP_TRY(hipMemsetAsync(c->list_cnt.p, 0, 128, s)); c->lc_flip = 0; }
-            sa.list_cnt = c->list_cnt.p + 16 * (c->lc_flip & 1u); sa.list_cnt_next = c->list_cnt.p + 16 * ((c->lc_flip & 1u) ^ 1u);
-            // ---- ONE kernel per tile (l2r_tile.hip.h): the descriptors first (spans from the upload), then walk + probes + write-out in
-            //      one workgroup; k_probe_slab behind it for the few tiles that kept the slab form (none on most inputs)
-            const DescribeScan job{c->tile_total.p, c->tile_xbase.p, c->totals.p + 0, c->n_tiles};
-            const unsigned gd = (unsigned)std::max<int64_t>((c->n_tiles + DESCRIBE_TILES - 1) / DESCRIBE_TILES, 1);
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_describe_scan<true>), dim3(gd), dim3(TILE_THREADS), 0, s, sa, job, 0u, (const TileRec *)c->tile_rec.p);
-            MARK(ST_SCAN1);
-            // (the three list-driven kernels behind k_tile: not launched once a completed run of the same inputs and parameters has shown
-            //  their lists empty -- what ends up on them does not depend on anything else)
-            skip_lists = c->lists_known && c->lists_empty && !c->env_launch_all;
-            const unsigned gl = (unsigned)std::min<int64_t>(c->n_tiles ? c->n_tiles : 1, (int64_t)c->n_cu * 2);
-            // (the WIDE instance beside the plain one, on a stream of its own: see l2r_ctx::side; with per-stage events or L2R_CHECK one behind the other)
-            const bool wide_launch = !skip_lists && sa.wide_direct_on;
-            const bool beside = c->side_on && !ev && !c->check_stages;
-            hipStream_t sw = s;
-            if (wide_launch && beside) { sw = c->side[0]; HIP_TRY(hipEventRecord(c->ev_fork, s)); HIP_TRY(hipStreamWaitEvent(sw, c->ev_fork, 0)); }
-            if (wide_launch) {
-                // the exact 64-bit-mask tiles straight from their CIGARs: k_tile's WIDE instance, a workgroup per entry of wide_list (the
-                // list's length is known to the host once a run has completed: until then a grid for every tile, most of which leave at once)
-                const unsigned gwd = c->lists_known ? std::max(c->n_wide_tiles, 1u) : (unsigned)std::max<int64_t>(c->n_tiles, 1);
-#define launch_tw_k(L, D) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_tile<L, false, D, true>), dim3(gwd), dim3(TILE_THREADS), 0, sw, sa, (const TileRec *)c->tile_rec.p, (const TileWin *)c->tw.p, (const TileStat *)c->tile_stat.p, (const SlotRec *)c->slot_rec.p, c->tile_xbase.p)
-#define launch_tw_level(L) do { if (p.ss_dis > 0) launch_tw_k(L, true); else launch_tw_k(L, false); } while (0)
-                switch (p.full_level) {
-                case 1: launch_tw_level(1); break;
-                case 2: launch_tw_level(2); break;
-                case 3: launch_tw_level(3); break;
-                case 4: launch_tw_level(4); break;
-                case 5: launch_tw_level(5); break;
-                default: launch_tw_level(0); break;
-                }
-#undef launch_tw_level
-#undef launch_tw_k
-            }
-            if (wide_launch && beside) HIP_TRY(hipEventRecord(c->ev_join[0], sw));
-            // ... and the exact tiles of the chunked kernel: k_tile_chunk (l2r_tchunk.hip.h), a workgroup per entry of chunk_list
-            const bool chunk_launch = !skip_lists && sa.chunk_direct_on && !(c->lists_known && c->n_chunk_tiles == 0u);
-            hipStream_t sc = s;
-            if (chunk_launch && beside) { sc = c->side[1]; if (!wide_launch) HIP_TRY(hipEventRecord(c->ev_fork, s)); HIP_TRY(hipStreamWaitEvent(sc, c->ev_fork, 0)); }
-            auto launch_tchunk = [&](hipStream_t sc, unsigned gcd, uint32_t late) {
-#define launch_tc_level(L) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_tile_chunk<L>), dim3(gcd), dim3(TILE_THREADS), 0, sc, sa, (const TileRec *)c->tile_rec.p, (const TileWin *)c->tw.p, (const TileStat *)c->tile_stat.p, (const SlotRec *)c->slot_rec.p, c->tile_xbase.p, late)
-                switch (p.full_level) {
-                case 1: launch_tc_level(1); break;
-                case 2: launch_tc_level(2); break;
-                case 3: launch_tc_level(3); break;
-                case 4: launch_tc_level(4); break;
-                case 5: launch_tc_level(5); break;
-                default: launch_tc_level(0); break;
-                }
-#undef launch_tc_level
-            };
-            const unsigned gcd = c->lists_known ? std::max(c->n_chunk_tiles, 1u) : (unsigned)std::max<int64_t>(c->n_tiles, 1);
-            if (chunk_launch && beside) { launch_tchunk(sc, gcd, 0u); HIP_TRY(hipEventRecord(c->ev_join[1], sc)); }
-            const unsigned gf = fused_grid(c->n_tiles);
-#define launch_tile_k(L, A, D) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_tile<L, A, D>), dim3(gf), dim3(TILE_THREADS), 0, s, sa, (const TileRec *)c->tile_rec.p, (const TileWin *)c->tw.p, (const TileStat *)c->tile_stat.p, (const SlotRec *)c->slot_rec.p, c->tile_xbase.p)
-#define launch_tile_level(L) do { if (p.ss_dis > 0) { if (probe_acc) launch_tile_k(L, true, true); else launch_tile_k(L, false, true); } \
-                                  else { if (probe_acc) launch_tile_k(L, true, false); else launch_tile_k(L, false, false); } } while (0)
-            switch (p.full_level) {
-            case 1: launch_tile_level(1); break;
-            case 2: launch_tile_level(2); break;
-            case 3: launch_tile_level(3); break;
-            case 4: launch_tile_level(4); break;
-            case 5: launch_tile_level(5); break;
-            default: launch_tile_level(0); break;
-            }
-#undef launch_tile_level
-#undef launch_tile_k
-            MARK(ST_FAST);
-            if (chunk_launch && !beside) launch_tchunk(s, gcd, 0u);
-            if (wide_launch && beside) HIP_TRY(hipStreamWaitEvent(s, c->ev_join[0], 0));
-            if (chunk_launch && beside) HIP_TRY(hipStreamWaitEvent(s, c->ev_join[1], 0));
-            if (!skip_lists && !(c->lists_known && c->fb_empty && !c->env_launch_all)) launch_probe(true, gl);
-        } else {
-        if (c->wide_cigar)
-            hipLaunchKernelGGL(k_walk_slab_long, dim3(gx), dim3(TILE_THREADS), pass_a_dynamic_lds(c->reads_per_tile), s, sa, (const TileRec *)c->tile_rec.p);
-        else if (p.min_exon >= 1)
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_walk_slab<false>), dim3(gx), dim3(TILE_THREADS), 0, s, sa, (const TileRec *)c->tile_rec.p);
-        else
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_walk_slab<true>), dim3(gx), dim3(TILE_THREADS), 0, s, sa, (const TileRec *)c->tile_rec.p);
-        MARK(ST_SCAN1);
-        {   // the tiles' exon counts -> their first slots in the read-order result arrays (tile_xbase; the sum = the exon count): the
-            // first workgroups of the launch, a segment each; the tiles' descriptors and windows, sixteen lanes per tile, and the lists
-            // of the 64-bit-mask and the chunked kernel: the workgroups behind them (l2r_slab.hip.h)
-            const DescribeScan job{c->tile_total.p, c->tile_xbase.p, c->totals.p + 0, c->n_tiles};
-            unsigned n_scan = (unsigned)std::max<int64_t>((c->n_tiles + DESCRIBE_SEG - 1) / DESCRIBE_SEG, 1);
-            if (c->n_tiles > c->seg_max) {
-                // (very large shards: one workgroup scans, in a launch of its own)
-                HIP_TRY(hipMemcpyAsync(c->tile_xbase.p, c->tile_total.p, (size_t)c->n_tiles * 4, hipMemcpyDeviceToDevice, s));
-                ScanJobs jobs = {}; jobs.job[0] = ScanJob{c->tile_xbase.p, c->n_tiles, c->totals.p + 0}; jobs.job[1] = jobs.job[0];
-                hipLaunchKernelGGL(k_scan_u32, dim3(1), dim3(1024), 0, s, jobs);
-                n_scan = 0;
-            }
-            const unsigned gd = n_scan + (unsigned)std::max<int64_t>((c->n_tiles + DESCRIBE_TILES - 1) / DESCRIBE_TILES, 1);
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_describe_scan<false>), dim3(gd), dim3(TILE_THREADS), 0, s, sa, job, (uint32_t)n_scan, (const TileRec *)nullptr);
-        }
-        MARK(ST_FAST);
-        launch_probe(false, gx);
-        }
-#undef launch_probe
-#undef launch_probe_level
-#undef launch_probe_k
-        if (!skip_lists && !(c->tile && c->lists_known && c->wide_rest_empty && !c->env_launch_all))
-        {   // the tiles with 33 .. 63 window members (none on most inputs: the grid finds an empty list and leaves)
-            const WideArgs wa{c->tw64.p};
-            const unsigned gw = (unsigned)std::min<int64_t>(c->n_tiles ? c->n_tiles : 1, (int64_t)c->n_cu * 5);
-#define launch_wide_level(L) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_probe_slab_wide<L>), dim3(gw), dim3(TILE_THREADS), 0, s, sa, wa, (const uint32_t *)c->tile_first.p, \
-                (const int32_t *)c->r_pos.p, (const uint32_t *)c->tile_sbase.p, (const TileWin *)c->tw.p, (const uint32_t *)c->tile_xbase.p, (const TileStat *)(c->tile ? c->tile_stat.p : nullptr))
-            switch (p.full_level) {
-            case 1: launch_wide_level(1); break;
-            case 2: launch_wide_level(2); break;
-            case 3: launch_wide_level(3); break;
-            case 4: launch_wide_level(4); break;
-            case 5: launch_wide_level(5); break;
-            default: launch_wide_level(0); break;
-            }
-#undef launch_wide_level
-        }
-        if (c->tile && sa.chunk_direct_on && !skip_lists && !(c->lists_known && c->n_late_tiles == 0u && !c->env_launch_all)) {
-            // the tiles a one-window kernel handed on late (a key in several entries): k_tile_chunk once more, over that list
-            const unsigned gl2 = c->lists_known ? std::max(c->n_late_tiles, 1u) : (unsigned)std::max<int64_t>(c->n_tiles, 1);      // (every entry needs its workgroup: k_probe_slab_chunked skips what this launch takes)
-            auto launch_late = [&]() {
-#define launch_tcl_level(L) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_tile_chunk<L>), dim3(gl2), dim3(TILE_THREADS), 0, s, sa, (const TileRec *)c->tile_rec.p, (const TileWin *)c->tw.p, (const TileStat *)c->tile_stat.p, (const SlotRec *)c->slot_rec.p, c->tile_xbase.p, 1u)
-                switch (p.full_level) {
-                case 1: launch_tcl_level(1); break;
-                case 2: launch_tcl_level(2); break;
-                case 3: launch_tcl_level(3); break;
-                case 4: launch_tcl_level(4); break;
-                case 5: launch_tcl_level(5); break;
-                default: launch_tcl_level(0); break;
-                }
-#undef launch_tcl_level
-            };
-            launch_late();
-        }
-        if (sa.chunk_on && !skip_lists && !(c->tile && c->lists_known && c->chunk_rest_empty && !c->env_launch_all)) {   // the tiles without a window record, or with a dictionary key in several entries (none on most inputs)
-            const unsigned gc = (unsigned)std::min<int64_t>(c->n_tiles ? c->n_tiles : 1, (int64_t)c->n_cu * 4);
-#define launch_chunk_level(L) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_probe_slab_chunked<L>), dim3(gc), dim3(TILE_THREADS), 0, s, sa, (const uint32_t *)c->tile_first.p, \
-                (const int32_t *)c->r_pos.p, (const uint32_t *)c->tile_sbase.p, (const TileWin *)c->tw.p, (const uint32_t *)c->tile_xbase.p)
-            switch (p.full_level) {
-            case 1: launch_chunk_level(1); break;
-            case 2: launch_chunk_level(2); break;
-            case 3: launch_chunk_level(3); break;
-            case 4: launch_chunk_level(4); break;
-            case 5: launch_chunk_level(5); break;
-            default: launch_chunk_level(0); break;
-            }
-#undef launch_chunk_level
-        }
-        // (accepted list: k_describe_scan marks every tile CHUNK_DEFERRED, k_probe_slab<., true> takes that back for the tiles whose
-        //  chunk it has written itself; k_count_accepted / k_gather_accepted place the rest)
-    } else {
+    return fa;
+}
+
+// The slab and the tile pipeline's arguments (l2r_slab.hip.h).  Every launch does all of it: nothing is kept from an earlier run of the same upload.
+static SlabArgs slab_args(const l2r_ctx *c, const FastArgs &fa, const CursorDir &cd, bool tile)
+{
+    SlabArgs sa;
+    sa.g.f = fa; sa.g.cd = cd; sa.g.tid_base = c->tid_base.p; sa.g.n_tid_dir = c->n_tid_dir; sa.g.tile_total = c->tile_total.p;
+    sa.tile_sbase = c->tile_sbase.p; sa.slab_row = c->slab_row.p;
+    sa.dense_start = c->dense_start.p; sa.dense_end = c->dense_end.p; sa.ovf_cursor = c->ovf_cursor.p;
+    sa.pl = c->s_pl.p; sa.pre_x = c->s_pre.p; sa.loc_x = c->s_loc.p; sa.cig_off32 = c->cig_off32.p; sa.tw = c->tw.p; sa.span = (TileSpan *)c->tile_span.p;
+    sa.n_tiles = (uint32_t)c->n_tiles;
+    sa.tw64 = (c->ablate & 4) ? nullptr : c->tw64.p;
+    sa.chunk_on = (c->ablate & 32) ? 0u : 1u;          // (L2R_ABLATE bit 2: no 64-member windows, bit 5: no chunked windows)
+    sa.wide_list = c->wide_list.p; sa.chunk_list = c->chunk_list.p; sa.list_cnt = c->list_cnt.p; sa.list_cnt_next = nullptr; sa.tile_flags = c->tile_flags.p;
+    if (tile) { sa.list_cnt = c->list_cnt.p + 16 * (c->lc_flip & 1u); sa.list_cnt_next = c->list_cnt.p + 16 * ((c->lc_flip & 1u) ^ 1u); }
+    {   const size_t sup_words = (size_t)(c->n_tiles >> LB_SUP_SHIFT) + 64;
+        sa.lb_sup = c->lb_sup.p ? c->lb_sup.p + (c->lb_flip ? sup_words : 0) : nullptr;
+        sa.lb_sup_next = c->lb_sup.p ? c->lb_sup.p + (c->lb_flip ? 0 : sup_words) : nullptr;
+        sa.n_sup = (uint32_t)(c->n_tiles >> LB_SUP_SHIFT) + 1u; }
+    sa.lb_tile = c->lb_tile.p; sa.lb_blk = c->lb_blk.p; sa.lb_err = c->totals.p + 6; sa.fb_list = c->fb_list.p; sa.exon_total = c->totals.p + 0; sa.tile_stat = c->tile_stat.p; sa.sup_stat = c->sup_stat.p;
+    sa.sj = SjDir{CursorDir{c->sj_key.p, c->sj_cdir.p, c->sj_cbase.p, c->sj_ntid, (int32_t)c->n_sj}, c->sj_ddir.p, c->sj_dbase.p, c->sj_ntid, c->sj_row.p};
+    sa.has_wide_keys = c->n_wide > 0 ? 1u : 0u;
+    sa.wide_direct_on = (tile && c->wide_direct && c->tw64.p && !(c->ablate & 4)) ? 1u : 0u;
+    sa.chunk_direct_on = (tile && c->chunk_direct && sa.chunk_on) ? 1u : 0u;
+    return sa;
+}
+
+// k_probe_slab: every tile (slab pipeline), or the tiles k_tile left in slab form (`list`: fb_list, tile path).  `acc`: the tiles leave
+// their accepted chunks themselves (with the accepted list wanted and no junction table to decide later)
+static void launch_probe(const l2r_ctx *c, const DevParams &p, const SlabArgs &sa, bool list, bool acc, unsigned grid)
+{
+    with_level(p.full_level, [&](auto L) { with_flag(p.ss_dis > 0, [&](auto D) { with_flag(list, [&](auto LIST) { with_flag(acc && !list, [&](auto A) {
+        // (the tiles k_tile left in slab form leave no accepted chunks themselves: they stay k_gather_accepted's -- so the
+        //  instances with both are never made, half of those with a list)
+        if constexpr (!(A && LIST))
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_probe_slab<L, A, D, LIST>), dim3(grid), dim3(TILE_THREADS), 0, c->stream, sa, (const TileSpan *)c->tile_span.p,
+                               (const TileWin *)c->tw.p, (const uint32_t *)c->tile_xbase.p, (const uint32_t *)c->fb_list.p);
+    }); }); }); });
+}
+
+// k_tile_chunk (l2r_tchunk.hip.h): a workgroup per entry of chunk_list (late = 0), or of the tiles a one-window kernel handed on late (1)
+static void launch_tile_chunk(const l2r_ctx *c, const DevParams &p, const SlabArgs &sa, unsigned grid, uint32_t late, hipStream_t s)
+{
+    with_level(p.full_level, [&](auto L) {
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_tile_chunk<L>), dim3(grid), dim3(TILE_THREADS), 0, s, sa, (const TileRec *)c->tile_rec.p, (const TileWin *)c->tw.p,
+                           (const TileStat *)c->tile_stat.p, (const SlotRec *)c->slot_rec.p, c->tile_xbase.p, late);
+    });
+}
+
+// ---- classic: pass A (exons walked into the tiles' staging, the reads ordered), a scan of the tiles' exon counts, k_classify_fast
+static int launch_classic(l2r_ctx *c, hipEvent_t *ev, const DevParams &p, const FastArgs &fa, const CursorDir &cd, const SiteTabs &tabs)
+{
+    hipStream_t s = c->stream;
+    const unsigned gt = (unsigned)(c->n_tiles ? c->n_tiles : 1);
     // sorted input: the cursor value of every read is computed on the device; unsorted input: it was replayed on the host
-    if (c->wide_cigar)
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_pass_a<true>), dim3(gt), dim3(TILE_THREADS), pass_a_dynamic_lds(c->reads_per_tile), s, N, c->r_tid.p, c->r_pos.p, c->cig_off.p, c->cig.p, cd, tabs, p,
-                           (c->sorted ? (const int32_t *)nullptr : (const int32_t *)c->win_start.p), c->j0.p, c->local.p, c->order.p, c->tile_base.p, c->desc.p,
-                           c->totals.p + 3, (const TxHdr *)c->hdr.p, c->win_hdr.p, (const uint32_t *)c->tile_first.p, c->walked.p);
-    else
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_pass_a<false>), dim3(gt), dim3(TILE_THREADS), 0, s, N, c->r_tid.p, c->r_pos.p, c->cig_off.p, c->cig.p, cd, tabs, p,
-                       (c->sorted ? (const int32_t *)nullptr : (const int32_t *)c->win_start.p), c->j0.p, c->local.p, c->order.p, c->tile_base.p, c->desc.p,
-                       c->totals.p + 3, (const TxHdr *)c->hdr.p, c->win_hdr.p, (const uint32_t *)c->tile_first.p, c->walked.p);
+    with_flag(c->wide_cigar, [&](auto W) {
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_pass_a<W>), dim3(gt), dim3(TILE_THREADS), W ? pass_a_dynamic_lds(c->reads_per_tile) : 0, s, c->n_reads, c->r_tid.p, c->r_pos.p,
+                           c->cig_off.p, c->cig.p, cd, tabs, p, (c->sorted ? (const int32_t *)nullptr : (const int32_t *)c->win_start.p), c->j0.p, c->local.p, c->order.p,
+                           c->tile_base.p, c->desc.p, c->totals.p + 3, (const TxHdr *)c->hdr.p, c->win_hdr.p, (const uint32_t *)c->tile_first.p, c->walked.p);
+    });
     MARK(ST_SCAN1);
     {
         ScanJobs jobs = {}; jobs.job[0] = ScanJob{c->tile_base.p, c->n_tiles, c->totals.p + 0}; jobs.job[1] = jobs.job[0];
         hipLaunchKernelGGL(k_scan_u32, dim3(1), dim3(1024), 0, s, jobs);
     }
     MARK(ST_FAST);
-    {
-        switch (p.full_level) {
-        case 1: launch_fast_level(1, fa, gp, s); break;
-        case 2: launch_fast_level(2, fa, gp, s); break;
-        case 3: launch_fast_level(3, fa, gp, s); break;
-        case 4: launch_fast_level(4, fa, gp, s); break;
-        case 5: launch_fast_level(5, fa, gp, s); break;
-        default: launch_fast_level(0, fa, gp, s); break;      // src/update_gtf.c:629-696: no evidence is gathered, full = lfull && rfull = 0
+    // persistent grid: a few workgroups per CU walk over the tiles (l2r_kernels.hip.h)
+    unsigned gp = (unsigned)std::min<int64_t>(c->n_tiles ? c->n_tiles : 1, (int64_t)c->n_cu * c->wg_per_cu);
+    if (c->fast_grid > 0) gp = (unsigned)std::min<int64_t>(gp, c->fast_grid);           // L2R_FAST_GRID: tests force many tiles per workgroup
+    with_level(p.full_level, [&](auto L) { with_flag(c->wide_cigar, [&](auto W) {
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_classify_fast<L, W>), dim3(gp), dim3(TILE_THREADS), 0, s, fa, c->n_tiles, (const TileDesc *)c->desc.p,
+                           (const uint32_t *)c->tile_base.p, (const int64_t *)c->cig_off.p, (const uint8_t *)c->order.p, (const uint32_t *)c->tile_first.p);
+    }); });
+    return 0;
+}
+
+// ---- slab: two light kernels at full occupancy -- the walk (exons into the tiles' slabs, read-order places, descriptors), a scan of
+//      the tiles' exon counts -- then the probes, which write the read-order results (l2r_slab.hip.h)
+static int launch_slab(l2r_ctx *c, hipEvent_t *ev, const DevParams &p, const SlabArgs &sa)
+{
+    hipStream_t s = c->stream;
+    const unsigned gx = 8u * (unsigned)std::max<int64_t>((c->n_tiles + 7) / 8, 1);      // (l2r_slab.hip.h xcd_tile; an empty upload still launches)
+    if (c->wide_cigar)
+        hipLaunchKernelGGL(k_walk_slab_long, dim3(gx), dim3(TILE_THREADS), pass_a_dynamic_lds(c->reads_per_tile), s, sa, (const TileRec *)c->tile_rec.p);
+    else
+        with_flag(p.min_exon < 1, [&](auto E) { hipLaunchKernelGGL(HIP_KERNEL_NAME(k_walk_slab<E>), dim3(gx), dim3(TILE_THREADS), 0, s, sa, (const TileRec *)c->tile_rec.p); });
+    MARK(ST_SCAN1);
+    {   // the tiles' exon counts -> their first slots in the read-order result arrays (tile_xbase; the sum = the exon count): the
+        // first workgroups of the launch, a segment each; the tiles' descriptors and windows, sixteen lanes per tile, and the lists
+        // of the 64-bit-mask and the chunked kernel: the workgroups behind them (l2r_slab.hip.h)
+        const DescribeScan job{c->tile_total.p, c->tile_xbase.p, c->totals.p + 0, c->n_tiles};
+        unsigned n_scan = (unsigned)std::max<int64_t>((c->n_tiles + DESCRIBE_SEG - 1) / DESCRIBE_SEG, 1);
+        if (c->n_tiles > c->seg_max) {
+            // (very large shards: one workgroup scans, in a launch of its own)
+            HIP_TRY(hipMemcpyAsync(c->tile_xbase.p, c->tile_total.p, (size_t)c->n_tiles * 4, hipMemcpyDeviceToDevice, s));
+            ScanJobs jobs = {}; jobs.job[0] = ScanJob{c->tile_xbase.p, c->n_tiles, c->totals.p + 0}; jobs.job[1] = jobs.job[0];
+            hipLaunchKernelGGL(k_scan_u32, dim3(1), dim3(1024), 0, s, jobs);
+            n_scan = 0;
         }
+        const unsigned gd = n_scan + (unsigned)std::max<int64_t>((c->n_tiles + DESCRIBE_TILES - 1) / DESCRIBE_TILES, 1);
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_describe_scan<false>), dim3(gd), dim3(TILE_THREADS), 0, s, sa, job, (uint32_t)n_scan, (const TileRec *)nullptr);
     }
+    MARK(ST_FAST);
+    launch_probe(c, p, sa, false, (c->want & L2R_WANT_ACCEPTED) && c->n_sj == 0, gx);
+    return 0;
+}
+
+// ---- tile: ONE kernel per tile (l2r_tile.hip.h) -- the descriptors first (spans from the upload), then walk + probes + write-out in one
+//      workgroup; the instances that take the isoform-rich tiles beside it, k_probe_slab behind it for the few tiles that kept the slab
+//      form (none on most inputs)
+static int launch_tile(l2r_ctx *c, hipEvent_t *ev, const DevParams &p, const SlabArgs &sa, bool skip_lists)
+{
+    hipStream_t s = c->stream;
+    const DescribeScan job{c->tile_total.p, c->tile_xbase.p, c->totals.p + 0, c->n_tiles};
+    const unsigned gd = (unsigned)std::max<int64_t>((c->n_tiles + DESCRIBE_TILES - 1) / DESCRIBE_TILES, 1);
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_describe_scan<true>), dim3(gd), dim3(TILE_THREADS), 0, s, sa, job, 0u, (const TileRec *)c->tile_rec.p);
+    MARK(ST_SCAN1);
+    // the exact 64-bit-mask tiles straight from their CIGARs: k_tile's WIDE instance, a workgroup per entry of wide_list; the exact
+    // tiles of the chunked kernel: k_tile_chunk, a workgroup per entry of chunk_list (the lists' lengths are known to the host once a run
+    // has completed: until then a grid for every tile, most of which leave at once).  Both beside the plain instance, on streams of
+    // their own (see l2r_ctx::side); with per-stage events or L2R_CHECK one behind the other.
+    const bool wide_launch = !skip_lists && sa.wide_direct_on;
+    const bool chunk_launch = !skip_lists && sa.chunk_direct_on && !(c->lists_known && c->n_chunk_tiles == 0u);
+    const bool beside = c->side_on && !ev && !c->check_stages;
+    if (beside && (wide_launch || chunk_launch)) HIP_TRY(hipEventRecord(c->ev_fork, s));
+    if (wide_launch) {
+        hipStream_t sw = beside ? c->side[0] : s;
+        if (beside) HIP_TRY(hipStreamWaitEvent(sw, c->ev_fork, 0));
+        const unsigned gwd = c->lists_known ? std::max(c->n_wide_tiles, 1u) : (unsigned)std::max<int64_t>(c->n_tiles, 1);
+        with_level(p.full_level, [&](auto L) { with_flag(p.ss_dis > 0, [&](auto D) {
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_tile<L, false, D, true>), dim3(gwd), dim3(TILE_THREADS), 0, sw, sa, (const TileRec *)c->tile_rec.p, (const TileWin *)c->tw.p,
+                               (const TileStat *)c->tile_stat.p, (const SlotRec *)c->slot_rec.p, c->tile_xbase.p);
+        }); });
+        if (beside) HIP_TRY(hipEventRecord(c->ev_join[0], sw));
     }
+    const unsigned gcd = c->lists_known ? std::max(c->n_chunk_tiles, 1u) : (unsigned)std::max<int64_t>(c->n_tiles, 1);
+    if (chunk_launch && beside) {
+        HIP_TRY(hipStreamWaitEvent(c->side[1], c->ev_fork, 0));
+        launch_tile_chunk(c, p, sa, gcd, 0u, c->side[1]);
+        HIP_TRY(hipEventRecord(c->ev_join[1], c->side[1]));
+    }
+    const unsigned gf = fused_grid(c->n_tiles);
+    with_level(p.full_level, [&](auto L) { with_flag(p.ss_dis > 0, [&](auto D) { with_flag(c->want & L2R_WANT_ACCEPTED, [&](auto A) {
+        // (k_tile decides acceptance itself, junction table or not)
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_tile<L, A, D>), dim3(gf), dim3(TILE_THREADS), 0, s, sa, (const TileRec *)c->tile_rec.p, (const TileWin *)c->tw.p,
+                           (const TileStat *)c->tile_stat.p, (const SlotRec *)c->slot_rec.p, c->tile_xbase.p);
+    }); }); });
+    MARK(ST_FAST);
+    if (chunk_launch && !beside) launch_tile_chunk(c, p, sa, gcd, 0u, s);
+    if (wide_launch && beside) HIP_TRY(hipStreamWaitEvent(s, c->ev_join[0], 0));
+    if (chunk_launch && beside) HIP_TRY(hipStreamWaitEvent(s, c->ev_join[1], 0));
+    const unsigned gl = (unsigned)std::min<int64_t>(c->n_tiles ? c->n_tiles : 1, (int64_t)c->n_cu * 2);
+    if (!skip_lists && !(c->lists_known && c->fb_empty && !c->env_launch_all)) launch_probe(c, p, sa, true, false, gl);
+    return 0;
+}
+
+// ---- slab and tile: the list-driven kernels behind the probes (none has anything to do on most inputs: the grid finds an empty list and leaves)
+static void launch_lists(l2r_ctx *c, const DevParams &p, const SlabArgs &sa, bool tile, bool skip_lists)
+{
+    if (skip_lists) return;
+    hipStream_t s = c->stream;
+    const bool known = tile && c->lists_known && !c->env_launch_all;      // (a completed run of the tile path has shown a list empty)
+    if (!(known && c->wide_rest_empty)) {
+        // the tiles with 33 .. 63 window members
+        const WideArgs wa{c->tw64.p};
+        const unsigned gw = (unsigned)std::min<int64_t>(c->n_tiles ? c->n_tiles : 1, (int64_t)c->n_cu * 5);
+        with_level(p.full_level, [&](auto L) {
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_probe_slab_wide<L>), dim3(gw), dim3(TILE_THREADS), 0, s, sa, wa, (const uint32_t *)c->tile_first.p, (const int32_t *)c->r_pos.p,
+                               (const uint32_t *)c->tile_sbase.p, (const TileWin *)c->tw.p, (const uint32_t *)c->tile_xbase.p, (const TileStat *)(tile ? c->tile_stat.p : nullptr));
+        });
+    }
+    if (sa.chunk_direct_on && !(known && c->n_late_tiles == 0u)) {
+        // the tiles a one-window kernel handed on late (a key in several entries): k_tile_chunk once more, over that list
+        // (every entry needs its workgroup: k_probe_slab_chunked skips what this launch takes)
+        const unsigned gl2 = c->lists_known ? std::max(c->n_late_tiles, 1u) : (unsigned)std::max<int64_t>(c->n_tiles, 1);
+        launch_tile_chunk(c, p, sa, gl2, 1u, s);
+    }
+    if (sa.chunk_on && !(known && c->chunk_rest_empty)) {
+        // the tiles without a window record, or with a dictionary key in several entries
+        const unsigned gc = (unsigned)std::min<int64_t>(c->n_tiles ? c->n_tiles : 1, (int64_t)c->n_cu * 4);
+        with_level(p.full_level, [&](auto L) {
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_probe_slab_chunked<L>), dim3(gc), dim3(TILE_THREADS), 0, s, sa, (const uint32_t *)c->tile_first.p, (const int32_t *)c->r_pos.p,
+                               (const uint32_t *)c->tile_sbase.p, (const TileWin *)c->tw.p, (const uint32_t *)c->tile_xbase.p);
+        });
+    }
+    // (accepted list: k_describe_scan marks every tile CHUNK_DEFERRED, k_probe_slab<., true> takes that back for the tiles whose
+    //  chunk it has written itself; k_count_accepted / k_gather_accepted place the rest)
+}
+
+// ---- every pipeline: the generic kernel (reads the others handed on), the junction check, the accepted list's count / scan / gather
+static int launch_tail(l2r_ctx *c, hipEvent_t *ev, const DevParams &p, const CursorDir &cd, const int32_t *j0)
+{
+    hipStream_t s = c->stream;
+    const bool tile = c->pipe == Pipeline::tile;
+    const unsigned gt = (unsigned)(c->n_tiles ? c->n_tiles : 1), g256 = (unsigned)(c->n_tiles256 ? c->n_tiles256 : 1);
     MARK(ST_GENERIC);
     // (one-kernel tile path: a completed run of the same inputs and parameters has left nothing on the redo list and nothing to the
     //  list-driven kernels -- no read is left for the generic kernel, and what it used to clear for the next run is cleared in front)
     // (... or nothing on the redo list: the list counters need no launch for their clearing, they take turns)
-    const bool nothing_left = c->tile && c->lists_known && c->redo_empty && (c->lists_empty || c->n_sj == 0) && !c->env_launch_all;
-    if (c->tile) { c->lb_flip ^= 1u; c->lc_flip ^= 1u; }
-    c->prev_run_tile = c->tile;
+    const bool nothing_left = tile && c->lists_known && c->redo_empty && (c->lists_empty || c->n_sj == 0) && !c->env_launch_all;
+    if (tile) { c->lb_flip ^= 1u; c->lc_flip ^= 1u; }
+    c->prev_run_tile = tile;
     if (!nothing_left) {
         const unsigned gg = (unsigned)std::min<int64_t>(c->n_tiles ? c->n_tiles * 4 : 1, 4096);      // one wave per listed read, grid-stride
         hipLaunchKernelGGL(k_classify_generic, dim3(gg), dim3(TILE_THREADS), 0, s, c->totals.p + 3, c->redo.p, c->r_tid.p, c->r_rev.p,
-                           (c->slab ? (const int32_t *)nullptr : j0),
+                           (c->pipe != Pipeline::classic ? (const int32_t *)nullptr : j0),
                            c->hdr.p, c->anno_ex.p, p, c->ex_off.p, c->ex_start.p, c->ex_end.p, c->ex_flag.p, c->info.p, c->ref_tx.p,
                            c->tile_acc.p, c->tile_acc_ex.p, (const uint32_t *)c->tile_first.p, (int)c->n_tiles, cd, (uint32_t *)nullptr);
     }
     MARK(ST_SJ);
     // (one-kernel tile path: k_tile has checked every read whose verdict it made; with nothing on the redo list and nothing left to the
     //  list-driven kernels -- seen by a completed run of the same inputs and parameters -- no read is left for this launch)
-    const bool sj_all_in_tile = nothing_left;
-    if (c->n_sj > 0 && !sj_all_in_tile) {
+    if (c->n_sj > 0 && !nothing_left) {
         if (!c->sorted) { int rc = prepare_unsorted_sj_cursor(c); if (rc) return rc; }
-        hipLaunchKernelGGL(k_validate_sj, dim3(g256), dim3(TILE_THREADS), 0, s, N, c->r_tid.p, c->ex_off.p, c->ex_start.p, c->ex_end.p, c->ex_flag.p,
+        hipLaunchKernelGGL(k_validate_sj, dim3(g256), dim3(TILE_THREADS), 0, s, c->n_reads, c->r_tid.p, c->ex_off.p, c->ex_start.p, c->ex_end.p, c->ex_flag.p,
                            c->sj_key.p, (c->sorted ? (const int32_t *)nullptr : c->sj_cursor.p), c->sj_tid.p, c->sj_don.p, c->sj_acc.p,
                            c->sj_uniq.p, c->sj_multi.p, p, c->info.p,
                            SjDir{CursorDir{c->sj_key.p, c->sj_cdir.p, c->sj_cbase.p, c->sj_ntid, (int32_t)c->n_sj}, c->sj_ddir.p, c->sj_dbase.p, c->sj_ntid, c->sj_row.p});
     }
-    if ((c->n_sj > 0 || c->slab) && (c->want & L2R_WANT_ACCEPTED)) {
+    if ((c->n_sj > 0 || c->pipe != Pipeline::classic) && (c->want & L2R_WANT_ACCEPTED)) {
         // acceptance is decided by the junction check (and the slab pipeline counts nothing itself): count per tile
-            hipLaunchKernelGGL(k_count_accepted, dim3((gt + 3u) / 4u), dim3(TILE_THREADS), 0, s, (const uint32_t *)c->tile_first.p, c->info.p, (const uint32_t *)c->tile_chunk.p, c->tile_acc.p, c->tile_acc_ex.p, (uint32_t)c->n_tiles);
+        hipLaunchKernelGGL(k_count_accepted, dim3((gt + 3u) / 4u), dim3(TILE_THREADS), 0, s, (const uint32_t *)c->tile_first.p, c->info.p, (const uint32_t *)c->tile_chunk.p, c->tile_acc.p, c->tile_acc_ex.p, (uint32_t)c->n_tiles);
     }
     MARK(ST_SCAN2);
     if (c->want & L2R_WANT_ACCEPTED) {
@@ -1426,14 +1419,42 @@ static int launch_all(l2r_ctx *c, hipEvent_t *ev /* ST_N + 1 events or null */)
     }
     MARK(ST_GATHER);
     if (c->want & L2R_WANT_ACCEPTED)
-    hipLaunchKernelGGL(k_gather_accepted, dim3((gt + GATHER_TILES - 1) / GATHER_TILES), dim3(TILE_THREADS), 0, s, (const uint32_t *)c->tile_first.p, c->first_read, c->info.p, c->ref_tx.p, c->ex_off.p,
-                       c->ex_start.p, c->ex_end.p, c->ex_flag.p, c->tile_acc_at.p, c->tile_acc_ex_at.p, c->tile_chunk.p, c->tile_rchunk.p, c->totals.p + 4,
-                       c->acc_rec.p, c->acc_ex_off.p, c->acc_start.p, c->acc_end.p, c->acc_flag.p, (uint32_t)c->n_tiles);
+        hipLaunchKernelGGL(k_gather_accepted, dim3((gt + GATHER_TILES - 1) / GATHER_TILES), dim3(TILE_THREADS), 0, s, (const uint32_t *)c->tile_first.p, c->first_read, c->info.p, c->ref_tx.p, c->ex_off.p,
+                           c->ex_start.p, c->ex_end.p, c->ex_flag.p, c->tile_acc_at.p, c->tile_acc_ex_at.p, c->tile_chunk.p, c->tile_rchunk.p, c->totals.p + 4,
+                           c->acc_rec.p, c->acc_ex_off.p, c->acc_start.p, c->acc_end.p, c->acc_flag.p, (uint32_t)c->n_tiles);
     MARK(ST_N);
-#undef MARK
+    return 0;
+}
+
+// One run: the front of the pipeline choose_pipeline picks, the list-driven kernels of the slab and the tile pipeline, the common tail
+static int launch_all(l2r_ctx *c, hipEvent_t *ev /* ST_N + 1 events or null */)
+{
+    const DevParams p = dev_params(c);
+    MARK(ST_PASS_A);
+    c->pipe = choose_pipeline(c, p);
+    const int32_t *j0 = c->sorted ? (const int32_t *)c->j0.p : (const int32_t *)c->win_start.p;
+    const CursorDir cd{c->anno_key.p, c->key_dir.p, c->kb_base.p, c->n_tid_key, (int32_t)c->n_tx};
+    const SiteTabs tabs{{c->sk_st.p, c->sd_st.p, c->sr_st.p}, {c->sk_en.p, c->sd_en.p, nullptr}, c->tid_base.p, c->n_tid_dir};
+    const FastArgs fa = fast_args(c, p, tabs, j0);
+    int rc = 0;
+    if (c->pipe == Pipeline::classic) rc = launch_classic(c, ev, p, fa, cd, tabs);
+    else {
+        const bool tile = c->pipe == Pipeline::tile;
+        // (the list counters are whatever a slab run left: cleared in front of the first tile run behind one)
+        if (tile && !c->prev_run_tile) { HIP_TRY(hipMemsetAsync(c->list_cnt.p, 0, 128, c->stream)); c->lc_flip = 0; }
+        const SlabArgs sa = slab_args(c, fa, cd, tile);
+        // (the three list-driven kernels behind k_tile: not launched once a completed run of the same inputs and parameters has shown
+        //  their lists empty -- what ends up on them does not depend on anything else)
+        const bool skip_lists = tile && c->lists_known && c->lists_empty && !c->env_launch_all;
+        rc = tile ? launch_tile(c, ev, p, sa, skip_lists) : launch_slab(c, ev, p, sa);
+        if (!rc) launch_lists(c, p, sa, tile, skip_lists);
+    }
+    if (!rc) rc = launch_tail(c, ev, p, cd, j0);
+    if (rc) return rc;
     HIP_TRY(hipGetLastError());
     return 0;
 }
+#undef MARK
 
 /* diagnostics: L2R_STAMPS=1 makes k_classify_fast accumulate per-phase cycles; this prints and clears them */
 int l2r_debug_stamps(l2r_ctx *c, unsigned long long *out, int n)
@@ -1455,7 +1476,7 @@ int l2r_debug_stamps(l2r_ctx *c, unsigned long long *out, int n)
 int l2r_debug_tile_times(l2r_ctx *c, uint32_t *out, int64_t n_tiles)
 {
     if (!c || !out) return fail(-1, "[l2r_debug_tile_times] null argument");
-    if (!c->tile || !c->ran || n_tiles > c->n_tiles) return fail(-1, "[l2r_debug_tile_times] no run of the one-kernel tile path to report");
+    if (c->pipe != Pipeline::tile || !c->ran || n_tiles > c->n_tiles) return fail(-1, "[l2r_debug_tile_times] no run of the one-kernel tile path to report");
     HIP_TRY(hipSetDevice(c->device));
     const uint32_t *src[4] = {c->tile_total.p, c->tile_acc.p, c->tile_acc_ex.p, c->tile_flags.p};
     std::vector<uint32_t> h((size_t)n_tiles);
@@ -1482,14 +1503,14 @@ int l2r_debug_counters(l2r_ctx *c, long long *out, int n)
     if (n >= 14) out[13] = c->n_lb_fallback;              // runs done again on the slab pipeline because k_tile's look-back starved
     if (n >= 16) {                                        // one-kernel tile path, last run: entries of chunk_list k_tile_chunk declined, tiles handed to the chunked kernel late
         out[14] = 0; out[15] = 0;
-        if (c->tile && c->ran && c->list_cnt.p) {
+        if (c->pipe == Pipeline::tile && c->ran && c->list_cnt.p) {
             uint32_t lc[16];
             HIP_TRY(hipMemcpyAsync(lc, c->list_cnt.p + 16 * ((c->lc_flip & 1u) ^ 1u), sizeof lc, hipMemcpyDeviceToHost, c->stream));
             HIP_TRY(hipStreamSynchronize(c->stream));
             out[14] = lc[9]; out[15] = lc[8];
         }
     }
-    if (n >= 12 && c->slab && c->ran && c->tw.p && c->n_tiles > 0) {     // slab pipeline: the descriptors k_walk_slab made (flags as the probe kernels left them)
+    if (n >= 12 && c->pipe != Pipeline::classic && c->ran && c->tw.p && c->n_tiles > 0) {     // slab pipeline: the descriptors k_walk_slab made (flags as the probe kernels left them)
         std::vector<TileWin> w((size_t)c->n_tiles);
         HIP_TRY(hipMemcpyAsync(w.data(), c->tw.p, w.size() * sizeof(TileWin), hipMemcpyDeviceToHost, c->stream));
         HIP_TRY(hipStreamSynchronize(c->stream));
@@ -1510,7 +1531,7 @@ int l2r_debug_counters(l2r_ctx *c, long long *out, int n)
             out[4 + ((t.d.flags >> 8) & 7u)]++;
             if (n >= 13 && (t.d.flags & TD_WIDE) && !(t.d.flags & TD_CHUNK)) out[12]++;     // out[12]: tiles k_probe_slab_wide classified (33 .. 63 window members)
         }
-    } else if (n >= 12 && !c->slab && c->desc.p && c->n_tiles > 0) {     // out[4 + k]: tiles that are not fast for reason k (k_pass_a), k = 0: fast
+    } else if (n >= 12 && c->pipe == Pipeline::classic && c->desc.p && c->n_tiles > 0) {     // out[4 + k]: tiles that are not fast for reason k (k_pass_a), k = 0: fast
         std::vector<TileDesc> d((size_t)c->n_tiles);
         HIP_TRY(hipMemcpyAsync(d.data(), c->desc.p, d.size() * sizeof(TileDesc), hipMemcpyDeviceToHost, c->stream));
         HIP_TRY(hipStreamSynchronize(c->stream));
@@ -1530,8 +1551,8 @@ const char *l2r_stage_kernel(l2r_ctx *c, int stage)
     // (the first word is the kernel's name as a profile lists it; both scans are launches of k_scan_u32)
     static const char *const classic[L2R_N_STAGES] = {"k_pass_a", "k_scan_u32 (tile sums)", "k_classify_fast", "k_classify_generic",
                                                       "k_validate_sj", "k_scan_accepted (k_scan_u32 of the accepted counts)", "k_gather_accepted", ""};
-    if (stage >= 3 || !c->slab) return classic[stage];
-    if (c->tile) return stage == 0 ? "k_describe_scan (tile descriptors + tile lists; first kernel of the run)" : stage == 1 ? "k_tile (walk + probes + write-out, one workgroup per tile)" : "k_probe_slab (tiles k_tile left in slab form) (+ k_tile_chunk + k_probe_slab_wide + k_probe_slab_chunked)";
+    if (stage >= 3 || c->pipe == Pipeline::classic) return classic[stage];
+    if (c->pipe == Pipeline::tile) return stage == 0 ? "k_describe_scan (tile descriptors + tile lists; first kernel of the run)" : stage == 1 ? "k_tile (walk + probes + write-out, one workgroup per tile)" : "k_probe_slab (tiles k_tile left in slab form) (+ k_tile_chunk + k_probe_slab_wide + k_probe_slab_chunked)";
     return stage == 0 ? (c->wide_cigar ? "k_walk_slab_long" : "k_walk_slab") : stage == 1 ? "k_describe_scan (tile descriptors + scan of the exon counts + tile lists)" : "k_probe_slab (+ k_probe_slab_wide + k_probe_slab_chunked)";
 }
 
@@ -1541,25 +1562,7 @@ int l2r_run(l2r_ctx *c)
     HIP_TRY(hipSetDevice(c->device));
     int rc = prepare_unsorted_windows(c);
     if (rc) return rc;
-    // L2R_GRAPH=1: the launch sequence (7 kernels, no host round trip) is captured into a hipGraph on first use and
-    // replayed, one submission per pass instead of seven.  Off by default: measured on MI355X / ROCm 7.2 the replay is
-    // 2-4 % slower than the seven direct launches (config 2: 0.093 vs 0.089 ms, config 3: 1.42 vs 1.40 ms per pass).
-    // Not for unsorted input with a junction table (its cursor replay syncs).
-    // Not for the one-kernel tile path either (two launches: nothing to gain, and its launch arguments change run by run -- the
-    // super-block words take turns, launches are dropped once a run has shown them empty).
-    const bool graphable = !(c->n_sj > 0 && !c->sorted) && (c->want_pipeline < 2 || (c->ran && !c->tile)) && getenv("L2R_GRAPH") != nullptr;
-    if (graphable && !c->graph_valid) {
-        hipGraph_t g = nullptr;
-        if (hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal) == hipSuccess) {
-            rc = launch_all(c, nullptr);
-            const hipError_t e = hipStreamEndCapture(c->stream, &g);
-            if (rc == 0 && e == hipSuccess && g && hipGraphInstantiate(&c->graph, g, nullptr, nullptr, 0) == hipSuccess) c->graph_valid = true;
-            if (g) (void)hipGraphDestroy(g);
-            if (!c->graph_valid) { (void)hipGetLastError(); c->graph = nullptr; }
-        }
-    }
-    if (graphable && c->graph_valid) HIP_TRY(hipGraphLaunch(c->graph, c->stream));
-    else { rc = launch_all(c, nullptr); if (rc) return rc; }
+    if ((rc = launch_all(c, nullptr))) return rc;
     c->ran = true; c->totals_valid = false;
     return 0;
 }
@@ -1569,7 +1572,7 @@ int l2r_sync(l2r_ctx *c)
     if (!c) return fail(-1, "[l2r_sync] null context");
     HIP_TRY(hipSetDevice(c->device));
     HIP_TRY(hipStreamSynchronize(c->stream));
-    if (c->ran && c->tile && c->totals.p) {
+    if (c->ran && c->pipe == Pipeline::tile && c->totals.p) {
         // a tile of k_tile waited in vain for the exon counts in front of it (its poll limit ended every wait: the run is complete but its
         // result slots are not to be trusted): the SAME resident upload once more on the slab pipeline, which has no such wait -- and no
         // later run of this context takes the tile path again (the cause is the device's occupancy, not this input)
@@ -1585,7 +1588,7 @@ int l2r_sync(l2r_ctx *c)
             snprintf(g_err, sizeof g_err, "[l2r_sync] note: k_tile's look-back starved; the run was done again on the slab pipeline (this context keeps to it)");
         }
     }
-    if (c->ran && c->tile && !c->lists_known && c->list_cnt.p) {
+    if (c->ran && c->pipe == Pipeline::tile && !c->lists_known && c->list_cnt.p) {
         // what the run left on the lists of the kernels behind k_tile (k_classify_generic keeps the counts of the 64-bit-mask and the
         // chunked kernel's lists in words 6, 7 when it clears them; word 4: k_probe_slab's)
         uint32_t lc[16];
@@ -1619,7 +1622,7 @@ static int fetch_totals(l2r_ctx *c)
     HIP_TRY(hipMemcpyAsync(dev, c->totals.p, sizeof dev, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     // accepted exons = the chunks the classification kernel placed itself (cursor) + the ones k_gather_accepted placed
-    if (c->tile && dev[6] != 0u) return fail(-2, "[l2r] k_tile: a tile waited in vain for the exon counts of the tiles in front of it and l2r_sync was not called behind the run (it does the run again on the slab pipeline)");
+    if (c->pipe == Pipeline::tile && dev[6] != 0u) return fail(-2, "[l2r] k_tile: a tile waited in vain for the exon counts of the tiles in front of it and l2r_sync was not called behind the run (it does the run again on the slab pipeline)");
     c->h_totals[0] = dev[0]; c->h_totals[1] = dev[1] + dev[5]; c->h_totals[2] = dev[2] + dev[4];
     if (!(c->want & L2R_WANT_ACCEPTED)) c->h_totals[1] = c->h_totals[2] = 0;
     c->totals_valid = true;
@@ -1865,8 +1868,6 @@ int l2r_filter_score(l2r_ctx *c, const l2r_filter_records *r, const l2r_filter_p
     }
     hipError_t e = hipStreamSynchronize(c->stream);          // (the host vectors and the DevBufs above are locals)
     if (!rc && e != hipSuccess) rc = fail(-2, "[l2r_filter_score] %s", hipGetErrorString(e));
-    d_flag.release(); d_tid.release(); d_pos.release(); d_lq.release(); d_nm.release(); d_score.release(); d_in.release(); d_st.release(); d_pe.release();
-    d_off.release(); d_soff.release(); d_cig.release(); d_drop.release();
     return rc;
 }
 
@@ -1891,7 +1892,6 @@ int l2r_filter_select(l2r_ctx *c, int64_t n_groups, const int64_t *group_off, co
     }
     hipError_t e = hipStreamSynchronize(c->stream);
     if (!rc && e != hipSuccess) rc = fail(-2, "[l2r_filter_select] %s", hipGetErrorString(e));
-    d_off.release(); d_win.release(); d_score.release(); d_in.release();
     return rc;
 }
 

@@ -113,19 +113,27 @@ l2r_xchg *l2r_xchg_create(l2r_ctx *c, int rank, int world, const void *id_in)
     return x;
 }
 
+// The k words `mine` of every rank, all-gathered: all = world x k words, rank by rank (on every rank)
+static int xchg_all_gather(l2r_xchg *x, hipStream_t s, const long long *mine, int k, std::vector<long long> &all)
+{
+    const size_t W = (size_t)x->world;
+    DevBuf<long long> d;
+    if (d.ensure((size_t)k * (W + 1))) return -2;
+    HIP_TRY(hipMemcpyAsync(d.p + k * W, mine, (size_t)k * 8, hipMemcpyHostToDevice, s));
+    NCCL_TRY(ncclAllGather(d.p + k * W, d.p, (size_t)k, ncclInt64, x->comm, s));
+    all.resize(k * W);
+    HIP_TRY(hipMemcpyAsync(all.data(), d.p, all.size() * 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    return 0;
+}
+
 // Every rank says whether it can go on (0) before any of them enters a send / receive group: a rank that left alone -- rank 0 with
 // buffers too small -- would leave its peers blocked in ncclSend.  Returns the first non-zero status of the world (on every rank).
 static int xchg_agree(l2r_xchg *x, hipStream_t s, long long status, const char *who)
 {
     const int W = x->world;
-    DevBuf<long long> d;
-    if (d.ensure((size_t)W + 1)) return -2;
-    HIP_TRY(hipMemcpyAsync(d.p + W, &status, 8, hipMemcpyHostToDevice, s));
-    NCCL_TRY(ncclAllGather(d.p + W, d.p, 1, ncclInt64, x->comm, s));
-    std::vector<long long> all((size_t)W);
-    HIP_TRY(hipMemcpyAsync(all.data(), d.p, (size_t)W * 8, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    d.release();
+    std::vector<long long> all;
+    if (int rc = xchg_all_gather(x, s, &status, 1, all)) return rc;
     for (int k = 0; k < W; ++k)
         if (all[(size_t)k] != 0) {
             if (k == x->rank) return (int)status;              // (its own message stands)
@@ -156,15 +164,9 @@ int l2r_xchg_gather_results(l2r_xchg *x, l2r_result *res, int64_t *counts_out)
     const int W = x->world;
     hipStream_t s = c->stream;
     // ---- sizes
-    DevBuf<long long> d_cnt;
-    if (d_cnt.ensure((size_t)2 * (W + 1))) return -2;
     const long long mine[2] = {(long long)c->n_reads, (long long)c->h_totals[0]};
-    HIP_TRY(hipMemcpyAsync(d_cnt.p + 2 * W, mine, sizeof mine, hipMemcpyHostToDevice, s));
-    NCCL_TRY(ncclAllGather(d_cnt.p + 2 * W, d_cnt.p, 2, ncclInt64, x->comm, s));
-    std::vector<long long> cnt((size_t)2 * W);
-    HIP_TRY(hipMemcpyAsync(cnt.data(), d_cnt.p, cnt.size() * 8, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    d_cnt.release();
+    std::vector<long long> cnt;
+    if ((rc = xchg_all_gather(x, s, mine, 2, cnt))) return rc;
     std::vector<long long> r_at((size_t)W + 1, 0), x_at((size_t)W + 1, 0);
     for (int k = 0; k < W; ++k) { r_at[k + 1] = r_at[k] + cnt[2 * k]; x_at[k + 1] = x_at[k] + cnt[2 * k + 1]; }
     if (counts_out) for (int k = 0; k < 2 * W; ++k) counts_out[k] = cnt[k];
@@ -179,7 +181,7 @@ int l2r_xchg_gather_results(l2r_xchg *x, l2r_result *res, int64_t *counts_out)
         else if (res->n_reads < R || res->ex_cap < X) status = fail(-4, "[l2r_xchg_gather_results] result buffers too small (%lld reads, %lld exons)", R, X);
         else for (int a = 0; a < 6 && !status; ++a) if (g[a].ensure((size_t)(parts[a].per_exon ? X : R) * parts[a].width + 16)) status = -2;
     }
-    if ((rc = xchg_agree(x, s, status, "l2r_xchg_gather_results"))) { for (int a = 0; a < 6; ++a) g[a].release(); return rc; }
+    if ((rc = xchg_agree(x, s, status, "l2r_xchg_gather_results"))) return rc;
     NCCL_TRY(ncclGroupStart());
     for (int a = 0; a < 6; ++a) {
         const std::vector<long long> &at = parts[a].per_exon ? x_at : r_at;
@@ -217,7 +219,6 @@ int l2r_xchg_gather_results(l2r_xchg *x, l2r_result *res, int64_t *counts_out)
         for (long long i = 0; i < R; ++i)
             if (res->ex_off[i] + (int64_t)(res->info[i] >> 8) != res->ex_off[i + 1]) return fail(-5, "[l2r_xchg_gather_results] exon counts do not add up at read %lld", i);
     } else HIP_TRY(hipStreamSynchronize(s));
-    for (int a = 0; a < 6; ++a) g[a].release();
     return 0;
 }
 
@@ -237,15 +238,9 @@ int l2r_xchg_gather_accepted(l2r_xchg *x, l2r_accepted *acc, int64_t *counts_out
     if (!(c->want & L2R_WANT_ACCEPTED)) return fail(-1, "[l2r_xchg_gather_accepted] the accepted list was not requested (l2r_set_outputs)");
     const int W = x->world;
     hipStream_t s = c->stream;
-    DevBuf<long long> d_cnt;
-    if (d_cnt.ensure((size_t)3 * (W + 1))) return -2;
     const long long mine[3] = {(long long)c->h_totals[1], (long long)c->h_totals[2], (long long)c->n_tiles};
-    HIP_TRY(hipMemcpyAsync(d_cnt.p + 3 * W, mine, sizeof mine, hipMemcpyHostToDevice, s));
-    NCCL_TRY(ncclAllGather(d_cnt.p + 3 * W, d_cnt.p, 3, ncclInt64, x->comm, s));
-    std::vector<long long> cnt((size_t)3 * W);
-    HIP_TRY(hipMemcpyAsync(cnt.data(), d_cnt.p, cnt.size() * 8, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    d_cnt.release();
+    std::vector<long long> cnt;
+    if ((rc = xchg_all_gather(x, s, mine, 3, cnt))) return rc;
     std::vector<long long> m_at((size_t)W + 1, 0), x_at((size_t)W + 1, 0), t_at((size_t)W + 1, 0);
     for (int k = 0; k < W; ++k) { m_at[k + 1] = m_at[k] + cnt[3 * k]; x_at[k + 1] = x_at[k] + cnt[3 * k + 1]; t_at[k + 1] = t_at[k] + cnt[3 * k + 2]; }
     if (counts_out) for (int k = 0; k < W; ++k) { counts_out[2 * k] = cnt[3 * k]; counts_out[2 * k + 1] = cnt[3 * k + 1]; }
@@ -261,7 +256,7 @@ int l2r_xchg_gather_accepted(l2r_xchg *x, l2r_accepted *acc, int64_t *counts_out
         else if (acc->n_reads < M || acc->ex_cap < X) status = fail(-4, "[l2r_xchg_gather_accepted] buffers too small (%lld records, %lld exons)", M, X);
         else for (int a = 0; a < 6 && !status; ++a) if (g[a].ensure((size_t)at_of(parts[a].by)[W] * parts[a].width + 16)) status = -2;
     }
-    if ((rc = xchg_agree(x, s, status, "l2r_xchg_gather_accepted"))) { for (int a = 0; a < 6; ++a) g[a].release(); return rc; }
+    if ((rc = xchg_agree(x, s, status, "l2r_xchg_gather_accepted"))) return rc;
     NCCL_TRY(ncclGroupStart());
     for (int a = 0; a < 6; ++a) {
         const std::vector<long long> &at = at_of(parts[a].by);
@@ -313,7 +308,6 @@ int l2r_xchg_gather_accepted(l2r_xchg *x, l2r_accepted *acc, int64_t *counts_out
             if (a1 <= a0) return fail(-5, "[l2r_xchg_gather_accepted] records out of read order at %lld (do the uploads say their first_read_index?)", i);
         }
     } else HIP_TRY(hipStreamSynchronize(s));
-    for (int a = 0; a < 6; ++a) g[a].release();
     return 0;
 }
 
