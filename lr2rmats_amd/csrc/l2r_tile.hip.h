@@ -45,6 +45,12 @@ namespace l2r {
 #define L2R_TILE_GROUP_SHIFT 4
 #endif
 constexpr uint32_t TILE_GROUP = 1u << L2R_TILE_GROUP_SHIFT;      // consecutive tiles per XCD
+// k_tile's front (A/B switch; on in the product):
+//   L2R_TILE_EXACT_WALK  an exact tile places its exons with a walk that knows "a cut is an N, every cut keeps" (the general walk is
+//                        for the tiles that count, and for L2R_ABLATE bit 8)
+#ifndef L2R_TILE_EXACT_WALK
+#define L2R_TILE_EXACT_WALK 1
+#endif
 // Workgroup -> tile, blocked-cyclic: workgroup b runs on XCD b % 8 (observed placement: for speed only), so XCD x takes the tile groups
 // x, x + 8, x + 16, ...  The grid is a whole number of rounds of 8 groups; workgroups behind the last tile leave at once.
 __device__ __forceinline__ uint32_t fused_tile(uint32_t b)
@@ -648,8 +654,10 @@ void k_tile(SlabArgs kernarg_block, const TileRec *__restrict__ u_rec, const Til
     if constexpr (WIDE) wide_stage_dict(d, dv, reinterpret_cast<const int *>(sa->tw64[t].win), s_ent0, s_ent1, s_dir0, s_dir1, s_rdir);
     else if (!pre_slab) my_wide = slab_stage_dict(d, dv, reinterpret_cast<const int *>(u_tw[t].win), SlabLds{nullptr, s_ent0, s_ent1, s_dir0, s_dir1, s_rdir});
     stamp.mark(0);
+    // (a vector is fetched if its first word is the read's: only the three behind it can be another read's.  The WIDE instance keeps
+    //  the whole sweep: without it the compiler spills one register more there)
 #pragma unroll
-    for (int i = 0; i < SLAB_HEAD; ++i) cg[i] = (uint32_t)i < n_cig ? cg[i] : 1u;
+    for (int i = 0; i < SLAB_HEAD; ++i) if ((i & 3) || WIDE) cg[i] = (uint32_t)i < n_cig ? cg[i] : 1u;
     DevParams p;
     p.min_exon = a->f.p.min_exon; p.min_intron = a->f.p.min_intron; p.max_delet = a->f.p.max_delet;
     const uint32_t t3 = ((uint32_t)p.min_intron << 4) | 3u, t2 = ((uint32_t)(p.max_delet + 1) << 4) | 2u;      // op and length compare as one number
@@ -727,7 +735,40 @@ void k_tile(SlabArgs kernarg_block, const TileRec *__restrict__ u_rec, const Til
     ReadEnds re{0, 0, 0, 0};
     bool sane = true, big = false;
     n = 0u;
-    if (active) {
+    if (active && L2R_TILE_EXACT_WALK && counted) {
+        // EXACT (uniform over the workgroup): every N cuts and keeps, nothing else does -- no thresholds, no `first`.  The exon under way
+        // is {rel, xl}: its start relative to the tile's first base and its length so far.
+        uint32_t *const Ap = s_A + loc;
+        uint32_t *wp = Ap;
+        uint32_t rel = (uint32_t)(pos + 1 - tile_lo), xl = 0u, longest = 0u;
+        auto step = [&](uint32_t c) {
+            const uint32_t op = c & 0xfu, len = c >> 4;
+            const bool is_n = op == 3u;
+            if (is_n) *wp = slab_pack((int)rel, xl);
+            wp += is_n ? 1 : 0;
+            longest = max(longest, xl);                              // (xl only grows until its exon is stored)
+            rel += is_n ? xl + len : 0u;
+            xl = is_n ? 0u : xl + (len & (uint32_t)__builtin_amdgcn_sbfe(0x18d, op, 1u));
+        };
+#pragma unroll
+        for (int q = 0; q < SLAB_HEAD_VEC; ++q)
+            if (4 * q < c_max) { step(cg[4 * q]); step(cg[4 * q + 1]); step(cg[4 * q + 2]); step(cg[4 * q + 3]); }       // (wave-uniform)
+        if (n_cig > (uint32_t)SLAB_HEAD) {
+            const uint32_t n_ops = ld32(sa->cig_off32, r0 + idx + 1u) - c_lo;
+            const uint32_t *const words = a->f.cig + c_lo;
+            for (uint32_t i = SLAB_HEAD; i < n_ops; ++i) step(words[i]);
+        }
+        *wp = slab_pack((int)rel, xl);
+        longest = max(longest, xl);
+        if (rel >= SLAB_REL_MASK) longest = 0xffffffffu;
+        n = (uint32_t)(wp - Ap) + 1u;
+        big = longest > SLAB_LEN_MAX;
+        // the first exon's length from its row word (whole unless the read is `big`, and then nobody asks)
+        const uint32_t x0 = Ap[0] >> SLAB_REL_BITS;
+        sane = x0 >= 1u && xl >= 1u;
+        const int start = tile_lo + (int)rel;
+        re = ReadEnds{pos + 1, pos + (int)x0, start, start + (int)xl - 1};
+    } else if (active) {
         uint32_t *const Ap = s_A + loc;
         int start = pos + 1, end = pos;
         int s0 = 0, e0 = 0;
