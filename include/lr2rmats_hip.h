@@ -265,8 +265,11 @@ void         l2r_xchg_destroy(l2r_xchg *x);
  *   declined in the last run (its staging caps), [15] tiles handed to the chunked kernel late (a key in several entries); the last run's
  *   tile descriptors (slab / tile pipeline; classic: 24 and 25 only): [16..20] tiles of the chunked kernels by the END entries of their
  *   dictionary slices (<= 256, <= 512, <= 768, <= 1024, more), [21] / [22] ... with more than 128 / 256 START entries, [23] all of
- *   them, [24] / [25] the largest START / END slice of any tile, [26] tiles k_tile_chunk took from their CIGARs (TD_CDIRECT);
- *   n = words of out (4, 12, 13, 14, 16, 24 or 27).
+ *   them, [24] / [25] the largest START / END slice of any tile, [26] tiles k_tile_chunk took from their CIGARs (TD_CDIRECT),
+ *   [27] tiles k_describe_scan marked for k_tile's EXACT instance, which took them whole (TD_XDIRECT; tile pipeline), [28] entries of
+ *   the rest list the last run's k_describe_scan made: the tiles k_tile's general instance ran over beside the EXACT one ([27] + [28]
+ *   = [3]; both 0 with L2R_TILE_SPLIT=0, where the general instance takes every tile);
+ *   n = words of out (4, 12, 13, 14, 16, 24, 27 or 29).
  * l2r_debug_stamps: with L2R_STAMPS=1 in the environment at l2r_create, per-phase cycle sums of the classification kernel
  *   (and clears them); zeros otherwise.
  * l2r_debug_tile_times: with L2R_STAMPS=1, one-kernel tile path: four words per tile -- the chip's 100 MHz clock at the tile's start

@@ -92,6 +92,10 @@ struct l2r_ctx {
     uint32_t n_chunk_tiles = 0;                         // ... entries of chunk_list a completed run has left: k_tile_chunk's grid
     bool wide_rest_empty = false;                       // ... and none of them kept the slab form (list_cnt[5]): k_probe_slab_wide has nothing to do
     uint32_t n_wide_tiles = 0;                          // ... entries of wide_list a completed run has left (l2r_sync): the WIDE instance's grid
+    bool tile_split = true;                             // L2R_TILE_SPLIT=0: no EXACT instance of k_tile -- the general instance takes every tile (A/B runs, tests)
+    int64_t tile_resident = 0;                          // workgroups of k_tile the device holds at a time (l2r_create)
+    uint32_t n_rest_tiles = 0;                          // ... entries of rest_list a completed run has left (list_cnt[11]): the general instance's grid beside the EXACT one
+    DevBuf<uint32_t> rest_list;                         //     the tiles k_describe_scan<true> has not marked for the EXACT instance
     bool prev_run_tile = false;                         // the last launch of this upload took the tile path (else the list counters are whatever a slab run left: cleared before the next tile run)
     uint32_t lc_flip = 0;                               // ... and which of the two blocks of list counters (SlabArgs::list_cnt / list_cnt_next)
     uint32_t lb_flip = 0;                               // which of the two lb_sup arrays the next run of the tile path uses (l2r_slab.hip.h SlabArgs::lb_sup)
@@ -124,6 +128,10 @@ struct l2r_ctx {
     // their tiles' first slots are known since k_describe_scan -- and run BESIDE it on streams of their own (forked behind
     // k_describe_scan, joined in front of the list kernels): a few thousand long-lived workgroups fill in where the plain instance's
     // short ones leave CUs, instead of costing a launch each with a tail of its own.  L2R_SIDE=0: one behind the other on `stream`.
+    // k_tile's general instance over the rest list runs beside the EXACT instance too, on side[0] in front of the WIDE instance -- but only
+    // in runs WITHOUT an inexact tile (split_wait_free): then no tile of any instance waits for a count.  With inexact tiles the general
+    // instance is their only publisher, and EXACT workgroups that wait for them keep their CU slots: it goes on the main stream IN FRONT
+    // of the EXACT instance (launch_tile).  No stream of its own: with a third side stream two of the four streams shared a hardware queue.
     hipStream_t side[2] = {nullptr, nullptr};
     hipEvent_t ev_fork = nullptr, ev_join[2] = {nullptr, nullptr};
     bool side_on = true;
@@ -290,6 +298,8 @@ l2r_ctx *l2r_create(int device)
         c->env_tile_anyway = getenv("L2R_TILE_ANYWAY") != nullptr; c->env_launch_all = getenv("L2R_LAUNCH_ALL") != nullptr;
         e = getenv("L2R_CHUNK_DIRECT");
         if (e) c->chunk_direct = atoi(e) != 0;
+        e = getenv("L2R_TILE_SPLIT");
+        if (e) c->tile_split = atoi(e) != 0;
         e = getenv("L2R_SIDE");
         if (e) c->side_on = atoi(e) != 0;
         c->env_stamps = getenv("L2R_STAMPS") != nullptr;
@@ -300,6 +310,7 @@ l2r_ctx *l2r_create(int device)
             // masks): a device that cannot hold them takes the slab pipeline from the start
             int per_cu = 0;
             if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_tile<3, false, false, false>, TILE_THREADS, 0) != hipSuccess) { (void)hipGetLastError(); per_cu = 0; }
+            c->tile_resident = (int64_t)per_cu * c->n_cu;
             if ((int64_t)per_cu * c->n_cu < 8 * (int64_t)TILE_GROUP + 1 || getenv("L2R_TILE_STARVED")) c->tile_starved = true;
         }
     }
@@ -960,7 +971,7 @@ int l2r_upload_reads(l2r_ctx *c, const l2r_reads *r)
             sbase[T] = (uint32_t)total;                     // (rows of tile t = (sbase[t + 1] - sbase[t]) / 256)
             c->slab_ok = true;
             if (c->tw64.ensure(T + 1) || c->wide_list.ensure(2 * (T + 1)) || c->chunk_list.ensure(2 * (T + 1)) || c->list_cnt.ensure(32) || c->tile_flags.ensure(T + 8) ||
-                c->lb_tile.ensure(T + 64) || c->lb_blk.ensure(T / LB_BLK + 64) || c->lb_sup.ensure(2 * ((T >> LB_SUP_SHIFT) + 64)) || c->fb_list.ensure(T + 1) || c->tile_stat.ensure(T + 1) || c->sup_stat.ensure((T >> LB_SUP_SHIFT) + 2) ||
+                c->lb_tile.ensure(T + 64) || c->lb_blk.ensure(T / LB_BLK + 64) || c->lb_sup.ensure(2 * ((T >> LB_SUP_SHIFT) + 64)) || c->fb_list.ensure(T + 1) || c->rest_list.ensure(T + 1) || c->tile_stat.ensure(T + 1) || c->sup_stat.ensure((T >> LB_SUP_SHIFT) + 2) ||
                 (!c->wide_cigar && c->slot_rec.ensure((T + 1) * TILE_THREADS))) return -2;
             HIP_TRY(hipMemsetAsync(c->lb_sup.p, 0, 2 * ((T >> LB_SUP_SHIFT) + 64) * 8, c->stream)); c->lb_flip = 0;      // (two arrays taking turns; from then on each is cleared by the run in front of its own)      // (an isoform-rich annotation makes EVERY tile wide: 2.4 KB each)
             HIP_TRY(hipMemsetAsync(c->list_cnt.p, 0, 128, c->stream)); c->lc_flip = 0; c->prev_run_tile = false;
@@ -1182,6 +1193,25 @@ static FastArgs fast_args(const l2r_ctx *c, const DevParams &p, const SiteTabs &
     return fa;
 }
 
+// The split of k_tile (l2r_tile.hip.h) and who may wait for whom.  Only an INEXACT tile publishes its exon count late, from the general
+// instance; every other count is known since k_describe_scan.  So:
+//   no inexact tile in this run (split_wait_free): nobody waits for anybody -- the split is on from the first run, the general instance
+//       runs beside the EXACT one;
+//   inexact tiles: a general tile may wait for one that stands ANYWHERE on the rest list (the list is not in tile order), and EXACT tiles
+//       wait for general ones.  Progress then needs every listed tile resident at once and the general instance dispatched before the
+//       EXACT one: the split is on only once a completed run has shown the list to fit half of what the device holds (and 4 per CU),
+//       with the general instance on the main stream in front.  Until the length is known the run only MAKES the list (SPLIT_LIST): the
+//       general instance takes every tile in tile order, whose look-back the dispatch order carries as it always has.
+//   a list beyond 4 entries per CU (an isoform-rich annotation): the split is off, the general instance's walk over the list buys nothing.
+static bool split_wait_free(const l2r_ctx *c) { return c->inexact_tiles == 0 && !(c->ablate & 256); }      // (inexact_tiles: choose_pipeline has counted them)
+static uint32_t split_mode(const l2r_ctx *c)
+{
+    if (!c->tile_split || !c->rest_list.p) return SPLIT_OFF;
+    const uint32_t fits = (uint32_t)std::min<int64_t>((int64_t)c->n_cu * 4, c->tile_resident / 2);
+    if (c->lists_known) return c->n_rest_tiles <= fits ? SPLIT_ON : SPLIT_OFF;
+    return split_wait_free(c) ? SPLIT_ON : SPLIT_LIST;
+}
+
 // The slab and the tile pipeline's arguments (l2r_slab.hip.h).  Every launch does all of it: nothing is kept from an earlier run of the same upload.
 static SlabArgs slab_args(const l2r_ctx *c, const FastArgs &fa, const CursorDir &cd, bool tile)
 {
@@ -1204,6 +1234,8 @@ static SlabArgs slab_args(const l2r_ctx *c, const FastArgs &fa, const CursorDir 
     sa.has_wide_keys = c->n_wide > 0 ? 1u : 0u;
     sa.wide_direct_on = (tile && c->wide_direct && c->tw64.p && !(c->ablate & 4)) ? 1u : 0u;
     sa.chunk_direct_on = (tile && c->chunk_direct && sa.chunk_on) ? 1u : 0u;
+    sa.rest_list = c->rest_list.p;
+    sa.split_on = tile ? split_mode(c) : SPLIT_OFF;
     return sa;
 }
 
@@ -1301,13 +1333,36 @@ static int launch_tile(l2r_ctx *c, hipEvent_t *ev, const DevParams &p, const Sla
     // tiles of the chunked kernel: k_tile_chunk, a workgroup per entry of chunk_list (the lists' lengths are known to the host once a run
     // has completed: until then a grid for every tile, most of which leave at once).  Both beside the plain instance, on streams of
     // their own (see l2r_ctx::side); with per-stage events or L2R_CHECK one behind the other.
-    const bool wide_launch = !skip_lists && sa.wide_direct_on;
-    const bool chunk_launch = !skip_lists && sa.chunk_direct_on && !(c->lists_known && c->n_chunk_tiles == 0u);
+    const bool wide_launch = !skip_lists && sa.wide_direct_on && !(c->lists_known && c->n_wide_tiles == 0u && !c->env_launch_all);
+    const bool chunk_launch = !skip_lists && sa.chunk_direct_on && !(c->lists_known && c->n_chunk_tiles == 0u && !c->env_launch_all);
     const bool beside = c->side_on && !ev && !c->check_stages;
-    if (beside && (wide_launch || chunk_launch)) HIP_TRY(hipEventRecord(c->ev_fork, s));
+    // the split of k_tile: the EXACT instance over every tile number (it leaves at once where k_describe_scan has not marked the tile),
+    // the general instance over the rest list -- not launched once a completed run has shown that list empty
+    const bool split = sa.split_on == SPLIT_ON;
+    const bool rest_beside = beside && split_wait_free(c);      // (else on the main stream, in front of the EXACT instance: split_mode)
+    const bool rest_launch = split && !(c->lists_known && c->n_rest_tiles == 0u && !c->env_launch_all);
+    const unsigned gf = fused_grid(c->n_tiles);
+    const unsigned gr = c->lists_known ? std::max(c->n_rest_tiles, 1u) : (unsigned)std::max<int64_t>(c->n_tiles, 1);
+    auto launch_general = [&](unsigned grid, hipStream_t st) {
+        with_level(p.full_level, [&](auto L) { with_flag(p.ss_dis > 0, [&](auto D) { with_flag(c->want & L2R_WANT_ACCEPTED, [&](auto A) {
+            // (k_tile decides acceptance itself, junction table or not)
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_tile<L, A, D>), dim3(grid), dim3(TILE_THREADS), 0, st, sa, (const TileRec *)c->tile_rec.p, (const TileWin *)c->tw.p,
+                               (const TileStat *)c->tile_stat.p, (const SlotRec *)c->slot_rec.p, c->tile_xbase.p);
+        }); }); });
+    };
+    // (a general instance with tiles that others wait for: in front of everything that may wait, the side instances included -- they
+    //  fork behind it)
+    if (rest_launch && !rest_beside) launch_general(gr, s);
+    if (beside && (wide_launch || chunk_launch || (rest_launch && rest_beside))) HIP_TRY(hipEventRecord(c->ev_fork, s));
+    if (rest_launch && rest_beside) {
+        // (on the WIDE instance's stream, in front of it: the WIDE instance starts when this one has ended)
+        HIP_TRY(hipStreamWaitEvent(c->side[0], c->ev_fork, 0));
+        launch_general(gr, c->side[0]);
+        if (!wide_launch) HIP_TRY(hipEventRecord(c->ev_join[0], c->side[0]));      // (else the WIDE instance behind it on this stream records the join)
+    }
     if (wide_launch) {
         hipStream_t sw = beside ? c->side[0] : s;
-        if (beside) HIP_TRY(hipStreamWaitEvent(sw, c->ev_fork, 0));
+        if (beside && !(rest_launch && rest_beside)) HIP_TRY(hipStreamWaitEvent(sw, c->ev_fork, 0));
         const unsigned gwd = c->lists_known ? std::max(c->n_wide_tiles, 1u) : (unsigned)std::max<int64_t>(c->n_tiles, 1);
         with_level(p.full_level, [&](auto L) { with_flag(p.ss_dis > 0, [&](auto D) {
             hipLaunchKernelGGL(HIP_KERNEL_NAME(k_tile<L, false, D, true>), dim3(gwd), dim3(TILE_THREADS), 0, sw, sa, (const TileRec *)c->tile_rec.p, (const TileWin *)c->tw.p,
@@ -1321,14 +1376,14 @@ static int launch_tile(l2r_ctx *c, hipEvent_t *ev, const DevParams &p, const Sla
         launch_tile_chunk(c, p, sa, gcd, 0u, c->side[1]);
         HIP_TRY(hipEventRecord(c->ev_join[1], c->side[1]));
     }
-    const unsigned gf = fused_grid(c->n_tiles);
-    with_level(p.full_level, [&](auto L) { with_flag(p.ss_dis > 0, [&](auto D) { with_flag(c->want & L2R_WANT_ACCEPTED, [&](auto A) {
-        // (k_tile decides acceptance itself, junction table or not)
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_tile<L, A, D>), dim3(gf), dim3(TILE_THREADS), 0, s, sa, (const TileRec *)c->tile_rec.p, (const TileWin *)c->tw.p,
+    if (!split) launch_general(gf, s);
+    else with_level(p.full_level, [&](auto L) { with_flag(p.ss_dis > 0, [&](auto D) { with_flag(c->want & L2R_WANT_ACCEPTED, [&](auto A) {
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_tile<L, A, D, false, true>), dim3(gf), dim3(TILE_THREADS), 0, s, sa, (const TileRec *)c->tile_rec.p, (const TileWin *)c->tw.p,
                            (const TileStat *)c->tile_stat.p, (const SlotRec *)c->slot_rec.p, c->tile_xbase.p);
     }); }); });
     MARK(ST_FAST);
     if (chunk_launch && !beside) launch_tile_chunk(c, p, sa, gcd, 0u, s);
+    if (rest_launch && rest_beside && !wide_launch) HIP_TRY(hipStreamWaitEvent(s, c->ev_join[0], 0));
     if (wide_launch && beside) HIP_TRY(hipStreamWaitEvent(s, c->ev_join[0], 0));
     if (chunk_launch && beside) HIP_TRY(hipStreamWaitEvent(s, c->ev_join[1], 0));
     const unsigned gl = (unsigned)std::min<int64_t>(c->n_tiles ? c->n_tiles : 1, (int64_t)c->n_cu * 2);
@@ -1499,7 +1554,7 @@ int l2r_debug_counters(l2r_ctx *c, long long *out, int n)
     out[0] = redo; out[1] = c->n_wide; out[2] = c->n_compact; out[3] = c->n_tiles;
     if (n >= 12) for (int k = 0; k < 8; ++k) out[4 + k] = 0;
     if (n >= 13) out[12] = 0;
-    for (int k = 16; k < std::min(n, 27); ++k) out[k] = 0;         // (the descriptor words below: 0 where no run left descriptors)
+    for (int k = 16; k < std::min(n, 29); ++k) out[k] = 0;         // (the descriptor words below: 0 where no run left descriptors)
     if (n >= 14) out[13] = c->n_lb_fallback;              // runs done again on the slab pipeline because k_tile's look-back starved
     if (n >= 16) {                                        // one-kernel tile path, last run: entries of chunk_list k_tile_chunk declined, tiles handed to the chunked kernel late
         out[14] = 0; out[15] = 0;
@@ -1508,6 +1563,7 @@ int l2r_debug_counters(l2r_ctx *c, long long *out, int n)
             HIP_TRY(hipMemcpyAsync(lc, c->list_cnt.p + 16 * ((c->lc_flip & 1u) ^ 1u), sizeof lc, hipMemcpyDeviceToHost, c->stream));
             HIP_TRY(hipStreamSynchronize(c->stream));
             out[14] = lc[9]; out[15] = lc[8];
+            if (n >= 29) out[28] = lc[11];              // entries of the rest list: the tiles k_tile's general instance ran over beside the EXACT one (0: split off)
         }
     }
     if (n >= 12 && c->pipe != Pipeline::classic && c->ran && c->tw.p && c->n_tiles > 0) {     // slab pipeline: the descriptors k_walk_slab made (flags as the probe kernels left them)
@@ -1518,6 +1574,7 @@ int l2r_debug_counters(l2r_ctx *c, long long *out, int n)
             if (n >= 27) {                                  // largest dictionary slices of any tile, tiles k_tile_chunk took (k_describe_scan<true>)
                 out[24] = std::max<long long>(out[24], t.d.st_nk); out[25] = std::max<long long>(out[25], t.d.en_nk);
                 if (t.d.flags & TD_CDIRECT) out[26]++;
+                if (n >= 29 && c->pipe == Pipeline::tile && (t.d.flags & TD_XDIRECT)) out[27]++;      // tiles k_tile's EXACT instance took
             }
             if (n >= 24) {                                  // tiles of the chunked kernel by the END entries of their dictionary slices (<= 256, 512, 768, 1024, more), START entries beyond 128 / 256, all of them
                 const uint32_t why = (t.d.flags >> 8) & 7u;
@@ -1608,6 +1665,7 @@ int l2r_sync(l2r_ctx *c)
         c->lists_heavy = 2ull * ((unsigned long long)lc[4] + (c->wide_direct ? lc[5] : lc[6]) + chunk_rest) > (unsigned long long)c->n_tiles;
         c->n_wide_tiles = lc[6]; c->wide_rest_empty = lc[5] == 0u; c->fb_empty = lc[4] == 0u;
         c->n_chunk_tiles = lc[7]; c->chunk_rest_empty = chunk_rest == 0ull;
+        c->n_rest_tiles = lc[11];
         c->redo_empty = redo_n == 0u;
         c->lists_known = true;
     }

@@ -131,7 +131,16 @@ struct SlabArgs {
     uint32_t chunk_direct_on;                            // ... and k_tile_chunk (l2r_tchunk.hip.h) the exact tiles of the chunked kernel
     uint32_t wide_direct_on;                             // one-kernel tile path: k_tile's WIDE instance takes the exact 64-bit-mask tiles straight from their CIGARs
     uint32_t *exon_total;                                // the run's exon count (k_tile: written by the last tile)
+    // one-kernel tile path, the split of k_tile: k_describe_scan<true> marks the tiles the EXACT instance takes whole (TD_XDIRECT,
+    // tile_exact_direct below) and lists every other tile on rest_list (list_cnt[11] entries, in no particular order; the count is
+    // cleared a run ahead like words 0, 1), over which the general instance runs, one workgroup per entry.  split_on SPLIT_OFF (L2R_TILE_SPLIT=0):
+    // no tile is marked, nothing is listed, the general instance takes every tile by its workgroup number as before the split.
+    // split_on SPLIT_LIST: the rest list is made (its length is what the host wants to know) but no tile is marked -- the general
+    // instance takes every tile by its workgroup number, in tile order, as with SPLIT_OFF.
+    uint32_t *rest_list;
+    uint32_t split_on;                                   // SPLIT_*
 };
+constexpr uint32_t SPLIT_OFF = 0u, SPLIT_ON = 1u, SPLIT_LIST = 2u;
 typedef const __attribute__((address_space(4))) SlabArgs *SlabArgsK;
 __device__ __forceinline__ SlabArgsK slab_args()
 {
@@ -632,6 +641,7 @@ void k_walk_slab_long(SlabArgs kernarg_block, const TileRec *__restrict__ u_rec)
 //       those kernels' lists with ONE reservation per workgroup and list (no particular order; list_cnt is cleared by k_walk_slab).
 __device__ __forceinline__ bool tile_chunk_direct(uint32_t on, uint32_t flags, uint32_t chunk_on, const TileDesc &d, const TileStat &st, uint32_t n_act,
                                                   int min_exon, int min_intron, int max_delet, int dis, int ablate, bool late = false);      // (below, beside tile_wide_direct)
+__device__ __forceinline__ bool tile_exact_direct(uint32_t on, uint32_t flags, uint32_t has_wide_keys, const TileStat &st, uint32_t n_act, int min_exon, int min_intron, int max_delet, int ablate);
 typedef SegScan DescribeScan;
 constexpr int DESCRIBE_G = 16;                           // lanes per tile
 constexpr int DESCRIBE_TILES = TILE_THREADS / DESCRIBE_G;       // tiles per workgroup
@@ -671,7 +681,7 @@ void k_describe_scan(SlabArgs kernarg_block, DescribeScan job, uint32_t n_scan, 
         *sa->exon_total = 0u;                            // (k_tile's last tile writes the run's exon count: an upload without reads has none)
         uint32_t *const lc = sa->list_cnt;
         lc[2] = 0u; lc[3] = 0u; lc[4] = 0u; lc[5] = 0u; lc[8] = 0u; lc[9] = 0u; lc[10] = 0u;
-        if (sa->list_cnt_next) { sa->list_cnt_next[0] = 0u; sa->list_cnt_next[1] = 0u; }      // (the next run's entry counts: k_describe_scan appends to them from its first workgroup on)
+        if (sa->list_cnt_next) { sa->list_cnt_next[0] = 0u; sa->list_cnt_next[1] = 0u; sa->list_cnt_next[11] = 0u; }      // (the next run's entry counts: k_describe_scan appends to them from its first workgroup on)
     }
     if (FIRST && blockIdx.x == 0) for (uint32_t i = threadIdx.x; i < sa->n_sup; i += TILE_THREADS) sa->lb_sup_next[i] = 0ull;      // (the next run's super-block words)
     if (t < sa->n_tiles) {
@@ -708,7 +718,15 @@ void k_describe_scan(SlabArgs kernarg_block, DescribeScan job, uint32_t n_scan, 
                 sa->tw[t].d.flags = flags;
             }
         }
+        // (... or the EXACT instance's, whole?  The same way: every tile without the bit goes onto the rest list below)
+        // (SPLIT_LIST: the verdict only makes the rest list, the descriptor stays unmarked and the general instance takes every tile)
+        const bool xdirect = FIRST && gl == 0 && tile_exact_direct(sa->split_on, flags, sa->has_wide_keys, st_first, n_act_first, a->f.p.min_exon, a->f.p.min_intron, a->f.p.max_delet, a->f.p.ablate);
+        if (xdirect && sa->split_on == SPLIT_ON) {
+            flags |= TD_XDIRECT;
+            sa->tw[t].d.flags = flags;
+        }
         if (gl == 0) sa->tile_flags[t] = flags;
+        if (xdirect) flags |= TD_XDIRECT;                    // (SPLIT_LIST: for the rest list below only)
         // (accepted list: every tile's chunk is k_gather_accepted's until a probe kernel has left it itself)
         if (gl == 0 && (a->f.p.want & WANT_ACCEPTED)) a->f.tile_chunk[t] = CHUNK_DEFERRED;
     }
@@ -740,14 +758,20 @@ void k_describe_scan(SlabArgs kernarg_block, DescribeScan job, uint32_t n_scan, 
         const uint32_t f = lane < DESCRIBE_TILES ? s_flags[lane] : TD_FAST;
         const uint32_t tl = t0 + (uint32_t)lane;
         const bool is_w = (f & TD_WIDE) != 0u, is_c = sa->chunk_on && slab_tile_is_chunked(f);
-        const unsigned long long mw = __ballot(is_w), mc = __ballot(is_c);
-        if (mw | mc) {
-            uint32_t bw = 0u, bc = 0u;
-            if (lane == 0) { if (mw) bw = atomicAdd(sa->list_cnt + 0, (uint32_t)__popcll(mw)); if (mc) bc = atomicAdd(sa->list_cnt + 1, (uint32_t)__popcll(mc)); }
-            bw = (uint32_t)__builtin_amdgcn_readfirstlane((int)bw); bc = (uint32_t)__builtin_amdgcn_readfirstlane((int)bc);
+        // (the split of k_tile: every tile the EXACT instance does not take -- the general instance's, whatever becomes of it there)
+        const bool is_r = FIRST && sa->split_on != 0u && lane < DESCRIBE_TILES && tl < sa->n_tiles && (f & TD_XDIRECT) == 0u;
+        const unsigned long long mw = __ballot(is_w), mc = __ballot(is_c), mr = __ballot(is_r);
+        if (mw | mc | mr) {
+            uint32_t bw = 0u, bc = 0u, br = 0u;
+            if (lane == 0) {
+                if (mw) bw = atomicAdd(sa->list_cnt + 0, (uint32_t)__popcll(mw)); if (mc) bc = atomicAdd(sa->list_cnt + 1, (uint32_t)__popcll(mc));
+                if (mr) br = atomicAdd(sa->list_cnt + 11, (uint32_t)__popcll(mr));
+            }
+            bw = (uint32_t)__builtin_amdgcn_readfirstlane((int)bw); bc = (uint32_t)__builtin_amdgcn_readfirstlane((int)bc); br = (uint32_t)__builtin_amdgcn_readfirstlane((int)br);
             const unsigned long long below = (1ull << lane) - 1ull;
             if (is_w) sa->wide_list[bw + (uint32_t)__popcll(mw & below)] = tl;
             if (is_c) sa->chunk_list[bc + (uint32_t)__popcll(mc & below)] = tl;
+            if (is_r) sa->rest_list[br + (uint32_t)__popcll(mr & below)] = tl;
         }
     }
 }
@@ -800,6 +824,24 @@ __device__ __forceinline__ bool tile_chunk_direct(uint32_t on, uint32_t flags, u
            // (strict for both: the slot behind a dictionary's entries -- the masks of "no entry", tc_lookup2 / tc_map_exons -- is entry
            // number st_nk / en_nk and has to fit the 9-bit first-part field of a lookup half word; 512 would read as entry 0, one part)
            tile_exact(st, min_exon, min_intron, max_delet) && !(ablate & 256) && n_act + (uint32_t)st.n_ops_n <= (uint32_t)TILE_POS_CAP;
+}
+
+// The tile is taken WHOLE by k_tile's EXACT instance (l2r_tile.hip.h), which has no count walk, no scan of counts, no late decision and no
+// slab form compiled in -- so the verdict has to rule out every way into those, and it can, before any CIGAR is walked:
+//   - TD_FAST: a window of at most 32 members and dictionary slices within the staging's caps.  TD_WIDE and the chunked tiles (no
+//     TD_FAST: the WIDE instance's, k_tile_chunk's -- TD_CDIRECT needs a chunked tile -- or slab-bound, `pre_slab`) are out; TD_CHUNK
+//     is only ever set by a kernel behind this launch, on a tile that staged a key in several entries (next item);
+//   - exact under this run's -e / -i / -t with L2R_ABLATE bit 8 off: the reads' places are their slot records' `loc`, the tile's exon
+//     count n_act + n_ops_n is what k_describe_scan has published: nothing to count, to scan or to publish late.  k_tile_index has
+//     made a tile with a read of 255 exons or more, or with places beyond SLOT_LOC_LIMIT, inexact for every threshold (min_seg =
+//     INT32_MIN; the host does the same for the summaries): neither arises in an exact tile, so bit 0 of the late decision is never set;
+//   - n_act + n_ops_n <= TILE_POS_CAP: the staged positions hold every exon (the late decision's `total > TILE_POS_CAP`);
+//   - the annotation has no dictionary key in several entries at all (has_wide_keys 0): no tile stages one, so the waves have no
+//     flag to meet over (bit 1 of the late decision, `any_wide`) -- an annotation with such keys keeps every tile in the general instance.
+__device__ __forceinline__ bool tile_exact_direct(uint32_t on, uint32_t flags, uint32_t has_wide_keys, const TileStat &st, uint32_t n_act, int min_exon, int min_intron, int max_delet, int ablate)
+{
+    return on != 0u && has_wide_keys == 0u && (flags & (TD_FAST | TD_WIDE | TD_CHUNK | TD_CDIRECT)) == TD_FAST && tile_exact(st, min_exon, min_intron, max_delet) && !(ablate & 256) &&
+           n_act + (uint32_t)st.n_ops_n <= (uint32_t)TILE_POS_CAP;
 }
 
 constexpr uint32_t SLAB_POS_SKIP = 0xffffffffu;          // A of a position that was written directly (a staged start is below 2^18 - 1)

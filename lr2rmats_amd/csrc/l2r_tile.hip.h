@@ -34,6 +34,24 @@
 //                           hold (only outliers make such tiles).  For those the workgroup runs k_walk_slab's tile body instead
 //                           (slab_walk_tile: slab rows, reads' words, span record) and lists the tile for k_probe_slab (fb_list).
 //
+//   k_tile<..., EXACT>      THE instance nearly every tile runs in: the tiles k_describe_scan has marked TD_XDIRECT (tile_exact_direct,
+//                           l2r_slab.hip.h: exact, a window of at most 32 members, every exon fits the staged positions, no key in
+//                           several entries anywhere).  Only what such a tile executes is compiled in: the front, the exact place walk,
+//                           classification, the -j check, the accepted chunk, the looks at the counts in front, `big` reads and CIGAR
+//                           tails.  No count walk, no scan of counts, no meeting of the waves over flags, nothing to publish, no general
+//                           place walk, no late decision, no slab form.  One workgroup per tile number (fused_tile); it returns at
+//                           once for a tile without the mark.
+//   k_tile<...>             the general instance = the whole body, over the REST list k_describe_scan made (every tile without the mark),
+//                           one workgroup per entry.  Where it runs follows from who may wait for whom (l2r_engine.hip, split_mode):
+//                           in a run with inexact tiles it is their only publisher, so it is launched on the main stream IN FRONT of
+//                           the EXACT instance, and only once a completed run has shown the list short enough for all its tiles
+//                           to be resident together (the list is not in tile order); the first run of such an upload only makes
+//                           the list (SPLIT_LIST) and this instance takes every tile by workgroup number.  In a run without
+//                           inexact tiles nobody waits: the split is on at once and this instance runs beside the EXACT one, on the
+//                           WIDE instance's stream in front of it (the WIDE instance starts when it has ended).  With the split
+//                           off (L2R_TILE_SPLIT=0, or a rest list beyond 4 entries per CU) nothing is marked or listed and this
+//                           instance takes every tile by workgroup number.
+//
 // -e < 1 and long CIGARs keep the two-kernel path (l2r_slab.hip.h).
 #pragma once
 #include <type_traits>
@@ -542,11 +560,14 @@ static_assert(SLAB_AUX_BYTES >= (SJ_STAGE / 32 + 2 * 4 + 2) * 4 && SLAB_AUX_BYTE
 // WIDE: the instance for the tiles of the 64-bit-mask kernel that tile_wide_direct (l2r_slab.hip.h) names -- launched behind the plain
 // instance over wide_list (one workgroup per entry): the same tile, with 64-bit masks, 24-byte entries, a 63-member window record, at 5
 // workgroups per CU.  The plain instance returns at once for those tiles instead of giving them the slab form.
-template <int LEVEL, bool ACC, bool DIS, bool WIDE = false>
+// EXACT: the instance for the tiles k_describe_scan has marked TD_XDIRECT (see the head of this file); everything a tile of another
+// kind needs is compiled out of it.
+template <int LEVEL, bool ACC, bool DIS, bool WIDE = false, bool EXACT = false>
 __global__ __launch_bounds__(TILE_THREADS, WIDE ? L2R_WIDE_WGS : 7)
 void k_tile(SlabArgs kernarg_block, const TileRec *__restrict__ u_rec, const TileWin *__restrict__ u_tw, const TileStat *__restrict__ u_stat, const SlotRec *__restrict__ u_slot,
             uint32_t *__restrict__ u_xbase)
 {
+    static_assert(!(WIDE && EXACT), "the EXACT instance is a plain one");
     constexpr int DIR_BYTES = FAST_DIR_BYTES;
     using WinT = typename std::conditional<WIDE, TileWin64, TileWin>::type;
     using EntT = typename std::conditional<WIDE, WEnt, v4i_t>::type;
@@ -570,6 +591,7 @@ void k_tile(SlabArgs kernarg_block, const TileRec *__restrict__ u_rec, const Til
     const int lane = threadIdx.x & (WAVE - 1), wv = threadIdx.x >> 6;
     uint32_t t;
     if (WIDE) { if (blockIdx.x >= sa->list_cnt[0]) return; t = sa->wide_list[blockIdx.x]; }
+    else if (!EXACT && sa->split_on == SPLIT_ON) { if (blockIdx.x >= sa->list_cnt[11]) return; t = sa->rest_list[blockIdx.x]; }
     else { t = fused_tile(blockIdx.x); if (t >= sa->n_tiles) return; }
     // diagnostics (L2R_STAMPS=1), wave 0: [0] records, CIGAR heads asked for, staging  [1] (count walk + barrier)  [6] scan, count
     // published, place walk  [2] window pass  [3] probe rounds  [4] verdicts  [7] the tile's first slot (exon counts in front)  [5] write-out
@@ -590,17 +612,23 @@ void k_tile(SlabArgs kernarg_block, const TileRec *__restrict__ u_rec, const Til
     const TileStat tst = u_stat[t];
     const uint32_t chunk_on = sa->chunk_on; const int32_t ablate = a->f.p.ablate;
     const uint32_t n_tiles = sa->n_tiles;
+    if constexpr (EXACT)      // (of the statistics only the N operations, of the record no slab)
+        asm volatile("" :: "s"(tst.n_ops_n), "s"(ablate), "s"(n_tiles), "s"(rec.r0), "s"(rec.n_act), "s"(rec.tid0), "s"(rec.lo),
+                           "s"(d0.j_lo), "s"(d0.b_off), "s"(d0.nb), "s"(d0.b0), "s"(d0.nbk), "s"(d0.st_r0), "s"(d0.st_nk), "s"(d0.en_r0), "s"(d0.en_nk), "s"(d0.flags), "s"(d0.n_win));
+    else
     asm volatile("" :: "s"(tst.n_ops_n), "s"(tst.min_n), "s"(tst.max_d), "s"(tst.min_seg), "s"(chunk_on), "s"(ablate), "s"(n_tiles), "s"(rec.r0), "s"(rec.n_act), "s"(rec.sbase), "s"(rec.rows), "s"(rec.tid0), "s"(rec.lo),
                        "s"(d0.j_lo), "s"(d0.b_off), "s"(d0.nb), "s"(d0.b0), "s"(d0.nbk), "s"(d0.st_r0), "s"(d0.st_nk), "s"(d0.en_r0), "s"(d0.en_nk), "s"(d0.flags), "s"(d0.n_win));
+    // the EXACT instance's tiles carry k_describe_scan's mark (every other tile is on the general instance's list)
+    if (EXACT && (d0.flags & TD_XDIRECT) == 0u) return;
     const uint32_t r0 = rec.r0, n_act = rec.n_act;
     const int32_t tid0 = rec.tid0, pos0 = rec.lo - 1;
     const int32_t tile_lo = rec.lo;                              // the base of the tile's row words: its first read's first base
     // a tile of the 64-bit-mask or the chunked kernel (on their lists since k_describe_scan): slab form, nothing is staged here
-    const bool pre_slab = !WIDE && ((d0.flags & TD_WIDE) != 0u || (chunk_on && slab_tile_is_chunked(d0.flags)));
+    const bool pre_slab = !WIDE && !EXACT && ((d0.flags & TD_WIDE) != 0u || (chunk_on && slab_tile_is_chunked(d0.flags)));
     // The tile is EXACT: no threshold is borderline in it, so a read's exon count is 1 + its N operations (the upload's read_n) and
     // the tile's count is known to the later tiles since k_describe_scan -- no count walk, nothing to publish.
-    const bool counted = tile_exact(tst, a->f.p.min_exon, a->f.p.min_intron, a->f.p.max_delet) && !(ablate & 256);
-    {   // (a wide tile that the WIDE instance takes whole, behind this launch: nothing of it happens in the plain one -- and the other way round)
+    const bool counted = EXACT || (tile_exact(tst, a->f.p.min_exon, a->f.p.min_intron, a->f.p.max_delet) && !(ablate & 256));
+    if constexpr (!EXACT) {   // (a wide tile that the WIDE instance takes whole, behind this launch: nothing of it happens in the plain one -- and the other way round)
         const bool direct = tile_wide_direct(sa->wide_direct_on, d0.flags, chunk_on, tst, n_act, a->f.p.min_exon, a->f.p.min_intron, a->f.p.max_delet, ablate);
         if (WIDE ? !direct : direct) return;
         // (... or k_tile_chunk, l2r_tchunk.hip.h: an exact tile of the chunked kernel)
@@ -652,6 +680,7 @@ void k_tile(SlabArgs kernarg_block, const TileRec *__restrict__ u_rec, const Til
     if (!pre_slab && (int)threadIdx.x < (WIDE ? WIDE_TW_VECS : SLAB_TW_VECS)) reinterpret_cast<int4 *>(&s_tw)[threadIdx.x] = twv;
     int my_wide = 0;
     if constexpr (WIDE) wide_stage_dict(d, dv, reinterpret_cast<const int *>(sa->tw64[t].win), s_ent0, s_ent1, s_dir0, s_dir1, s_rdir);
+    else if (EXACT) (void)slab_stage_dict(d, dv, reinterpret_cast<const int *>(u_tw[t].win), SlabLds{nullptr, s_ent0, s_ent1, s_dir0, s_dir1, s_rdir});      // (no key in several entries anywhere: tile_exact_direct)
     else if (!pre_slab) my_wide = slab_stage_dict(d, dv, reinterpret_cast<const int *>(u_tw[t].win), SlabLds{nullptr, s_ent0, s_ent1, s_dir0, s_dir1, s_rdir});
     stamp.mark(0);
     // (a vector is fetched if its first word is the read's: only the three behind it can be another read's.  The WIDE instance keeps
@@ -667,7 +696,8 @@ void k_tile(SlabArgs kernarg_block, const TileRec *__restrict__ u_rec, const Til
     //      annotation has dictionary keys in several entries (rare: a site shared by transcripts more than 64 apart): whether this
     //      tile staged one is every wave's business.
     uint32_t n = 0u;
-    const bool meet = !WIDE && !pre_slab && (!counted || sa->has_wide_keys != 0u);       // (else the waves meet behind the place walk: the staged slices must be whole before the probes)
+    const bool meet = !WIDE && !EXACT && !pre_slab && (!counted || sa->has_wide_keys != 0u);       // (else the waves meet behind the place walk: the staged slices must be whole before the probes)
+    if constexpr (!EXACT) {
     if (!pre_slab && !counted) {
         if (active) {
             int start = pos + 1, end = pos;
@@ -700,11 +730,13 @@ void k_tile(SlabArgs kernarg_block, const TileRec *__restrict__ u_rec, const Til
         if (lane == 0) s_flagw[wv] = fw;
         __syncthreads();
     }
+    }
     stamp.mark(1);
     uint32_t total = 0u, loc = 0u;
     bool late_slab = false, wide_key = false;
     int any_wide = 0;
-    if (!pre_slab) {
+    if constexpr (EXACT) { total = n_act + (uint32_t)tst.n_ops_n; loc = (xs >> SLOT_LOC_SHIFT) & (SLOT_LOC_LIMIT - 1u); }
+    else if (!pre_slab) {
         if (counted) { total = n_act + (uint32_t)tst.n_ops_n; loc = (xs >> SLOT_LOC_SHIFT) & (SLOT_LOC_LIMIT - 1u); }
         else {
             // each wave scans the 256 counts (four per lane) for itself
@@ -728,14 +760,14 @@ void k_tile(SlabArgs kernarg_block, const TileRec *__restrict__ u_rec, const Til
     auto staged_form = [&]() {
     // ---- the tile's exon count is known: published for every later tile's first slot
     // (L2R_ABLATE bit 15, tests: tile 3 never publishes its count -- the tiles behind it wait in vain, the engine falls back to the slab pipeline)
-    if (threadIdx.x == 0 && !counted && !(ablate & 128) && !((ablate & 32768) && t == 3u)) lb_publish(sa, t, total);
+    if constexpr (!EXACT) if (threadIdx.x == 0 && !counted && !(ablate & 128) && !((ablate & 32768) && t == 3u)) lb_publish(sa, t, total);
     const uint32_t clk1 = stamp.p ? (uint32_t)__builtin_amdgcn_s_memrealtime() : 0u;
     // ---- second walk: PLACE the exons as row words at their positions in LDS
     const SlabStage st{s_A, s_L, loc, tile_lo, true};
     ReadEnds re{0, 0, 0, 0};
     bool sane = true, big = false;
     n = 0u;
-    if (active && L2R_TILE_EXACT_WALK && counted) {
+    if (active && (EXACT || (L2R_TILE_EXACT_WALK && counted))) {
         // EXACT (uniform over the workgroup): every N cuts and keeps, nothing else does -- no thresholds, no `first`.  The exon under way
         // is {rel, xl}: its start relative to the tile's first base and its length so far.
         uint32_t *const Ap = s_A + loc;
@@ -768,7 +800,7 @@ void k_tile(SlabArgs kernarg_block, const TileRec *__restrict__ u_rec, const Til
         sane = x0 >= 1u && xl >= 1u;
         const int start = tile_lo + (int)rel;
         re = ReadEnds{pos + 1, pos + (int)x0, start, start + (int)xl - 1};
-    } else if (active) {
+    } else if constexpr (!EXACT) if (active) {
         uint32_t *const Ap = s_A + loc;
         int start = pos + 1, end = pos;
         int s0 = 0, e0 = 0;
@@ -1062,8 +1094,8 @@ void k_tile(SlabArgs kernarg_block, const TileRec *__restrict__ u_rec, const Til
     };
     // (For its register allocation the compiler lays the two forms of a tile out one behind the other -- "the staged form, then, if a flag
     //  says so, the slab form" -- whatever the order here: what the slab form needs is alive through the staged form's probe rounds.)
-    if (WIDE || !(pre_slab || late_slab)) { staged_form(); return; }
-    if constexpr (!WIDE) {
+    if (WIDE || EXACT || !(pre_slab || late_slab)) { staged_form(); return; }
+    if constexpr (!WIDE && !EXACT) {
     // ---- the tile keeps the slab form: k_walk_slab's body on the CIGAR registers (its LDS words behind the sort's arrays, which a
     //      slower wave may still be reading), then the tile's first slot and the list of the kernel that takes it
     // (the thread's slot once more, from a tile number the compiler cannot recognise: kept from above it would be spilled through the staged form)
