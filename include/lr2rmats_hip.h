@@ -305,6 +305,48 @@ int          l2r_filter_score(l2r_ctx *ctx, const l2r_filter_records *recs, cons
 int          l2r_filter_select(l2r_ctx *ctx, int64_t n_groups, const int64_t *group_off, const int32_t *score,
                                const int32_t *intron_n, const l2r_filter_params *prm, int64_t *winner);
 
+/* ---- `bam2sj` (src/parse_bam.c:896-924 bam2sj_core): the junction table of an alignment file -- one row per distinct
+ * (tid, don, acc) in that order, with how many uniquely / multiply mapped records carry it, its intron motif and strand.
+ * Replaces gen_sj() :402-442 per record, the list search and insertion of sj_sch_group() / sj_update_group() :339-380 (a device
+ * radix sort + a segmented sum: the list of the reference equals that order wherever the records' tids never decrease) and
+ * intr_deri_str() :319-337.  Reading the records and the FASTA and printing the table stay with the caller (host/sj.c).
+ * A short-read file does not fit one upload, so the records come in batches:
+ *     l2r_sj_begin  once: parameters, the genome (NULL: no -g; motif and strand are 0 then) -- copied to HBM as bytes
+ *     l2r_sj_add    a batch of records, any number of times: record filter (FLAG & 4 skipped; pair_only: without FLAG & 2 skipped),
+ *                   CIGAR walk (an N of at least min_intron bases is a row {tid, don = first, acc = last intron base, uniq, 1 - uniq}),
+ *                   rows appended in record order; the rows so far are sorted and reduced whenever they exceed a bound
+ *     l2r_sj_add_rows  rows that are counted already (a table made earlier, or another file's): the count COLUMNS are summed,
+ *                   so tables merge by the same sort + reduce
+ *     l2r_sj_finish sorts and reduces all rows, looks up the motifs; *n_rows = rows of the table.  A row on a sequence the genome
+ *                   does not have (tid >= n_seq): L2R_SJ_E_UNKNOWN_TID, l2r_last_error() names the tid (the reference: err_fatal)
+ *     l2r_sj_download  the table; its first five columns have the layout of l2r_junctions (l2r_set_junctions takes them as they are)
+ * The result does not depend on how the records were cut into batches.  The sort is stable and the rows are made in record
+ * order, so every intermediate order is the same run after run. */
+#define L2R_SJ_SORT_TILE 4096           /* rows one workgroup of a radix pass ranks (csrc/l2r_sj.hip.h) */
+#define L2R_SJ_E_UNKNOWN_TID (-3)
+typedef struct { int32_t min_intron, pair_only; } l2r_sj_params;         /* -i INTRON_MIN_LEN 3; read_type PAIR_T: 1 */
+typedef struct { int32_t n_seq; const int64_t *seq_off /* n_seq + 1 */; const uint8_t *bases; } l2r_sj_genome;   /* sequences in FILE order */
+typedef struct {
+    int64_t n, n_cigar;
+    const uint16_t *flag;
+    const int32_t *tid, *pos;           /* core.tid, core.pos (0-based) */
+    const uint8_t *uniq;                /* NH tag present and bam_aux2i(NH) == 1 */
+    const int64_t *cig_off;             /* n + 1 */
+    const uint32_t *cig;                /* len << 4 | op */
+} l2r_sj_records;
+typedef struct { int64_t cap, n; int32_t *tid, *don, *acc, *uniq_c, *multi_c; uint8_t *strand, *motif; } l2r_sj_table;   /* in: cap; out: n */
+int          l2r_sj_begin(l2r_ctx *ctx, const l2r_sj_params *prm, const l2r_sj_genome *genome);
+int          l2r_sj_add(l2r_ctx *ctx, const l2r_sj_records *recs);
+int          l2r_sj_add_rows(l2r_ctx *ctx, const l2r_junctions *rows);
+int          l2r_sj_finish(l2r_ctx *ctx, int64_t *n_rows);
+int          l2r_sj_download(l2r_ctx *ctx, l2r_sj_table *table);
+/* diagnostics (tools/bench_sj.py, tests): out[0] rows made by l2r_sj_add / _add_rows since l2r_sj_begin, [1] sort + reduce rounds,
+ * [2] radix passes the last round ran (of 12), [3] rows that went into it, [4] rows it left; with L2R_SJ_TIMING=1 in the environment
+ * at l2r_sj_begin (every launch is then waited for), device milliseconds summed since then: [5] k_sj_count [6] k_scan_u32 of the
+ * counts [7] k_sj_fill [8] k_sj_hist12 [9] k_sj_digit_hist [10] k_scan_u32 of the tile histograms [11] k_sj_scatter [12] k_sj_heads +
+ * its scan [13] k_sj_reduce [14] k_sj_motif; n = words of out (up to 15) */
+int          l2r_sj_stats(l2r_ctx *ctx, double *out, int n);
+
 #ifdef __cplusplus
 }
 #endif

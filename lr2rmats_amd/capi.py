@@ -31,7 +31,9 @@ EXPORTS = [
     "l2r_stage_kernel", "l2r_set_annotation_cache", "l2r_annotation_cache_state", "l2r_filter_score", "l2r_filter_select",
     "l2r_debug_counters", "l2r_debug_stamps", "l2r_debug_tile_times", "l2r_upload_index_ms", "l2r_hint_single_run",
     "l2r_xchg_id_bytes", "l2r_xchg_unique_id", "l2r_xchg_create", "l2r_xchg_gather_results", "l2r_xchg_gather_accepted", "l2r_xchg_destroy",
+    "l2r_sj_begin", "l2r_sj_add", "l2r_sj_add_rows", "l2r_sj_finish", "l2r_sj_download", "l2r_sj_stats",
 ]
+SJ_E_UNKNOWN_TID = -3
 
 _i32p, _i64p, _u8p, _u32p = C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.POINTER(C.c_uint8), C.POINTER(C.c_uint32)
 
@@ -84,6 +86,24 @@ class CFilterRecords(C.Structure):
 
 class CFilterSpans(C.Structure):
     _fields_ = [("n", C.c_int64), ("tid", C.c_void_p), ("start", C.c_void_p), ("end", C.c_void_p)]
+
+
+class CSjParams(C.Structure):
+    _fields_ = [("min_intron", C.c_int32), ("pair_only", C.c_int32)]
+
+
+class CSjGenome(C.Structure):
+    _fields_ = [("n_seq", C.c_int32), ("seq_off", C.c_void_p), ("bases", C.c_void_p)]
+
+
+class CSjRecords(C.Structure):
+    _fields_ = [("n", C.c_int64), ("n_cigar", C.c_int64), ("flag", C.c_void_p), ("tid", C.c_void_p), ("pos", C.c_void_p),
+                ("uniq", C.c_void_p), ("cig_off", C.c_void_p), ("cig", C.c_void_p)]
+
+
+class CSjTable(C.Structure):
+    _fields_ = [("cap", C.c_int64), ("n", C.c_int64), ("tid", C.c_void_p), ("don", C.c_void_p), ("acc", C.c_void_p),
+                ("uniq_c", C.c_void_p), ("multi_c", C.c_void_p), ("strand", C.c_void_p), ("motif", C.c_void_p)]
 
 
 class CTiming(C.Structure):
@@ -145,6 +165,10 @@ def load_library():
         lib.l2r_upload_index_ms.argtypes = [C.c_void_p]
         lib.l2r_stage_kernel.restype = C.c_char_p
         lib.l2r_stage_kernel.argtypes = [C.c_void_p, C.c_int]
+        for name in ("l2r_sj_add", "l2r_sj_add_rows", "l2r_sj_finish", "l2r_sj_download"):
+            getattr(lib, name).argtypes = [C.c_void_p, C.c_void_p]
+        lib.l2r_sj_begin.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        lib.l2r_sj_stats.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
         _lib = lib
     return _lib
 
@@ -165,6 +189,22 @@ class Result:
     ex_flag: np.ndarray
     info: np.ndarray
     ref_tx: np.ndarray
+
+
+@dataclass
+class SjTable:
+    """The junction table of ``bam2sj``: sorted by (tid, don, acc), one row per junction."""
+    tid: np.ndarray
+    don: np.ndarray
+    acc: np.ndarray
+    uniq_c: np.ndarray
+    multi_c: np.ndarray
+    strand: np.ndarray
+    motif: np.ndarray
+
+
+SJ_STAT_NAMES = ["rows_made", "rounds", "radix_passes", "rows_in", "rows_out", "k_sj_count", "k_scan_u32 (counts)", "k_sj_fill", "k_sj_hist12",
+                 "k_sj_digit_hist", "k_scan_u32 (tile histograms)", "k_sj_scatter", "k_sj_heads + scan", "k_sj_reduce", "k_sj_motif"]
 
 
 @dataclass
@@ -252,6 +292,46 @@ class Engine:
         win = np.zeros(max(ng, 1), np.int64)
         self._chk(self.lib.l2r_filter_select(self.ctx, ng, g.ctypes.data, s.ctypes.data, i.ctypes.data, C.byref(prm), win.ctypes.data))
         return win[:ng]
+
+    # ---- `bam2sj` (include/lr2rmats_hip.h: l2r_sj_begin / _add / _add_rows / _finish / _download)
+    def sj_begin(self, min_intron: int = 3, pair_only: bool = True, genome=None):
+        """``genome``: (seq_off [n_seq + 1] int64, bases uint8) with the sequences in file order, or None (no -g)."""
+        prm = CSjParams(min_intron, 1 if pair_only else 0)
+        if genome is None:
+            self._chk(self.lib.l2r_sj_begin(self.ctx, C.byref(prm), None))
+            return
+        off = np.ascontiguousarray(genome[0], np.int64); bases = np.ascontiguousarray(genome[1], np.uint8)
+        g = CSjGenome(len(off) - 1, off.ctypes.data, bases.ctypes.data)
+        self._chk(self.lib.l2r_sj_begin(self.ctx, C.byref(prm), C.byref(g)))
+
+    def sj_add(self, flag, tid, pos, uniq, cig_off, cig):
+        """One batch of records (the columns of l2r_sj_records)."""
+        a = [np.ascontiguousarray(flag, np.uint16), np.ascontiguousarray(tid, np.int32), np.ascontiguousarray(pos, np.int32),
+             np.ascontiguousarray(uniq, np.uint8), np.ascontiguousarray(cig_off, np.int64), np.ascontiguousarray(cig, np.uint32)]
+        r = CSjRecords(int(a[0].shape[0]), int(a[5].shape[0]), *[x.ctypes.data for x in a])
+        self._chk(self.lib.l2r_sj_add(self.ctx, C.byref(r)))
+
+    def sj_add_rows(self, tid, don, acc, uniq_c, multi_c):
+        """Rows that are counted already: their count columns are summed per junction."""
+        a = [np.ascontiguousarray(x, np.int32) for x in (tid, don, acc, uniq_c, multi_c)]
+        cj = CJunctions(len(a[0]), *[_ptr(x, _i32p) for x in a])
+        self._chk(self.lib.l2r_sj_add_rows(self.ctx, C.byref(cj)))
+
+    def sj_finish(self) -> SjTable:
+        """Sort + reduce + motifs, then the table as numpy columns.  An unknown tid raises L2RError (rc = SJ_E_UNKNOWN_TID)."""
+        n = C.c_int64(0)
+        self._chk(self.lib.l2r_sj_finish(self.ctx, C.byref(n)))
+        m = int(n.value)
+        cols = [np.zeros(max(m, 1), np.int32) for _ in range(5)] + [np.zeros(max(m, 1), np.uint8) for _ in range(2)]
+        t = CSjTable(max(m, 1), 0, *[x.ctypes.data for x in cols])
+        self._chk(self.lib.l2r_sj_download(self.ctx, C.byref(t)))
+        return SjTable(*[x[:m] for x in cols])
+
+    def sj_stats(self) -> dict:
+        """l2r_sj_stats: counters, and with L2R_SJ_TIMING=1 device milliseconds per kernel."""
+        out = np.zeros(len(SJ_STAT_NAMES), np.float64)
+        self._chk(self.lib.l2r_sj_stats(self.ctx, out.ctypes.data, len(out)))
+        return {k: float(v) for k, v in zip(SJ_STAT_NAMES, out)}
 
     def set_annotation_cache(self, directory) -> None:
         """Keep the annotation tables on disk under ``directory`` (None: off); see include/lr2rmats_hip.h."""

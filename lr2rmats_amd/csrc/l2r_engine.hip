@@ -23,6 +23,7 @@
 #include "l2r_chunk.hip.h"
 #include "l2r_tchunk.hip.h"
 #include "l2r_filter.hip.h"
+#include "l2r_sj.hip.h"
 
 using namespace l2r;
 
@@ -70,6 +71,29 @@ struct DevBuf {
 // The three kernel pipelines: classic (l2r_kernels.hip.h, two walks), slab (l2r_slab.hip.h, one walk, two kernels), tile (l2r_tile.hip.h,
 // one kernel per tile).  The upload says which of them its layout allows, choose_pipeline which one a launch takes.
 enum class Pipeline { classic, slab, tile };
+
+// `bam2sj` (l2r_sj.hip.h): what lives between l2r_sj_begin and l2r_sj_download.  Every buffer belongs to the context and is used again
+// by the next batch; the two row buffers take turns as source and target of the radix passes and of the reduction.
+struct SjRowBuf {
+    DevBuf<int32_t> col[5];
+    size_t cap = 0;
+    SjCols cols() const { return SjCols{col[0].p, col[1].p, col[2].p, col[3].p, col[4].p}; }
+};
+struct SjState {
+    bool open = false, finished = false, timing = false;
+    SjPrm prm{3, 1};
+    int32_t n_seq = 0;
+    DevBuf<int64_t> seq_off; DevBuf<uint8_t> bases;
+    SjRowBuf rows[2]; int cur = 0;
+    int64_t n_rows = 0;                     // rows[cur] holds that many
+    int64_t compact_rows = (int64_t)1 << 24, compact_at = (int64_t)1 << 24;     // L2R_SJ_COMPACT_ROWS: rows beyond which an add sorts and reduces what is there
+    DevBuf<uint16_t> flag; DevBuf<int32_t> tid, pos; DevBuf<uint8_t> uniq; DevBuf<int64_t> cig_off; DevBuf<uint32_t> cig, cnt;   // one batch
+    DevBuf<uint32_t> hist12, tile_hist, head, word;     // word[0]: a scan's total, word[1]: k_sj_motif's bad row
+    DevBuf<uint8_t> strand, motif;
+    double stats[15] = {0};
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    ~SjState() { for (int k = 0; k < 2; ++k) if (ev[k]) (void)hipEventDestroy(ev[k]); }
+};
 
 struct l2r_ctx {
     int device = 0;
@@ -201,6 +225,7 @@ struct l2r_ctx {
     DevBuf<unsigned long long> stamps;      // diagnostics, L2R_STAMPS=1
     uint32_t h_totals[3] = {0, 0, 0};
     bool totals_valid = false;
+    SjState sj;                             // `bam2sj`
 };
 
 // What completed runs have shown about the tile path's lists and the inexact tiles: forgotten wherever inputs, parameters or outputs change
@@ -1951,6 +1976,237 @@ int l2r_filter_select(l2r_ctx *c, int64_t n_groups, const int64_t *group_off, co
     hipError_t e = hipStreamSynchronize(c->stream);
     if (!rc && e != hipSuccess) rc = fail(-2, "[l2r_filter_select] %s", hipGetErrorString(e));
     return rc;
+}
+
+// ---------------------------------------------------------------------------------------------- bam2sj
+extern "C++" {
+// a launch (or a group of launches) on the context stream; with L2R_SJ_TIMING=1 bracketed by events, waited for and added to stats[slot]
+template <typename F> static int sj_launch(l2r_ctx *c, int slot, F f)
+{
+    SjState &s = c->sj;
+    if (s.timing) HIP_TRY(hipEventRecord(s.ev[0], c->stream));
+    f();
+    HIP_TRY(hipGetLastError());
+    if (s.timing) {
+        float ms = 0.0f;
+        HIP_TRY(hipEventRecord(s.ev[1], c->stream));
+        HIP_TRY(hipEventSynchronize(s.ev[1]));
+        HIP_TRY(hipEventElapsedTime(&ms, s.ev[0], s.ev[1]));
+        s.stats[slot] += ms;
+    }
+    return 0;
+}
+}
+
+// room for `want` rows; the first `keep` rows stay (DevBuf::ensure carries nothing over, so the columns are moved here)
+static int sj_rows_reserve(l2r_ctx *c, SjRowBuf &b, size_t want, size_t keep)
+{
+    if (want <= b.cap) return 0;
+    const size_t cap = std::max(std::max(want, b.cap * 2), (size_t)1 << 16);
+    int32_t *q[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+    hipError_t e = hipSuccess;
+    for (int k = 0; k < 5 && e == hipSuccess; ++k) {
+        e = hipMalloc((void **)&q[k], cap * sizeof(int32_t));
+        if (e == hipSuccess && keep) e = hipMemcpyAsync(q[k], b.col[k].p, keep * sizeof(int32_t), hipMemcpyDeviceToDevice, c->stream);
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    if (e != hipSuccess) {
+        for (int k = 0; k < 5; ++k) if (q[k]) (void)hipFree(q[k]);
+        return fail(-2, "[l2r_sj] %zu junction rows: %s", cap, hipGetErrorString(e));
+    }
+    for (int k = 0; k < 5; ++k) { b.col[k].release(); b.col[k].p = q[k]; b.col[k].cap = cap; }
+    b.cap = cap;
+    return 0;
+}
+
+static int sj_scan(l2r_ctx *c, int slot, uint32_t *v, int64_t n)
+{
+    ScanJobs jobs = {}; jobs.job[0] = ScanJob{v, n, c->sj.word.p}; jobs.job[1] = jobs.job[0];
+    return sj_launch(c, slot, [&] { hipLaunchKernelGGL(k_scan_u32, dim3(1), dim3(1024), 0, c->stream, jobs); });
+}
+
+// rows[cur][0, n_rows) -> sorted by (tid, don, acc), one row per key with the count columns summed
+static int sj_compact(l2r_ctx *c)
+{
+    SjState &s = c->sj;
+    const int64_t n64 = s.n_rows;
+    s.stats[1] += 1; s.stats[2] = 0; s.stats[3] = (double)n64; s.stats[4] = 0;
+    if (n64 == 0) return 0;
+    if (n64 >= ((int64_t)1 << 31)) return fail(-1, "[l2r_sj] %lld junction rows in one sort (2^31 at most)", (long long)n64);
+    const uint32_t n = (uint32_t)n64;
+    const unsigned grid = (n + SJ_THREADS - 1) / SJ_THREADS;
+    const uint32_t n_tiles = (n + SJ_SORT_TILE - 1) / SJ_SORT_TILE;
+    if (sj_rows_reserve(c, s.rows[1 - s.cur], n, 0) || s.hist12.ensure(SJ_KEY_BYTES * 256) || s.tile_hist.ensure((size_t)256 * n_tiles + 1) ||
+        s.head.ensure((size_t)n + 1) || s.word.ensure(4)) return -2;
+    // which key bytes differ at all
+    uint32_t h12[SJ_KEY_BYTES * 256];
+    HIP_TRY(hipMemsetAsync(s.hist12.p, 0, sizeof h12, c->stream));
+    int rc = sj_launch(c, 8, [&] { hipLaunchKernelGGL(k_sj_hist12, dim3(std::min(grid, 2048u)), dim3(SJ_THREADS), 0, c->stream, s.rows[s.cur].cols(), n, s.hist12.p); });
+    if (rc) return rc;
+    HIP_TRY(hipMemcpyAsync(h12, s.hist12.p, sizeof h12, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    int src = s.cur, passes = 0;
+    for (int b = 0; b < SJ_KEY_BYTES; ++b) {
+        bool one_value = false;
+        for (int d = 0; d < 256; ++d) if (h12[b * 256 + d] == n) { one_value = true; break; }
+        if (one_value) continue;
+        const SjCols in = s.rows[src].cols(), out = s.rows[1 - src].cols();
+        if ((rc = sj_launch(c, 9, [&] { hipLaunchKernelGGL(k_sj_digit_hist, dim3(n_tiles), dim3(SJ_THREADS), 0, c->stream, in, n, b, n_tiles, s.tile_hist.p); }))) return rc;
+        if ((rc = sj_scan(c, 10, s.tile_hist.p, (int64_t)256 * n_tiles))) return rc;
+        if ((rc = sj_launch(c, 11, [&] { hipLaunchKernelGGL(k_sj_scatter, dim3(n_tiles), dim3(SJ_THREADS), 0, c->stream, in, out, n, b, n_tiles, (const uint32_t *)s.tile_hist.p); }))) return rc;
+        src = 1 - src; ++passes;
+    }
+    // runs of equal keys
+    if ((rc = sj_launch(c, 12, [&] { hipLaunchKernelGGL(k_sj_heads, dim3(grid), dim3(SJ_THREADS), 0, c->stream, s.rows[src].cols(), n, s.head.p); }))) return rc;
+    if ((rc = sj_scan(c, 12, s.head.p, (int64_t)n))) return rc;
+    uint32_t n_runs = 0;
+    HIP_TRY(hipMemcpyAsync(&n_runs, s.word.p, 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    if (n_runs == 0 || n_runs > n) return fail(-2, "[l2r_sj] %u runs in %u rows", n_runs, n);
+    const int dst = 1 - src;
+    HIP_TRY(hipMemsetAsync(s.rows[dst].col[3].p, 0, (size_t)n_runs * 4, c->stream));
+    HIP_TRY(hipMemsetAsync(s.rows[dst].col[4].p, 0, (size_t)n_runs * 4, c->stream));
+    if ((rc = sj_launch(c, 13, [&] { hipLaunchKernelGGL(k_sj_reduce, dim3(grid), dim3(SJ_THREADS), 0, c->stream, s.rows[src].cols(), n, (const uint32_t *)s.head.p, s.rows[dst].cols(), n_runs); }))) return rc;
+    s.cur = dst; s.n_rows = n_runs;
+    s.stats[2] = passes; s.stats[4] = n_runs;
+    s.compact_at = std::max(s.compact_rows, 2 * s.n_rows);
+    return 0;
+}
+
+int l2r_sj_begin(l2r_ctx *c, const l2r_sj_params *prm, const l2r_sj_genome *g)
+{
+    if (!c || !prm) return fail(-1, "[l2r_sj_begin] null argument");
+    if (g && (g->n_seq < 0 || (g->n_seq > 0 && (!g->seq_off || !g->bases)))) return fail(-1, "[l2r_sj_begin] bad genome");
+    HIP_TRY(hipSetDevice(c->device));
+    SjState &s = c->sj;
+    s.open = false; s.finished = false; s.n_rows = 0; s.cur = 0; s.n_seq = 0;
+    for (double &v : s.stats) v = 0;
+    s.prm = SjPrm{prm->min_intron, prm->pair_only};
+    const char *e = getenv("L2R_SJ_COMPACT_ROWS");
+    s.compact_rows = e && atoll(e) > 0 ? atoll(e) : (int64_t)1 << 24;
+    s.compact_at = s.compact_rows;
+    s.timing = getenv("L2R_SJ_TIMING") != nullptr && atoi(getenv("L2R_SJ_TIMING")) != 0;
+    for (int k = 0; k < 2; ++k) if (!s.ev[k]) HIP_TRY(hipEventCreate(&s.ev[k]));
+    if (s.word.ensure(4)) return -2;
+    if (g && g->n_seq > 0) {
+        for (int32_t k = 0; k < g->n_seq; ++k) if (g->seq_off[k + 1] < g->seq_off[k] || g->seq_off[0] != 0) return fail(-1, "[l2r_sj_begin] sequence offsets do not ascend from 0");
+        int rc;
+        if ((rc = to_dev(c, s.seq_off, g->seq_off, (size_t)g->n_seq + 1)) || (rc = to_dev(c, s.bases, g->bases, (size_t)g->seq_off[g->n_seq]))) return rc;
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        s.n_seq = g->n_seq;
+    }
+    s.open = true;
+    return 0;
+}
+
+static int sj_after_add(l2r_ctx *c, int64_t added)
+{
+    SjState &s = c->sj;
+    s.n_rows += added; s.stats[0] += (double)added; s.finished = false;
+    return s.n_rows > s.compact_at ? sj_compact(c) : 0;
+}
+
+int l2r_sj_add(l2r_ctx *c, const l2r_sj_records *r)
+{
+    if (!c || !r) return fail(-1, "[l2r_sj_add] null argument");
+    SjState &s = c->sj;
+    if (!s.open) return fail(-1, "[l2r_sj_add] l2r_sj_begin comes first");
+    if (r->n < 0 || r->n_cigar < 0 || r->n >= ((int64_t)1 << 31) || r->n_cigar >= ((int64_t)1 << 31)) return fail(-1, "[l2r_sj_add] a batch holds fewer than 2^31 records and CIGAR operations");
+    if (r->n == 0) return 0;
+    if (!r->flag || !r->tid || !r->pos || !r->uniq || !r->cig_off || (r->n_cigar && !r->cig)) return fail(-1, "[l2r_sj_add] null column");
+    const size_t N = (size_t)r->n;
+    if (r->cig_off[0] != 0 || r->cig_off[N] != r->n_cigar) return fail(-1, "[l2r_sj_add] cig_off does not span the CIGAR array");
+    for (size_t i = 0; i < N; ++i) if (r->cig_off[i + 1] < r->cig_off[i]) return fail(-1, "[l2r_sj_add] cig_off descends at record %zu", i);
+    HIP_TRY(hipSetDevice(c->device));
+    int rc;
+    if ((rc = to_dev(c, s.flag, r->flag, N)) || (rc = to_dev(c, s.tid, r->tid, N)) || (rc = to_dev(c, s.pos, r->pos, N)) || (rc = to_dev(c, s.uniq, r->uniq, N)) ||
+        (rc = to_dev(c, s.cig_off, r->cig_off, N + 1)) || (rc = to_dev(c, s.cig, r->cig, (size_t)r->n_cigar))) return rc;
+    if (s.cnt.ensure(N + 1)) return -2;
+    const SjRecs recs{(int64_t)N, s.flag.p, s.tid.p, s.pos.p, s.uniq.p, s.cig_off.p, s.cig.p};
+    const unsigned grid = (unsigned)((N + SJ_THREADS - 1) / SJ_THREADS);
+    if ((rc = sj_launch(c, 5, [&] { hipLaunchKernelGGL(k_sj_count, dim3(grid), dim3(SJ_THREADS), 0, c->stream, recs, s.prm, s.cnt.p); }))) return rc;
+    if ((rc = sj_scan(c, 6, s.cnt.p, (int64_t)N))) return rc;
+    uint32_t total = 0;
+    HIP_TRY(hipMemcpyAsync(&total, s.word.p, 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    if (total == 0) return 0;
+    if ((rc = sj_rows_reserve(c, s.rows[s.cur], (size_t)s.n_rows + total, (size_t)s.n_rows))) return rc;
+    if ((rc = sj_launch(c, 7, [&] { hipLaunchKernelGGL(k_sj_fill, dim3(grid), dim3(SJ_THREADS), 0, c->stream, recs, s.prm, (const uint32_t *)s.cnt.p, s.rows[s.cur].cols(),
+                                                        s.n_rows, s.n_rows + (int64_t)total); }))) return rc;
+    return sj_after_add(c, (int64_t)total);
+}
+
+int l2r_sj_add_rows(l2r_ctx *c, const l2r_junctions *j)
+{
+    if (!c || !j) return fail(-1, "[l2r_sj_add_rows] null argument");
+    SjState &s = c->sj;
+    if (!s.open) return fail(-1, "[l2r_sj_add_rows] l2r_sj_begin comes first");
+    if (j->n < 0 || j->n >= ((int64_t)1 << 31)) return fail(-1, "[l2r_sj_add_rows] fewer than 2^31 rows at a time");
+    if (j->n == 0) return 0;
+    if (!j->tid || !j->don || !j->acc || !j->uniq_c || !j->multi_c) return fail(-1, "[l2r_sj_add_rows] null column");
+    HIP_TRY(hipSetDevice(c->device));
+    int rc;
+    if ((rc = sj_rows_reserve(c, s.rows[s.cur], (size_t)(s.n_rows + j->n), (size_t)s.n_rows))) return rc;
+    const int32_t *src[5] = {j->tid, j->don, j->acc, j->uniq_c, j->multi_c};
+    for (int k = 0; k < 5; ++k) HIP_TRY(hipMemcpyAsync(s.rows[s.cur].col[k].p + s.n_rows, src[k], (size_t)j->n * 4, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return sj_after_add(c, j->n);
+}
+
+int l2r_sj_finish(l2r_ctx *c, int64_t *n_rows)
+{
+    if (!c || !n_rows) return fail(-1, "[l2r_sj_finish] null argument");
+    SjState &s = c->sj;
+    if (!s.open) return fail(-1, "[l2r_sj_finish] l2r_sj_begin comes first");
+    HIP_TRY(hipSetDevice(c->device));
+    int rc;
+    if ((rc = sj_compact(c))) return rc;
+    const uint32_t n = (uint32_t)s.n_rows;
+    if (s.strand.ensure(n ? n : 1) || s.motif.ensure(n ? n : 1)) return -2;
+    if (n) {
+        uint32_t bad = 0xffffffffu;
+        HIP_TRY(hipMemcpyAsync(s.word.p + 1, &bad, 4, hipMemcpyHostToDevice, c->stream));
+        const SjGenome g{s.n_seq, s.seq_off.p, s.bases.p};
+        const SjCols t = s.rows[s.cur].cols();
+        if ((rc = sj_launch(c, 14, [&] { hipLaunchKernelGGL(k_sj_motif, dim3((n + SJ_THREADS - 1) / SJ_THREADS), dim3(SJ_THREADS), 0, c->stream, (const int32_t *)t.tid, (const int32_t *)t.don,
+                                                             (const int32_t *)t.acc, n, g, s.strand.p, s.motif.p, s.word.p + 1); }))) return rc;
+        HIP_TRY(hipMemcpyAsync(&bad, s.word.p + 1, 4, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        if (bad != 0xffffffffu) {
+            int32_t tid = -1;
+            if (bad < n) HIP_TRY(hipMemcpy(&tid, t.tid + bad, 4, hipMemcpyDeviceToHost));
+            return fail(L2R_SJ_E_UNKNOWN_TID, "[intr_deri_str] unknown tid: %d", tid);
+        }
+    }
+    s.finished = true;
+    *n_rows = s.n_rows;
+    return 0;
+}
+
+int l2r_sj_download(l2r_ctx *c, l2r_sj_table *t)
+{
+    if (!c || !t) return fail(-1, "[l2r_sj_download] null argument");
+    SjState &s = c->sj;
+    if (!s.finished) return fail(-1, "[l2r_sj_download] l2r_sj_finish comes first");
+    if (t->cap < s.n_rows) return fail(-1, "[l2r_sj_download] room for %lld rows, the table has %lld", (long long)t->cap, (long long)s.n_rows);
+    HIP_TRY(hipSetDevice(c->device));
+    const size_t n = (size_t)s.n_rows;
+    t->n = s.n_rows;
+    if (!n) return 0;
+    if (!t->tid || !t->don || !t->acc || !t->uniq_c || !t->multi_c || !t->strand || !t->motif) return fail(-1, "[l2r_sj_download] null column");
+    int32_t *dst[5] = {t->tid, t->don, t->acc, t->uniq_c, t->multi_c};
+    for (int k = 0; k < 5; ++k) HIP_TRY(hipMemcpyAsync(dst[k], s.rows[s.cur].col[k].p, n * 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(t->strand, s.strand.p, n, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(t->motif, s.motif.p, n, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+int l2r_sj_stats(l2r_ctx *c, double *out, int n)
+{
+    if (!c || !out || n < 0) return fail(-1, "[l2r_sj_stats] bad argument");
+    for (int k = 0; k < n; ++k) out[k] = k < 15 ? c->sj.stats[k] : 0.0;
+    return 0;
 }
 
 }  // extern "C"

@@ -1,0 +1,250 @@
+// l2r_sj.hip.h -- the kernels of `bam2sj` (reference src/parse_bam.c:402-442 gen_sj, :339-380 sj_sch_group / sj_update_group,
+// :319-337 intr_deri_str): junction rows from alignment records, ordered and counted on the device.
+//
+//   k_sj_count / k_sj_fill   one thread per record: the record filter and one walk over its CIGAR words; count -> k_scan_u32 ->
+//                            fill writes the rows {tid, don, acc, uniq_c, multi_c} in record order (a compaction: most short reads
+//                            carry no N operation)
+//   k_sj_hist12              one pass over the keys: the histograms of all twelve key bytes (a byte that is equal in every key is
+//                            a radix pass that is not run)
+//   k_sj_digit_hist          per pass: the digit histogram of every tile of SJ_SORT_TILE rows, digit-major (one k_scan_u32 over it
+//                            gives every (digit, tile) its first slot)
+//   k_sj_scatter             per pass: stable scatter, one workgroup per tile, 256 rows per round in row order: the rank of a row
+//                            among the rows of its digit = rows of earlier rounds + rows of earlier waves + lanes in front of it
+//   k_sj_heads / k_sj_reduce head flags where the key changes -> k_scan_u32 -> per run the sums of the two count COLUMNS (so the same
+//                            sort + reduce merges tables that were reduced before); a wave sums its part of a run by shuffles and
+//                            adds it with one integer atomic, so a run may cross waves and workgroups and be of any length
+//   k_sj_motif               per reduced row: four bases -> motif and strand; the first row on a sequence the genome lacks
+//
+// LSD radix with 8-bit digits over the 12-byte key (tid, don, acc), least significant byte of acc first; signed order (the top byte of
+// every column is compared with its sign bit flipped).  HBM-bound integer work: a pass reads and writes 20 bytes per row.  No kernel
+// waits for another workgroup.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+namespace l2r {
+
+constexpr int SJ_THREADS = 256;
+constexpr int SJ_SORT_TILE = L2R_SJ_SORT_TILE;          // rows of one workgroup of a radix pass (include/lr2rmats_hip.h)
+constexpr int SJ_ROUNDS = SJ_SORT_TILE / SJ_THREADS;
+constexpr int SJ_KEY_BYTES = 12;
+static_assert(SJ_SORT_TILE % SJ_THREADS == 0, "a tile is a whole number of rounds");
+
+struct SjCols { int32_t *tid, *don, *acc, *uq, *mc; };
+struct SjPrm { int32_t min_intron, pair_only; };
+struct SjRecs { int64_t n; const uint16_t *flag; const int32_t *tid, *pos; const uint8_t *uniq; const int64_t *cig_off; const uint32_t *cig; };
+
+// src/parse_bam.c:909-914: unmapped records and, with read_type PAIR_T, records that are not properly paired are skipped
+__device__ __forceinline__ bool sj_record_kept(uint32_t flag, const SjPrm &p) { return !(flag & 4u) && (!p.pair_only || (flag & 2u)); }
+
+// gen_sj: `end` = last reference base so far (1-based); M = X D N grow it, an N of at least min_intron bases is a junction first
+template <typename Emit>
+__device__ __forceinline__ uint32_t sj_walk(const uint32_t *__restrict__ cig, int64_t c0, int64_t c1, int32_t pos, int32_t min_intron, Emit emit)
+{
+    int32_t end = pos;
+    uint32_t k = 0;
+    for (int64_t j = c0; j < c1; ++j) {
+        const uint32_t w = cig[j], op = w & 0xfu; const int32_t len = (int32_t)(w >> 4);
+        if (op == 3u && len >= min_intron) { emit(k, end + 1, end + len); ++k; }
+        if ((0x18du >> op) & 1u) end += len;
+    }
+    return k;
+}
+
+__global__ __launch_bounds__(SJ_THREADS)
+void k_sj_count(SjRecs r, SjPrm p, uint32_t *__restrict__ cnt)
+{
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= r.n) return;
+    uint32_t k = 0;
+    if (sj_record_kept(r.flag[i], p)) k = sj_walk(r.cig, r.cig_off[i], r.cig_off[i + 1], r.pos[i], p.min_intron, [](uint32_t, int32_t, int32_t) {});
+    cnt[i] = k;
+}
+
+// at[]: the scanned counts (n + 1 words); rows go to out[base + at[i] ...), never beyond `cap`
+__global__ __launch_bounds__(SJ_THREADS)
+void k_sj_fill(SjRecs r, SjPrm p, const uint32_t *__restrict__ at, SjCols out, int64_t base, int64_t cap)
+{
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= r.n) return;
+    const uint32_t a = at[i];
+    if (at[i + 1] == a) return;
+    const int32_t t = r.tid[i], u = r.uniq[i] ? 1 : 0;
+    sj_walk(r.cig, r.cig_off[i], r.cig_off[i + 1], r.pos[i], p.min_intron, [&](uint32_t k, int32_t don, int32_t acc) {
+        const int64_t o = base + a + k;
+        if (o < cap) { out.tid[o] = t; out.don[o] = don; out.acc[o] = acc; out.uq[o] = u; out.mc[o] = 1 - u; }
+    });
+}
+
+// byte b (0 = least significant of acc ... 11 = most significant of tid) of a key, in unsigned order
+__device__ __forceinline__ uint32_t sj_digit(int32_t tid, int32_t don, int32_t acc, int b)
+{
+    const uint32_t col = b < 4 ? (uint32_t)acc : b < 8 ? (uint32_t)don : (uint32_t)tid;
+    return ((col ^ 0x80000000u) >> (8 * (b & 3))) & 0xffu;
+}
+
+// hist: 12 x 256 words, cleared by the caller
+__global__ __launch_bounds__(SJ_THREADS)
+void k_sj_hist12(SjCols in, uint32_t n, uint32_t *__restrict__ hist)
+{
+    __shared__ uint32_t s_h[SJ_KEY_BYTES * 256];
+    for (int k = threadIdx.x; k < SJ_KEY_BYTES * 256; k += SJ_THREADS) s_h[k] = 0u;
+    __syncthreads();
+    for (uint32_t i = blockIdx.x * SJ_THREADS + threadIdx.x; i < n; i += gridDim.x * SJ_THREADS) {
+        const int32_t t = in.tid[i], d = in.don[i], a = in.acc[i];
+#pragma unroll
+        for (int b = 0; b < SJ_KEY_BYTES; ++b) atomicAdd(&s_h[b * 256 + sj_digit(t, d, a, b)], 1u);
+    }
+    __syncthreads();
+    for (int k = threadIdx.x; k < SJ_KEY_BYTES * 256; k += SJ_THREADS) { const uint32_t v = s_h[k]; if (v) atomicAdd(&hist[k], v); }
+}
+
+__device__ __forceinline__ uint32_t sj_pass_digit(const SjCols &in, uint32_t i, int b)
+{
+    const int32_t *__restrict__ col = b < 4 ? in.acc : b < 8 ? in.don : in.tid;
+    return (((uint32_t)col[i] ^ 0x80000000u) >> (8 * (b & 3))) & 0xffu;
+}
+
+// tile_hist[d * n_tiles + tile] = rows of the tile with digit d
+__global__ __launch_bounds__(SJ_THREADS)
+void k_sj_digit_hist(SjCols in, uint32_t n, int b, uint32_t n_tiles, uint32_t *__restrict__ tile_hist)
+{
+    __shared__ uint32_t s_h[256];
+    s_h[threadIdx.x] = 0u;
+    __syncthreads();
+    const uint32_t t0 = blockIdx.x * (uint32_t)SJ_SORT_TILE;
+    for (int r = 0; r < SJ_ROUNDS; ++r) {
+        const uint32_t i = t0 + (uint32_t)r * SJ_THREADS + threadIdx.x;
+        if (i < n) atomicAdd(&s_h[sj_pass_digit(in, i, b)], 1u);
+    }
+    __syncthreads();
+    tile_hist[threadIdx.x * n_tiles + blockIdx.x] = s_h[threadIdx.x];
+}
+
+// first[]: tile_hist after its exclusive scan: the first slot of the tile's rows of every digit
+__global__ __launch_bounds__(SJ_THREADS)
+void k_sj_scatter(SjCols in, SjCols out, uint32_t n, int b, uint32_t n_tiles, const uint32_t *__restrict__ first)
+{
+    __shared__ uint32_t s_base[256];
+    __shared__ uint32_t s_wcnt[SJ_THREADS / 64][256];
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    s_base[threadIdx.x] = first[threadIdx.x * n_tiles + blockIdx.x];
+#pragma unroll
+    for (int k = 0; k < SJ_THREADS / 64; ++k) s_wcnt[k][threadIdx.x] = 0u;
+    __syncthreads();
+    const uint32_t t0 = blockIdx.x * (uint32_t)SJ_SORT_TILE;
+    for (int r = 0; r < SJ_ROUNDS; ++r) {
+        const uint32_t r0 = t0 + (uint32_t)r * SJ_THREADS;
+        if (r0 >= n) break;                                            // (uniform)
+        const uint32_t i = r0 + threadIdx.x;
+        const bool active = i < n;
+        int32_t t = 0, d = 0, a = 0, u = 0, m = 0;
+        if (active) { t = in.tid[i]; d = in.don[i]; a = in.acc[i]; u = in.uq[i]; m = in.mc[i]; }
+        const uint32_t dg = sj_digit(t, d, a, b);
+        // the lanes of this wave that hold the same digit
+        unsigned long long same = __ballot(active);
+#pragma unroll
+        for (int q = 0; q < 8; ++q) {
+            const bool bit = (dg >> q) & 1u;
+            const unsigned long long bal = __ballot(active && bit);
+            same &= bit ? bal : ~bal;
+        }
+        const uint32_t rank = (uint32_t)__popcll(same & ((1ull << lane) - 1ull));
+        if (active && rank == 0u) s_wcnt[w][dg] = (uint32_t)__popcll(same);
+        __syncthreads();
+        if (active) {
+            uint32_t o = s_base[dg] + rank;
+            for (int k = 0; k < w; ++k) o += s_wcnt[k][dg];
+            if (o < n) { out.tid[o] = t; out.don[o] = d; out.acc[o] = a; out.uq[o] = u; out.mc[o] = m; }
+        }
+        __syncthreads();
+        {
+            uint32_t s = 0;
+#pragma unroll
+            for (int k = 0; k < SJ_THREADS / 64; ++k) { s += s_wcnt[k][threadIdx.x]; s_wcnt[k][threadIdx.x] = 0u; }
+            s_base[threadIdx.x] += s;
+        }
+        __syncthreads();
+    }
+}
+
+// head[i] = 1 where row i starts a run of equal keys (head has n + 1 words for the scan)
+__global__ __launch_bounds__(SJ_THREADS)
+void k_sj_heads(SjCols in, uint32_t n, uint32_t *__restrict__ head)
+{
+    const uint32_t i = blockIdx.x * SJ_THREADS + threadIdx.x;
+    if (i >= n) return;
+    head[i] = (i == 0u || in.tid[i] != in.tid[i - 1] || in.don[i] != in.don[i - 1] || in.acc[i] != in.acc[i - 1]) ? 1u : 0u;
+}
+
+// before[]: head[] after its exclusive scan (before[n] = runs).  Row i belongs to run before[i + 1] - 1.  out.uq / out.mc are cleared by
+// the caller; a wave adds up its rows of a run (segmented inclusive scan by shuffles) and the last lane of every such piece adds it.
+__global__ __launch_bounds__(SJ_THREADS)
+void k_sj_reduce(SjCols in, uint32_t n, const uint32_t *__restrict__ before, SjCols out, uint32_t n_runs)
+{
+    const uint32_t i = blockIdx.x * SJ_THREADS + threadIdx.x;
+    const int lane = threadIdx.x & 63;
+    const bool active = i < n;
+    uint32_t run = 0xffffffffu; int32_t u = 0, m = 0;
+    if (active) {
+        run = before[i + 1] - 1u;
+        u = in.uq[i]; m = in.mc[i];
+        if (before[i] != before[i + 1] && run < n_runs) { out.tid[run] = in.tid[i]; out.don[run] = in.don[i]; out.acc[run] = in.acc[i]; }
+    }
+#pragma unroll
+    for (int s = 1; s < 64; s <<= 1) {
+        const uint32_t pr = (uint32_t)__shfl_up((int)run, s, 64);
+        const int32_t pu = __shfl_up(u, s, 64), pm = __shfl_up(m, s, 64);
+        if (lane >= s && pr == run) { u += pu; m += pm; }
+    }
+    const uint32_t next = (uint32_t)__shfl_down((int)run, 1, 64);
+    if (active && (lane == 63 || next != run) && run < n_runs) {
+        if (u) atomicAdd(&out.uq[run], u);
+        if (m) atomicAdd(&out.mc[run], m);
+    }
+}
+
+struct SjGenome { int32_t n_seq; const int64_t *seq_off; const uint8_t *bases; };
+
+// src/parse_bam.c:319-337 with the table of src/parse_bam.c's intron_motif / intron_motif_strand.  A base outside its sequence matches
+// nothing.  bad_row: the smallest row index on a sequence the genome does not have (cleared to 0xffffffff by the caller).
+__global__ __launch_bounds__(SJ_THREADS)
+void k_sj_motif(const int32_t *__restrict__ tid, const int32_t *__restrict__ don, const int32_t *__restrict__ acc, uint32_t n, SjGenome g,
+                uint8_t *__restrict__ strand, uint8_t *__restrict__ motif, uint32_t *__restrict__ bad_row)
+{
+    const uint32_t i = blockIdx.x * SJ_THREADS + threadIdx.x;
+    if (i >= n) return;
+    uint8_t mo = 0, st = 0;
+    if (g.n_seq > 0) {
+        const int32_t t = tid[i];
+        if (t >= g.n_seq) atomicMin(bad_row, i);
+        else if (t >= 0) {
+            const int64_t s0 = g.seq_off[t], len = g.seq_off[t + 1] - s0;
+            const int64_t at[4] = {(int64_t)don[i] - 1, (int64_t)don[i], (int64_t)acc[i] - 2, (int64_t)acc[i] - 1};
+            uint32_t word = 0; bool inside = true;
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                uint32_t c = 0;
+                if (at[k] >= 0 && at[k] < len) c = g.bases[s0 + at[k]]; else inside = false;
+                if (c >= 'a' && c <= 'z') c -= 32u;
+                word = (word << 8) | c;
+            }
+#define SJ_M4(a, b, c, d) (((uint32_t)(a) << 24) | ((uint32_t)(b) << 16) | ((uint32_t)(c) << 8) | (uint32_t)(d))
+            if (inside) {
+                switch (word) {
+                case SJ_M4('G', 'T', 'A', 'G'): mo = 1; st = 1; break;
+                case SJ_M4('C', 'T', 'A', 'C'): mo = 2; st = 2; break;
+                case SJ_M4('G', 'C', 'A', 'G'): mo = 3; st = 1; break;
+                case SJ_M4('C', 'T', 'G', 'C'): mo = 4; st = 2; break;
+                case SJ_M4('A', 'T', 'A', 'C'): mo = 5; st = 1; break;
+                case SJ_M4('G', 'T', 'A', 'T'): mo = 6; st = 2; break;
+                default: break;
+                }
+            }
+#undef SJ_M4
+        }
+    }
+    strand[i] = st; motif[i] = mo;
+}
+
+}  // namespace l2r

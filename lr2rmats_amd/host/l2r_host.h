@@ -83,6 +83,26 @@ int  h_write_bam(FILE *fp, const h_records *r, const int64_t *keep, int64_t n_ke
 int  h_records_to_bam(const char *in_fn, const char *out_fn);
 int  h_filter_run(const char *in_fn, const char *remove_fn, const l2r_filter_params *prm, FILE *out, int64_t *n_written);
 
+/* ---- `bam2sj` (sj.c): FASTA, a record source whose memory is bounded by the batch, the reference's junction list */
+typedef struct { int32_t n_seq; int64_t *seq_off; uint8_t *bases; char **name; } h_fasta;      /* sequences in FILE order; seq_off: n_seq + 1 */
+void h_read_fasta(const char *fn, h_fasta *out, const char *who);      /* plain or gzip */
+void h_fasta_free(h_fasta *f);
+typedef struct {
+    int64_t n, cap;
+    uint16_t *flag; int32_t *tid, *pos;
+    uint8_t *uniq;                         /* NH present and bam_aux2i(NH) == 1 */
+    uint8_t *nh_seen;                      /* the record has an NH tag */
+    int64_t *cig_off; uint32_t *cig; int64_t n_cig, cap_cig;
+} h_sj_batch;                              /* the columns of l2r_sj_records */
+typedef struct h_sj_source h_sj_source;
+h_sj_source *h_sj_source_open(const char *fn, h_chroms *chr, const char *who);      /* SAM, gzip / BGZF SAM, BAM; reads the header */
+int64_t h_sj_source_next(h_sj_source *s, h_sj_batch *b, int64_t max_records);       /* refills *b; records read, 0 at the end */
+void h_sj_source_close(h_sj_source *s);
+void h_sj_batch_free(h_sj_batch *b);
+/* junction rows in record order -> the list of sj_update_group() (src/parse_bam.c:339-380); out columns hold n rows; returns the list's rows */
+int64_t h_sj_literal(int64_t n, const int32_t *tid, const int32_t *don, const int32_t *acc, const int32_t *uniq_c, const int32_t *multi_c,
+                     int32_t *o_tid, int32_t *o_don, int32_t *o_acc, int32_t *o_uniq, int32_t *o_multi);
+
 /* ---- transcripts from a GTF (annotation, or read-like input of `-m g`) */
 typedef struct {
     int64_t n_tx, cap_tx, n_ex, cap_ex;
@@ -156,6 +176,7 @@ int h_cmd_update_gtf(int argc, char **argv);
 int h_cmd_bam2gtf(int argc, char **argv);
 int h_cmd_unique_gtf(int argc, char **argv);
 int h_cmd_filter(int argc, char **argv);
+int h_cmd_bam2sj(int argc, char **argv);
 int h_main(int argc, char **argv);
 
 /* ---- staged form of update-gtf, used by the CLI itself and by the one-process-per-GPU driver

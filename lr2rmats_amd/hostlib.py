@@ -63,6 +63,22 @@ def load_library():
         lib.h_job_set_out_path.argtypes = [C.c_void_p, C.c_int, C.c_char_p]
         lib.h_cigar_summaries.argtypes = [C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
         lib.h_cigar_summaries.restype = None
+        lib.h_read_fasta.argtypes = [C.c_char_p, C.c_void_p, C.c_char_p]
+        lib.h_read_fasta.restype = None
+        lib.h_fasta_free.argtypes = [C.c_void_p]
+        lib.h_fasta_free.restype = None
+        lib.h_sj_literal.argtypes = [C.c_int64] + [C.c_void_p] * 10
+        lib.h_sj_literal.restype = C.c_int64
+        lib.h_sj_source_open.argtypes = [C.c_char_p, C.c_void_p, C.c_char_p]
+        lib.h_sj_source_open.restype = C.c_void_p
+        lib.h_sj_source_next.argtypes = [C.c_void_p, C.c_void_p, C.c_int64]
+        lib.h_sj_source_next.restype = C.c_int64
+        lib.h_sj_source_close.argtypes = [C.c_void_p]
+        lib.h_sj_source_close.restype = None
+        lib.h_sj_batch_free.argtypes = [C.c_void_p]
+        lib.h_sj_batch_free.restype = None
+        lib.h_chroms_free.argtypes = [C.c_void_p]
+        lib.h_chroms_free.restype = None
         _lib = lib
     return _lib
 
@@ -82,6 +98,68 @@ def cigar_summaries(cig_off, cig) -> np.ndarray:
     out = np.empty((len(off) - 1, 3), np.uint32)
     load_library().h_cigar_summaries(len(off) - 1, off.ctypes.data, cg.ctypes.data, out.ctypes.data)
     return out
+
+# ---- `bam2sj` (host/sj.c): the FASTA reader, the batch-bounded record source and the reference's junction list (no GPU)
+
+class _CFasta(C.Structure):
+    _fields_ = [("n_seq", C.c_int32), ("seq_off", C.POINTER(C.c_int64)), ("bases", C.POINTER(C.c_uint8)), ("name", C.POINTER(C.c_char_p))]
+
+
+class _CChroms(C.Structure):
+    _fields_ = [("name", C.POINTER(C.c_char_p)), ("n", C.c_int), ("cap", C.c_int), ("n_hdr", C.c_int)]
+
+
+class _CSjBatch(C.Structure):
+    _fields_ = [("n", C.c_int64), ("cap", C.c_int64), ("flag", C.POINTER(C.c_uint16)), ("tid", C.POINTER(C.c_int32)), ("pos", C.POINTER(C.c_int32)),
+                ("uniq", C.POINTER(C.c_uint8)), ("nh_seen", C.POINTER(C.c_uint8)), ("cig_off", C.POINTER(C.c_int64)), ("cig", C.POINTER(C.c_uint32)),
+                ("n_cig", C.c_int64), ("cap_cig", C.c_int64)]
+
+
+def read_fasta(path: str):
+    """(names, seq_off [n + 1] int64, bases uint8): the sequences of a plain or gzip FASTA in FILE order (h_read_fasta)."""
+    lib = load_library()
+    f = _CFasta()
+    lib.h_read_fasta(path.encode(), C.byref(f), b"read_fasta")
+    n = int(f.n_seq)
+    names = [f.name[i].decode() for i in range(n)]
+    off = _arr(f.seq_off, n + 1, np.int64).copy()
+    bases = _arr(f.bases, int(off[n]), np.uint8).copy()
+    lib.h_fasta_free(C.byref(f))
+    return names, off, bases
+
+
+def sj_literal(tid, don, acc, uniq_c, multi_c):
+    """Junction rows in record order -> the list the reference's insertion builds (h_sj_literal): five int32 columns."""
+    a = [np.ascontiguousarray(x, np.int32) for x in (tid, don, acc, uniq_c, multi_c)]
+    n = len(a[0])
+    o = [np.zeros(max(n, 1), np.int32) for _ in range(5)]
+    m = load_library().h_sj_literal(n, *[x.ctypes.data for x in a], *[x.ctypes.data for x in o])
+    return tuple(x[:m] for x in o)
+
+
+def sj_read_records(path: str, batch: int = 1 << 20):
+    """Every record of a SAM / gzip SAM / BAM file through the record source of ``bam2sj``, ``batch`` records at a time:
+    dict of flag, tid, pos, uniq, nh_seen, cig_off, cig (concatenated over the batches) and the header's reference names."""
+    lib = load_library()
+    chr_ = _CChroms()
+    src = lib.h_sj_source_open(path.encode(), C.byref(chr_), b"sj_read_records")
+    b = _CSjBatch()
+    cols = {k: [] for k in ("flag", "tid", "pos", "uniq", "nh_seen", "cig")}
+    lens = []
+    while lib.h_sj_source_next(src, C.byref(b), batch) > 0:
+        n = int(b.n)
+        for k, t in (("flag", np.uint16), ("tid", np.int32), ("pos", np.int32), ("uniq", np.uint8), ("nh_seen", np.uint8)):
+            cols[k].append(_arr(getattr(b, k), n, t).copy())
+        cols["cig"].append(_arr(b.cig, int(b.n_cig), np.uint32).copy())
+        lens.append(np.diff(_arr(b.cig_off, n + 1, np.int64)))
+    names = [chr_.name[i].decode() for i in range(chr_.n_hdr)]
+    lib.h_sj_source_close(src); lib.h_sj_batch_free(C.byref(b)); lib.h_chroms_free(C.byref(chr_))
+    dt = dict(flag=np.uint16, tid=np.int32, pos=np.int32, uniq=np.uint8, nh_seen=np.uint8, cig=np.uint32)
+    out = {k: (np.concatenate(v) if v else np.zeros(0, dt[k])) for k, v in cols.items()}
+    out["cig_off"] = np.concatenate([[0], np.cumsum(np.concatenate(lens) if lens else np.zeros(0, np.int64))]).astype(np.int64)
+    out["names"] = names
+    return out
+
 
 class Job:
     """One ``update-gtf`` invocation: argv = ["update-gtf", options..., in.bam, old.gtf]."""

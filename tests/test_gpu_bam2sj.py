@@ -1,0 +1,354 @@
+"""`lr2rmats bam2sj` on the GPU: the CLI against the restatement (tests/sj_restatement.py) byte for byte, and the sort / reduce
+kernels through the C-ABI with rows chosen directly."""
+import os
+import re
+
+import numpy as np
+import pytest
+
+from lr2rmats_amd import capi, hostlib, synth
+from tests import sj_cases as sc
+from tests import sj_restatement as sr
+
+pytestmark = pytest.mark.gpu
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def _cli(args, env=None):
+    p = hostlib.run_cli(["bam2sj"] + list(args), env=env)
+    return p.returncode, p.stdout, p.stderr.decode()
+
+
+def _sort_tile():
+    text = open(os.path.join(ROOT, "include", "lr2rmats_hip.h")).read()
+    return int(re.search(r"#define\s+L2R_SJ_SORT_TILE\s+(\d+)", text).group(1))
+
+
+# ---------------------------------------------------------------------------------------------------- 1: the hand file
+
+def test_hand_file_in_every_format(tmp_path):
+    text = sc.hand_sam()
+    want = sr.expected_stdout(text)
+    assert want.count(b"\n") == 4 + len(sc.HAND_TABLE)
+    for path in sc.write_inputs(tmp_path, "hand", text):
+        rc, out, err = _cli([path])
+        assert rc == 0 and out == want, path
+        assert err.count('No "NH" tag.\n') == sc.HAND_NO_NH_MESSAGES
+    sam = str(tmp_path / "hand.sam")
+    assert _cli(["-p", sam])[1] == want                                  # -p changes nothing: read_type is PAIR_T either way
+    assert _cli(["-i", "4", sam])[1] == sr.expected_stdout(text, min_intron=4) != want
+    assert _cli(["-i", "2", sam])[1] == sr.expected_stdout(text, min_intron=2) != want
+    assert _cli(["-a", "1,2,3,4,5", "-U", "1,1,1,1,1", "-A", "0:0:0:0:0", sam])[1] == want      # parsed, unused
+
+
+def test_empty_result_and_usage(tmp_path):
+    for path in sc.write_inputs(tmp_path, "none", sc.no_junction_sam()):
+        rc, out, err = _cli([path])
+        assert rc == 0 and out == sr.HEADER.encode()
+    sam = str(tmp_path / "none.sam")
+    for args in (["-G", "x.gtf", sam], ["-a", "1,2,3", sam], [], [sam, sam]):
+        rc, out, err = _cli(args)
+        assert rc == 1 and out == b"" and "Usage:" in err
+    assert "unknown option" in _cli(["-G", "x.gtf", sam])[2]
+    rc, out, err = _cli(["-g", str(tmp_path / "missing.fa"), sam])
+    assert rc == 1 and out == b"" and "Can not open genome file" in err
+    p = hostlib.run_cli(["fusion"])
+    assert p.returncode == 1 and b"outside the MI355X build" in p.stderr
+
+
+# ---------------------------------------------------------------------------------------------------- 2: motifs
+
+HDR4 = sc.HDR + "@SQ\tSN:chr4\tLN:1000\n"
+
+
+def _genome():
+    """Three sequences of 'A'; (tid, don, acc, bases at don, don + 1, acc - 1, acc)."""
+    placed = [(0, 11, 30, "GTAG"), (0, 41, 60, "CTAC"), (0, 71, 90, "GCAG"), (0, 101, 120, "gtAg"),
+              (1, 11, 30, "CTGC"), (1, 41, 60, "ATAC"), (1, 71, 90, "GTAT"), (1, 101, 120, "TTTT"),
+              (2, 11, 50, "GTAG")]                                        # chr3 is 50 bases long: this acceptor is its last base
+    seqs = [list("A" * 150), list("A" * 150), list("A" * 50)]
+    for t, d, a, b in placed:
+        seqs[t][d - 1], seqs[t][d], seqs[t][a - 2], seqs[t][a - 1] = b
+    return ["".join(s) for s in seqs], placed
+
+
+def _motif_sam(placed, extra=()):
+    lines = [sc.sam_line("q%d" % k, 3, "chr%d" % (t + 1), d - 10, "10M%dN10M" % (a - d + 1), ["NH:i:1"])
+             for k, (t, d, a, _) in enumerate(list(placed) + list(extra))]
+    return HDR4 + "".join(lines)
+
+
+def test_motifs(tmp_path):
+    seqs, placed = _genome()
+    # one junction whose acceptor is one base beyond chr3, one two beyond
+    text = _motif_sam(placed, [(2, 21, 51, None), (2, 31, 52, None)])
+    fa = str(tmp_path / "g.fa")
+    with open(fa, "w") as fh:                                             # file order chrX, chrY, chrZ: the NAMES play no part, tid indexes
+        for name, s in zip(("chrX", "chrY", "chrZ"), seqs):
+            fh.write(">%s\n%s\n%s\n" % (name, s[:70], s[70:]))
+    want = sr.expected_stdout(text, seqs)
+    rows = [l.split("\t") for l in want.decode().splitlines()[4:]]
+    by_key = {(r[0], int(r[1])): (int(r[3]), int(r[7])) for r in rows}
+    assert [by_key[("chr1", d)] for d in (11, 41, 71, 101)] == [(1, 1), (2, 2), (1, 3), (1, 1)]      # (strand, motif); lower case counts
+    assert [by_key[("chr2", d)] for d in (11, 41, 71, 101)] == [(2, 4), (1, 5), (2, 6), (0, 0)]
+    # the acceptor ON the last base reads four bases inside the sequence (GT..AG here); one beyond reads outside: nothing matches
+    assert by_key[("chr3", 11)] == (1, 1) and by_key[("chr3", 21)] == (0, 0) and by_key[("chr3", 31)] == (0, 0)
+    for path in sc.write_inputs(tmp_path, "motif", text):
+        rc, out, err = _cli(["-g", fa, path])
+        assert rc == 0 and out == want, path
+    sam = str(tmp_path / "motif.sam")
+    no_g = _cli([sam])[1]
+    assert no_g == sr.expected_stdout(text) and all(l.split("\t")[3] == "0" and l.split("\t")[7] == "0" for l in no_g.decode().splitlines()[4:])
+    import gzip
+    with gzip.open(fa + ".gz", "wt") as fh:
+        fh.write(open(fa).read())
+    assert _cli(["-g", fa + ".gz", sam])[1] == want
+    # last base of a sequence without a motif there: chr3's last bases as 'AA'
+    seqs2 = list(seqs); seqs2[2] = seqs[2][:48] + "AA"
+    with open(fa, "w") as fh:
+        for name, s in zip(("a", "b", "c"), seqs2):
+            fh.write(">%s\n%s\n" % (name, s))
+    want2 = sr.expected_stdout(text, seqs2)
+    assert want2 != want and b"chr3\t11\t50\t0\t1\t1\t0\t0\n" in want2
+    assert _cli(["-g", fa, sam])[1] == want2
+
+
+def test_unknown_tid_ends_the_run(tmp_path):
+    seqs, placed = _genome()
+    text = _motif_sam(placed, [(3, 11, 30, None)])                        # chr4 = tid 3, the FASTA has three sequences
+    fa = str(tmp_path / "g.fa")
+    with open(fa, "w") as fh:
+        for k, s in enumerate(seqs):
+            fh.write(">s%d\n%s\n" % (k, s))
+    with pytest.raises(sr.UnknownTid):
+        sr.expected_stdout(text, seqs)
+    for path in sc.write_inputs(tmp_path, "tid3", text):
+        rc, out, err = _cli(["-g", fa, path])
+        assert rc == 1 and out == b"" and "[intr_deri_str] unknown tid: 3" in err
+    assert _cli([str(tmp_path / "tid3.sam")])[0] == 0                     # without -g the tid is never looked up
+
+
+# ---------------------------------------------------------------------------------------------------- 3: sort and reduce edges
+
+@pytest.fixture(scope="module")
+def eng():
+    e = capi.Engine(0)
+    yield e
+    e.close()
+
+
+def _table(eng, rows, pieces=1):
+    """rows: five columns -> the engine's table of them (added in `pieces` calls), checked against the numpy restatement."""
+    cols = [np.asarray(c, np.int32) for c in rows]
+    eng.sj_begin()
+    cut = np.linspace(0, len(cols[0]), pieces + 1).astype(int)
+    for a, b in zip(cut[:-1], cut[1:]):
+        eng.sj_add_rows(*[c[a:b] for c in cols])
+    got = eng.sj_finish()
+    want = sr.table_numpy(*cols)
+    for g, w, name in zip((got.tid, got.don, got.acc, got.uniq_c, got.multi_c), want, ("tid", "don", "acc", "uniq_c", "multi_c")):
+        assert np.array_equal(g.astype(np.int64), w), name
+    assert not got.strand.any() and not got.motif.any()
+    return got
+
+
+def test_sort_reduce_small_edges(eng):
+    z = np.zeros(0, np.int32)
+    assert _table(eng, [z, z, z, z, z]).tid.size == 0
+    assert eng.sj_stats()["radix_passes"] == 0
+    _table(eng, [[2], [10], [20], [3], [4]])
+    assert eng.sj_stats()["radix_passes"] == 0
+    rng = np.random.default_rng(1)
+    n = 700
+    # keys that differ only in the top byte of acc; only in tid; all but one byte shared (one pass, eleven skipped)
+    top = (rng.permutation(n) % 100).astype(np.int32)
+    _table(eng, [np.full(n, 1), np.full(n, 5), (top << 24) | 0x10, rng.integers(0, 3, n), rng.integers(0, 3, n)])
+    assert eng.sj_stats()["radix_passes"] == 1
+    _table(eng, [rng.integers(0, 200, n), np.full(n, 77), np.full(n, 99), np.ones(n), np.zeros(n)])
+    assert eng.sj_stats()["radix_passes"] == 1
+    _table(eng, [np.full(n, 3), 0x01020300 + rng.integers(0, 256, n), np.full(n, 0x01020400), rng.integers(0, 2, n), np.ones(n)])
+    assert eng.sj_stats()["radix_passes"] == 1
+    # signed order: a negative tid sorts in front (no file has one; the sort must not depend on that)
+    _table(eng, [[1, -1, 0, -1], [5, 6, 7, 6], [9, 9, 9, 9], [1, 1, 1, 1], [0, 0, 0, 2]])
+    # 5 000 identical keys: one run longer than any workgroup; the counts are column sums, not row counts
+    got = _table(eng, [np.full(5000, 4), np.full(5000, 1000), np.full(5000, 2000), np.full(5000, 3), np.arange(5000) % 2])
+    assert got.uniq_c.tolist() == [15000] and got.multi_c.tolist() == [2500]
+
+
+def test_sort_reduce_runs_across_tile_boundaries(eng):
+    tile = _sort_tile()
+    n = 3 * tile + 17
+    rng = np.random.default_rng(2)
+    # sorted position = key order: runs of one key placed over every tile boundary (and every 256-row round next to it) of the sorted
+    # rows, distinct keys elsewhere; the rows arrive shuffled
+    key = np.arange(n, dtype=np.int64)
+    for b in (tile, 2 * tile, 3 * tile):
+        key[b - 300:b + 300] = b                                           # a 600-row run across the boundary
+        key[b - 700:b - 636] = b - 700                                     # a 64-row run inside
+    key[n - 10:] = n                                                       # a run that ends the table
+    perm = rng.permutation(n)
+    k = key[perm]
+    rows = [(k >> 20).astype(np.int32), ((k >> 8) & 0xfff).astype(np.int32) + 1, (k & 0xff).astype(np.int32) * 3 + 5,
+            rng.integers(0, 4, n).astype(np.int32), rng.integers(0, 4, n).astype(np.int32)]
+    got = _table(eng, rows)
+    assert got.tid.size == len(np.unique(key)) < n
+    assert eng.sj_stats()["rows_in"] == n
+    # the same rows added in pieces and sorted + reduced on the way give the same table
+    os.environ["L2R_SJ_COMPACT_ROWS"] = "1000"
+    try:
+        again = _table(eng, rows, pieces=7)
+        assert eng.sj_stats()["rounds"] > 2
+    finally:
+        del os.environ["L2R_SJ_COMPACT_ROWS"]
+    assert all(np.array_equal(a, b) for a, b in zip((got.tid, got.don, got.acc, got.uniq_c, got.multi_c),
+                                                    (again.tid, again.don, again.acc, again.uniq_c, again.multi_c)))
+    # exactly one tile, one row more, one row less
+    for m in (tile, tile + 1, tile - 1, 255, 256, 257):
+        _table(eng, [c[:m] for c in rows])
+
+
+# ---------------------------------------------------------------------------------------------------- 4 - 7: batches, size, chaining
+
+@pytest.fixture(scope="module")
+def records5000():
+    rec = sc.synth_records(5000, 21)
+    # records 999 and 1000 (the last of one batch of 1000 and the first of the next) carry one junction
+    for name in ("flag", "tid", "pos", "uniq"):
+        rec[name][1000] = rec[name][999] = {"flag": 3, "tid": rec["tid"][999], "pos": 5000, "uniq": 1}[name]
+    lens = np.diff(rec["cig_off"])
+    cig = [rec["cig"][rec["cig_off"][i]:rec["cig_off"][i + 1]] for i in range(5000)]
+    cig[999] = cig[1000] = np.array([(20 << 4), (333 << 4) | 3, (20 << 4)], np.uint32)
+    rec["cig"] = np.concatenate(cig)
+    rec["cig_off"] = np.concatenate([[0], np.cumsum([len(c) for c in cig])]).astype(np.int64)
+    assert lens.size == 5000
+    return rec
+
+
+def test_batches_give_identical_bytes(tmp_path, records5000):
+    text = sc.records_sam(records5000)
+    sam = str(tmp_path / "b.sam")
+    with open(sam, "w") as fh:
+        fh.write(text)
+    want = sr.expected_stdout(text)
+    t999 = int(records5000["tid"][999])
+    assert ("chr%d\t5021\t5353\t0\t1\t2\t0\t0\n" % (t999 + 1)).encode() in want       # 5000 + 20 = 5020 -> (5021, 5353), both records
+    outs = [_cli([sam], env=env) for env in (None, {"L2R_SJ_BATCH": 1000}, {"L2R_SJ_BATCH": 1}, {"L2R_SJ_BATCH": 64, "L2R_SJ_COMPACT_ROWS": 300})]
+    assert all(rc == 0 for rc, _, _ in outs)
+    assert all(out == want for _, out, _ in outs)
+    assert outs[0][2].count('No "NH" tag.\n') == sr.missing_nh_messages(text) > 0
+
+
+@pytest.fixture(scope="module")
+def records200k():
+    return sc.synth_records(200000, 5)
+
+
+def test_table_at_size_equals_the_numpy_restatement(eng, records200k):
+    r = records200k
+    rows = sr.rows_numpy(r["flag"], r["tid"], r["pos"], r["uniq"], r["cig_off"], r["cig"])
+    want = sr.table_numpy(*rows)
+    assert len(rows[0]) > 30000 and len(want[0]) > 3000                   # the input is not trivial
+    assert ((r["flag"] & 4) != 0).sum() > 2000 and ((r["flag"] & 2) == 0).sum() > 5000 and 0 < r["uniq"].sum() < len(r["uniq"])
+    runs = []
+    for cuts in ([0, 200000], [0, 1, 70000, 70001, 199999, 200000]):
+        eng.sj_begin()
+        for a, b in zip(cuts[:-1], cuts[1:]):
+            c0, c1 = r["cig_off"][a], r["cig_off"][b]
+            eng.sj_add(r["flag"][a:b], r["tid"][a:b], r["pos"][a:b], r["uniq"][a:b], r["cig_off"][a:b + 1] - c0, r["cig"][c0:c1])
+        runs.append(eng.sj_finish())
+        assert eng.sj_stats()["rows_made"] == len(rows[0])
+    for got in runs:
+        for g, w in zip((got.tid, got.don, got.acc, got.uniq_c, got.multi_c), want):
+            assert np.array_equal(g.astype(np.int64), w)
+        assert not got.strand.any() and not got.motif.any()
+    # pair_only = 0 keeps the records without FLAG & 2 (the engine's parameter; the CLI always sets it)
+    eng.sj_begin(pair_only=False)
+    eng.sj_add(r["flag"], r["tid"], r["pos"], r["uniq"], r["cig_off"], r["cig"])
+    got = eng.sj_finish()
+    want0 = sr.table_numpy(*sr.rows_numpy(r["flag"], r["tid"], r["pos"], r["uniq"], r["cig_off"], r["cig"], pair_only=False))
+    assert np.array_equal(got.uniq_c.astype(np.int64), want0[3]) and int(want0[3].sum() + want0[4].sum()) > len(rows[0])
+
+
+def test_motifs_at_size(eng, records200k):
+    r = sc.subset(records200k, np.arange(0, 200000, 5))                  # every fifth record: all five chromosomes
+    rng = np.random.default_rng(9)
+    n_seq = int(r["tid"].max()) + 1
+    lens = np.full(n_seq, 400000); lens[-1] = 200000                      # the last sequence is shorter than its junctions reach
+    off = np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)
+    bases = np.frombuffer(b"ACGTacgtN", np.uint8)[rng.integers(0, 9, int(off[-1]))]
+    eng.sj_begin(genome=(off, bases))
+    eng.sj_add(r["flag"], r["tid"], r["pos"], r["uniq"], r["cig_off"], r["cig"])
+    got = eng.sj_finish()
+    strand, motif = sr.motifs_numpy(off, bases, got.tid, got.don, got.acc)
+    assert np.array_equal(got.strand, strand) and np.array_equal(got.motif, motif)
+    assert len(set(motif.tolist())) == 7 and (got.acc[got.tid == n_seq - 1] > 200000).any()
+    # one sequence fewer: the first row on the missing one ends the table
+    eng.sj_begin(genome=(off[:-1], bases[:off[-2]]))
+    eng.sj_add(r["flag"], r["tid"], r["pos"], r["uniq"], r["cig_off"], r["cig"])
+    with pytest.raises(capi.L2RError, match=r"rc=-3: \[intr_deri_str\] unknown tid: %d" % (n_seq - 1)):
+        eng.sj_finish()
+
+
+def test_long_cigar(eng):
+    # a 300-operation CIGAR: the walk is a loop
+    ops = []
+    for k in range(100):
+        ops += [(5 + k % 3, 0), (1, 1) if k % 2 else (2, 2), (10 + k, 3)]
+    cig = np.array([(l << 4) | op for l, op in ops], np.uint32)
+    eng.sj_begin()
+    eng.sj_add([3, 3], [0, 0], [100, 100], [1, 0], [0, 300, 600], np.concatenate([cig, cig]))
+    got = eng.sj_finish()
+    want = sr.table_numpy(*sr.rows_numpy([3, 3], [0, 0], [100, 100], [1, 0], [0, 300, 600], np.concatenate([cig, cig])))
+    assert got.tid.size == 100 and np.array_equal(got.don.astype(np.int64), want[1]) and np.array_equal(got.acc.astype(np.int64), want[2])
+    assert got.uniq_c.tolist() == [1] * 100 and got.multi_c.tolist() == [1] * 100
+
+
+def test_table_feeds_update_gtf(eng, records5000):
+    """The table's first five columns go to l2r_set_junctions as they are: the same per-read results as with the restatement's rows."""
+    anno = synth.make_annotation(8000, 7)
+    af = anno.in_file_order()
+    reads = synth.make_reads(anno, 5000, 5, 7)
+    r = records5000
+    flag = np.full(reads.n, 3, np.uint16); uniq = (np.arange(reads.n) % 3 != 0).astype(np.uint8)
+    # the junctions of the reads themselves (so the check has something to find) and the rows of the batch test's records
+    order = np.argsort(reads.tid, kind="stable")                         # bam2sj's contract: tids never decrease
+    lens = np.diff(reads.cig_off)[order]
+    cig = np.concatenate([reads.cig[reads.cig_off[i]:reads.cig_off[i + 1]] for i in order])
+    cig_off = np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)
+    eng.sj_begin()
+    eng.sj_add(flag, reads.tid[order], reads.pos[order], uniq[order], cig_off, cig)
+    eng.sj_add(r["flag"], r["tid"], r["pos"], r["uniq"], r["cig_off"], r["cig"])
+    t = eng.sj_finish()
+    rows = [np.concatenate(p) for p in zip(sr.rows_numpy(flag, reads.tid[order], reads.pos[order], uniq[order], cig_off, cig),
+                                            sr.rows_numpy(r["flag"], r["tid"], r["pos"], r["uniq"], r["cig_off"], r["cig"]))]
+    want = sr.table_numpy(*rows)
+    assert t.tid.size == len(want[0]) > 5000
+
+    def run(sj):
+        e = capi.Engine(0)
+        try:
+            e.set_annotation(af.tx_tid, af.tx_start, af.tx_end, af.tx_rev, af.tx_ex_off, af.ex_start, af.ex_end)
+            e.set_junctions(sj)
+            return e.classify(reads, capi.default_params(full_level=3, min_sj_cnt=2))
+        finally:
+            e.close()
+    a = run((t.tid, t.don, t.acc, t.uniq_c, t.multi_c))
+    b = run(tuple(c.astype(np.int32) for c in want))
+    for name in ("ex_off", "ex_start", "ex_end", "ex_flag", "info", "ref_tx"):
+        assert np.array_equal(getattr(a, name), getattr(b, name)), name
+    checked = (a.info & capi.INFO_SJ_CHECKED) != 0
+    passed = (a.info & capi.INFO_SJ_PASS) != 0
+    assert checked.sum() > 100 and 0 < passed.sum() < checked.sum()      # the table decided something
+
+
+def test_decreasing_tids_take_the_literal_list(tmp_path):
+    text = sc.tids_0_1_0_sam()
+    _, recs = sr.records_from_sam(text)
+    rows = sr.rows_in_record_order(recs)
+    want = sr.expected_stdout(text)
+    assert want != sr.format_table(sr.sorted_table(rows), sc.NAMES)
+    for path in sc.write_inputs(tmp_path, "dec", text):
+        rc, out, err = _cli([path])
+        assert rc == 0 and out == want, path
+        assert err.count('No "NH" tag.\n') == 1
+    assert _cli([str(tmp_path / "dec.sam")], env={"L2R_SJ_BATCH": 2})[1] == want

@@ -1,0 +1,100 @@
+"""Diagnostics on the GPU box: the engine side of `lr2rmats bam2sj` (l2r_sj_begin / _add / _finish) on synthetic short-read records.
+Not part of the product.   tools/bench_sj.py [records = 50_000_000] [rounds = 5] [batch = 8_388_608]
+
+Reports, over `rounds` warm rounds (median and spread): wall time of add + finish with uploads, rows/s; then from ONE more round with
+L2R_SJ_TIMING=1 (every launch bracketed by HIP events and waited for) the device time per kernel, the bytes the algorithm moves
+divided by the kernel time as a fraction of 8 TB/s, and the radix passes that ran; and the wall time of the numpy restatement
+(np.unique + np.bincount, tests/sj_restatement.py) on the same rows on this host -- the only yardstick there is."""
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), '..'))
+from lr2rmats_amd import capi                      # noqa: E402
+from tests import sj_restatement as sr            # noqa: E402
+
+n = int(sys.argv[1]) if len(sys.argv) > 1 else 50_000_000
+rounds = int(sys.argv[2]) if len(sys.argv) > 2 else 5
+batch = int(sys.argv[3]) if len(sys.argv) > 3 else 1 << 23
+
+
+def make(n, seed=1, n_chrom=24, n_intron=12000, span=100_000_000):
+    """Coordinate-sorted records, a third with one or two N between fixed introns (about n_chrom * n_intron junctions), vectorised."""
+    rng = np.random.default_rng(seed)
+    tid = np.sort(rng.integers(0, n_chrom, n)).astype(np.int32)
+    sites = np.sort(rng.integers(1000, span, (n_chrom, 2 * n_intron)), axis=1)
+    spliced = rng.random(n) < 0.34
+    k = np.where(spliced, rng.integers(1, 3, n), 0)                       # introns per record
+    j0 = rng.integers(0, n_intron - 2, n)
+    don0, acc0 = sites[tid, 2 * j0], sites[tid, 2 * j0 + 1]
+    don1, acc1 = sites[tid, 2 * j0 + 2], sites[tid, 2 * j0 + 3]
+    lead = rng.integers(5, 70, n)
+    pos = np.where(spliced, don0 - lead, rng.integers(0, span, n)).astype(np.int32)
+    n_ops = 1 + 2 * k
+    off = np.concatenate([[0], np.cumsum(n_ops)]).astype(np.int64)
+    cig = np.empty(off[-1], np.uint32)
+    m = lambda ln: (np.maximum(ln, 1).astype(np.uint32) << 4)
+    s0 = off[:-1]
+    cig[s0] = np.where(spliced, m(lead), m(rng.integers(50, 151, n)))
+    a = spliced
+    cig[s0[a] + 1] = m(acc0[a] - don0[a]) | 3
+    cig[s0[a] + 2] = np.where(k[a] == 2, m(don1[a] - acc0[a]), m(rng.integers(5, 70, a.sum())))
+    b = k == 2
+    cig[s0[b] + 3] = m(acc1[b] - don1[b]) | 3
+    cig[s0[b] + 4] = m(rng.integers(5, 70, b.sum()))
+    order = np.lexsort((pos, tid))                                        # coordinate sorted
+    lens = n_ops[order]
+    new_off = np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)
+    idx = np.repeat(off[:-1][order] - new_off[:-1], lens) + np.arange(new_off[-1])
+    flag = np.full(n, 3, np.uint16); flag[rng.random(n) < 0.05] = 1; flag[rng.random(n) < 0.02] |= 4
+    uniq = (rng.random(n) < 0.8).astype(np.uint8)
+    return dict(flag=flag, tid=tid[order], pos=pos[order], uniq=uniq, cig_off=new_off, cig=cig[idx])
+
+
+def run(eng, r):
+    eng.sj_begin()
+    for a in range(0, len(r["flag"]), batch):
+        b = min(a + batch, len(r["flag"]))
+        c0, c1 = r["cig_off"][a], r["cig_off"][b]
+        eng.sj_add(r["flag"][a:b], r["tid"][a:b], r["pos"][a:b], r["uniq"][a:b], r["cig_off"][a:b + 1] - c0, r["cig"][c0:c1])
+    return eng.sj_finish()
+
+
+t0 = time.perf_counter()
+r = make(n)
+print("input: %d records, %d CIGAR operations (made in %.1f s)" % (n, len(r["cig"]), time.perf_counter() - t0), flush=True)
+eng = capi.Engine(0)
+run(eng, r)                                                               # warm: buffers, code objects
+walls = []
+for _ in range(rounds):
+    t0 = time.perf_counter(); tab = run(eng, r); walls.append(time.perf_counter() - t0)
+st = eng.sj_stats()
+os.environ["L2R_SJ_TIMING"] = "1"
+run(eng, r)
+tm = eng.sj_stats()
+del os.environ["L2R_SJ_TIMING"]
+rows, out_rows, passes = st["rows_made"], len(tab.tid), int(tm["radix_passes"])
+kern = {k: v for k, v in tm.items() if k.startswith("k_")}
+kernel_ms = sum(kern.values())
+# bytes the algorithm has to move: records in (15 B + 4 B per op), rows out 20 B and in again for hist12 (12 B); per pass 4 B of keys for
+# the tile histograms and 20 B in + 20 B out for the scatter; heads 12 B + 4, reduce 28 B (summed over the rounds' rows where there are several)
+rows_sorted = rows if st["rounds"] == 1 else None
+moved = 15 * n + 4 * len(r["cig"]) + 20 * rows + (12 + passes * 44 + 16 + 28) * rows
+t0 = time.perf_counter()
+want = sr.table_numpy(*sr.rows_numpy(r["flag"], r["tid"], r["pos"], r["uniq"], r["cig_off"], r["cig"]))
+numpy_s = time.perf_counter() - t0
+ok = all(np.array_equal(g.astype(np.int64), w) for g, w in zip((tab.tid, tab.don, tab.acc, tab.uniq_c, tab.multi_c), want))
+walls.sort()
+line = dict(records=n, rows=int(rows), table_rows=out_rows, rounds=rounds, sort_rounds=int(st["rounds"]), radix_passes=passes,
+            wall_s_median=walls[len(walls) // 2], wall_s_min=walls[0], wall_s_max=walls[-1], records_per_s=n / walls[len(walls) // 2],
+            kernel_ms=kernel_ms, rows_per_s_kernels=rows / (kernel_ms / 1e3) if kernel_ms else 0.0,
+            bytes_moved=int(moved), fraction_of_8TBs=(moved / (kernel_ms / 1e3)) / 8e12 if kernel_ms else 0.0,
+            numpy_restatement_s=numpy_s, equals_numpy=bool(ok))
+print("| kernel | ms (one round, every launch waited for) |\n|---|---|")
+for k, v in kern.items():
+    print("| %s | %.3f |" % (k, v))
+print(json.dumps(line))
+assert ok
