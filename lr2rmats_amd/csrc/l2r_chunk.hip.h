@@ -249,10 +249,10 @@ void k_probe_slab_chunked(SlabArgs kernarg_block, const uint32_t *__restrict__ u
     uint32_t *const X0 = s_dir, *const X1 = s_dir + DIR_N, *const XR = s_dir + 2 * DIR_N;
     // the tiles of this kernel: chunk_list (TileLists + what the one-window kernels appended), taken from a cursor
     // (... = the entries k_describe_scan / TileLists made, then the ones the one-window kernels appended late: chunk_list_append_late)
-    const uint32_t n_first = min(sa->list_cnt[1], (uint32_t)sa->n_tiles), n_list = n_first + min(sa->list_cnt[8], (uint32_t)sa->n_tiles);
+    const uint32_t n_first = min(sa->list_cnt[LC_CHUNK], (uint32_t)sa->n_tiles), n_list = n_first + min(sa->list_cnt[LC_LATE], (uint32_t)sa->n_tiles);
     for (bool own = true;; own = false) {
         if (own && blockIdx.x >= n_list) break;
-        if (threadIdx.x == 0) s_next = own ? blockIdx.x : gridDim.x + atomicAdd(sa->list_cnt + 3, 1u);
+        if (threadIdx.x == 0) s_next = own ? blockIdx.x : gridDim.x + atomicAdd(sa->list_cnt + LC_CHUNK_CURSOR, 1u);
         __syncthreads();
         const uint32_t wi = s_next;
         if (wi >= n_list) break;

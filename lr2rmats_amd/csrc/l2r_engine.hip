@@ -95,58 +95,23 @@ struct SjState {
     ~SjState() { for (int k = 0; k < 2; ++k) if (ev[k]) (void)hipEventDestroy(ev[k]); }
 };
 
+// What l2r_sync has learned from the counters of a completed run of the tile path (fetch_run_facts): a later run of the same inputs,
+// parameters and outputs sizes its list-driven launches by the counts and skips those whose list was empty.  One record, forgotten as a
+// whole wherever one of those changes (forget_list_state).  LC_*: the list counter a field is a copy of (l2r_kernels.hip.h).
+struct RunFacts {
+    bool known = false;                 // a completed run has been looked at: what follows is what it left
+    uint32_t n_wide = 0;                // LC_WIDE: entries of wide_list -- the grid of k_tile's WIDE instance
+    uint32_t n_chunk = 0;               // LC_CHUNK: entries of chunk_list -- k_tile_chunk's grid
+    uint32_t n_rest = 0;                // LC_REST: entries of rest_list -- the grid of k_tile's general instance beside the EXACT one
+    uint32_t n_late = 0;                // LC_LATE: tiles a one-window kernel handed to the chunked kernel late -- the grid of k_tile_chunk's second launch
+    uint32_t n_fb = 0;                  // LC_FB: tiles k_tile left in slab form for k_probe_slab
+    uint32_t n_wide_rest = 0;           // LC_WIDE_REST: wide tiles that kept the slab form, for k_probe_slab_wide
+    unsigned long long chunk_rest = 0;  // tiles left to k_probe_slab_chunked: with k_tile_chunk what its two launches declined (LC_DECLINED, LC_DECLINED_LATE), else every entry (LC_LATE + LC_CHUNK)
+    bool redo_empty = false;            // TOT_REDO was 0: nothing for the generic kernel, and -- every read had its junction check in k_tile -- nothing for k_validate_sj
+};
+
 struct l2r_ctx {
     int device = 0;
-    int fast_grid = 0;
-    bool wide_cigar = false;                // long CIGARs: the HBM walks fetch 16 words per lane and round (l2r_upload_reads decides)
-    int n_cu = 256, wg_per_cu = 4;          // persistent grid of k_classify_fast (L2R_WG_PER_CU overrides)
-    int ablate = 0;                         // diagnostics, L2R_ABLATE (read once, at l2r_create)
-    int64_t seg_max = SEG_MAX;              // tiles up to which the segmented scans are used (l2r_kernels.hip.h); L2R_SEG_MAX
-    Pipeline want_pipe = Pipeline::tile;    // L2R_PIPELINE (see Pipeline); the default takes the tile path where the input allows it, else slab
-    bool many_exon_reads = false;           // the upload's sample: more than 0.5 % of the reads have more exons than a slab has rows
-    bool slab_ok = false;                   // the current upload can run the slab pipeline: coordinate-sorted records, short CIGARs, its slab layout fits
-    Pipeline pipe = Pipeline::classic;      // ... what the last launch took (the parameters have a say: choose_pipeline)
-    bool lists_heavy = false;                           // ... or most tiles went to them (an isoform-rich annotation): k_tile would only walk for them, which k_walk_slab does faster -- later runs take the slab pipeline
-    bool redo_empty = false;                            // ... and nothing to the generic kernel either: every read had its junction check in k_tile, k_validate_sj has nothing to do
-    bool wide_direct = true;                            // L2R_WIDE_DIRECT=0: the exact 64-bit-mask tiles keep the slab form and k_probe_slab_wide (k_tile's WIDE instance, l2r_tile.hip.h)
-    bool fb_empty = false;                              // ... and k_tile left no tile in slab form for k_probe_slab (list_cnt[4])
-    bool chunk_direct = true;                           // L2R_CHUNK_DIRECT=0: the exact tiles of the chunked kernel keep the slab form and k_probe_slab_chunked (k_tile_chunk, l2r_tchunk.hip.h)
-    bool chunk_rest_empty = false;                      // ... and k_tile_chunk declined none, nobody appended late (list_cnt[9], [8]): k_probe_slab_chunked has nothing to do
-    uint32_t n_late_tiles = 0;                          // ... tiles a one-window kernel handed to the chunked kernel late (list_cnt[8]): the grid of k_tile_chunk's second launch
-    uint32_t n_chunk_tiles = 0;                         // ... entries of chunk_list a completed run has left: k_tile_chunk's grid
-    bool wide_rest_empty = false;                       // ... and none of them kept the slab form (list_cnt[5]): k_probe_slab_wide has nothing to do
-    uint32_t n_wide_tiles = 0;                          // ... entries of wide_list a completed run has left (l2r_sync): the WIDE instance's grid
-    bool tile_split = true;                             // L2R_TILE_SPLIT=0: no EXACT instance of k_tile -- the general instance takes every tile (A/B runs, tests)
-    int64_t tile_resident = 0;                          // workgroups of k_tile the device holds at a time (l2r_create)
-    uint32_t n_rest_tiles = 0;                          // ... entries of rest_list a completed run has left (list_cnt[11]): the general instance's grid beside the EXACT one
-    DevBuf<uint32_t> rest_list;                         //     the tiles k_describe_scan<true> has not marked for the EXACT instance
-    bool prev_run_tile = false;                         // the last launch of this upload took the tile path (else the list counters are whatever a slab run left: cleared before the next tile run)
-    uint32_t lc_flip = 0;                               // ... and which of the two blocks of list counters (SlabArgs::list_cnt / list_cnt_next)
-    uint32_t lb_flip = 0;                               // which of the two lb_sup arrays the next run of the tile path uses (l2r_slab.hip.h SlabArgs::lb_sup)
-    bool lists_known = false, lists_empty = false;      // one-kernel tile path: a completed run of these inputs and parameters left nothing to k_probe_slab / _wide / _chunked (l2r_sync looks): their launches are skipped until something changes
-    DevBuf<unsigned long long> lb_tile, lb_blk, lb_sup;     // one-kernel tile path: the tiles' exon counts on their way to the later tiles' first slots
-    DevBuf<uint32_t> fb_list;                               //                       the tiles it leaves to k_probe_slab
-    DevBuf<uint16_t> sum_nn;                                //                       the records' N operations (l2r_reads::cig_summary) for k_tile_index<true>
-    bool env_tile_anyway = false, env_launch_all = false;   // L2R_TILE_ANYWAY / L2R_LAUNCH_ALL (diagnostics), read once at l2r_create
-    int64_t inexact_tiles = -1;                             //                       tiles that are not exact under the parameters now set (-1: not counted yet; forget_list_state forgets it)
-    bool tile_starved = false;                              //                       a tile of k_tile has waited in vain for the counts in front of it (or the device cannot hold the workgroups its look-back needs): the slab pipeline from then on
-    int64_t n_lb_fallback = 0;                              //                       ... runs that were done again on the slab pipeline for that reason (l2r_debug_counters)
-    bool have_index = false;                                //                       the current upload has its tile index (slot records, op statistics)
-    bool pipeline_forced = false;                           // L2R_PIPELINE is set: the pipeline it names also for single-run uploads (tests, A/B runs)
-    bool one_shot_upload = false;                           //                       ONE run will follow the upload (l2r_classify, l2r_hint_single_run): see l2r_classify
-    float index_ms = 0.0f;                                  //                       GPU time of the last upload's k_tile_index (l2r_upload_index_ms)
-    DevBuf<SlotRec> slot_rec;                               //                       the upload's slot records (k_tile_index)
-    DevBuf<TileStat> sup_stat;                              //                       ... summed up per super-block of 1024 tiles
-    DevBuf<TileStat> tile_stat; std::vector<TileStat> h_tile_stat;      //                 the upload's index of the tiles' CIGAR operations (k_tile_index)
-    DevBuf<uint32_t> tile_sbase, s_pre, s_loc, s_pl, cig_off32, tile_rec, tile_total, tile_xbase, tile_span;    // (tile_span: 16-byte TileSpan records, l2r_slab.hip.h)
-    DevBuf<int32_t> dense_start, dense_end;                 // slab pipeline: the outliers' dense area
-    DevBuf<uint32_t> slab_row;                              //                the exon rows between its kernels (one word per exon)
-    DevBuf<TileWin> tw;
-    DevBuf<TileWin64> tw64; DevBuf<uint32_t> wide_list, chunk_list, list_cnt, tile_flags;     // tiles with 33 .. 63 window members (l2r_wide.hip.h)
-    DevBuf<unsigned long long> ovf_cursor;
-    std::string anno_cache_dir;             // L2R_ANNO_CACHE / l2r_set_annotation_cache: where the annotation tables are kept between runs
-    int anno_cache_state = 0;               // last l2r_set_annotation: 0 no cache, 1 built + stored, 2 read from the cache
-    unsigned want = L2R_WANT_RESULTS | L2R_WANT_ACCEPTED;      // l2r_set_outputs
     hipStream_t stream = nullptr;
     // one-kernel tile path: the instances of k_tile that take the isoform-rich tiles (WIDE, CHUNK) need nothing of the plain instance --
     // their tiles' first slots are known since k_describe_scan -- and run BESIDE it on streams of their own (forked behind
@@ -158,9 +123,59 @@ struct l2r_ctx {
     // of the EXACT instance (launch_tile).  No stream of its own: with a third side stream two of the four streams shared a hardware queue.
     hipStream_t side[2] = {nullptr, nullptr};
     hipEvent_t ev_fork = nullptr, ev_join[2] = {nullptr, nullptr};
-    bool side_on = true;
+
+    // ---- switches and device facts, read once at l2r_create
+    int fast_grid = 0;                      // L2R_FAST_GRID: tests force many tiles per workgroup of k_classify_fast
+    int n_cu = 256, wg_per_cu = 4;          // persistent grid of k_classify_fast (L2R_WG_PER_CU overrides)
+    int ablate = 0;                         // diagnostics, L2R_ABLATE
+    int64_t seg_max = SEG_MAX;              // tiles up to which the segmented scans are used (l2r_kernels.hip.h); L2R_SEG_MAX
+    Pipeline want_pipe = Pipeline::tile;    // L2R_PIPELINE (see Pipeline); the default takes the tile path where the input allows it, else slab
+    bool pipeline_forced = false;           // L2R_PIPELINE is set: the pipeline it names also for single-run uploads (tests, A/B runs)
+    bool wide_direct = true;                // L2R_WIDE_DIRECT=0: the exact 64-bit-mask tiles keep the slab form and k_probe_slab_wide (k_tile's WIDE instance, l2r_tile.hip.h)
+    bool chunk_direct = true;               // L2R_CHUNK_DIRECT=0: the exact tiles of the chunked kernel keep the slab form and k_probe_slab_chunked (k_tile_chunk, l2r_tchunk.hip.h)
+    bool tile_split = true;                 // L2R_TILE_SPLIT=0: no EXACT instance of k_tile -- the general instance takes every tile (A/B runs, tests)
+    bool side_on = true;                    // L2R_SIDE=0: no side streams
+    bool env_tile_anyway = false, env_launch_all = false;   // L2R_TILE_ANYWAY / L2R_LAUNCH_ALL (diagnostics)
+    bool check_stages = false;              // L2R_CHECK
     bool env_stamps = false;                // L2R_STAMPS (diagnostics): the next upload makes the `stamps` buffer
+    int64_t tile_resident = 0;              // workgroups of k_tile the device holds at a time
+    bool tile_starved = false;              // the device cannot hold the workgroups k_tile's look-back needs -- or (l2r_sync) a tile has waited in vain for the counts in front of it: the slab pipeline from then on
+    int64_t n_lb_fallback = 0;              // runs that were done again on the slab pipeline for that reason (l2r_debug_counters)
+
+    // ---- caller's settings
     l2r_params prm;
+    std::string anno_cache_dir;             // L2R_ANNO_CACHE / l2r_set_annotation_cache: where the annotation tables are kept between runs
+    int anno_cache_state = 0;               // last l2r_set_annotation: 0 no cache, 1 built + stored, 2 read from the cache
+    unsigned want = L2R_WANT_RESULTS | L2R_WANT_ACCEPTED;      // l2r_set_outputs
+    bool one_shot_upload = false;           // ONE run will follow the upload (l2r_classify, l2r_hint_single_run): see l2r_classify
+
+    // ---- per upload (l2r_upload_reads)
+    bool wide_cigar = false;                // long CIGARs: the HBM walks fetch 16 words per lane and round
+    bool many_exon_reads = false;           // the upload's sample: more than 0.5 % of the reads have more exons than a slab has rows
+    bool slab_ok = false;                   // the upload can run the slab pipeline: coordinate-sorted records, short CIGARs, its slab layout fits
+    bool have_index = false;                // the upload has its tile index (slot records, op statistics): the tile path is possible
+    float index_ms = 0.0f;                  // GPU time of the upload's k_tile_index (l2r_upload_index_ms)
+    DevBuf<SlotRec> slot_rec;               // the upload's slot records (k_tile_index)
+    DevBuf<TileStat> tile_stat; std::vector<TileStat> h_tile_stat;      // the upload's index of the tiles' CIGAR operations (k_tile_index)
+    DevBuf<TileStat> sup_stat;              // ... summed up per super-block of 1024 tiles
+    DevBuf<uint16_t> sum_nn;                // the records' N operations (l2r_reads::cig_summary) for k_tile_index<true>
+    DevBuf<uint32_t> tile_sbase, s_pre, s_loc, s_pl, cig_off32, tile_rec, tile_total, tile_xbase, tile_span;    // (tile_span: 16-byte TileSpan records, l2r_slab.hip.h)
+    DevBuf<int32_t> dense_start, dense_end; // slab pipeline: the outliers' dense area
+    DevBuf<uint32_t> slab_row;              //                the exon rows between its kernels (one word per exon)
+    DevBuf<TileWin> tw;
+    DevBuf<TileWin64> tw64; DevBuf<uint32_t> wide_list, chunk_list, list_cnt, tile_flags;     // tiles with 33 .. 63 window members (l2r_wide.hip.h); list_cnt: two blocks of LC_WORDS
+    DevBuf<unsigned long long> ovf_cursor;
+    DevBuf<unsigned long long> lb_tile, lb_blk, lb_sup;     // one-kernel tile path: the tiles' exon counts on their way to the later tiles' first slots
+    DevBuf<uint32_t> fb_list;               //                       the tiles it leaves to k_probe_slab
+    DevBuf<uint32_t> rest_list;             //                       the tiles k_describe_scan<true> has not marked for the EXACT instance
+
+    // ---- per run: what the last launch did, and what completed runs have taught (forgotten with inputs, parameters or outputs: forget_list_state)
+    Pipeline pipe = Pipeline::classic;      // what the last launch took (choose_pipeline)
+    bool prev_run_tile = false;             // the last launch of this upload took the tile path (else the list counters are whatever a slab run left: cleared before the next tile run)
+    uint32_t lc_flip = 0;                   // which of the two blocks of list counters the next run of the tile path uses (lc_this_run / lc_next_run / lc_last_run; lc_reset, end_of_run)
+    uint32_t lb_flip = 0;                   // which of the two lb_sup arrays it uses (l2r_slab.hip.h SlabArgs::lb_sup)
+    RunFacts facts;                         // the list counters and the redo count of a completed run of the tile path
+    int64_t inexact_tiles = -1;             // tiles that are not exact under the parameters now set (-1: not counted yet; choose_pipeline counts)
     // annotation
     int64_t n_tx = 0, n_anno_exon = 0;
     DevBuf<TxHdr> hdr;
@@ -206,7 +221,7 @@ struct l2r_ctx {
     bool have_win = false;
     // work + results
     int64_t n_tiles = 0, n_tiles256 = 0;
-    DevBuf<uint32_t> local, tile_base, ex_off, info, tile_acc, tile_acc_ex, tile_acc_at, tile_acc_ex_at, tile_chunk, tile_rchunk, totals;  // totals[0]=exons [1]=accepted [2]=accepted exons [3]=redo count [4],[5]=chunk cursor of the accepted list (one 64-bit word: exon slot low, record slot high)
+    DevBuf<uint32_t> local, tile_base, ex_off, info, tile_acc, tile_acc_ex, tile_acc_at, tile_acc_ex_at, tile_chunk, tile_rchunk, totals;  // totals: TOT_WORDS words, by name TOT_* (l2r_kernels.hip.h)
     DevBuf<uint32_t> redo;                  // reads the fast kernel hands to the generic one
     DevBuf<uint8_t> order;                  // per tile: reads by falling exon count (pass A)
     DevBuf<TileDesc> desc;
@@ -221,7 +236,6 @@ struct l2r_ctx {
     DevBuf<int32_t> acc_start, acc_end;
     DevBuf<uint8_t> acc_flag;
     bool ran = false;
-    bool check_stages = false;              // L2R_CHECK
     DevBuf<unsigned long long> stamps;      // diagnostics, L2R_STAMPS=1
     uint32_t h_totals[3] = {0, 0, 0};
     bool totals_valid = false;
@@ -231,9 +245,36 @@ struct l2r_ctx {
 // What completed runs have shown about the tile path's lists and the inexact tiles: forgotten wherever inputs, parameters or outputs change
 static void forget_list_state(l2r_ctx *c)
 {
-    c->lists_known = false; c->lists_empty = false; c->redo_empty = false; c->lists_heavy = false;
+    c->facts = RunFacts{};
     c->inexact_tiles = -1;
 }
+
+// A completed run left nothing to the list-driven kernels behind k_tile (k_probe_slab, the WIDE instance / k_probe_slab_wide, k_tile_chunk /
+// k_probe_slab_chunked): what ends up on their lists depends on nothing else, so none of them is launched until something changes
+static bool lists_empty(const RunFacts &f) { return f.n_fb == 0u && f.n_wide == 0u && f.n_chunk == 0u && f.n_late == 0u; }
+// ... or left most tiles in slab form (an isoform-rich annotation): k_tile would only walk for them, which k_walk_slab does faster -- later
+// runs take the slab pipeline.  (The tiles k_tile's WIDE instance / k_tile_chunk take are no burden of the tile path.)
+static bool lists_heavy(const l2r_ctx *c)
+{
+    const RunFacts &f = c->facts;
+    return 2ull * ((unsigned long long)f.n_fb + (c->wide_direct ? f.n_wide_rest : f.n_wide) + f.chunk_rest) > (unsigned long long)c->n_tiles;
+}
+// Does a kernel over a list of n entries (as a completed run left it) run: unless that run has shown the list empty (L2R_LAUNCH_ALL: always)
+static bool list_runs(const l2r_ctx *c, unsigned long long n) { return !c->facts.known || n != 0ull || c->env_launch_all; }
+// ... and its grid when it has a workgroup per entry: the list's length once a run has shown it, until then one for every tile (most leave at once)
+static unsigned list_grid(const l2r_ctx *c, uint32_t n) { return c->facts.known ? std::max(n, 1u) : (unsigned)std::max<int64_t>(c->n_tiles, 1); }
+
+// The tile path's two blocks of list counters take turns run by run (SlabArgs::list_cnt_next): lc_flip names the block of the next run to
+// be launched.  Three addresses: the block a run being launched counts in, the one it clears for the run behind it, and -- between
+// runs, when end_of_run has flipped -- the block of the run that has just ended (of two blocks, the one that is not the next run's).
+static uint32_t *lc_this_run(const l2r_ctx *c) { return c->list_cnt.p + LC_WORDS * (c->lc_flip & 1u); }
+static uint32_t *lc_next_run(const l2r_ctx *c) { return c->list_cnt.p + LC_WORDS * ((c->lc_flip & 1u) ^ 1u); }
+static uint32_t *lc_last_run(const l2r_ctx *c) { return lc_next_run(c); }
+// Both blocks cleared and the turn back at block 0: at an upload, and in front of the first tile run behind a slab run (whose kernels
+// leave their own counts in block 0)
+static hipError_t lc_reset(l2r_ctx *c) { c->lc_flip = 0; return hipMemsetAsync(c->list_cnt.p, 0, 2 * LC_WORDS * sizeof(uint32_t), c->stream); }
+// A run has been launched: the list counters and lb_sup (SlabArgs::lb_sup) change turns behind a run of the tile path
+static void end_of_run(l2r_ctx *c, bool tile) { if (tile) { c->lb_flip ^= 1u; c->lc_flip ^= 1u; } c->prev_run_tile = tile; }
 
 static DevParams dev_params(const l2r_ctx *c)
 {
@@ -263,6 +304,19 @@ template <typename F> static void with_flag(bool on, F &&f)
 {
     if (on) f(std::true_type());
     else f(std::false_type());
+}
+
+// One instance of k_tile (l2r_tile.hip.h): the general one, WIDE over wide_list, EXACT over the tiles k_describe_scan<true> marked.
+// (A template: in front of the C linkage block, with the other two.)
+template <bool WIDE, bool EXACT>
+static void launch_k_tile(const l2r_ctx *c, const DevParams &p, const SlabArgs &sa, unsigned grid, hipStream_t st)
+{
+    // (k_tile decides acceptance itself, junction table or not; the WIDE instance's tiles leave their accepted chunks to k_gather_accepted)
+    with_level(p.full_level, [&](auto L) { with_flag(p.ss_dis > 0, [&](auto D) { with_flag(!WIDE && (c->want & L2R_WANT_ACCEPTED), [&](auto A) {
+        if constexpr (!(WIDE && A))
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_tile<L, A, D, WIDE, EXACT>), dim3(grid), dim3(TILE_THREADS), 0, st, sa, (const TileRec *)c->tile_rec.p, (const TileWin *)c->tw.p,
+                               (const TileStat *)c->tile_stat.p, (const SlotRec *)c->slot_rec.p, c->tile_xbase.p);
+    }); }); });
 }
 
 static inline int64_t host_key(int32_t tid, int32_t x) { return ((int64_t)(tid + 1) << 32) | (uint32_t)x; }
@@ -950,7 +1004,7 @@ int l2r_upload_reads(l2r_ctx *c, const l2r_reads *r)
     size_t exb = (size_t)r->n_cigar + (size_t)N;
     if (c->wide_cigar) {
         unsigned long long *d_cnt = reinterpret_cast<unsigned long long *>(c->totals.p ? c->totals.p : nullptr);
-        if (!d_cnt) { if (c->totals.ensure(8)) return -2; d_cnt = reinterpret_cast<unsigned long long *>(c->totals.p); }
+        if (!d_cnt) { if (c->totals.ensure(TOT_WORDS)) return -2; d_cnt = reinterpret_cast<unsigned long long *>(c->totals.p); }
         HIP_TRY(hipMemsetAsync(d_cnt, 0, 8, c->stream));
         hipLaunchKernelGGL(k_count_cut_ops, dim3(4096), dim3(TILE_THREADS), 0, c->stream, (const uint32_t *)c->cig.p, (int64_t)r->n_cigar, d_cnt);
         unsigned long long cuts = 0;
@@ -962,7 +1016,7 @@ int l2r_upload_reads(l2r_ctx *c, const l2r_reads *r)
         c->redo.ensure((size_t)N) || c->order.ensure((size_t)N + TILE_THREADS) || c->desc.ensure((size_t)c->n_tiles) || c->win_hdr.ensure((size_t)c->n_tiles * WIN_TX) ||
         c->tile_base.ensure((size_t)c->n_tiles + 1) || c->tile_acc.ensure((size_t)c->n_tiles + 1) || c->tile_acc_ex.ensure((size_t)c->n_tiles + 1) ||
         c->tile_acc_at.ensure((size_t)c->n_tiles + 2) || c->tile_acc_ex_at.ensure((size_t)c->n_tiles + 2) ||
-        c->totals.ensure(8) || c->tile_chunk.ensure((size_t)c->n_tiles + 1) || c->tile_rchunk.ensure((size_t)c->n_tiles + 1) || c->ex_start.ensure(exb) || c->ex_end.ensure(exb) || c->ex_flag.ensure(exb) ||
+        c->totals.ensure(TOT_WORDS) || c->tile_chunk.ensure((size_t)c->n_tiles + 1) || c->tile_rchunk.ensure((size_t)c->n_tiles + 1) || c->ex_start.ensure(exb) || c->ex_end.ensure(exb) || c->ex_flag.ensure(exb) ||
         c->acc_rec.ensure((size_t)N) || c->acc_ex_off.ensure((size_t)N) ||
         c->acc_start.ensure(exb) || c->acc_end.ensure(exb) || c->acc_flag.ensure(exb) || (c->wide_cigar && c->walked.ensure((size_t)(c->n_tiles + 1) * LDS_EXON_CAP))) return -2;
     c->ex_cap = (int64_t)exb;
@@ -995,11 +1049,11 @@ int l2r_upload_reads(l2r_ctx *c, const l2r_reads *r)
         if (total < 0x7ffffff0ULL && ovf < 0x7ffffff0ULL) {
             sbase[T] = (uint32_t)total;                     // (rows of tile t = (sbase[t + 1] - sbase[t]) / 256)
             c->slab_ok = true;
-            if (c->tw64.ensure(T + 1) || c->wide_list.ensure(2 * (T + 1)) || c->chunk_list.ensure(2 * (T + 1)) || c->list_cnt.ensure(32) || c->tile_flags.ensure(T + 8) ||
+            if (c->tw64.ensure(T + 1) || c->wide_list.ensure(2 * (T + 1)) || c->chunk_list.ensure(2 * (T + 1)) || c->list_cnt.ensure(2 * LC_WORDS) || c->tile_flags.ensure(T + 8) ||
                 c->lb_tile.ensure(T + 64) || c->lb_blk.ensure(T / LB_BLK + 64) || c->lb_sup.ensure(2 * ((T >> LB_SUP_SHIFT) + 64)) || c->fb_list.ensure(T + 1) || c->rest_list.ensure(T + 1) || c->tile_stat.ensure(T + 1) || c->sup_stat.ensure((T >> LB_SUP_SHIFT) + 2) ||
                 (!c->wide_cigar && c->slot_rec.ensure((T + 1) * TILE_THREADS))) return -2;
             HIP_TRY(hipMemsetAsync(c->lb_sup.p, 0, 2 * ((T >> LB_SUP_SHIFT) + 64) * 8, c->stream)); c->lb_flip = 0;      // (two arrays taking turns; from then on each is cleared by the run in front of its own)      // (an isoform-rich annotation makes EVERY tile wide: 2.4 KB each)
-            HIP_TRY(hipMemsetAsync(c->list_cnt.p, 0, 128, c->stream)); c->lc_flip = 0; c->prev_run_tile = false;
+            HIP_TRY(lc_reset(c)); c->prev_run_tile = false;
             if (c->tile_sbase.ensure(T + 1) || c->ovf_cursor.ensure(1) || c->tw.ensure(T + 1) || c->tile_total.ensure(T + 2) || c->tile_xbase.ensure(T + 2) || c->tile_span.ensure(12 * (T + 1)) ||
                 c->s_pre.ensure((size_t)N + 1) || c->s_loc.ensure((size_t)N + 1) ||
                 c->slab_row.ensure((size_t)total + 4) ||
@@ -1193,7 +1247,7 @@ static Pipeline choose_pipeline(l2r_ctx *c, const DevParams &p)
     }
     if (c->inexact_tiles * 50 > c->n_tiles + 800 && !c->env_tile_anyway) return Pipeline::slab;
     // (measured: cfg3_iso40 -- every tile wide or chunked -- 1.34 ms on this path against 1.26 on the slab pipeline)
-    if (c->lists_known && c->lists_heavy && !c->env_tile_anyway) return Pipeline::slab;
+    if (c->facts.known && lists_heavy(c) && !c->env_tile_anyway) return Pipeline::slab;
     return Pipeline::tile;
 }
 
@@ -1211,8 +1265,8 @@ static FastArgs fast_args(const l2r_ctx *c, const DevParams &p, const SiteTabs &
     fa.walked = c->walked.p; fa.local = c->local.p; fa.order = c->order.p; fa.tile_base = c->tile_base.p; fa.j0 = j0; fa.desc = c->desc.p; fa.win_hdr = c->win_hdr.p;
     fa.hdr = c->hdr.p; fa.st = tabs.st; fa.en = tabs.en;
     fa.ex_off = c->ex_off.p; fa.ex_start = c->ex_start.p; fa.ex_end = c->ex_end.p; fa.ex_flag = c->ex_flag.p; fa.info = c->info.p; fa.ref_tx = c->ref_tx.p;
-    fa.tile_acc = c->tile_acc.p; fa.tile_acc_ex = c->tile_acc_ex.p; fa.redo_count = c->totals.p + 3; fa.redo = c->redo.p;
-    fa.tile_chunk = c->tile_chunk.p; fa.tile_rchunk = c->tile_rchunk.p; fa.chunk_cursor = (unsigned long long *)(c->totals.p + 4);
+    fa.tile_acc = c->tile_acc.p; fa.tile_acc_ex = c->tile_acc_ex.p; fa.redo_count = c->totals.p + TOT_REDO; fa.redo = c->redo.p;
+    fa.tile_chunk = c->tile_chunk.p; fa.tile_rchunk = c->tile_rchunk.p; fa.chunk_cursor = (unsigned long long *)(c->totals.p + TOT_CHUNK_CURSOR);
     fa.acc_start = c->acc_start.p; fa.acc_end = c->acc_end.p; fa.acc_flag = c->acc_flag.p; fa.acc_rec = (AccRec *)c->acc_rec.p; fa.acc_ex_off = c->acc_ex_off.p; fa.first_read = c->first_read;
     fa.stamps = c->stamps.p; fa.p = p;
     return fa;
@@ -1233,7 +1287,7 @@ static uint32_t split_mode(const l2r_ctx *c)
 {
     if (!c->tile_split || !c->rest_list.p) return SPLIT_OFF;
     const uint32_t fits = (uint32_t)std::min<int64_t>((int64_t)c->n_cu * 4, c->tile_resident / 2);
-    if (c->lists_known) return c->n_rest_tiles <= fits ? SPLIT_ON : SPLIT_OFF;
+    if (c->facts.known) return c->facts.n_rest <= fits ? SPLIT_ON : SPLIT_OFF;
     return split_wait_free(c) ? SPLIT_ON : SPLIT_LIST;
 }
 
@@ -1249,12 +1303,12 @@ static SlabArgs slab_args(const l2r_ctx *c, const FastArgs &fa, const CursorDir 
     sa.tw64 = (c->ablate & 4) ? nullptr : c->tw64.p;
     sa.chunk_on = (c->ablate & 32) ? 0u : 1u;          // (L2R_ABLATE bit 2: no 64-member windows, bit 5: no chunked windows)
     sa.wide_list = c->wide_list.p; sa.chunk_list = c->chunk_list.p; sa.list_cnt = c->list_cnt.p; sa.list_cnt_next = nullptr; sa.tile_flags = c->tile_flags.p;
-    if (tile) { sa.list_cnt = c->list_cnt.p + 16 * (c->lc_flip & 1u); sa.list_cnt_next = c->list_cnt.p + 16 * ((c->lc_flip & 1u) ^ 1u); }
+    if (tile) { sa.list_cnt = lc_this_run(c); sa.list_cnt_next = lc_next_run(c); }
     {   const size_t sup_words = (size_t)(c->n_tiles >> LB_SUP_SHIFT) + 64;
         sa.lb_sup = c->lb_sup.p ? c->lb_sup.p + (c->lb_flip ? sup_words : 0) : nullptr;
         sa.lb_sup_next = c->lb_sup.p ? c->lb_sup.p + (c->lb_flip ? 0 : sup_words) : nullptr;
         sa.n_sup = (uint32_t)(c->n_tiles >> LB_SUP_SHIFT) + 1u; }
-    sa.lb_tile = c->lb_tile.p; sa.lb_blk = c->lb_blk.p; sa.lb_err = c->totals.p + 6; sa.fb_list = c->fb_list.p; sa.exon_total = c->totals.p + 0; sa.tile_stat = c->tile_stat.p; sa.sup_stat = c->sup_stat.p;
+    sa.lb_tile = c->lb_tile.p; sa.lb_blk = c->lb_blk.p; sa.lb_err = c->totals.p + TOT_LB_ERR; sa.fb_list = c->fb_list.p; sa.exon_total = c->totals.p + TOT_EXONS; sa.tile_stat = c->tile_stat.p; sa.sup_stat = c->sup_stat.p;
     sa.sj = SjDir{CursorDir{c->sj_key.p, c->sj_cdir.p, c->sj_cbase.p, c->sj_ntid, (int32_t)c->n_sj}, c->sj_ddir.p, c->sj_dbase.p, c->sj_ntid, c->sj_row.p};
     sa.has_wide_keys = c->n_wide > 0 ? 1u : 0u;
     sa.wide_direct_on = (tile && c->wide_direct && c->tw64.p && !(c->ablate & 4)) ? 1u : 0u;
@@ -1295,11 +1349,11 @@ static int launch_classic(l2r_ctx *c, hipEvent_t *ev, const DevParams &p, const 
     with_flag(c->wide_cigar, [&](auto W) {
         hipLaunchKernelGGL(HIP_KERNEL_NAME(k_pass_a<W>), dim3(gt), dim3(TILE_THREADS), W ? pass_a_dynamic_lds(c->reads_per_tile) : 0, s, c->n_reads, c->r_tid.p, c->r_pos.p,
                            c->cig_off.p, c->cig.p, cd, tabs, p, (c->sorted ? (const int32_t *)nullptr : (const int32_t *)c->win_start.p), c->j0.p, c->local.p, c->order.p,
-                           c->tile_base.p, c->desc.p, c->totals.p + 3, (const TxHdr *)c->hdr.p, c->win_hdr.p, (const uint32_t *)c->tile_first.p, c->walked.p);
+                           c->tile_base.p, c->desc.p, c->totals.p + TOT_REDO, (const TxHdr *)c->hdr.p, c->win_hdr.p, (const uint32_t *)c->tile_first.p, c->walked.p);
     });
     MARK(ST_SCAN1);
     {
-        ScanJobs jobs = {}; jobs.job[0] = ScanJob{c->tile_base.p, c->n_tiles, c->totals.p + 0}; jobs.job[1] = jobs.job[0];
+        ScanJobs jobs = {}; jobs.job[0] = ScanJob{c->tile_base.p, c->n_tiles, c->totals.p + TOT_EXONS}; jobs.job[1] = jobs.job[0];
         hipLaunchKernelGGL(k_scan_u32, dim3(1), dim3(1024), 0, s, jobs);
     }
     MARK(ST_FAST);
@@ -1327,12 +1381,12 @@ static int launch_slab(l2r_ctx *c, hipEvent_t *ev, const DevParams &p, const Sla
     {   // the tiles' exon counts -> their first slots in the read-order result arrays (tile_xbase; the sum = the exon count): the
         // first workgroups of the launch, a segment each; the tiles' descriptors and windows, sixteen lanes per tile, and the lists
         // of the 64-bit-mask and the chunked kernel: the workgroups behind them (l2r_slab.hip.h)
-        const DescribeScan job{c->tile_total.p, c->tile_xbase.p, c->totals.p + 0, c->n_tiles};
+        const DescribeScan job{c->tile_total.p, c->tile_xbase.p, c->totals.p + TOT_EXONS, c->n_tiles};
         unsigned n_scan = (unsigned)std::max<int64_t>((c->n_tiles + DESCRIBE_SEG - 1) / DESCRIBE_SEG, 1);
         if (c->n_tiles > c->seg_max) {
             // (very large shards: one workgroup scans, in a launch of its own)
             HIP_TRY(hipMemcpyAsync(c->tile_xbase.p, c->tile_total.p, (size_t)c->n_tiles * 4, hipMemcpyDeviceToDevice, s));
-            ScanJobs jobs = {}; jobs.job[0] = ScanJob{c->tile_xbase.p, c->n_tiles, c->totals.p + 0}; jobs.job[1] = jobs.job[0];
+            ScanJobs jobs = {}; jobs.job[0] = ScanJob{c->tile_xbase.p, c->n_tiles, c->totals.p + TOT_EXONS}; jobs.job[1] = jobs.job[0];
             hipLaunchKernelGGL(k_scan_u32, dim3(1), dim3(1024), 0, s, jobs);
             n_scan = 0;
         }
@@ -1350,69 +1404,51 @@ static int launch_slab(l2r_ctx *c, hipEvent_t *ev, const DevParams &p, const Sla
 static int launch_tile(l2r_ctx *c, hipEvent_t *ev, const DevParams &p, const SlabArgs &sa, bool skip_lists)
 {
     hipStream_t s = c->stream;
-    const DescribeScan job{c->tile_total.p, c->tile_xbase.p, c->totals.p + 0, c->n_tiles};
+    const RunFacts &f = c->facts;
+    const DescribeScan job{c->tile_total.p, c->tile_xbase.p, c->totals.p + TOT_EXONS, c->n_tiles};
     const unsigned gd = (unsigned)std::max<int64_t>((c->n_tiles + DESCRIBE_TILES - 1) / DESCRIBE_TILES, 1);
     hipLaunchKernelGGL(HIP_KERNEL_NAME(k_describe_scan<true>), dim3(gd), dim3(TILE_THREADS), 0, s, sa, job, 0u, (const TileRec *)c->tile_rec.p);
     MARK(ST_SCAN1);
-    // the exact 64-bit-mask tiles straight from their CIGARs: k_tile's WIDE instance, a workgroup per entry of wide_list; the exact
-    // tiles of the chunked kernel: k_tile_chunk, a workgroup per entry of chunk_list (the lists' lengths are known to the host once a run
-    // has completed: until then a grid for every tile, most of which leave at once).  Both beside the plain instance, on streams of
-    // their own (see l2r_ctx::side); with per-stage events or L2R_CHECK one behind the other.
-    const bool wide_launch = !skip_lists && sa.wide_direct_on && !(c->lists_known && c->n_wide_tiles == 0u && !c->env_launch_all);
-    const bool chunk_launch = !skip_lists && sa.chunk_direct_on && !(c->lists_known && c->n_chunk_tiles == 0u && !c->env_launch_all);
-    const bool beside = c->side_on && !ev && !c->check_stages;
+    // ---- the plan: which instances run, and where
     // the split of k_tile: the EXACT instance over every tile number (it leaves at once where k_describe_scan has not marked the tile),
-    // the general instance over the rest list -- not launched once a completed run has shown that list empty
+    // the general instance over the rest list
     const bool split = sa.split_on == SPLIT_ON;
-    const bool rest_beside = beside && split_wait_free(c);      // (else on the main stream, in front of the EXACT instance: split_mode)
-    const bool rest_launch = split && !(c->lists_known && c->n_rest_tiles == 0u && !c->env_launch_all);
-    const unsigned gf = fused_grid(c->n_tiles);
-    const unsigned gr = c->lists_known ? std::max(c->n_rest_tiles, 1u) : (unsigned)std::max<int64_t>(c->n_tiles, 1);
-    auto launch_general = [&](unsigned grid, hipStream_t st) {
-        with_level(p.full_level, [&](auto L) { with_flag(p.ss_dis > 0, [&](auto D) { with_flag(c->want & L2R_WANT_ACCEPTED, [&](auto A) {
-            // (k_tile decides acceptance itself, junction table or not)
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_tile<L, A, D>), dim3(grid), dim3(TILE_THREADS), 0, st, sa, (const TileRec *)c->tile_rec.p, (const TileWin *)c->tw.p,
-                               (const TileStat *)c->tile_stat.p, (const SlotRec *)c->slot_rec.p, c->tile_xbase.p);
-        }); }); });
-    };
-    // (a general instance with tiles that others wait for: in front of everything that may wait, the side instances included -- they
-    //  fork behind it)
-    if (rest_launch && !rest_beside) launch_general(gr, s);
-    if (beside && (wide_launch || chunk_launch || (rest_launch && rest_beside))) HIP_TRY(hipEventRecord(c->ev_fork, s));
-    if (rest_launch && rest_beside) {
-        // (on the WIDE instance's stream, in front of it: the WIDE instance starts when this one has ended)
-        HIP_TRY(hipStreamWaitEvent(c->side[0], c->ev_fork, 0));
-        launch_general(gr, c->side[0]);
-        if (!wide_launch) HIP_TRY(hipEventRecord(c->ev_join[0], c->side[0]));      // (else the WIDE instance behind it on this stream records the join)
-    }
-    if (wide_launch) {
-        hipStream_t sw = beside ? c->side[0] : s;
-        if (beside && !(rest_launch && rest_beside)) HIP_TRY(hipStreamWaitEvent(sw, c->ev_fork, 0));
-        const unsigned gwd = c->lists_known ? std::max(c->n_wide_tiles, 1u) : (unsigned)std::max<int64_t>(c->n_tiles, 1);
-        with_level(p.full_level, [&](auto L) { with_flag(p.ss_dis > 0, [&](auto D) {
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_tile<L, false, D, true>), dim3(gwd), dim3(TILE_THREADS), 0, sw, sa, (const TileRec *)c->tile_rec.p, (const TileWin *)c->tw.p,
-                               (const TileStat *)c->tile_stat.p, (const SlotRec *)c->slot_rec.p, c->tile_xbase.p);
-        }); });
-        if (beside) HIP_TRY(hipEventRecord(c->ev_join[0], sw));
-    }
-    const unsigned gcd = c->lists_known ? std::max(c->n_chunk_tiles, 1u) : (unsigned)std::max<int64_t>(c->n_tiles, 1);
-    if (chunk_launch && beside) {
+    const bool rest_launch = split && list_runs(c, f.n_rest);
+    // the exact 64-bit-mask tiles straight from their CIGARs: k_tile's WIDE instance, a workgroup per entry of wide_list; the exact
+    // tiles of the chunked kernel: k_tile_chunk, a workgroup per entry of chunk_list
+    const bool wide_launch = !skip_lists && sa.wide_direct_on && list_runs(c, f.n_wide);
+    const bool chunk_launch = !skip_lists && sa.chunk_direct_on && list_runs(c, f.n_chunk);
+    // beside the plain instance, on streams of their own (see l2r_ctx::side); with per-stage events or L2R_CHECK one behind the other.
+    // The general instance over the rest list goes beside it only in a run where nobody waits for a count; else on the main stream in
+    // front of everything that may wait for its tiles, the side instances included -- they fork behind it (split_mode)
+    const bool beside = c->side_on && !ev && !c->check_stages;
+    const bool rest_side = rest_launch && beside && split_wait_free(c);
+    const bool wide_side = wide_launch && beside, chunk_side = chunk_launch && beside;
+    const bool side0 = rest_side || wide_side, side1 = chunk_side;       // side[0]: the general instance, the WIDE instance behind it; side[1]: k_tile_chunk
+    const unsigned gf = fused_grid(c->n_tiles), gr = list_grid(c, f.n_rest), gwd = list_grid(c, f.n_wide), gcd = list_grid(c, f.n_chunk);
+    // ---- fork
+    if (rest_launch && !rest_side) launch_k_tile<false, false>(c, p, sa, gr, s);
+    if (side0 || side1) HIP_TRY(hipEventRecord(c->ev_fork, s));
+    // ---- launches: side[0] (its join is recorded behind whichever launch came last on it), side[1], the main stream
+    if (side0) HIP_TRY(hipStreamWaitEvent(c->side[0], c->ev_fork, 0));
+    if (rest_side) launch_k_tile<false, false>(c, p, sa, gr, c->side[0]);
+    if (wide_launch) launch_k_tile<true, false>(c, p, sa, gwd, wide_side ? c->side[0] : s);
+    if (side0) HIP_TRY(hipEventRecord(c->ev_join[0], c->side[0]));
+    if (side1) {
         HIP_TRY(hipStreamWaitEvent(c->side[1], c->ev_fork, 0));
         launch_tile_chunk(c, p, sa, gcd, 0u, c->side[1]);
         HIP_TRY(hipEventRecord(c->ev_join[1], c->side[1]));
     }
-    if (!split) launch_general(gf, s);
-    else with_level(p.full_level, [&](auto L) { with_flag(p.ss_dis > 0, [&](auto D) { with_flag(c->want & L2R_WANT_ACCEPTED, [&](auto A) {
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_tile<L, A, D, false, true>), dim3(gf), dim3(TILE_THREADS), 0, s, sa, (const TileRec *)c->tile_rec.p, (const TileWin *)c->tw.p,
-                           (const TileStat *)c->tile_stat.p, (const SlotRec *)c->slot_rec.p, c->tile_xbase.p);
-    }); }); });
+    if (split) launch_k_tile<false, true>(c, p, sa, gf, s);
+    else launch_k_tile<false, false>(c, p, sa, gf, s);
     MARK(ST_FAST);
-    if (chunk_launch && !beside) launch_tile_chunk(c, p, sa, gcd, 0u, s);
-    if (rest_launch && rest_beside && !wide_launch) HIP_TRY(hipStreamWaitEvent(s, c->ev_join[0], 0));
-    if (wide_launch && beside) HIP_TRY(hipStreamWaitEvent(s, c->ev_join[0], 0));
-    if (chunk_launch && beside) HIP_TRY(hipStreamWaitEvent(s, c->ev_join[1], 0));
+    if (chunk_launch && !chunk_side) launch_tile_chunk(c, p, sa, gcd, 0u, s);
+    // ---- joins
+    if (side0) HIP_TRY(hipStreamWaitEvent(s, c->ev_join[0], 0));
+    if (side1) HIP_TRY(hipStreamWaitEvent(s, c->ev_join[1], 0));
+    // k_probe_slab over the tiles k_tile left in slab form
     const unsigned gl = (unsigned)std::min<int64_t>(c->n_tiles ? c->n_tiles : 1, (int64_t)c->n_cu * 2);
-    if (!skip_lists && !(c->lists_known && c->fb_empty && !c->env_launch_all)) launch_probe(c, p, sa, true, false, gl);
+    if (!skip_lists && list_runs(c, f.n_fb)) launch_probe(c, p, sa, true, false, gl);
     return 0;
 }
 
@@ -1421,8 +1457,8 @@ static void launch_lists(l2r_ctx *c, const DevParams &p, const SlabArgs &sa, boo
 {
     if (skip_lists) return;
     hipStream_t s = c->stream;
-    const bool known = tile && c->lists_known && !c->env_launch_all;      // (a completed run of the tile path has shown a list empty)
-    if (!(known && c->wide_rest_empty)) {
+    const RunFacts &f = c->facts;       // (what a completed run of the tile path has shown; the slab pipeline launches all three)
+    if (!tile || list_runs(c, f.n_wide_rest)) {
         // the tiles with 33 .. 63 window members
         const WideArgs wa{c->tw64.p};
         const unsigned gw = (unsigned)std::min<int64_t>(c->n_tiles ? c->n_tiles : 1, (int64_t)c->n_cu * 5);
@@ -1431,13 +1467,12 @@ static void launch_lists(l2r_ctx *c, const DevParams &p, const SlabArgs &sa, boo
                                (const uint32_t *)c->tile_sbase.p, (const TileWin *)c->tw.p, (const uint32_t *)c->tile_xbase.p, (const TileStat *)(tile ? c->tile_stat.p : nullptr));
         });
     }
-    if (sa.chunk_direct_on && !(known && c->n_late_tiles == 0u)) {
+    if (sa.chunk_direct_on && list_runs(c, f.n_late)) {
         // the tiles a one-window kernel handed on late (a key in several entries): k_tile_chunk once more, over that list
         // (every entry needs its workgroup: k_probe_slab_chunked skips what this launch takes)
-        const unsigned gl2 = c->lists_known ? std::max(c->n_late_tiles, 1u) : (unsigned)std::max<int64_t>(c->n_tiles, 1);
-        launch_tile_chunk(c, p, sa, gl2, 1u, s);
+        launch_tile_chunk(c, p, sa, list_grid(c, f.n_late), 1u, s);
     }
-    if (sa.chunk_on && !(known && c->chunk_rest_empty)) {
+    if (sa.chunk_on && (!tile || list_runs(c, f.chunk_rest))) {
         // the tiles without a window record, or with a dictionary key in several entries
         const unsigned gc = (unsigned)std::min<int64_t>(c->n_tiles ? c->n_tiles : 1, (int64_t)c->n_cu * 4);
         with_level(p.full_level, [&](auto L) {
@@ -1456,18 +1491,17 @@ static int launch_tail(l2r_ctx *c, hipEvent_t *ev, const DevParams &p, const Cur
     const bool tile = c->pipe == Pipeline::tile;
     const unsigned gt = (unsigned)(c->n_tiles ? c->n_tiles : 1), g256 = (unsigned)(c->n_tiles256 ? c->n_tiles256 : 1);
     MARK(ST_GENERIC);
-    // (one-kernel tile path: a completed run of the same inputs and parameters has left nothing on the redo list and nothing to the
-    //  list-driven kernels -- no read is left for the generic kernel, and what it used to clear for the next run is cleared in front)
-    // (... or nothing on the redo list: the list counters need no launch for their clearing, they take turns)
-    const bool nothing_left = tile && c->lists_known && c->redo_empty && (c->lists_empty || c->n_sj == 0) && !c->env_launch_all;
-    if (tile) { c->lb_flip ^= 1u; c->lc_flip ^= 1u; }
-    c->prev_run_tile = tile;
+    // (one-kernel tile path: a completed run of the same inputs and parameters has left nothing on the redo list -- no read is left for
+    //  the generic kernel, and the list counters need no launch for their clearing, they take turns -- and nothing to the list-driven
+    //  kernels or no junction table: no read is left for the junction check either, k_tile has checked every read whose verdict it made)
+    const bool nothing_left = tile && c->facts.known && c->facts.redo_empty && (lists_empty(c->facts) || c->n_sj == 0) && !c->env_launch_all;
+    end_of_run(c, tile);
     if (!nothing_left) {
         const unsigned gg = (unsigned)std::min<int64_t>(c->n_tiles ? c->n_tiles * 4 : 1, 4096);      // one wave per listed read, grid-stride
-        hipLaunchKernelGGL(k_classify_generic, dim3(gg), dim3(TILE_THREADS), 0, s, c->totals.p + 3, c->redo.p, c->r_tid.p, c->r_rev.p,
+        hipLaunchKernelGGL(k_classify_generic, dim3(gg), dim3(TILE_THREADS), 0, s, c->totals.p + TOT_REDO, c->redo.p, c->r_tid.p, c->r_rev.p,
                            (c->pipe != Pipeline::classic ? (const int32_t *)nullptr : j0),
                            c->hdr.p, c->anno_ex.p, p, c->ex_off.p, c->ex_start.p, c->ex_end.p, c->ex_flag.p, c->info.p, c->ref_tx.p,
-                           c->tile_acc.p, c->tile_acc_ex.p, (const uint32_t *)c->tile_first.p, (int)c->n_tiles, cd, (uint32_t *)nullptr);
+                           c->tile_acc.p, c->tile_acc_ex.p, (const uint32_t *)c->tile_first.p, (int)c->n_tiles, cd);
     }
     MARK(ST_SJ);
     // (one-kernel tile path: k_tile has checked every read whose verdict it made; with nothing on the redo list and nothing left to the
@@ -1485,22 +1519,22 @@ static int launch_tail(l2r_ctx *c, hipEvent_t *ev, const DevParams &p, const Cur
     }
     MARK(ST_SCAN2);
     if (c->want & L2R_WANT_ACCEPTED) {
-        // the deferred tiles' counts -> their places behind the fused chunks (tile_acc_at / tile_acc_ex_at; the sums = totals[1], [2])
+        // the deferred tiles' counts -> their places behind the fused chunks (tile_acc_at / tile_acc_ex_at; the sums = totals[TOT_ACCEPTED], [TOT_ACCEPTED_EXONS])
         if (c->n_tiles <= c->seg_max) {
             const unsigned n_seg = (unsigned)std::max<int64_t>((c->n_tiles + SEG_COUNT - 1) / SEG_COUNT, 1);
-            hipLaunchKernelGGL(k_scan_segments, dim3(2u * n_seg), dim3(TILE_THREADS), 0, s, SegScan{c->tile_acc.p, c->tile_acc_at.p, c->totals.p + 1, c->n_tiles},
-                               SegScan{c->tile_acc_ex.p, c->tile_acc_ex_at.p, c->totals.p + 2, c->n_tiles}, (uint32_t)n_seg);
+            hipLaunchKernelGGL(k_scan_segments, dim3(2u * n_seg), dim3(TILE_THREADS), 0, s, SegScan{c->tile_acc.p, c->tile_acc_at.p, c->totals.p + TOT_ACCEPTED, c->n_tiles},
+                               SegScan{c->tile_acc_ex.p, c->tile_acc_ex_at.p, c->totals.p + TOT_ACCEPTED_EXONS, c->n_tiles}, (uint32_t)n_seg);
         } else {
             HIP_TRY(hipMemcpyAsync(c->tile_acc_at.p, c->tile_acc.p, (size_t)c->n_tiles * 4, hipMemcpyDeviceToDevice, s));
             HIP_TRY(hipMemcpyAsync(c->tile_acc_ex_at.p, c->tile_acc_ex.p, (size_t)c->n_tiles * 4, hipMemcpyDeviceToDevice, s));
-            ScanJobs jobs = {}; jobs.job[0] = ScanJob{c->tile_acc_at.p, c->n_tiles, c->totals.p + 1}; jobs.job[1] = ScanJob{c->tile_acc_ex_at.p, c->n_tiles, c->totals.p + 2};
+            ScanJobs jobs = {}; jobs.job[0] = ScanJob{c->tile_acc_at.p, c->n_tiles, c->totals.p + TOT_ACCEPTED}; jobs.job[1] = ScanJob{c->tile_acc_ex_at.p, c->n_tiles, c->totals.p + TOT_ACCEPTED_EXONS};
             hipLaunchKernelGGL(k_scan_u32, dim3(2), dim3(1024), 0, s, jobs);
         }
     }
     MARK(ST_GATHER);
     if (c->want & L2R_WANT_ACCEPTED)
         hipLaunchKernelGGL(k_gather_accepted, dim3((gt + GATHER_TILES - 1) / GATHER_TILES), dim3(TILE_THREADS), 0, s, (const uint32_t *)c->tile_first.p, c->first_read, c->info.p, c->ref_tx.p, c->ex_off.p,
-                           c->ex_start.p, c->ex_end.p, c->ex_flag.p, c->tile_acc_at.p, c->tile_acc_ex_at.p, c->tile_chunk.p, c->tile_rchunk.p, c->totals.p + 4,
+                           c->ex_start.p, c->ex_end.p, c->ex_flag.p, c->tile_acc_at.p, c->tile_acc_ex_at.p, c->tile_chunk.p, c->tile_rchunk.p, c->totals.p + TOT_CHUNK_CURSOR,
                            c->acc_rec.p, c->acc_ex_off.p, c->acc_start.p, c->acc_end.p, c->acc_flag.p, (uint32_t)c->n_tiles);
     MARK(ST_N);
     return 0;
@@ -1521,11 +1555,11 @@ static int launch_all(l2r_ctx *c, hipEvent_t *ev /* ST_N + 1 events or null */)
     else {
         const bool tile = c->pipe == Pipeline::tile;
         // (the list counters are whatever a slab run left: cleared in front of the first tile run behind one)
-        if (tile && !c->prev_run_tile) { HIP_TRY(hipMemsetAsync(c->list_cnt.p, 0, 128, c->stream)); c->lc_flip = 0; }
+        if (tile && !c->prev_run_tile) HIP_TRY(lc_reset(c));
         const SlabArgs sa = slab_args(c, fa, cd, tile);
         // (the three list-driven kernels behind k_tile: not launched once a completed run of the same inputs and parameters has shown
         //  their lists empty -- what ends up on them does not depend on anything else)
-        const bool skip_lists = tile && c->lists_known && c->lists_empty && !c->env_launch_all;
+        const bool skip_lists = tile && c->facts.known && lists_empty(c->facts) && !c->env_launch_all;
         rc = tile ? launch_tile(c, ev, p, sa, skip_lists) : launch_slab(c, ev, p, sa);
         if (!rc) launch_lists(c, p, sa, tile, skip_lists);
     }
@@ -1575,7 +1609,7 @@ int l2r_debug_counters(l2r_ctx *c, long long *out, int n)
     if (!c || !out || n < 4) return fail(-1, "[l2r_debug_counters] bad argument");
     HIP_TRY(hipSetDevice(c->device));
     uint32_t redo = 0;
-    if (c->totals.p) { HIP_TRY(hipMemcpyAsync(&redo, c->totals.p + 3, 4, hipMemcpyDeviceToHost, c->stream)); HIP_TRY(hipStreamSynchronize(c->stream)); }
+    if (c->totals.p) { HIP_TRY(hipMemcpyAsync(&redo, c->totals.p + TOT_REDO, 4, hipMemcpyDeviceToHost, c->stream)); HIP_TRY(hipStreamSynchronize(c->stream)); }
     out[0] = redo; out[1] = c->n_wide; out[2] = c->n_compact; out[3] = c->n_tiles;
     if (n >= 12) for (int k = 0; k < 8; ++k) out[4 + k] = 0;
     if (n >= 13) out[12] = 0;
@@ -1584,11 +1618,11 @@ int l2r_debug_counters(l2r_ctx *c, long long *out, int n)
     if (n >= 16) {                                        // one-kernel tile path, last run: entries of chunk_list k_tile_chunk declined, tiles handed to the chunked kernel late
         out[14] = 0; out[15] = 0;
         if (c->pipe == Pipeline::tile && c->ran && c->list_cnt.p) {
-            uint32_t lc[16];
-            HIP_TRY(hipMemcpyAsync(lc, c->list_cnt.p + 16 * ((c->lc_flip & 1u) ^ 1u), sizeof lc, hipMemcpyDeviceToHost, c->stream));
+            uint32_t lc[LC_WORDS];
+            HIP_TRY(hipMemcpyAsync(lc, lc_last_run(c), sizeof lc, hipMemcpyDeviceToHost, c->stream));
             HIP_TRY(hipStreamSynchronize(c->stream));
-            out[14] = lc[9]; out[15] = lc[8];
-            if (n >= 29) out[28] = lc[11];              // entries of the rest list: the tiles k_tile's general instance ran over beside the EXACT one (0: split off)
+            out[14] = lc[LC_DECLINED]; out[15] = lc[LC_LATE];
+            if (n >= 29) out[28] = lc[LC_REST];             // entries of the rest list: the tiles k_tile's general instance ran over beside the EXACT one (0: split off)
         }
     }
     if (n >= 12 && c->pipe != Pipeline::classic && c->ran && c->tw.p && c->n_tiles > 0) {     // slab pipeline: the descriptors k_walk_slab made (flags as the probe kernels left them)
@@ -1649,6 +1683,25 @@ int l2r_run(l2r_ctx *c)
     return 0;
 }
 
+// What a completed run of the tile path left on the lists of the kernels behind k_tile, and on the redo list: c->facts
+static int fetch_run_facts(l2r_ctx *c)
+{
+    uint32_t lc[LC_WORDS];
+    HIP_TRY(hipMemcpyAsync(lc, lc_last_run(c), sizeof lc, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    uint32_t redo_n = 1u;
+    HIP_TRY(hipMemcpyAsync(&redo_n, c->totals.p + TOT_REDO, 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    RunFacts &f = c->facts;
+    f.n_wide = lc[LC_WIDE]; f.n_chunk = lc[LC_CHUNK]; f.n_rest = lc[LC_REST]; f.n_late = lc[LC_LATE];
+    f.n_fb = lc[LC_FB]; f.n_wide_rest = lc[LC_WIDE_REST];
+    const bool tchunk = c->chunk_direct && !(c->ablate & 32);
+    f.chunk_rest = tchunk ? (unsigned long long)lc[LC_DECLINED] + lc[LC_DECLINED_LATE] : (unsigned long long)lc[LC_LATE] + lc[LC_CHUNK];
+    f.redo_empty = redo_n == 0u;
+    f.known = true;
+    return 0;
+}
+
 int l2r_sync(l2r_ctx *c)
 {
     if (!c) return fail(-1, "[l2r_sync] null context");
@@ -1659,41 +1712,18 @@ int l2r_sync(l2r_ctx *c)
         // result slots are not to be trusted): the SAME resident upload once more on the slab pipeline, which has no such wait -- and no
         // later run of this context takes the tile path again (the cause is the device's occupancy, not this input)
         uint32_t lb = 0u;
-        HIP_TRY(hipMemcpyAsync(&lb, c->totals.p + 6, 4, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipMemcpyAsync(&lb, c->totals.p + TOT_LB_ERR, 4, hipMemcpyDeviceToHost, c->stream));
         HIP_TRY(hipStreamSynchronize(c->stream));
         if (lb != 0u) {
             c->tile_starved = true; c->n_lb_fallback++;
-            c->lists_known = false; c->totals_valid = false;
+            forget_list_state(c); c->totals_valid = false;
             int rc = launch_all(c, nullptr);
             if (rc) return rc;
             HIP_TRY(hipStreamSynchronize(c->stream));
             snprintf(g_err, sizeof g_err, "[l2r_sync] note: k_tile's look-back starved; the run was done again on the slab pipeline (this context keeps to it)");
         }
     }
-    if (c->ran && c->pipe == Pipeline::tile && !c->lists_known && c->list_cnt.p) {
-        // what the run left on the lists of the kernels behind k_tile (k_classify_generic keeps the counts of the 64-bit-mask and the
-        // chunked kernel's lists in words 6, 7 when it clears them; word 4: k_probe_slab's)
-        uint32_t lc[16];
-        HIP_TRY(hipMemcpyAsync(lc, c->list_cnt.p + 16 * ((c->lc_flip & 1u) ^ 1u), sizeof lc, hipMemcpyDeviceToHost, c->stream));      // (the block of the run that has just ended: launch_all has flipped already)
-        lc[6] = lc[0]; lc[7] = lc[1];                              // (entries of wide_list / chunk_list: nobody clears them behind their readers any more)
-        HIP_TRY(hipStreamSynchronize(c->stream));
-        uint32_t redo_n = 1u;
-        HIP_TRY(hipMemcpyAsync(&redo_n, c->totals.p + 3, 4, hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(hipStreamSynchronize(c->stream));
-        // (lc[8]: tiles a one-window kernel handed to the chunked kernel late; lc[9]: entries of chunk_list k_tile_chunk declined)
-        c->lists_empty = lc[4] == 0u && lc[6] == 0u && lc[7] == 0u && lc[8] == 0u;
-        const bool tchunk = c->chunk_direct && !(c->ablate & 32);
-        // (what is left to k_probe_slab_chunked: with k_tile_chunk the entries it declined in its two launches, else every entry)
-        const unsigned long long chunk_rest = tchunk ? (unsigned long long)lc[9] + lc[10] : (unsigned long long)lc[8] + lc[7];
-        c->n_late_tiles = lc[8];
-        // (with k_tile's WIDE instance / k_tile_chunk the tiles they take are no burden of the tile path: what counts is what keeps the slab form)
-        c->lists_heavy = 2ull * ((unsigned long long)lc[4] + (c->wide_direct ? lc[5] : lc[6]) + chunk_rest) > (unsigned long long)c->n_tiles;
-        c->n_wide_tiles = lc[6]; c->wide_rest_empty = lc[5] == 0u; c->fb_empty = lc[4] == 0u;
-        c->n_chunk_tiles = lc[7]; c->chunk_rest_empty = chunk_rest == 0ull;
-        c->n_rest_tiles = lc[11];
-        c->redo_empty = redo_n == 0u;
-        c->lists_known = true;
-    }
+    if (c->ran && c->pipe == Pipeline::tile && !c->facts.known && c->list_cnt.p) return fetch_run_facts(c);
     return 0;
 }
 
@@ -1701,12 +1731,12 @@ static int fetch_totals(l2r_ctx *c)
 {
     if (!c->ran) return fail(-1, "no completed run on this context");
     if (c->totals_valid) return 0;
-    uint32_t dev[8];
+    uint32_t dev[TOT_WORDS];
     HIP_TRY(hipMemcpyAsync(dev, c->totals.p, sizeof dev, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     // accepted exons = the chunks the classification kernel placed itself (cursor) + the ones k_gather_accepted placed
-    if (c->pipe == Pipeline::tile && dev[6] != 0u) return fail(-2, "[l2r] k_tile: a tile waited in vain for the exon counts of the tiles in front of it and l2r_sync was not called behind the run (it does the run again on the slab pipeline)");
-    c->h_totals[0] = dev[0]; c->h_totals[1] = dev[1] + dev[5]; c->h_totals[2] = dev[2] + dev[4];
+    if (c->pipe == Pipeline::tile && dev[TOT_LB_ERR] != 0u) return fail(-2, "[l2r] k_tile: a tile waited in vain for the exon counts of the tiles in front of it and l2r_sync was not called behind the run (it does the run again on the slab pipeline)");
+    c->h_totals[0] = dev[TOT_EXONS]; c->h_totals[1] = dev[TOT_ACCEPTED] + dev[TOT_CHUNK_CURSOR + 1]; c->h_totals[2] = dev[TOT_ACCEPTED_EXONS] + dev[TOT_CHUNK_CURSOR];
     if (!(c->want & L2R_WANT_ACCEPTED)) c->h_totals[1] = c->h_totals[2] = 0;
     c->totals_valid = true;
     return 0;

@@ -44,6 +44,35 @@ constexpr int WIN_TX = 32;              // annotation transcripts in a tile's wi
 constexpr int SITE_SHIFT = 9;
 constexpr int DIS_MASK_MAX = 64;        // largest -d the mask kernels take (probe_near: a probe then looks at two 512-bp buckets at most)
 
+// The words of the engine's two small counter arrays, by name on the device and on the host.
+// List counters (SlabArgs::list_cnt, l2r_slab.hip.h): what the slab and the tile pipeline's kernels leave on each other's tile lists.
+// The tile path has TWO blocks of LC_WORDS words that take turns run by run (SlabArgs::list_cnt_next).
+constexpr int LC_WIDE = 0;              // entries of wide_list (k_describe_scan appends; k_tile's WIDE instance or k_probe_slab_wide reads)
+constexpr int LC_CHUNK = 1;             // entries of chunk_list (k_describe_scan appends; k_tile_chunk / k_probe_slab_chunked read)
+constexpr int LC_WIDE_CURSOR = 2;       // k_probe_slab_wide's work cursor
+constexpr int LC_CHUNK_CURSOR = 3;      // k_probe_slab_chunked's work cursor
+constexpr int LC_FB = 4;                // entries of fb_list: the tiles k_tile left in slab form for k_probe_slab
+constexpr int LC_WIDE_REST = 5;         // wide tiles k_tile kept in slab form for k_probe_slab_wide (listed behind wide_list's own entries)
+constexpr int LC_LATE = 8;              // tiles a one-window kernel handed to the chunked kernel late (chunk_list_append_late)
+constexpr int LC_DECLINED = 9;          // entries k_tile_chunk's first launch declined: left to k_probe_slab_chunked
+constexpr int LC_DECLINED_LATE = 10;    // ... and its late launch
+constexpr int LC_REST = 11;             // entries of rest_list: the tiles of k_tile's general instance beside the EXACT one
+constexpr int LC_WORDS = 16;            // words per block
+// Totals (l2r_ctx::totals): the run's sums and cursors.  FastArgs::redo_count points at TOT_REDO, and the first kernel of a run
+// clears the words from there up to the chunk cursor's second word through it.
+constexpr int TOT_EXONS = 0;            // exons of the run
+constexpr int TOT_ACCEPTED = 1;         // accepted reads k_gather_accepted placed
+constexpr int TOT_ACCEPTED_EXONS = 2;   // ... and their exons
+constexpr int TOT_REDO = 3;             // entries of the redo list (reads for k_classify_generic)
+constexpr int TOT_CHUNK_CURSOR = 4;     // chunk cursor of the accepted list, one 64-bit word in two: exon slot low, record slot high
+constexpr int TOT_LB_ERR = 6;           // set by a tile of k_tile that waited in vain for the counts in front of it
+constexpr int TOT_WORDS = 8;
+// (the first kernel of a run, one thread: the redo count and the two words of the chunk cursor, through the pointer at TOT_REDO)
+__device__ __forceinline__ void clear_run_counters(uint32_t *redo_count)
+{
+    redo_count[TOT_REDO - TOT_REDO] = 0u; redo_count[TOT_CHUNK_CURSOR - TOT_REDO] = 0u; redo_count[TOT_CHUNK_CURSOR + 1 - TOT_REDO] = 0u;
+}
+
 // One annotation transcript (file order), 48 B = three 16-byte loads.
 struct TxHdr {
     int32_t tid, start, end, ex_off;          // h0
@@ -433,7 +462,7 @@ void k_pass_a(int64_t n_reads, const int32_t *__restrict__ r_tid, const int32_t 
     const uint32_t r0 = tile_first[blockIdx.x], n_act = tile_first[blockIdx.x + 1] - r0;
     const int64_t r = (int64_t)r0 + threadIdx.x;
     const bool active = threadIdx.x < n_act;
-    if (blockIdx.x == 0 && threadIdx.x == 0) { redo_count[0] = 0u; redo_count[1] = 0u; redo_count[2] = 0u; }   // redo list and accepted-exon cursor: the kernels that fill them run after this one
+    if (blockIdx.x == 0 && threadIdx.x == 0) clear_run_counters(redo_count);   // redo list and accepted-exon cursor: the kernels that fill them run after this one
     uint32_t n = 0;
     bool unwalked = false;
     int j0 = INT32_MAX, tid = 0, pos = 0, el = 0;
@@ -648,7 +677,7 @@ struct ScanJob { uint32_t *v; int64_t n; uint32_t *total; };
 // lists: block 1 of a two-block launch (slab pipeline) does not scan: it lists the tiles of k_probe_slab_wide (TD_WIDE) and of
 // k_probe_slab_chunked (slab_tile_is_chunked) from the descriptors k_walk_slab left -- in tile order, beside the scan of the tiles' exon
 // counts, so the lists cost no launch and no tile appends to a shared counter (40 k appends to one address take 0.4 ms).
-// cnt[0] / cnt[1] = entries, cnt[2] / cnt[3] = the two kernels' work cursors (cleared here).
+// cnt[LC_WIDE] / cnt[LC_CHUNK] = entries, cnt[LC_WIDE_CURSOR] / cnt[LC_CHUNK_CURSOR] = the two kernels' work cursors (cleared here).
 struct TileLists { const uint32_t *flags0; uint32_t n_tiles, chunk_on; uint32_t *wide_list, *chunk_list, *cnt; };      // flags0: every tile's descriptor flags, densely (k_walk_slab)
 struct ScanJobs { ScanJob job[2]; TileLists lists; };
 // a tile k_probe_slab_chunked takes (l2r_chunk.hip.h): no window record (window beyond 63 members, dictionary slices beyond the
@@ -755,7 +784,7 @@ void k_scan_u32(ScanJobs jobs)
             if (threadIdx.x == 0) { s_base[0] += tw_; s_base[1] += tc_; }
             __syncthreads();
         }
-        if (threadIdx.x == 0) { L.cnt[0] = s_base[0]; L.cnt[1] = s_base[1]; L.cnt[2] = 0u; L.cnt[3] = 0u; }
+        if (threadIdx.x == 0) { L.cnt[LC_WIDE] = s_base[0]; L.cnt[LC_CHUNK] = s_base[1]; L.cnt[LC_WIDE_CURSOR] = 0u; L.cnt[LC_CHUNK_CURSOR] = 0u; }
         return;
     }
     scan_block_u32(jobs.job[blockIdx.x], s_wave, s_carry);
@@ -984,15 +1013,12 @@ void k_classify_generic(const uint32_t *__restrict__ redo_count, const uint32_t 
                         const uint32_t *__restrict__ ex_off, const int32_t *__restrict__ ex_start, const int32_t *__restrict__ ex_end,
                         uint8_t *__restrict__ ex_flag, uint32_t *__restrict__ info_io, int32_t *__restrict__ ref_out,
                         uint32_t *__restrict__ tile_acc, uint32_t *__restrict__ tile_acc_ex, const uint32_t *__restrict__ tile_first, int n_tiles,
-                        CursorDir cd /* used when j0_arr is null: the one-walk pipeline keeps no per-read cursor values */,
-                        uint32_t *__restrict__ list_cnt /* slab pipelines: the entry counts of the list-driven probe kernels in front of this launch,
-                                                           cleared here for the next run (its FIRST kernel appends to them); else null */)
+                        CursorDir cd /* used when j0_arr is null: the one-walk pipeline keeps no per-read cursor values */)
 {
     __shared__ int g_S[GEN_WAVES][GEN_CAP];
     __shared__ int g_E[GEN_WAVES][GEN_CAP];
     __shared__ uint32_t g_F[GEN_WAVES][GEN_CAP];
     __shared__ uint32_t g_cnt[GEN_WAVES][2];
-    if (list_cnt && blockIdx.x == 0 && threadIdx.x == 0) { list_cnt[6] = list_cnt[0]; list_cnt[7] = list_cnt[1]; list_cnt[0] = 0u; list_cnt[1] = 0u; }
     const uint32_t cnt = *redo_count;
     const int lane = threadIdx.x & (WAVE - 1), wv = threadIdx.x >> 6;
     int *S = g_S[wv], *E = g_E[wv];

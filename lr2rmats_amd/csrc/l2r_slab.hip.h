@@ -104,11 +104,11 @@ struct SlabArgs {
     TileSpan *span;                                      // k_walk_slab -> k_describe_scan: what a tile's descriptor is made from
     // tw64[tile]: the 64-member window record of a tile whose window holds 33 .. 63 transcripts (TD_WIDE).  The tiles of
     // k_probe_slab_wide / k_probe_slab_chunked are listed by block 1 of the scan launch between the walk and the probes (TileLists,
-    // l2r_kernels.hip.h): wide_list / chunk_list, list_cnt[0] / [1] = entries, [2] / [3] = the kernels' work cursors.  A one-window
+    // l2r_kernels.hip.h): wide_list / chunk_list, list_cnt[LC_WIDE] / [LC_CHUNK] = entries, [LC_WIDE_CURSOR] / [LC_CHUNK_CURSOR] = the kernels' work cursors (LC_*, l2r_kernels.hip.h).  A one-window
     // kernel that finds a dictionary key in several entries appends its tile to chunk_list (rare).  chunk_on 0: no chunked windows.
     TileWin64 *tw64;
     uint32_t *wide_list, *chunk_list, *list_cnt;
-    uint32_t *list_cnt_next;                             // one-kernel tile path: the list counters take turns run by run like lb_sup (16 words each): this run's k_describe_scan<true> clears the entry counts of the NEXT run's block, so no launch behind the list kernels is needed for that
+    uint32_t *list_cnt_next;                             // one-kernel tile path: the list counters take turns run by run like lb_sup (LC_WORDS words each): this run's k_describe_scan<true> clears the entry counts of the NEXT run's block, so no launch behind the list kernels is needed for that
     uint32_t *tile_flags;                                // every tile's descriptor flags once more, densely (what TileLists reads)
     uint32_t chunk_on;
     uint32_t n_tiles;
@@ -118,7 +118,7 @@ struct SlabArgs {
     // the complete blocks to lb_sup.  lb_sup is one of TWO arrays that take turns run by run: the words add up during a run, so they
     // have to start from zero -- this run's k_describe_scan<true> clears the other array (lb_sup_next, n_sup words), which nobody
     // touches meanwhile, for the next run; no launch behind k_tile is needed for that.  lb_err: set by a tile that waited in vain
-    // (diagnostics; never seen).  fb_list: the tiles k_tile left in slab form for k_probe_slab (list_cnt[4] entries).
+    // (diagnostics; never seen).  fb_list: the tiles k_tile left in slab form for k_probe_slab (list_cnt[LC_FB] entries).
     unsigned long long *lb_tile, *lb_blk, *lb_sup, *lb_sup_next;
     uint32_t n_sup;
     const TileStat *tile_stat;
@@ -132,8 +132,8 @@ struct SlabArgs {
     uint32_t wide_direct_on;                             // one-kernel tile path: k_tile's WIDE instance takes the exact 64-bit-mask tiles straight from their CIGARs
     uint32_t *exon_total;                                // the run's exon count (k_tile: written by the last tile)
     // one-kernel tile path, the split of k_tile: k_describe_scan<true> marks the tiles the EXACT instance takes whole (TD_XDIRECT,
-    // tile_exact_direct below) and lists every other tile on rest_list (list_cnt[11] entries, in no particular order; the count is
-    // cleared a run ahead like words 0, 1), over which the general instance runs, one workgroup per entry.  split_on SPLIT_OFF (L2R_TILE_SPLIT=0):
+    // tile_exact_direct below) and lists every other tile on rest_list (list_cnt[LC_REST] entries, in no particular order; the count is
+    // cleared a run ahead like LC_WIDE, LC_CHUNK), over which the general instance runs, one workgroup per entry.  split_on SPLIT_OFF (L2R_TILE_SPLIT=0):
     // no tile is marked, nothing is listed, the general instance takes every tile by its workgroup number as before the split.
     // split_on SPLIT_LIST: the rest list is made (its length is what the host wants to know) but no tile is marked -- the general
     // instance takes every tile by its workgroup number, in tile order, as with SPLIT_OFF.
@@ -150,9 +150,9 @@ __device__ __forceinline__ SlabArgsK slab_args()
 }
 
 // A one-window kernel that finds a dictionary key in several entries hands its tile to k_probe_slab_chunked LATE: behind the entries
-// k_describe_scan / TileLists made (list_cnt[1] of them, which k_tile_chunk may be walking over beside the caller), in a region of its own:
-// chunk_list[n_tiles + 1 + i], i < list_cnt[8].
-__device__ __forceinline__ void chunk_list_append_late(SlabArgsK sa, uint32_t t) { sa->chunk_list[sa->n_tiles + 1u + atomicAdd(sa->list_cnt + 8, 1u)] = t; }
+// k_describe_scan / TileLists made (list_cnt[LC_CHUNK] of them, which k_tile_chunk may be walking over beside the caller), in a region of its own:
+// chunk_list[n_tiles + 1 + i], i < list_cnt[LC_LATE].
+__device__ __forceinline__ void chunk_list_append_late(SlabArgsK sa, uint32_t t) { sa->chunk_list[sa->n_tiles + 1u + atomicAdd(sa->list_cnt + LC_LATE, 1u)] = t; }
 constexpr int SLAB_TW_VECS = (int)(sizeof(TileWin) / 16);
 // Which 16-byte vectors of a window record carry something for a window of n_win members: the members' two header arrays, their
 // transcript numbers (four per vector), and the descriptor + masks at the end.  Only those travel from k_walk_slab to k_probe_slab.
@@ -276,11 +276,10 @@ __device__ __forceinline__ uint32_t slab_walk_tile(SlabArgsK sa, PipeArgsK a, ui
     if (FIRST && t == 0u && threadIdx.x == 0) {
         // the run's counters (this kernel is the first of a run): redo list, chunk cursor of the accepted list.
         // (The cursor of the outlier area is cleared by k_probe_slab for the next run.)
-        uint32_t *const cnt = a->f.redo_count;
-        cnt[0] = 0u; cnt[1] = 0u; cnt[2] = 0u;
+        clear_run_counters(a->f.redo_count);
         // ... and the tile lists of k_probe_slab_wide / k_probe_slab_chunked with their work cursors (k_describe_scan appends)
         uint32_t *const lc = sa->list_cnt;
-        lc[0] = 0u; lc[1] = 0u; lc[2] = 0u; lc[3] = 0u; lc[8] = 0u; lc[9] = 0u;
+        lc[LC_WIDE] = 0u; lc[LC_CHUNK] = 0u; lc[LC_WIDE_CURSOR] = 0u; lc[LC_CHUNK_CURSOR] = 0u; lc[LC_LATE] = 0u; lc[LC_DECLINED] = 0u;
     }
     __syncthreads();
     // ---- every read's place among the tile's exons in READ order: each wave scans the 256 counts (four per lane) for itself
@@ -575,10 +574,9 @@ void k_walk_slab_long(SlabArgs kernarg_block, const TileRec *__restrict__ u_rec)
         const int wn_all = wave_max(active ? (int)min(n, 0x7fffffffu) : 0);
         if (lane == 0) { s_wmax[wv] = m; s_nmax[wv] = (uint32_t)wn_all; } }
     if (t == 0u && threadIdx.x == 0) {
-        uint32_t *const cnt = a->f.redo_count;
-        cnt[0] = 0u; cnt[1] = 0u; cnt[2] = 0u;
+        clear_run_counters(a->f.redo_count);
         uint32_t *const lc = sa->list_cnt;
-        lc[0] = 0u; lc[1] = 0u; lc[2] = 0u; lc[3] = 0u; lc[8] = 0u; lc[9] = 0u;
+        lc[LC_WIDE] = 0u; lc[LC_CHUNK] = 0u; lc[LC_WIDE_CURSOR] = 0u; lc[LC_CHUNK_CURSOR] = 0u; lc[LC_LATE] = 0u; lc[LC_DECLINED] = 0u;
     }
     __syncthreads();
     {   const int wn = wave_max((int)s_nslot[threadIdx.x]);            // (thread = slot here: the rows each wave of the probe kernels has to look at)
@@ -673,15 +671,14 @@ void k_describe_scan(SlabArgs kernarg_block, DescribeScan job, uint32_t n_scan, 
     unsigned long long my_total = 0ull;                  // FIRST, lane 0 of a tile's group: {1, its exon count} where it is known here
     if (FIRST && blockIdx.x == 0 && threadIdx.x == 0) {
         // the run's counters: redo list, chunk cursor of the accepted list, the outlier area's cursor, the work cursors of the list-driven
-        // kernels and k_probe_slab's list.  (The lists of the 64-bit-mask / chunked kernel are appended to by THIS launch: their
-        // counts are cleared behind their readers, by k_classify_generic.)
-        uint32_t *const cnt = a->f.redo_count;
-        cnt[0] = 0u; cnt[1] = 0u; cnt[2] = 0u;
+        // kernels and k_probe_slab's list.  (The lists of the 64-bit-mask / chunked kernel and the rest list are appended to by THIS
+        // launch: their counts were cleared a run ahead, through list_cnt_next below.)
+        clear_run_counters(a->f.redo_count);
         *sa->ovf_cursor = 0ull; *sa->lb_err = 0u;
         *sa->exon_total = 0u;                            // (k_tile's last tile writes the run's exon count: an upload without reads has none)
         uint32_t *const lc = sa->list_cnt;
-        lc[2] = 0u; lc[3] = 0u; lc[4] = 0u; lc[5] = 0u; lc[8] = 0u; lc[9] = 0u; lc[10] = 0u;
-        if (sa->list_cnt_next) { sa->list_cnt_next[0] = 0u; sa->list_cnt_next[1] = 0u; sa->list_cnt_next[11] = 0u; }      // (the next run's entry counts: k_describe_scan appends to them from its first workgroup on)
+        lc[LC_WIDE_CURSOR] = 0u; lc[LC_CHUNK_CURSOR] = 0u; lc[LC_FB] = 0u; lc[LC_WIDE_REST] = 0u; lc[LC_LATE] = 0u; lc[LC_DECLINED] = 0u; lc[LC_DECLINED_LATE] = 0u;
+        if (sa->list_cnt_next) { sa->list_cnt_next[LC_WIDE] = 0u; sa->list_cnt_next[LC_CHUNK] = 0u; sa->list_cnt_next[LC_REST] = 0u; }      // (the next run's entry counts: k_describe_scan appends to them from its first workgroup on)
     }
     if (FIRST && blockIdx.x == 0) for (uint32_t i = threadIdx.x; i < sa->n_sup; i += TILE_THREADS) sa->lb_sup_next[i] = 0ull;      // (the next run's super-block words)
     if (t < sa->n_tiles) {
@@ -764,8 +761,8 @@ void k_describe_scan(SlabArgs kernarg_block, DescribeScan job, uint32_t n_scan, 
         if (mw | mc | mr) {
             uint32_t bw = 0u, bc = 0u, br = 0u;
             if (lane == 0) {
-                if (mw) bw = atomicAdd(sa->list_cnt + 0, (uint32_t)__popcll(mw)); if (mc) bc = atomicAdd(sa->list_cnt + 1, (uint32_t)__popcll(mc));
-                if (mr) br = atomicAdd(sa->list_cnt + 11, (uint32_t)__popcll(mr));
+                if (mw) bw = atomicAdd(sa->list_cnt + LC_WIDE, (uint32_t)__popcll(mw)); if (mc) bc = atomicAdd(sa->list_cnt + LC_CHUNK, (uint32_t)__popcll(mc));
+                if (mr) br = atomicAdd(sa->list_cnt + LC_REST, (uint32_t)__popcll(mr));
             }
             bw = (uint32_t)__builtin_amdgcn_readfirstlane((int)bw); bc = (uint32_t)__builtin_amdgcn_readfirstlane((int)bc); br = (uint32_t)__builtin_amdgcn_readfirstlane((int)br);
             const unsigned long long below = (1ull << lane) - 1ull;
@@ -1128,7 +1125,7 @@ constexpr int SLAB_DIR_BYTES = (3 * FAST_DIR_BYTES + 15) & ~15;
 constexpr int SLAB_AUX_BYTES = SLAB_DIR_BYTES + (int)sizeof(TileWin);
 static_assert(SLAB_AUX_BYTES >= 2 * TILE_THREADS * 4, "the accepted counts and their scan (one word per read each) reuse the directories + window record");
 static_assert(2 * SLAB_KEY_CAP * 16 >= SLAB_POS_CAP * 2, "the slot -> position map of a tile's accepted exons reuses the staged dictionary entries");
-// LIST (behind k_tile, l2r_tile.hip.h): the workgroups share the list_cnt[4] tiles of u_list -- the tiles k_tile left in slab form, few or none;
+// LIST (behind k_tile, l2r_tile.hip.h): the workgroups share the list_cnt[LC_FB] tiles of u_list -- the tiles k_tile left in slab form, few or none;
 // else workgroup b takes tile xcd_tile(b).  (A template parameter: as a run-time choice the loop cost the hot form 12 spilled registers.)
 template <int LEVEL, bool ACC, bool DIS, bool LIST = false>
 __global__ __launch_bounds__(TILE_THREADS, slab_probe_wgs(LEVEL))
@@ -1306,7 +1303,7 @@ void k_probe_slab(SlabArgs kernarg_block, const TileSpan *__restrict__ u_span, c
         const uint32_t t = xcd_tile(blockIdx.x, gridDim.x);
         if (t < sa->n_tiles) one_tile(t);
     } else {
-        const uint32_t n_list = sa->list_cnt[4];
+        const uint32_t n_list = sa->list_cnt[LC_FB];
         for (uint32_t wi = blockIdx.x; wi < n_list; wi += gridDim.x) {
             one_tile(u_list[wi]);
             __syncthreads();                             // (the next tile of this workgroup overwrites the LDS image)

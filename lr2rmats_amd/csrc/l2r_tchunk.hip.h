@@ -323,7 +323,7 @@ void k_tile_chunk(SlabArgs kernarg_block, const TileRec *__restrict__ u_rec, con
     const PipeArgsK a = pipe_args();
     const int lane = threadIdx.x & (WAVE - 1), wv = threadIdx.x >> 6;
     const uint32_t n_tiles = sa->n_tiles;
-    if (blockIdx.x >= sa->list_cnt[late ? 8 : 1]) return;
+    if (blockIdx.x >= sa->list_cnt[late ? LC_LATE : LC_CHUNK]) return;
     const uint32_t t = sa->chunk_list[late ? n_tiles + 1u + blockIdx.x : blockIdx.x];
     if (t >= n_tiles) return;
     // diagnostics (L2R_STAMPS=1), wave 0: [0] records, loads asked for, window scan  [1] place walk + barrier  [2] chunk list, key lookups + barrier
@@ -342,7 +342,7 @@ void k_tile_chunk(SlabArgs kernarg_block, const TileRec *__restrict__ u_rec, con
     // (the tiles of the first launch carry k_describe_scan's verdict as a bit of their flags; the late ones are tested here)
     if (late ? !tile_chunk_direct(sa->chunk_direct_on, flags0, chunk_on, d, tst, n_act, a->f.p.min_exon, a->f.p.min_intron, a->f.p.max_delet, a->f.p.ss_dis, ablate, true)
              : (flags0 & TD_CDIRECT) == 0u) {
-        if (threadIdx.x == 0) atomicAdd(sa->list_cnt + (late ? 10 : 9), 1u);            // (left to k_probe_slab_chunked: the host skips that launch while nobody counts here)
+        if (threadIdx.x == 0) atomicAdd(sa->list_cnt + (late ? LC_DECLINED_LATE : LC_DECLINED), 1u);            // (left to k_probe_slab_chunked: the host skips that launch while nobody counts here)
         return;
     }
     // ---- the counts in front of the tile (waves 0 .. 2, one level each): plain loads, complete unless a tile in front is not exact

@@ -590,8 +590,8 @@ void k_tile(SlabArgs kernarg_block, const TileRec *__restrict__ u_rec, const Til
     const PipeArgsK a = pipe_args();
     const int lane = threadIdx.x & (WAVE - 1), wv = threadIdx.x >> 6;
     uint32_t t;
-    if (WIDE) { if (blockIdx.x >= sa->list_cnt[0]) return; t = sa->wide_list[blockIdx.x]; }
-    else if (!EXACT && sa->split_on == SPLIT_ON) { if (blockIdx.x >= sa->list_cnt[11]) return; t = sa->rest_list[blockIdx.x]; }
+    if (WIDE) { if (blockIdx.x >= sa->list_cnt[LC_WIDE]) return; t = sa->wide_list[blockIdx.x]; }
+    else if (!EXACT && sa->split_on == SPLIT_ON) { if (blockIdx.x >= sa->list_cnt[LC_REST]) return; t = sa->rest_list[blockIdx.x]; }
     else { t = fused_tile(blockIdx.x); if (t >= sa->n_tiles) return; }
     // diagnostics (L2R_STAMPS=1), wave 0: [0] records, CIGAR heads asked for, staging  [1] (count walk + barrier)  [6] scan, count
     // published, place walk  [2] window pass  [3] probe rounds  [4] verdicts  [7] the tile's first slot (exon counts in front)  [5] write-out
@@ -1140,8 +1140,8 @@ void k_tile(SlabArgs kernarg_block, const TileRec *__restrict__ u_rec, const Til
         // several entries makes it k_probe_slab_chunked's (as k_probe_slab decides), anything else k_probe_slab's
         if (!pre_slab) {
             if (wide_key && chunk_on) { sa->tw[t].d.flags = d0.flags | TD_CHUNK; chunk_list_append_late(sa, t); }
-            else sa->fb_list[atomicAdd(sa->list_cnt + 4, 1u)] = t;
-        } else if (d0.flags & TD_WIDE) sa->wide_list[n_tiles + 1u + atomicAdd(sa->list_cnt + 5, 1u)] = t;      // (k_probe_slab_wide's, behind the WIDE instance's tiles)
+            else sa->fb_list[atomicAdd(sa->list_cnt + LC_FB, 1u)] = t;
+        } else if (d0.flags & TD_WIDE) sa->wide_list[n_tiles + 1u + atomicAdd(sa->list_cnt + LC_WIDE_REST, 1u)] = t;      // (k_probe_slab_wide's, behind the WIDE instance's tiles)
     }
     }
 

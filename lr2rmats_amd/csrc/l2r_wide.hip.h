@@ -284,13 +284,13 @@ void k_probe_slab_wide(SlabArgs kernarg_block, WideArgs wa, const uint32_t *__re
     uint8_t *const s_dir0 = s_dir, *const s_dir1 = s_dir + DIR_BYTES, *const s_rdir = s_dir + 2 * DIR_BYTES;
     // the tiles of this kernel: wide_list (TileLists), taken from a cursor -- they differ in cost; a workgroup's FIRST entry is its
     // own number: an empty list costs no atomic
-    // (one-kernel tile path: the wide tiles k_tile has given the slab form -- its list behind wide_list, list_cnt[5] entries; the others
+    // (one-kernel tile path: the wide tiles k_tile has given the slab form -- its list behind wide_list, list_cnt[LC_WIDE_REST] entries; the others
     //  are its WIDE instance's)
     const uint32_t *const w_list = u_stat ? sa->wide_list + sa->n_tiles + 1u : sa->wide_list;
-    const uint32_t n_wide = u_stat ? sa->list_cnt[5] : sa->list_cnt[0];
+    const uint32_t n_wide = u_stat ? sa->list_cnt[LC_WIDE_REST] : sa->list_cnt[LC_WIDE];
     for (bool own = true;; own = false) {
         if (own && blockIdx.x >= n_wide) break;
-        if (threadIdx.x == 0) s_next = own ? blockIdx.x : gridDim.x + atomicAdd(sa->list_cnt + 2, 1u);
+        if (threadIdx.x == 0) s_next = own ? blockIdx.x : gridDim.x + atomicAdd(sa->list_cnt + LC_WIDE_CURSOR, 1u);
         __syncthreads();
         const uint32_t wi = s_next;
         if (wi >= n_wide) break;
