@@ -305,6 +305,32 @@ int          l2r_filter_score(l2r_ctx *ctx, const l2r_filter_records *recs, cons
 int          l2r_filter_select(l2r_ctx *ctx, int64_t n_groups, const int64_t *group_off, const int32_t *score,
                                const int32_t *intron_n, const l2r_filter_params *prm, int64_t *winner);
 
+/* ---- `fusion` (src/bam_fusion.c): per alignment record the part of the read and of the reference it covers, per read the two
+ * parts of a candidate gene fusion.  Replaces bam2seg() (src/parse_bam.c:543-595) with bam_query_len() (:261-270), and
+ * check_fusion() (src/bam_fusion.c:114-129) with its comparator and tests; reading the records, the AS / NM tags, the grouping
+ * by read name and the writers stay with the caller (host/fusion.c). */
+typedef struct { float ovlp_frac, each_cov, all_cov; int32_t dis; } l2r_fusion_params;            /* -o 0.1  -v 0.1  -V 0.99  dis 100000 */
+typedef l2r_filter_records l2r_fusion_records;                  /* the same columns; flag, pos, cig_off and cig are read */
+/* Row i: read_start / read_end (1-based on the read as sequenced, first clip counted, swapped round on the reverse strand),
+ * ref_start / ref_end (1-based), qlen (bam_query_len: M I S = X).  The rows of unmapped records (FLAG & 4) are 0.  32-bit sums
+ * that wrap.  The kernel has a form of one thread and a form of one wave per record; the engine takes the second where the
+ * records have more than 32 operations on average (L2R_FUSION_WAVE=0|1 in the environment forces one). */
+int          l2r_fusion_segments(l2r_ctx *ctx, const l2r_fusion_records *recs, int32_t *read_start, int32_t *read_end,
+                                 int32_t *ref_start, int32_t *ref_end, int32_t *qlen);
+/* Groups = runs of consecutive MAPPED records with one read name; group g covers rows [group_off[g], group_off[g+1]) of the
+ * seven columns (score = bam_aux2i(AS), ed = bam_aux2i(NM), 0 without the tag); rlen_of_group[g] = qlen of the group's first
+ * record.  first[g] / second[g] = rows of the two segments check_fusion() leaves in seg[0] / seg[1] when it returns 2, else
+ * -1 / -1.  Equal (score, ed): the earlier row first; scores compared by value; the coverage counts positions of [1, rlen]
+ * only; rlen <= 0 or a group of one row: not a candidate. */
+int          l2r_fusion_select(l2r_ctx *ctx, int64_t n_groups, const int64_t *group_off, const int32_t *score, const int32_t *ed,
+                               const int32_t *tid, const int32_t *read_start, const int32_t *read_end, const int32_t *ref_start,
+                               const int32_t *ref_end, const int32_t *rlen_of_group, const l2r_fusion_params *prm,
+                               int64_t *first, int64_t *second);
+/* diagnostics (tools/bench_fusion.py, tests): out[0] the form the last l2r_fusion_segments took (0 thread, 1 wave per record);
+ * with L2R_FUSION_TIMING=1 in the environment (every one of these launches is then waited for) device milliseconds of the last
+ * [1] k_fusion_seg [2] k_fusion_select [3] k_filter_score [4] k_filter_select; n = words of out (up to 5) */
+int          l2r_fusion_stats(l2r_ctx *ctx, double *out, int n);
+
 /* ---- `bam2sj` (src/parse_bam.c:896-924 bam2sj_core): the junction table of an alignment file -- one row per distinct
  * (tid, don, acc) in that order, with how many uniquely / multiply mapped records carry it, its intron motif and strand.
  * Replaces gen_sj() :402-442 per record, the list search and insertion of sj_sch_group() / sj_update_group() :339-380 (a device

@@ -32,6 +32,7 @@ EXPORTS = [
     "l2r_debug_counters", "l2r_debug_stamps", "l2r_debug_tile_times", "l2r_upload_index_ms", "l2r_hint_single_run",
     "l2r_xchg_id_bytes", "l2r_xchg_unique_id", "l2r_xchg_create", "l2r_xchg_gather_results", "l2r_xchg_gather_accepted", "l2r_xchg_destroy",
     "l2r_sj_begin", "l2r_sj_add", "l2r_sj_add_rows", "l2r_sj_finish", "l2r_sj_download", "l2r_sj_stats",
+    "l2r_fusion_segments", "l2r_fusion_select", "l2r_fusion_stats",
 ]
 SJ_E_UNKNOWN_TID = -3
 
@@ -82,6 +83,10 @@ class CFilterParams(C.Structure):
 class CFilterRecords(C.Structure):
     _fields_ = [("n", C.c_int64), ("n_cigar", C.c_int64), ("flag", C.c_void_p), ("tid", C.c_void_p), ("pos", C.c_void_p),
                 ("l_qseq", C.c_void_p), ("nm", C.c_void_p), ("cig_off", C.c_void_p), ("cig", C.c_void_p)]
+
+
+class CFusionParams(C.Structure):
+    _fields_ = [("ovlp_frac", C.c_float), ("each_cov", C.c_float), ("all_cov", C.c_float), ("dis", C.c_int32)]
 
 
 class CFilterSpans(C.Structure):
@@ -160,6 +165,9 @@ def load_library():
         lib.l2r_annotation_cache_state.argtypes = [C.c_void_p]
         lib.l2r_filter_score.argtypes = [C.c_void_p] * 7
         lib.l2r_filter_select.argtypes = [C.c_void_p, C.c_int64] + [C.c_void_p] * 5
+        lib.l2r_fusion_segments.argtypes = [C.c_void_p] * 7
+        lib.l2r_fusion_select.argtypes = [C.c_void_p, C.c_int64] + [C.c_void_p] * 12
+        lib.l2r_fusion_stats.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
         lib.l2r_hint_single_run.argtypes = [C.c_void_p, C.c_int]
         lib.l2r_upload_index_ms.restype = C.c_float
         lib.l2r_upload_index_ms.argtypes = [C.c_void_p]
@@ -205,6 +213,9 @@ class SjTable:
 
 SJ_STAT_NAMES = ["rows_made", "rounds", "radix_passes", "rows_in", "rows_out", "k_sj_count", "k_scan_u32 (counts)", "k_sj_fill", "k_sj_hist12",
                  "k_sj_digit_hist", "k_scan_u32 (tile histograms)", "k_sj_scatter", "k_sj_heads + scan", "k_sj_reduce", "k_sj_motif"]
+
+
+FUSION_STAT_NAMES = ["wave_form", "k_fusion_seg", "k_fusion_select", "k_filter_score", "k_filter_select"]
 
 
 @dataclass
@@ -292,6 +303,33 @@ class Engine:
         win = np.zeros(max(ng, 1), np.int64)
         self._chk(self.lib.l2r_filter_select(self.ctx, ng, g.ctypes.data, s.ctypes.data, i.ctypes.data, C.byref(prm), win.ctypes.data))
         return win[:ng]
+
+    # ---- `fusion` (include/lr2rmats_hip.h: l2r_fusion_segments / l2r_fusion_select)
+    def fusion_segments(self, flag, pos, cig_off, cig):
+        """(read_start, read_end, ref_start, ref_end, qlen) of every record; the rows of unmapped records are 0."""
+        a = [np.ascontiguousarray(flag, np.uint16), np.ascontiguousarray(pos, np.int32), np.ascontiguousarray(cig_off, np.int64),
+             np.ascontiguousarray(cig, np.uint32)]
+        n = int(a[0].shape[0])
+        recs = CFilterRecords(n, int(a[3].shape[0]), a[0].ctypes.data, None, a[1].ctypes.data, None, None, a[2].ctypes.data, a[3].ctypes.data)
+        out = [np.zeros(max(n, 1), np.int32) for _ in range(5)]
+        self._chk(self.lib.l2r_fusion_segments(self.ctx, C.byref(recs), *[x.ctypes.data for x in out]))
+        return tuple(x[:n] for x in out)
+
+    def fusion_select(self, group_off, score, ed, tid, read_start, read_end, ref_start, ref_end, rlen_of_group, prm: "CFusionParams"):
+        """(first, second): per group the rows of the two segments of a candidate, or -1, -1."""
+        g = np.ascontiguousarray(group_off, np.int64)
+        cols = [np.ascontiguousarray(x, np.int32) for x in (score, ed, tid, read_start, read_end, ref_start, ref_end, rlen_of_group)]
+        ng = int(g.shape[0]) - 1
+        first = np.zeros(max(ng, 1), np.int64); second = np.zeros(max(ng, 1), np.int64)
+        self._chk(self.lib.l2r_fusion_select(self.ctx, ng, g.ctypes.data, *[x.ctypes.data for x in cols], C.byref(prm),
+                                             first.ctypes.data, second.ctypes.data))
+        return first[:ng], second[:ng]
+
+    def fusion_stats(self) -> dict:
+        """l2r_fusion_stats: the form of the last fusion_segments, and with L2R_FUSION_TIMING=1 device milliseconds per kernel."""
+        out = np.zeros(len(FUSION_STAT_NAMES), np.float64)
+        self._chk(self.lib.l2r_fusion_stats(self.ctx, out.ctypes.data, len(out)))
+        return {k: float(v) for k, v in zip(FUSION_STAT_NAMES, out)}
 
     # ---- `bam2sj` (include/lr2rmats_hip.h: l2r_sj_begin / _add / _add_rows / _finish / _download)
     def sj_begin(self, min_intron: int = 3, pair_only: bool = True, genome=None):

@@ -23,6 +23,7 @@
 #include "l2r_chunk.hip.h"
 #include "l2r_tchunk.hip.h"
 #include "l2r_filter.hip.h"
+#include "l2r_fusion.hip.h"
 #include "l2r_sj.hip.h"
 
 using namespace l2r;
@@ -240,6 +241,7 @@ struct l2r_ctx {
     uint32_t h_totals[3] = {0, 0, 0};
     bool totals_valid = false;
     SjState sj;                             // `bam2sj`
+    double fusion_stats[5] = {0, 0, 0, 0, 0};        // `fusion`: l2r_fusion_stats
 };
 
 // What completed runs have shown about the tile path's lists and the inexact tiles: forgotten wherever inputs, parameters or outputs change
@@ -1931,6 +1933,26 @@ template <typename T> static int to_dev(l2r_ctx *c, DevBuf<T> &b, const T *src, 
     if (n) HIP_TRY(hipMemcpyAsync(b.p, src, n * sizeof(T), hipMemcpyHostToDevice, c->stream));
     return 0;
 }
+// a launch of `filter` / `fusion` on the context stream; with L2R_FUSION_TIMING=1 (tools/bench_fusion.py) bracketed by events and waited for: device milliseconds into *ms
+template <typename F> static int fusion_launch(l2r_ctx *c, double *ms, F f)
+{
+    const char *e = getenv("L2R_FUSION_TIMING");
+    const bool timing = e && atoi(e) != 0;
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    if (timing) { HIP_TRY(hipEventCreate(&ev[0])); HIP_TRY(hipEventCreate(&ev[1])); HIP_TRY(hipEventRecord(ev[0], c->stream)); }
+    f();
+    hipError_t err = hipGetLastError();
+    if (timing) {
+        float t = 0.0f;
+        if (err == hipSuccess) err = hipEventRecord(ev[1], c->stream);
+        if (err == hipSuccess) err = hipEventSynchronize(ev[1]);
+        if (err == hipSuccess) err = hipEventElapsedTime(&t, ev[0], ev[1]);
+        (void)hipEventDestroy(ev[0]); (void)hipEventDestroy(ev[1]);
+        *ms = (double)t;
+    }
+    if (err != hipSuccess) return fail(-2, "[kernel launch] %s", hipGetErrorString(err));
+    return 0;
+}
 }
 
 int l2r_filter_score(l2r_ctx *c, const l2r_filter_records *r, const l2r_filter_params *prm, const l2r_filter_spans *rm,
@@ -1970,13 +1992,15 @@ int l2r_filter_score(l2r_ctx *c, const l2r_filter_records *r, const l2r_filter_p
     if (!rc && N) {
         const FilterPrm fp{prm->cov_rate, prm->map_qual, prm->sec_rat, prm->min_intron_n};
         const FilterSpans sp{d_soff.p, d_st.p, d_pe.p, n_tid};
-        hipLaunchKernelGGL(k_filter_score, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, c->stream, (int64_t)N, (const uint16_t *)d_flag.p, (const int32_t *)d_tid.p,
-                           (const int32_t *)d_pos.p, (const int32_t *)d_lq.p, (const int32_t *)d_nm.p, (const int64_t *)d_off.p, (const uint32_t *)d_cig.p, fp, sp,
-                           d_drop.p, d_score.p, d_in.p);
-        hipError_t e = hipGetLastError();
-        if (e == hipSuccess) e = hipMemcpyAsync(drop, d_drop.p, N, hipMemcpyDeviceToHost, c->stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(score, d_score.p, N * 4, hipMemcpyDeviceToHost, c->stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(intron_n, d_in.p, N * 4, hipMemcpyDeviceToHost, c->stream);
+        rc = fusion_launch(c, &c->fusion_stats[3], [&] {
+            hipLaunchKernelGGL(k_filter_score, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, c->stream, (int64_t)N, (const uint16_t *)d_flag.p, (const int32_t *)d_tid.p,
+                               (const int32_t *)d_pos.p, (const int32_t *)d_lq.p, (const int32_t *)d_nm.p, (const int64_t *)d_off.p, (const uint32_t *)d_cig.p, fp, sp,
+                               d_drop.p, d_score.p, d_in.p);
+        });
+        hipError_t e = hipSuccess;
+        if (!rc) e = hipMemcpyAsync(drop, d_drop.p, N, hipMemcpyDeviceToHost, c->stream);
+        if (!rc && e == hipSuccess) e = hipMemcpyAsync(score, d_score.p, N * 4, hipMemcpyDeviceToHost, c->stream);
+        if (!rc && e == hipSuccess) e = hipMemcpyAsync(intron_n, d_in.p, N * 4, hipMemcpyDeviceToHost, c->stream);
         if (e != hipSuccess) rc = fail(-2, "[l2r_filter_score] %s", hipGetErrorString(e));
     }
     hipError_t e = hipStreamSynchronize(c->stream);          // (the host vectors and the DevBufs above are locals)
@@ -1997,15 +2021,99 @@ int l2r_filter_select(l2r_ctx *c, int64_t n_groups, const int64_t *group_off, co
     if ((rc = to_dev(c, d_off, group_off, G + 1)) || (rc = to_dev(c, d_score, score, R)) || (rc = to_dev(c, d_in, intron_n, R)) || d_win.ensure(G)) rc = rc ? rc : -2;
     if (!rc) {
         const FilterPrm fp{prm->cov_rate, prm->map_qual, prm->sec_rat, prm->min_intron_n};
-        hipLaunchKernelGGL(k_filter_select, dim3((unsigned)((G + 255) / 256)), dim3(256), 0, c->stream, (int64_t)G, (const int64_t *)d_off.p, (const int32_t *)d_score.p,
-                           (const int32_t *)d_in.p, fp, d_win.p);
-        hipError_t e = hipGetLastError();
-        if (e == hipSuccess) e = hipMemcpyAsync(winner, d_win.p, G * 8, hipMemcpyDeviceToHost, c->stream);
+        rc = fusion_launch(c, &c->fusion_stats[4], [&] {
+            hipLaunchKernelGGL(k_filter_select, dim3((unsigned)((G + 255) / 256)), dim3(256), 0, c->stream, (int64_t)G, (const int64_t *)d_off.p, (const int32_t *)d_score.p,
+                               (const int32_t *)d_in.p, fp, d_win.p);
+        });
+        hipError_t e = hipSuccess;
+        if (!rc) e = hipMemcpyAsync(winner, d_win.p, G * 8, hipMemcpyDeviceToHost, c->stream);
         if (e != hipSuccess) rc = fail(-2, "[l2r_filter_select] %s", hipGetErrorString(e));
     }
     hipError_t e = hipStreamSynchronize(c->stream);
     if (!rc && e != hipSuccess) rc = fail(-2, "[l2r_filter_select] %s", hipGetErrorString(e));
     return rc;
+}
+
+// ---------------------------------------------------------------------------------------------- fusion
+int l2r_fusion_segments(l2r_ctx *c, const l2r_fusion_records *r, int32_t *read_start, int32_t *read_end, int32_t *ref_start, int32_t *ref_end,
+                        int32_t *qlen)
+{
+    if (!c || !r || !read_start || !read_end || !ref_start || !ref_end || !qlen) return fail(-1, "[l2r_fusion_segments] null argument");
+    if (r->n < 0 || r->n_cigar < 0) return fail(-1, "[l2r_fusion_segments] negative size");
+    const size_t N = (size_t)r->n;
+    if (N == 0) return 0;
+    if (!r->flag || !r->pos || !r->cig_off || (r->n_cigar && !r->cig)) return fail(-1, "[l2r_fusion_segments] null column");
+    if (r->cig_off[0] != 0 || r->cig_off[N] != r->n_cigar) return fail(-1, "[l2r_fusion_segments] cig_off does not span the CIGAR array");
+    for (size_t i = 0; i < N; ++i) if (r->cig_off[i + 1] < r->cig_off[i]) return fail(-1, "[l2r_fusion_segments] cig_off descends at record %lld", (long long)i);
+    HIP_TRY(hipSetDevice(c->device));
+    // one wave per record where the CIGARs are long (the bound of l2r_upload_reads' wide_cigar); L2R_FUSION_WAVE=0|1: tests, tools/bench_fusion.py
+    bool wave = (double)r->n_cigar / (double)N > 32.0;
+    if (const char *e = getenv("L2R_FUSION_WAVE")) wave = atoi(e) != 0;
+    DevBuf<uint16_t> d_flag; DevBuf<int32_t> d_pos, d_out; DevBuf<int64_t> d_off; DevBuf<uint32_t> d_cig;
+    int rc = 0;
+    if ((rc = to_dev(c, d_flag, r->flag, N)) || (rc = to_dev(c, d_pos, r->pos, N)) || (rc = to_dev(c, d_off, r->cig_off, N + 1)) ||
+        (rc = to_dev(c, d_cig, r->cig, (size_t)r->n_cigar)) || d_out.ensure(5 * N)) rc = rc ? rc : -2;
+    if (!rc) {
+        int32_t *o = d_out.p;
+        const size_t threads = wave ? N * 64 : N;
+        const dim3 grid((unsigned)((threads + 255) / 256));
+        c->fusion_stats[0] = wave ? 1.0 : 0.0;
+        rc = fusion_launch(c, &c->fusion_stats[1], [&] {
+            if (wave) hipLaunchKernelGGL(k_fusion_seg<true>, grid, dim3(256), 0, c->stream, (int64_t)N, (const uint16_t *)d_flag.p, (const int32_t *)d_pos.p,
+                                         (const int64_t *)d_off.p, (const uint32_t *)d_cig.p, o, o + N, o + 2 * N, o + 3 * N, o + 4 * N);
+            else hipLaunchKernelGGL(k_fusion_seg<false>, grid, dim3(256), 0, c->stream, (int64_t)N, (const uint16_t *)d_flag.p, (const int32_t *)d_pos.p,
+                                    (const int64_t *)d_off.p, (const uint32_t *)d_cig.p, o, o + N, o + 2 * N, o + 3 * N, o + 4 * N);
+        });
+        int32_t *host[5] = {read_start, read_end, ref_start, ref_end, qlen};
+        for (int k = 0; k < 5 && !rc; ++k) {
+            const hipError_t e = hipMemcpyAsync(host[k], o + (size_t)k * N, N * 4, hipMemcpyDeviceToHost, c->stream);
+            if (e != hipSuccess) rc = fail(-2, "[l2r_fusion_segments] %s", hipGetErrorString(e));
+        }
+    }
+    hipError_t e = hipStreamSynchronize(c->stream);
+    if (!rc && e != hipSuccess) rc = fail(-2, "[l2r_fusion_segments] %s", hipGetErrorString(e));
+    return rc;
+}
+
+int l2r_fusion_select(l2r_ctx *c, int64_t n_groups, const int64_t *group_off, const int32_t *score, const int32_t *ed, const int32_t *tid,
+                      const int32_t *read_start, const int32_t *read_end, const int32_t *ref_start, const int32_t *ref_end,
+                      const int32_t *rlen_of_group, const l2r_fusion_params *prm, int64_t *first, int64_t *second)
+{
+    if (!c || !prm || n_groups < 0 || (n_groups && (!group_off || !score || !ed || !tid || !read_start || !read_end || !ref_start || !ref_end ||
+                                                    !rlen_of_group || !first || !second))) return fail(-1, "[l2r_fusion_select] bad argument");
+    if (n_groups == 0) return 0;
+    HIP_TRY(hipSetDevice(c->device));
+    const size_t G = (size_t)n_groups;
+    if (group_off[0] < 0) return fail(-1, "[l2r_fusion_select] negative group offset");
+    for (size_t g = 0; g < G; ++g) if (group_off[g + 1] <= group_off[g]) return fail(-1, "[l2r_fusion_select] group %lld is empty", (long long)g);
+    const size_t R = (size_t)group_off[G];
+    DevBuf<int64_t> d_off, d_out; DevBuf<int32_t> d_score, d_ed, d_tid, d_rs, d_re, d_fs, d_fe, d_rlen;
+    int rc = 0;
+    if ((rc = to_dev(c, d_off, group_off, G + 1)) || (rc = to_dev(c, d_score, score, R)) || (rc = to_dev(c, d_ed, ed, R)) || (rc = to_dev(c, d_tid, tid, R)) ||
+        (rc = to_dev(c, d_rs, read_start, R)) || (rc = to_dev(c, d_re, read_end, R)) || (rc = to_dev(c, d_fs, ref_start, R)) ||
+        (rc = to_dev(c, d_fe, ref_end, R)) || (rc = to_dev(c, d_rlen, rlen_of_group, G)) || d_out.ensure(2 * G)) rc = rc ? rc : -2;
+    if (!rc) {
+        const FusionPrm fp{prm->ovlp_frac, prm->each_cov, prm->all_cov, prm->dis};
+        rc = fusion_launch(c, &c->fusion_stats[2], [&] {
+            hipLaunchKernelGGL(k_fusion_select, dim3((unsigned)((G + 255) / 256)), dim3(256), 0, c->stream, (int64_t)G, (const int64_t *)d_off.p,
+                               (const int32_t *)d_score.p, (const int32_t *)d_ed.p, (const int32_t *)d_tid.p, (const int32_t *)d_rs.p, (const int32_t *)d_re.p,
+                               (const int32_t *)d_fs.p, (const int32_t *)d_fe.p, (const int32_t *)d_rlen.p, fp, d_out.p, d_out.p + G);
+        });
+        hipError_t e = hipSuccess;
+        if (!rc) e = hipMemcpyAsync(first, d_out.p, G * 8, hipMemcpyDeviceToHost, c->stream);
+        if (!rc && e == hipSuccess) e = hipMemcpyAsync(second, d_out.p + G, G * 8, hipMemcpyDeviceToHost, c->stream);
+        if (e != hipSuccess) rc = fail(-2, "[l2r_fusion_select] %s", hipGetErrorString(e));
+    }
+    hipError_t e = hipStreamSynchronize(c->stream);
+    if (!rc && e != hipSuccess) rc = fail(-2, "[l2r_fusion_select] %s", hipGetErrorString(e));
+    return rc;
+}
+
+int l2r_fusion_stats(l2r_ctx *c, double *out, int n)
+{
+    if (!c || !out || n < 0) return fail(-1, "[l2r_fusion_stats] bad argument");
+    for (int k = 0; k < n; ++k) out[k] = k < 5 ? c->fusion_stats[k] : 0.0;
+    return 0;
 }
 
 // ---------------------------------------------------------------------------------------------- bam2sj

@@ -1475,6 +1475,7 @@ int h_main(int argc, char **argv)
     if (strcmp(argv[0], "unique-gtf") == 0) return h_cmd_unique_gtf(argc, argv);
     if (strcmp(argv[0], "filter") == 0) return h_cmd_filter(argc, argv);
     if (strcmp(argv[0], "bam2sj") == 0) return h_cmd_bam2sj(argc, argv);
+    if (strcmp(argv[0], "fusion") == 0) return h_cmd_fusion(argc, argv);
     /* (diagnostics, no GPU: every record of a SAM / BAM file written out as BAM -- reader, encoder and BGZF writer of `filter`) */
     if (strcmp(argv[0], "records2bam") == 0 && argc == 3) return h_records_to_bam(argv[1], argv[2]) ? 1 : 0;
     /* (diagnostics, no GPU: the block ranges `world` ranks of a multi-process run would inflate of a BAM file, one line per rank:
@@ -1494,10 +1495,6 @@ int h_main(int argc, char **argv)
         }
         printf("%s, %lld records\n", ok ? "ranges meet" : "RANGES DO NOT MEET", (long long)total);
         return ok ? 0 : 1;
-    }
-    if (!strcmp(argv[0], "fusion")) {
-        fprintf(stderr, "[main] command '%s' is outside the MI355X build (see DESIGN.md, scope)\n", argv[0]);
-        return 1;
     }
     fprintf(stderr, "[main] unrecognized command '%s'\n", argv[0]);
     return 1;

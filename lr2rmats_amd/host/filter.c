@@ -55,6 +55,7 @@ static void rec_reserve(h_records *r, int64_t more_cig)
         r->flag = (uint16_t *)h_realloc(r->flag, (size_t)c * 2); r->tid = (int32_t *)h_realloc(r->tid, (size_t)c * 4);
         r->pos = (int32_t *)h_realloc(r->pos, (size_t)c * 4); r->l_qseq = (int32_t *)h_realloc(r->l_qseq, (size_t)c * 4);
         r->nm = (int32_t *)h_realloc(r->nm, (size_t)c * 4); r->nm_seen = (uint8_t *)h_realloc(r->nm_seen, (size_t)c);
+        r->as_score = (int32_t *)h_realloc(r->as_score, (size_t)c * 4);
         r->cap = c;
     }
     if (r->n_cig + more_cig + 1 > r->cap_cig) {
@@ -67,7 +68,7 @@ static void rec_reserve(h_records *r, int64_t more_cig)
 void h_records_free(h_records *r)
 {
     free(r->hdr); free(r->buf); free(r->rec_off); free(r->cig_off); free(r->flag); free(r->tid); free(r->pos); free(r->l_qseq);
-    free(r->nm); free(r->nm_seen); free(r->cig);
+    free(r->nm); free(r->nm_seen); free(r->as_score); free(r->cig);
     memset(r, 0, sizeof *r);
 }
 
@@ -91,7 +92,18 @@ static size_t aux_size(uint8_t type, const uint8_t *p, const uint8_t *end)
 
 /* The fields the tests read, from the BAM-encoded record at r->buf + off (block_size word first).  The CIGAR is the real one:
  * beyond 65535 operations BAM keeps it in the CG:B,I tag behind a <l_seq>S<ref len>N placeholder (htslib swaps it back in
- * when it reads the record).  NM: bam_aux2i() of the first NM tag -- its value for the integer types, 0 for any other. */
+ * when it reads the record).  NM, AS (`fusion`): bam_aux2i() of the first tag of that name -- its value for the integer types, 0 for
+ * any other; AS 0 without the tag. */
+static int32_t aux_int(uint8_t t, const uint8_t *v)
+{
+    switch (t) {
+    case 'c': return (int8_t)v[0]; case 'C': return v[0];
+    case 's': return (int16_t)le16(v); case 'S': return le16(v);
+    case 'i': case 'I': return (int32_t)le32(v);
+    default: return 0;
+    }
+}
+
 static void index_record(h_records *r, int64_t off, const char *who)
 {
     const uint8_t *p = r->buf + off;
@@ -102,20 +114,13 @@ static void index_record(h_records *r, int64_t off, const char *who)
     const uint8_t *aux = cig + 4 * (size_t)n_cig + (l_seq + 1) / 2 + l_seq;
     if (bs < 32 || aux > rend || l_read_name == 0) h_fatal(who, "corrupt BAM record");
     const uint8_t *cg = NULL; uint32_t cg_n = 0;
-    int32_t nm = 0; uint8_t nm_seen = 0;
+    int32_t nm = 0, as_score = 0; uint8_t nm_seen = 0, as_seen = 0;
     for (const uint8_t *a = aux; a + 3 <= rend;) {
         const uint8_t t = a[2];
         const size_t sz = aux_size(t, a + 3, rend);
         if (sz == 0 || a + 3 + sz > rend) h_fatal(who, "corrupt BAM aux field");
-        if (!nm_seen && a[0] == 'N' && a[1] == 'M') {
-            nm_seen = 1;
-            switch (t) {
-            case 'c': nm = (int8_t)a[3]; break; case 'C': nm = a[3]; break;
-            case 's': nm = (int16_t)le16(a + 3); break; case 'S': nm = le16(a + 3); break;
-            case 'i': case 'I': nm = (int32_t)le32(a + 3); break;
-            default: nm = 0;
-            }
-        }
+        if (!nm_seen && a[0] == 'N' && a[1] == 'M') { nm_seen = 1; nm = aux_int(t, a + 3); }
+        if (!as_seen && a[0] == 'A' && a[1] == 'S') { as_seen = 1; as_score = aux_int(t, a + 3); }
         if (a[0] == 'C' && a[1] == 'G' && t == 'B' && a[3] == 'I') { cg_n = le32(a + 4); cg = a + 8; }
         a += 3 + sz;
     }
@@ -125,7 +130,7 @@ static void index_record(h_records *r, int64_t off, const char *who)
     const int64_t i = r->n;
     r->rec_off[i] = off; r->rec_off[i + 1] = off + 4 + bs;
     r->tid[i] = (int32_t)le32(rec); r->pos[i] = (int32_t)le32(rec + 4); r->flag[i] = le16(rec + 14); r->l_qseq[i] = (int32_t)l_seq;
-    r->nm[i] = nm; r->nm_seen[i] = nm_seen;
+    r->nm[i] = nm; r->nm_seen[i] = nm_seen; r->as_score[i] = as_score;
     r->cig_off[i] = r->n_cig;
     for (uint32_t k = 0; k < cn; ++k) r->cig[r->n_cig++] = le32(cp + 4 * (size_t)k);
     r->cig_off[i + 1] = r->n_cig;
@@ -383,6 +388,7 @@ static void records_join(h_records *r, sam_piece *pc, int n_pc)
     r->rec_off = (int64_t *)h_malloc((size_t)(n + 2) * 8); r->cig_off = (int64_t *)h_malloc((size_t)(n + 2) * 8);
     r->flag = (uint16_t *)h_malloc((size_t)(n + 1) * 2); r->tid = (int32_t *)h_malloc((size_t)(n + 1) * 4); r->pos = (int32_t *)h_malloc((size_t)(n + 1) * 4);
     r->l_qseq = (int32_t *)h_malloc((size_t)(n + 1) * 4); r->nm = (int32_t *)h_malloc((size_t)(n + 1) * 4); r->nm_seen = (uint8_t *)h_malloc((size_t)n + 1);
+    r->as_score = (int32_t *)h_malloc((size_t)(n + 1) * 4);
     r->cig = (uint32_t *)h_malloc((size_t)(n_cig + 1) * 4);
     r->buf = (uint8_t *)h_malloc(bytes_total + 1); r->buf_len = bytes_total;
     r->cap = n + 1; r->cap_cig = n_cig + 1;
@@ -393,6 +399,7 @@ static void records_join(h_records *r, sam_piece *pc, int n_pc)
         for (int64_t i = 0; i < q->n; ++i) { r->rec_off[at + i] = q->rec_off[i] + (int64_t)bat; r->cig_off[at + i] = q->cig_off[i] + cat; }
         memcpy(r->flag + at, q->flag, (size_t)q->n * 2); memcpy(r->tid + at, q->tid, (size_t)q->n * 4); memcpy(r->pos + at, q->pos, (size_t)q->n * 4);
         memcpy(r->l_qseq + at, q->l_qseq, (size_t)q->n * 4); memcpy(r->nm + at, q->nm, (size_t)q->n * 4); memcpy(r->nm_seen + at, q->nm_seen, (size_t)q->n);
+        memcpy(r->as_score + at, q->as_score, (size_t)q->n * 4);
         memcpy(r->cig + cat, q->cig, (size_t)q->n_cig * 4);
         at += q->n; cat += q->n_cig; bat += q->buf_len;
         uint8_t *hdr_keep = q->hdr; q->hdr = NULL; (void)hdr_keep;
@@ -464,7 +471,7 @@ static void records_from_sam(const h_blob *b, h_chroms *chr, h_records *r, const
         if (n_pc) sam_piece_main(&pc[0]);
         for (int k = 1; k < n_pc; ++k) pthread_join(th[k], NULL);
         uint8_t *hdr = r->hdr; const size_t hdr_len = r->hdr_len;
-        free(r->rec_off); free(r->cig_off); free(r->flag); free(r->tid); free(r->pos); free(r->l_qseq); free(r->nm); free(r->nm_seen); free(r->cig);
+        free(r->rec_off); free(r->cig_off); free(r->flag); free(r->tid); free(r->pos); free(r->l_qseq); free(r->nm); free(r->nm_seen); free(r->as_score); free(r->cig);
         records_join(r, pc, n_pc);
         r->hdr = hdr; r->hdr_len = hdr_len;
     }
@@ -574,7 +581,7 @@ int h_write_bam(FILE *fp, const h_records *r, const int64_t *keep, int64_t n_kee
     /* header: blocks of its own (bam_hdr_write ends with bgzf_flush) */
     {   int64_t cut = (int64_t)r->hdr_len;
         if (bgzf_write_stream(fp, r->hdr, &cut, 1, level)) return -1; }
-    /* records, gathered */
+    /* records, gathered in the order given */
     size_t total = 0;
     for (int64_t k = 0; k < n_keep; ++k) total += (size_t)(r->rec_off[keep[k] + 1] - r->rec_off[keep[k]]);
     uint8_t *data = (uint8_t *)h_malloc(total + 1);

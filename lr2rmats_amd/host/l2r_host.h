@@ -75,13 +75,22 @@ typedef struct {
     /* what the tests of `filter` read (l2r_filter_records) */
     uint16_t *flag; int32_t *tid, *pos, *l_qseq, *nm; uint8_t *nm_seen;
     int64_t *cig_off; uint32_t *cig; int64_t n_cig, cap_cig;
+    int32_t *as_score;                     /* `fusion`: bam_aux2i() of the AS tag, 0 without it */
 } h_records;
 void h_read_records(const char *fn, h_chroms *chr, h_records *out, const char *who);
 void h_records_free(h_records *r);
-/* header + the records keep[0..n_keep) (indices, ascending) as a BGZF-compressed BAM stream */
+/* header + the records keep[0..n_keep) (indices; written in the order given) as a BGZF-compressed BAM stream */
 int  h_write_bam(FILE *fp, const h_records *r, const int64_t *keep, int64_t n_keep);
 int  h_records_to_bam(const char *in_fn, const char *out_fn);
 int  h_filter_run(const char *in_fn, const char *remove_fn, const l2r_filter_params *prm, FILE *out, int64_t *n_written);
+
+/* ---- `fusion` (fusion.c).  h_fusion_groups (no GPU): the runs of consecutive MAPPED records with one read name -- rows[k] = record
+ * of row k, group g = rows [group_off[g], group_off[g + 1]), rlen[g] = query length (M I S = X) of its first record, taken from
+ * `qlen` (one word per record, as l2r_fusion_segments leaves it) or, with qlen NULL, from that record's CIGAR; the three
+ * outputs hold r->n, r->n + 1 and r->n words; returns the groups */
+int64_t h_fusion_groups(const h_records *r, const int32_t *qlen, int64_t *rows, int64_t *group_off, int32_t *rlen);
+/* the BAM stream to `out`, the site table to `site` (NULL: none); *n_pairs = candidates */
+int  h_fusion_run(const char *in_fn, const l2r_fusion_params *prm, FILE *out, FILE *site, int64_t *n_pairs);
 
 /* ---- `bam2sj` (sj.c): FASTA, a record source whose memory is bounded by the batch, the reference's junction list */
 typedef struct { int32_t n_seq; int64_t *seq_off; uint8_t *bases; char **name; } h_fasta;      /* sequences in FILE order; seq_off: n_seq + 1 */
@@ -177,6 +186,7 @@ int h_cmd_bam2gtf(int argc, char **argv);
 int h_cmd_unique_gtf(int argc, char **argv);
 int h_cmd_filter(int argc, char **argv);
 int h_cmd_bam2sj(int argc, char **argv);
+int h_cmd_fusion(int argc, char **argv);
 int h_main(int argc, char **argv);
 
 /* ---- staged form of update-gtf, used by the CLI itself and by the one-process-per-GPU driver

@@ -79,6 +79,12 @@ def load_library():
         lib.h_sj_batch_free.restype = None
         lib.h_chroms_free.argtypes = [C.c_void_p]
         lib.h_chroms_free.restype = None
+        lib.h_read_records.argtypes = [C.c_char_p, C.c_void_p, C.c_void_p, C.c_char_p]
+        lib.h_read_records.restype = None
+        lib.h_records_free.argtypes = [C.c_void_p]
+        lib.h_records_free.restype = None
+        lib.h_fusion_groups.argtypes = [C.c_void_p] * 5
+        lib.h_fusion_groups.restype = C.c_int64
         _lib = lib
     return _lib
 
@@ -158,6 +164,31 @@ def sj_read_records(path: str, batch: int = 1 << 20):
     out = {k: (np.concatenate(v) if v else np.zeros(0, dt[k])) for k, v in cols.items()}
     out["cig_off"] = np.concatenate([[0], np.cumsum(np.concatenate(lens) if lens else np.zeros(0, np.int64))]).astype(np.int64)
     out["names"] = names
+    return out
+
+
+# ---- `fusion` (host/fusion.c): the grouping by read name (no GPU)
+
+class _CRecords(C.Structure):
+    _fields_ = [("hdr", C.c_void_p), ("hdr_len", C.c_size_t), ("buf", C.c_void_p), ("buf_len", C.c_size_t), ("n", C.c_int64), ("cap", C.c_int64),
+                ("rec_off", C.POINTER(C.c_int64)), ("flag", C.POINTER(C.c_uint16)), ("tid", C.POINTER(C.c_int32)), ("pos", C.POINTER(C.c_int32)),
+                ("l_qseq", C.POINTER(C.c_int32)), ("nm", C.POINTER(C.c_int32)), ("nm_seen", C.POINTER(C.c_uint8)),
+                ("cig_off", C.POINTER(C.c_int64)), ("cig", C.POINTER(C.c_uint32)), ("n_cig", C.c_int64), ("cap_cig", C.c_int64),
+                ("as_score", C.POINTER(C.c_int32))]
+
+
+def fusion_groups(path: str):
+    """The records of a SAM / gzip SAM / BAM file as ``fusion`` groups them (h_read_records + h_fusion_groups, query lengths walked on the
+    host): dict of rows (record index of every mapped record), group_off, rlen per group, and the records' as_score / nm / flag columns."""
+    lib = load_library()
+    chr_, r = _CChroms(), _CRecords()
+    lib.h_read_records(path.encode(), C.byref(chr_), C.byref(r), b"fusion_groups")
+    n = int(r.n)
+    rows = np.zeros(n + 1, np.int64); goff = np.zeros(n + 2, np.int64); rlen = np.zeros(n + 1, np.int32)
+    g = int(lib.h_fusion_groups(C.byref(r), None, rows.ctypes.data, goff.ctypes.data, rlen.ctypes.data))
+    out = dict(rows=rows[:int(goff[g])].copy(), group_off=goff[:g + 1].copy(), rlen=rlen[:g].copy(),
+               as_score=_arr(r.as_score, n, np.int32).copy(), nm=_arr(r.nm, n, np.int32).copy(), flag=_arr(r.flag, n, np.uint16).copy())
+    lib.h_records_free(C.byref(r)); lib.h_chroms_free(C.byref(chr_))
     return out
 
 
@@ -301,7 +332,7 @@ def records_to_bam(in_path: str, out_path: str) -> int:
 
 
 def run_cli(args, stdout_path=None, cwd=None, env=None) -> subprocess.CompletedProcess:
-    """Run the C binary ``lr2rmats <args>`` (needs a GPU for update-gtf / bam2gtf / unique-gtf -m b).
+    """Run the C binary ``lr2rmats <args>`` (needs a GPU for update-gtf / bam2gtf / unique-gtf -m b / filter / bam2sj / fusion).
     ``env``: extra environment variables (L2R_CHUNK_READS, L2R_ROUTE, L2R_THREADS ...)."""
     full_env = None
     if env:
