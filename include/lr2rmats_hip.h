@@ -370,8 +370,36 @@ int          l2r_sj_download(l2r_ctx *ctx, l2r_sj_table *table);
  * [2] radix passes the last round ran (of 12), [3] rows that went into it, [4] rows it left; with L2R_SJ_TIMING=1 in the environment
  * at l2r_sj_begin (every launch is then waited for), device milliseconds summed since then: [5] k_sj_count [6] k_scan_u32 of the
  * counts [7] k_sj_fill [8] k_sj_hist12 [9] k_sj_digit_hist [10] k_scan_u32 of the tile histograms [11] k_sj_scatter [12] k_sj_heads +
- * its scan [13] k_sj_reduce [14] k_sj_motif; n = words of out (up to 15) */
+ * its scan [13] k_sj_reduce [14] k_sj_motif; n = words of out (up to 15 for `bam2sj`; `sjtab` below adds words from 15 on) */
 int          l2r_sj_stats(l2r_ctx *ctx, double *out, int n);
+
+/* ---- `sjtab` (host/sj.c): the junction table in the form `update-gtf -j` reads (STAR's SJ.out.tab: ..., annotated, unique count,
+ * multi count, maximum overhang), filtered as STAR's outSJfilter* options do.  The table of `bam2sj` with a sixth column:
+ *   overhang  the junction operations (N of at least min_intron bases) cut a record's CIGAR into blocks; a block's length is the
+ *             sum of its M = X lengths (I D S H P B and a shorter N add nothing and cut nothing); a record's overhang at a junction
+ *             is the shorter of the blocks on its two sides (0 where the N is the first or the last operation); a row's max_over is
+ *             the maximum over its records.  The reference has no such rule (src/parse_bam.c:415 stops at the comment).
+ *     l2r_sj_begin_tab   as l2r_sj_begin, with the overhang tracked: l2r_sj_add and l2r_sj_finish carry the column, l2r_sj_add_rows
+ *                   gives its rows overhang 0
+ *     l2r_sj_add_rows_over  rows of tables that carry the column: counts summed, max_over (n words, none negative) by maximum
+ *     l2r_sj_annotate    behind l2r_sj_finish: anno = 1 for every row that is an intron of the annotation -- the interval between two
+ *                   consecutive exons of a transcript (exons ascending inside a transcript, as l2r_set_annotation takes them;
+ *                   transcripts with tid -1 skipped; abutting or overlapping exons give none).  Never called: anno is 0 everywhere
+ *     l2r_sj_filter_rows behind l2r_sj_finish (and l2r_sj_annotate where that is used): a row of category c -- annotated 0; else
+ *                   motif 0: 1, motif 1 2: 2, motif 3 4: 3, motif 5 6: 4 -- stays when
+ *                   max_over >= anchor_min[c] && (uniq_c >= uniq_min[c] || uniq_c + multi_c >= all_min[c]); order kept; *n_rows = rows left
+ *     l2r_sj_download_tab  the nine columns
+ * On a table begun with l2r_sj_begin, or in front of l2r_sj_finish, each of these returns an error (l2r_last_error() says which).
+ * l2r_sj_stats from word 15: [15] rows the last l2r_sj_filter_rows dropped, [16] distinct annotation introns; with L2R_SJ_TIMING=1
+ * device milliseconds of [17] k_sj_introns [18] k_sj_annotate [19] k_sj_keep [20] k_scan_u32 of the keep flags [21] k_sj_take
+ * [22] the sort + reduce of the introns (all its kernels). */
+typedef struct { int32_t anchor_min[5], uniq_min[5], all_min[5]; } l2r_sj_filter;     /* STAR: 30 12 12 12 / 3 1 1 1 / 3 1 1 1 behind the annotated one */
+typedef struct { int64_t cap, n; int32_t *tid, *don, *acc, *uniq_c, *multi_c; uint8_t *strand, *motif; uint8_t *anno; int32_t *max_over; } l2r_sj_tab;   /* l2r_sj_table + two */
+int          l2r_sj_begin_tab(l2r_ctx *ctx, const l2r_sj_params *prm, const l2r_sj_genome *genome);
+int          l2r_sj_add_rows_over(l2r_ctx *ctx, const l2r_junctions *rows, const int32_t *max_over);
+int          l2r_sj_annotate(l2r_ctx *ctx, const l2r_annotation *anno);
+int          l2r_sj_filter_rows(l2r_ctx *ctx, const l2r_sj_filter *filter, int64_t *n_rows);
+int          l2r_sj_download_tab(l2r_ctx *ctx, l2r_sj_tab *table);
 
 #ifdef __cplusplus
 }

@@ -32,6 +32,7 @@ EXPORTS = [
     "l2r_debug_counters", "l2r_debug_stamps", "l2r_debug_tile_times", "l2r_upload_index_ms", "l2r_hint_single_run",
     "l2r_xchg_id_bytes", "l2r_xchg_unique_id", "l2r_xchg_create", "l2r_xchg_gather_results", "l2r_xchg_gather_accepted", "l2r_xchg_destroy",
     "l2r_sj_begin", "l2r_sj_add", "l2r_sj_add_rows", "l2r_sj_finish", "l2r_sj_download", "l2r_sj_stats",
+    "l2r_sj_begin_tab", "l2r_sj_add_rows_over", "l2r_sj_annotate", "l2r_sj_filter_rows", "l2r_sj_download_tab",
     "l2r_fusion_segments", "l2r_fusion_select", "l2r_fusion_stats",
 ]
 SJ_E_UNKNOWN_TID = -3
@@ -111,6 +112,17 @@ class CSjTable(C.Structure):
                 ("uniq_c", C.c_void_p), ("multi_c", C.c_void_p), ("strand", C.c_void_p), ("motif", C.c_void_p)]
 
 
+class CSjTab(C.Structure):
+    _fields_ = CSjTable._fields_ + [("anno", C.c_void_p), ("max_over", C.c_void_p)]
+
+
+class CSjFilter(C.Structure):
+    _fields_ = [("anchor_min", C.c_int32 * 5), ("uniq_min", C.c_int32 * 5), ("all_min", C.c_int32 * 5)]
+
+
+SJ_FILTER_DEFAULTS = ((1, 30, 12, 12, 12), (0, 3, 1, 1, 1), (0, 3, 1, 1, 1))      # anchor, unique, total: STAR's outSJfilter* behind the annotated class
+
+
 class CTiming(C.Structure):
     _fields_ = [("stage_ms", C.c_float * N_STAGES), ("total_ms", C.c_float), ("iters", C.c_int32)]
 
@@ -177,6 +189,11 @@ def load_library():
             getattr(lib, name).argtypes = [C.c_void_p, C.c_void_p]
         lib.l2r_sj_begin.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         lib.l2r_sj_stats.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
+        lib.l2r_sj_begin_tab.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        lib.l2r_sj_add_rows_over.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        lib.l2r_sj_annotate.argtypes = [C.c_void_p, C.c_void_p]
+        lib.l2r_sj_filter_rows.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        lib.l2r_sj_download_tab.argtypes = [C.c_void_p, C.c_void_p]
         _lib = lib
     return _lib
 
@@ -211,8 +228,17 @@ class SjTable:
     motif: np.ndarray
 
 
+@dataclass
+class SjTab(SjTable):
+    """The table of ``sjtab``: SjTable and the annotated flag and the maximum overhang of every row."""
+    anno: np.ndarray
+    max_over: np.ndarray
+
+
 SJ_STAT_NAMES = ["rows_made", "rounds", "radix_passes", "rows_in", "rows_out", "k_sj_count", "k_scan_u32 (counts)", "k_sj_fill", "k_sj_hist12",
-                 "k_sj_digit_hist", "k_scan_u32 (tile histograms)", "k_sj_scatter", "k_sj_heads + scan", "k_sj_reduce", "k_sj_motif"]
+                 "k_sj_digit_hist", "k_scan_u32 (tile histograms)", "k_sj_scatter", "k_sj_heads + scan", "k_sj_reduce", "k_sj_motif",
+                 "rows_dropped", "anno_introns", "k_sj_introns", "k_sj_annotate", "k_sj_keep", "k_scan_u32 (keep flags)", "k_sj_take",
+                 "intron sort + reduce"]
 
 
 FUSION_STAT_NAMES = ["wave_form", "k_fusion_seg", "k_fusion_select", "k_filter_score", "k_filter_select"]
@@ -332,15 +358,22 @@ class Engine:
         return {k: float(v) for k, v in zip(FUSION_STAT_NAMES, out)}
 
     # ---- `bam2sj` (include/lr2rmats_hip.h: l2r_sj_begin / _add / _add_rows / _finish / _download)
-    def sj_begin(self, min_intron: int = 3, pair_only: bool = True, genome=None):
-        """``genome``: (seq_off [n_seq + 1] int64, bases uint8) with the sequences in file order, or None (no -g)."""
+    def sj_begin(self, min_intron: int = 3, pair_only: bool = True, genome=None, tab: bool = False):
+        """``genome``: (seq_off [n_seq + 1] int64, bases uint8) with the sequences in file order, or None (no -g).
+        ``tab``: l2r_sj_begin_tab -- the table carries the overhang column (``sj_begin_tab``)."""
         prm = CSjParams(min_intron, 1 if pair_only else 0)
+        begin = self.lib.l2r_sj_begin_tab if tab else self.lib.l2r_sj_begin
+        self._sj_tab = bool(tab)
         if genome is None:
-            self._chk(self.lib.l2r_sj_begin(self.ctx, C.byref(prm), None))
+            self._chk(begin(self.ctx, C.byref(prm), None))
             return
         off = np.ascontiguousarray(genome[0], np.int64); bases = np.ascontiguousarray(genome[1], np.uint8)
         g = CSjGenome(len(off) - 1, off.ctypes.data, bases.ctypes.data)
-        self._chk(self.lib.l2r_sj_begin(self.ctx, C.byref(prm), C.byref(g)))
+        self._chk(begin(self.ctx, C.byref(prm), C.byref(g)))
+
+    def sj_begin_tab(self, min_intron: int = 3, pair_only: bool = False, genome=None):
+        """The table of ``sjtab``: as sj_begin, with the overhang of every row tracked; sj_finish then returns an SjTab."""
+        self.sj_begin(min_intron, pair_only, genome, tab=True)
 
     def sj_add(self, flag, tid, pos, uniq, cig_off, cig):
         """One batch of records (the columns of l2r_sj_records)."""
@@ -355,15 +388,46 @@ class Engine:
         cj = CJunctions(len(a[0]), *[_ptr(x, _i32p) for x in a])
         self._chk(self.lib.l2r_sj_add_rows(self.ctx, C.byref(cj)))
 
+    def sj_add_rows_over(self, tid, don, acc, uniq_c, multi_c, max_over):
+        """Rows of tables that carry the overhang column: counts summed, overhangs by maximum (a table of sj_begin_tab only)."""
+        a = [np.ascontiguousarray(x, np.int32) for x in (tid, don, acc, uniq_c, multi_c, max_over)]
+        cj = CJunctions(len(a[0]), *[_ptr(x, _i32p) for x in a[:5]])
+        self._chk(self.lib.l2r_sj_add_rows_over(self.ctx, C.byref(cj), a[5].ctypes.data))
+
     def sj_finish(self) -> SjTable:
-        """Sort + reduce + motifs, then the table as numpy columns.  An unknown tid raises L2RError (rc = SJ_E_UNKNOWN_TID)."""
+        """Sort + reduce + motifs, then the table as numpy columns (an SjTab with its nine columns for a table of sj_begin_tab).
+        An unknown tid raises L2RError (rc = SJ_E_UNKNOWN_TID)."""
         n = C.c_int64(0)
         self._chk(self.lib.l2r_sj_finish(self.ctx, C.byref(n)))
         m = int(n.value)
+        if getattr(self, "_sj_tab", False):
+            return self.sj_download_tab(m)
         cols = [np.zeros(max(m, 1), np.int32) for _ in range(5)] + [np.zeros(max(m, 1), np.uint8) for _ in range(2)]
         t = CSjTable(max(m, 1), 0, *[x.ctypes.data for x in cols])
         self._chk(self.lib.l2r_sj_download(self.ctx, C.byref(t)))
         return SjTable(*[x[:m] for x in cols])
+
+    def sj_download_tab(self, n_rows: int) -> SjTab:
+        """l2r_sj_download_tab into room for ``n_rows`` rows (what sj_finish / sj_filter_rows reported)."""
+        m = max(int(n_rows), 1)
+        cols = [np.zeros(m, np.int32) for _ in range(5)] + [np.zeros(m, np.uint8) for _ in range(3)] + [np.zeros(m, np.int32)]
+        t = CSjTab(int(n_rows), 0, *[x.ctypes.data for x in cols])
+        self._chk(self.lib.l2r_sj_download_tab(self.ctx, C.byref(t)))
+        return SjTab(*[x[:int(t.n)] for x in cols])
+
+    def sj_annotate(self, tx_tid, tx_ex_off, ex_start, ex_end) -> None:
+        """l2r_sj_annotate (behind sj_finish): rows that are an intron of these transcripts get anno = 1."""
+        a = [np.ascontiguousarray(tx_tid, np.int32), np.ascontiguousarray(tx_ex_off, np.int64), np.ascontiguousarray(ex_start, np.int32),
+             np.ascontiguousarray(ex_end, np.int32)]
+        ca = CAnnotation(len(a[0]), len(a[2]), _ptr(a[0], _i32p), None, None, None, _ptr(a[1], _i64p), _ptr(a[2], _i32p), _ptr(a[3], _i32p))
+        self._chk(self.lib.l2r_sj_annotate(self.ctx, C.byref(ca)))
+
+    def sj_filter_rows(self, anchor_min=SJ_FILTER_DEFAULTS[0], uniq_min=SJ_FILTER_DEFAULTS[1], all_min=SJ_FILTER_DEFAULTS[2]) -> SjTab:
+        """l2r_sj_filter_rows (behind sj_finish and sj_annotate): the rows that stay, as an SjTab."""
+        f = CSjFilter((C.c_int32 * 5)(*[int(v) for v in anchor_min]), (C.c_int32 * 5)(*[int(v) for v in uniq_min]), (C.c_int32 * 5)(*[int(v) for v in all_min]))
+        n = C.c_int64(0)
+        self._chk(self.lib.l2r_sj_filter_rows(self.ctx, C.byref(f), C.byref(n)))
+        return self.sj_download_tab(int(n.value))
 
     def sj_stats(self) -> dict:
         """l2r_sj_stats: counters, and with L2R_SJ_TIMING=1 device milliseconds per kernel."""

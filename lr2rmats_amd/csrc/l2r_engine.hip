@@ -76,12 +76,13 @@ enum class Pipeline { classic, slab, tile };
 // `bam2sj` (l2r_sj.hip.h): what lives between l2r_sj_begin and l2r_sj_download.  Every buffer belongs to the context and is used again
 // by the next batch; the two row buffers take turns as source and target of the radix passes and of the reduction.
 struct SjRowBuf {
-    DevBuf<int32_t> col[5];
+    DevBuf<int32_t> col[6];                 // col[5], the overhang: only in a table begun with l2r_sj_begin_tab
     size_t cap = 0;
-    SjCols cols() const { return SjCols{col[0].p, col[1].p, col[2].p, col[3].p, col[4].p}; }
+    SjCols cols() const { return SjCols{col[0].p, col[1].p, col[2].p, col[3].p, col[4].p, col[5].p}; }
 };
 struct SjState {
     bool open = false, finished = false, timing = false;
+    bool over = false;                      // l2r_sj_begin_tab: six columns, the OVER instances of fill / scatter / reduce
     SjPrm prm{3, 1};
     int32_t n_seq = 0;
     DevBuf<int64_t> seq_off; DevBuf<uint8_t> bases;
@@ -89,11 +90,16 @@ struct SjState {
     int64_t n_rows = 0;                     // rows[cur] holds that many
     int64_t compact_rows = (int64_t)1 << 24, compact_at = (int64_t)1 << 24;     // L2R_SJ_COMPACT_ROWS: rows beyond which an add sorts and reduces what is there
     DevBuf<uint16_t> flag; DevBuf<int32_t> tid, pos; DevBuf<uint8_t> uniq; DevBuf<int64_t> cig_off; DevBuf<uint32_t> cig, cnt;   // one batch
-    DevBuf<uint32_t> hist12, tile_hist, head, word;     // word[0]: a scan's total, word[1]: k_sj_motif's bad row
-    DevBuf<uint8_t> strand, motif;
-    double stats[15] = {0};
+    DevBuf<uint32_t> hist12, tile_hist, head, word;     // word[0]: a scan's total, word[1]: k_sj_motif's bad row, word[2]: k_sj_introns' row count
+    DevBuf<uint8_t> strand[2], motif[2], anno[2]; int bcur = 0;      // per-row bytes; the filter moves them to the other set
+    double stats[24] = {0};
     hipEvent_t ev[2] = {nullptr, nullptr};
     ~SjState() { for (int k = 0; k < 2; ++k) if (ev[k]) (void)hipEventDestroy(ev[k]); }
+};
+// the annotation of l2r_sj_annotate on the device, and its introns: a table of their own (five columns), sorted and made unique by sj_compact
+struct SjIntrons {
+    DevBuf<int32_t> tx_tid, ex_start, ex_end; DevBuf<int64_t> tx_ex_off;
+    SjState st;
 };
 
 // What l2r_sync has learned from the counters of a completed run of the tile path (fetch_run_facts): a later run of the same inputs,
@@ -240,7 +246,8 @@ struct l2r_ctx {
     DevBuf<unsigned long long> stamps;      // diagnostics, L2R_STAMPS=1
     uint32_t h_totals[3] = {0, 0, 0};
     bool totals_valid = false;
-    SjState sj;                             // `bam2sj`
+    SjState sj;                             // `bam2sj`, `sjtab`
+    SjIntrons sj_intr;                      // `sjtab`: l2r_sj_annotate
     double fusion_stats[5] = {0, 0, 0, 0, 0};        // `fusion`: l2r_fusion_stats
 };
 
@@ -2116,12 +2123,11 @@ int l2r_fusion_stats(l2r_ctx *c, double *out, int n)
     return 0;
 }
 
-// ---------------------------------------------------------------------------------------------- bam2sj
+// ---------------------------------------------------------------------------------------------- bam2sj, sjtab
 extern "C++" {
 // a launch (or a group of launches) on the context stream; with L2R_SJ_TIMING=1 bracketed by events, waited for and added to stats[slot]
-template <typename F> static int sj_launch(l2r_ctx *c, int slot, F f)
+template <typename F> static int sj_launch(l2r_ctx *c, SjState &s, int slot, F f)
 {
-    SjState &s = c->sj;
     if (s.timing) HIP_TRY(hipEventRecord(s.ev[0], c->stream));
     f();
     HIP_TRY(hipGetLastError());
@@ -2136,37 +2142,40 @@ template <typename F> static int sj_launch(l2r_ctx *c, int slot, F f)
 }
 }
 
+// slots of l2r_sj_stats behind the fifteen of `bam2sj`
+enum { SJS_DROPPED = 15, SJS_INTRONS, SJS_K_INTRONS, SJS_K_ANNOTATE, SJS_K_KEEP, SJS_K_KEEP_SCAN, SJS_K_TAKE, SJS_INTRON_SORT, SJS_N };
+
 // room for `want` rows; the first `keep` rows stay (DevBuf::ensure carries nothing over, so the columns are moved here)
-static int sj_rows_reserve(l2r_ctx *c, SjRowBuf &b, size_t want, size_t keep)
+static int sj_rows_reserve(l2r_ctx *c, const SjState &s, SjRowBuf &b, size_t want, size_t keep)
 {
-    if (want <= b.cap) return 0;
-    const size_t cap = std::max(std::max(want, b.cap * 2), (size_t)1 << 16);
-    int32_t *q[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+    const int n_col = s.over ? 6 : 5;
+    if (want <= b.cap && (!s.over || b.col[5].cap >= b.cap)) return 0;
+    const size_t cap = want <= b.cap ? b.cap : std::max(std::max(want, b.cap * 2), (size_t)1 << 16);      // (want <= cap: only the sixth column is missing)
+    int32_t *q[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
     hipError_t e = hipSuccess;
-    for (int k = 0; k < 5 && e == hipSuccess; ++k) {
+    for (int k = 0; k < n_col && e == hipSuccess; ++k) {
         e = hipMalloc((void **)&q[k], cap * sizeof(int32_t));
         if (e == hipSuccess && keep) e = hipMemcpyAsync(q[k], b.col[k].p, keep * sizeof(int32_t), hipMemcpyDeviceToDevice, c->stream);
     }
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
     if (e != hipSuccess) {
-        for (int k = 0; k < 5; ++k) if (q[k]) (void)hipFree(q[k]);
+        for (int k = 0; k < n_col; ++k) if (q[k]) (void)hipFree(q[k]);
         return fail(-2, "[l2r_sj] %zu junction rows: %s", cap, hipGetErrorString(e));
     }
-    for (int k = 0; k < 5; ++k) { b.col[k].release(); b.col[k].p = q[k]; b.col[k].cap = cap; }
+    for (int k = 0; k < n_col; ++k) { b.col[k].release(); b.col[k].p = q[k]; b.col[k].cap = cap; }
     b.cap = cap;
     return 0;
 }
 
-static int sj_scan(l2r_ctx *c, int slot, uint32_t *v, int64_t n)
+static int sj_scan(l2r_ctx *c, SjState &s, int slot, uint32_t *v, int64_t n)
 {
-    ScanJobs jobs = {}; jobs.job[0] = ScanJob{v, n, c->sj.word.p}; jobs.job[1] = jobs.job[0];
-    return sj_launch(c, slot, [&] { hipLaunchKernelGGL(k_scan_u32, dim3(1), dim3(1024), 0, c->stream, jobs); });
+    ScanJobs jobs = {}; jobs.job[0] = ScanJob{v, n, s.word.p}; jobs.job[1] = jobs.job[0];
+    return sj_launch(c, s, slot, [&] { hipLaunchKernelGGL(k_scan_u32, dim3(1), dim3(1024), 0, c->stream, jobs); });
 }
 
-// rows[cur][0, n_rows) -> sorted by (tid, don, acc), one row per key with the count columns summed
-static int sj_compact(l2r_ctx *c)
+// s.rows[cur][0, n_rows) -> sorted by (tid, don, acc), one row per key with the count columns summed (and, s.over, the overhangs' maximum)
+static int sj_compact(l2r_ctx *c, SjState &s)
 {
-    SjState &s = c->sj;
     const int64_t n64 = s.n_rows;
     s.stats[1] += 1; s.stats[2] = 0; s.stats[3] = (double)n64; s.stats[4] = 0;
     if (n64 == 0) return 0;
@@ -2174,12 +2183,12 @@ static int sj_compact(l2r_ctx *c)
     const uint32_t n = (uint32_t)n64;
     const unsigned grid = (n + SJ_THREADS - 1) / SJ_THREADS;
     const uint32_t n_tiles = (n + SJ_SORT_TILE - 1) / SJ_SORT_TILE;
-    if (sj_rows_reserve(c, s.rows[1 - s.cur], n, 0) || s.hist12.ensure(SJ_KEY_BYTES * 256) || s.tile_hist.ensure((size_t)256 * n_tiles + 1) ||
+    if (sj_rows_reserve(c, s, s.rows[1 - s.cur], n, 0) || s.hist12.ensure(SJ_KEY_BYTES * 256) || s.tile_hist.ensure((size_t)256 * n_tiles + 1) ||
         s.head.ensure((size_t)n + 1) || s.word.ensure(4)) return -2;
     // which key bytes differ at all
     uint32_t h12[SJ_KEY_BYTES * 256];
     HIP_TRY(hipMemsetAsync(s.hist12.p, 0, sizeof h12, c->stream));
-    int rc = sj_launch(c, 8, [&] { hipLaunchKernelGGL(k_sj_hist12, dim3(std::min(grid, 2048u)), dim3(SJ_THREADS), 0, c->stream, s.rows[s.cur].cols(), n, s.hist12.p); });
+    int rc = sj_launch(c, s, 8, [&] { hipLaunchKernelGGL(k_sj_hist12, dim3(std::min(grid, 2048u)), dim3(SJ_THREADS), 0, c->stream, s.rows[s.cur].cols(), n, s.hist12.p); });
     if (rc) return rc;
     HIP_TRY(hipMemcpyAsync(h12, s.hist12.p, sizeof h12, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
@@ -2189,14 +2198,17 @@ static int sj_compact(l2r_ctx *c)
         for (int d = 0; d < 256; ++d) if (h12[b * 256 + d] == n) { one_value = true; break; }
         if (one_value) continue;
         const SjCols in = s.rows[src].cols(), out = s.rows[1 - src].cols();
-        if ((rc = sj_launch(c, 9, [&] { hipLaunchKernelGGL(k_sj_digit_hist, dim3(n_tiles), dim3(SJ_THREADS), 0, c->stream, in, n, b, n_tiles, s.tile_hist.p); }))) return rc;
-        if ((rc = sj_scan(c, 10, s.tile_hist.p, (int64_t)256 * n_tiles))) return rc;
-        if ((rc = sj_launch(c, 11, [&] { hipLaunchKernelGGL(k_sj_scatter, dim3(n_tiles), dim3(SJ_THREADS), 0, c->stream, in, out, n, b, n_tiles, (const uint32_t *)s.tile_hist.p); }))) return rc;
+        if ((rc = sj_launch(c, s, 9, [&] { hipLaunchKernelGGL(k_sj_digit_hist, dim3(n_tiles), dim3(SJ_THREADS), 0, c->stream, in, n, b, n_tiles, s.tile_hist.p); }))) return rc;
+        if ((rc = sj_scan(c, s, 10, s.tile_hist.p, (int64_t)256 * n_tiles))) return rc;
+        if ((rc = sj_launch(c, s, 11, [&] {
+                if (s.over) hipLaunchKernelGGL(k_sj_scatter<true>, dim3(n_tiles), dim3(SJ_THREADS), 0, c->stream, in, out, n, b, n_tiles, (const uint32_t *)s.tile_hist.p);
+                else hipLaunchKernelGGL(k_sj_scatter<false>, dim3(n_tiles), dim3(SJ_THREADS), 0, c->stream, in, out, n, b, n_tiles, (const uint32_t *)s.tile_hist.p);
+            }))) return rc;
         src = 1 - src; ++passes;
     }
     // runs of equal keys
-    if ((rc = sj_launch(c, 12, [&] { hipLaunchKernelGGL(k_sj_heads, dim3(grid), dim3(SJ_THREADS), 0, c->stream, s.rows[src].cols(), n, s.head.p); }))) return rc;
-    if ((rc = sj_scan(c, 12, s.head.p, (int64_t)n))) return rc;
+    if ((rc = sj_launch(c, s, 12, [&] { hipLaunchKernelGGL(k_sj_heads, dim3(grid), dim3(SJ_THREADS), 0, c->stream, s.rows[src].cols(), n, s.head.p); }))) return rc;
+    if ((rc = sj_scan(c, s, 12, s.head.p, (int64_t)n))) return rc;
     uint32_t n_runs = 0;
     HIP_TRY(hipMemcpyAsync(&n_runs, s.word.p, 4, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
@@ -2204,31 +2216,42 @@ static int sj_compact(l2r_ctx *c)
     const int dst = 1 - src;
     HIP_TRY(hipMemsetAsync(s.rows[dst].col[3].p, 0, (size_t)n_runs * 4, c->stream));
     HIP_TRY(hipMemsetAsync(s.rows[dst].col[4].p, 0, (size_t)n_runs * 4, c->stream));
-    if ((rc = sj_launch(c, 13, [&] { hipLaunchKernelGGL(k_sj_reduce, dim3(grid), dim3(SJ_THREADS), 0, c->stream, s.rows[src].cols(), n, (const uint32_t *)s.head.p, s.rows[dst].cols(), n_runs); }))) return rc;
+    if (s.over) { HIP_TRY(hipMemsetAsync(s.rows[dst].col[5].p, 0, (size_t)n_runs * 4, c->stream)); }
+    if ((rc = sj_launch(c, s, 13, [&] {
+            if (s.over) hipLaunchKernelGGL(k_sj_reduce<true>, dim3(grid), dim3(SJ_THREADS), 0, c->stream, s.rows[src].cols(), n, (const uint32_t *)s.head.p, s.rows[dst].cols(), n_runs);
+            else hipLaunchKernelGGL(k_sj_reduce<false>, dim3(grid), dim3(SJ_THREADS), 0, c->stream, s.rows[src].cols(), n, (const uint32_t *)s.head.p, s.rows[dst].cols(), n_runs);
+        }))) return rc;
     s.cur = dst; s.n_rows = n_runs;
     s.stats[2] = passes; s.stats[4] = n_runs;
     s.compact_at = std::max(s.compact_rows, 2 * s.n_rows);
     return 0;
 }
 
-int l2r_sj_begin(l2r_ctx *c, const l2r_sj_params *prm, const l2r_sj_genome *g)
+// what l2r_sj_begin and l2r_sj_begin_tab share; `intr`: the state of the annotation introns (no genome, no batches)
+static int sj_state_begin(l2r_ctx *c, SjState &s, bool over)
 {
-    if (!c || !prm) return fail(-1, "[l2r_sj_begin] null argument");
-    if (g && (g->n_seq < 0 || (g->n_seq > 0 && (!g->seq_off || !g->bases)))) return fail(-1, "[l2r_sj_begin] bad genome");
-    HIP_TRY(hipSetDevice(c->device));
-    SjState &s = c->sj;
-    s.open = false; s.finished = false; s.n_rows = 0; s.cur = 0; s.n_seq = 0;
+    s.open = false; s.finished = false; s.n_rows = 0; s.cur = 0; s.bcur = 0; s.n_seq = 0; s.over = over;
     for (double &v : s.stats) v = 0;
-    s.prm = SjPrm{prm->min_intron, prm->pair_only};
     const char *e = getenv("L2R_SJ_COMPACT_ROWS");
     s.compact_rows = e && atoll(e) > 0 ? atoll(e) : (int64_t)1 << 24;
     s.compact_at = s.compact_rows;
     s.timing = getenv("L2R_SJ_TIMING") != nullptr && atoi(getenv("L2R_SJ_TIMING")) != 0;
     for (int k = 0; k < 2; ++k) if (!s.ev[k]) HIP_TRY(hipEventCreate(&s.ev[k]));
     if (s.word.ensure(4)) return -2;
+    return 0;
+}
+
+static int sj_begin(l2r_ctx *c, const l2r_sj_params *prm, const l2r_sj_genome *g, bool over, const char *who)
+{
+    if (!c || !prm) return fail(-1, "[%s] null argument", who);
+    if (g && (g->n_seq < 0 || (g->n_seq > 0 && (!g->seq_off || !g->bases)))) return fail(-1, "[%s] bad genome", who);
+    HIP_TRY(hipSetDevice(c->device));
+    SjState &s = c->sj;
+    int rc;
+    if ((rc = sj_state_begin(c, s, over))) return rc;
+    s.prm = SjPrm{prm->min_intron, prm->pair_only};
     if (g && g->n_seq > 0) {
-        for (int32_t k = 0; k < g->n_seq; ++k) if (g->seq_off[k + 1] < g->seq_off[k] || g->seq_off[0] != 0) return fail(-1, "[l2r_sj_begin] sequence offsets do not ascend from 0");
-        int rc;
+        for (int32_t k = 0; k < g->n_seq; ++k) if (g->seq_off[k + 1] < g->seq_off[k] || g->seq_off[0] != 0) return fail(-1, "[%s] sequence offsets do not ascend from 0", who);
         if ((rc = to_dev(c, s.seq_off, g->seq_off, (size_t)g->n_seq + 1)) || (rc = to_dev(c, s.bases, g->bases, (size_t)g->seq_off[g->n_seq]))) return rc;
         HIP_TRY(hipStreamSynchronize(c->stream));
         s.n_seq = g->n_seq;
@@ -2237,11 +2260,14 @@ int l2r_sj_begin(l2r_ctx *c, const l2r_sj_params *prm, const l2r_sj_genome *g)
     return 0;
 }
 
+int l2r_sj_begin(l2r_ctx *c, const l2r_sj_params *prm, const l2r_sj_genome *g) { return sj_begin(c, prm, g, false, "l2r_sj_begin"); }
+int l2r_sj_begin_tab(l2r_ctx *c, const l2r_sj_params *prm, const l2r_sj_genome *g) { return sj_begin(c, prm, g, true, "l2r_sj_begin_tab"); }
+
 static int sj_after_add(l2r_ctx *c, int64_t added)
 {
     SjState &s = c->sj;
     s.n_rows += added; s.stats[0] += (double)added; s.finished = false;
-    return s.n_rows > s.compact_at ? sj_compact(c) : 0;
+    return s.n_rows > s.compact_at ? sj_compact(c, s) : 0;
 }
 
 int l2r_sj_add(l2r_ctx *c, const l2r_sj_records *r)
@@ -2262,33 +2288,55 @@ int l2r_sj_add(l2r_ctx *c, const l2r_sj_records *r)
     if (s.cnt.ensure(N + 1)) return -2;
     const SjRecs recs{(int64_t)N, s.flag.p, s.tid.p, s.pos.p, s.uniq.p, s.cig_off.p, s.cig.p};
     const unsigned grid = (unsigned)((N + SJ_THREADS - 1) / SJ_THREADS);
-    if ((rc = sj_launch(c, 5, [&] { hipLaunchKernelGGL(k_sj_count, dim3(grid), dim3(SJ_THREADS), 0, c->stream, recs, s.prm, s.cnt.p); }))) return rc;
-    if ((rc = sj_scan(c, 6, s.cnt.p, (int64_t)N))) return rc;
+    if ((rc = sj_launch(c, s, 5, [&] { hipLaunchKernelGGL(k_sj_count, dim3(grid), dim3(SJ_THREADS), 0, c->stream, recs, s.prm, s.cnt.p); }))) return rc;
+    if ((rc = sj_scan(c, s, 6, s.cnt.p, (int64_t)N))) return rc;
     uint32_t total = 0;
     HIP_TRY(hipMemcpyAsync(&total, s.word.p, 4, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     if (total == 0) return 0;
-    if ((rc = sj_rows_reserve(c, s.rows[s.cur], (size_t)s.n_rows + total, (size_t)s.n_rows))) return rc;
-    if ((rc = sj_launch(c, 7, [&] { hipLaunchKernelGGL(k_sj_fill, dim3(grid), dim3(SJ_THREADS), 0, c->stream, recs, s.prm, (const uint32_t *)s.cnt.p, s.rows[s.cur].cols(),
-                                                        s.n_rows, s.n_rows + (int64_t)total); }))) return rc;
+    if ((rc = sj_rows_reserve(c, s, s.rows[s.cur], (size_t)s.n_rows + total, (size_t)s.n_rows))) return rc;
+    if ((rc = sj_launch(c, s, 7, [&] {
+            if (s.over) hipLaunchKernelGGL(k_sj_fill<true>, dim3(grid), dim3(SJ_THREADS), 0, c->stream, recs, s.prm, (const uint32_t *)s.cnt.p, s.rows[s.cur].cols(), s.n_rows, s.n_rows + (int64_t)total);
+            else hipLaunchKernelGGL(k_sj_fill<false>, dim3(grid), dim3(SJ_THREADS), 0, c->stream, recs, s.prm, (const uint32_t *)s.cnt.p, s.rows[s.cur].cols(), s.n_rows, s.n_rows + (int64_t)total);
+        }))) return rc;
     return sj_after_add(c, (int64_t)total);
+}
+
+// max_over: NULL -> the rows' overhang is 0 (only looked at in a table that has the column)
+static int sj_add_rows(l2r_ctx *c, const l2r_junctions *j, const int32_t *max_over, const char *who)
+{
+    SjState &s = c->sj;
+    if (j->n < 0 || j->n >= ((int64_t)1 << 31)) return fail(-1, "[%s] fewer than 2^31 rows at a time", who);
+    if (j->n == 0) return 0;
+    if (!j->tid || !j->don || !j->acc || !j->uniq_c || !j->multi_c) return fail(-1, "[%s] null column", who);
+    if (max_over) for (int64_t i = 0; i < j->n; ++i) if (max_over[i] < 0) return fail(-1, "[%s] row %lld: negative overhang", who, (long long)i);
+    HIP_TRY(hipSetDevice(c->device));
+    int rc;
+    if ((rc = sj_rows_reserve(c, s, s.rows[s.cur], (size_t)(s.n_rows + j->n), (size_t)s.n_rows))) return rc;
+    const int32_t *src[5] = {j->tid, j->don, j->acc, j->uniq_c, j->multi_c};
+    for (int k = 0; k < 5; ++k) HIP_TRY(hipMemcpyAsync(s.rows[s.cur].col[k].p + s.n_rows, src[k], (size_t)j->n * 4, hipMemcpyHostToDevice, c->stream));
+    if (s.over) {
+        if (max_over) { HIP_TRY(hipMemcpyAsync(s.rows[s.cur].col[5].p + s.n_rows, max_over, (size_t)j->n * 4, hipMemcpyHostToDevice, c->stream)); }
+        else { HIP_TRY(hipMemsetAsync(s.rows[s.cur].col[5].p + s.n_rows, 0, (size_t)j->n * 4, c->stream)); }
+    }
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return sj_after_add(c, j->n);
 }
 
 int l2r_sj_add_rows(l2r_ctx *c, const l2r_junctions *j)
 {
     if (!c || !j) return fail(-1, "[l2r_sj_add_rows] null argument");
-    SjState &s = c->sj;
-    if (!s.open) return fail(-1, "[l2r_sj_add_rows] l2r_sj_begin comes first");
-    if (j->n < 0 || j->n >= ((int64_t)1 << 31)) return fail(-1, "[l2r_sj_add_rows] fewer than 2^31 rows at a time");
-    if (j->n == 0) return 0;
-    if (!j->tid || !j->don || !j->acc || !j->uniq_c || !j->multi_c) return fail(-1, "[l2r_sj_add_rows] null column");
-    HIP_TRY(hipSetDevice(c->device));
-    int rc;
-    if ((rc = sj_rows_reserve(c, s.rows[s.cur], (size_t)(s.n_rows + j->n), (size_t)s.n_rows))) return rc;
-    const int32_t *src[5] = {j->tid, j->don, j->acc, j->uniq_c, j->multi_c};
-    for (int k = 0; k < 5; ++k) HIP_TRY(hipMemcpyAsync(s.rows[s.cur].col[k].p + s.n_rows, src[k], (size_t)j->n * 4, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    return sj_after_add(c, j->n);
+    if (!c->sj.open) return fail(-1, "[l2r_sj_add_rows] l2r_sj_begin comes first");
+    return sj_add_rows(c, j, nullptr, "l2r_sj_add_rows");
+}
+
+int l2r_sj_add_rows_over(l2r_ctx *c, const l2r_junctions *j, const int32_t *max_over)
+{
+    if (!c || !j) return fail(-1, "[l2r_sj_add_rows_over] null argument");
+    if (!c->sj.open) return fail(-1, "[l2r_sj_add_rows_over] l2r_sj_begin_tab comes first");
+    if (!c->sj.over) return fail(-1, "[l2r_sj_add_rows_over] the table was begun with l2r_sj_begin: it has no overhang column (l2r_sj_begin_tab)");
+    if (j->n > 0 && !max_over) return fail(-1, "[l2r_sj_add_rows_over] null column");
+    return sj_add_rows(c, j, max_over, "l2r_sj_add_rows_over");
 }
 
 int l2r_sj_finish(l2r_ctx *c, int64_t *n_rows)
@@ -2298,16 +2346,22 @@ int l2r_sj_finish(l2r_ctx *c, int64_t *n_rows)
     if (!s.open) return fail(-1, "[l2r_sj_finish] l2r_sj_begin comes first");
     HIP_TRY(hipSetDevice(c->device));
     int rc;
-    if ((rc = sj_compact(c))) return rc;
+    if ((rc = sj_compact(c, s))) return rc;
     const uint32_t n = (uint32_t)s.n_rows;
-    if (s.strand.ensure(n ? n : 1) || s.motif.ensure(n ? n : 1)) return -2;
+    s.bcur = 0;
+    if (s.strand[0].ensure(n ? n : 1) || s.motif[0].ensure(n ? n : 1)) return -2;
+    if (s.over) {                                               // anno: all 0 until l2r_sj_annotate says otherwise
+        if (s.anno[0].ensure(n ? n : 1)) return -2;
+        HIP_TRY(hipMemsetAsync(s.anno[0].p, 0, n ? n : 1, c->stream));
+        s.stats[SJS_DROPPED] = 0; s.stats[SJS_INTRONS] = 0;
+    }
     if (n) {
         uint32_t bad = 0xffffffffu;
         HIP_TRY(hipMemcpyAsync(s.word.p + 1, &bad, 4, hipMemcpyHostToDevice, c->stream));
         const SjGenome g{s.n_seq, s.seq_off.p, s.bases.p};
         const SjCols t = s.rows[s.cur].cols();
-        if ((rc = sj_launch(c, 14, [&] { hipLaunchKernelGGL(k_sj_motif, dim3((n + SJ_THREADS - 1) / SJ_THREADS), dim3(SJ_THREADS), 0, c->stream, (const int32_t *)t.tid, (const int32_t *)t.don,
-                                                             (const int32_t *)t.acc, n, g, s.strand.p, s.motif.p, s.word.p + 1); }))) return rc;
+        if ((rc = sj_launch(c, s, 14, [&] { hipLaunchKernelGGL(k_sj_motif, dim3((n + SJ_THREADS - 1) / SJ_THREADS), dim3(SJ_THREADS), 0, c->stream, (const int32_t *)t.tid, (const int32_t *)t.don,
+                                                             (const int32_t *)t.acc, n, g, s.strand[0].p, s.motif[0].p, s.word.p + 1); }))) return rc;
         HIP_TRY(hipMemcpyAsync(&bad, s.word.p + 1, 4, hipMemcpyDeviceToHost, c->stream));
         HIP_TRY(hipStreamSynchronize(c->stream));
         if (bad != 0xffffffffu) {
@@ -2321,29 +2375,141 @@ int l2r_sj_finish(l2r_ctx *c, int64_t *n_rows)
     return 0;
 }
 
+// the calls behind l2r_sj_finish that only a table with the overhang column takes
+static int sj_tab_ready(l2r_ctx *c, const char *who)
+{
+    const SjState &s = c->sj;
+    if (s.open && !s.over) return fail(-1, "[%s] the table was begun with l2r_sj_begin: l2r_sj_begin_tab makes the table this call works on", who);
+    if (!s.finished) return fail(-1, "[%s] l2r_sj_finish comes first", who);
+    return 0;
+}
+
+int l2r_sj_annotate(l2r_ctx *c, const l2r_annotation *a)
+{
+    if (!c || !a) return fail(-1, "[l2r_sj_annotate] null argument");
+    int rc;
+    if ((rc = sj_tab_ready(c, "l2r_sj_annotate"))) return rc;
+    if (a->n_tx < 0 || a->n_exon < 0 || a->n_exon >= ((int64_t)1 << 31) || a->n_tx >= ((int64_t)1 << 31)) return fail(-1, "[l2r_sj_annotate] fewer than 2^31 transcripts and exons");
+    if (a->n_tx > 0 && (!a->tx_tid || !a->tx_ex_off)) return fail(-1, "[l2r_sj_annotate] null column");
+    if (a->n_exon > 0 && (a->n_tx == 0 || !a->ex_start || !a->ex_end)) return fail(-1, "[l2r_sj_annotate] null column");
+    if (a->n_tx > 0) {
+        if (a->tx_ex_off[0] != 0 || a->tx_ex_off[a->n_tx] != a->n_exon) return fail(-1, "[l2r_sj_annotate] tx_ex_off does not span the exon array");
+        for (int64_t t = 0; t < a->n_tx; ++t) if (a->tx_ex_off[t + 1] < a->tx_ex_off[t]) return fail(-1, "[l2r_sj_annotate] tx_ex_off descends at transcript %lld", (long long)t);
+    }
+    HIP_TRY(hipSetDevice(c->device));
+    SjState &s = c->sj;
+    SjIntrons &in = c->sj_intr;
+    SjState &is = in.st;
+    if ((rc = sj_state_begin(c, is, false))) return rc;
+    is.timing = s.timing;
+    uint32_t n_in = 0;
+    if (a->n_exon > 0) {
+        const size_t T = (size_t)a->n_tx, E = (size_t)a->n_exon;
+        if ((rc = to_dev(c, in.tx_tid, a->tx_tid, T)) || (rc = to_dev(c, in.tx_ex_off, a->tx_ex_off, T + 1)) || (rc = to_dev(c, in.ex_start, a->ex_start, E)) ||
+            (rc = to_dev(c, in.ex_end, a->ex_end, E))) return rc;
+        if ((rc = sj_rows_reserve(c, is, is.rows[0], E, 0))) return rc;
+        HIP_TRY(hipMemsetAsync(is.word.p + 2, 0, 4, c->stream));
+        const SjAnno an{a->n_tx, a->n_exon, in.tx_tid.p, in.tx_ex_off.p, in.ex_start.p, in.ex_end.p};
+        if ((rc = sj_launch(c, s, SJS_K_INTRONS, [&] { hipLaunchKernelGGL(k_sj_introns, dim3((unsigned)((E + SJ_THREADS - 1) / SJ_THREADS)), dim3(SJ_THREADS), 0, c->stream, an, is.rows[0].cols(),
+                                                                          is.word.p + 2, (uint32_t)E); }))) return rc;
+        HIP_TRY(hipMemcpyAsync(&n_in, is.word.p + 2, 4, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        if (n_in > E) return fail(-2, "[l2r_sj_annotate] %u introns from %zu exons", n_in, E);
+        is.n_rows = n_in;
+        if ((rc = sj_compact(c, is))) return rc;
+        n_in = (uint32_t)is.n_rows;
+        for (int k = 8; k <= 13; ++k) s.stats[SJS_INTRON_SORT] += is.stats[k];
+    }
+    s.stats[SJS_INTRONS] = n_in;
+    const uint32_t n = (uint32_t)s.n_rows;
+    if (n) {
+        const SjCols t = s.rows[s.cur].cols();
+        if ((rc = sj_launch(c, s, SJS_K_ANNOTATE, [&] { hipLaunchKernelGGL(k_sj_annotate, dim3((n + SJ_THREADS - 1) / SJ_THREADS), dim3(SJ_THREADS), 0, c->stream, (const int32_t *)t.tid,
+                                                                           (const int32_t *)t.don, (const int32_t *)t.acc, n, is.rows[is.cur].cols(), n_in, s.anno[s.bcur].p); }))) return rc;
+        HIP_TRY(hipStreamSynchronize(c->stream));
+    }
+    return 0;
+}
+
+int l2r_sj_filter_rows(l2r_ctx *c, const l2r_sj_filter *f, int64_t *n_rows)
+{
+    if (!c || !f || !n_rows) return fail(-1, "[l2r_sj_filter_rows] null argument");
+    int rc;
+    if ((rc = sj_tab_ready(c, "l2r_sj_filter_rows"))) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    SjState &s = c->sj;
+    const uint32_t n = (uint32_t)s.n_rows;
+    s.stats[SJS_DROPPED] = 0;
+    *n_rows = s.n_rows;
+    if (!n) return 0;
+    SjFilter flt;
+    for (int k = 0; k < 5; ++k) { flt.anchor_min[k] = f->anchor_min[k]; flt.uniq_min[k] = f->uniq_min[k]; flt.all_min[k] = f->all_min[k]; }
+    const unsigned grid = (n + SJ_THREADS - 1) / SJ_THREADS;
+    const int bsrc = s.bcur, bdst = 1 - s.bcur, src = s.cur, dst = 1 - s.cur;
+    if (s.head.ensure((size_t)n + 1) || s.strand[bdst].ensure(n) || s.motif[bdst].ensure(n) || s.anno[bdst].ensure(n)) return -2;
+    if ((rc = sj_rows_reserve(c, s, s.rows[dst], n, 0))) return rc;
+    if ((rc = sj_launch(c, s, SJS_K_KEEP, [&] { hipLaunchKernelGGL(k_sj_keep, dim3(grid), dim3(SJ_THREADS), 0, c->stream, s.rows[src].cols(), (const uint8_t *)s.motif[bsrc].p,
+                                                                   (const uint8_t *)s.anno[bsrc].p, n, flt, s.head.p); }))) return rc;
+    if ((rc = sj_scan(c, s, SJS_K_KEEP_SCAN, s.head.p, (int64_t)n))) return rc;
+    uint32_t kept = 0;
+    HIP_TRY(hipMemcpyAsync(&kept, s.word.p, 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    if (kept > n) return fail(-2, "[l2r_sj_filter_rows] %u of %u rows kept", kept, n);
+    if (kept) {
+        const SjBytes bin{s.strand[bsrc].p, s.motif[bsrc].p, s.anno[bsrc].p}, bout{s.strand[bdst].p, s.motif[bdst].p, s.anno[bdst].p};
+        if ((rc = sj_launch(c, s, SJS_K_TAKE, [&] { hipLaunchKernelGGL(k_sj_take, dim3(grid), dim3(SJ_THREADS), 0, c->stream, s.rows[src].cols(), bin, n, (const uint32_t *)s.head.p,
+                                                                       s.rows[dst].cols(), bout, kept); }))) return rc;
+        HIP_TRY(hipStreamSynchronize(c->stream));
+    }
+    s.cur = dst; s.bcur = bdst; s.n_rows = kept;
+    s.stats[SJS_DROPPED] = (double)(n - kept);
+    *n_rows = kept;
+    return 0;
+}
+
+static int sj_download(l2r_ctx *c, int64_t cap, int64_t *n_out, int32_t *const dst[6], uint8_t *const bytes[3], const char *who)
+{
+    SjState &s = c->sj;
+    if (cap < s.n_rows) return fail(-1, "[%s] room for %lld rows, the table has %lld", who, (long long)cap, (long long)s.n_rows);
+    HIP_TRY(hipSetDevice(c->device));
+    const size_t n = (size_t)s.n_rows;
+    *n_out = s.n_rows;
+    if (!n) return 0;
+    for (int k = 0; k < 6; ++k) if (dst[k]) HIP_TRY(hipMemcpyAsync(dst[k], s.rows[s.cur].col[k].p, n * 4, hipMemcpyDeviceToHost, c->stream));
+    const uint8_t *from[3] = {s.strand[s.bcur].p, s.motif[s.bcur].p, s.anno[s.bcur].p};
+    for (int k = 0; k < 3; ++k) if (bytes[k]) HIP_TRY(hipMemcpyAsync(bytes[k], from[k], n, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return 0;
+}
+
 int l2r_sj_download(l2r_ctx *c, l2r_sj_table *t)
 {
     if (!c || !t) return fail(-1, "[l2r_sj_download] null argument");
     SjState &s = c->sj;
     if (!s.finished) return fail(-1, "[l2r_sj_download] l2r_sj_finish comes first");
-    if (t->cap < s.n_rows) return fail(-1, "[l2r_sj_download] room for %lld rows, the table has %lld", (long long)t->cap, (long long)s.n_rows);
-    HIP_TRY(hipSetDevice(c->device));
-    const size_t n = (size_t)s.n_rows;
-    t->n = s.n_rows;
-    if (!n) return 0;
-    if (!t->tid || !t->don || !t->acc || !t->uniq_c || !t->multi_c || !t->strand || !t->motif) return fail(-1, "[l2r_sj_download] null column");
-    int32_t *dst[5] = {t->tid, t->don, t->acc, t->uniq_c, t->multi_c};
-    for (int k = 0; k < 5; ++k) HIP_TRY(hipMemcpyAsync(dst[k], s.rows[s.cur].col[k].p, n * 4, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipMemcpyAsync(t->strand, s.strand.p, n, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipMemcpyAsync(t->motif, s.motif.p, n, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    return 0;
+    if (t->cap >= s.n_rows && s.n_rows && (!t->tid || !t->don || !t->acc || !t->uniq_c || !t->multi_c || !t->strand || !t->motif)) return fail(-1, "[l2r_sj_download] null column");
+    int32_t *const dst[6] = {t->tid, t->don, t->acc, t->uniq_c, t->multi_c, nullptr};
+    uint8_t *const bytes[3] = {t->strand, t->motif, nullptr};
+    return sj_download(c, t->cap, &t->n, dst, bytes, "l2r_sj_download");
+}
+
+int l2r_sj_download_tab(l2r_ctx *c, l2r_sj_tab *t)
+{
+    if (!c || !t) return fail(-1, "[l2r_sj_download_tab] null argument");
+    int rc;
+    if ((rc = sj_tab_ready(c, "l2r_sj_download_tab"))) return rc;
+    SjState &s = c->sj;
+    if (t->cap >= s.n_rows && s.n_rows && (!t->tid || !t->don || !t->acc || !t->uniq_c || !t->multi_c || !t->strand || !t->motif || !t->anno || !t->max_over))
+        return fail(-1, "[l2r_sj_download_tab] null column");
+    int32_t *const dst[6] = {t->tid, t->don, t->acc, t->uniq_c, t->multi_c, t->max_over};
+    uint8_t *const bytes[3] = {t->strand, t->motif, t->anno};
+    return sj_download(c, t->cap, &t->n, dst, bytes, "l2r_sj_download_tab");
 }
 
 int l2r_sj_stats(l2r_ctx *c, double *out, int n)
 {
     if (!c || !out || n < 0) return fail(-1, "[l2r_sj_stats] bad argument");
-    for (int k = 0; k < n; ++k) out[k] = k < 15 ? c->sj.stats[k] : 0.0;
+    for (int k = 0; k < n; ++k) out[k] = k < SJS_N ? c->sj.stats[k] : 0.0;
     return 0;
 }
 

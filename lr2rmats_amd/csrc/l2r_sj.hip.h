@@ -15,6 +15,14 @@
 //                            adds it with one integer atomic, so a run may cross waves and workgroups and be of any length
 //   k_sj_motif               per reduced row: four bases -> motif and strand; the first row on a sequence the genome lacks
 //
+// `sjtab` adds a sixth column, the overhang (the shorter of the two aligned blocks beside the junction), reduced by MAXIMUM: k_sj_fill,
+// k_sj_scatter and k_sj_reduce have an OVER instance each that carries it (24 bytes per row and pass); the plain instances are the
+// code above, unchanged.  Behind the reduction:
+//   k_sj_introns             per annotation exon that is not the last of its transcript: the intron behind it as a row (sorted and made
+//                            unique by the same passes, in a state of their own)
+//   k_sj_annotate            per table row: binary search in the sorted intron keys -> anno 0 / 1
+//   k_sj_keep / k_sj_take    the filter by category (annotated, or by motif) -> k_scan_u32 -> the nine columns of the kept rows, in order
+//
 // LSD radix with 8-bit digits over the 12-byte key (tid, don, acc), least significant byte of acc first; signed order (the top byte of
 // every column is compared with its sign bit flipped).  HBM-bound integer work: a pass reads and writes 20 bytes per row.  No kernel
 // waits for another workgroup.
@@ -30,7 +38,7 @@ constexpr int SJ_ROUNDS = SJ_SORT_TILE / SJ_THREADS;
 constexpr int SJ_KEY_BYTES = 12;
 static_assert(SJ_SORT_TILE % SJ_THREADS == 0, "a tile is a whole number of rounds");
 
-struct SjCols { int32_t *tid, *don, *acc, *uq, *mc; };
+struct SjCols { int32_t *tid, *don, *acc, *uq, *mc, *ov; };      // ov: only the OVER instances touch it (null in a plain table)
 struct SjPrm { int32_t min_intron, pair_only; };
 struct SjRecs { int64_t n; const uint16_t *flag; const int32_t *tid, *pos; const uint8_t *uniq; const int64_t *cig_off; const uint32_t *cig; };
 
@@ -61,7 +69,31 @@ void k_sj_count(SjRecs r, SjPrm p, uint32_t *__restrict__ cnt)
     cnt[i] = k;
 }
 
-// at[]: the scanned counts (n + 1 words); rows go to out[base + at[i] ...), never beyond `cap`
+// The overhang rule of `sjtab`: the junction operations cut the CIGAR into blocks, a block's length is the sum of its M = X lengths (I D
+// S H P B and an N below min_intron add nothing and cut nothing), and a record's overhang at a junction is the shorter of the blocks on its
+// two sides.  The right block is complete only at the next junction or at the end of the CIGAR: done(k, overhang) follows emit(k, ...)
+// late.  An N that is the first or the last operation has an empty block beside it: overhang 0.
+template <typename Emit, typename Done>
+__device__ __forceinline__ uint32_t sj_walk_over(const uint32_t *__restrict__ cig, int64_t c0, int64_t c1, int32_t pos, int32_t min_intron, Emit emit, Done done)
+{
+    int32_t end = pos;
+    uint32_t k = 0;
+    int64_t blk = 0, left = 0;
+    for (int64_t j = c0; j < c1; ++j) {
+        const uint32_t w = cig[j], op = w & 0xfu; const int32_t len = (int32_t)(w >> 4);
+        if (op == 3u && len >= min_intron) {
+            if (k) done(k - 1, (int32_t)(left < blk ? left : blk));
+            emit(k, end + 1, end + len); ++k;
+            left = blk; blk = 0;
+        } else if ((0x181u >> op) & 1u) blk = blk + len < 0x7fffffff ? blk + len : 0x7fffffff;
+        if ((0x18du >> op) & 1u) end += len;
+    }
+    if (k) done(k - 1, (int32_t)(left < blk ? left : blk));
+    return k;
+}
+
+// at[]: the scanned counts (n + 1 words); rows go to out[base + at[i] ...), never beyond `cap`.  OVER: the sixth column as well.
+template <bool OVER>
 __global__ __launch_bounds__(SJ_THREADS)
 void k_sj_fill(SjRecs r, SjPrm p, const uint32_t *__restrict__ at, SjCols out, int64_t base, int64_t cap)
 {
@@ -70,10 +102,17 @@ void k_sj_fill(SjRecs r, SjPrm p, const uint32_t *__restrict__ at, SjCols out, i
     const uint32_t a = at[i];
     if (at[i + 1] == a) return;
     const int32_t t = r.tid[i], u = r.uniq[i] ? 1 : 0;
-    sj_walk(r.cig, r.cig_off[i], r.cig_off[i + 1], r.pos[i], p.min_intron, [&](uint32_t k, int32_t don, int32_t acc) {
+    auto row = [&](uint32_t k, int32_t don, int32_t acc) {
         const int64_t o = base + a + k;
         if (o < cap) { out.tid[o] = t; out.don[o] = don; out.acc[o] = acc; out.uq[o] = u; out.mc[o] = 1 - u; }
-    });
+    };
+    if constexpr (OVER)
+        sj_walk_over(r.cig, r.cig_off[i], r.cig_off[i + 1], r.pos[i], p.min_intron, row, [&](uint32_t k, int32_t over) {
+            const int64_t o = base + a + k;
+            if (o < cap) out.ov[o] = over;
+        });
+    else
+        sj_walk(r.cig, r.cig_off[i], r.cig_off[i + 1], r.pos[i], p.min_intron, row);
 }
 
 // byte b (0 = least significant of acc ... 11 = most significant of tid) of a key, in unsigned order
@@ -121,7 +160,8 @@ void k_sj_digit_hist(SjCols in, uint32_t n, int b, uint32_t n_tiles, uint32_t *_
     tile_hist[threadIdx.x * n_tiles + blockIdx.x] = s_h[threadIdx.x];
 }
 
-// first[]: tile_hist after its exclusive scan: the first slot of the tile's rows of every digit
+// first[]: tile_hist after its exclusive scan: the first slot of the tile's rows of every digit.  OVER: the sixth column moves too.
+template <bool OVER>
 __global__ __launch_bounds__(SJ_THREADS)
 void k_sj_scatter(SjCols in, SjCols out, uint32_t n, int b, uint32_t n_tiles, const uint32_t *__restrict__ first)
 {
@@ -138,8 +178,8 @@ void k_sj_scatter(SjCols in, SjCols out, uint32_t n, int b, uint32_t n_tiles, co
         if (r0 >= n) break;                                            // (uniform)
         const uint32_t i = r0 + threadIdx.x;
         const bool active = i < n;
-        int32_t t = 0, d = 0, a = 0, u = 0, m = 0;
-        if (active) { t = in.tid[i]; d = in.don[i]; a = in.acc[i]; u = in.uq[i]; m = in.mc[i]; }
+        int32_t t = 0, d = 0, a = 0, u = 0, m = 0, v = 0;
+        if (active) { t = in.tid[i]; d = in.don[i]; a = in.acc[i]; u = in.uq[i]; m = in.mc[i]; if constexpr (OVER) v = in.ov[i]; }
         const uint32_t dg = sj_digit(t, d, a, b);
         // the lanes of this wave that hold the same digit
         unsigned long long same = __ballot(active);
@@ -155,7 +195,7 @@ void k_sj_scatter(SjCols in, SjCols out, uint32_t n, int b, uint32_t n_tiles, co
         if (active) {
             uint32_t o = s_base[dg] + rank;
             for (int k = 0; k < w; ++k) o += s_wcnt[k][dg];
-            if (o < n) { out.tid[o] = t; out.don[o] = d; out.acc[o] = a; out.uq[o] = u; out.mc[o] = m; }
+            if (o < n) { out.tid[o] = t; out.don[o] = d; out.acc[o] = a; out.uq[o] = u; out.mc[o] = m; if constexpr (OVER) out.ov[o] = v; }
         }
         __syncthreads();
         {
@@ -179,28 +219,37 @@ void k_sj_heads(SjCols in, uint32_t n, uint32_t *__restrict__ head)
 
 // before[]: head[] after its exclusive scan (before[n] = runs).  Row i belongs to run before[i + 1] - 1.  out.uq / out.mc are cleared by
 // the caller; a wave adds up its rows of a run (segmented inclusive scan by shuffles) and the last lane of every such piece adds it.
+// OVER: out.ov is cleared to 0 too (an overhang is never negative); the same scan takes the maximum of the sixth column and the piece's
+// last lane hands it over with one atomicMax.
+template <bool OVER>
 __global__ __launch_bounds__(SJ_THREADS)
 void k_sj_reduce(SjCols in, uint32_t n, const uint32_t *__restrict__ before, SjCols out, uint32_t n_runs)
 {
     const uint32_t i = blockIdx.x * SJ_THREADS + threadIdx.x;
     const int lane = threadIdx.x & 63;
     const bool active = i < n;
-    uint32_t run = 0xffffffffu; int32_t u = 0, m = 0;
+    uint32_t run = 0xffffffffu; int32_t u = 0, m = 0, v = 0;
     if (active) {
         run = before[i + 1] - 1u;
-        u = in.uq[i]; m = in.mc[i];
+        u = in.uq[i]; m = in.mc[i]; if constexpr (OVER) v = in.ov[i];
         if (before[i] != before[i + 1] && run < n_runs) { out.tid[run] = in.tid[i]; out.don[run] = in.don[i]; out.acc[run] = in.acc[i]; }
     }
 #pragma unroll
     for (int s = 1; s < 64; s <<= 1) {
         const uint32_t pr = (uint32_t)__shfl_up((int)run, s, 64);
         const int32_t pu = __shfl_up(u, s, 64), pm = __shfl_up(m, s, 64);
-        if (lane >= s && pr == run) { u += pu; m += pm; }
+        if constexpr (OVER) {
+            const int32_t pv = __shfl_up(v, s, 64);
+            if (lane >= s && pr == run) { u += pu; m += pm; v = pv > v ? pv : v; }
+        } else {
+            if (lane >= s && pr == run) { u += pu; m += pm; }
+        }
     }
     const uint32_t next = (uint32_t)__shfl_down((int)run, 1, 64);
     if (active && (lane == 63 || next != run) && run < n_runs) {
         if (u) atomicAdd(&out.uq[run], u);
         if (m) atomicAdd(&out.mc[run], m);
+        if constexpr (OVER) { if (v > 0) atomicMax(&out.ov[run], v); }
     }
 }
 
@@ -245,6 +294,75 @@ void k_sj_motif(const int32_t *__restrict__ tid, const int32_t *__restrict__ don
         }
     }
     strand[i] = st; motif[i] = mo;
+}
+
+// ---- `sjtab`: annotated flag, filter
+
+struct SjAnno { int64_t n_tx, n_exon; const int32_t *tx_tid; const int64_t *tx_ex_off; const int32_t *ex_start, *ex_end; };
+
+// One thread per exon.  Its transcript: the last t with tx_ex_off[t] <= e (transcripts without exons share an offset with their
+// successor and are stepped over by the search).  Not the last exon of a transcript with tid >= 0 -> the interval up to the next exon, where
+// it is not empty, as a row {tid, first base, last base, 1, 0} at a slot taken from *count (any order: the rows are sorted next).
+__global__ __launch_bounds__(SJ_THREADS)
+void k_sj_introns(SjAnno a, SjCols out, uint32_t *__restrict__ count, uint32_t cap)
+{
+    const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= a.n_exon) return;
+    int64_t lo = 0, hi = a.n_tx;                                  // tx_ex_off[lo] <= e < tx_ex_off[hi]
+    while (hi - lo > 1) { const int64_t mid = lo + (hi - lo) / 2; if (a.tx_ex_off[mid] <= e) lo = mid; else hi = mid; }
+    if (e + 1 >= a.tx_ex_off[lo + 1]) return;
+    const int32_t t = a.tx_tid[lo];
+    if (t < 0) return;
+    const int64_t first = (int64_t)a.ex_end[e] + 1, last = (int64_t)a.ex_start[e + 1] - 1;
+    if (last < first) return;
+    const uint32_t o = atomicAdd(count, 1u);
+    if (o < cap) { out.tid[o] = t; out.don[o] = (int32_t)first; out.acc[o] = (int32_t)last; out.uq[o] = 1; out.mc[o] = 0; }
+}
+
+// in: the sorted, distinct intron keys
+__global__ __launch_bounds__(SJ_THREADS)
+void k_sj_annotate(const int32_t *__restrict__ tid, const int32_t *__restrict__ don, const int32_t *__restrict__ acc, uint32_t n,
+                   SjCols in, uint32_t n_in, uint8_t *__restrict__ anno)
+{
+    const uint32_t i = blockIdx.x * SJ_THREADS + threadIdx.x;
+    if (i >= n) return;
+    const int32_t t = tid[i], d = don[i], a = acc[i];
+    uint32_t lo = 0, hi = n_in;                                   // the first key that is not below (t, d, a)
+    while (lo < hi) {
+        const uint32_t mid = lo + (hi - lo) / 2;
+        const int32_t mt = in.tid[mid], md = in.don[mid], ma = in.acc[mid];
+        const bool below = mt != t ? mt < t : md != d ? md < d : ma < a;
+        if (below) lo = mid + 1; else hi = mid;
+    }
+    anno[i] = (lo < n_in && in.tid[lo] == t && in.don[lo] == d && in.acc[lo] == a) ? 1 : 0;
+}
+
+struct SjFilter { int32_t anchor_min[5], uniq_min[5], all_min[5]; };
+
+// category: annotated 0; else by motif: 0 -> 1, 1 2 -> 2, 3 4 -> 3, 5 6 -> 4.  keep has n + 1 words for the scan.
+__global__ __launch_bounds__(SJ_THREADS)
+void k_sj_keep(SjCols in, const uint8_t *__restrict__ motif, const uint8_t *__restrict__ anno, uint32_t n, SjFilter f, uint32_t *__restrict__ keep)
+{
+    const uint32_t i = blockIdx.x * SJ_THREADS + threadIdx.x;
+    if (i >= n) return;
+    const uint32_t mo = motif[i];
+    const int c = anno[i] ? 0 : mo == 0u ? 1 : mo > 6u ? 1 : (int)((mo + 1u) / 2u) + 1;
+    const int64_t u = in.uq[i], all = (int64_t)in.uq[i] + in.mc[i];
+    keep[i] = (in.ov[i] >= f.anchor_min[c] && (u >= f.uniq_min[c] || all >= f.all_min[c])) ? 1u : 0u;
+}
+
+struct SjBytes { uint8_t *strand, *motif, *anno; };
+
+// at[]: keep[] after its exclusive scan
+__global__ __launch_bounds__(SJ_THREADS)
+void k_sj_take(SjCols in, SjBytes bin, uint32_t n, const uint32_t *__restrict__ at, SjCols out, SjBytes bout, uint32_t n_out)
+{
+    const uint32_t i = blockIdx.x * SJ_THREADS + threadIdx.x;
+    if (i >= n) return;
+    const uint32_t o = at[i];
+    if (at[i + 1] == o || o >= n_out) return;
+    out.tid[o] = in.tid[i]; out.don[o] = in.don[i]; out.acc[o] = in.acc[i]; out.uq[o] = in.uq[i]; out.mc[o] = in.mc[i]; out.ov[o] = in.ov[i];
+    bout.strand[o] = bin.strand[i]; bout.motif[o] = bin.motif[i]; bout.anno[o] = bin.anno[i];
 }
 
 }  // namespace l2r

@@ -1475,6 +1475,7 @@ int h_main(int argc, char **argv)
     if (strcmp(argv[0], "unique-gtf") == 0) return h_cmd_unique_gtf(argc, argv);
     if (strcmp(argv[0], "filter") == 0) return h_cmd_filter(argc, argv);
     if (strcmp(argv[0], "bam2sj") == 0) return h_cmd_bam2sj(argc, argv);
+    if (strcmp(argv[0], "sjtab") == 0) return h_cmd_sjtab(argc, argv);
     if (strcmp(argv[0], "fusion") == 0) return h_cmd_fusion(argc, argv);
     /* (diagnostics, no GPU: every record of a SAM / BAM file written out as BAM -- reader, encoder and BGZF writer of `filter`) */
     if (strcmp(argv[0], "records2bam") == 0 && argc == 3) return h_records_to_bam(argv[1], argv[2]) ? 1 : 0;

@@ -112,6 +112,9 @@ void h_sj_batch_free(h_sj_batch *b);
 int64_t h_sj_literal(int64_t n, const int32_t *tid, const int32_t *don, const int32_t *acc, const int32_t *uniq_c, const int32_t *multi_c,
                      int32_t *o_tid, int32_t *o_don, int32_t *o_acc, int32_t *o_uniq, int32_t *o_multi);
 
+/* `sjtab`: a -a / -U / -A list -- exactly five integers with commas between them; 1 and out[] on success, 0 otherwise */
+int h_sj_five_ints(const char *arg, int32_t out[5]);
+
 /* ---- transcripts from a GTF (annotation, or read-like input of `-m g`) */
 typedef struct {
     int64_t n_tx, cap_tx, n_ex, cap_ex;
@@ -186,6 +189,7 @@ int h_cmd_bam2gtf(int argc, char **argv);
 int h_cmd_unique_gtf(int argc, char **argv);
 int h_cmd_filter(int argc, char **argv);
 int h_cmd_bam2sj(int argc, char **argv);
+int h_cmd_sjtab(int argc, char **argv);
 int h_cmd_fusion(int argc, char **argv);
 int h_main(int argc, char **argv);
 

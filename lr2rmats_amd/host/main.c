@@ -11,7 +11,8 @@ int main(int argc, char **argv)
         fprintf(stderr, "         update-gtf   generate new GTF file based on BAM/SAM and existing GTF file\n");
         fprintf(stderr, "         unique-gtf   generate GTF file that only contain unique transcript based on BAM/SAM or GTF file\n");
         fprintf(stderr, "         bam2gtf      generate transcript and exon information based on BAM/SAM file\n");
-        fprintf(stderr, "         bam2sj       generate splice-junction information based on BAM/SAM file\n\n");
+        fprintf(stderr, "         bam2sj       generate splice-junction information based on BAM/SAM file\n");
+        fprintf(stderr, "         sjtab        generate the filtered splice-junction table that update-gtf -j reads\n\n");
         return 1;
     }
     return h_main(argc - 1, argv + 1);

@@ -6,6 +6,9 @@
  *   table     the engine: l2r_sj_begin / _add per batch / _finish / _download (include/lr2rmats_hip.h)
  *   output    the four header lines and one line per junction (print_sj :974-985)
  *
+ * `lr2rmats sjtab` (the end of this file) is the same source and engine with the table `update-gtf -j` reads: nine columns, no header,
+ * annotated flag from a GTF, maximum overhang, and the filter the usage text of bam2sj only advertises.
+ *
  * The reference keeps ONE list and, per junction, searches it backwards for its place (sj_sch_group :339-351).  Where the tids of
  * the records never decrease that list is the table sorted by (tid, don, acc) -- what the engine makes.  Where a tid decreases, the
  * search stops early inside the block of a larger tid and the list is no sort at all: such input takes h_sj_literal(), the same
@@ -564,4 +567,147 @@ int h_cmd_bam2sj(int argc, char **argv)
     h_chroms_free(&chr);
     if (have_genome) h_fasta_free(&g);
     return rc;
+}
+
+/* ------------------------------------------------------------------ `sjtab`: the table update-gtf -j reads */
+
+static int sjtab_usage(void)
+{
+    fprintf(stderr, "\n");
+    fprintf(stderr, "Usage:   %s sjtab [option] <in.bam|sam> > SJ.out.tab\n\n", "lr2rmats");
+    fprintf(stderr, "Output:  chr, first and last intron base, strand (0 undefined, 1 +, 2 -), motif (0 non-canonical, 1 GT/AG,\n");
+    fprintf(stderr, "         2 CT/AC, 3 GC/AG, 4 CT/GC, 5 AT/AC, 6 GT/AT), annotated, unique count, multi count, maximum overhang;\n");
+    fprintf(stderr, "         no header, sorted by chr (header order), first base, last base: what `update-gtf -j` reads\n\n");
+    fprintf(stderr, "Input Options:\n\n");
+    fprintf(stderr, "         -G --gtf-anno    [STR]    GTF annotation file, indicating known splice-junctions. [None]\n");
+    fprintf(stderr, "         -g --genome-file [STR]    genome.fa. Use genome sequence to classify intron-motif. \n");
+    fprintf(stderr, "                                   If no genome file is give, intron-motif will be set as 0\n");
+    fprintf(stderr, "                                   (non-canonical) [None]\n");
+    fprintf(stderr, "\nFilter Options:\n\n");
+    fprintf(stderr, "         -p --prop-pair            only use reads mapped in proper pair. [False]\n");
+    fprintf(stderr, "         -a --anchor-len  [INT,INT,INT,INT,INT]\n");
+    fprintf(stderr, "                                   minimum anchor length (maximum overhang) of a junction, [annotated,\n");
+    fprintf(stderr, "                                   non-canonical, GT/AG, GC/AG, AT/AC]. [%d,%d,%d,%d,%d]\n", 1, 30, 12, 12, 12);
+    fprintf(stderr, "         -U --uniq-map    [INT,INT,INT,INT,INT]\n");
+    fprintf(stderr, "                                   minimum uniq-map read count of a junction. [%d,%d,%d,%d,%d]\n", 0, 3, 1, 1, 1);
+    fprintf(stderr, "         -A --all-map     [INT,INT,INT,INT,INT]\n");
+    fprintf(stderr, "                                   minimum total uniq-map and multi-map read count of a junction; a junction\n");
+    fprintf(stderr, "                                   that meets -U or -A is kept. [%d,%d,%d,%d,%d]\n", 0, 3, 1, 1, 1);
+    fprintf(stderr, "         -i --intron-len  [INT]    minimum intron length for junction read. [%d]\n", SJ_INTRON_MIN_LEN);
+    fprintf(stderr, "\nOutput Options:\n\n");
+    fprintf(stderr, "         -o --output      [STR]    junction table. [stdout]\n");
+    fprintf(stderr, "\n");
+    return 1;
+}
+
+/* -a / -U / -A of sjtab: exactly five decimal integers with a comma between them and nothing else; 1 and out[] on success, else 0 */
+int h_sj_five_ints(const char *arg, int32_t out[5])
+{
+    if (!arg) return 0;
+    const char *p = arg;
+    for (int k = 0; k < 5; ++k) {
+        if (k && *p++ != ',') return 0;
+        const char *d = p;
+        if (*d == '-' || *d == '+') ++d;
+        if (*d < '0' || *d > '9') return 0;
+        char *e;
+        const long v = strtol(p, &e, 10);
+        if (v < INT32_MIN || v > INT32_MAX) return 0;
+        out[k] = (int32_t)v;
+        p = e;
+    }
+    return *p == 0;
+}
+
+int h_cmd_sjtab(int argc, char **argv)
+{
+    static const struct option lopt[] = {
+        {"prop-pair", 0, NULL, 'p'}, {"gtf-anno", 1, NULL, 'G'}, {"genome-file", 1, NULL, 'g'}, {"anchor-len", 1, NULL, 'a'},
+        {"uniq-map", 1, NULL, 'U'}, {"all-map", 1, NULL, 'A'}, {"intron-len", 1, NULL, 'i'}, {"output", 1, NULL, 'o'}, {0, 0, 0, 0}};
+    const char *ref_fn = NULL, *gtf_fn = NULL, *out_fn = NULL;
+    l2r_sj_filter flt = {{1, 30, 12, 12, 12}, {0, 3, 1, 1, 1}, {0, 3, 1, 1, 1}};
+    int min_intron = SJ_INTRON_MIN_LEN, pair_only = 0, c;
+    optind = 1;
+    while ((c = getopt_long(argc, argv, "G:g:pa:i:A:U:o:", lopt, NULL)) >= 0) {
+        switch (c) {
+        case 'g': ref_fn = optarg; break;
+        case 'G': gtf_fn = optarg; break;
+        case 'p': pair_only = 1; break;
+        case 'a': if (!h_sj_five_ints(optarg, flt.anchor_min)) return sjtab_usage(); break;
+        case 'U': if (!h_sj_five_ints(optarg, flt.uniq_min)) return sjtab_usage(); break;
+        case 'A': if (!h_sj_five_ints(optarg, flt.all_min)) return sjtab_usage(); break;
+        case 'i': min_intron = atoi(optarg); break;
+        case 'o': out_fn = optarg; break;
+        default: fprintf(stderr, "Error: unknown option: %s.\n", optarg); return sjtab_usage();
+        }
+    }
+    if (argc - optind != 1) return sjtab_usage();
+    const char *in_fn = argv[optind];
+    h_fasta g; memset(&g, 0, sizeof g);
+    int have_genome = ref_fn && ref_fn[0];
+    if (have_genome) {
+        FILE *t = fopen(ref_fn, "rb");
+        if (!t) h_fatal("sjtab", "Can not open genome file. %s\n", ref_fn);
+        fclose(t);
+        h_read_fasta(ref_fn, &g, "sjtab");
+        if (g.n_seq == 0) { h_fasta_free(&g); have_genome = 0; }
+    }
+    if (gtf_fn) {
+        FILE *t = fopen(gtf_fn, "rb");
+        if (!t) h_fatal("sjtab", "Can not open annotation file. %s\n", gtf_fn);
+        fclose(t);
+    }
+    const char *e = getenv("L2R_SJ_BATCH");
+    const int64_t batch_records = e && atoll(e) > 0 ? atoll(e) : SJ_DEFAULT_BATCH;
+
+    h_chroms chr; memset(&chr, 0, sizeof chr);
+    h_sj_source *src = h_sj_source_open(in_fn, &chr, "sjtab");
+    h_gtf anno; memset(&anno, 0, sizeof anno);
+    if (gtf_fn) h_read_gtf(gtf_fn, &chr, &anno, 0);           /* tids against the header's names; -1 for any other sequence */
+    FILE *out = stdout;
+    if (out_fn && !(out = fopen(out_fn, "w"))) h_fatal("sjtab", "Can not open \"%s\" for writing\n", out_fn);
+    l2r_ctx *ctx = l2r_create(0);
+    if (!ctx) h_fatal("sjtab", "%s", l2r_last_error());
+    const l2r_sj_params prm = {min_intron, pair_only};
+    const l2r_sj_genome gen = {g.n_seq, g.seq_off, g.bases};
+    if (l2r_sj_begin_tab(ctx, &prm, have_genome ? &gen : NULL)) h_fatal("sjtab", "%s", l2r_last_error());
+    h_sj_batch b; memset(&b, 0, sizeof b);
+    int64_t no_nh = 0;
+    while (h_sj_source_next(src, &b, batch_records) > 0) {
+        for (int64_t i = 0; i < b.n; ++i) if (!(b.flag[i] & 4u) && (!pair_only || (b.flag[i] & 2u)) && !b.nh_seen[i]) ++no_nh;
+        const l2r_sj_records recs = {b.n, b.n_cig, b.flag, b.tid, b.pos, b.uniq, b.cig_off, b.cig};
+        if (l2r_sj_add(ctx, &recs)) h_fatal("sjtab", "%s", l2r_last_error());
+    }
+    h_sj_source_close(src); h_sj_batch_free(&b);
+    int64_t n = 0;
+    const int frc = l2r_sj_finish(ctx, &n);
+    if (frc == L2R_SJ_E_UNKNOWN_TID) { fprintf(stderr, "%s\n", l2r_last_error()); l2r_destroy(ctx); exit(EXIT_FAILURE); }
+    if (frc) h_fatal("sjtab", "%s", l2r_last_error());
+    if (gtf_fn) {
+        l2r_annotation a; memset(&a, 0, sizeof a);
+        a.n_tx = anno.n_tx; a.n_exon = anno.n_ex; a.tx_tid = anno.tid; a.tx_start = anno.start; a.tx_end = anno.end; a.tx_rev = anno.rev;
+        a.tx_ex_off = anno.ex_off; a.ex_start = anno.ex_start; a.ex_end = anno.ex_end;
+        if (l2r_sj_annotate(ctx, &a)) h_fatal("sjtab", "%s", l2r_last_error());
+    }
+    const int64_t n_all = n;
+    if (l2r_sj_filter_rows(ctx, &flt, &n)) h_fatal("sjtab", "%s", l2r_last_error());
+    int32_t *col[6]; uint8_t *byt[3];
+    for (int q = 0; q < 6; ++q) col[q] = (int32_t *)h_malloc((size_t)(n + 1) * 4);
+    for (int q = 0; q < 3; ++q) byt[q] = (uint8_t *)h_malloc((size_t)n + 1);
+    l2r_sj_tab t = {n, 0, col[0], col[1], col[2], col[3], col[4], byt[0], byt[1], byt[2], col[5]};
+    if (l2r_sj_download_tab(ctx, &t)) h_fatal("sjtab", "%s", l2r_last_error());
+    l2r_destroy(ctx);
+    for (int64_t i = 0; i < t.n; ++i) {
+        if (col[0][i] < 0 || col[0][i] >= chr.n_hdr) h_fatal("sjtab", "junction on reference %d, the header has %d", col[0][i], chr.n_hdr);
+        fprintf(out, "%s\t%d\t%d\t%d\t%d\t%d\t%d\t%d\t%d\n", chr.name[col[0][i]], col[1][i], col[2][i], byt[0][i], byt[1][i], byt[2][i], col[3][i], col[4][i], col[5][i]);
+    }
+    if (out == stdout) fflush(stdout); else fclose(out);
+    fprintf(stderr, "[sjtab] %lld junctions, %lld left by the filter; %lld records without an NH tag counted as multi-mapped\n", (long long)n_all, (long long)t.n,
+            (long long)no_nh);
+    for (int q = 0; q < 6; ++q) free(col[q]);
+    for (int q = 0; q < 3; ++q) free(byt[q]);
+    if (gtf_fn) h_gtf_free(&anno);
+    h_chroms_free(&chr);
+    if (have_genome) h_fasta_free(&g);
+    return 0;
 }

@@ -77,6 +77,8 @@ def load_library():
         lib.h_sj_source_close.restype = None
         lib.h_sj_batch_free.argtypes = [C.c_void_p]
         lib.h_sj_batch_free.restype = None
+        lib.h_sj_five_ints.argtypes = [C.c_char_p, C.c_void_p]
+        lib.h_sj_five_ints.restype = C.c_int
         lib.h_chroms_free.argtypes = [C.c_void_p]
         lib.h_chroms_free.restype = None
         lib.h_read_records.argtypes = [C.c_char_p, C.c_void_p, C.c_void_p, C.c_char_p]
@@ -132,6 +134,12 @@ def read_fasta(path: str):
     bases = _arr(f.bases, int(off[n]), np.uint8).copy()
     lib.h_fasta_free(C.byref(f))
     return names, off, bases
+
+
+def sj_five_ints(text: str):
+    """A -a / -U / -A list of ``sjtab`` as the command parses it (h_sj_five_ints): five ints, or None where the usage is printed."""
+    out = (C.c_int32 * 5)()
+    return [int(v) for v in out] if load_library().h_sj_five_ints(text.encode(), out) else None
 
 
 def sj_literal(tid, don, acc, uniq_c, multi_c):
@@ -332,7 +340,7 @@ def records_to_bam(in_path: str, out_path: str) -> int:
 
 
 def run_cli(args, stdout_path=None, cwd=None, env=None) -> subprocess.CompletedProcess:
-    """Run the C binary ``lr2rmats <args>`` (needs a GPU for update-gtf / bam2gtf / unique-gtf -m b / filter / bam2sj / fusion).
+    """Run the C binary ``lr2rmats <args>`` (needs a GPU for update-gtf / bam2gtf / unique-gtf -m b / filter / bam2sj / sjtab / fusion).
     ``env``: extra environment variables (L2R_CHUNK_READS, L2R_ROUTE, L2R_THREADS ...)."""
     full_env = None
     if env:

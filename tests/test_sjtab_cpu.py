@@ -1,0 +1,141 @@
+"""CPU: the restatement of `lr2rmats sjtab` (tests/sjtab_restatement.py) against hand-worked answers, its numpy form against its literal
+form, and the option-list parser of the command through the host library."""
+import numpy as np
+import pytest
+
+from tests import sj_cases as sc
+from tests import sj_restatement as sr
+from tests import sjtab_restatement as st
+
+
+# ---------------------------------------------------------------------------------------------------- overhang
+
+HAND_CIGARS = st.HAND_CIGARS
+
+
+@pytest.mark.parametrize("name,cigar,min_intron,want", HAND_CIGARS, ids=[c[0] for c in HAND_CIGARS])
+def test_hand_cigars(name, cigar, min_intron, want):
+    assert st.cigar_overhangs(sr.parse_cigar(cigar), min_intron) == want
+
+
+def test_left_block_of_the_long_hand_cigar():
+    # the blocks themselves: 21 and 9
+    cig = sr.parse_cigar("3S8M2I4M2D3M2N6M50N9M")
+    assert st.cigar_overhangs(cig + [(50, 3), (100, 0)], 3) == [9, 9] and st.cigar_overhangs([(100, 0), (50, 3)] + cig, 3) == [21, 9]
+
+
+def _rec(pos, cigar, uniq=True, flag=3, tid=0):
+    return dict(flag=flag, tid=tid, pos=pos, cigar=sr.parse_cigar(cigar), uniq=uniq, has_nh=True)
+
+
+def test_row_maximum_and_counts():
+    # one junction (tid 0, 1001..1100) seen by three records with overhangs 4, 31 and 12
+    recs = [_rec(1000 - 4, "4M100N50M"), _rec(1000 - 40, "40M100N31M", uniq=False), _rec(1000 - 12, "12M100N12M")]
+    assert st.table(st.rows_of(recs)) == [(0, 1001, 1100, 2, 1, 31)]
+    # -p: only FLAG & 2; the default keeps every mapped record
+    recs.append(_rec(1000 - 60, "60M100N60M", flag=0))
+    assert st.table(st.rows_of(recs)) == [(0, 1001, 1100, 3, 1, 60)]
+    assert st.table(st.rows_of(recs, pair_only=True)) == [(0, 1001, 1100, 2, 1, 31)]
+    recs.append(_rec(1000 - 90, "90M100N90M", flag=4))
+    assert st.table(st.rows_of(recs)) == [(0, 1001, 1100, 3, 1, 60)]
+
+
+# ---------------------------------------------------------------------------------------------------- category, keep rule
+
+def test_categories():
+    assert [st.category(0, m) for m in range(7)] == [1, 2, 2, 3, 3, 4, 4]
+    assert [st.category(1, m) for m in range(7)] == [0] * 7
+    assert st.category_numpy([0] * 7 + [1] * 7, list(range(7)) * 2).tolist() == [1, 2, 2, 3, 3, 4, 4] + [0] * 7
+
+
+FILT = ((5, 30, 12, 13, 14), (2, 3, 4, 5, 6), (7, 8, 9, 10, 11))
+ROW_OF_CATEGORY = {0: (1, 0), 1: (0, 0), 2: (0, 2), 3: (0, 3), 4: (0, 6)}       # (anno, motif)
+
+
+@pytest.mark.parametrize("c", range(5))
+def test_keep_rule_on_every_threshold(c):
+    an, mo = ROW_OF_CATEGORY[c]
+    a, u, t = FILT[0][c], FILT[1][c], FILT[2][c]
+    assert st.kept(an, mo, u, 0, a, FILT)                    # exactly on the anchor and the unique threshold
+    assert not st.kept(an, mo, u, 0, a - 1, FILT)            # one below the anchor
+    assert not st.kept(an, mo, u - 1, 0, a, FILT)            # one below the unique threshold, the total (u - 1) far below its own
+    assert st.kept(an, mo, 0, t, a, FILT)                    # fails uniq_min, meets all_min exactly: kept
+    assert st.kept(an, mo, u - 1, t - u + 1, a, FILT)
+    assert not st.kept(an, mo, 0, t - 1, a, FILT)            # one below the total
+    rows = [(an, mo, u, 0, a), (an, mo, u, 0, a - 1), (an, mo, u - 1, 0, a), (an, mo, 0, t, a), (an, mo, 0, t - 1, a)]
+    assert st.keep_numpy(*[np.array(x) for x in zip(*rows)], filt=FILT).tolist() == [True, False, False, True, False]
+
+
+def test_defaults():
+    assert st.DEFAULT_FILTER == ((1, 30, 12, 12, 12), (0, 3, 1, 1, 1), (0, 3, 1, 1, 1))
+    assert st.kept(1, 0, 0, 1, 1)                            # annotated, non-canonical, one (multi-mapped) read: kept
+    assert not st.kept(1, 0, 1, 0, 0)                        # ... but never on an overhang of 0
+    assert not st.kept(0, 0, 2, 0, 40) and st.kept(0, 0, 1, 2, 30) and not st.kept(0, 0, 3, 0, 29)
+    assert st.kept(0, 1, 1, 0, 12) and not st.kept(0, 1, 1, 0, 11) and st.kept(0, 5, 0, 1, 12)
+
+
+# ---------------------------------------------------------------------------------------------------- annotation introns
+
+def test_annotation_introns():
+    #            tx0: 3 exons              tx1: abut, overlap     tx2: tid -1        tx3: tx0's first intron again   tx4: one exon
+    ex = [(100, 200), (301, 400), (501, 600), (100, 200), (201, 300), (250, 400), (100, 200), (301, 400), (150, 200), (301, 350), (10, 20)]
+    off = [0, 3, 6, 8, 10, 11]
+    tid = [0, 0, -1, 0, 1]
+    got = st.annotation_introns(tid, off, [e[0] for e in ex], [e[1] for e in ex])
+    assert got == {(0, 201, 300), (0, 401, 500)}
+    tid[2] = 2
+    assert st.annotation_introns(tid, off, [e[0] for e in ex], [e[1] for e in ex]) == {(0, 201, 300), (0, 401, 500), (2, 201, 300)}
+    assert st.annotation_introns([], [0], [], []) == set()
+    assert st.anno_numpy(got, [0, 0, 1], [201, 201, 201], [300, 301, 300]).tolist() == [1, 0, 0]
+
+
+# ---------------------------------------------------------------------------------------------------- the two forms agree; bytes
+
+def test_numpy_form_equals_the_literal_form():
+    text = sc.hand_sam()
+    _, recs = sr.records_from_sam(text)
+    for pair_only in (False, True):
+        for mi in (2, 3, 4):
+            lit = st.table(st.rows_of(recs, mi, pair_only))
+            mapped = [r for r in recs]
+            cig = [(ln << 4) | op for r in mapped for ln, op in r["cigar"]]
+            off = np.concatenate([[0], np.cumsum([len(r["cigar"]) for r in mapped])])
+            rows = st.rows_numpy([r["flag"] for r in mapped], [r["tid"] for r in mapped], [r["pos"] for r in mapped], [r["uniq"] for r in mapped],
+                                 off, np.array(cig, np.int64), mi, pair_only)
+            assert [tuple(int(v) for v in row) for row in zip(*st.table_numpy(*rows))] == lit
+    rec = sc.synth_records(3000, 3)
+    rows = st.rows_numpy(rec["flag"], rec["tid"], rec["pos"], rec["uniq"], rec["cig_off"], rec["cig"])
+    recs = [dict(flag=int(rec["flag"][i]), tid=int(rec["tid"][i]), pos=int(rec["pos"][i]), uniq=bool(rec["uniq"][i]), has_nh=True,
+                 cigar=[(int(w) >> 4, int(w) & 15) for w in rec["cig"][rec["cig_off"][i]:rec["cig_off"][i + 1]]]) for i in range(3000)]
+    lit = st.table(st.rows_of(recs))
+    assert len(lit) > 100 and [tuple(int(v) for v in row) for row in zip(*st.table_numpy(*rows))] == lit
+    assert len({r[5] for r in lit}) > 20
+
+
+def test_expected_bytes_of_the_hand_file():
+    text = sc.hand_sam()
+    keep_all = st.expected_stdout(text, filt=st.KEEP_ALL)
+    lines = keep_all.decode().splitlines()
+    # every mapped record counts (r13 and r14 too): (0, 1011, 1035) appears, which bam2sj never sees
+    assert "chr1\t1011\t1035\t0\t0\t0\t1\t1\t10" in lines and "chr1\t611\t635\t0\t0\t0\t1\t1\t10" in lines
+    assert "chr1\t501\t540\t0\t0\t0\t1\t0\t0" in lines                    # r07: N first
+    assert "chr1\t411\t430\t0\t0\t0\t1\t0\t10" in lines and "chr1\t441\t470\t0\t0\t0\t1\t0\t10" in lines
+    assert "chr2\t61\t1060\t0\t0\t0\t1\t0\t10" in lines and len(lines) == 13
+    assert all(len(l.split("\t")) == 9 for l in lines)
+    assert st.expected_stdout(text) == b""                                # no genome: every row non-canonical, none has 30 bases and 3 reads
+    introns = {(0, 611, 635), (0, 501, 540)}
+    assert st.expected_stdout(text, introns=introns) == b"chr1\t611\t635\t0\t0\t1\t1\t1\t10\n"      # annotated: kept; the overhang-0 row is not
+    assert st.missing_nh(text) == 2 and st.missing_nh(text, pair_only=True) == 1
+
+
+# ---------------------------------------------------------------------------------------------------- -a / -U / -A through the host library
+
+def test_five_ints_of_the_command():
+    from lr2rmats_amd import hostlib
+    if not hasattr(hostlib, "sj_five_ints"):
+        pytest.fail("hostlib.sj_five_ints is missing: the sjtab command is not built")
+    assert hostlib.sj_five_ints("1,30,12,12,12") == [1, 30, 12, 12, 12]
+    assert hostlib.sj_five_ints("0,0,0,0,0") == [0] * 5
+    assert hostlib.sj_five_ints("-1,+2,3,4,2147483647") == [-1, 2, 3, 4, 2147483647]
+    for bad in ("1,2,3", "1,2,3,4", "1,2,3,4,5,6", "1,2,3,4,5,", "1:2:3:4:5", "", "a,b,c,d,e", "1,,2,3,4", "1,2,3,4,x", "1, 2,3,4,5", "1,2,3,4,99999999999"):
+        assert hostlib.sj_five_ints(bad) is None, bad

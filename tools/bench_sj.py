@@ -4,7 +4,11 @@ Not part of the product.   tools/bench_sj.py [records = 50_000_000] [rounds = 5]
 Reports, over `rounds` warm rounds (median and spread): wall time of add + finish with uploads, rows/s; then from ONE more round with
 L2R_SJ_TIMING=1 (every launch bracketed by HIP events and waited for) the device time per kernel, the bytes the algorithm moves
 divided by the kernel time as a fraction of 8 TB/s, and the radix passes that ran; and the wall time of the numpy restatement
-(np.unique + np.bincount, tests/sj_restatement.py) on the same rows on this host -- the only yardstick there is."""
+(np.unique + np.bincount, tests/sj_restatement.py) on the same rows on this host -- the only yardstick there is.
+
+A second leg runs the same records through the table of `lr2rmats sjtab` (l2r_sj_begin_tab + l2r_sj_annotate + l2r_sj_filter_rows, six
+columns per row instead of five) and prints a second JSON line ("leg": "sjtab"): the same figures, the device time of every new kernel,
+and the ratio of its scatter passes to the plain leg's (24 / 20 by the bytes per row).  L2R_BENCH_SJ_LEGS=plain runs the first leg only."""
 import json
 import os
 import sys
@@ -54,13 +58,26 @@ def make(n, seed=1, n_chrom=24, n_intron=12000, span=100_000_000):
     return dict(flag=flag, tid=tid[order], pos=pos[order], uniq=uniq, cig_off=new_off, cig=cig[idx])
 
 
-def run(eng, r):
-    eng.sj_begin()
+def add_all(eng, r):
     for a in range(0, len(r["flag"]), batch):
         b = min(a + batch, len(r["flag"]))
         c0, c1 = r["cig_off"][a], r["cig_off"][b]
         eng.sj_add(r["flag"][a:b], r["tid"][a:b], r["pos"][a:b], r["uniq"][a:b], r["cig_off"][a:b + 1] - c0, r["cig"][c0:c1])
+
+
+def run(eng, r):
+    eng.sj_begin()
+    add_all(eng, r)
     return eng.sj_finish()
+
+
+def run_tab(eng, r, anno):
+    """The `sjtab` leg: pair_only as in the plain leg (the same records make the same rows), annotate, default filter."""
+    eng.sj_begin_tab(pair_only=True)
+    add_all(eng, r)
+    full = eng.sj_finish()
+    eng.sj_annotate(*anno)
+    return full, eng.sj_filter_rows()
 
 
 t0 = time.perf_counter()
@@ -96,5 +113,55 @@ line = dict(records=n, rows=int(rows), table_rows=out_rows, rounds=rounds, sort_
 print("| kernel | ms (one round, every launch waited for) |\n|---|---|")
 for k, v in kern.items():
     print("| %s | %.3f |" % (k, v))
-print(json.dumps(line))
+print(json.dumps(line), flush=True)
 assert ok
+if os.environ.get("L2R_BENCH_SJ_LEGS", "") == "plain":
+    sys.exit(0)
+
+# ---- the sjtab leg: the annotation is every second junction of the table as a two-exon transcript, and as many transcripts beside them
+from tests import sjtab_restatement as st         # noqa: E402
+sel = np.arange(len(tab.tid)) % 2 == 0
+a_tid = np.concatenate([tab.tid[sel], tab.tid[sel]]).astype(np.int32)
+a_don = np.concatenate([tab.don[sel], tab.don[sel] + 7]).astype(np.int64)
+a_acc = np.concatenate([tab.acc[sel], tab.acc[sel] + 7]).astype(np.int64)
+anno = (a_tid, (2 * np.arange(len(a_tid) + 1)).astype(np.int64), np.stack([a_don - 50, a_acc + 1], axis=1).reshape(-1).astype(np.int32),
+        np.stack([a_don - 1, a_acc + 50], axis=1).reshape(-1).astype(np.int32))
+run_tab(eng, r, anno)
+walls2 = []
+for _ in range(rounds):
+    t0 = time.perf_counter(); full, kept = run_tab(eng, r, anno); walls2.append(time.perf_counter() - t0)
+st2 = eng.sj_stats()
+os.environ["L2R_SJ_TIMING"] = "1"
+run_tab(eng, r, anno)
+tm2 = eng.sj_stats()
+del os.environ["L2R_SJ_TIMING"]
+kern2 = {k: v for k, v in tm2.items() if k.startswith("k_") or k.startswith("intron sort")}
+kernel_ms2 = sum(kern2.values())
+passes2 = int(tm2["radix_passes"])
+n_in, n_tab = int(tm2["anno_introns"]), len(full.tid)
+# as above with 24 B rows: rows out 24, hist12 12, per pass 4 + 24 + 24, heads 16, reduce 32; the annotation's exons in (8 B) and its introns
+# through a sort of their own (counted at 20 B rows and `passes2` passes at most); annotate 12 B + 1 per row; keep 13 B + 4, take 27 B in and out
+moved2 = 15 * n + 4 * len(r["cig"]) + 24 * rows + (12 + passes2 * 52 + 16 + 32) * rows + 8 * len(anno[2]) + (20 + 12 + passes2 * 44 + 44) * len(a_tid) + \
+    13 * n_tab + 17 * n_tab + 54 * len(kept.tid)
+t0 = time.perf_counter()
+want6 = st.table_numpy(*st.rows_numpy(r["flag"], r["tid"], r["pos"], r["uniq"], r["cig_off"], r["cig"], pair_only=True))
+numpy_s2 = time.perf_counter() - t0
+introns = set(zip(a_tid.tolist(), a_don.tolist(), a_acc.tolist()))
+an = st.anno_numpy(introns, want6[0], want6[1], want6[2])
+keep = st.keep_numpy(an, np.zeros(len(an)), want6[3], want6[4], want6[5])
+ok2 = all(np.array_equal(g.astype(np.int64), w) for g, w in zip((full.tid, full.don, full.acc, full.uniq_c, full.multi_c, full.max_over), want6)) and \
+    all(np.array_equal(g.astype(np.int64), w[keep]) for g, w in zip((kept.tid, kept.don, kept.acc, kept.uniq_c, kept.multi_c, kept.max_over), want6)) and \
+    np.array_equal(kept.anno, an[keep])
+walls2.sort()
+line2 = dict(leg="sjtab", records=n, rows=int(st2["rows_made"]), table_rows=n_tab, kept_rows=len(kept.tid), anno_introns=n_in, rounds=rounds,
+             radix_passes=passes2, wall_s_median=walls2[len(walls2) // 2], wall_s_min=walls2[0], wall_s_max=walls2[-1],
+             records_per_s=n / walls2[len(walls2) // 2], kernel_ms=kernel_ms2, bytes_moved=int(moved2),
+             fraction_of_8TBs=(moved2 / (kernel_ms2 / 1e3)) / 8e12 if kernel_ms2 else 0.0,
+             scatter_ms=tm2["k_sj_scatter"], scatter_ms_plain=tm["k_sj_scatter"],
+             scatter_ratio_to_plain=(tm2["k_sj_scatter"] / passes2) / (tm["k_sj_scatter"] / passes) if passes and passes2 and tm["k_sj_scatter"] else 0.0,
+             numpy_restatement_s=numpy_s2, equals_numpy=bool(ok2))
+print("| kernel (sjtab leg) | ms (one round, every launch waited for) |\n|---|---|")
+for k, v in kern2.items():
+    print("| %s | %.3f |" % (k, v))
+print(json.dumps(line2))
+assert ok2
