@@ -25,6 +25,7 @@
 #include "l2r_filter.hip.h"
 #include "l2r_fusion.hip.h"
 #include "l2r_sj.hip.h"
+#include "l2r_plan.hip.h"
 
 using namespace l2r;
 
@@ -67,6 +68,15 @@ struct DevBuf {
         return 0;
     }
     void release() { if (p) (void)hipFree(p); p = nullptr; cap = 0; }
+};
+
+// Two events around a piece of device work whose time is wanted (hipEventElapsedTime(a, b)), destroyed with the scope
+struct EventPair {
+    hipEvent_t a = nullptr, b = nullptr;
+    EventPair() = default;
+    EventPair(const EventPair &) = delete;
+    EventPair &operator=(const EventPair &) = delete;
+    ~EventPair() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); }
 };
 
 // The three kernel pipelines: classic (l2r_kernels.hip.h, two walks), slab (l2r_slab.hip.h, one walk, two kernels), tile (l2r_tile.hip.h,
@@ -157,6 +167,10 @@ struct l2r_ctx {
     bool one_shot_upload = false;           // ONE run will follow the upload (l2r_classify, l2r_hint_single_run): see l2r_classify
 
     // ---- per upload (l2r_upload_reads)
+    // ... what the upload's plan (UploadPlan, l2r_plan.hip.h) found: written by the upload alone
+    bool sorted = true;
+    int reads_per_tile = TILE_THREADS;
+    int64_t n_tiles = 0, n_tiles256 = 0;
     bool wide_cigar = false;                // long CIGARs: the HBM walks fetch 16 words per lane and round
     bool many_exon_reads = false;           // the upload's sample: more than 0.5 % of the reads have more exons than a slab has rows
     bool slab_ok = false;                   // the upload can run the slab pipeline: coordinate-sorted records, short CIGARs, its slab layout fits
@@ -205,8 +219,6 @@ struct l2r_ctx {
     std::vector<int64_t> h_sj_key_pm;       // ... and its running maximum
     // reads
     int64_t n_reads = 0, n_cigar = 0, first_read = 0;
-    bool sorted = true;
-    int reads_per_tile = TILE_THREADS;
     DevBuf<int32_t> r_tid, r_pos;
     DevBuf<uint8_t> r_rev;
     DevBuf<int64_t> cig_off;
@@ -227,7 +239,6 @@ struct l2r_ctx {
     DevBuf<int32_t> win_start, sj_cursor;   // only for unsorted input
     bool have_win = false;
     // work + results
-    int64_t n_tiles = 0, n_tiles256 = 0;
     DevBuf<uint32_t> local, tile_base, ex_off, info, tile_acc, tile_acc_ex, tile_acc_at, tile_acc_ex_at, tile_chunk, tile_rchunk, totals;  // totals: TOT_WORDS words, by name TOT_* (l2r_kernels.hip.h)
     DevBuf<uint32_t> redo;                  // reads the fast kernel hands to the generic one
     DevBuf<uint8_t> order;                  // per tile: reads by falling exon count (pass A)
@@ -864,140 +875,25 @@ int l2r_set_junctions(l2r_ctx *c, const l2r_junctions *s)
 static int prepare_unsorted_windows(l2r_ctx *c);
 static int finish_stream_sj_cursor(l2r_ctx *c);
 
-int l2r_upload_reads(l2r_ctx *c, const l2r_reads *r)
+// is this upload the continuation of the previous one?  (see l2r_ctx::Stream; its sorted / last_key follow from the plan)
+static int stream_begin_upload(l2r_ctx *c, const l2r_reads *r)
 {
-    if (!c || !r) return fail(-1, "[l2r_upload_reads] null argument");
-    if (r->n_reads < 0 || r->n_cigar < 0) return fail(-1, "[l2r_upload_reads] negative size");
-    // exon offsets are 32 bit on the device: n_exon(read) <= n_cigar(read) + 1
-    if ((uint64_t)r->n_cigar + (uint64_t)r->n_reads >= 0xfffffff0ULL)
-        return fail(-1, "[l2r_upload_reads] shard too large for 32-bit exon offsets (%lld ops + %lld reads); split it", (long long)r->n_cigar, (long long)r->n_reads);
-    HIP_TRY(hipSetDevice(c->device));
+    l2r_ctx::Stream &st = c->seq;
+    const bool cont = st.valid && r->first_read_index > 0 && r->first_read_index == st.next;
+    if (cont) { int rc = finish_stream_sj_cursor(c); if (rc) return rc; }      // (needs the previous upload's results: before they are overwritten)
+    else st = l2r_ctx::Stream();
+    st.anno_cur_start = st.anno_cur; st.sj_cur_start = st.sj_cur;
+    st.next = r->first_read_index + r->n_reads; st.valid = true;
+    st.sj_pending = false;
+    return 0;
+}
+
+// the five record columns and the tiles' first reads
+static int stage_reads(l2r_ctx *c, const l2r_reads *r, const UploadPlan &pl)
+{
     const int64_t N = r->n_reads;
-    if (N && (r->cig_off[0] != 0 || r->cig_off[N] != r->n_cigar)) return fail(-1, "[l2r_upload_reads] cig_off does not span n_cigar");
-    bool sorted = true;
-    for (int64_t i = 0; i < N; ++i) {
-        if (r->tid[i] < 0) return fail(-1, "[l2r_upload_reads] record %lld has no reference (unmapped); the reference aborts on it (bam2gtf.c:100)", (long long)i);
-        if (r->cig_off[i + 1] < r->cig_off[i]) return fail(-1, "[l2r_upload_reads] cig_off not monotone at %lld", (long long)i);
-        if (i && (r->tid[i] < r->tid[i - 1] || (r->tid[i] == r->tid[i - 1] && r->pos[i] < r->pos[i - 1]))) sorted = false;
-    }
-    {   // is this upload the continuation of the previous one?  (see l2r_ctx::Stream)
-        l2r_ctx::Stream &st = c->seq;
-        const bool cont = st.valid && r->first_read_index > 0 && r->first_read_index == st.next;
-        if (cont) { int rc = finish_stream_sj_cursor(c); if (rc) return rc; }      // (needs the previous upload's results: before they are overwritten)
-        else st = l2r_ctx::Stream();
-        if (N && st.sorted) {
-            const int64_t first = ((int64_t)r->tid[0] << 32) | (uint32_t)r->pos[0];
-            if (!sorted || first < st.last_key) st.sorted = false;            // from here on the cursors depend on the history
-        }
-        sorted = st.sorted;
-        if (N) st.last_key = ((int64_t)r->tid[N - 1] << 32) | (uint32_t)r->pos[N - 1];
-        st.anno_cur_start = st.anno_cur; st.sj_cur_start = st.sj_cur;
-        st.next = r->first_read_index + N; st.valid = true;
-        st.sj_pending = false;
-    }
-    c->sorted = sorted; c->have_win = false;
-    if (!sorted || c->n_sj > 0) { c->h_tid.assign(r->tid, r->tid + N); c->h_pos.assign(r->pos, r->pos + N); }
-    else { c->h_tid.clear(); c->h_pos.clear(); }
-
-    c->wide_cigar = N > 0 && (double)r->n_cigar / (double)N > 32.0;
-    // tile size: keep the expected exons of a tile inside the LDS staging area.
-    // Estimate exons/read from a sample of the CIGARs (ops that can start an exon).
-    c->many_exon_reads = false;
-    double est = 1.0;
-    if (N) {
-        const int64_t sample = N < 4096 ? N : 4096;
-        const int64_t step = N / sample;
-        double cuts = 0;
-        int64_t many = 0;                                  // sampled reads with more exons than a slab has rows
-        for (int64_t s = 0; s < sample; ++s) {
-            const int64_t i = s * step;
-            int64_t mine = 0;
-            for (int64_t k = r->cig_off[i]; k < r->cig_off[i + 1]; ++k) {
-                const uint32_t op = r->cig[k] & 15u; const int len = (int)(r->cig[k] >> 4);
-                mine += (op == 3u && len >= c->prm.min_intron) || (op == 2u && len > c->prm.max_delet);
-            }
-            cuts += (double)mine; many += mine + 1 > (int64_t)SLAB_ROWS;
-        }
-        // (k_walk_slab_long hands a read beyond SLAB_ROWS exons to the generic kernel, the classic kernels keep it on the mask path: an
-        //  input where such reads are more than a rarity stays with them)
-        c->many_exon_reads = many * 200 > sample;
-        est = cuts / (double)sample + 1.0;
-    }
-    // What this upload's layout allows, decided once: the slab pipeline takes coordinate-sorted records; with long CIGARs
-    // (k_walk_slab_long) only where reads beyond SLAB_ROWS exons are a rarity.  Its tiles are cut by span and get the slab layout.
-    const bool slab_wanted = c->want_pipe != Pipeline::classic && sorted;
-    const bool slab_tiles = slab_wanted && !c->wide_cigar;                               // short CIGARs (k_walk_slab)
-    const bool slab_long = slab_wanted && c->wide_cigar && !c->many_exon_reads;          // long CIGARs (k_walk_slab_long)
-    const bool slab_layout = slab_tiles || slab_long;                                    // -> slab_ok
-    // ... and the tile index (k_tile_index) that the one-kernel tile path needs: not for an upload that ONE run follows (l2r_classify)
-    const bool make_index = c->want_pipe == Pipeline::tile && !c->wide_cigar && !(c->one_shot_upload && !c->env_tile_anyway && !c->pipeline_forced);
-    int rpt = TILE_THREADS;
-    // (long CIGARs on the slab pipeline: the probe kernels stage SLAB_POS_CAP positions per tile)
-    if (N) while (rpt > 32 && est * rpt * 1.25 > (double)(slab_long ? SLAB_POS_CAP : LDS_EXON_CAP)) rpt >>= 1;
-    // ... and keep the genomic span of a tile inside the staged bucket directory (DIR_CAP buckets of 512 bp):
-    // sparse input (few reads per locus) makes 256 consecutive reads span many genes, and a tile that does not
-    // fit goes to the generic kernel read by read (~30x the cost).  Sample windows of the sorted input, take for
-    // every candidate size the share of windows that would not fit, and pick the cheapest size.
-    // (The slab pipeline's tiles are cut by span one by one, below: a sparse stretch makes ITS tiles small, not every tile of the
-    //  upload -- an annotation with a few isoform-rich loci and long sparse stretches got 128-read tiles throughout, twice the tiles.)
-    if (sorted && N >= 2 * TILE_THREADS && !slab_layout) {
-        const int64_t n_win = std::min<int64_t>(N / TILE_THREADS, 384);
-        const int64_t wstep = (N / TILE_THREADS) / n_win;
-        const int64_t limit = (int64_t)(DIR_CAP - 8) << SITE_SHIFT;
-        int64_t bad[4] = {0, 0, 0, 0};                 // sizes 256, 128, 64, 32
-        for (int64_t w = 0; w < n_win; ++w) {
-            const int64_t i0 = w * wstep * TILE_THREADS;
-            int64_t hi = 0;
-            int size_idx = 3, next_mark = 32;
-            for (int64_t q = 0; q < TILE_THREADS && i0 + q < N; ++q) {
-                const int64_t i = i0 + q;
-                if (r->tid[i] != r->tid[i0]) break;
-                int64_t end = r->pos[i];
-                for (int64_t k = r->cig_off[i]; k < r->cig_off[i + 1]; ++k) if ((0x18du >> (r->cig[k] & 15u)) & 1u) end += r->cig[k] >> 4;
-                hi = std::max(hi, end - r->pos[i0]);
-                if (q + 1 == next_mark) {              // the first 32 / 64 / 128 / 256 reads of the window
-                    if (hi > limit) { for (int z = 0; z <= size_idx; ++z) bad[z]++; break; }   // this size and every larger one
-                    --size_idx; next_mark <<= 1;
-                }
-            }
-        }
-        double best = 1e300; int best_rpt = rpt;
-        for (int z = 0; z < 4; ++z) {
-            const int cand = TILE_THREADS >> z;
-            if (cand > rpt) continue;
-            const double f = (double)bad[z] / (double)n_win;
-            const double cost = (1.0 - f) * (z == 0 ? 1.0 : z == 1 ? 1.6 : z == 2 ? 2.6 : 4.5) + 30.0 * f;
-            if (cost < best - 1e-9) { best = cost; best_rpt = cand; }
-        }
-        rpt = best_rpt;
-    }
-    c->reads_per_tile = rpt;
-    // Tiles: runs of up to rpt consecutive reads; for sorted input a tile also ends where the chromosome changes, so
-    // that every read of a tile can use the tile's dictionary slices (unsorted input: plain runs, the reads that are
-    // not on the chromosome of their tile's first read take the generic kernel).
-    std::vector<uint32_t> tile_first;
-    tile_first.reserve((size_t)(N / rpt + 64));
-    // (slab pipeline: a tile's exons are staged by position in LDS on their way out, l2r_slab.hip.h SLAB_POS_CAP: a tile also ends
-    //  where the exon bounds of its reads -- from the CIGAR lengths -- would exceed that, so no read of it is left outside)
-    uint64_t pos_sum = 0;
-    for (int64_t i = 0, start = 0; i <= N; ++i) {
-        if (i == N) { if (i > start) tile_first.push_back((uint32_t)start); break; }
-        const uint64_t need = slab_tiles ? (uint64_t)slab_rows_of((uint32_t)std::min<int64_t>(r->cig_off[i + 1] - r->cig_off[i], 0x7ffffff0)) : 0u;
-        // (tiles of sorted records also end where the reads would begin 2^17 bases apart: a slab tile's exons are kept relative to its
-        //  first base, and any tile's dictionary slices cover 196 kb -- sparse stretches give small tiles instead of tiles for the
-        //  generic kernel; the classic pipeline, whose tiles own 24 KB of hand-over buffer each, keeps at least 8 reads per tile)
-        if (i - start == rpt || (sorted && r->tid[i] != r->tid[start]) || (i > start && pos_sum + need > (uint64_t)TILE_POS_CAP) ||
-            (sorted && i > start && (int64_t)r->pos[i] - (int64_t)r->pos[start] >= (int64_t)SLAB_TILE_SPAN && (slab_layout || i - start >= 8))) { tile_first.push_back((uint32_t)start); start = i; pos_sum = 0; }
-        pos_sum += need;
-    }
-    c->n_tiles = (int64_t)tile_first.size();
-    tile_first.push_back((uint32_t)N);
-    if (tile_first.size() < 2) tile_first.push_back((uint32_t)N);        // (an empty launch still runs one workgroup)
-    c->n_tiles256 = (N + TILE_THREADS - 1) / TILE_THREADS;
-    if (c->tile_first.ensure(tile_first.size())) return -2;
-    HIP_TRY(hipMemcpyAsync(c->tile_first.p, tile_first.data(), tile_first.size() * 4, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));                              // (tile_first is a local)
-
+    if (c->tile_first.ensure(pl.tile_first.size())) return -2;
+    HIP_TRY(hipMemcpyAsync(c->tile_first.p, pl.tile_first.data(), pl.tile_first.size() * 4, hipMemcpyHostToDevice, c->stream));
     if (c->r_tid.ensure((size_t)N) || c->r_pos.ensure((size_t)N) || c->r_rev.ensure((size_t)N) ||
         c->cig_off.ensure((size_t)N + 1) || c->cig.ensure((size_t)r->n_cigar + 8)) return -2;     // + 8: the kernels read whole 16-byte vectors (pass A: two per lane)
     if (N) {
@@ -1007,149 +903,146 @@ int l2r_upload_reads(l2r_ctx *c, const l2r_reads *r)
         HIP_TRY(hipMemcpyAsync(c->cig_off.p, r->cig_off, (size_t)(N + 1) * 8, hipMemcpyHostToDevice, c->stream));
         if (r->n_cigar) HIP_TRY(hipMemcpyAsync(c->cig.p, r->cig, (size_t)r->n_cigar * 4, hipMemcpyHostToDevice, c->stream));
     }
-    // work buffers.  n_exon(read) <= ops(read) + 1, so n_cigar + n_reads bounds the exon arrays; for long CIGARs (hundreds of
-    // M/I/D ops per exon) that bound is 10-50 times too generous, so the ops that can end an exon at all (N, D) are
-    // counted on the device (one pass over the words that were just uploaded; sizing only, nothing of it is kept).
-    size_t exb = (size_t)r->n_cigar + (size_t)N;
-    if (c->wide_cigar) {
-        unsigned long long *d_cnt = reinterpret_cast<unsigned long long *>(c->totals.p ? c->totals.p : nullptr);
-        if (!d_cnt) { if (c->totals.ensure(TOT_WORDS)) return -2; d_cnt = reinterpret_cast<unsigned long long *>(c->totals.p); }
-        HIP_TRY(hipMemsetAsync(d_cnt, 0, 8, c->stream));
-        hipLaunchKernelGGL(k_count_cut_ops, dim3(4096), dim3(TILE_THREADS), 0, c->stream, (const uint32_t *)c->cig.p, (int64_t)r->n_cigar, d_cnt);
-        unsigned long long cuts = 0;
-        HIP_TRY(hipMemcpyAsync(&cuts, d_cnt, 8, hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(hipStreamSynchronize(c->stream));
-        exb = (size_t)cuts + (size_t)N;
-    }
-    if (c->j0.ensure((size_t)N) || c->local.ensure((size_t)N + 1) || c->ex_off.ensure((size_t)N) || c->info.ensure((size_t)N) || c->ref_tx.ensure((size_t)N) ||
-        c->redo.ensure((size_t)N) || c->order.ensure((size_t)N + TILE_THREADS) || c->desc.ensure((size_t)c->n_tiles) || c->win_hdr.ensure((size_t)c->n_tiles * WIN_TX) ||
-        c->tile_base.ensure((size_t)c->n_tiles + 1) || c->tile_acc.ensure((size_t)c->n_tiles + 1) || c->tile_acc_ex.ensure((size_t)c->n_tiles + 1) ||
-        c->tile_acc_at.ensure((size_t)c->n_tiles + 2) || c->tile_acc_ex_at.ensure((size_t)c->n_tiles + 2) ||
-        c->totals.ensure(TOT_WORDS) || c->tile_chunk.ensure((size_t)c->n_tiles + 1) || c->tile_rchunk.ensure((size_t)c->n_tiles + 1) || c->ex_start.ensure(exb) || c->ex_end.ensure(exb) || c->ex_flag.ensure(exb) ||
-        c->acc_rec.ensure((size_t)N) || c->acc_ex_off.ensure((size_t)N) ||
-        c->acc_start.ensure(exb) || c->acc_end.ensure(exb) || c->acc_flag.ensure(exb) || (c->wide_cigar && c->walked.ensure((size_t)(c->n_tiles + 1) * LDS_EXON_CAP))) return -2;
-    c->ex_cap = (int64_t)exb;
-    c->slab_ok = false; c->pipe = Pipeline::classic;
-    if (slab_layout) {
-        // the slab layout (l2r_slab.hip.h): per tile as many rows of 256 elements as its longest read can have exons (bound from
-        // the CIGAR lengths); reads beyond SLAB_ROWS rows are outliers and get a run of the dense area
-        const size_t T = (size_t)c->n_tiles;
-        std::vector<uint32_t> sbase(T + 1, 0u);
-        uint64_t total = 0, ovf = 0;
-        for (size_t t = 0; t < T; ++t) {
-            uint32_t m = 1;
-            if (c->wide_cigar) {
-                // long CIGARs (k_walk_slab_long): the CIGAR length says nothing about the exons -- every tile has SLAB_ROWS rows, and
-                // the dense area has room for every exon of the shard (exb: reads + the operations that can cut)
-                m = (uint32_t)SLAB_ROWS;
-            } else
-            for (uint32_t i = tile_first[t]; i < tile_first[t + 1]; ++i) {
-                const uint64_t cc = (uint64_t)(r->cig_off[i + 1] - r->cig_off[i]);
-                const uint64_t rw = (cc + 3u) >> 1;
-                // (room in the dense area for EVERY read: besides the long CIGARs a read with an exon of 64 kb or more ends up
-                //  there, which only the walk finds out)
-                ovf += cc + 1;
-                if (rw <= (uint64_t)SLAB_ROWS) m = std::max<uint32_t>(m, (uint32_t)rw);
-            }
-            sbase[t] = (uint32_t)total; total += (uint64_t)m * SLAB_STRIDE;
-            if (total >= 0x7ffffff0ULL || ovf >= 0x7ffffff0ULL) break;
-        }
-        if (c->wide_cigar) ovf = (uint64_t)exb;
-        if (total < 0x7ffffff0ULL && ovf < 0x7ffffff0ULL) {
-            sbase[T] = (uint32_t)total;                     // (rows of tile t = (sbase[t + 1] - sbase[t]) / 256)
-            c->slab_ok = true;
-            if (c->tw64.ensure(T + 1) || c->wide_list.ensure(2 * (T + 1)) || c->chunk_list.ensure(2 * (T + 1)) || c->list_cnt.ensure(2 * LC_WORDS) || c->tile_flags.ensure(T + 8) ||
-                c->lb_tile.ensure(T + 64) || c->lb_blk.ensure(T / LB_BLK + 64) || c->lb_sup.ensure(2 * ((T >> LB_SUP_SHIFT) + 64)) || c->fb_list.ensure(T + 1) || c->rest_list.ensure(T + 1) || c->tile_stat.ensure(T + 1) || c->sup_stat.ensure((T >> LB_SUP_SHIFT) + 2) ||
-                (!c->wide_cigar && c->slot_rec.ensure((T + 1) * TILE_THREADS))) return -2;
-            HIP_TRY(hipMemsetAsync(c->lb_sup.p, 0, 2 * ((T >> LB_SUP_SHIFT) + 64) * 8, c->stream)); c->lb_flip = 0;      // (two arrays taking turns; from then on each is cleared by the run in front of its own)      // (an isoform-rich annotation makes EVERY tile wide: 2.4 KB each)
-            HIP_TRY(lc_reset(c)); c->prev_run_tile = false;
-            if (c->tile_sbase.ensure(T + 1) || c->ovf_cursor.ensure(1) || c->tw.ensure(T + 1) || c->tile_total.ensure(T + 2) || c->tile_xbase.ensure(T + 2) || c->tile_span.ensure(12 * (T + 1)) ||
-                c->s_pre.ensure((size_t)N + 1) || c->s_loc.ensure((size_t)N + 1) ||
-                c->slab_row.ensure((size_t)total + 4) ||
-                c->dense_start.ensure((size_t)ovf + 1) || c->dense_end.ensure((size_t)ovf + 1)) return -2;
-            HIP_TRY(hipMemsetAsync(c->ovf_cursor.p, 0, 8, c->stream));
-            HIP_TRY(hipMemcpyAsync(c->tile_sbase.p, sbase.data(), (T + 1) * 4, hipMemcpyHostToDevice, c->stream));
-            // the tiles' records for k_walk_slab (TileRec: reads, slab, chromosome and first base of the tile in one place) and the
-            // records' CIGAR offsets in 32 bits (the walk reads 4 bytes per record instead of 8 at a stride of 8)
-            std::vector<TileRec> rec(T ? T : 1);
-            for (size_t t = 0; t < T; ++t) {
-                TileRec &q = rec[t];
-                q.r0 = tile_first[t]; q.n_act = tile_first[t + 1] - tile_first[t]; q.sbase = sbase[t]; q.rows = (sbase[t + 1] - sbase[t]) >> 8;
-                q.tid0 = q.n_act ? r->tid[q.r0] : 0; q.lo = (q.n_act ? r->pos[q.r0] : 0) + 1; q.pad[0] = q.pad[1] = 0u;
-            }
-            std::vector<uint32_t> off32((size_t)N + 1);
-            for (int64_t i = 0; i <= N; ++i) off32[(size_t)i] = (uint32_t)r->cig_off[i];
-            if (c->tile_rec.ensure(8 * (T + 1)) || c->cig_off32.ensure((size_t)N + 2) || c->s_pl.ensure((size_t)N + 1)) return -2;
-            HIP_TRY(hipMemcpyAsync(c->tile_rec.p, rec.data(), rec.size() * sizeof(TileRec), hipMemcpyHostToDevice, c->stream));
-            HIP_TRY(hipMemcpyAsync(c->cig_off32.p, off32.data(), off32.size() * 4, hipMemcpyHostToDevice, c->stream));
-            // every tile's last base (the largest read end: CIGAR lengths only, no parameter has a say) into its record: the one-kernel
-            // tile path makes the tiles' windows from it in front of the walk (l2r_tile.hip.h)
-            // ... and an index of its CIGAR operations from which a run knows the tile's exon count unless a threshold is borderline in it
-            c->h_tile_stat.assign(T, TileStat{0, INT32_MAX, 0, INT32_MAX});
-            c->index_ms = 0.0f; c->have_index = false;
-            if (T && make_index) {
-                c->have_index = true;
-                struct Ev { hipEvent_t a = nullptr, b = nullptr; ~Ev() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); } } ev;
-                HIP_TRY(hipEventCreate(&ev.a)); HIP_TRY(hipEventCreate(&ev.b));
-                const unsigned gi = (unsigned)std::min<size_t>(T, 8192);
-                if (r->cig_summary) {
-                    // the reader's per-record summaries: the tiles' statistics and last bases on the host (no parameter has a say in them), the
-                    // records' N operations as one 16-bit column for the kernel -- which then touches no CIGAR
-                    std::vector<uint16_t> nn((size_t)N);
-                    for (size_t t = 0; t < T; ++t) {
-                        TileStat st{0, INT32_MAX, 0, INT32_MAX};
-                        int64_t hi = INT32_MIN; uint32_t tot_x = 0u; bool many = false;
-                        for (uint32_t i = tile_first[t]; i < tile_first[t + 1]; ++i) {
-                            const uint32_t *q = r->cig_summary + 3 * (size_t)i;
-                            const uint32_t n_n = q[1] & 0xffffu, mn = q[1] >> 16, md = q[2] & 0xffffu, ms = q[2] >> 16;
-                            nn[i] = (uint16_t)n_n;
-                            st.n_ops_n += (int32_t)n_n; st.min_n = std::min(st.min_n, (int32_t)mn); st.min_seg = std::min(st.min_seg, (int32_t)ms);
-                            st.max_d = std::max(st.max_d, md == 0xffffu ? INT32_MAX : (int32_t)md);      // (65535: that long or longer)
-                            hi = std::max<int64_t>(hi, (int64_t)r->pos[i] + (int64_t)q[0]);
-                            tot_x += n_n + 1u; many = many || n_n + 1u >= 255u;
-                        }
-                        // (a read of 255 exons or more, places a slot record cannot say: never an exact tile -- as k_tile_index<false> rules)
-                        if (many || tot_x >= SLOT_LOC_LIMIT) st.min_seg = INT32_MIN;
-                        c->h_tile_stat[t] = st;
-                        rec[t].pad[0] = (uint32_t)std::min<int64_t>(std::max<int64_t>(hi, INT32_MIN), INT32_MAX);
-                    }
-                    if (c->sum_nn.ensure((size_t)N + 1)) return -2;
-                    HIP_TRY(hipMemcpyAsync(c->sum_nn.p, nn.data(), (size_t)N * 2, hipMemcpyHostToDevice, c->stream));
-                    HIP_TRY(hipMemcpyAsync(c->tile_rec.p, rec.data(), rec.size() * sizeof(TileRec), hipMemcpyHostToDevice, c->stream));
-                    HIP_TRY(hipMemcpyAsync(c->tile_stat.p, c->h_tile_stat.data(), T * sizeof(TileStat), hipMemcpyHostToDevice, c->stream));
-                    HIP_TRY(hipEventRecord(ev.a, c->stream));
-                    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_tile_index<true>), dim3(gi), dim3(TILE_THREADS), 0, c->stream, (TileRec *)c->tile_rec.p, c->tile_stat.p, c->slot_rec.p, (uint32_t)T,
-                                       (const uint32_t *)c->cig_off32.p, (const int32_t *)c->r_pos.p, (const uint8_t *)c->r_rev.p, (const uint32_t *)c->cig.p, (const uint16_t *)c->sum_nn.p);
-                    HIP_TRY(hipEventRecord(ev.b, c->stream));
-                    HIP_TRY(hipStreamSynchronize(c->stream));       // (nn, rec)
-                } else {
-                    HIP_TRY(hipEventRecord(ev.a, c->stream));
-                    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_tile_index<false>), dim3(gi), dim3(TILE_THREADS), 0, c->stream, (TileRec *)c->tile_rec.p, c->tile_stat.p, c->slot_rec.p, (uint32_t)T,
-                                       (const uint32_t *)c->cig_off32.p, (const int32_t *)c->r_pos.p, (const uint8_t *)c->r_rev.p, (const uint32_t *)c->cig.p, (const uint16_t *)nullptr);
-                    HIP_TRY(hipEventRecord(ev.b, c->stream));
-                    HIP_TRY(hipMemcpyAsync(c->h_tile_stat.data(), c->tile_stat.p, T * sizeof(TileStat), hipMemcpyDeviceToHost, c->stream));
-                }
-                HIP_TRY(hipEventSynchronize(ev.b));
-                HIP_TRY(hipEventElapsedTime(&c->index_ms, ev.a, ev.b));
-            }
-            HIP_TRY(hipStreamSynchronize(c->stream));       // (locals)
-            {   // the index once more per super-block (l2r_slab.hip.h SlabArgs::sup_stat)
-                std::vector<TileStat> sup((T >> LB_SUP_SHIFT) + 1, TileStat{0, INT32_MAX, 0, INT32_MAX});
-                for (size_t t = 0; t < T; ++t) {
-                    TileStat &q = sup[t >> LB_SUP_SHIFT]; const TileStat &st = c->h_tile_stat[t];
-                    q.n_ops_n += st.n_ops_n + (int32_t)rec[t].n_act; q.min_n = std::min(q.min_n, st.min_n); q.max_d = std::max(q.max_d, st.max_d); q.min_seg = std::min(q.min_seg, st.min_seg);
-                }
-                HIP_TRY(hipMemcpyAsync(c->sup_stat.p, sup.data(), sup.size() * sizeof(TileStat), hipMemcpyHostToDevice, c->stream));
-                HIP_TRY(hipStreamSynchronize(c->stream));
-            }
-        }
-    }
+    return 0;
+}
+
+// work buffers.  n_exon(read) <= ops(read) + 1, so n_cigar + n_reads bounds the exon arrays; for long CIGARs (hundreds of
+// M/I/D ops per exon) that bound is 10-50 times too generous, so the ops that can end an exon at all (N, D) are
+// counted on the device (one pass over the words that were just uploaded; sizing only, nothing of it is kept).
+static int count_exon_bound(l2r_ctx *c, const l2r_reads *r, bool wide_cigar, size_t *exb)
+{
+    *exb = (size_t)r->n_cigar + (size_t)r->n_reads;
+    if (!wide_cigar) return 0;
+    if (c->totals.ensure(TOT_WORDS)) return -2;
+    unsigned long long *d_cnt = reinterpret_cast<unsigned long long *>(c->totals.p);
+    HIP_TRY(hipMemsetAsync(d_cnt, 0, 8, c->stream));
+    hipLaunchKernelGGL(k_count_cut_ops, dim3(4096), dim3(TILE_THREADS), 0, c->stream, (const uint32_t *)c->cig.p, (int64_t)r->n_cigar, d_cnt);
+    unsigned long long cuts = 0;
+    HIP_TRY(hipMemcpyAsync(&cuts, d_cnt, 8, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
+    *exb = (size_t)cuts + (size_t)r->n_reads;
+    return 0;
+}
+
+static int reserve_work(l2r_ctx *c, size_t n_reads, size_t exb)
+{
+    const size_t N = n_reads, T = (size_t)c->n_tiles;
+    if (c->j0.ensure(N) || c->local.ensure(N + 1) || c->ex_off.ensure(N) || c->info.ensure(N) || c->ref_tx.ensure(N) ||
+        c->redo.ensure(N) || c->order.ensure(N + TILE_THREADS) || c->desc.ensure(T) || c->win_hdr.ensure(T * WIN_TX) ||
+        c->tile_base.ensure(T + 1) || c->tile_acc.ensure(T + 1) || c->tile_acc_ex.ensure(T + 1) ||
+        c->tile_acc_at.ensure(T + 2) || c->tile_acc_ex_at.ensure(T + 2) ||
+        c->totals.ensure(TOT_WORDS) || c->tile_chunk.ensure(T + 1) || c->tile_rchunk.ensure(T + 1) || c->ex_start.ensure(exb) || c->ex_end.ensure(exb) || c->ex_flag.ensure(exb) ||
+        c->acc_rec.ensure(N) || c->acc_ex_off.ensure(N) ||
+        c->acc_start.ensure(exb) || c->acc_end.ensure(exb) || c->acc_flag.ensure(exb) || (c->wide_cigar && c->walked.ensure((T + 1) * LDS_EXON_CAP))) return -2;
+    c->ex_cap = (int64_t)exb;
+    return 0;
+}
+
+// the slab pipeline's buffers, and what the plan has laid out for them
+static int stage_slab(l2r_ctx *c, size_t n_reads, const UploadPlan &pl)
+{
+    const size_t N = n_reads, T = (size_t)pl.n_tiles;
+    if (c->tw64.ensure(T + 1) || c->wide_list.ensure(2 * (T + 1)) || c->chunk_list.ensure(2 * (T + 1)) || c->list_cnt.ensure(2 * LC_WORDS) || c->tile_flags.ensure(T + 8) ||
+        c->lb_tile.ensure(T + 64) || c->lb_blk.ensure(T / LB_BLK + 64) || c->lb_sup.ensure(2 * ((T >> LB_SUP_SHIFT) + 64)) || c->fb_list.ensure(T + 1) || c->rest_list.ensure(T + 1) || c->tile_stat.ensure(T + 1) || c->sup_stat.ensure((T >> LB_SUP_SHIFT) + 2) ||
+        (!c->wide_cigar && c->slot_rec.ensure((T + 1) * TILE_THREADS))) return -2;
+    HIP_TRY(hipMemsetAsync(c->lb_sup.p, 0, 2 * ((T >> LB_SUP_SHIFT) + 64) * 8, c->stream)); c->lb_flip = 0;      // (two arrays taking turns; from then on each is cleared by the run in front of its own)      // (an isoform-rich annotation makes EVERY tile wide: 2.4 KB each)
+    HIP_TRY(lc_reset(c)); c->prev_run_tile = false;
+    if (c->tile_sbase.ensure(T + 1) || c->ovf_cursor.ensure(1) || c->tw.ensure(T + 1) || c->tile_total.ensure(T + 2) || c->tile_xbase.ensure(T + 2) || c->tile_span.ensure(12 * (T + 1)) ||
+        c->s_pre.ensure(N + 1) || c->s_loc.ensure(N + 1) ||
+        c->slab_row.ensure((size_t)pl.slab_total + 4) ||
+        c->dense_start.ensure((size_t)pl.dense_rows + 1) || c->dense_end.ensure((size_t)pl.dense_rows + 1)) return -2;
+    HIP_TRY(hipMemsetAsync(c->ovf_cursor.p, 0, 8, c->stream));
+    HIP_TRY(hipMemcpyAsync(c->tile_sbase.p, pl.sbase.data(), (T + 1) * 4, hipMemcpyHostToDevice, c->stream));
+    if (c->tile_rec.ensure(8 * (T + 1)) || c->cig_off32.ensure(N + 2) || c->s_pl.ensure(N + 1)) return -2;
+    HIP_TRY(hipMemcpyAsync(c->tile_rec.p, pl.rec.data(), pl.rec.size() * sizeof(TileRec), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(c->cig_off32.p, pl.off32.data(), pl.off32.size() * 4, hipMemcpyHostToDevice, c->stream));
+    return 0;
+}
+
+// the upload's tile index (k_tile_index): the slot records, and the tiles' statistics -- which come from the plan where the reader's
+// summaries made them, and from the kernel's walk of the CIGARs where not.  Leaves them in h_tile_stat either way.
+static int make_tile_index(l2r_ctx *c, const l2r_reads *r, const UploadPlan &pl)
+{
+    const size_t N = (size_t)r->n_reads, T = (size_t)pl.n_tiles;
+    const bool summaries = r->cig_summary != nullptr;
+    c->h_tile_stat = pl.tile_stat;
+    c->index_ms = 0.0f; c->have_index = pl.have_index;
+    if (!pl.have_index) return 0;
+    EventPair ev;
+    HIP_TRY(hipEventCreate(&ev.a)); HIP_TRY(hipEventCreate(&ev.b));
+    if (summaries) {
+        if (c->sum_nn.ensure(N + 1)) return -2;
+        HIP_TRY(hipMemcpyAsync(c->sum_nn.p, pl.nn.data(), N * 2, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(hipMemcpyAsync(c->tile_stat.p, c->h_tile_stat.data(), T * sizeof(TileStat), hipMemcpyHostToDevice, c->stream));
+    }
+    const unsigned gi = (unsigned)std::min<size_t>(T, 8192);
+    HIP_TRY(hipEventRecord(ev.a, c->stream));
+    with_flag(summaries, [&](auto S) {
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_tile_index<S>), dim3(gi), dim3(TILE_THREADS), 0, c->stream, (TileRec *)c->tile_rec.p, c->tile_stat.p, c->slot_rec.p, (uint32_t)T,
+                           (const uint32_t *)c->cig_off32.p, (const int32_t *)c->r_pos.p, (const uint8_t *)c->r_rev.p, (const uint32_t *)c->cig.p, S ? (const uint16_t *)c->sum_nn.p : (const uint16_t *)nullptr);
+    });
+    HIP_TRY(hipEventRecord(ev.b, c->stream));
+    if (!summaries) {
+        HIP_TRY(hipMemcpyAsync(c->h_tile_stat.data(), c->tile_stat.p, T * sizeof(TileStat), hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));       // (sup_stat is made from them)
+    }
+    HIP_TRY(hipEventSynchronize(ev.b));
+    HIP_TRY(hipEventElapsedTime(&c->index_ms, ev.a, ev.b));
+    return 0;
+}
+
+int l2r_upload_reads(l2r_ctx *c, const l2r_reads *r)
+{
+    if (!c || !r) return fail(-1, "[l2r_upload_reads] null argument");
+    if (r->n_reads < 0 || r->n_cigar < 0) return fail(-1, "[l2r_upload_reads] negative size");
+    // exon offsets are 32 bit on the device: n_exon(read) <= n_cigar(read) + 1
+    if ((uint64_t)r->n_cigar + (uint64_t)r->n_reads >= 0xfffffff0ULL)
+        return fail(-1, "[l2r_upload_reads] shard too large for 32-bit exon offsets (%lld ops + %lld reads); split it", (long long)r->n_cigar, (long long)r->n_reads);
+    HIP_TRY(hipSetDevice(c->device));
+    const int64_t N = r->n_reads;
+    // The plan and the super-block sums are the source of asynchronous copies: they live until the function returns, and whichever way
+    // it returns the stream has drained by then
+    UploadPlan pl;
+    std::vector<TileStat> sup;
+    struct Drain { hipStream_t s; ~Drain() { (void)hipStreamSynchronize(s); } } drain{c->stream};
+    std::string msg;
+    if (int rc = plan_check_reads(*r, pl, msg)) return fail(rc, "%s", msg.c_str());
+
+    if (int rc = stream_begin_upload(c, r)) return rc;
+
+    PlanOpts po;
+    po.min_intron = c->prm.min_intron; po.max_delet = c->prm.max_delet;
+    po.want_slab = c->want_pipe != Pipeline::classic;
+    po.want_index = c->want_pipe == Pipeline::tile && !(c->one_shot_upload && !c->env_tile_anyway && !c->pipeline_forced);
+    po.stream_sorted = c->seq.sorted; po.last_key = c->seq.last_key;
+    plan_tiles(*r, po, pl);
+    c->seq.sorted = pl.sorted; c->seq.last_key = pl.last_key;
+    const bool sorted = pl.sorted;
+    c->sorted = sorted; c->have_win = false;
+    if (!sorted || c->n_sj > 0) { c->h_tid.assign(r->tid, r->tid + N); c->h_pos.assign(r->pos, r->pos + N); }
+    else { c->h_tid.clear(); c->h_pos.clear(); }
+    c->wide_cigar = pl.wide_cigar; c->many_exon_reads = pl.many_exon_reads;
+    c->reads_per_tile = pl.reads_per_tile; c->n_tiles = pl.n_tiles; c->n_tiles256 = pl.n_tiles256;
+
+    if (int rc = stage_reads(c, r, pl)) return rc;
+    size_t exb = 0;
+    if (int rc = count_exon_bound(c, r, pl.wide_cigar, &exb)) return rc;
+    if (int rc = reserve_work(c, (size_t)N, exb)) return rc;
+
+    plan_slab(*r, exb, pl);
+    c->slab_ok = pl.slab_ok; c->pipe = Pipeline::classic;
+    if (pl.slab_ok) {
+        if (int rc = stage_slab(c, (size_t)N, pl)) return rc;
+        if (int rc = make_tile_index(c, r, pl)) return rc;
+        sup = plan_sup_stat(pl, c->h_tile_stat);
+        HIP_TRY(hipMemcpyAsync(c->sup_stat.p, sup.data(), sup.size() * sizeof(TileStat), hipMemcpyHostToDevice, c->stream));
+    }
     if (c->env_stamps && !c->stamps.p) {
         if (c->stamps.ensure(1024 * 8 + 16)) return -2;
         HIP_TRY(hipMemsetAsync(c->stamps.p, 0, (1024 * 8 + 16) * 8, c->stream));
-        HIP_TRY(hipStreamSynchronize(c->stream));
     }
+    HIP_TRY(hipStreamSynchronize(c->stream));
+
     c->n_reads = N; c->n_cigar = r->n_cigar; c->first_read = r->first_read_index;
     c->ran = false; c->totals_valid = false; forget_list_state(c);
     if (sorted) {

@@ -21,37 +21,12 @@ import pytest
 
 from lr2rmats_amd import capi, synth
 from tests import util
+from tests.upload_plan_restatement import TILE_POS_CAP, _tile_firsts, _tile_stats      # the model of the upload's tile cut
 
 SEED = 8008
 N_READS = 16000
-TILE_READS, TILE_POS_CAP, TILE_SPAN = 256, 2400, 1 << 17        # l2r_slab.hip.h: TILE_THREADS, TILE_POS_CAP, SLAB_TILE_SPAN
 MAX_DELET = 50
 MIN_EXACT, MIN_INEXACT, MAX_INEXACT = 20, 4, 12
-
-
-def _tile_firsts(reads):
-    """The upload's tile cut for coordinate-sorted records with short CIGARs (l2r_upload_reads): runs of up to 256 reads of one
-    chromosome that begin less than 2^17 bases apart and whose exon bounds ((ops + 3) >> 1 per read) fit the staged positions."""
-    n_ops = np.diff(reads.cig_off)
-    firsts, start, pos_sum = [], 0, 0
-    for i in range(reads.n):
-        need = (int(n_ops[i]) + 3) >> 1
-        if i > start and (i - start == TILE_READS or reads.tid[i] != reads.tid[start] or pos_sum + need > TILE_POS_CAP or
-                          int(reads.pos[i]) - int(reads.pos[start]) >= TILE_SPAN):
-            firsts.append(start)
-            start, pos_sum = i, 0
-        pos_sum += need
-    firsts.append(start)
-    return np.array(firsts + [reads.n], np.int64)
-
-
-def _tile_stats(reads, firsts):
-    """TileStat per tile from the records' CIGAR summaries: N operations, the shortest N, the longest D, the shortest inner stretch."""
-    s = synth.cigar_summary(reads.cig_off, reads.cig).astype(np.int64)
-    n_n, min_n, max_d, min_seg = s[:, 1] & 0xffff, s[:, 1] >> 16, s[:, 2] & 0xffff, s[:, 2] >> 16
-    lo = firsts[:-1]
-    return (np.add.reduceat(n_n, lo), np.minimum.reduceat(min_n, lo), np.maximum.reduceat(max_d, lo), np.minimum.reduceat(min_seg, lo),
-            np.maximum.reduceat(n_n, lo))
 
 
 def _exact(stats, min_exon, min_intron):
