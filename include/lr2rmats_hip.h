@@ -401,6 +401,24 @@ int          l2r_sj_annotate(l2r_ctx *ctx, const l2r_annotation *anno);
 int          l2r_sj_filter_rows(l2r_ctx *ctx, const l2r_sj_filter *filter, int64_t *n_rows);
 int          l2r_sj_download_tab(l2r_ctx *ctx, l2r_sj_tab *table);
 
+/* ---- `sort`, `filter -S` (host/sort.c): the coordinate order of alignment records -- what `update-gtf` wants of its input and the
+ * reference pipeline gets from `samtools sort` (Snakefile, rule sam_novel_gtf).  One 64-bit key per record,
+ *     key = (tid < 0 ? 0x7fffffff : tid) << 33  |  (uint32)(pos + 1) << 1  |  ((flag >> 4) & 1)
+ * (pos: core.pos, 0-based, so -1 gives 0; records without a reference last); records with equal keys keep their input order.  That is
+ * the whole definition: no byte equality with the output of any samtools release is claimed.
+ * l2r_sort_order: order_out[k] = index of the record at rank k (n words).  A stable LSD radix sort on the device with 8-bit digits
+ * and the record index as the payload (csrc/l2r_sort.hip.h); a key byte that is equal in every record is a pass that is not run, and
+ * input whose keys never descend is answered with the identity and no pass at all.  n == 0 succeeds; n > 2^32 - 1 - L2R_SORT_TILE
+ * fails before any pointer is read.  The device buffers belong to the context, grow on demand and go with l2r_destroy.
+ * l2r_sort_stats, of the last l2r_sort_order: out[0] rows, [1] radix passes run (of 8), [2] 1 where the input was in order already;
+ * with L2R_SORT_TIMING=1 in the environment at the call (every launch is then waited for) device milliseconds of [3] k_sort_keys
+ * [4] k_sort_digit_hist [5] k_scan_u32 of the tile histograms [6] k_sort_scatter, each summed over the passes; n = words of out (up
+ * to 7).  L2R_SORT_FORCE=1 (tests): all eight passes run, whether the input is in order and whether bytes are constant. */
+#define L2R_SORT_TILE 4096              /* rows one workgroup of a radix pass ranks (csrc/l2r_sort.hip.h) */
+typedef struct { int64_t n; const uint16_t *flag; const int32_t *tid, *pos; } l2r_sort_records;
+int          l2r_sort_order(l2r_ctx *ctx, const l2r_sort_records *recs, uint32_t *order_out);  /* order_out[k] = record at rank k */
+int          l2r_sort_stats(l2r_ctx *ctx, double *out, int n);
+
 #ifdef __cplusplus
 }
 #endif

@@ -34,6 +34,7 @@ EXPORTS = [
     "l2r_sj_begin", "l2r_sj_add", "l2r_sj_add_rows", "l2r_sj_finish", "l2r_sj_download", "l2r_sj_stats",
     "l2r_sj_begin_tab", "l2r_sj_add_rows_over", "l2r_sj_annotate", "l2r_sj_filter_rows", "l2r_sj_download_tab",
     "l2r_fusion_segments", "l2r_fusion_select", "l2r_fusion_stats",
+    "l2r_sort_order", "l2r_sort_stats",
 ]
 SJ_E_UNKNOWN_TID = -3
 
@@ -123,6 +124,10 @@ class CSjFilter(C.Structure):
 SJ_FILTER_DEFAULTS = ((1, 30, 12, 12, 12), (0, 3, 1, 1, 1), (0, 3, 1, 1, 1))      # anchor, unique, total: STAR's outSJfilter* behind the annotated class
 
 
+class CSortRecords(C.Structure):
+    _fields_ = [("n", C.c_int64), ("flag", C.c_void_p), ("tid", C.c_void_p), ("pos", C.c_void_p)]
+
+
 class CTiming(C.Structure):
     _fields_ = [("stage_ms", C.c_float * N_STAGES), ("total_ms", C.c_float), ("iters", C.c_int32)]
 
@@ -194,6 +199,8 @@ def load_library():
         lib.l2r_sj_annotate.argtypes = [C.c_void_p, C.c_void_p]
         lib.l2r_sj_filter_rows.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         lib.l2r_sj_download_tab.argtypes = [C.c_void_p, C.c_void_p]
+        lib.l2r_sort_order.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        lib.l2r_sort_stats.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
         _lib = lib
     return _lib
 
@@ -239,6 +246,17 @@ SJ_STAT_NAMES = ["rows_made", "rounds", "radix_passes", "rows_in", "rows_out", "
                  "k_sj_digit_hist", "k_scan_u32 (tile histograms)", "k_sj_scatter", "k_sj_heads + scan", "k_sj_reduce", "k_sj_motif",
                  "rows_dropped", "anno_introns", "k_sj_introns", "k_sj_annotate", "k_sj_keep", "k_scan_u32 (keep flags)", "k_sj_take",
                  "intron sort + reduce"]
+
+
+SORT_STAT_NAMES = ["rows", "radix_passes", "in_order", "k_sort_keys", "k_sort_digit_hist", "k_scan_u32 (tile histograms)", "k_sort_scatter"]
+
+
+def sort_keys(flag, tid, pos) -> np.ndarray:
+    """The 64-bit keys of l2r_sort_order (include/lr2rmats_hip.h), in numpy: what ``sort_order`` sorts by, stably."""
+    t = np.asarray(tid, np.int64)
+    t = np.where(t < 0, 0x7fffffff, t).astype(np.uint64)
+    p = (np.asarray(pos, np.int64) + 1).astype(np.uint32).astype(np.uint64)
+    return (t << np.uint64(33)) | (p << np.uint64(1)) | ((np.asarray(flag, np.uint64) >> np.uint64(4)) & np.uint64(1))
 
 
 FUSION_STAT_NAMES = ["wave_form", "k_fusion_seg", "k_fusion_select", "k_filter_score", "k_filter_select"]
@@ -434,6 +452,22 @@ class Engine:
         out = np.zeros(len(SJ_STAT_NAMES), np.float64)
         self._chk(self.lib.l2r_sj_stats(self.ctx, out.ctypes.data, len(out)))
         return {k: float(v) for k, v in zip(SJ_STAT_NAMES, out)}
+
+    # ---- `sort`, `filter -S` (include/lr2rmats_hip.h: l2r_sort_order / l2r_sort_stats)
+    def sort_order(self, flag, tid, pos) -> np.ndarray:
+        """order[k] = index of the record at rank k in coordinate order (uint32); records with equal keys keep their input order."""
+        a = [np.ascontiguousarray(flag, np.uint16), np.ascontiguousarray(tid, np.int32), np.ascontiguousarray(pos, np.int32)]
+        n = int(a[0].shape[0])
+        recs = CSortRecords(n, *[x.ctypes.data for x in a])
+        order = np.zeros(max(n, 1), np.uint32)
+        self._chk(self.lib.l2r_sort_order(self.ctx, C.byref(recs), order.ctypes.data))
+        return order[:n]
+
+    def sort_stats(self) -> dict:
+        """l2r_sort_stats of the last sort_order: rows, passes run, in_order, and with L2R_SORT_TIMING=1 device milliseconds per kernel."""
+        out = np.zeros(len(SORT_STAT_NAMES), np.float64)
+        self._chk(self.lib.l2r_sort_stats(self.ctx, out.ctypes.data, len(out)))
+        return {k: float(v) for k, v in zip(SORT_STAT_NAMES, out)}
 
     def set_annotation_cache(self, directory) -> None:
         """Keep the annotation tables on disk under ``directory`` (None: off); see include/lr2rmats_hip.h."""

@@ -25,6 +25,7 @@
 #include "l2r_filter.hip.h"
 #include "l2r_fusion.hip.h"
 #include "l2r_sj.hip.h"
+#include "l2r_sort.hip.h"
 #include "l2r_plan.hip.h"
 
 using namespace l2r;
@@ -110,6 +111,18 @@ struct SjState {
 struct SjIntrons {
     DevBuf<int32_t> tx_tid, ex_start, ex_end; DevBuf<int64_t> tx_ex_off;
     SjState st;
+};
+
+// `sort`, `filter -S` (l2r_sort.hip.h): the buffers of l2r_sort_order.  They belong to the context, grow on demand and are used again by
+// the next call; the two key / index columns take turns as source and target of the radix passes.
+struct SortState {
+    DevBuf<uint16_t> flag; DevBuf<int32_t> tid, pos;
+    DevBuf<uint64_t> key[2]; DevBuf<uint32_t> idx[2];
+    DevBuf<uint32_t> hist, tile_hist, word;             // hist: 8 x 256 and, behind them, the descent flag; word[0]: a scan's total
+    bool timing = false;
+    double stats[7] = {0};                              // l2r_sort_stats
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    ~SortState() { for (int k = 0; k < 2; ++k) if (ev[k]) (void)hipEventDestroy(ev[k]); }
 };
 
 // What l2r_sync has learned from the counters of a completed run of the tile path (fetch_run_facts): a later run of the same inputs,
@@ -260,6 +273,7 @@ struct l2r_ctx {
     SjState sj;                             // `bam2sj`, `sjtab`
     SjIntrons sj_intr;                      // `sjtab`: l2r_sj_annotate
     double fusion_stats[5] = {0, 0, 0, 0, 0};        // `fusion`: l2r_fusion_stats
+    SortState sort;                         // `sort`, `filter -S`
 };
 
 // What completed runs have shown about the tile path's lists and the inexact tiles: forgotten wherever inputs, parameters or outputs change
@@ -2403,6 +2417,103 @@ int l2r_sj_stats(l2r_ctx *c, double *out, int n)
 {
     if (!c || !out || n < 0) return fail(-1, "[l2r_sj_stats] bad argument");
     for (int k = 0; k < n; ++k) out[k] = k < SJS_N ? c->sj.stats[k] : 0.0;
+    return 0;
+}
+
+// ---------------------------------------------------------------------------------------------- sort, filter -S
+extern "C++" {
+// a launch on the context stream; with L2R_SORT_TIMING=1 bracketed by events, waited for and added to stats[slot]; L2R_CHECK: waited for
+template <typename F> static int sort_launch(l2r_ctx *c, SortState &s, int slot, F f)
+{
+    if (s.timing) HIP_TRY(hipEventRecord(s.ev[0], c->stream));
+    f();
+    HIP_TRY(hipGetLastError());
+    if (s.timing) {
+        float ms = 0.0f;
+        HIP_TRY(hipEventRecord(s.ev[1], c->stream));
+        HIP_TRY(hipEventSynchronize(s.ev[1]));
+        HIP_TRY(hipEventElapsedTime(&ms, s.ev[0], s.ev[1]));
+        s.stats[slot] += ms;
+    }
+    if (c->check_stages) HIP_TRY(hipStreamSynchronize(c->stream));
+    return 0;
+}
+}
+
+enum { SORTS_ROWS = 0, SORTS_PASSES, SORTS_IN_ORDER, SORTS_K_KEYS, SORTS_K_HIST, SORTS_K_SCAN, SORTS_K_SCATTER, SORTS_N };
+
+int l2r_sort_order(l2r_ctx *c, const l2r_sort_records *r, uint32_t *order_out)
+{
+    if (!c || !r) return fail(-1, "[l2r_sort_order] null argument");
+    SortState &s = c->sort;
+    for (double &v : s.stats) v = 0;
+    if (r->n < 0) return fail(-1, "[l2r_sort_order] %lld records", (long long)r->n);
+    if (r->n > (int64_t)0xffffffffll - L2R_SORT_TILE)
+        return fail(-1, "[l2r_sort_order] %lld records: one sort takes 2^32 - 1 - %d at most (the index of a record is a 32-bit word)", (long long)r->n, L2R_SORT_TILE);
+    if (r->n == 0) { s.stats[SORTS_IN_ORDER] = 1; return 0; }
+    if (!r->flag || !r->tid || !r->pos || !order_out) return fail(-1, "[l2r_sort_order] null column");
+    const char *e = getenv("L2R_SORT_TIMING");
+    s.timing = e && atoi(e) != 0;
+    e = getenv("L2R_SORT_FORCE");
+    const bool force = e && atoi(e) != 0;
+    HIP_TRY(hipSetDevice(c->device));
+    for (int k = 0; k < 2; ++k) if (!s.ev[k]) HIP_TRY(hipEventCreate(&s.ev[k]));
+    const size_t N = (size_t)r->n;
+    const uint32_t n = (uint32_t)r->n;
+    const uint32_t n_tiles = (uint32_t)((N + SORT_TILE - 1) / SORT_TILE);
+    s.stats[SORTS_ROWS] = (double)r->n;
+    int rc;
+    if ((rc = to_dev(c, s.flag, r->flag, N)) || (rc = to_dev(c, s.tid, r->tid, N)) || (rc = to_dev(c, s.pos, r->pos, N))) return rc;
+    if (s.key[0].ensure(N) || s.hist.ensure(SORT_KEY_BYTES * 256 + 1) || s.word.ensure(4)) return -2;
+    // the keys, which of their bytes differ at all, whether they descend anywhere
+    uint32_t h8[SORT_KEY_BYTES * 256 + 1];
+    HIP_TRY(hipMemsetAsync(s.hist.p, 0, sizeof h8, c->stream));
+    const unsigned grid = (unsigned)std::min<size_t>((N + SORT_THREADS - 1) / SORT_THREADS, 2048);
+    const SortRecs recs{r->n, s.flag.p, s.tid.p, s.pos.p};
+    if ((rc = sort_launch(c, s, SORTS_K_KEYS, [&] {
+            hipLaunchKernelGGL(k_sort_keys, dim3(grid), dim3(SORT_THREADS), 0, c->stream, recs, s.key[0].p, s.hist.p, s.hist.p + SORT_KEY_BYTES * 256);
+        }))) return rc;
+    HIP_TRY(hipMemcpyAsync(h8, s.hist.p, sizeof h8, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    const bool in_order = h8[SORT_KEY_BYTES * 256] == 0u;
+    s.stats[SORTS_IN_ORDER] = in_order ? 1 : 0;
+    int pass_byte[SORT_KEY_BYTES], n_pass = 0;
+    for (int b = 0; b < SORT_KEY_BYTES; ++b) {
+        bool one_value = false;
+        for (int d = 0; d < 256; ++d) if (h8[b * 256 + d] == n) { one_value = true; break; }
+        if (force || (!in_order && !one_value)) pass_byte[n_pass++] = b;
+    }
+    if (n_pass == 0) {                                              // (keys that never descend: the order is the identity)
+        for (size_t i = 0; i < N; ++i) order_out[i] = (uint32_t)i;
+        return 0;
+    }
+    if (s.idx[0].ensure(N) || s.idx[1].ensure(N) || (n_pass > 1 && s.key[1].ensure(N)) || s.tile_hist.ensure((size_t)256 * n_tiles + 1)) return -2;
+    int src = 0;
+    for (int p = 0; p < n_pass; ++p) {
+        const int b = pass_byte[p];
+        const bool first = p == 0, last = p == n_pass - 1;
+        const uint64_t *key_in = s.key[src].p; const uint32_t *idx_in = s.idx[src].p;
+        uint64_t *key_out = s.key[1 - src].p; uint32_t *idx_out = s.idx[1 - src].p;
+        if ((rc = sort_launch(c, s, SORTS_K_HIST, [&] { hipLaunchKernelGGL(k_sort_digit_hist, dim3(n_tiles), dim3(SORT_THREADS), 0, c->stream, key_in, n, b, n_tiles, s.tile_hist.p); }))) return rc;
+        ScanJobs jobs = {}; jobs.job[0] = ScanJob{s.tile_hist.p, (int64_t)256 * n_tiles, s.word.p}; jobs.job[1] = jobs.job[0];
+        if ((rc = sort_launch(c, s, SORTS_K_SCAN, [&] { hipLaunchKernelGGL(k_scan_u32, dim3(1), dim3(1024), 0, c->stream, jobs); }))) return rc;
+        if ((rc = sort_launch(c, s, SORTS_K_SCATTER, [&] {
+#define SORT_SCATTER(F, L) hipLaunchKernelGGL((k_sort_scatter<F, L>), dim3(n_tiles), dim3(SORT_THREADS), 0, c->stream, key_in, idx_in, key_out, idx_out, n, b, n_tiles, (const uint32_t *)s.tile_hist.p)
+                if (first && last) SORT_SCATTER(true, true); else if (first) SORT_SCATTER(true, false); else if (last) SORT_SCATTER(false, true); else SORT_SCATTER(false, false);
+#undef SORT_SCATTER
+            }))) return rc;
+        src = 1 - src;
+    }
+    s.stats[SORTS_PASSES] = n_pass;
+    HIP_TRY(hipMemcpyAsync(order_out, s.idx[src].p, N * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+int l2r_sort_stats(l2r_ctx *c, double *out, int n)
+{
+    if (!c || !out || n < 0) return fail(-1, "[l2r_sort_stats] bad argument");
+    for (int k = 0; k < n; ++k) out[k] = k < SORTS_N ? c->sort.stats[k] : 0.0;
     return 0;
 }
 

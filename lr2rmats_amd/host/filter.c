@@ -28,7 +28,8 @@ static int filter_usage(void)
 {
     /* src/bam_filter.c:16-30 */
     fprintf(stderr, "\n");
-    fprintf(stderr, "Usage:   %s filter [option] <in.bam/sam> | samtools sort > out.sort.bam\n\n", "lr2rmats");
+    fprintf(stderr, "Usage:   %s filter [option] <in.bam/sam> | samtools sort > out.sort.bam\n", "lr2rmats");
+    fprintf(stderr, "     or: %s filter -S [option] <in.bam/sam> > out.sort.bam\n\n", "lr2rmats");
     fprintf(stderr, "Options:\n");
     fprintf(stderr, "         -v --coverage   [FLOAT]    minimum fraction of aligned bases. [%.2f]\n", COV_RATIO);
     fprintf(stderr, "         -q --map-qual   [FLOAT]    minimum fraction of identically aligned bases. [%.2f]\n", MAP_QUAL);
@@ -36,6 +37,7 @@ static int filter_usage(void)
     fprintf(stderr, "                                    alignment, or no alignments will be retained. [%.2f]\n", SEC_RATIO);
     fprintf(stderr, "         -i --intron     [INT]      minimum number of intron indicated by the alignment. [%d]\n", MIN_INTRON_NUM);
     fprintf(stderr, "         -r --remove-gtf [STR]      remove all the alignment record that overlap with transcript in this GTF file. [NONE]\n");
+    fprintf(stderr, "         -S --sorted                write the retained alignments sorted by coordinate (as `%s sort` does). [False]\n", "lr2rmats");
     fprintf(stderr, "\n");
     return 1;
 }
@@ -622,6 +624,11 @@ int h_records_to_bam(const char *in_fn, const char *out_fn)
 
 int h_filter_run(const char *in_fn, const char *remove_fn, const l2r_filter_params *prm, FILE *out, int64_t *n_written)
 {
+    return h_filter_run_sorted(in_fn, remove_fn, prm, 0, out, n_written);
+}
+
+int h_filter_run_sorted(const char *in_fn, const char *remove_fn, const l2r_filter_params *prm, int sorted, FILE *out, int64_t *n_written)
+{
     h_chroms chr; memset(&chr, 0, sizeof chr);
     h_records r;
     h_stage_time("start");
@@ -677,13 +684,21 @@ int h_filter_run(const char *in_fn, const char *remove_fn, const l2r_filter_para
     int64_t *winner = (int64_t *)h_malloc((size_t)(n_groups + 1) * 8);
     if (l2r_filter_select(ctx, n_groups, goff, k_score, k_intron, prm, winner)) h_fatal("bam_filter", "%s", l2r_last_error());
     h_stage_time("engine: select (upload, kernel, download)");
-    l2r_destroy(ctx);
     int64_t n_out = 0;
     for (int64_t gi = 0; gi < n_groups; ++gi) {
         /* (a read name that is the empty string is never written: strcmp(lqname, "\0") != 0, :141,:149) */
         const char *name = (const char *)(r.buf + r.rec_off[kept[goff[gi]]] + 4 + 32);
         if (winner[gi] >= 0 && name[0]) kept[n_out++] = kept[winner[gi]];      /* (in place: winner[gi] >= goff[gi] >= n_out) */
     }
+    if (sorted) {                                            /* -S: what `| samtools sort` does behind the reference's filter */
+        int64_t *by_coord = (int64_t *)h_malloc((size_t)(n_out + 1) * 8);
+        h_sort_order(ctx, &r, kept, n_out, by_coord, "bam_filter");
+        memcpy(kept, by_coord, (size_t)n_out * 8);
+        free(by_coord);
+        h_records_set_coordinate(&r, "bam_filter");
+        h_stage_time("engine: order (upload, kernels, download)");
+    }
+    l2r_destroy(ctx);
     int rc = h_write_bam(out, &r, kept, n_out);
     if (rc) h_fatal("bam_filter", "Error in writing SAM record\n");
     h_stage_time("write BAM (BGZF)");
@@ -697,25 +712,26 @@ int h_cmd_filter(int argc, char **argv)
 {
     static const struct option long_opt[] = {
         { "coverage", 1, NULL, 'v' }, { "map-quality", 1, NULL, 'q' }, { "sec-rat", 1, NULL, 's' }, { "intron", 1, NULL, 'i' },
-        { "remove-gtf", 1, NULL, 'r' }, { 0, 0, 0, 0 }
+        { "remove-gtf", 1, NULL, 'r' }, { "sorted", 0, NULL, 'S' }, { 0, 0, 0, 0 }
     };
     l2r_filter_params prm = { (float)COV_RATIO, (float)MAP_QUAL, (float)SEC_RATIO, MIN_INTRON_NUM };
     char remove_fn[1024] = "";
-    int c;
+    int c, sorted = 0;
     optind = 1;
-    while ((c = getopt_long(argc, argv, "v:q:s:i:r:", long_opt, NULL)) >= 0) {
+    while ((c = getopt_long(argc, argv, "v:q:s:i:r:S", long_opt, NULL)) >= 0) {
         switch (c) {
         case 'v': prm.cov_rate = (float)atof(optarg); break;
         case 'q': prm.map_qual = (float)atof(optarg); break;
         case 's': prm.sec_rat = (float)atof(optarg); break;
         case 'i': prm.min_intron_n = atoi(optarg); break;
         case 'r': snprintf(remove_fn, sizeof remove_fn, "%s", optarg); break;
+        case 'S': sorted = 1; break;
         default: return filter_usage();
         }
     }
     if (argc - optind != 1) return filter_usage();
     int64_t cnt = 0;
-    const int rc = h_filter_run(argv[optind], remove_fn, &prm, stdout, &cnt);
+    const int rc = h_filter_run_sorted(argv[optind], remove_fn, &prm, sorted, stdout, &cnt);
     fprintf(stderr, "[%s] Filtered alignments: %d\n", "bam_filter", (int)cnt);
     return rc;
 }

@@ -83,6 +83,23 @@ void h_records_free(h_records *r);
 int  h_write_bam(FILE *fp, const h_records *r, const int64_t *keep, int64_t n_keep);
 int  h_records_to_bam(const char *in_fn, const char *out_fn);
 int  h_filter_run(const char *in_fn, const char *remove_fn, const l2r_filter_params *prm, FILE *out, int64_t *n_written);
+/* `filter -S`: sorted != 0 -> the records that are written come in coordinate order and the header says so (sort.c) */
+int  h_filter_run_sorted(const char *in_fn, const char *remove_fn, const l2r_filter_params *prm, int sorted, FILE *out, int64_t *n_written);
+
+/* ---- `sort`, `sort-check`, `filter -S` (sort.c).  The order: ascending h_sort_key, records with equal keys in input order.
+ * h_sort_key: (tid < 0 ? 0x7fffffff : tid) << 33 | (uint32)(pos + 1) << 1 | (flag >> 4 & 1) -- the key of l2r_sort_order.
+ * h_header_coordinate (no GPU): the BAM header block `hdr` (magic, l_text, text, n_ref, references) with SO:coordinate in its @HD
+ * line -- an SO field there gets that value, an @HD line without one gets the field appended, a text without an @HD line gets
+ * "@HD\tVN:1.6\tSO:coordinate" as its first line; l_text follows, the references are copied as they are.  Returns the bytes of the
+ * new block (at most hdr_len + H_HEADER_SO_ROOM) and writes them to `out` where out_cap holds them; -1: not a BAM header block.
+ * h_records_set_coordinate: the same on the header of records in memory.
+ * h_sort_order: sorted[k] = the record at rank k among rows[0..n) (rows NULL: records 0..n), by l2r_sort_order on `ctx`. */
+#define H_HEADER_SO_ROOM 32
+uint64_t h_sort_key(int32_t tid, int32_t pos, uint32_t flag);
+int64_t h_header_coordinate(const uint8_t *hdr, size_t hdr_len, uint8_t *out, size_t out_cap);
+void h_records_set_coordinate(h_records *r, const char *who);
+void h_sort_order(l2r_ctx *ctx, const h_records *r, const int64_t *rows, int64_t n, int64_t *sorted, const char *who);
+int  h_sort_run(const char *in_fn, FILE *out, int64_t *n_written);
 
 /* ---- `fusion` (fusion.c).  h_fusion_groups (no GPU): the runs of consecutive MAPPED records with one read name -- rows[k] = record
  * of row k, group g = rows [group_off[g], group_off[g + 1]), rlen[g] = query length (M I S = X) of its first record, taken from
@@ -191,6 +208,8 @@ int h_cmd_filter(int argc, char **argv);
 int h_cmd_bam2sj(int argc, char **argv);
 int h_cmd_sjtab(int argc, char **argv);
 int h_cmd_fusion(int argc, char **argv);
+int h_cmd_sort(int argc, char **argv);
+int h_cmd_sort_check(int argc, char **argv);            /* no GPU; 0 sorted, 1 not, 2 usage */
 int h_main(int argc, char **argv);
 
 /* ---- staged form of update-gtf, used by the CLI itself and by the one-process-per-GPU driver

@@ -87,6 +87,10 @@ def load_library():
         lib.h_records_free.restype = None
         lib.h_fusion_groups.argtypes = [C.c_void_p] * 5
         lib.h_fusion_groups.restype = C.c_int64
+        lib.h_header_coordinate.argtypes = [C.c_char_p, C.c_size_t, C.c_void_p, C.c_size_t]
+        lib.h_header_coordinate.restype = C.c_int64
+        lib.h_sort_key.argtypes = [C.c_int32, C.c_int32, C.c_uint32]
+        lib.h_sort_key.restype = C.c_uint64
         _lib = lib
     return _lib
 
@@ -198,6 +202,25 @@ def fusion_groups(path: str):
                as_score=_arr(r.as_score, n, np.int32).copy(), nm=_arr(r.nm, n, np.int32).copy(), flag=_arr(r.flag, n, np.uint16).copy())
     lib.h_records_free(C.byref(r)); lib.h_chroms_free(C.byref(chr_))
     return out
+
+
+# ---- `sort`, `filter -S` (host/sort.c): the header rewrite and the key (no GPU)
+
+HEADER_SO_ROOM = 32
+
+
+def header_coordinate(block: bytes):
+    """The BAM header block (magic, l_text, text, n_ref, references) with SO:coordinate in its @HD line (h_header_coordinate);
+    None where the bytes are no such block."""
+    lib = load_library()
+    out = C.create_string_buffer(len(block) + HEADER_SO_ROOM)
+    n = int(lib.h_header_coordinate(block, len(block), out, len(out)))
+    return None if n < 0 else out.raw[:n]
+
+
+def sort_key(tid: int, pos: int, flag: int) -> int:
+    """The 64-bit key of one record as the host computes it (h_sort_key; ``sort-check`` walks these)."""
+    return int(load_library().h_sort_key(tid, pos, flag))
 
 
 class Job:
@@ -340,7 +363,7 @@ def records_to_bam(in_path: str, out_path: str) -> int:
 
 
 def run_cli(args, stdout_path=None, cwd=None, env=None) -> subprocess.CompletedProcess:
-    """Run the C binary ``lr2rmats <args>`` (needs a GPU for update-gtf / bam2gtf / unique-gtf -m b / filter / bam2sj / sjtab / fusion).
+    """Run the C binary ``lr2rmats <args>`` (needs a GPU for update-gtf / bam2gtf / unique-gtf -m b / filter / bam2sj / sjtab / fusion / sort).
     ``env``: extra environment variables (L2R_CHUNK_READS, L2R_ROUTE, L2R_THREADS ...)."""
     full_env = None
     if env:
