@@ -318,6 +318,9 @@ static DevParams dev_params(const l2r_ctx *c)
     p.min_sj_cnt = c->prm.min_sj_cnt; p.split_trans = c->prm.split_trans; p.frac = c->prm.single_exon_ovlp_frac;
     p.n_tx = (int32_t)c->n_tx; p.n_sj = (int32_t)c->n_sj; p.reads_per_tile = c->reads_per_tile;
     p.ablate = c->ablate; p.want = (int32_t)c->want;
+    // (bits 9 / 10 leave the junction check to k_validate_sj: with a table no read is accepted yet when k_tile is done, so it must not place
+    //  the tile's accepted chunk itself -- bit 1: every chunk is k_gather_accepted's)
+    if (c->n_sj > 0 && (c->ablate & (512 | 1024))) p.ablate |= 2;
     return p;
 }
 
@@ -1410,7 +1413,9 @@ static int launch_tail(l2r_ctx *c, hipEvent_t *ev, const DevParams &p, const Cur
     // (one-kernel tile path: a completed run of the same inputs and parameters has left nothing on the redo list -- no read is left for
     //  the generic kernel, and the list counters need no launch for their clearing, they take turns -- and nothing to the list-driven
     //  kernels or no junction table: no read is left for the junction check either, k_tile has checked every read whose verdict it made)
-    const bool nothing_left = tile && c->facts.known && c->facts.redo_empty && (lists_empty(c->facts) || c->n_sj == 0) && !c->env_launch_all;
+    // (L2R_ABLATE bits 9 / 10 take the junction check out of k_tile: with a table every candidate is then k_validate_sj's, in every run)
+    const bool sj_left = c->n_sj > 0 && (c->ablate & (512 | 1024)) != 0;
+    const bool nothing_left = tile && c->facts.known && c->facts.redo_empty && (lists_empty(c->facts) || c->n_sj == 0) && !c->env_launch_all && !sj_left;
     end_of_run(c, tile);
     if (!nothing_left) {
         const unsigned gg = (unsigned)std::min<int64_t>(c->n_tiles ? c->n_tiles * 4 : 1, 4096);      // one wave per listed read, grid-stride
