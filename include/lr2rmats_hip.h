@@ -392,13 +392,36 @@ int          l2r_sj_stats(l2r_ctx *ctx, double *out, int n);
  * On a table begun with l2r_sj_begin, or in front of l2r_sj_finish, each of these returns an error (l2r_last_error() says which).
  * l2r_sj_stats from word 15: [15] rows the last l2r_sj_filter_rows dropped, [16] distinct annotation introns; with L2R_SJ_TIMING=1
  * device milliseconds of [17] k_sj_introns [18] k_sj_annotate [19] k_sj_keep [20] k_scan_u32 of the keep flags [21] k_sj_take
- * [22] the sort + reduce of the introns (all its kernels). */
+ * [22] the sort + reduce of the introns (all its kernels).
+ *
+ * l2r_sj_filter_rows2: l2r_sj_filter_rows and, after STAR's outSJfilterIntronMaxVsReadN and outSJfilterDistToOtherSJmin, two more rules
+ * (the project's own definition: no byte equality with a STAR release is claimed).  Categories as above; a motif above 6 counts as 0.
+ *   stage 1, row-local   the test of l2r_sj_filter_rows, and the intron-size rule: with reads = max(1, uniq_c + multi_c), a row of
+ *             category 1..4 with reads <= n_intron_max stays only if acc - don + 1 <= intron_max[reads - 1] (64-bit arithmetic);
+ *             annotated rows are exempt; n_intron_max = 0 switches the rule off
+ *   stage 2, neighbours  over exactly the rows stage 1 left, annotated ones included: dd(r) = the smallest |don(r) - don(q)| over the
+ *             OTHER rows q with r's tid, da(r) the same for acc (another row with the same coordinate: 0; no other row on the tid:
+ *             0x7fffffff; differences in 64 bits, clamped to 0x7fffffff).  A row of category c stays iff dd >= dist_min[c] and
+ *             da >= dist_min[c].  The neighbours are the rows stage 1 left: a row that stage 2 drops still counts as a neighbour of
+ *             the others, so nothing is iterated.  All five dist_min zero switch the stage off, and no sort runs.
+ * Row order is kept.  g == NULL, or all dist_min zero with n_intron_max == 0: exactly l2r_sj_filter_rows, launch for launch.
+ * n_intron_max outside 0..8, a negative dist_min or a negative intron_max entry: an error, l2r_last_error() says which.  The
+ * preconditions are those of l2r_sj_filter_rows.  The acceptor side needs the rows in (tid, acc) order: one 64-bit key per row,
+ * ordered by the radix passes of `sort` below in the context's sort buffers (a byte that is equal in every key is a pass that is not
+ * run, keys that never descend run none, L2R_SORT_FORCE=1 runs all eight); more than 2^32 - 1 - L2R_SORT_TILE rows fail before any
+ * pointer is read.
+ * l2r_sj_stats from word 23, of the last filter call (all 0 behind l2r_sj_filter_rows): [23] rows stage 2 dropped, [24] radix passes
+ * the acceptor order ran; with L2R_SJ_TIMING=1 device milliseconds of [25] k_sj_acc_keys [26] the acceptor order's passes (all their
+ * kernels) [27] k_sj_near_acc [28] k_sj_keep_near; [29] rows that passed the test of l2r_sj_filter_rows and that the intron-size rule
+ * dropped.  [15] is then the rows both stages dropped together. */
 typedef struct { int32_t anchor_min[5], uniq_min[5], all_min[5]; } l2r_sj_filter;     /* STAR: 30 12 12 12 / 3 1 1 1 / 3 1 1 1 behind the annotated one */
+typedef struct { int32_t dist_min[5]; int32_t n_intron_max; int32_t intron_max[8]; } l2r_sj_filter2;   /* STAR: 10 0 5 10 behind the annotated 0 / 50000 100000 200000 */
 typedef struct { int64_t cap, n; int32_t *tid, *don, *acc, *uniq_c, *multi_c; uint8_t *strand, *motif; uint8_t *anno; int32_t *max_over; } l2r_sj_tab;   /* l2r_sj_table + two */
 int          l2r_sj_begin_tab(l2r_ctx *ctx, const l2r_sj_params *prm, const l2r_sj_genome *genome);
 int          l2r_sj_add_rows_over(l2r_ctx *ctx, const l2r_junctions *rows, const int32_t *max_over);
 int          l2r_sj_annotate(l2r_ctx *ctx, const l2r_annotation *anno);
 int          l2r_sj_filter_rows(l2r_ctx *ctx, const l2r_sj_filter *filter, int64_t *n_rows);
+int          l2r_sj_filter_rows2(l2r_ctx *ctx, const l2r_sj_filter *filter, const l2r_sj_filter2 *filter2, int64_t *n_rows);
 int          l2r_sj_download_tab(l2r_ctx *ctx, l2r_sj_tab *table);
 
 /* ---- `sort`, `filter -S` (host/sort.c): the coordinate order of alignment records -- what `update-gtf` wants of its input and the

@@ -32,7 +32,7 @@ EXPORTS = [
     "l2r_debug_counters", "l2r_debug_stamps", "l2r_debug_tile_times", "l2r_upload_index_ms", "l2r_hint_single_run",
     "l2r_xchg_id_bytes", "l2r_xchg_unique_id", "l2r_xchg_create", "l2r_xchg_gather_results", "l2r_xchg_gather_accepted", "l2r_xchg_destroy",
     "l2r_sj_begin", "l2r_sj_add", "l2r_sj_add_rows", "l2r_sj_finish", "l2r_sj_download", "l2r_sj_stats",
-    "l2r_sj_begin_tab", "l2r_sj_add_rows_over", "l2r_sj_annotate", "l2r_sj_filter_rows", "l2r_sj_download_tab",
+    "l2r_sj_begin_tab", "l2r_sj_add_rows_over", "l2r_sj_annotate", "l2r_sj_filter_rows", "l2r_sj_download_tab", "l2r_sj_filter_rows2",
     "l2r_fusion_segments", "l2r_fusion_select", "l2r_fusion_stats",
     "l2r_sort_order", "l2r_sort_stats",
 ]
@@ -121,7 +121,12 @@ class CSjFilter(C.Structure):
     _fields_ = [("anchor_min", C.c_int32 * 5), ("uniq_min", C.c_int32 * 5), ("all_min", C.c_int32 * 5)]
 
 
+class CSjFilter2(C.Structure):
+    _fields_ = [("dist_min", C.c_int32 * 5), ("n_intron_max", C.c_int32), ("intron_max", C.c_int32 * 8)]
+
+
 SJ_FILTER_DEFAULTS = ((1, 30, 12, 12, 12), (0, 3, 1, 1, 1), (0, 3, 1, 1, 1))      # anchor, unique, total: STAR's outSJfilter* behind the annotated class
+SJ_FILTER2_STAR = ((0, 10, 0, 5, 10), (50000, 100000, 200000))                    # dist_min, intron_max: outSJfilterDistToOtherSJmin, outSJfilterIntronMaxVsReadN
 
 
 class CSortRecords(C.Structure):
@@ -199,6 +204,7 @@ def load_library():
         lib.l2r_sj_annotate.argtypes = [C.c_void_p, C.c_void_p]
         lib.l2r_sj_filter_rows.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         lib.l2r_sj_download_tab.argtypes = [C.c_void_p, C.c_void_p]
+        lib.l2r_sj_filter_rows2.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         lib.l2r_sort_order.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         lib.l2r_sort_stats.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
         _lib = lib
@@ -245,7 +251,8 @@ class SjTab(SjTable):
 SJ_STAT_NAMES = ["rows_made", "rounds", "radix_passes", "rows_in", "rows_out", "k_sj_count", "k_scan_u32 (counts)", "k_sj_fill", "k_sj_hist12",
                  "k_sj_digit_hist", "k_scan_u32 (tile histograms)", "k_sj_scatter", "k_sj_heads + scan", "k_sj_reduce", "k_sj_motif",
                  "rows_dropped", "anno_introns", "k_sj_introns", "k_sj_annotate", "k_sj_keep", "k_scan_u32 (keep flags)", "k_sj_take",
-                 "intron sort + reduce"]
+                 "intron sort + reduce", "rows_dropped_near", "acc_radix_passes", "k_sj_acc_keys", "acceptor order passes", "k_sj_near_acc",
+                 "k_sj_keep_near", "rows_dropped_long"]
 
 
 SORT_STAT_NAMES = ["rows", "radix_passes", "in_order", "k_sort_keys", "k_sort_digit_hist", "k_scan_u32 (tile histograms)", "k_sort_scatter"]
@@ -445,6 +452,17 @@ class Engine:
         f = CSjFilter((C.c_int32 * 5)(*[int(v) for v in anchor_min]), (C.c_int32 * 5)(*[int(v) for v in uniq_min]), (C.c_int32 * 5)(*[int(v) for v in all_min]))
         n = C.c_int64(0)
         self._chk(self.lib.l2r_sj_filter_rows(self.ctx, C.byref(f), C.byref(n)))
+        return self.sj_download_tab(int(n.value))
+
+    def sj_filter_rows2(self, anchor_min=SJ_FILTER_DEFAULTS[0], uniq_min=SJ_FILTER_DEFAULTS[1], all_min=SJ_FILTER_DEFAULTS[2], dist_min=(0,) * 5,
+                        intron_max=()) -> SjTab:
+        """l2r_sj_filter_rows2: sj_filter_rows and the intron-size rule (``intron_max``, up to eight lengths) and the distance to the
+        nearest other donor and acceptor (``dist_min``); SJ_FILTER2_STAR holds STAR's defaults for the two."""
+        f = CSjFilter((C.c_int32 * 5)(*[int(v) for v in anchor_min]), (C.c_int32 * 5)(*[int(v) for v in uniq_min]), (C.c_int32 * 5)(*[int(v) for v in all_min]))
+        lens = [int(v) for v in intron_max]
+        g = CSjFilter2((C.c_int32 * 5)(*[int(v) for v in dist_min]), len(lens), (C.c_int32 * 8)(*lens[:8]))
+        n = C.c_int64(0)
+        self._chk(self.lib.l2r_sj_filter_rows2(self.ctx, C.byref(f), C.byref(g), C.byref(n)))
         return self.sj_download_tab(int(n.value))
 
     def sj_stats(self) -> dict:

@@ -101,9 +101,10 @@ struct SjState {
     int64_t n_rows = 0;                     // rows[cur] holds that many
     int64_t compact_rows = (int64_t)1 << 24, compact_at = (int64_t)1 << 24;     // L2R_SJ_COMPACT_ROWS: rows beyond which an add sorts and reduces what is there
     DevBuf<uint16_t> flag; DevBuf<int32_t> tid, pos; DevBuf<uint8_t> uniq; DevBuf<int64_t> cig_off; DevBuf<uint32_t> cig, cnt;   // one batch
-    DevBuf<uint32_t> hist12, tile_hist, head, word;     // word[0]: a scan's total, word[1]: k_sj_motif's bad row, word[2]: k_sj_introns' row count
+    DevBuf<uint32_t> hist12, tile_hist, head, word;     // word[0]: a scan's total, word[1]: k_sj_motif's bad row, word[2]: k_sj_introns' row count, word[3]: rows the intron-size rule dropped
     DevBuf<uint8_t> strand[2], motif[2], anno[2]; int bcur = 0;      // per-row bytes; the filter moves them to the other set
-    double stats[24] = {0};
+    DevBuf<int32_t> near_acc;               // l2r_sj_filter_rows2: per row the distance to the nearest other acceptor
+    double stats[32] = {0};
     hipEvent_t ev[2] = {nullptr, nullptr};
     ~SjState() { for (int k = 0; k < 2; ++k) if (ev[k]) (void)hipEventDestroy(ev[k]); }
 };
@@ -2054,8 +2055,13 @@ template <typename F> static int sj_launch(l2r_ctx *c, SjState &s, int slot, F f
 }
 }
 
+// slots of l2r_sort_stats (the acceptor order of `sjtab` runs the passes of `sort`)
+enum { SORTS_ROWS = 0, SORTS_PASSES, SORTS_IN_ORDER, SORTS_K_KEYS, SORTS_K_HIST, SORTS_K_SCAN, SORTS_K_SCATTER, SORTS_N };
+
 // slots of l2r_sj_stats behind the fifteen of `bam2sj`
-enum { SJS_DROPPED = 15, SJS_INTRONS, SJS_K_INTRONS, SJS_K_ANNOTATE, SJS_K_KEEP, SJS_K_KEEP_SCAN, SJS_K_TAKE, SJS_INTRON_SORT, SJS_N };
+enum { SJS_DROPPED = 15, SJS_INTRONS, SJS_K_INTRONS, SJS_K_ANNOTATE, SJS_K_KEEP, SJS_K_KEEP_SCAN, SJS_K_TAKE, SJS_INTRON_SORT,
+       SJS_NEAR_DROPPED, SJS_ACC_PASSES, SJS_K_ACC_KEYS, SJS_K_ACC_ORDER, SJS_K_NEAR_ACC, SJS_K_KEEP_NEAR, SJS_LONG_DROPPED, SJS_N };
+static_assert(SJS_NEAR_DROPPED == 23 && SJS_N <= 32, "l2r_sj_stats: the words of include/lr2rmats_hip.h");
 
 // room for `want` rows; the first `keep` rows stay (DevBuf::ensure carries nothing over, so the columns are moved here)
 static int sj_rows_reserve(l2r_ctx *c, const SjState &s, SjRowBuf &b, size_t want, size_t keep)
@@ -2343,30 +2349,17 @@ int l2r_sj_annotate(l2r_ctx *c, const l2r_annotation *a)
     return 0;
 }
 
-int l2r_sj_filter_rows(l2r_ctx *c, const l2r_sj_filter *f, int64_t *n_rows)
+// keep words in s.head -> their scan -> the kept rows in the other row buffer and byte set, which become the current ones; *kept_out = rows left
+static int sj_take_kept(l2r_ctx *c, SjState &s, uint32_t n, const char *who, uint32_t *kept_out)
 {
-    if (!c || !f || !n_rows) return fail(-1, "[l2r_sj_filter_rows] null argument");
     int rc;
-    if ((rc = sj_tab_ready(c, "l2r_sj_filter_rows"))) return rc;
-    HIP_TRY(hipSetDevice(c->device));
-    SjState &s = c->sj;
-    const uint32_t n = (uint32_t)s.n_rows;
-    s.stats[SJS_DROPPED] = 0;
-    *n_rows = s.n_rows;
-    if (!n) return 0;
-    SjFilter flt;
-    for (int k = 0; k < 5; ++k) { flt.anchor_min[k] = f->anchor_min[k]; flt.uniq_min[k] = f->uniq_min[k]; flt.all_min[k] = f->all_min[k]; }
     const unsigned grid = (n + SJ_THREADS - 1) / SJ_THREADS;
     const int bsrc = s.bcur, bdst = 1 - s.bcur, src = s.cur, dst = 1 - s.cur;
-    if (s.head.ensure((size_t)n + 1) || s.strand[bdst].ensure(n) || s.motif[bdst].ensure(n) || s.anno[bdst].ensure(n)) return -2;
-    if ((rc = sj_rows_reserve(c, s, s.rows[dst], n, 0))) return rc;
-    if ((rc = sj_launch(c, s, SJS_K_KEEP, [&] { hipLaunchKernelGGL(k_sj_keep, dim3(grid), dim3(SJ_THREADS), 0, c->stream, s.rows[src].cols(), (const uint8_t *)s.motif[bsrc].p,
-                                                                   (const uint8_t *)s.anno[bsrc].p, n, flt, s.head.p); }))) return rc;
     if ((rc = sj_scan(c, s, SJS_K_KEEP_SCAN, s.head.p, (int64_t)n))) return rc;
     uint32_t kept = 0;
     HIP_TRY(hipMemcpyAsync(&kept, s.word.p, 4, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
-    if (kept > n) return fail(-2, "[l2r_sj_filter_rows] %u of %u rows kept", kept, n);
+    if (kept > n) return fail(-2, "[%s] %u of %u rows kept", who, kept, n);
     if (kept) {
         const SjBytes bin{s.strand[bsrc].p, s.motif[bsrc].p, s.anno[bsrc].p}, bout{s.strand[bdst].p, s.motif[bdst].p, s.anno[bdst].p};
         if ((rc = sj_launch(c, s, SJS_K_TAKE, [&] { hipLaunchKernelGGL(k_sj_take, dim3(grid), dim3(SJ_THREADS), 0, c->stream, s.rows[src].cols(), bin, n, (const uint32_t *)s.head.p,
@@ -2374,9 +2367,147 @@ int l2r_sj_filter_rows(l2r_ctx *c, const l2r_sj_filter *f, int64_t *n_rows)
         HIP_TRY(hipStreamSynchronize(c->stream));
     }
     s.cur = dst; s.bcur = bdst; s.n_rows = kept;
-    s.stats[SJS_DROPPED] = (double)(n - kept);
-    *n_rows = kept;
+    *kept_out = kept;
     return 0;
+}
+
+// room for the keep words and for the rows a filter stage leaves
+static int sj_filter_reserve(l2r_ctx *c, SjState &s, uint32_t n)
+{
+    const int bdst = 1 - s.bcur;
+    if (s.head.ensure((size_t)n + 1) || s.strand[bdst].ensure(n) || s.motif[bdst].ensure(n) || s.anno[bdst].ensure(n)) return -2;
+    return sj_rows_reserve(c, s, s.rows[1 - s.cur], n, 0);
+}
+
+// The row-local stage of both filter calls.  g: the intron-size rule as well (the INTRON instance of k_sj_keep), or null: the launches
+// of l2r_sj_filter_rows.  *n_long: rows the intron-size rule alone dropped.
+static int sj_filter_local(l2r_ctx *c, const l2r_sj_filter *f, const SjFilter2 *g, const char *who, uint32_t *n_long)
+{
+    SjState &s = c->sj;
+    const uint32_t n = (uint32_t)s.n_rows;
+    *n_long = 0;
+    SjFilter flt;
+    for (int k = 0; k < 5; ++k) { flt.anchor_min[k] = f->anchor_min[k]; flt.uniq_min[k] = f->uniq_min[k]; flt.all_min[k] = f->all_min[k]; }
+    const unsigned grid = (n + SJ_THREADS - 1) / SJ_THREADS;
+    int rc;
+    if ((rc = sj_filter_reserve(c, s, n))) return rc;
+    const SjFilter2 none = {};
+    if (g) HIP_TRY(hipMemsetAsync(s.word.p + 3, 0, 4, c->stream));
+    if ((rc = sj_launch(c, s, SJS_K_KEEP, [&] {
+            if (g) hipLaunchKernelGGL(k_sj_keep<true>, dim3(grid), dim3(SJ_THREADS), 0, c->stream, s.rows[s.cur].cols(), (const uint8_t *)s.motif[s.bcur].p,
+                                      (const uint8_t *)s.anno[s.bcur].p, n, flt, *g, s.head.p, s.word.p + 3);
+            else hipLaunchKernelGGL(k_sj_keep<false>, dim3(grid), dim3(SJ_THREADS), 0, c->stream, s.rows[s.cur].cols(), (const uint8_t *)s.motif[s.bcur].p,
+                                    (const uint8_t *)s.anno[s.bcur].p, n, flt, none, s.head.p, (uint32_t *)nullptr);
+        }))) return rc;
+    if (g) HIP_TRY(hipMemcpyAsync(n_long, s.word.p + 3, 4, hipMemcpyDeviceToHost, c->stream));      // (waited for with the scan's total)
+    uint32_t kept = 0;
+    return sj_take_kept(c, s, n, who, &kept);
+}
+
+int l2r_sj_filter_rows(l2r_ctx *c, const l2r_sj_filter *f, int64_t *n_rows)
+{
+    if (!c || !f || !n_rows) return fail(-1, "[l2r_sj_filter_rows] null argument");
+    int rc;
+    if ((rc = sj_tab_ready(c, "l2r_sj_filter_rows"))) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    SjState &s = c->sj;
+    const int64_t n = s.n_rows;
+    for (int k = SJS_NEAR_DROPPED; k < SJS_N; ++k) s.stats[k] = 0;
+    s.stats[SJS_DROPPED] = 0;
+    *n_rows = s.n_rows;
+    if (!n) return 0;
+    uint32_t n_long = 0;
+    if ((rc = sj_filter_local(c, f, nullptr, "l2r_sj_filter_rows", &n_long))) return rc;
+    s.stats[SJS_DROPPED] = (double)(n - s.n_rows);
+    *n_rows = s.n_rows;
+    return 0;
+}
+
+static int sort_passes(l2r_ctx *c, SortState &s, uint32_t n, int *n_pass_out, bool *in_order_out, int *src_out);
+
+// The neighbour stage over the rows the row-local stage left (s.rows[s.cur], sorted by (tid, don, acc)).
+static int sj_filter_near(l2r_ctx *c, const SjFilter2 &g)
+{
+    SjState &s = c->sj;
+    SortState &o = c->sort;
+    const uint32_t n = (uint32_t)s.n_rows;
+    if (!n) return 0;
+    const unsigned grid = (n + SJ_THREADS - 1) / SJ_THREADS;
+    int rc;
+    if ((rc = sj_filter_reserve(c, s, n))) return rc;
+    if (s.near_acc.ensure(n) || o.key[0].ensure(n) || o.hist.ensure(SORT_KEY_BYTES * 256 + 1) || o.word.ensure(4)) return -2;
+    for (int k = 0; k < 2; ++k) if (!o.ev[k]) HIP_TRY(hipEventCreate(&o.ev[k]));
+    const SjCols t = s.rows[s.cur].cols();
+    HIP_TRY(hipMemsetAsync(o.hist.p, 0, (SORT_KEY_BYTES * 256 + 1) * sizeof(uint32_t), c->stream));
+    if ((rc = sj_launch(c, s, SJS_K_ACC_KEYS, [&] {
+            hipLaunchKernelGGL(k_sj_acc_keys, dim3(std::min(grid, 2048u)), dim3(SJ_THREADS), 0, c->stream, (const int32_t *)t.tid, (const int32_t *)t.acc, n, o.key[0].p, o.hist.p,
+                               o.hist.p + SORT_KEY_BYTES * 256);
+        }))) return rc;
+    // the passes are those of `sort`, in its buffers; what l2r_sort_stats says of the last l2r_sort_order stays
+    double sort_stats[sizeof o.stats / sizeof o.stats[0]];
+    const bool sort_timing = o.timing;
+    std::copy(std::begin(o.stats), std::end(o.stats), sort_stats);
+    for (double &v : o.stats) v = 0;
+    o.timing = s.timing;
+    int n_pass = 0, src = 0; bool in_order = false;
+    rc = sort_passes(c, o, n, &n_pass, &in_order, &src);
+    s.stats[SJS_K_ACC_ORDER] += o.stats[SORTS_K_HIST] + o.stats[SORTS_K_SCAN] + o.stats[SORTS_K_SCATTER];
+    std::copy(std::begin(sort_stats), std::end(sort_stats), o.stats);
+    o.timing = sort_timing;
+    if (rc) return rc;
+    s.stats[SJS_ACC_PASSES] = n_pass;
+    const uint32_t *idx = n_pass ? o.idx[src].p : nullptr;
+    if ((rc = sj_launch(c, s, SJS_K_NEAR_ACC, [&] {
+            hipLaunchKernelGGL(k_sj_near_acc, dim3(grid), dim3(SJ_THREADS), 0, c->stream, (const int32_t *)t.tid, (const int32_t *)t.acc, idx, n, s.near_acc.p);
+        }))) return rc;
+    if ((rc = sj_launch(c, s, SJS_K_KEEP_NEAR, [&] {
+            hipLaunchKernelGGL(k_sj_keep_near, dim3(grid), dim3(SJ_THREADS), 0, c->stream, (const int32_t *)t.tid, (const int32_t *)t.don, (const int32_t *)s.near_acc.p,
+                               (const uint8_t *)s.motif[s.bcur].p, (const uint8_t *)s.anno[s.bcur].p, n, g, s.head.p);
+        }))) return rc;
+    uint32_t kept = 0;
+    if ((rc = sj_take_kept(c, s, n, "l2r_sj_filter_rows2", &kept))) return rc;
+    s.stats[SJS_NEAR_DROPPED] = (double)(n - kept);
+    return 0;
+}
+
+int l2r_sj_filter_rows2(l2r_ctx *c, const l2r_sj_filter *f, const l2r_sj_filter2 *g, int64_t *n_rows)
+{
+    if (!c || !f || !n_rows) return fail(-1, "[l2r_sj_filter_rows2] null argument");
+    int rc;
+    if ((rc = sj_tab_ready(c, "l2r_sj_filter_rows2"))) return rc;
+    SjFilter2 flt = {};
+    bool near = false;
+    if (g) {
+        if (g->n_intron_max < 0 || g->n_intron_max > 8) return fail(-1, "[l2r_sj_filter_rows2] n_intron_max = %d: the list holds 0 to 8 lengths", g->n_intron_max);
+        for (int k = 0; k < 5; ++k) {
+            if (g->dist_min[k] < 0) return fail(-1, "[l2r_sj_filter_rows2] dist_min[%d] = %d: a distance is not negative", k, g->dist_min[k]);
+            flt.dist_min[k] = g->dist_min[k]; near |= g->dist_min[k] != 0;
+        }
+        for (int k = 0; k < g->n_intron_max; ++k) {
+            if (g->intron_max[k] < 0) return fail(-1, "[l2r_sj_filter_rows2] intron_max[%d] = %d: a length is not negative", k, g->intron_max[k]);
+            flt.intron_max[k] = g->intron_max[k];
+        }
+        flt.n_intron_max = g->n_intron_max;
+    }
+    SjState &s = c->sj;
+    if (s.n_rows > (int64_t)0xffffffffll - L2R_SORT_TILE)
+        return fail(-1, "[l2r_sj_filter_rows2] %lld rows: the acceptor order takes 2^32 - 1 - %d at most (the index of a row is a 32-bit word)", (long long)s.n_rows, L2R_SORT_TILE);
+    if (!near && flt.n_intron_max == 0) return l2r_sj_filter_rows(c, f, n_rows);
+    HIP_TRY(hipSetDevice(c->device));
+    const int64_t n = s.n_rows;
+    for (int k = SJS_NEAR_DROPPED; k < SJS_N; ++k) s.stats[k] = 0;
+    s.stats[SJS_DROPPED] = 0;
+    *n_rows = s.n_rows;
+    if (!n) return 0;
+    if (s.word.ensure(4)) return -2;
+    uint32_t n_long = 0;
+    rc = sj_filter_local(c, f, flt.n_intron_max ? &flt : nullptr, "l2r_sj_filter_rows2", &n_long);
+    if (!rc && near) rc = sj_filter_near(c, flt);
+    // (a failure behind the first stage leaves that stage's table, and the words say so)
+    s.stats[SJS_LONG_DROPPED] = (double)n_long;
+    s.stats[SJS_DROPPED] = (double)(n - s.n_rows);
+    *n_rows = s.n_rows;
+    return rc;
 }
 
 static int sj_download(l2r_ctx *c, int64_t cap, int64_t *n_out, int32_t *const dst[6], uint8_t *const bytes[3], const char *who)
@@ -2445,55 +2576,30 @@ template <typename F> static int sort_launch(l2r_ctx *c, SortState &s, int slot,
 }
 }
 
-enum { SORTS_ROWS = 0, SORTS_PASSES, SORTS_IN_ORDER, SORTS_K_KEYS, SORTS_K_HIST, SORTS_K_SCAN, SORTS_K_SCATTER, SORTS_N };
-
-int l2r_sort_order(l2r_ctx *c, const l2r_sort_records *r, uint32_t *order_out)
+// The radix passes over the keys in s.key[0][0, n), behind a keys kernel that left the histograms of the eight key bytes and the descent
+// word in s.hist: l2r_sort_order's, and the acceptor order of l2r_sj_filter_rows2.  A byte that is equal in every key is a pass that is
+// not run, keys that never descend run none (L2R_SORT_FORCE=1: all eight, whatever the keys).  *n_pass_out: passes run; the order is
+// then in s.idx[*src_out], and with no pass it is the identity and no index column is written.
+static int sort_passes(l2r_ctx *c, SortState &s, uint32_t n, int *n_pass_out, bool *in_order_out, int *src_out)
 {
-    if (!c || !r) return fail(-1, "[l2r_sort_order] null argument");
-    SortState &s = c->sort;
-    for (double &v : s.stats) v = 0;
-    if (r->n < 0) return fail(-1, "[l2r_sort_order] %lld records", (long long)r->n);
-    if (r->n > (int64_t)0xffffffffll - L2R_SORT_TILE)
-        return fail(-1, "[l2r_sort_order] %lld records: one sort takes 2^32 - 1 - %d at most (the index of a record is a 32-bit word)", (long long)r->n, L2R_SORT_TILE);
-    if (r->n == 0) { s.stats[SORTS_IN_ORDER] = 1; return 0; }
-    if (!r->flag || !r->tid || !r->pos || !order_out) return fail(-1, "[l2r_sort_order] null column");
-    const char *e = getenv("L2R_SORT_TIMING");
-    s.timing = e && atoi(e) != 0;
-    e = getenv("L2R_SORT_FORCE");
+    const char *e = getenv("L2R_SORT_FORCE");
     const bool force = e && atoi(e) != 0;
-    HIP_TRY(hipSetDevice(c->device));
-    for (int k = 0; k < 2; ++k) if (!s.ev[k]) HIP_TRY(hipEventCreate(&s.ev[k]));
-    const size_t N = (size_t)r->n;
-    const uint32_t n = (uint32_t)r->n;
+    const size_t N = n;
     const uint32_t n_tiles = (uint32_t)((N + SORT_TILE - 1) / SORT_TILE);
-    s.stats[SORTS_ROWS] = (double)r->n;
-    int rc;
-    if ((rc = to_dev(c, s.flag, r->flag, N)) || (rc = to_dev(c, s.tid, r->tid, N)) || (rc = to_dev(c, s.pos, r->pos, N))) return rc;
-    if (s.key[0].ensure(N) || s.hist.ensure(SORT_KEY_BYTES * 256 + 1) || s.word.ensure(4)) return -2;
-    // the keys, which of their bytes differ at all, whether they descend anywhere
     uint32_t h8[SORT_KEY_BYTES * 256 + 1];
-    HIP_TRY(hipMemsetAsync(s.hist.p, 0, sizeof h8, c->stream));
-    const unsigned grid = (unsigned)std::min<size_t>((N + SORT_THREADS - 1) / SORT_THREADS, 2048);
-    const SortRecs recs{r->n, s.flag.p, s.tid.p, s.pos.p};
-    if ((rc = sort_launch(c, s, SORTS_K_KEYS, [&] {
-            hipLaunchKernelGGL(k_sort_keys, dim3(grid), dim3(SORT_THREADS), 0, c->stream, recs, s.key[0].p, s.hist.p, s.hist.p + SORT_KEY_BYTES * 256);
-        }))) return rc;
     HIP_TRY(hipMemcpyAsync(h8, s.hist.p, sizeof h8, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     const bool in_order = h8[SORT_KEY_BYTES * 256] == 0u;
-    s.stats[SORTS_IN_ORDER] = in_order ? 1 : 0;
     int pass_byte[SORT_KEY_BYTES], n_pass = 0;
     for (int b = 0; b < SORT_KEY_BYTES; ++b) {
         bool one_value = false;
         for (int d = 0; d < 256; ++d) if (h8[b * 256 + d] == n) { one_value = true; break; }
         if (force || (!in_order && !one_value)) pass_byte[n_pass++] = b;
     }
-    if (n_pass == 0) {                                              // (keys that never descend: the order is the identity)
-        for (size_t i = 0; i < N; ++i) order_out[i] = (uint32_t)i;
-        return 0;
-    }
+    *n_pass_out = n_pass; *in_order_out = in_order; *src_out = 0;
+    if (n_pass == 0) return 0;
     if (s.idx[0].ensure(N) || s.idx[1].ensure(N) || (n_pass > 1 && s.key[1].ensure(N)) || s.tile_hist.ensure((size_t)256 * n_tiles + 1)) return -2;
-    int src = 0;
+    int rc, src = 0;
     for (int p = 0; p < n_pass; ++p) {
         const int b = pass_byte[p];
         const bool first = p == 0, last = p == n_pass - 1;
@@ -2508,6 +2614,44 @@ int l2r_sort_order(l2r_ctx *c, const l2r_sort_records *r, uint32_t *order_out)
 #undef SORT_SCATTER
             }))) return rc;
         src = 1 - src;
+    }
+    *src_out = src;
+    return 0;
+}
+
+int l2r_sort_order(l2r_ctx *c, const l2r_sort_records *r, uint32_t *order_out)
+{
+    if (!c || !r) return fail(-1, "[l2r_sort_order] null argument");
+    SortState &s = c->sort;
+    for (double &v : s.stats) v = 0;
+    if (r->n < 0) return fail(-1, "[l2r_sort_order] %lld records", (long long)r->n);
+    if (r->n > (int64_t)0xffffffffll - L2R_SORT_TILE)
+        return fail(-1, "[l2r_sort_order] %lld records: one sort takes 2^32 - 1 - %d at most (the index of a record is a 32-bit word)", (long long)r->n, L2R_SORT_TILE);
+    if (r->n == 0) { s.stats[SORTS_IN_ORDER] = 1; return 0; }
+    if (!r->flag || !r->tid || !r->pos || !order_out) return fail(-1, "[l2r_sort_order] null column");
+    const char *e = getenv("L2R_SORT_TIMING");
+    s.timing = e && atoi(e) != 0;
+    HIP_TRY(hipSetDevice(c->device));
+    for (int k = 0; k < 2; ++k) if (!s.ev[k]) HIP_TRY(hipEventCreate(&s.ev[k]));
+    const size_t N = (size_t)r->n;
+    const uint32_t n = (uint32_t)r->n;
+    s.stats[SORTS_ROWS] = (double)r->n;
+    int rc;
+    if ((rc = to_dev(c, s.flag, r->flag, N)) || (rc = to_dev(c, s.tid, r->tid, N)) || (rc = to_dev(c, s.pos, r->pos, N))) return rc;
+    if (s.key[0].ensure(N) || s.hist.ensure(SORT_KEY_BYTES * 256 + 1) || s.word.ensure(4)) return -2;
+    // the keys, which of their bytes differ at all, whether they descend anywhere
+    HIP_TRY(hipMemsetAsync(s.hist.p, 0, (SORT_KEY_BYTES * 256 + 1) * sizeof(uint32_t), c->stream));
+    const unsigned grid = (unsigned)std::min<size_t>((N + SORT_THREADS - 1) / SORT_THREADS, 2048);
+    const SortRecs recs{r->n, s.flag.p, s.tid.p, s.pos.p};
+    if ((rc = sort_launch(c, s, SORTS_K_KEYS, [&] {
+            hipLaunchKernelGGL(k_sort_keys, dim3(grid), dim3(SORT_THREADS), 0, c->stream, recs, s.key[0].p, s.hist.p, s.hist.p + SORT_KEY_BYTES * 256);
+        }))) return rc;
+    int n_pass = 0, src = 0; bool in_order = false;
+    if ((rc = sort_passes(c, s, n, &n_pass, &in_order, &src))) return rc;
+    s.stats[SORTS_IN_ORDER] = in_order ? 1 : 0;
+    if (n_pass == 0) {                                              // (keys that never descend: the order is the identity)
+        for (size_t i = 0; i < N; ++i) order_out[i] = (uint32_t)i;
+        return 0;
     }
     s.stats[SORTS_PASSES] = n_pass;
     HIP_TRY(hipMemcpyAsync(order_out, s.idx[src].p, N * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));

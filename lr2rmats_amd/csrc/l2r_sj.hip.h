@@ -23,6 +23,15 @@
 //   k_sj_annotate            per table row: binary search in the sorted intron keys -> anno 0 / 1
 //   k_sj_keep / k_sj_take    the filter by category (annotated, or by motif) -> k_scan_u32 -> the nine columns of the kept rows, in order
 //
+// The second filter stage of `sjtab` (l2r_sj_filter_rows2; the rule is in include/lr2rmats_hip.h).  k_sj_keep has an INTRON instance that
+// applies the intron-size rule as well; the plain instance is the code above, unchanged.  Over the rows that instance left:
+//   k_sj_acc_keys            per row one 64-bit key (tid, acc) for the radix passes of l2r_sort.hip.h, the histograms of its eight bytes
+//                            and one word that says whether any key is below its predecessor (none: no pass runs)
+//   k_sj_near_acc            per position of the acceptor order: the distance to the nearest other acceptor on the reference, from
+//                            the two neighbours in that order (adjacent lanes by shuffles), written to the row's own slot
+//   k_sj_keep_near           per row in table order: the distance to the nearest other donor from rows i - 1 and i + 1 (the table is in
+//                            donor order inside a reference), the acceptor distance from the column above -> the keep words
+//
 // LSD radix with 8-bit digits over the 12-byte key (tid, don, acc), least significant byte of acc first; signed order (the top byte of
 // every column is compared with its sign bit flipped).  HBM-bound integer work: a pass reads and writes 20 bytes per row.  No kernel
 // waits for another workgroup.
@@ -338,17 +347,130 @@ void k_sj_annotate(const int32_t *__restrict__ tid, const int32_t *__restrict__ 
 }
 
 struct SjFilter { int32_t anchor_min[5], uniq_min[5], all_min[5]; };
+struct SjFilter2 { int32_t dist_min[5], n_intron_max, intron_max[8]; };
 
 // category: annotated 0; else by motif: 0 -> 1, 1 2 -> 2, 3 4 -> 3, 5 6 -> 4.  keep has n + 1 words for the scan.
+// INTRON: a row of category 1..4 seen by reads = max(1, uniq_c + multi_c) <= n_intron_max records stays only where its intron is no
+// longer than intron_max[reads - 1]; *n_long counts the rows that this rule alone drops (one atomic per wave).
+template <bool INTRON>
 __global__ __launch_bounds__(SJ_THREADS)
-void k_sj_keep(SjCols in, const uint8_t *__restrict__ motif, const uint8_t *__restrict__ anno, uint32_t n, SjFilter f, uint32_t *__restrict__ keep)
+void k_sj_keep(SjCols in, const uint8_t *__restrict__ motif, const uint8_t *__restrict__ anno, uint32_t n, SjFilter f, SjFilter2 g, uint32_t *__restrict__ keep,
+               uint32_t *__restrict__ n_long)
+{
+    const uint32_t i = blockIdx.x * SJ_THREADS + threadIdx.x;
+    if constexpr (!INTRON) {
+        if (i >= n) return;
+        const uint32_t mo = motif[i];
+        const int c = anno[i] ? 0 : mo == 0u ? 1 : mo > 6u ? 1 : (int)((mo + 1u) / 2u) + 1;
+        const int64_t u = in.uq[i], all = (int64_t)in.uq[i] + in.mc[i];
+        keep[i] = (in.ov[i] >= f.anchor_min[c] && (u >= f.uniq_min[c] || all >= f.all_min[c])) ? 1u : 0u;
+    } else {
+        bool stays = false, too_long = false;
+        if (i < n) {
+            const uint32_t mo = motif[i];
+            const int c = anno[i] ? 0 : mo == 0u ? 1 : mo > 6u ? 1 : (int)((mo + 1u) / 2u) + 1;
+            const int64_t u = in.uq[i], all = (int64_t)in.uq[i] + in.mc[i];
+            stays = in.ov[i] >= f.anchor_min[c] && (u >= f.uniq_min[c] || all >= f.all_min[c]);
+            const int64_t reads = all > 1 ? all : 1, len = (int64_t)in.acc[i] - in.don[i] + 1;
+            if (c != 0 && reads <= g.n_intron_max) {
+                int64_t lim = 0;
+#pragma unroll
+                for (int k = 0; k < 8; ++k) if (reads == k + 1) lim = g.intron_max[k];        // (constant indices: the list stays in scalar registers)
+                too_long = len > lim;
+            }
+            keep[i] = (stays && !too_long) ? 1u : 0u;
+        }
+        const unsigned long long hit = __ballot(stays && too_long);
+        if (hit && (threadIdx.x & 63) == 0) atomicAdd(n_long, (uint32_t)__popcll(hit));
+    }
+}
+
+// the (tid, acc) key of the acceptor order: each column with its sign bit flipped, as sj_digit has it
+__device__ __forceinline__ uint64_t sj_acc_key(int32_t tid, int32_t acc)
+{
+    return ((uint64_t)((uint32_t)tid ^ 0x80000000u) << 32) | (uint64_t)((uint32_t)acc ^ 0x80000000u);
+}
+
+// hist: 8 x 256 words and *descends, cleared by the caller (the layout k_sort_keys leaves: the passes of l2r_sort.hip.h read it).
+// A wave whose 64 keys share a byte adds 64 to one word instead of 64 times 1.
+__global__ __launch_bounds__(SJ_THREADS)
+void k_sj_acc_keys(const int32_t *__restrict__ tid, const int32_t *__restrict__ acc, uint32_t n, uint64_t *__restrict__ key, uint32_t *__restrict__ hist,
+                   uint32_t *__restrict__ descends)
+{
+    __shared__ uint32_t s_h[8 * 256];
+    for (int k = threadIdx.x; k < 8 * 256; k += SJ_THREADS) s_h[k] = 0u;
+    __syncthreads();
+    const int lane = threadIdx.x & 63;
+    bool down = false;
+    for (uint64_t base = (uint64_t)blockIdx.x * SJ_THREADS; base < n; base += (uint64_t)gridDim.x * SJ_THREADS) {      // (uniform)
+        const uint64_t i = base + threadIdx.x;
+        const bool active = i < n;
+        uint64_t k = 0;
+        if (active) { k = sj_acc_key(tid[i], acc[i]); key[i] = k; }
+        uint64_t prev = (uint64_t)__shfl_up((unsigned long long)k, 1, 64);
+        if (lane == 0 && active && i > 0) prev = sj_acc_key(tid[i - 1], acc[i - 1]);
+        down |= active && i > 0 && k < prev;
+        const bool whole = __ballot(active) == ~0ull;
+#pragma unroll
+        for (int b = 0; b < 8; ++b) {
+            const uint32_t d = (uint32_t)(k >> (8 * b)) & 0xffu;
+            if (whole && __all(d == (uint32_t)__builtin_amdgcn_readfirstlane((int)d))) { if (lane == 0) atomicAdd(&s_h[b * 256 + d], 64u); }
+            else if (active) atomicAdd(&s_h[b * 256 + d], 1u);
+        }
+    }
+    if (__any(down) && lane == 0) atomicOr(descends, 1u);
+    __syncthreads();
+    for (int k = threadIdx.x; k < 8 * 256; k += SJ_THREADS) { const uint32_t v = s_h[k]; if (v) atomicAdd(&hist[k], v); }
+}
+
+constexpr int32_t SJ_FAR = 0x7fffffff;                   // no other row on the reference
+
+__device__ __forceinline__ int32_t sj_gap(int32_t a, int32_t b)
+{
+    const int64_t d = (int64_t)a - (int64_t)b, m = d < 0 ? -d : d;
+    return m < (int64_t)SJ_FAR ? (int32_t)m : SJ_FAR;
+}
+
+// idx: the acceptor order (idx[j] = row at rank j), or null where the rows are in that order as they stand.  Thread j holds the row at
+// rank j; its neighbours at ranks j - 1 and j + 1 sit in the adjacent lanes, and only the first and the last lane of a wave load theirs.
+// The last radix pass writes the index column alone, so there is no sorted key column to read the neighbours from.
+__global__ __launch_bounds__(SJ_THREADS)
+void k_sj_near_acc(const int32_t *__restrict__ tid, const int32_t *__restrict__ acc, const uint32_t *__restrict__ idx, uint32_t n, int32_t *__restrict__ da)
+{
+    const uint32_t j = blockIdx.x * SJ_THREADS + threadIdx.x;
+    const int lane = threadIdx.x & 63;
+    const bool active = j < n;
+    uint32_t r = 0; int32_t t = 0, a = 0;
+    if (active) { r = idx ? idx[j] : j; if (r >= n) r = n - 1u; t = tid[r]; a = acc[r]; }
+    int32_t pt = __shfl_up(t, 1, 64), pa = __shfl_up(a, 1, 64), nt = __shfl_down(t, 1, 64), na = __shfl_down(a, 1, 64);
+    if (!active) return;
+    const bool has_prev = j > 0u, has_next = j + 1u < n;
+    if (lane == 0 && has_prev) { uint32_t q = idx ? idx[j - 1u] : j - 1u; if (q >= n) q = n - 1u; pt = tid[q]; pa = acc[q]; }
+    if (lane == 63 && has_next) { uint32_t q = idx ? idx[j + 1u] : j + 1u; if (q >= n) q = n - 1u; nt = tid[q]; na = acc[q]; }
+    int32_t d = SJ_FAR;
+    if (has_prev && pt == t) d = sj_gap(a, pa);
+    if (has_next && nt == t) { const int32_t e = sj_gap(na, a); d = e < d ? e : d; }
+    da[r] = d;
+}
+
+// A row of category c stays iff both distances are at least dist_min[c].  Rows i - 1 and i + 1 hold the nearest other donors of the
+// reference: the table is sorted by (tid, don, acc).  keep has n + 1 words for the scan.
+__global__ __launch_bounds__(SJ_THREADS)
+void k_sj_keep_near(const int32_t *__restrict__ tid, const int32_t *__restrict__ don, const int32_t *__restrict__ da, const uint8_t *__restrict__ motif,
+                    const uint8_t *__restrict__ anno, uint32_t n, SjFilter2 g, uint32_t *__restrict__ keep)
 {
     const uint32_t i = blockIdx.x * SJ_THREADS + threadIdx.x;
     if (i >= n) return;
     const uint32_t mo = motif[i];
     const int c = anno[i] ? 0 : mo == 0u ? 1 : mo > 6u ? 1 : (int)((mo + 1u) / 2u) + 1;
-    const int64_t u = in.uq[i], all = (int64_t)in.uq[i] + in.mc[i];
-    keep[i] = (in.ov[i] >= f.anchor_min[c] && (u >= f.uniq_min[c] || all >= f.all_min[c])) ? 1u : 0u;
+    int32_t lim = 0;
+#pragma unroll
+    for (int k = 0; k < 5; ++k) if (c == k) lim = g.dist_min[k];
+    const int32_t t = tid[i], d = don[i];
+    int32_t dd = SJ_FAR;
+    if (i > 0u && tid[i - 1u] == t) dd = sj_gap(d, don[i - 1u]);
+    if (i + 1u < n && tid[i + 1u] == t) { const int32_t e = sj_gap(don[i + 1u], d); dd = e < dd ? e : dd; }
+    keep[i] = (dd >= lim && da[i] >= lim) ? 1u : 0u;
 }
 
 struct SjBytes { uint8_t *strand, *motif, *anno; };

@@ -131,6 +131,9 @@ int64_t h_sj_literal(int64_t n, const int32_t *tid, const int32_t *don, const in
 
 /* `sjtab`: a -a / -U / -A list -- exactly five integers with commas between them; 1 and out[] on success, 0 otherwise */
 int h_sj_five_ints(const char *arg, int32_t out[5]);
+/* `sjtab` -m: 1 to `cap` decimal integers with a comma between them and nothing else, none negative; the count and out[] on success,
+ * 0 otherwise */
+int h_sj_int_list(const char *arg, int32_t *out, int cap);
 
 /* ---- transcripts from a GTF (annotation, or read-like input of `-m g`) */
 typedef struct {

@@ -7,7 +7,8 @@
  *   output    the four header lines and one line per junction (print_sj :974-985)
  *
  * `lr2rmats sjtab` (the end of this file) is the same source and engine with the table `update-gtf -j` reads: nine columns, no header,
- * annotated flag from a GTF, maximum overhang, and the filter the usage text of bam2sj only advertises.
+ * annotated flag from a GTF, maximum overhang, and the filter the usage text of bam2sj only advertises; with -d, -m or -s also the
+ * intron-size rule and the distance to the nearest other junction (l2r_sj_filter_rows2).
  *
  * The reference keeps ONE list and, per junction, searches it backwards for its place (sj_sch_group :339-351).  Where the tids of
  * the records never decrease that list is the table sorted by (tid, don, acc) -- what the engine makes.  Where a tid decreases, the
@@ -594,6 +595,14 @@ static int sjtab_usage(void)
     fprintf(stderr, "                                   minimum total uniq-map and multi-map read count of a junction; a junction\n");
     fprintf(stderr, "                                   that meets -U or -A is kept. [%d,%d,%d,%d,%d]\n", 0, 3, 1, 1, 1);
     fprintf(stderr, "         -i --intron-len  [INT]    minimum intron length for junction read. [%d]\n", SJ_INTRON_MIN_LEN);
+    fprintf(stderr, "         -d --dist-other  [INT,INT,INT,INT,INT]\n");
+    fprintf(stderr, "                                   minimum distance of a junction's donor and of its acceptor to those of\n");
+    fprintf(stderr, "                                   every other junction that meets the options above. [%d,%d,%d,%d,%d]\n", 0, 0, 0, 0, 0);
+    fprintf(stderr, "         -m --intron-max  [INT[,INT...]]\n");
+    fprintf(stderr, "                                   up to 8 lengths: a junction that is not annotated and is seen by n reads\n");
+    fprintf(stderr, "                                   (n up to the length of the list) spans the n-th length at most. [None]\n");
+    fprintf(stderr, "         -s --star-filter          -d %d,%d,%d,%d,%d -m %d,%d,%d: the defaults of STAR's outSJfilterDistToOtherSJmin\n", 0, 10, 0, 5, 10, 50000, 100000, 200000);
+    fprintf(stderr, "                                   and outSJfilterIntronMaxVsReadN. -d -m -s apply from left to right.\n");
     fprintf(stderr, "\nOutput Options:\n\n");
     fprintf(stderr, "         -o --output      [STR]    junction table. [stdout]\n");
     fprintf(stderr, "\n");
@@ -619,16 +628,37 @@ int h_sj_five_ints(const char *arg, int32_t out[5])
     return *p == 0;
 }
 
+/* -m of sjtab: 1 to cap decimal integers with a comma between them and nothing else, none negative; the count and out[], else 0 */
+int h_sj_int_list(const char *arg, int32_t *out, int cap)
+{
+    if (!arg) return 0;
+    const char *p = arg;
+    int k = 0;
+    for (;;) {
+        if (k == cap || *p < '0' || *p > '9') return 0;
+        char *e;
+        const long long v = strtoll(p, &e, 10);
+        if (v > INT32_MAX) return 0;
+        out[k++] = (int32_t)v;
+        p = e;
+        if (*p == 0) return k;
+        if (*p++ != ',') return 0;
+    }
+}
+
 int h_cmd_sjtab(int argc, char **argv)
 {
     static const struct option lopt[] = {
         {"prop-pair", 0, NULL, 'p'}, {"gtf-anno", 1, NULL, 'G'}, {"genome-file", 1, NULL, 'g'}, {"anchor-len", 1, NULL, 'a'},
-        {"uniq-map", 1, NULL, 'U'}, {"all-map", 1, NULL, 'A'}, {"intron-len", 1, NULL, 'i'}, {"output", 1, NULL, 'o'}, {0, 0, 0, 0}};
+        {"uniq-map", 1, NULL, 'U'}, {"all-map", 1, NULL, 'A'}, {"intron-len", 1, NULL, 'i'}, {"output", 1, NULL, 'o'}, {"dist-other", 1, NULL, 'd'},
+        {"intron-max", 1, NULL, 'm'}, {"star-filter", 0, NULL, 's'}, {0, 0, 0, 0}};
+    static const l2r_sj_filter2 star = {{0, 10, 0, 5, 10}, 3, {50000, 100000, 200000, 0, 0, 0, 0, 0}};
     const char *ref_fn = NULL, *gtf_fn = NULL, *out_fn = NULL;
     l2r_sj_filter flt = {{1, 30, 12, 12, 12}, {0, 3, 1, 1, 1}, {0, 3, 1, 1, 1}};
-    int min_intron = SJ_INTRON_MIN_LEN, pair_only = 0, c;
+    l2r_sj_filter2 flt2; memset(&flt2, 0, sizeof flt2);
+    int min_intron = SJ_INTRON_MIN_LEN, pair_only = 0, second = 0, c;       /* second: -d, -m or -s was given */
     optind = 1;
-    while ((c = getopt_long(argc, argv, "G:g:pa:i:A:U:o:", lopt, NULL)) >= 0) {
+    while ((c = getopt_long(argc, argv, "G:g:pa:i:A:U:o:d:m:s", lopt, NULL)) >= 0) {
         switch (c) {
         case 'g': ref_fn = optarg; break;
         case 'G': gtf_fn = optarg; break;
@@ -638,6 +668,19 @@ int h_cmd_sjtab(int argc, char **argv)
         case 'A': if (!h_sj_five_ints(optarg, flt.all_min)) return sjtab_usage(); break;
         case 'i': min_intron = atoi(optarg); break;
         case 'o': out_fn = optarg; break;
+        case 'd': {
+            if (!h_sj_five_ints(optarg, flt2.dist_min)) return sjtab_usage();
+            for (int k = 0; k < 5; ++k) if (flt2.dist_min[k] < 0) return sjtab_usage();
+            second = 1; break;
+        }
+        case 'm': {
+            int32_t v[8];
+            const int k = h_sj_int_list(optarg, v, 8);
+            if (!k) return sjtab_usage();
+            memset(flt2.intron_max, 0, sizeof flt2.intron_max); memcpy(flt2.intron_max, v, (size_t)k * sizeof v[0]);
+            flt2.n_intron_max = k; second = 1; break;
+        }
+        case 's': flt2 = star; second = 1; break;
         default: fprintf(stderr, "Error: unknown option: %s.\n", optarg); return sjtab_usage();
         }
     }
@@ -690,7 +733,9 @@ int h_cmd_sjtab(int argc, char **argv)
         if (l2r_sj_annotate(ctx, &a)) h_fatal("sjtab", "%s", l2r_last_error());
     }
     const int64_t n_all = n;
-    if (l2r_sj_filter_rows(ctx, &flt, &n)) h_fatal("sjtab", "%s", l2r_last_error());
+    double st2[30]; memset(st2, 0, sizeof st2);
+    if (!second) { if (l2r_sj_filter_rows(ctx, &flt, &n)) h_fatal("sjtab", "%s", l2r_last_error()); }
+    else if (l2r_sj_filter_rows2(ctx, &flt, &flt2, &n) || l2r_sj_stats(ctx, st2, 30)) h_fatal("sjtab", "%s", l2r_last_error());
     int32_t *col[6]; uint8_t *byt[3];
     for (int q = 0; q < 6; ++q) col[q] = (int32_t *)h_malloc((size_t)(n + 1) * 4);
     for (int q = 0; q < 3; ++q) byt[q] = (uint8_t *)h_malloc((size_t)n + 1);
@@ -704,6 +749,8 @@ int h_cmd_sjtab(int argc, char **argv)
     if (out == stdout) fflush(stdout); else fclose(out);
     fprintf(stderr, "[sjtab] %lld junctions, %lld left by the filter; %lld records without an NH tag counted as multi-mapped\n", (long long)n_all, (long long)t.n,
             (long long)no_nh);
+    if (second)
+        fprintf(stderr, "[sjtab] %lld junctions dropped for their intron size, %lld for the distance to another junction\n", (long long)st2[29], (long long)st2[23]);
     for (int q = 0; q < 6; ++q) free(col[q]);
     for (int q = 0; q < 3; ++q) free(byt[q]);
     if (gtf_fn) h_gtf_free(&anno);

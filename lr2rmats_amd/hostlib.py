@@ -79,6 +79,8 @@ def load_library():
         lib.h_sj_batch_free.restype = None
         lib.h_sj_five_ints.argtypes = [C.c_char_p, C.c_void_p]
         lib.h_sj_five_ints.restype = C.c_int
+        lib.h_sj_int_list.argtypes = [C.c_char_p, C.c_void_p, C.c_int]
+        lib.h_sj_int_list.restype = C.c_int
         lib.h_chroms_free.argtypes = [C.c_void_p]
         lib.h_chroms_free.restype = None
         lib.h_read_records.argtypes = [C.c_char_p, C.c_void_p, C.c_void_p, C.c_char_p]
@@ -144,6 +146,13 @@ def sj_five_ints(text: str):
     """A -a / -U / -A list of ``sjtab`` as the command parses it (h_sj_five_ints): five ints, or None where the usage is printed."""
     out = (C.c_int32 * 5)()
     return [int(v) for v in out] if load_library().h_sj_five_ints(text.encode(), out) else None
+
+
+def sj_int_list(text: str, cap: int = 8):
+    """A -m list of ``sjtab`` as the command parses it (h_sj_int_list): 1 to ``cap`` ints, or None where the usage is printed."""
+    out = (C.c_int32 * max(cap, 1))()
+    k = load_library().h_sj_int_list(text.encode(), out, cap)
+    return [int(v) for v in out[:k]] if k > 0 else None
 
 
 def sj_literal(tid, don, acc, uniq_c, multi_c):

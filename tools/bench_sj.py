@@ -6,9 +6,12 @@ L2R_SJ_TIMING=1 (every launch bracketed by HIP events and waited for) the device
 divided by the kernel time as a fraction of 8 TB/s, and the radix passes that ran; and the wall time of the numpy restatement
 (np.unique + np.bincount, tests/sj_restatement.py) on the same rows on this host -- the only yardstick there is.
 
-A second leg runs the same records through the table of `lr2rmats sjtab` (l2r_sj_begin_tab + l2r_sj_annotate + l2r_sj_filter_rows, six
-columns per row instead of five) and prints a second JSON line ("leg": "sjtab"): the same figures, the device time of every new kernel,
-and the ratio of its scatter passes to the plain leg's (24 / 20 by the bytes per row).  L2R_BENCH_SJ_LEGS=plain runs the first leg only."""
+A second leg runs the same records through the table of `lr2rmats sjtab` (l2r_sj_begin_tab + l2r_sj_annotate + l2r_sj_filter_rows2 with
+STAR's defaults for the distance and the intron-size lists, six columns per row instead of five) and prints a second JSON line
+("leg": "sjtab"): the same figures, the device time of every new kernel, the ratio of its scatter passes to the plain leg's (24 / 20 by
+the bytes per row), and for the neighbour stage the rows it saw and dropped, the passes of the acceptor order, bytes moved / time per
+kernel and the acceptor order's time per row and pass beside k_sj_scatter's.  The synthetic table has no genome, so every row has motif 0.
+L2R_BENCH_SJ_LEGS=plain runs the first leg only."""
 import json
 import os
 import sys
@@ -72,12 +75,12 @@ def run(eng, r):
 
 
 def run_tab(eng, r, anno):
-    """The `sjtab` leg: pair_only as in the plain leg (the same records make the same rows), annotate, default filter."""
+    """The `sjtab` leg: pair_only as in the plain leg (the same records make the same rows), annotate, default filter with both stages."""
     eng.sj_begin_tab(pair_only=True)
     add_all(eng, r)
     full = eng.sj_finish()
     eng.sj_annotate(*anno)
-    return full, eng.sj_filter_rows()
+    return full, eng.sj_filter_rows2(dist_min=capi.SJ_FILTER2_STAR[0], intron_max=capi.SJ_FILTER2_STAR[1])
 
 
 t0 = time.perf_counter()
@@ -120,6 +123,7 @@ if os.environ.get("L2R_BENCH_SJ_LEGS", "") == "plain":
 
 # ---- the sjtab leg: the annotation is every second junction of the table as a two-exon transcript, and as many transcripts beside them
 from tests import sjtab_restatement as st         # noqa: E402
+from tests import sjtab_near_restatement as nr    # noqa: E402
 sel = np.arange(len(tab.tid)) % 2 == 0
 a_tid = np.concatenate([tab.tid[sel], tab.tid[sel]]).astype(np.int32)
 a_don = np.concatenate([tab.don[sel], tab.don[sel] + 7]).astype(np.int64)
@@ -135,7 +139,7 @@ os.environ["L2R_SJ_TIMING"] = "1"
 run_tab(eng, r, anno)
 tm2 = eng.sj_stats()
 del os.environ["L2R_SJ_TIMING"]
-kern2 = {k: v for k, v in tm2.items() if k.startswith("k_") or k.startswith("intron sort")}
+kern2 = {k: v for k, v in tm2.items() if k.startswith("k_") or k.startswith("intron sort") or k.startswith("acceptor order")}
 kernel_ms2 = sum(kern2.values())
 passes2 = int(tm2["radix_passes"])
 n_in, n_tab = int(tm2["anno_introns"]), len(full.tid)
@@ -143,12 +147,19 @@ n_in, n_tab = int(tm2["anno_introns"]), len(full.tid)
 # through a sort of their own (counted at 20 B rows and `passes2` passes at most); annotate 12 B + 1 per row; keep 13 B + 4, take 27 B in and out
 moved2 = 15 * n + 4 * len(r["cig"]) + 24 * rows + (12 + passes2 * 52 + 16 + 32) * rows + 8 * len(anno[2]) + (20 + 12 + passes2 * 44 + 44) * len(a_tid) + \
     13 * n_tab + 17 * n_tab + 54 * len(kept.tid)
+# the neighbour stage over the n1 rows stage 1 left: keys 8 B in + 8 out; per pass of the acceptor order 8 B for the tile histograms and 12 + 12 for
+# the scatter; near_acc 4 B index + 8 gathered + 4 out; keep_near 8 + 4 + 2 in, 4 out; its take 27 B in over n1 and out over the kept rows
+n1 = len(kept.tid) + int(tm2["rows_dropped_near"])
+acc_passes = int(tm2["acc_radix_passes"])
+near_bytes = {"k_sj_acc_keys": 16 * n1, "acceptor order passes": acc_passes * 32 * n1, "k_sj_near_acc": 16 * n1, "k_sj_keep_near": 18 * n1}
+moved2 += sum(near_bytes.values()) + 27 * n1
 t0 = time.perf_counter()
 want6 = st.table_numpy(*st.rows_numpy(r["flag"], r["tid"], r["pos"], r["uniq"], r["cig_off"], r["cig"], pair_only=True))
 numpy_s2 = time.perf_counter() - t0
 introns = set(zip(a_tid.tolist(), a_don.tolist(), a_acc.tolist()))
 an = st.anno_numpy(introns, want6[0], want6[1], want6[2])
-keep = st.keep_numpy(an, np.zeros(len(an)), want6[3], want6[4], want6[5])
+zero = np.zeros(len(an), np.int64)
+keep = nr.filter2_numpy([want6[0], want6[1], want6[2], zero, zero, an, want6[3], want6[4], want6[5]], st.DEFAULT_FILTER, nr.STAR_DIST, nr.STAR_INTRON_MAX)["keep"]
 ok2 = all(np.array_equal(g.astype(np.int64), w) for g, w in zip((full.tid, full.don, full.acc, full.uniq_c, full.multi_c, full.max_over), want6)) and \
     all(np.array_equal(g.astype(np.int64), w[keep]) for g, w in zip((kept.tid, kept.don, kept.acc, kept.uniq_c, kept.multi_c, kept.max_over), want6)) and \
     np.array_equal(kept.anno, an[keep])
@@ -159,6 +170,10 @@ line2 = dict(leg="sjtab", records=n, rows=int(st2["rows_made"]), table_rows=n_ta
              fraction_of_8TBs=(moved2 / (kernel_ms2 / 1e3)) / 8e12 if kernel_ms2 else 0.0,
              scatter_ms=tm2["k_sj_scatter"], scatter_ms_plain=tm["k_sj_scatter"],
              scatter_ratio_to_plain=(tm2["k_sj_scatter"] / passes2) / (tm["k_sj_scatter"] / passes) if passes and passes2 and tm["k_sj_scatter"] else 0.0,
+             stage1_rows=n1, rows_dropped_near=int(tm2["rows_dropped_near"]), rows_dropped_long=int(tm2["rows_dropped_long"]), acc_radix_passes=acc_passes,
+             near_GBs={k: (b / (tm2[k] / 1e3)) / 1e9 if tm2[k] else 0.0 for k, b in near_bytes.items()},
+             acc_order_ps_per_row_pass=tm2["acceptor order passes"] * 1e9 / (n1 * acc_passes) if n1 and acc_passes else 0.0,
+             scatter_ps_per_row_pass=tm2["k_sj_scatter"] * 1e9 / (st2["rows_in"] * passes2) if passes2 and st2["rows_in"] else 0.0,
              numpy_restatement_s=numpy_s2, equals_numpy=bool(ok2))
 print("| kernel (sjtab leg) | ms (one round, every launch waited for) |\n|---|---|")
 for k, v in kern2.items():
