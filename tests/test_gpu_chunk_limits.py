@@ -15,13 +15,13 @@ and l2r_debug_counters says what the engine staged (words 24 / 25) and which til
 On the tile pipeline every case also runs with L2R_CHUNK_DIRECT=0: k_probe_slab_chunked then takes the same tiles.
 """
 import bisect
-from collections import defaultdict
 
 import numpy as np
 import pytest
 
 from tests import util
 from tests.test_gpu_edges import _anno, _chain, _reads, _run, pipeline  # noqa: F401  (pipeline: autouse fixture)
+from tests.window_cases import _dictionaries, _parts  # noqa: F401  (the dictionary model, shared with the one-window cases)
 
 pytestmark = pytest.mark.gpu
 
@@ -31,45 +31,6 @@ LO_B, HI_B = 200, 262          # every read begins in bucket LO_B and ends in bu
 
 
 # ---- the model: build_dict (l2r_engine.hip) and the slice bounds of make_descriptor (l2r_window.hip.h)
-
-def _parts(pairs, singles):
-    """Entries of one dictionary as sorted keys (tid, k1, k2), one per part.  A key's members are its pairs and the singles with the
-    same (tid, k1); a part starts at the lowest member left and takes every member less than 64 past it."""
-    members, by_k1 = defaultdict(list), defaultdict(list)
-    for tid, k1, k2, tx in pairs:
-        members[(tid, k1, k2)].append(tx)
-    for tid, k1, tx in singles:
-        by_k1[(tid, k1)].append(tx)
-    ent = []
-    for key in sorted(members):
-        p, s = sorted(members[key]), sorted(by_k1[key[:2]])
-        while p or s:
-            lo = min(p[:1] + s[:1])
-            p, s = [t for t in p if t - lo >= 64], [t for t in s if t - lo >= 64]
-            ent.append(key)
-    return ent
-
-
-def _dictionaries(txs):
-    """START (exons + acceptors) and END (junctions + donors) entries; transcripts of one exon or without a chromosome enter none."""
-    kx, ka, kj, kd = [], [], [], []
-    for i, (tid, _rev, ex) in enumerate(txs):
-        if tid < 0 or len(ex) < 2:
-            continue
-        for k, (s, e) in enumerate(ex):
-            kx.append((tid, s, e, i))
-            if k + 1 < len(ex):
-                kd.append((tid, e, i))
-                kj.append((tid, e, ex[k + 1][0], i))
-            if k:
-                ka.append((tid, s, i))
-    nb = defaultdict(int)                       # buckets per chromosome: up to its largest key 1, and exon end
-    for tid, k1, k2, _ in kx:
-        nb[tid] = max(nb[tid], (max(k1, k2) >> SITE_SHIFT) + 1)
-    for tid, k1, _k2, _ in kj:
-        nb[tid] = max(nb[tid], (k1 >> SITE_SHIFT) + 1)
-    return _parts(kx, ka), _parts(kj, kd), nb
-
 
 def _model(txs, rows, tid=0):
     """(st_nk, en_nk, END entries of the slice) of the tiles of `rows`, which all share one span."""

@@ -56,7 +56,7 @@ def pipeline(request, monkeypatch):
     return request.param
 
 
-def _run(oracle, af, reads, counters=None, sj=None, words=None, want=None, **kw):
+def _run(oracle, af, reads, counters=None, sj=None, words=None, want=None, n_words=27, **kw):
     if want is None:                            # (want: the oracle's result for these inputs and parameters, when the caller has it)
         want = util.oracle_run(oracle, af, reads, oracle.default_params(**kw), sj)
     eng = capi.Engine(0)
@@ -85,9 +85,9 @@ def _run(oracle, af, reads, counters=None, sj=None, words=None, want=None, **kw)
         if words is not None:                   # every word l2r_debug_counters has (include/lr2rmats_hip.h)
             import ctypes as C
             lib = capi.load_library()
-            cnt = (C.c_longlong * 27)()
+            cnt = (C.c_longlong * n_words)()          # (n_words = 29: with the tiles of k_tile's EXACT instance and the rest list)
             lib.l2r_debug_counters.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
-            assert lib.l2r_debug_counters(eng.ctx, cnt, 27) == 0
+            assert lib.l2r_debug_counters(eng.ctx, cnt, n_words) == 0
             words[:] = list(cnt)
     finally:
         eng.close()
