@@ -348,7 +348,7 @@ int          l2r_fusion_stats(l2r_ctx *ctx, double *out, int n);
  *     l2r_sj_download  the table; its first five columns have the layout of l2r_junctions (l2r_set_junctions takes them as they are)
  * The result does not depend on how the records were cut into batches.  The sort is stable and the rows are made in record
  * order, so every intermediate order is the same run after run. */
-#define L2R_SJ_SORT_TILE 4096           /* rows one workgroup of a radix pass ranks (csrc/l2r_sj.hip.h) */
+#define L2R_SJ_SORT_TILE 4096           /* rows one workgroup of a radix pass ranks (csrc/l2r_radix.hip.h holds both to its one tile) */
 #define L2R_SJ_E_UNKNOWN_TID (-3)
 typedef struct { int32_t min_intron, pair_only; } l2r_sj_params;         /* -i INTRON_MIN_LEN 3; read_type PAIR_T: 1 */
 typedef struct { int32_t n_seq; const int64_t *seq_off /* n_seq + 1 */; const uint8_t *bases; } l2r_sj_genome;   /* sequences in FILE order */
@@ -369,7 +369,7 @@ int          l2r_sj_download(l2r_ctx *ctx, l2r_sj_table *table);
 /* diagnostics (tools/bench_sj.py, tests): out[0] rows made by l2r_sj_add / _add_rows since l2r_sj_begin, [1] sort + reduce rounds,
  * [2] radix passes the last round ran (of 12), [3] rows that went into it, [4] rows it left; with L2R_SJ_TIMING=1 in the environment
  * at l2r_sj_begin (every launch is then waited for), device milliseconds summed since then: [5] k_sj_count [6] k_scan_u32 of the
- * counts [7] k_sj_fill [8] k_sj_hist12 [9] k_sj_digit_hist [10] k_scan_u32 of the tile histograms [11] k_sj_scatter [12] k_sj_heads +
+ * counts [7] k_sj_fill [8] k_sj_hist12 [9] k_radix_digit_hist<SjRows> [10] k_scan_u32 of the tile histograms [11] k_radix_scatter<SjRows> [12] k_sj_heads +
  * its scan [13] k_sj_reduce [14] k_sj_motif; n = words of out (up to 15 for `bam2sj`; `sjtab` below adds words from 15 on) */
 int          l2r_sj_stats(l2r_ctx *ctx, double *out, int n);
 
@@ -411,7 +411,7 @@ int          l2r_sj_stats(l2r_ctx *ctx, double *out, int n);
  * run, keys that never descend run none, L2R_SORT_FORCE=1 runs all eight); more than 2^32 - 1 - L2R_SORT_TILE rows fail before any
  * pointer is read.
  * l2r_sj_stats from word 23, of the last filter call (all 0 behind l2r_sj_filter_rows): [23] rows stage 2 dropped, [24] radix passes
- * the acceptor order ran; with L2R_SJ_TIMING=1 device milliseconds of [25] k_sj_acc_keys [26] the acceptor order's passes (all their
+ * the acceptor order ran; with L2R_SJ_TIMING=1 device milliseconds of [25] k_radix_keys<SjAccKeyOf> [26] the acceptor order's passes (all their
  * kernels) [27] k_sj_near_acc [28] k_sj_keep_near; [29] rows that passed the test of l2r_sj_filter_rows and that the intron-size rule
  * dropped.  [15] is then the rows both stages dropped together. */
 typedef struct { int32_t anchor_min[5], uniq_min[5], all_min[5]; } l2r_sj_filter;     /* STAR: 30 12 12 12 / 3 1 1 1 / 3 1 1 1 behind the annotated one */
@@ -434,10 +434,10 @@ int          l2r_sj_download_tab(l2r_ctx *ctx, l2r_sj_tab *table);
  * input whose keys never descend is answered with the identity and no pass at all.  n == 0 succeeds; n > 2^32 - 1 - L2R_SORT_TILE
  * fails before any pointer is read.  The device buffers belong to the context, grow on demand and go with l2r_destroy.
  * l2r_sort_stats, of the last l2r_sort_order: out[0] rows, [1] radix passes run (of 8), [2] 1 where the input was in order already;
- * with L2R_SORT_TIMING=1 in the environment at the call (every launch is then waited for) device milliseconds of [3] k_sort_keys
- * [4] k_sort_digit_hist [5] k_scan_u32 of the tile histograms [6] k_sort_scatter, each summed over the passes; n = words of out (up
+ * with L2R_SORT_TIMING=1 in the environment at the call (every launch is then waited for) device milliseconds of [3] k_radix_keys<SortKeyOf>
+ * [4] k_radix_digit_hist<SortRows> [5] k_scan_u32 of the tile histograms [6] k_radix_scatter<SortRows>, each summed over the passes; n = words of out (up
  * to 7).  L2R_SORT_FORCE=1 (tests): all eight passes run, whether the input is in order and whether bytes are constant. */
-#define L2R_SORT_TILE 4096              /* rows one workgroup of a radix pass ranks (csrc/l2r_sort.hip.h) */
+#define L2R_SORT_TILE 4096              /* rows one workgroup of a radix pass ranks (csrc/l2r_radix.hip.h holds both to its one tile) */
 typedef struct { int64_t n; const uint16_t *flag; const int32_t *tid, *pos; } l2r_sort_records;
 int          l2r_sort_order(l2r_ctx *ctx, const l2r_sort_records *recs, uint32_t *order_out);  /* order_out[k] = record at rank k */
 int          l2r_sort_stats(l2r_ctx *ctx, double *out, int n);

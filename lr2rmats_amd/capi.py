@@ -249,13 +249,13 @@ class SjTab(SjTable):
 
 
 SJ_STAT_NAMES = ["rows_made", "rounds", "radix_passes", "rows_in", "rows_out", "k_sj_count", "k_scan_u32 (counts)", "k_sj_fill", "k_sj_hist12",
-                 "k_sj_digit_hist", "k_scan_u32 (tile histograms)", "k_sj_scatter", "k_sj_heads + scan", "k_sj_reduce", "k_sj_motif",
+                 "k_radix_digit_hist<SjRows>", "k_scan_u32 (tile histograms)", "k_radix_scatter<SjRows>", "k_sj_heads + scan", "k_sj_reduce", "k_sj_motif",
                  "rows_dropped", "anno_introns", "k_sj_introns", "k_sj_annotate", "k_sj_keep", "k_scan_u32 (keep flags)", "k_sj_take",
-                 "intron sort + reduce", "rows_dropped_near", "acc_radix_passes", "k_sj_acc_keys", "acceptor order passes", "k_sj_near_acc",
+                 "intron sort + reduce", "rows_dropped_near", "acc_radix_passes", "k_radix_keys<SjAccKeyOf>", "acceptor order passes", "k_sj_near_acc",
                  "k_sj_keep_near", "rows_dropped_long"]
 
 
-SORT_STAT_NAMES = ["rows", "radix_passes", "in_order", "k_sort_keys", "k_sort_digit_hist", "k_scan_u32 (tile histograms)", "k_sort_scatter"]
+SORT_STAT_NAMES = ["rows", "radix_passes", "in_order", "k_radix_keys<SortKeyOf>", "k_radix_digit_hist<SortRows>", "k_scan_u32 (tile histograms)", "k_radix_scatter<SortRows>"]
 
 
 def sort_keys(flag, tid, pos) -> np.ndarray:

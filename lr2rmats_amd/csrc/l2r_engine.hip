@@ -2038,18 +2038,52 @@ int l2r_fusion_stats(l2r_ctx *c, double *out, int n)
 
 // ---------------------------------------------------------------------------------------------- bam2sj, sjtab
 extern "C++" {
-// a launch (or a group of launches) on the context stream; with L2R_SJ_TIMING=1 bracketed by events, waited for and added to stats[slot]
-template <typename F> static int sj_launch(l2r_ctx *c, SjState &s, int slot, F f)
+// A launch (or a group of launches) on the context stream.  timing (L2R_SJ_TIMING=1, L2R_SORT_TIMING=1): bracketed by the two events, waited
+// for, the device milliseconds added to *ms.  wait: waited for in any case (the sort path under L2R_CHECK).
+template <typename F> static int timed_launch(l2r_ctx *c, bool timing, hipEvent_t ev[2], double *ms, F f, bool wait = false)
 {
-    if (s.timing) HIP_TRY(hipEventRecord(s.ev[0], c->stream));
+    if (timing) HIP_TRY(hipEventRecord(ev[0], c->stream));
     f();
     HIP_TRY(hipGetLastError());
-    if (s.timing) {
-        float ms = 0.0f;
-        HIP_TRY(hipEventRecord(s.ev[1], c->stream));
-        HIP_TRY(hipEventSynchronize(s.ev[1]));
-        HIP_TRY(hipEventElapsedTime(&ms, s.ev[0], s.ev[1]));
-        s.stats[slot] += ms;
+    if (timing) {
+        float t = 0.0f;
+        HIP_TRY(hipEventRecord(ev[1], c->stream));
+        HIP_TRY(hipEventSynchronize(ev[1]));
+        HIP_TRY(hipEventElapsedTime(&t, ev[0], ev[1]));
+        *ms += t;
+    }
+    if (wait) HIP_TRY(hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+// v[0, n] <- the exclusive scan of v[0, n), *total_word <- the sum: one workgroup
+static void scan_u32(l2r_ctx *c, uint32_t *v, int64_t n, uint32_t *total_word)
+{
+    ScanJobs jobs = {}; jobs.job[0] = ScanJob{v, n, total_word}; jobs.job[1] = jobs.job[0];
+    hipLaunchKernelGGL(k_scan_u32, dim3(1), dim3(1024), 0, c->stream, jobs);
+}
+
+// hist: the 256 words of one key byte over n keys.  A byte that is equal in every key is a pass that is not run.
+static bool byte_is_one_value(const uint32_t *hist, uint32_t n)
+{
+    for (int d = 0; d < 256; ++d) if (hist[d] == n) return true;
+    return false;
+}
+
+// The passes of l2r_radix.hip.h over n rows, one per key byte of byte[0, n_pass), least significant first: digit histogram of every
+// tile -> its scan -> scatter.  The caller owns the rows and their two sides: hist(b, p, n_tiles) and scatter(b, p, last, n_tiles)
+// launch pass p over byte b, which reads the side pass p - 1 wrote; launch(k, f) is the caller's timed launch of f, k = 0 the digit
+// histogram, 1 the scan, 2 the scatter.  Which bytes run is the caller's rule.
+template <typename Launch, typename Hist, typename Scatter>
+static int radix_passes(l2r_ctx *c, const int *byte, int n_pass, uint32_t n, DevBuf<uint32_t> &tile_hist, uint32_t *total_word, Launch launch, Hist hist, Scatter scatter)
+{
+    const uint32_t n_tiles = (uint32_t)(((size_t)n + RADIX_TILE - 1) / RADIX_TILE);
+    if (n_pass && tile_hist.ensure((size_t)256 * n_tiles + 1)) return -2;
+    int rc;
+    for (int p = 0; p < n_pass; ++p) {
+        if ((rc = launch(0, [&] { hist(byte[p], p, n_tiles); }))) return rc;
+        if ((rc = launch(1, [&] { scan_u32(c, tile_hist.p, (int64_t)256 * n_tiles, total_word); }))) return rc;
+        if ((rc = launch(2, [&] { scatter(byte[p], p, p == n_pass - 1, n_tiles); }))) return rc;
     }
     return 0;
 }
@@ -2057,7 +2091,10 @@ template <typename F> static int sj_launch(l2r_ctx *c, SjState &s, int slot, F f
 
 // slots of l2r_sort_stats (the acceptor order of `sjtab` runs the passes of `sort`)
 enum { SORTS_ROWS = 0, SORTS_PASSES, SORTS_IN_ORDER, SORTS_K_KEYS, SORTS_K_HIST, SORTS_K_SCAN, SORTS_K_SCATTER, SORTS_N };
+static_assert(SORTS_K_SCAN == SORTS_K_HIST + 1 && SORTS_K_SCATTER == SORTS_K_HIST + 2, "radix_passes: digit histogram, scan and scatter are three slots in a row");
 
+// slots of l2r_sj_stats: of the fifteen of `bam2sj` the three of a radix pass, in the row radix_passes counts them in
+enum { SJS_K_HIST = 9, SJS_K_HIST_SCAN, SJS_K_SCATTER };
 // slots of l2r_sj_stats behind the fifteen of `bam2sj`
 enum { SJS_DROPPED = 15, SJS_INTRONS, SJS_K_INTRONS, SJS_K_ANNOTATE, SJS_K_KEEP, SJS_K_KEEP_SCAN, SJS_K_TAKE, SJS_INTRON_SORT,
        SJS_NEAR_DROPPED, SJS_ACC_PASSES, SJS_K_ACC_KEYS, SJS_K_ACC_ORDER, SJS_K_NEAR_ACC, SJS_K_KEEP_NEAR, SJS_LONG_DROPPED, SJS_N };
@@ -2085,12 +2122,6 @@ static int sj_rows_reserve(l2r_ctx *c, const SjState &s, SjRowBuf &b, size_t wan
     return 0;
 }
 
-static int sj_scan(l2r_ctx *c, SjState &s, int slot, uint32_t *v, int64_t n)
-{
-    ScanJobs jobs = {}; jobs.job[0] = ScanJob{v, n, s.word.p}; jobs.job[1] = jobs.job[0];
-    return sj_launch(c, s, slot, [&] { hipLaunchKernelGGL(k_scan_u32, dim3(1), dim3(1024), 0, c->stream, jobs); });
-}
-
 // s.rows[cur][0, n_rows) -> sorted by (tid, don, acc), one row per key with the count columns summed (and, s.over, the overhangs' maximum)
 static int sj_compact(l2r_ctx *c, SjState &s)
 {
@@ -2100,33 +2131,30 @@ static int sj_compact(l2r_ctx *c, SjState &s)
     if (n64 >= ((int64_t)1 << 31)) return fail(-1, "[l2r_sj] %lld junction rows in one sort (2^31 at most)", (long long)n64);
     const uint32_t n = (uint32_t)n64;
     const unsigned grid = (n + SJ_THREADS - 1) / SJ_THREADS;
-    const uint32_t n_tiles = (n + SJ_SORT_TILE - 1) / SJ_SORT_TILE;
-    if (sj_rows_reserve(c, s, s.rows[1 - s.cur], n, 0) || s.hist12.ensure(SJ_KEY_BYTES * 256) || s.tile_hist.ensure((size_t)256 * n_tiles + 1) ||
-        s.head.ensure((size_t)n + 1) || s.word.ensure(4)) return -2;
+    if (sj_rows_reserve(c, s, s.rows[1 - s.cur], n, 0) || s.hist12.ensure(SJ_KEY_BYTES * 256) || s.head.ensure((size_t)n + 1) || s.word.ensure(4)) return -2;
     // which key bytes differ at all
     uint32_t h12[SJ_KEY_BYTES * 256];
     HIP_TRY(hipMemsetAsync(s.hist12.p, 0, sizeof h12, c->stream));
-    int rc = sj_launch(c, s, 8, [&] { hipLaunchKernelGGL(k_sj_hist12, dim3(std::min(grid, 2048u)), dim3(SJ_THREADS), 0, c->stream, s.rows[s.cur].cols(), n, s.hist12.p); });
+    int rc = timed_launch(c, s.timing, s.ev, &s.stats[8], [&] { hipLaunchKernelGGL(k_sj_hist12, dim3(std::min(grid, 2048u)), dim3(SJ_THREADS), 0, c->stream, s.rows[s.cur].cols(), n, s.hist12.p); });
     if (rc) return rc;
     HIP_TRY(hipMemcpyAsync(h12, s.hist12.p, sizeof h12, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
-    int src = s.cur, passes = 0;
-    for (int b = 0; b < SJ_KEY_BYTES; ++b) {
-        bool one_value = false;
-        for (int d = 0; d < 256; ++d) if (h12[b * 256 + d] == n) { one_value = true; break; }
-        if (one_value) continue;
-        const SjCols in = s.rows[src].cols(), out = s.rows[1 - src].cols();
-        if ((rc = sj_launch(c, s, 9, [&] { hipLaunchKernelGGL(k_sj_digit_hist, dim3(n_tiles), dim3(SJ_THREADS), 0, c->stream, in, n, b, n_tiles, s.tile_hist.p); }))) return rc;
-        if ((rc = sj_scan(c, s, 10, s.tile_hist.p, (int64_t)256 * n_tiles))) return rc;
-        if ((rc = sj_launch(c, s, 11, [&] {
-                if (s.over) hipLaunchKernelGGL(k_sj_scatter<true>, dim3(n_tiles), dim3(SJ_THREADS), 0, c->stream, in, out, n, b, n_tiles, (const uint32_t *)s.tile_hist.p);
-                else hipLaunchKernelGGL(k_sj_scatter<false>, dim3(n_tiles), dim3(SJ_THREADS), 0, c->stream, in, out, n, b, n_tiles, (const uint32_t *)s.tile_hist.p);
-            }))) return rc;
-        src = 1 - src; ++passes;
-    }
+    int pass_byte[SJ_KEY_BYTES], passes = 0;
+    for (int b = 0; b < SJ_KEY_BYTES; ++b) if (!byte_is_one_value(h12 + b * 256, n)) pass_byte[passes++] = b;
+    auto rows = [&](int p) { const int from = s.cur ^ (p & 1); return SjRows<false>{s.rows[from].cols(), s.rows[1 - from].cols()}; };
+    rc = radix_passes(c, pass_byte, passes, n, s.tile_hist, s.word.p,
+        [&](int k, auto f) { return timed_launch(c, s.timing, s.ev, &s.stats[SJS_K_HIST + k], f); },
+        [&](int b, int p, uint32_t n_tiles) { hipLaunchKernelGGL(k_radix_digit_hist<SjRows<false>>, dim3(n_tiles), dim3(RADIX_THREADS), 0, c->stream, rows(p), n, b, n_tiles, s.tile_hist.p); },
+        [&](int b, int p, bool, uint32_t n_tiles) {
+            const SjRows<false> r = rows(p);
+            if (s.over) hipLaunchKernelGGL(k_radix_scatter<SjRows<true>>, dim3(n_tiles), dim3(RADIX_THREADS), 0, c->stream, SjRows<true>{r.in, r.out}, n, b, n_tiles, (const uint32_t *)s.tile_hist.p);
+            else hipLaunchKernelGGL(k_radix_scatter<SjRows<false>>, dim3(n_tiles), dim3(RADIX_THREADS), 0, c->stream, r, n, b, n_tiles, (const uint32_t *)s.tile_hist.p);
+        });
+    if (rc) return rc;
+    const int src = s.cur ^ (passes & 1);
     // runs of equal keys
-    if ((rc = sj_launch(c, s, 12, [&] { hipLaunchKernelGGL(k_sj_heads, dim3(grid), dim3(SJ_THREADS), 0, c->stream, s.rows[src].cols(), n, s.head.p); }))) return rc;
-    if ((rc = sj_scan(c, s, 12, s.head.p, (int64_t)n))) return rc;
+    if ((rc = timed_launch(c, s.timing, s.ev, &s.stats[12], [&] { hipLaunchKernelGGL(k_sj_heads, dim3(grid), dim3(SJ_THREADS), 0, c->stream, s.rows[src].cols(), n, s.head.p); }))) return rc;
+    if ((rc = timed_launch(c, s.timing, s.ev, &s.stats[12], [&] { scan_u32(c, s.head.p, (int64_t)n, s.word.p); }))) return rc;
     uint32_t n_runs = 0;
     HIP_TRY(hipMemcpyAsync(&n_runs, s.word.p, 4, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
@@ -2135,7 +2163,7 @@ static int sj_compact(l2r_ctx *c, SjState &s)
     HIP_TRY(hipMemsetAsync(s.rows[dst].col[3].p, 0, (size_t)n_runs * 4, c->stream));
     HIP_TRY(hipMemsetAsync(s.rows[dst].col[4].p, 0, (size_t)n_runs * 4, c->stream));
     if (s.over) { HIP_TRY(hipMemsetAsync(s.rows[dst].col[5].p, 0, (size_t)n_runs * 4, c->stream)); }
-    if ((rc = sj_launch(c, s, 13, [&] {
+    if ((rc = timed_launch(c, s.timing, s.ev, &s.stats[13], [&] {
             if (s.over) hipLaunchKernelGGL(k_sj_reduce<true>, dim3(grid), dim3(SJ_THREADS), 0, c->stream, s.rows[src].cols(), n, (const uint32_t *)s.head.p, s.rows[dst].cols(), n_runs);
             else hipLaunchKernelGGL(k_sj_reduce<false>, dim3(grid), dim3(SJ_THREADS), 0, c->stream, s.rows[src].cols(), n, (const uint32_t *)s.head.p, s.rows[dst].cols(), n_runs);
         }))) return rc;
@@ -2206,14 +2234,14 @@ int l2r_sj_add(l2r_ctx *c, const l2r_sj_records *r)
     if (s.cnt.ensure(N + 1)) return -2;
     const SjRecs recs{(int64_t)N, s.flag.p, s.tid.p, s.pos.p, s.uniq.p, s.cig_off.p, s.cig.p};
     const unsigned grid = (unsigned)((N + SJ_THREADS - 1) / SJ_THREADS);
-    if ((rc = sj_launch(c, s, 5, [&] { hipLaunchKernelGGL(k_sj_count, dim3(grid), dim3(SJ_THREADS), 0, c->stream, recs, s.prm, s.cnt.p); }))) return rc;
-    if ((rc = sj_scan(c, s, 6, s.cnt.p, (int64_t)N))) return rc;
+    if ((rc = timed_launch(c, s.timing, s.ev, &s.stats[5], [&] { hipLaunchKernelGGL(k_sj_count, dim3(grid), dim3(SJ_THREADS), 0, c->stream, recs, s.prm, s.cnt.p); }))) return rc;
+    if ((rc = timed_launch(c, s.timing, s.ev, &s.stats[6], [&] { scan_u32(c, s.cnt.p, (int64_t)N, s.word.p); }))) return rc;
     uint32_t total = 0;
     HIP_TRY(hipMemcpyAsync(&total, s.word.p, 4, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     if (total == 0) return 0;
     if ((rc = sj_rows_reserve(c, s, s.rows[s.cur], (size_t)s.n_rows + total, (size_t)s.n_rows))) return rc;
-    if ((rc = sj_launch(c, s, 7, [&] {
+    if ((rc = timed_launch(c, s.timing, s.ev, &s.stats[7], [&] {
             if (s.over) hipLaunchKernelGGL(k_sj_fill<true>, dim3(grid), dim3(SJ_THREADS), 0, c->stream, recs, s.prm, (const uint32_t *)s.cnt.p, s.rows[s.cur].cols(), s.n_rows, s.n_rows + (int64_t)total);
             else hipLaunchKernelGGL(k_sj_fill<false>, dim3(grid), dim3(SJ_THREADS), 0, c->stream, recs, s.prm, (const uint32_t *)s.cnt.p, s.rows[s.cur].cols(), s.n_rows, s.n_rows + (int64_t)total);
         }))) return rc;
@@ -2278,7 +2306,7 @@ int l2r_sj_finish(l2r_ctx *c, int64_t *n_rows)
         HIP_TRY(hipMemcpyAsync(s.word.p + 1, &bad, 4, hipMemcpyHostToDevice, c->stream));
         const SjGenome g{s.n_seq, s.seq_off.p, s.bases.p};
         const SjCols t = s.rows[s.cur].cols();
-        if ((rc = sj_launch(c, s, 14, [&] { hipLaunchKernelGGL(k_sj_motif, dim3((n + SJ_THREADS - 1) / SJ_THREADS), dim3(SJ_THREADS), 0, c->stream, (const int32_t *)t.tid, (const int32_t *)t.don,
+        if ((rc = timed_launch(c, s.timing, s.ev, &s.stats[14], [&] { hipLaunchKernelGGL(k_sj_motif, dim3((n + SJ_THREADS - 1) / SJ_THREADS), dim3(SJ_THREADS), 0, c->stream, (const int32_t *)t.tid, (const int32_t *)t.don,
                                                              (const int32_t *)t.acc, n, g, s.strand[0].p, s.motif[0].p, s.word.p + 1); }))) return rc;
         HIP_TRY(hipMemcpyAsync(&bad, s.word.p + 1, 4, hipMemcpyDeviceToHost, c->stream));
         HIP_TRY(hipStreamSynchronize(c->stream));
@@ -2328,7 +2356,7 @@ int l2r_sj_annotate(l2r_ctx *c, const l2r_annotation *a)
         if ((rc = sj_rows_reserve(c, is, is.rows[0], E, 0))) return rc;
         HIP_TRY(hipMemsetAsync(is.word.p + 2, 0, 4, c->stream));
         const SjAnno an{a->n_tx, a->n_exon, in.tx_tid.p, in.tx_ex_off.p, in.ex_start.p, in.ex_end.p};
-        if ((rc = sj_launch(c, s, SJS_K_INTRONS, [&] { hipLaunchKernelGGL(k_sj_introns, dim3((unsigned)((E + SJ_THREADS - 1) / SJ_THREADS)), dim3(SJ_THREADS), 0, c->stream, an, is.rows[0].cols(),
+        if ((rc = timed_launch(c, s.timing, s.ev, &s.stats[SJS_K_INTRONS], [&] { hipLaunchKernelGGL(k_sj_introns, dim3((unsigned)((E + SJ_THREADS - 1) / SJ_THREADS)), dim3(SJ_THREADS), 0, c->stream, an, is.rows[0].cols(),
                                                                           is.word.p + 2, (uint32_t)E); }))) return rc;
         HIP_TRY(hipMemcpyAsync(&n_in, is.word.p + 2, 4, hipMemcpyDeviceToHost, c->stream));
         HIP_TRY(hipStreamSynchronize(c->stream));
@@ -2342,7 +2370,7 @@ int l2r_sj_annotate(l2r_ctx *c, const l2r_annotation *a)
     const uint32_t n = (uint32_t)s.n_rows;
     if (n) {
         const SjCols t = s.rows[s.cur].cols();
-        if ((rc = sj_launch(c, s, SJS_K_ANNOTATE, [&] { hipLaunchKernelGGL(k_sj_annotate, dim3((n + SJ_THREADS - 1) / SJ_THREADS), dim3(SJ_THREADS), 0, c->stream, (const int32_t *)t.tid,
+        if ((rc = timed_launch(c, s.timing, s.ev, &s.stats[SJS_K_ANNOTATE], [&] { hipLaunchKernelGGL(k_sj_annotate, dim3((n + SJ_THREADS - 1) / SJ_THREADS), dim3(SJ_THREADS), 0, c->stream, (const int32_t *)t.tid,
                                                                            (const int32_t *)t.don, (const int32_t *)t.acc, n, is.rows[is.cur].cols(), n_in, s.anno[s.bcur].p); }))) return rc;
         HIP_TRY(hipStreamSynchronize(c->stream));
     }
@@ -2355,14 +2383,14 @@ static int sj_take_kept(l2r_ctx *c, SjState &s, uint32_t n, const char *who, uin
     int rc;
     const unsigned grid = (n + SJ_THREADS - 1) / SJ_THREADS;
     const int bsrc = s.bcur, bdst = 1 - s.bcur, src = s.cur, dst = 1 - s.cur;
-    if ((rc = sj_scan(c, s, SJS_K_KEEP_SCAN, s.head.p, (int64_t)n))) return rc;
+    if ((rc = timed_launch(c, s.timing, s.ev, &s.stats[SJS_K_KEEP_SCAN], [&] { scan_u32(c, s.head.p, (int64_t)n, s.word.p); }))) return rc;
     uint32_t kept = 0;
     HIP_TRY(hipMemcpyAsync(&kept, s.word.p, 4, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     if (kept > n) return fail(-2, "[%s] %u of %u rows kept", who, kept, n);
     if (kept) {
         const SjBytes bin{s.strand[bsrc].p, s.motif[bsrc].p, s.anno[bsrc].p}, bout{s.strand[bdst].p, s.motif[bdst].p, s.anno[bdst].p};
-        if ((rc = sj_launch(c, s, SJS_K_TAKE, [&] { hipLaunchKernelGGL(k_sj_take, dim3(grid), dim3(SJ_THREADS), 0, c->stream, s.rows[src].cols(), bin, n, (const uint32_t *)s.head.p,
+        if ((rc = timed_launch(c, s.timing, s.ev, &s.stats[SJS_K_TAKE], [&] { hipLaunchKernelGGL(k_sj_take, dim3(grid), dim3(SJ_THREADS), 0, c->stream, s.rows[src].cols(), bin, n, (const uint32_t *)s.head.p,
                                                                        s.rows[dst].cols(), bout, kept); }))) return rc;
         HIP_TRY(hipStreamSynchronize(c->stream));
     }
@@ -2393,7 +2421,7 @@ static int sj_filter_local(l2r_ctx *c, const l2r_sj_filter *f, const SjFilter2 *
     if ((rc = sj_filter_reserve(c, s, n))) return rc;
     const SjFilter2 none = {};
     if (g) HIP_TRY(hipMemsetAsync(s.word.p + 3, 0, 4, c->stream));
-    if ((rc = sj_launch(c, s, SJS_K_KEEP, [&] {
+    if ((rc = timed_launch(c, s.timing, s.ev, &s.stats[SJS_K_KEEP], [&] {
             if (g) hipLaunchKernelGGL(k_sj_keep<true>, dim3(grid), dim3(SJ_THREADS), 0, c->stream, s.rows[s.cur].cols(), (const uint8_t *)s.motif[s.bcur].p,
                                       (const uint8_t *)s.anno[s.bcur].p, n, flt, *g, s.head.p, s.word.p + 3);
             else hipLaunchKernelGGL(k_sj_keep<false>, dim3(grid), dim3(SJ_THREADS), 0, c->stream, s.rows[s.cur].cols(), (const uint8_t *)s.motif[s.bcur].p,
@@ -2439,8 +2467,8 @@ static int sj_filter_near(l2r_ctx *c, const SjFilter2 &g)
     for (int k = 0; k < 2; ++k) if (!o.ev[k]) HIP_TRY(hipEventCreate(&o.ev[k]));
     const SjCols t = s.rows[s.cur].cols();
     HIP_TRY(hipMemsetAsync(o.hist.p, 0, (SORT_KEY_BYTES * 256 + 1) * sizeof(uint32_t), c->stream));
-    if ((rc = sj_launch(c, s, SJS_K_ACC_KEYS, [&] {
-            hipLaunchKernelGGL(k_sj_acc_keys, dim3(std::min(grid, 2048u)), dim3(SJ_THREADS), 0, c->stream, (const int32_t *)t.tid, (const int32_t *)t.acc, n, o.key[0].p, o.hist.p,
+    if ((rc = timed_launch(c, s.timing, s.ev, &s.stats[SJS_K_ACC_KEYS], [&] {
+            hipLaunchKernelGGL(k_radix_keys<SjAccKeyOf>, dim3(std::min(grid, 2048u)), dim3(RADIX_THREADS), 0, c->stream, SjAccKeyOf{t.tid, t.acc}, (int64_t)n, o.key[0].p, o.hist.p,
                                o.hist.p + SORT_KEY_BYTES * 256);
         }))) return rc;
     // the passes are those of `sort`, in its buffers; what l2r_sort_stats says of the last l2r_sort_order stays
@@ -2457,10 +2485,10 @@ static int sj_filter_near(l2r_ctx *c, const SjFilter2 &g)
     if (rc) return rc;
     s.stats[SJS_ACC_PASSES] = n_pass;
     const uint32_t *idx = n_pass ? o.idx[src].p : nullptr;
-    if ((rc = sj_launch(c, s, SJS_K_NEAR_ACC, [&] {
+    if ((rc = timed_launch(c, s.timing, s.ev, &s.stats[SJS_K_NEAR_ACC], [&] {
             hipLaunchKernelGGL(k_sj_near_acc, dim3(grid), dim3(SJ_THREADS), 0, c->stream, (const int32_t *)t.tid, (const int32_t *)t.acc, idx, n, s.near_acc.p);
         }))) return rc;
-    if ((rc = sj_launch(c, s, SJS_K_KEEP_NEAR, [&] {
+    if ((rc = timed_launch(c, s.timing, s.ev, &s.stats[SJS_K_KEEP_NEAR], [&] {
             hipLaunchKernelGGL(k_sj_keep_near, dim3(grid), dim3(SJ_THREADS), 0, c->stream, (const int32_t *)t.tid, (const int32_t *)t.don, (const int32_t *)s.near_acc.p,
                                (const uint8_t *)s.motif[s.bcur].p, (const uint8_t *)s.anno[s.bcur].p, n, g, s.head.p);
         }))) return rc;
@@ -2557,25 +2585,6 @@ int l2r_sj_stats(l2r_ctx *c, double *out, int n)
 }
 
 // ---------------------------------------------------------------------------------------------- sort, filter -S
-extern "C++" {
-// a launch on the context stream; with L2R_SORT_TIMING=1 bracketed by events, waited for and added to stats[slot]; L2R_CHECK: waited for
-template <typename F> static int sort_launch(l2r_ctx *c, SortState &s, int slot, F f)
-{
-    if (s.timing) HIP_TRY(hipEventRecord(s.ev[0], c->stream));
-    f();
-    HIP_TRY(hipGetLastError());
-    if (s.timing) {
-        float ms = 0.0f;
-        HIP_TRY(hipEventRecord(s.ev[1], c->stream));
-        HIP_TRY(hipEventSynchronize(s.ev[1]));
-        HIP_TRY(hipEventElapsedTime(&ms, s.ev[0], s.ev[1]));
-        s.stats[slot] += ms;
-    }
-    if (c->check_stages) HIP_TRY(hipStreamSynchronize(c->stream));
-    return 0;
-}
-}
-
 // The radix passes over the keys in s.key[0][0, n), behind a keys kernel that left the histograms of the eight key bytes and the descent
 // word in s.hist: l2r_sort_order's, and the acceptor order of l2r_sj_filter_rows2.  A byte that is equal in every key is a pass that is
 // not run, keys that never descend run none (L2R_SORT_FORCE=1: all eight, whatever the keys).  *n_pass_out: passes run; the order is
@@ -2585,38 +2594,28 @@ static int sort_passes(l2r_ctx *c, SortState &s, uint32_t n, int *n_pass_out, bo
     const char *e = getenv("L2R_SORT_FORCE");
     const bool force = e && atoi(e) != 0;
     const size_t N = n;
-    const uint32_t n_tiles = (uint32_t)((N + SORT_TILE - 1) / SORT_TILE);
     uint32_t h8[SORT_KEY_BYTES * 256 + 1];
     HIP_TRY(hipMemcpyAsync(h8, s.hist.p, sizeof h8, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     const bool in_order = h8[SORT_KEY_BYTES * 256] == 0u;
     int pass_byte[SORT_KEY_BYTES], n_pass = 0;
-    for (int b = 0; b < SORT_KEY_BYTES; ++b) {
-        bool one_value = false;
-        for (int d = 0; d < 256; ++d) if (h8[b * 256 + d] == n) { one_value = true; break; }
-        if (force || (!in_order && !one_value)) pass_byte[n_pass++] = b;
-    }
-    *n_pass_out = n_pass; *in_order_out = in_order; *src_out = 0;
+    for (int b = 0; b < SORT_KEY_BYTES; ++b) if (force || (!in_order && !byte_is_one_value(h8 + b * 256, n))) pass_byte[n_pass++] = b;
+    *n_pass_out = n_pass; *in_order_out = in_order; *src_out = n_pass & 1;
     if (n_pass == 0) return 0;
-    if (s.idx[0].ensure(N) || s.idx[1].ensure(N) || (n_pass > 1 && s.key[1].ensure(N)) || s.tile_hist.ensure((size_t)256 * n_tiles + 1)) return -2;
-    int rc, src = 0;
-    for (int p = 0; p < n_pass; ++p) {
-        const int b = pass_byte[p];
-        const bool first = p == 0, last = p == n_pass - 1;
-        const uint64_t *key_in = s.key[src].p; const uint32_t *idx_in = s.idx[src].p;
-        uint64_t *key_out = s.key[1 - src].p; uint32_t *idx_out = s.idx[1 - src].p;
-        if ((rc = sort_launch(c, s, SORTS_K_HIST, [&] { hipLaunchKernelGGL(k_sort_digit_hist, dim3(n_tiles), dim3(SORT_THREADS), 0, c->stream, key_in, n, b, n_tiles, s.tile_hist.p); }))) return rc;
-        ScanJobs jobs = {}; jobs.job[0] = ScanJob{s.tile_hist.p, (int64_t)256 * n_tiles, s.word.p}; jobs.job[1] = jobs.job[0];
-        if ((rc = sort_launch(c, s, SORTS_K_SCAN, [&] { hipLaunchKernelGGL(k_scan_u32, dim3(1), dim3(1024), 0, c->stream, jobs); }))) return rc;
-        if ((rc = sort_launch(c, s, SORTS_K_SCATTER, [&] {
-#define SORT_SCATTER(F, L) hipLaunchKernelGGL((k_sort_scatter<F, L>), dim3(n_tiles), dim3(SORT_THREADS), 0, c->stream, key_in, idx_in, key_out, idx_out, n, b, n_tiles, (const uint32_t *)s.tile_hist.p)
-                if (first && last) SORT_SCATTER(true, true); else if (first) SORT_SCATTER(true, false); else if (last) SORT_SCATTER(false, true); else SORT_SCATTER(false, false);
+    if (s.idx[0].ensure(N) || s.idx[1].ensure(N) || (n_pass > 1 && s.key[1].ensure(N))) return -2;
+    return radix_passes(c, pass_byte, n_pass, n, s.tile_hist, s.word.p,
+        [&](int k, auto f) { return timed_launch(c, s.timing, s.ev, &s.stats[SORTS_K_HIST + k], f, c->check_stages); },
+        [&](int b, int p, uint32_t n_tiles) {
+            hipLaunchKernelGGL((k_radix_digit_hist<SortRows<false, false>>), dim3(n_tiles), dim3(RADIX_THREADS), 0, c->stream,
+                               SortRows<false, false>{s.key[p & 1].p, nullptr, nullptr, nullptr}, n, b, n_tiles, s.tile_hist.p);
+        },
+        [&](int b, int p, bool last, uint32_t n_tiles) {
+            const int from = p & 1;
+#define SORT_SCATTER(F, L) hipLaunchKernelGGL((k_radix_scatter<SortRows<F, L>>), dim3(n_tiles), dim3(RADIX_THREADS), 0, c->stream, \
+                                              SortRows<F, L>{s.key[from].p, s.idx[from].p, s.key[1 - from].p, s.idx[1 - from].p}, n, b, n_tiles, (const uint32_t *)s.tile_hist.p)
+            if (p == 0 && last) SORT_SCATTER(true, true); else if (p == 0) SORT_SCATTER(true, false); else if (last) SORT_SCATTER(false, true); else SORT_SCATTER(false, false);
 #undef SORT_SCATTER
-            }))) return rc;
-        src = 1 - src;
-    }
-    *src_out = src;
-    return 0;
+        });
 }
 
 int l2r_sort_order(l2r_ctx *c, const l2r_sort_records *r, uint32_t *order_out)
@@ -2642,10 +2641,10 @@ int l2r_sort_order(l2r_ctx *c, const l2r_sort_records *r, uint32_t *order_out)
     // the keys, which of their bytes differ at all, whether they descend anywhere
     HIP_TRY(hipMemsetAsync(s.hist.p, 0, (SORT_KEY_BYTES * 256 + 1) * sizeof(uint32_t), c->stream));
     const unsigned grid = (unsigned)std::min<size_t>((N + SORT_THREADS - 1) / SORT_THREADS, 2048);
-    const SortRecs recs{r->n, s.flag.p, s.tid.p, s.pos.p};
-    if ((rc = sort_launch(c, s, SORTS_K_KEYS, [&] {
-            hipLaunchKernelGGL(k_sort_keys, dim3(grid), dim3(SORT_THREADS), 0, c->stream, recs, s.key[0].p, s.hist.p, s.hist.p + SORT_KEY_BYTES * 256);
-        }))) return rc;
+    if ((rc = timed_launch(c, s.timing, s.ev, &s.stats[SORTS_K_KEYS], [&] {
+            hipLaunchKernelGGL(k_radix_keys<SortKeyOf>, dim3(grid), dim3(RADIX_THREADS), 0, c->stream, SortKeyOf{s.flag.p, s.tid.p, s.pos.p}, r->n, s.key[0].p, s.hist.p,
+                               s.hist.p + SORT_KEY_BYTES * 256);
+        }, c->check_stages))) return rc;
     int n_pass = 0, src = 0; bool in_order = false;
     if ((rc = sort_passes(c, s, n, &n_pass, &in_order, &src))) return rc;
     s.stats[SORTS_IN_ORDER] = in_order ? 1 : 0;

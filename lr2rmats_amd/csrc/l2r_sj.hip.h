@@ -6,17 +6,15 @@
 //                            carry no N operation)
 //   k_sj_hist12              one pass over the keys: the histograms of all twelve key bytes (a byte that is equal in every key is
 //                            a radix pass that is not run)
-//   k_sj_digit_hist          per pass: the digit histogram of every tile of SJ_SORT_TILE rows, digit-major (one k_scan_u32 over it
-//                            gives every (digit, tile) its first slot)
-//   k_sj_scatter             per pass: stable scatter, one workgroup per tile, 256 rows per round in row order: the rank of a row
-//                            among the rows of its digit = rows of earlier rounds + rows of earlier waves + lanes in front of it
+//   SjRows<OVER>             the rows of a radix pass of l2r_radix.hip.h: k_radix_digit_hist<SjRows<false>> reads the one column
+//                            the pass's byte lives in, k_radix_scatter<SjRows<OVER>> moves the five (OVER: six) columns
 //   k_sj_heads / k_sj_reduce head flags where the key changes -> k_scan_u32 -> per run the sums of the two count COLUMNS (so the same
 //                            sort + reduce merges tables that were reduced before); a wave sums its part of a run by shuffles and
 //                            adds it with one integer atomic, so a run may cross waves and workgroups and be of any length
 //   k_sj_motif               per reduced row: four bases -> motif and strand; the first row on a sequence the genome lacks
 //
 // `sjtab` adds a sixth column, the overhang (the shorter of the two aligned blocks beside the junction), reduced by MAXIMUM: k_sj_fill,
-// k_sj_scatter and k_sj_reduce have an OVER instance each that carries it (24 bytes per row and pass); the plain instances are the
+// k_radix_scatter<SjRows> and k_sj_reduce have an OVER instance each that carries it (24 bytes per row and pass); the plain instances are the
 // code above, unchanged.  Behind the reduction:
 //   k_sj_introns             per annotation exon that is not the last of its transcript: the intron behind it as a row (sorted and made
 //                            unique by the same passes, in a state of their own)
@@ -25,8 +23,8 @@
 //
 // The second filter stage of `sjtab` (l2r_sj_filter_rows2; the rule is in include/lr2rmats_hip.h).  k_sj_keep has an INTRON instance that
 // applies the intron-size rule as well; the plain instance is the code above, unchanged.  Over the rows that instance left:
-//   k_sj_acc_keys            per row one 64-bit key (tid, acc) for the radix passes of l2r_sort.hip.h, the histograms of its eight bytes
-//                            and one word that says whether any key is below its predecessor (none: no pass runs)
+//   SjAccKeyOf               k_radix_keys<SjAccKeyOf>: per row one 64-bit key (tid, acc) for the passes `sort` runs over SortRows
+//                            (l2r_sort.hip.h), the histograms of its eight bytes and the descent word (no key below its predecessor: no pass runs)
 //   k_sj_near_acc            per position of the acceptor order: the distance to the nearest other acceptor on the reference, from
 //                            the two neighbours in that order (adjacent lanes by shuffles), written to the row's own slot
 //   k_sj_keep_near           per row in table order: the distance to the nearest other donor from rows i - 1 and i + 1 (the table is in
@@ -36,16 +34,12 @@
 // every column is compared with its sign bit flipped).  HBM-bound integer work: a pass reads and writes 20 bytes per row.  No kernel
 // waits for another workgroup.
 #pragma once
-#include <hip/hip_runtime.h>
-#include <stdint.h>
+#include "l2r_radix.hip.h"
 
 namespace l2r {
 
-constexpr int SJ_THREADS = 256;
-constexpr int SJ_SORT_TILE = L2R_SJ_SORT_TILE;          // rows of one workgroup of a radix pass (include/lr2rmats_hip.h)
-constexpr int SJ_ROUNDS = SJ_SORT_TILE / SJ_THREADS;
+constexpr int SJ_THREADS = RADIX_THREADS;
 constexpr int SJ_KEY_BYTES = 12;
-static_assert(SJ_SORT_TILE % SJ_THREADS == 0, "a tile is a whole number of rounds");
 
 struct SjCols { int32_t *tid, *don, *acc, *uq, *mc, *ov; };      // ov: only the OVER instances touch it (null in a plain table)
 struct SjPrm { int32_t min_intron, pair_only; };
@@ -147,75 +141,31 @@ void k_sj_hist12(SjCols in, uint32_t n, uint32_t *__restrict__ hist)
     for (int k = threadIdx.x; k < SJ_KEY_BYTES * 256; k += SJ_THREADS) { const uint32_t v = s_h[k]; if (v) atomicAdd(&hist[k], v); }
 }
 
-__device__ __forceinline__ uint32_t sj_pass_digit(const SjCols &in, uint32_t i, int b)
-{
-    const int32_t *__restrict__ col = b < 4 ? in.acc : b < 8 ? in.don : in.tid;
-    return (((uint32_t)col[i] ^ 0x80000000u) >> (8 * (b & 3))) & 0xffu;
-}
-
-// tile_hist[d * n_tiles + tile] = rows of the tile with digit d
-__global__ __launch_bounds__(SJ_THREADS)
-void k_sj_digit_hist(SjCols in, uint32_t n, int b, uint32_t n_tiles, uint32_t *__restrict__ tile_hist)
-{
-    __shared__ uint32_t s_h[256];
-    s_h[threadIdx.x] = 0u;
-    __syncthreads();
-    const uint32_t t0 = blockIdx.x * (uint32_t)SJ_SORT_TILE;
-    for (int r = 0; r < SJ_ROUNDS; ++r) {
-        const uint32_t i = t0 + (uint32_t)r * SJ_THREADS + threadIdx.x;
-        if (i < n) atomicAdd(&s_h[sj_pass_digit(in, i, b)], 1u);
-    }
-    __syncthreads();
-    tile_hist[threadIdx.x * n_tiles + blockIdx.x] = s_h[threadIdx.x];
-}
-
-// first[]: tile_hist after its exclusive scan: the first slot of the tile's rows of every digit.  OVER: the sixth column moves too.
+// The rows of a pass (l2r_radix.hip.h).  OVER: the sixth column moves too.
 template <bool OVER>
-__global__ __launch_bounds__(SJ_THREADS)
-void k_sj_scatter(SjCols in, SjCols out, uint32_t n, int b, uint32_t n_tiles, const uint32_t *__restrict__ first)
-{
-    __shared__ uint32_t s_base[256];
-    __shared__ uint32_t s_wcnt[SJ_THREADS / 64][256];
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    s_base[threadIdx.x] = first[threadIdx.x * n_tiles + blockIdx.x];
-#pragma unroll
-    for (int k = 0; k < SJ_THREADS / 64; ++k) s_wcnt[k][threadIdx.x] = 0u;
-    __syncthreads();
-    const uint32_t t0 = blockIdx.x * (uint32_t)SJ_SORT_TILE;
-    for (int r = 0; r < SJ_ROUNDS; ++r) {
-        const uint32_t r0 = t0 + (uint32_t)r * SJ_THREADS;
-        if (r0 >= n) break;                                            // (uniform)
-        const uint32_t i = r0 + threadIdx.x;
-        const bool active = i < n;
-        int32_t t = 0, d = 0, a = 0, u = 0, m = 0, v = 0;
-        if (active) { t = in.tid[i]; d = in.don[i]; a = in.acc[i]; u = in.uq[i]; m = in.mc[i]; if constexpr (OVER) v = in.ov[i]; }
-        const uint32_t dg = sj_digit(t, d, a, b);
-        // the lanes of this wave that hold the same digit
-        unsigned long long same = __ballot(active);
-#pragma unroll
-        for (int q = 0; q < 8; ++q) {
-            const bool bit = (dg >> q) & 1u;
-            const unsigned long long bal = __ballot(active && bit);
-            same &= bit ? bal : ~bal;
-        }
-        const uint32_t rank = (uint32_t)__popcll(same & ((1ull << lane) - 1ull));
-        if (active && rank == 0u) s_wcnt[w][dg] = (uint32_t)__popcll(same);
-        __syncthreads();
-        if (active) {
-            uint32_t o = s_base[dg] + rank;
-            for (int k = 0; k < w; ++k) o += s_wcnt[k][dg];
-            if (o < n) { out.tid[o] = t; out.don[o] = d; out.acc[o] = a; out.uq[o] = u; out.mc[o] = m; if constexpr (OVER) out.ov[o] = v; }
-        }
-        __syncthreads();
-        {
-            uint32_t s = 0;
-#pragma unroll
-            for (int k = 0; k < SJ_THREADS / 64; ++k) { s += s_wcnt[k][threadIdx.x]; s_wcnt[k][threadIdx.x] = 0u; }
-            s_base[threadIdx.x] += s;
-        }
-        __syncthreads();
+struct SjRows {
+    SjCols in, out;
+    struct Row { int32_t t, d, a, u, m, v; };
+    static constexpr int HIST_UNROLL = RADIX_ROUNDS;
+    __device__ __forceinline__ Row blank(uint32_t) const { return Row{0, 0, 0, 0, 0, 0}; }
+    __device__ __forceinline__ Row load(uint32_t i) const
+    {
+        Row r{in.tid[i], in.don[i], in.acc[i], in.uq[i], in.mc[i], 0};
+        if constexpr (OVER) r.v = in.ov[i];
+        return r;
     }
-}
+    __device__ __forceinline__ uint32_t digit(const Row &r, int b) const { return sj_digit(r.t, r.d, r.a, b); }
+    __device__ __forceinline__ uint32_t digit_at(uint32_t i, int b) const
+    {
+        const int32_t *__restrict__ col = b < 4 ? in.acc : b < 8 ? in.don : in.tid;
+        return (((uint32_t)col[i] ^ 0x80000000u) >> (8 * (b & 3))) & 0xffu;
+    }
+    __device__ __forceinline__ void store(uint32_t o, const Row &r) const
+    {
+        out.tid[o] = r.t; out.don[o] = r.d; out.acc[o] = r.a; out.uq[o] = r.u; out.mc[o] = r.m;
+        if constexpr (OVER) out.ov[o] = r.v;
+    }
+};
 
 // head[i] = 1 where row i starts a run of equal keys (head has n + 1 words for the scan)
 __global__ __launch_bounds__(SJ_THREADS)
@@ -391,37 +341,10 @@ __device__ __forceinline__ uint64_t sj_acc_key(int32_t tid, int32_t acc)
     return ((uint64_t)((uint32_t)tid ^ 0x80000000u) << 32) | (uint64_t)((uint32_t)acc ^ 0x80000000u);
 }
 
-// hist: 8 x 256 words and *descends, cleared by the caller (the layout k_sort_keys leaves: the passes of l2r_sort.hip.h read it).
-// A wave whose 64 keys share a byte adds 64 to one word instead of 64 times 1.
-__global__ __launch_bounds__(SJ_THREADS)
-void k_sj_acc_keys(const int32_t *__restrict__ tid, const int32_t *__restrict__ acc, uint32_t n, uint64_t *__restrict__ key, uint32_t *__restrict__ hist,
-                   uint32_t *__restrict__ descends)
-{
-    __shared__ uint32_t s_h[8 * 256];
-    for (int k = threadIdx.x; k < 8 * 256; k += SJ_THREADS) s_h[k] = 0u;
-    __syncthreads();
-    const int lane = threadIdx.x & 63;
-    bool down = false;
-    for (uint64_t base = (uint64_t)blockIdx.x * SJ_THREADS; base < n; base += (uint64_t)gridDim.x * SJ_THREADS) {      // (uniform)
-        const uint64_t i = base + threadIdx.x;
-        const bool active = i < n;
-        uint64_t k = 0;
-        if (active) { k = sj_acc_key(tid[i], acc[i]); key[i] = k; }
-        uint64_t prev = (uint64_t)__shfl_up((unsigned long long)k, 1, 64);
-        if (lane == 0 && active && i > 0) prev = sj_acc_key(tid[i - 1], acc[i - 1]);
-        down |= active && i > 0 && k < prev;
-        const bool whole = __ballot(active) == ~0ull;
-#pragma unroll
-        for (int b = 0; b < 8; ++b) {
-            const uint32_t d = (uint32_t)(k >> (8 * b)) & 0xffu;
-            if (whole && __all(d == (uint32_t)__builtin_amdgcn_readfirstlane((int)d))) { if (lane == 0) atomicAdd(&s_h[b * 256 + d], 64u); }
-            else if (active) atomicAdd(&s_h[b * 256 + d], 1u);
-        }
-    }
-    if (__any(down) && lane == 0) atomicOr(descends, 1u);
-    __syncthreads();
-    for (int k = threadIdx.x; k < 8 * 256; k += SJ_THREADS) { const uint32_t v = s_h[k]; if (v) atomicAdd(&hist[k], v); }
-}
+struct SjAccKeyOf {
+    const int32_t *tid, *acc;
+    __device__ __forceinline__ uint64_t key(int64_t i) const { return sj_acc_key(tid[i], acc[i]); }
+};
 
 constexpr int32_t SJ_FAR = 0x7fffffff;                   // no other row on the reference
 

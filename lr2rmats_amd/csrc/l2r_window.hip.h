@@ -24,8 +24,6 @@ __device__ __forceinline__ PipeArgsK pipe_args()
     return q;
 }
 
-constexpr int PIPE_KEY_CAP = 200;                        // dictionary entries a descriptor may ask for per dictionary (default)
-
 // A tile's window and descriptor (built in LDS by one wave of k_walk_slab, handed to k_probe_slab through HBM).
 struct TileWin {
     int4 hk[WIN_TX];             // {start, end, n, flags | rev << 8} on the tile's chromosome

@@ -156,3 +156,20 @@ def records_sam(rec, nh_seed=0):
         aux = ["NH:i:1"] if rec["uniq"][i] else ([] if rng.random() < 0.5 else ["NH:i:%d" % int(rng.integers(2, 10))])
         out.append(sam_line("q%d" % i, int(rec["flag"][i]), "chr%d" % (rec["tid"][i] + 1), int(rec["pos"][i]) + 1, cigar, aux))
     return "".join(out)
+
+
+def heavy_digit_rows(n, seed):
+    """(five row columns, key bytes that differ) for the radix passes: about 80 % of the n shuffled rows share the lowest byte of acc and
+    the lowest byte of tid -- in those two passes one digit value holds far more than 256 rows of every tile, so a row's rank crosses
+    waves and rounds -- and differ in the bytes above and in don; the other rows are spread over every byte in use; a tenth of the keys
+    comes twice.  A pass runs per key byte (tid, don, acc: twelve) that is not one value in every row."""
+    rng = np.random.default_rng(seed)
+    heavy = rng.random(n) < 0.8
+    acc = np.where(heavy, 0x2a | (rng.integers(0, 4096, n) << 8), rng.integers(0, 1 << 20, n)).astype(np.int32)
+    don = rng.integers(1, 60000, n).astype(np.int32)
+    tid = np.where(heavy, 7 | (rng.integers(0, 3, n) << 8), rng.integers(0, 700, n)).astype(np.int32)
+    for c in (tid, don, acc):
+        c[n - n // 10:] = c[:n // 10]                                      # one key in ten comes twice, a tile or more apart
+    rows = [tid, don, acc, rng.integers(0, 4, n).astype(np.int32), rng.integers(0, 4, n).astype(np.int32)]
+    differ = sum(len(np.unique((c.astype(np.int64) >> (8 * b)) & 0xff)) > 1 for c in (tid, don, acc) for b in range(4))
+    return rows, int(differ)

@@ -104,6 +104,23 @@ def test_numpy_form_equals_the_literal_one():
     assert len(got[0]) > 200 and len(rows) > 2 * len(got[0])
 
 
+def test_heavy_digit_rows_and_the_restatement():
+    """The input of the GPU tests of the scatter's rank across waves and rounds: what it promises, and that the restatement takes it."""
+    tile = 4096
+    n = 3 * tile + 17
+    for seed in (5, 6):
+        rows, differ = sc.heavy_digit_rows(n, seed)
+        assert differ == 7
+        for col in (rows[2], rows[0]):                                      # the lowest byte of acc, of tid
+            low = col & 0xff
+            assert np.bincount(low).max() > 0.75 * n and min(np.bincount(low[t:t + tile]).max() for t in (0, tile, 2 * tile)) > 10 * 256
+        got = sr.table_numpy(*rows)
+        assert len(got[0]) == n - n // 10 == len(np.unique(np.stack(rows[:3], axis=1), axis=0))
+        assert int(got[3].sum()) == int(rows[3].sum()) and int(got[4].sum()) == int(rows[4].sum())
+        key = [tuple(int(c[i]) for c in got[:3]) for i in range(len(got[0]))]
+        assert key == sorted(key)
+
+
 # ---------------------------------------------------------------------------------------------------- host library
 
 FASTA = ">chrB second in the header\nACGTacgt\nNNNN\n\n>chrA\r\nGGGG\r\nCC\n>empty\n>chrC desc\tx\nTTTTTTTTTT\nAC"      # no newline at the end

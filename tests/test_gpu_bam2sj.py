@@ -207,6 +207,20 @@ def test_sort_reduce_runs_across_tile_boundaries(eng):
         _table(eng, [c[:m] for c in rows])
 
 
+def test_sort_one_digit_value_holds_most_of_a_tile(eng):
+    """The scatter's rank across waves and rounds: two of the passes see one digit value in four rows of five."""
+    tile = _sort_tile()
+    n = 3 * tile + 17
+    rows, differ = sc.heavy_digit_rows(n, 5)
+    low = rows[2] & 0xff
+    assert differ == 7 and np.bincount(low).max() > 0.75 * n and np.bincount(low[:tile]).max() > 10 * 256
+    for pieces in (1, 7):
+        got = _table(eng, rows, pieces=pieces)
+        st = eng.sj_stats()
+        assert st["rows_in"] == n and st["rounds"] == 1 and st["radix_passes"] == differ
+    assert got.tid.size == len(np.unique(np.stack(rows[:3], axis=1), axis=0)) == n - n // 10
+
+
 # ---------------------------------------------------------------------------------------------------- 4 - 7: batches, size, chaining
 
 @pytest.fixture(scope="module")

@@ -175,6 +175,21 @@ def test_runs_across_tile_boundaries(eng):
     assert all(np.array_equal(getattr(got, c), getattr(again, c)) for c in NINE)
 
 
+def test_one_digit_value_holds_most_of_a_tile(eng):
+    """The six-column scatter's rank across waves and rounds: two of the passes see one digit value in four rows of five."""
+    tile = _sort_tile()
+    n = 3 * tile + 17
+    rows, differ = sc.heavy_digit_rows(n, 6)
+    rows.append(np.random.default_rng(7).integers(0, 100000, n).astype(np.int32))
+    low = rows[2] & 0xff
+    assert differ == 7 and np.bincount(low).max() > 0.75 * n and np.bincount(low[:tile]).max() > 10 * 256
+    for pieces in (1, 7):
+        got = _rows_table(eng, rows, pieces=pieces)                         # (the maximum overhang per key: st.table_numpy)
+        stats = eng.sj_stats()
+        assert stats["rows_in"] == n and stats["rounds"] == 1 and stats["radix_passes"] == differ
+    assert got.tid.size == n - n // 10 and len(set(got.max_over.tolist())) > 1000
+
+
 # ---------------------------------------------------------------------------------------------------- 2: at size; filter
 
 @pytest.fixture(scope="module")

@@ -40,6 +40,19 @@ def test_row_maximum_and_counts():
     assert st.table(st.rows_of(recs)) == [(0, 1001, 1100, 3, 1, 60)]
 
 
+def test_heavy_digit_rows_and_the_six_column_restatement():
+    """The input of test_gpu_sjtab's heavy-digit case: the restatement takes it, and its overhang per key is the maximum over the key's rows."""
+    n = 3 * 4096 + 17
+    rows, differ = sc.heavy_digit_rows(n, 6)
+    rows.append(np.random.default_rng(7).integers(0, 100000, n).astype(np.int32))
+    got = st.table_numpy(*rows)
+    assert differ == 7 and len(got[0]) == n - n // 10
+    want = {}
+    for t, d, a, v in zip(*[c.tolist() for c in (rows[0], rows[1], rows[2], rows[5])]):
+        want[(t, d, a)] = max(want.get((t, d, a), 0), v)
+    assert [int(v) for v in got[5]] == [want[k] for k in sorted(want)]
+
+
 # ---------------------------------------------------------------------------------------------------- category, keep rule
 
 def test_categories():

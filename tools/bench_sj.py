@@ -10,7 +10,7 @@ A second leg runs the same records through the table of `lr2rmats sjtab` (l2r_sj
 STAR's defaults for the distance and the intron-size lists, six columns per row instead of five) and prints a second JSON line
 ("leg": "sjtab"): the same figures, the device time of every new kernel, the ratio of its scatter passes to the plain leg's (24 / 20 by
 the bytes per row), and for the neighbour stage the rows it saw and dropped, the passes of the acceptor order, bytes moved / time per
-kernel and the acceptor order's time per row and pass beside k_sj_scatter's.  The synthetic table has no genome, so every row has motif 0.
+kernel and the acceptor order's time per row and pass beside k_radix_scatter<SjRows>'s.  The synthetic table has no genome, so every row has motif 0.
 L2R_BENCH_SJ_LEGS=plain runs the first leg only."""
 import json
 import os
@@ -151,7 +151,7 @@ moved2 = 15 * n + 4 * len(r["cig"]) + 24 * rows + (12 + passes2 * 52 + 16 + 32) 
 # the scatter; near_acc 4 B index + 8 gathered + 4 out; keep_near 8 + 4 + 2 in, 4 out; its take 27 B in over n1 and out over the kept rows
 n1 = len(kept.tid) + int(tm2["rows_dropped_near"])
 acc_passes = int(tm2["acc_radix_passes"])
-near_bytes = {"k_sj_acc_keys": 16 * n1, "acceptor order passes": acc_passes * 32 * n1, "k_sj_near_acc": 16 * n1, "k_sj_keep_near": 18 * n1}
+near_bytes = {"k_radix_keys<SjAccKeyOf>": 16 * n1, "acceptor order passes": acc_passes * 32 * n1, "k_sj_near_acc": 16 * n1, "k_sj_keep_near": 18 * n1}
 moved2 += sum(near_bytes.values()) + 27 * n1
 t0 = time.perf_counter()
 want6 = st.table_numpy(*st.rows_numpy(r["flag"], r["tid"], r["pos"], r["uniq"], r["cig_off"], r["cig"], pair_only=True))
@@ -168,12 +168,12 @@ line2 = dict(leg="sjtab", records=n, rows=int(st2["rows_made"]), table_rows=n_ta
              radix_passes=passes2, wall_s_median=walls2[len(walls2) // 2], wall_s_min=walls2[0], wall_s_max=walls2[-1],
              records_per_s=n / walls2[len(walls2) // 2], kernel_ms=kernel_ms2, bytes_moved=int(moved2),
              fraction_of_8TBs=(moved2 / (kernel_ms2 / 1e3)) / 8e12 if kernel_ms2 else 0.0,
-             scatter_ms=tm2["k_sj_scatter"], scatter_ms_plain=tm["k_sj_scatter"],
-             scatter_ratio_to_plain=(tm2["k_sj_scatter"] / passes2) / (tm["k_sj_scatter"] / passes) if passes and passes2 and tm["k_sj_scatter"] else 0.0,
+             scatter_ms=tm2["k_radix_scatter<SjRows>"], scatter_ms_plain=tm["k_radix_scatter<SjRows>"],
+             scatter_ratio_to_plain=(tm2["k_radix_scatter<SjRows>"] / passes2) / (tm["k_radix_scatter<SjRows>"] / passes) if passes and passes2 and tm["k_radix_scatter<SjRows>"] else 0.0,
              stage1_rows=n1, rows_dropped_near=int(tm2["rows_dropped_near"]), rows_dropped_long=int(tm2["rows_dropped_long"]), acc_radix_passes=acc_passes,
              near_GBs={k: (b / (tm2[k] / 1e3)) / 1e9 if tm2[k] else 0.0 for k, b in near_bytes.items()},
              acc_order_ps_per_row_pass=tm2["acceptor order passes"] * 1e9 / (n1 * acc_passes) if n1 and acc_passes else 0.0,
-             scatter_ps_per_row_pass=tm2["k_sj_scatter"] * 1e9 / (st2["rows_in"] * passes2) if passes2 and st2["rows_in"] else 0.0,
+             scatter_ps_per_row_pass=tm2["k_radix_scatter<SjRows>"] * 1e9 / (st2["rows_in"] * passes2) if passes2 and st2["rows_in"] else 0.0,
              numpy_restatement_s=numpy_s2, equals_numpy=bool(ok2))
 print("| kernel (sjtab leg) | ms (one round, every launch waited for) |\n|---|---|")
 for k, v in kern2.items():

@@ -56,9 +56,9 @@ for form, (f, t, p) in forms.items():
     line = dict(form=form, config=cfg_name, records=n, rounds=rounds, radix_passes=passes, in_order=int(tm["in_order"]),
                 call_s_median=walls[len(walls) // 2], call_s_min=walls[0], call_s_max=walls[-1], records_per_s_call=n / walls[len(walls) // 2],
                 kernel_ms=kernel_ms, kernel_ms_each={k: round(v, 4) for k, v in kern.items()},
-                scatter_ms_per_pass=tm["k_sort_scatter"] / passes if passes else 0.0,
+                scatter_ms_per_pass=tm["k_radix_scatter<SortRows>"] / passes if passes else 0.0,
                 scatter_bytes_per_row_and_pass=scatter_bytes / (passes * n) if passes else 0.0,
-                scatter_TB_per_s=(scatter_bytes / (tm["k_sort_scatter"] / 1e3)) / 1e12 if passes and tm["k_sort_scatter"] else 0.0,
+                scatter_TB_per_s=(scatter_bytes / (tm["k_radix_scatter<SortRows>"] / 1e3)) / 1e12 if passes and tm["k_radix_scatter<SortRows>"] else 0.0,
                 bytes_moved=int(moved), fraction_of_8TBs=(moved / (kernel_ms / 1e3)) / 8e12 if kernel_ms else 0.0,
                 numpy_stable_argsort_s=numpy_s, equals_numpy=bool(ok))
     print("| kernel (%s) | ms (one call, every launch waited for) |\n|---|---|" % form)
