@@ -443,6 +443,33 @@ def test_annotation_table_cache(oracle, tmp_path):
     assert run(af, reads, want) == 2
 
 
+def test_annotation_cache_file_is_the_stand_alone_tables(tmp_path):
+    """The cache file the engine writes for the toy annotation (tests/golden/toy) and the one tests/tables_dump.hip writes for the same
+    arrays have the same name -- the hash -- and the same bytes: the tables tests/test_tables_cpu.py checks member by member are the
+    tables the library stages."""
+    import os
+    from lr2rmats_amd import hostlib
+    from tests import test_tables_cpu as tc
+    exe = tc.build_tables_dump()
+    toy = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "toy")
+    job = hostlib.Job(["update-gtf", os.path.join(toy, "toy.sam"), os.path.join(toy, "original.gtf")], open_outputs=False)
+    anno = {name: v.copy() for name, v in job.annotation_arrays().items()}
+    job.close()
+    assert len(anno["tx_tid"]) == 4 and len(anno["ex_start"]) == 18
+    e = capi.Engine(0)
+    try:
+        e.set_annotation_cache(str(tmp_path / "engine"))
+        e.set_annotation(**anno)
+        assert e.annotation_cache_state() == 1
+    finally:
+        e.close()
+    got = tc._dump(exe, tc.Case(anno), tmp_path, tmp_path / "program")
+    assert int(got["rc"][0]) == 0 and int(got["state"][0]) == 1
+    files = os.listdir(tmp_path / "engine")
+    assert len(files) == 1 and files == os.listdir(tmp_path / "program")
+    assert (tmp_path / "engine" / files[0]).read_bytes() == (tmp_path / "program" / files[0]).read_bytes()
+
+
 @pytest.mark.parametrize("opts", [dict(), dict(min_intron=66000), dict(max_delet=69000), dict(min_intron=70001, max_delet=70000, min_exon=19)])
 def test_summaries_at_their_saturation_limits(engine, oracle, opts):
     """Summary fields saturate at 65535: an N or a D operation of 70 000 bases with thresholds on either side of it, a stretch of 18 bases against

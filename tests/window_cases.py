@@ -35,7 +35,7 @@ B0, B1 = LO_B << SITE_SHIFT, HI_B << SITE_SHIFT
 M, N_ = 0, 3
 
 
-# ---- the model: build_dict (l2r_engine.hip), the window scan and the slice bounds of make_descriptor (l2r_window.hip.h)
+# ---- the model: build_dict (l2r_tables.hip.h), the window scan and the slice bounds of make_descriptor (l2r_window.hip.h)
 
 def _parts(pairs, singles):
     """Entries of one dictionary as sorted keys (tid, k1, k2), one per part.  A key's members are its pairs and the singles with the
