@@ -442,6 +442,29 @@ typedef struct { int64_t n; const uint16_t *flag; const int32_t *tid, *pos; } l2
 int          l2r_sort_order(l2r_ctx *ctx, const l2r_sort_records *recs, uint32_t *order_out);  /* order_out[k] = record at rank k */
 int          l2r_sort_stats(l2r_ctx *ctx, double *out, int n);
 
+/* ---- `sort -n`, `filter -N`, `fusion -N` (host/sort.c): the name order of alignment records -- what `filter` and `fusion` want of their
+ * input (a read is a run of consecutive records with one name) and the reference leaves to `samtools sort -n` / `samtools collate`.
+ * Names are byte strings of 0..254 bytes without a NUL; two names are the same read iff they have the same length and bytes.  The name
+ * order is the permutation in which (1) records with one name are consecutive, (2) the groups follow each other by the input index of
+ * their first record, (3) the records of a group keep their input order.  Input that is grouped already gives the identity.  That is the
+ * whole definition: no equality with the output of any samtools release is claimed.
+ * l2r_name_order: name i = names[name_off[i], name_off[i + 1]); order_out[k] = index of the record at rank k (n words), *n_groups =
+ * distinct names.  On the device (csrc/l2r_names.hip.h): a seeded 64-bit hash per name, the radix passes of `sort` over the hashes in the
+ * context's sort buffers (L2R_SORT_FORCE=1 as there), head flags by hash and byte compare, and the groups placed by two scans.  A pair
+ * of neighbours with one hash and two names is a mismatch: with none the result is exact; otherwise the call runs once more with a
+ * second seed, and if that mismatches too the order is computed on the host (csrc/l2r_nameorder.hip.h).  All three routes give the same
+ * order.  n == 0 succeeds with *n_groups = 0.  n > 2^32 - 1 - L2R_SORT_TILE, a descending name_off, a name of more than 254 bytes or a
+ * null column with n > 0 fail before any column is read (the offsets apart) and before anything is launched.
+ * L2R_NAME_HASH_BITS=<0..64> (tests): only that many low bits of the hash are kept.
+ * l2r_name_stats, of the last l2r_name_order: out[0] rows, [1] groups, [2] radix passes run, [3] 1 where the order is the identity,
+ * [4] route (0 first seed, 1 second seed, 2 host), [5] mismatching pairs seen on the first seed; with L2R_SORT_TIMING=1 device
+ * milliseconds (summed over the seeds that ran) of [6] k_radix_keys<NameHashOf> [7] the passes [8] k_name_heads [9] the two k_scan_u32
+ * [10] k_name_firsts + k_name_sizes + k_name_place; n = words of out (up to 11). */
+#define L2R_NAME_MAX 254
+typedef struct { int64_t n; const int64_t *name_off /* n + 1 */; const uint8_t *names; } l2r_name_records;
+int          l2r_name_order(l2r_ctx *ctx, const l2r_name_records *recs, uint32_t *order_out, int64_t *n_groups);
+int          l2r_name_stats(l2r_ctx *ctx, double *out, int n);
+
 #ifdef __cplusplus
 }
 #endif

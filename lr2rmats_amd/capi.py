@@ -35,6 +35,7 @@ EXPORTS = [
     "l2r_sj_begin_tab", "l2r_sj_add_rows_over", "l2r_sj_annotate", "l2r_sj_filter_rows", "l2r_sj_download_tab", "l2r_sj_filter_rows2",
     "l2r_fusion_segments", "l2r_fusion_select", "l2r_fusion_stats",
     "l2r_sort_order", "l2r_sort_stats",
+    "l2r_name_order", "l2r_name_stats",
 ]
 SJ_E_UNKNOWN_TID = -3
 
@@ -133,6 +134,10 @@ class CSortRecords(C.Structure):
     _fields_ = [("n", C.c_int64), ("flag", C.c_void_p), ("tid", C.c_void_p), ("pos", C.c_void_p)]
 
 
+class CNameRecords(C.Structure):
+    _fields_ = [("n", C.c_int64), ("name_off", C.c_void_p), ("names", C.c_void_p)]
+
+
 class CTiming(C.Structure):
     _fields_ = [("stage_ms", C.c_float * N_STAGES), ("total_ms", C.c_float), ("iters", C.c_int32)]
 
@@ -207,6 +212,8 @@ def load_library():
         lib.l2r_sj_filter_rows2.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         lib.l2r_sort_order.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         lib.l2r_sort_stats.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
+        lib.l2r_name_order.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        lib.l2r_name_stats.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
         _lib = lib
     return _lib
 
@@ -256,6 +263,19 @@ SJ_STAT_NAMES = ["rows_made", "rounds", "radix_passes", "rows_in", "rows_out", "
 
 
 SORT_STAT_NAMES = ["rows", "radix_passes", "in_order", "k_radix_keys<SortKeyOf>", "k_radix_digit_hist<SortRows>", "k_scan_u32 (tile histograms)", "k_radix_scatter<SortRows>"]
+
+
+NAME_STAT_NAMES = ["rows", "groups", "radix_passes", "identity", "route", "mismatches", "k_radix_keys<NameHashOf>", "radix passes (hist + scan + scatter)",
+                   "k_name_heads", "k_scan_u32 (heads, sizes)", "k_name_firsts + k_name_sizes + k_name_place"]
+
+
+def pack_names(names):
+    """A sequence of byte strings as l2r_name_records wants them: (name_off int64 [n + 1], blob uint8)."""
+    names = [bytes(x) for x in names]
+    off = np.zeros(len(names) + 1, np.int64)
+    if names:
+        off[1:] = np.cumsum([len(x) for x in names])
+    return off, np.frombuffer(b"".join(names) + b"\0", np.uint8)[:int(off[-1])]
 
 
 def sort_keys(flag, tid, pos) -> np.ndarray:
@@ -486,6 +506,28 @@ class Engine:
         out = np.zeros(len(SORT_STAT_NAMES), np.float64)
         self._chk(self.lib.l2r_sort_stats(self.ctx, out.ctypes.data, len(out)))
         return {k: float(v) for k, v in zip(SORT_STAT_NAMES, out)}
+
+    # ---- `sort -n`, `filter -N`, `fusion -N` (include/lr2rmats_hip.h: l2r_name_order / l2r_name_stats)
+    def name_order(self, names):
+        """(order, n_groups): order[k] = index of the record at rank k in name order (uint32) -- records with one name consecutive, groups by
+        first appearance, input order inside a group.  ``names``: a sequence of byte strings, or (name_off, blob) as ``pack_names`` gives."""
+        off, blob = names if isinstance(names, tuple) else pack_names(names)
+        off = np.ascontiguousarray(off, np.int64)
+        blob = np.ascontiguousarray(blob, np.uint8)
+        n = int(off.shape[0]) - 1
+        keep = blob if blob.size else np.zeros(1, np.uint8)
+        recs = CNameRecords(n, off.ctypes.data, keep.ctypes.data)
+        order = np.zeros(max(n, 1), np.uint32)
+        groups = C.c_int64(0)
+        self._chk(self.lib.l2r_name_order(self.ctx, C.byref(recs), order.ctypes.data, C.byref(groups)))
+        return order[:n], int(groups.value)
+
+    def name_stats(self) -> dict:
+        """l2r_name_stats of the last name_order: rows, groups, passes run, identity, route (0 first seed, 1 second seed, 2 host), mismatching
+        pairs on the first seed, and with L2R_SORT_TIMING=1 device milliseconds per kernel."""
+        out = np.zeros(len(NAME_STAT_NAMES), np.float64)
+        self._chk(self.lib.l2r_name_stats(self.ctx, out.ctypes.data, len(out)))
+        return {k: float(v) for k, v in zip(NAME_STAT_NAMES, out)}
 
     def set_annotation_cache(self, directory) -> None:
         """Keep the annotation tables on disk under ``directory`` (None: off); see include/lr2rmats_hip.h."""

@@ -23,8 +23,10 @@
 #include "l2r_fusion.hip.h"
 #include "l2r_sj.hip.h"
 #include "l2r_sort.hip.h"
+#include "l2r_names.hip.h"
 #include "l2r_plan.hip.h"
 #include "l2r_tables.hip.h"
+#include "l2r_nameorder.hip.h"
 
 using namespace l2r;
 
@@ -122,6 +124,19 @@ struct SortState {
     double stats[7] = {0};                              // l2r_sort_stats
     hipEvent_t ev[2] = {nullptr, nullptr};
     ~SortState() { for (int k = 0; k < 2; ++k) if (ev[k]) (void)hipEventDestroy(ev[k]); }
+};
+
+// `sort -n`, `filter -N`, `fusion -N` (l2r_names.hip.h): the buffers of l2r_name_order beside those of SortState, which hold the hashes
+// and the index column of the passes.  They belong to the context, grow on demand and are used again by the next call.
+struct NameState {
+    DevBuf<uint64_t> blob, hkey;                        // the name bytes as aligned words; the hashes in record order
+    DevBuf<int64_t> off;
+    DevBuf<uint32_t> head, head_pos, first_idx, sizes, order;
+    DevBuf<uint32_t> word;                              // word[0]: groups (the first scan's total), [1]: mismatching pairs, [2]: a record moved, [3]: the second scan's total
+    bool timing = false;
+    double stats[11] = {0};                             // l2r_name_stats
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    ~NameState() { for (int k = 0; k < 2; ++k) if (ev[k]) (void)hipEventDestroy(ev[k]); }
 };
 
 // What l2r_sync has learned from the counters of a completed run of the tile path (fetch_run_facts): a later run of the same inputs,
@@ -273,6 +288,7 @@ struct l2r_ctx {
     SjIntrons sj_intr;                      // `sjtab`: l2r_sj_annotate
     double fusion_stats[5] = {0, 0, 0, 0, 0};        // `fusion`: l2r_fusion_stats
     SortState sort;                         // `sort`, `filter -S`
+    NameState name;                         // `sort -n`, `filter -N`, `fusion -N`
 };
 
 // What completed runs have shown about the tile path's lists and the inexact tiles: forgotten wherever inputs, parameters or outputs change
@@ -2073,6 +2089,24 @@ int l2r_sj_filter_rows(l2r_ctx *c, const l2r_sj_filter *f, int64_t *n_rows)
 
 static int sort_passes(l2r_ctx *c, SortState &s, uint32_t n, int *n_pass_out, bool *in_order_out, int *src_out);
 
+// sort_passes in the context's sort buffers for another entry point (the acceptor order of `sjtab -d`, the hash order of `sort -n`): what
+// l2r_sort_stats says of the last l2r_sort_order stays, and with `timing` the device milliseconds of the passes are added to *ms
+static int sort_passes_beside(l2r_ctx *c, bool timing, double *ms, uint32_t n, int *n_pass_out, int *src_out)
+{
+    SortState &o = c->sort;
+    double sort_stats[sizeof o.stats / sizeof o.stats[0]];
+    const bool sort_timing = o.timing;
+    std::copy(std::begin(o.stats), std::end(o.stats), sort_stats);
+    for (double &v : o.stats) v = 0;
+    o.timing = timing;
+    bool in_order = false;
+    const int rc = sort_passes(c, o, n, n_pass_out, &in_order, src_out);
+    *ms += o.stats[SORTS_K_HIST] + o.stats[SORTS_K_SCAN] + o.stats[SORTS_K_SCATTER];
+    std::copy(std::begin(sort_stats), std::end(sort_stats), o.stats);
+    o.timing = sort_timing;
+    return rc;
+}
+
 // The neighbour stage over the rows the row-local stage left (s.rows[s.cur], sorted by (tid, don, acc)).
 static int sj_filter_near(l2r_ctx *c, const SjFilter2 &g)
 {
@@ -2091,18 +2125,8 @@ static int sj_filter_near(l2r_ctx *c, const SjFilter2 &g)
             hipLaunchKernelGGL(k_radix_keys<SjAccKeyOf>, dim3(std::min(grid, 2048u)), dim3(RADIX_THREADS), 0, c->stream, SjAccKeyOf{t.tid, t.acc}, (int64_t)n, o.key[0].p, o.hist.p,
                                o.hist.p + SORT_KEY_BYTES * 256);
         }))) return rc;
-    // the passes are those of `sort`, in its buffers; what l2r_sort_stats says of the last l2r_sort_order stays
-    double sort_stats[sizeof o.stats / sizeof o.stats[0]];
-    const bool sort_timing = o.timing;
-    std::copy(std::begin(o.stats), std::end(o.stats), sort_stats);
-    for (double &v : o.stats) v = 0;
-    o.timing = s.timing;
-    int n_pass = 0, src = 0; bool in_order = false;
-    rc = sort_passes(c, o, n, &n_pass, &in_order, &src);
-    s.stats[SJS_K_ACC_ORDER] += o.stats[SORTS_K_HIST] + o.stats[SORTS_K_SCAN] + o.stats[SORTS_K_SCATTER];
-    std::copy(std::begin(sort_stats), std::end(sort_stats), o.stats);
-    o.timing = sort_timing;
-    if (rc) return rc;
+    int n_pass = 0, src = 0;
+    if ((rc = sort_passes_beside(c, s.timing, &s.stats[SJS_K_ACC_ORDER], n, &n_pass, &src))) return rc;
     s.stats[SJS_ACC_PASSES] = n_pass;
     const uint32_t *idx = n_pass ? o.idx[src].p : nullptr;
     if ((rc = timed_launch(c, s.timing, s.ev, &s.stats[SJS_K_NEAR_ACC], [&] {
@@ -2282,6 +2306,112 @@ int l2r_sort_stats(l2r_ctx *c, double *out, int n)
 {
     if (!c || !out || n < 0) return fail(-1, "[l2r_sort_stats] bad argument");
     for (int k = 0; k < n; ++k) out[k] = k < SORTS_N ? c->sort.stats[k] : 0.0;
+    return 0;
+}
+
+// ---------------------------------------------------------------------------------------------- sort -n, filter -N, fusion -N
+// slots of l2r_name_stats
+enum { NAMES_ROWS = 0, NAMES_GROUPS, NAMES_PASSES, NAMES_IDENTITY, NAMES_ROUTE, NAMES_MISMATCH, NAMES_K_HASH, NAMES_K_PASSES, NAMES_K_HEADS, NAMES_K_SCANS, NAMES_K_PLACE, NAMES_N };
+static_assert(NAMES_N == sizeof(NameState::stats) / sizeof(double), "l2r_name_stats: the words of include/lr2rmats_hip.h");
+
+// One run over the names on the device with one seed: the order in m.order, *groups, *mismatch (pairs with one hash and two names: the
+// order is exact iff 0), *moved (0: the identity).
+static int name_order_seeded(l2r_ctx *c, uint32_t n, int64_t off0, uint64_t seed, uint64_t mask, uint32_t *groups, uint32_t *mismatch, uint32_t *moved)
+{
+    NameState &m = c->name;
+    SortState &o = c->sort;
+    const size_t N = n;
+    const unsigned grid = (unsigned)((N + NAME_THREADS - 1) / NAME_THREADS);
+    const NameCols cols{m.blob.p, m.off.p, off0};
+    int rc;
+    HIP_TRY(hipMemsetAsync(o.hist.p, 0, (SORT_KEY_BYTES * 256 + 1) * sizeof(uint32_t), c->stream));
+    HIP_TRY(hipMemsetAsync(m.word.p, 0, 4 * sizeof(uint32_t), c->stream));
+    // the hashes, which of their bytes differ at all, whether they descend anywhere; a copy in record order for k_name_heads (the passes
+    // use both key columns in turn)
+    if ((rc = timed_launch(c, m.timing, m.ev, &m.stats[NAMES_K_HASH], [&] {
+            hipLaunchKernelGGL(k_radix_keys<NameHashOf>, dim3(std::min(grid, 2048u)), dim3(RADIX_THREADS), 0, c->stream, NameHashOf{cols, seed, mask}, (int64_t)n, o.key[0].p, o.hist.p,
+                               o.hist.p + SORT_KEY_BYTES * 256);
+        }, c->check_stages))) return rc;
+    HIP_TRY(hipMemcpyAsync(m.hkey.p, o.key[0].p, N * sizeof(uint64_t), hipMemcpyDeviceToDevice, c->stream));
+    int n_pass = 0, src = 0;
+    if ((rc = sort_passes_beside(c, m.timing, &m.stats[NAMES_K_PASSES], n, &n_pass, &src))) return rc;
+    m.stats[NAMES_PASSES] = n_pass;
+    const uint32_t *idx = n_pass ? o.idx[src].p : nullptr;
+    if ((rc = timed_launch(c, m.timing, m.ev, &m.stats[NAMES_K_HEADS], [&] {
+            hipLaunchKernelGGL(k_name_heads, dim3(grid), dim3(NAME_THREADS), 0, c->stream, cols, (const uint64_t *)m.hkey.p, idx, n, m.head.p, m.word.p + 1);
+        }, c->check_stages))) return rc;
+    if ((rc = timed_launch(c, m.timing, m.ev, &m.stats[NAMES_K_SCANS], [&] { scan_u32(c, m.head.p, (int64_t)n, m.word.p); }, c->check_stages))) return rc;
+    HIP_TRY(hipMemsetAsync(m.sizes.p, 0, (N + 1) * sizeof(uint32_t), c->stream));
+    if ((rc = timed_launch(c, m.timing, m.ev, &m.stats[NAMES_K_PLACE], [&] {
+            hipLaunchKernelGGL(k_name_firsts, dim3(grid), dim3(NAME_THREADS), 0, c->stream, (const uint32_t *)m.head.p, idx, n, m.head_pos.p, m.first_idx.p);
+            hipLaunchKernelGGL(k_name_sizes, dim3(grid), dim3(NAME_THREADS), 0, c->stream, (const uint32_t *)m.head.p, (const uint32_t *)m.head_pos.p, (const uint32_t *)m.first_idx.p, n, m.sizes.p);
+        }, c->check_stages))) return rc;
+    if ((rc = timed_launch(c, m.timing, m.ev, &m.stats[NAMES_K_SCANS], [&] { scan_u32(c, m.sizes.p, (int64_t)n, m.word.p + 3); }, c->check_stages))) return rc;
+    if ((rc = timed_launch(c, m.timing, m.ev, &m.stats[NAMES_K_PLACE], [&] {
+            hipLaunchKernelGGL(k_name_place, dim3(grid), dim3(NAME_THREADS), 0, c->stream, (const uint32_t *)m.head.p, idx, (const uint32_t *)m.head_pos.p, (const uint32_t *)m.first_idx.p,
+                               (const uint32_t *)m.sizes.p, n, m.order.p, m.word.p + 2);
+        }, c->check_stages))) return rc;
+    uint32_t w[4];
+    HIP_TRY(hipMemcpyAsync(w, m.word.p, sizeof w, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    *groups = w[0]; *mismatch = w[1]; *moved = w[2];
+    return 0;
+}
+
+int l2r_name_order(l2r_ctx *c, const l2r_name_records *r, uint32_t *order_out, int64_t *n_groups)
+{
+    if (!c) return fail(-1, "[l2r_name_order] null argument");
+    NameState &m = c->name;
+    for (double &v : m.stats) v = 0;
+    {   std::string msg;
+        if (name_check(r, order_out, n_groups, msg)) return fail(-1, "%s", msg.c_str()); }
+    *n_groups = 0;
+    if (r->n == 0) { m.stats[NAMES_IDENTITY] = 1; return 0; }
+    const char *e = getenv("L2R_SORT_TIMING");
+    m.timing = e && atoi(e) != 0;
+    uint64_t mask = ~0ull;
+    if ((e = getenv("L2R_NAME_HASH_BITS"))) { const int b = atoi(e); mask = b >= 64 ? ~0ull : b <= 0 ? 0ull : (1ull << b) - 1ull; }
+    HIP_TRY(hipSetDevice(c->device));
+    SortState &o = c->sort;
+    for (int k = 0; k < 2; ++k) { if (!m.ev[k]) HIP_TRY(hipEventCreate(&m.ev[k])); if (!o.ev[k]) HIP_TRY(hipEventCreate(&o.ev[k])); }
+    const size_t N = (size_t)r->n;
+    const uint32_t n = (uint32_t)r->n;
+    const int64_t off0 = r->name_off[0];
+    const size_t bytes = (size_t)(r->name_off[N] - off0);
+    m.stats[NAMES_ROWS] = (double)r->n;
+    int rc;
+    if ((rc = to_dev(c, m.off, r->name_off, N + 1))) return rc;
+    if (m.blob.ensure((bytes + NAME_BLOB_ROOM + 7) / 8)) return -2;
+    if (bytes) HIP_TRY(hipMemcpyAsync(m.blob.p, r->names + off0, bytes, hipMemcpyHostToDevice, c->stream));
+    if (o.key[0].ensure(N) || o.hist.ensure(SORT_KEY_BYTES * 256 + 1) || o.word.ensure(4) || m.hkey.ensure(N) || m.head.ensure(N + 1) || m.head_pos.ensure(N + 1) ||
+        m.first_idx.ensure(N) || m.sizes.ensure(N + 1) || m.order.ensure(N) || m.word.ensure(4)) return -2;
+    static const uint64_t seeds[2] = {0x243f6a8885a308d3ull, 0x13198a2e03707344ull};
+    uint32_t groups = 0, mismatch = 1, moved = 1;
+    int route = 0;
+    for (; route < 2 && mismatch; ++route) {
+        if ((rc = name_order_seeded(c, n, off0, seeds[route], mask, &groups, &mismatch, &moved))) return rc;
+        if (route == 0) m.stats[NAMES_MISMATCH] = (double)mismatch;
+    }
+    if (mismatch) {                                                 // both seeds left a pair with one hash and two names: the exact routine
+        *n_groups = name_order_host(r->n, r->name_off, r->names, order_out);
+        moved = 0;
+        for (size_t i = 0; i < N && !moved; ++i) moved = order_out[i] != (uint32_t)i;
+        m.stats[NAMES_ROUTE] = 2;
+    } else {
+        HIP_TRY(hipMemcpyAsync(order_out, m.order.p, N * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        *n_groups = (int64_t)groups;
+        m.stats[NAMES_ROUTE] = route - 1;
+    }
+    m.stats[NAMES_GROUPS] = (double)*n_groups;
+    m.stats[NAMES_IDENTITY] = moved ? 0 : 1;
+    return 0;
+}
+
+int l2r_name_stats(l2r_ctx *c, double *out, int n)
+{
+    if (!c || !out || n < 0) return fail(-1, "[l2r_name_stats] bad argument");
+    for (int k = 0; k < n; ++k) out[k] = k < NAMES_N ? c->name.stats[k] : 0.0;
     return 0;
 }
 

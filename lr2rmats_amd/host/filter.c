@@ -38,6 +38,8 @@ static int filter_usage(void)
     fprintf(stderr, "         -i --intron     [INT]      minimum number of intron indicated by the alignment. [%d]\n", MIN_INTRON_NUM);
     fprintf(stderr, "         -r --remove-gtf [STR]      remove all the alignment record that overlap with transcript in this GTF file. [NONE]\n");
     fprintf(stderr, "         -S --sorted                write the retained alignments sorted by coordinate (as `%s sort` does). [False]\n", "lr2rmats");
+    fprintf(stderr, "         -N --group-names           group the records by read name first (as `%s sort -n` does): for input that is not\n", "lr2rmats");
+    fprintf(stderr, "                                    name-grouped, such as a coordinate-sorted BAM. [False]\n");
     fprintf(stderr, "\n");
     return 1;
 }
@@ -629,6 +631,11 @@ int h_filter_run(const char *in_fn, const char *remove_fn, const l2r_filter_para
 
 int h_filter_run_sorted(const char *in_fn, const char *remove_fn, const l2r_filter_params *prm, int sorted, FILE *out, int64_t *n_written)
 {
+    return h_filter_run_named(in_fn, remove_fn, prm, sorted, 0, out, n_written);
+}
+
+int h_filter_run_named(const char *in_fn, const char *remove_fn, const l2r_filter_params *prm, int sorted, int by_name, FILE *out, int64_t *n_written)
+{
     h_chroms chr; memset(&chr, 0, sizeof chr);
     h_records r;
     h_stage_time("start");
@@ -666,6 +673,13 @@ int h_filter_run_sorted(const char *in_fn, const char *remove_fn, const l2r_filt
     l2r_filter_records fr = { r.n, r.n_cig, r.flag, r.tid, r.pos, r.l_qseq, r.nm, r.cig_off, r.cig };
     if (l2r_filter_score(ctx, &fr, prm, spans.n ? &spans : NULL, drop, score, intron)) h_fatal("bam_filter", "%s", l2r_last_error());
     h_stage_time("engine: score (upload, kernel, download)");
+    int64_t *by = NULL;
+    if (by_name) {                                           /* -N: what `samtools sort -n` does in front of the reference's filter */
+        by = (int64_t *)h_malloc((size_t)(r.n + 1) * 8);
+        h_name_order(ctx, &r, by, "bam_filter");
+        if (!sorted) h_records_set_grouped(&r, "bam_filter");
+        h_stage_time("engine: name order (upload, kernels, download)");
+    }
     /* kept records, and the runs of one read name among them */
     int64_t n_kept = 0;
     for (int64_t i = 0; i < r.n; ++i) n_kept += !drop[i];
@@ -673,13 +687,16 @@ int h_filter_run_sorted(const char *in_fn, const char *remove_fn, const l2r_filt
     int32_t *k_score = (int32_t *)h_malloc((size_t)(n_kept + 1) * 4), *k_intron = (int32_t *)h_malloc((size_t)(n_kept + 1) * 4);
     int64_t m = 0, n_groups = 0;
     const char *last = NULL;
-    for (int64_t i = 0; i < r.n; ++i) if (!drop[i]) {
+    for (int64_t at = 0; at < r.n; ++at) {
+        const int64_t i = by ? by[at] : at;
+        if (drop[i]) continue;
         const char *name = (const char *)(r.buf + r.rec_off[i] + 4 + 32);
         if (!last || strcmp(name, last) != 0) goff[n_groups++] = m;
         kept[m] = i; k_score[m] = score[i]; k_intron[m] = intron[i]; ++m;
         last = name;
     }
     goff[n_groups] = m;
+    free(by);
     h_stage_time("groups of one read name");
     int64_t *winner = (int64_t *)h_malloc((size_t)(n_groups + 1) * 8);
     if (l2r_filter_select(ctx, n_groups, goff, k_score, k_intron, prm, winner)) h_fatal("bam_filter", "%s", l2r_last_error());
@@ -712,13 +729,13 @@ int h_cmd_filter(int argc, char **argv)
 {
     static const struct option long_opt[] = {
         { "coverage", 1, NULL, 'v' }, { "map-quality", 1, NULL, 'q' }, { "sec-rat", 1, NULL, 's' }, { "intron", 1, NULL, 'i' },
-        { "remove-gtf", 1, NULL, 'r' }, { "sorted", 0, NULL, 'S' }, { 0, 0, 0, 0 }
+        { "remove-gtf", 1, NULL, 'r' }, { "sorted", 0, NULL, 'S' }, { "group-names", 0, NULL, 'N' }, { 0, 0, 0, 0 }
     };
     l2r_filter_params prm = { (float)COV_RATIO, (float)MAP_QUAL, (float)SEC_RATIO, MIN_INTRON_NUM };
     char remove_fn[1024] = "";
-    int c, sorted = 0;
+    int c, sorted = 0, by_name = 0;
     optind = 1;
-    while ((c = getopt_long(argc, argv, "v:q:s:i:r:S", long_opt, NULL)) >= 0) {
+    while ((c = getopt_long(argc, argv, "v:q:s:i:r:SN", long_opt, NULL)) >= 0) {
         switch (c) {
         case 'v': prm.cov_rate = (float)atof(optarg); break;
         case 'q': prm.map_qual = (float)atof(optarg); break;
@@ -726,12 +743,13 @@ int h_cmd_filter(int argc, char **argv)
         case 'i': prm.min_intron_n = atoi(optarg); break;
         case 'r': snprintf(remove_fn, sizeof remove_fn, "%s", optarg); break;
         case 'S': sorted = 1; break;
+        case 'N': by_name = 1; break;
         default: return filter_usage();
         }
     }
     if (argc - optind != 1) return filter_usage();
     int64_t cnt = 0;
-    const int rc = h_filter_run_sorted(argv[optind], remove_fn, &prm, sorted, stdout, &cnt);
+    const int rc = h_filter_run_named(argv[optind], remove_fn, &prm, sorted, by_name, stdout, &cnt);
     fprintf(stderr, "[%s] Filtered alignments: %d\n", "bam_filter", (int)cnt);
     return rc;
 }

@@ -35,6 +35,7 @@ static int fusion_usage(void)
     fprintf(stderr, "         -d --dis         [INT]      minimum distance of two fusion parts. [%s]\n", FUSION_DIS_STR);
     fprintf(stderr, "         -f --fusion-site [STR]      output fusion site file. [NULL]\n");
     fprintf(stderr, "         -g --gtf         [STR]      gene annotation in GTF format. [None]\n");
+    fprintf(stderr, "         -N --group-names            group the records by read name first (input that is not name-grouped). [false]\n");
     fprintf(stderr, "\n");
     /* (one line of our own: what the text above promises and the reference's option loop does not do) */
     fprintf(stderr, "Note:    -d and -g are listed above but not accepted (src/bam_fusion.c:148,153); gene names from -g are outside the MI355X build as well.\n\n");
@@ -45,9 +46,15 @@ static inline const char *rec_name(const h_records *r, int64_t i) { return (cons
 
 int64_t h_fusion_groups(const h_records *r, const int32_t *qlen, int64_t *rows, int64_t *group_off, int32_t *rlen)
 {
+    return h_fusion_groups_in(r, qlen, NULL, rows, group_off, rlen);
+}
+
+int64_t h_fusion_groups_in(const h_records *r, const int32_t *qlen, const int64_t *order, int64_t *rows, int64_t *group_off, int32_t *rlen)
+{
     int64_t m = 0, n_groups = 0;
     const char *last = NULL;
-    for (int64_t i = 0; i < r->n; ++i) {
+    for (int64_t at = 0; at < r->n; ++at) {
+        const int64_t i = order ? order[at] : at;
         if (r->flag[i] & 4) continue;
         const char *name = rec_name(r, i);
         if (!last || strcmp(name, last) != 0) {
@@ -70,6 +77,11 @@ int64_t h_fusion_groups(const h_records *r, const int32_t *qlen, int64_t *rows, 
 
 int h_fusion_run(const char *in_fn, const l2r_fusion_params *prm, FILE *out, FILE *site, int64_t *n_pairs)
 {
+    return h_fusion_run_named(in_fn, prm, 0, out, site, n_pairs);
+}
+
+int h_fusion_run_named(const char *in_fn, const l2r_fusion_params *prm, int by_name, FILE *out, FILE *site, int64_t *n_pairs)
+{
     h_chroms chr; memset(&chr, 0, sizeof chr);
     h_records r;
     h_stage_time("start");
@@ -87,7 +99,15 @@ int h_fusion_run(const char *in_fn, const l2r_fusion_params *prm, FILE *out, FIL
     h_stage_time("engine: segments (upload, kernel, download)");
     int64_t *rows = (int64_t *)h_malloc(n1 * 8), *goff = (int64_t *)h_malloc((n1 + 1) * 8);
     int32_t *rlen = (int32_t *)h_malloc(n1 * 4);
-    const int64_t n_groups = h_fusion_groups(&r, ql, rows, goff, rlen);
+    int64_t *by = NULL;
+    if (by_name) {                                                   /* -N: what `samtools sort -n` does in front of the reference's fusion */
+        by = (int64_t *)h_malloc(n1 * 8);
+        h_name_order(ctx, &r, by, "bam_fusion");
+        h_records_set_grouped(&r, "bam_fusion");
+        h_stage_time("engine: name order (upload, kernels, download)");
+    }
+    const int64_t n_groups = h_fusion_groups_in(&r, ql, by, rows, goff, rlen);
+    free(by);
     const int64_t m = goff[n_groups];
     /* the columns of the rows (the mapped records) */
     int32_t *g = (int32_t *)h_malloc(((size_t)m + 1) * 4 * 7);
@@ -127,14 +147,15 @@ int h_cmd_fusion(int argc, char **argv)
 {
     /* src/bam_fusion.c:42-49,148-159: --fusion-site and --gtf are not in the table, and `-d` / `--dis` reach a switch that tests 's' */
     static const struct option long_opt[] = {
-        { "ovlp-frac", 1, NULL, 'o' }, { "each-cov", 1, NULL, 'v' }, { "all-cov", 1, NULL, 'V' }, { "dis", 1, NULL, 'd' }, { 0, 0, 0, 0 }
+        { "ovlp-frac", 1, NULL, 'o' }, { "each-cov", 1, NULL, 'v' }, { "all-cov", 1, NULL, 'V' }, { "dis", 1, NULL, 'd' }, { "group-names", 0, NULL, 'N' }, { 0, 0, 0, 0 }
     };
     l2r_fusion_params prm = { (float)OVLP_FRAC, (float)EACH_COV, (float)ALL_COV, FUSION_DIS };
     FILE *site = NULL;
-    int c;
+    int c, by_name = 0;
     optind = 1;
-    while ((c = getopt_long(argc, argv, "o:v:V:d:f:", long_opt, NULL)) >= 0) {
+    while ((c = getopt_long(argc, argv, "o:v:V:d:f:N", long_opt, NULL)) >= 0) {
         switch (c) {
+        case 'N': by_name = 1; break;
         case 'o': prm.ovlp_frac = (float)atof(optarg); break;
         case 'v': prm.each_cov = (float)atof(optarg); break;
         case 'V': prm.all_cov = (float)atof(optarg); break;
@@ -148,7 +169,7 @@ int h_cmd_fusion(int argc, char **argv)
     }
     if (argc - optind != 1) { if (site) fclose(site); return fusion_usage(); }
     int64_t cnt = 0;
-    const int rc = h_fusion_run(argv[optind], &prm, stdout, site, &cnt);
+    const int rc = h_fusion_run_named(argv[optind], &prm, by_name, stdout, site, &cnt);
     fprintf(stderr, "[%s] Candidate gene-fusion transcripts: %d\n", "bam_fusion", (int)cnt);
     if (site && fclose(site) != 0) return 1;
     return rc;

@@ -85,6 +85,9 @@ int  h_records_to_bam(const char *in_fn, const char *out_fn);
 int  h_filter_run(const char *in_fn, const char *remove_fn, const l2r_filter_params *prm, FILE *out, int64_t *n_written);
 /* `filter -S`: sorted != 0 -> the records that are written come in coordinate order and the header says so (sort.c) */
 int  h_filter_run_sorted(const char *in_fn, const char *remove_fn, const l2r_filter_params *prm, int sorted, FILE *out, int64_t *n_written);
+/* `filter -N`: by_name != 0 -> the records are put into name order (h_name_order) before the runs of one read name are formed; without
+ * -S the output is in that order and its header says SO:unsorted GO:query */
+int  h_filter_run_named(const char *in_fn, const char *remove_fn, const l2r_filter_params *prm, int sorted, int by_name, FILE *out, int64_t *n_written);
 
 /* ---- `sort`, `sort-check`, `filter -S` (sort.c).  The order: ascending h_sort_key, records with equal keys in input order.
  * h_sort_key: (tid < 0 ? 0x7fffffff : tid) << 33 | (uint32)(pos + 1) << 1 | (flag >> 4 & 1) -- the key of l2r_sort_order.
@@ -101,13 +104,35 @@ void h_records_set_coordinate(h_records *r, const char *who);
 void h_sort_order(l2r_ctx *ctx, const h_records *r, const int64_t *rows, int64_t n, int64_t *sorted, const char *who);
 int  h_sort_run(const char *in_fn, FILE *out, int64_t *n_written);
 
+/* ---- `sort -n`, `sort-check -n`, `filter -N`, `fusion -N` (sort.c).  The name order: records with one read name consecutive, the
+ * groups by the input index of their first record, input order inside a group (l2r_name_order, include/lr2rmats_hip.h).
+ * h_header_grouped (no GPU): the BAM header block with SO:unsorted and GO:query in its @HD line -- each field replaced where present
+ * and appended where not, a text without an @HD line gets "@HD\tVN:1.6\tSO:unsorted\tGO:query" as its first line; returns the bytes
+ * of the new block (at most hdr_len + H_HEADER_GO_ROOM) and writes them to `out` where out_cap holds them; -1: not a BAM header block.
+ * h_records_set_grouped: the same on the header of records in memory.
+ * h_name_order: order[k] = the record at rank k of the name order, by l2r_name_order on `ctx`; returns the groups.
+ * h_name_grouped (no GPU): -1 where every name's records are consecutive, else the first record whose name was seen in an earlier,
+ * already closed group; *n_groups = runs of one name.
+ * h_sort_run_named: h_sort_run, or with by_name != 0 the name order (*n_groups = reads). */
+#define H_HEADER_GO_ROOM 48
+int64_t h_header_grouped(const uint8_t *hdr, size_t hdr_len, uint8_t *out, size_t out_cap);
+void h_records_set_grouped(h_records *r, const char *who);
+int64_t h_name_order(l2r_ctx *ctx, const h_records *r, int64_t *order, const char *who);
+int64_t h_name_grouped(const h_records *r, int64_t *n_groups);
+int  h_sort_run_named(const char *in_fn, int by_name, FILE *out, int64_t *n_written, int64_t *n_groups);
+
 /* ---- `fusion` (fusion.c).  h_fusion_groups (no GPU): the runs of consecutive MAPPED records with one read name -- rows[k] = record
  * of row k, group g = rows [group_off[g], group_off[g + 1]), rlen[g] = query length (M I S = X) of its first record, taken from
  * `qlen` (one word per record, as l2r_fusion_segments leaves it) or, with qlen NULL, from that record's CIGAR; the three
  * outputs hold r->n, r->n + 1 and r->n words; returns the groups */
 int64_t h_fusion_groups(const h_records *r, const int32_t *qlen, int64_t *rows, int64_t *group_off, int32_t *rlen);
+/* the same over the records in the order order[0..r->n) (NULL: file order) */
+int64_t h_fusion_groups_in(const h_records *r, const int32_t *qlen, const int64_t *order, int64_t *rows, int64_t *group_off, int32_t *rlen);
 /* the BAM stream to `out`, the site table to `site` (NULL: none); *n_pairs = candidates */
 int  h_fusion_run(const char *in_fn, const l2r_fusion_params *prm, FILE *out, FILE *site, int64_t *n_pairs);
+/* `fusion -N`: by_name != 0 -> the records are put into name order (h_name_order) before the groups are formed, and the header says
+ * SO:unsorted GO:query */
+int  h_fusion_run_named(const char *in_fn, const l2r_fusion_params *prm, int by_name, FILE *out, FILE *site, int64_t *n_pairs);
 
 /* ---- `bam2sj` (sj.c): FASTA, a record source whose memory is bounded by the batch, the reference's junction list */
 typedef struct { int32_t n_seq; int64_t *seq_off; uint8_t *bases; char **name; } h_fasta;      /* sequences in FILE order; seq_off: n_seq + 1 */

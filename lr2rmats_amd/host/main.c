@@ -13,8 +13,8 @@ int main(int argc, char **argv)
         fprintf(stderr, "         bam2gtf      generate transcript and exon information based on BAM/SAM file\n");
         fprintf(stderr, "         bam2sj       generate splice-junction information based on BAM/SAM file\n");
         fprintf(stderr, "         sjtab        generate the filtered splice-junction table that update-gtf -j reads\n");
-        fprintf(stderr, "         sort         sort alignment records by coordinate, the order update-gtf wants\n");
-        fprintf(stderr, "         sort-check   tell whether alignment records are sorted by coordinate\n\n");
+        fprintf(stderr, "         sort         sort alignment records by coordinate, the order update-gtf wants (-n: group them by read name)\n");
+        fprintf(stderr, "         sort-check   tell whether alignment records are sorted by coordinate (-n: grouped by read name)\n\n");
         return 1;
     }
     return h_main(argc - 1, argv + 1);

@@ -93,6 +93,10 @@ def load_library():
         lib.h_header_coordinate.restype = C.c_int64
         lib.h_sort_key.argtypes = [C.c_int32, C.c_int32, C.c_uint32]
         lib.h_sort_key.restype = C.c_uint64
+        lib.h_header_grouped.argtypes = [C.c_char_p, C.c_size_t, C.c_void_p, C.c_size_t]
+        lib.h_header_grouped.restype = C.c_int64
+        lib.h_name_grouped.argtypes = [C.c_void_p, C.POINTER(C.c_int64)]
+        lib.h_name_grouped.restype = C.c_int64
         _lib = lib
     return _lib
 
@@ -230,6 +234,31 @@ def header_coordinate(block: bytes):
 def sort_key(tid: int, pos: int, flag: int) -> int:
     """The 64-bit key of one record as the host computes it (h_sort_key; ``sort-check`` walks these)."""
     return int(load_library().h_sort_key(tid, pos, flag))
+
+
+# ---- `sort -n`, `sort-check -n`, `filter -N`, `fusion -N` (host/sort.c): the header rewrite and the grouping check (no GPU)
+
+HEADER_GO_ROOM = 48
+
+
+def header_grouped(block: bytes):
+    """The BAM header block with SO:unsorted and GO:query in its @HD line (h_header_grouped); None where the bytes are no such block."""
+    lib = load_library()
+    out = C.create_string_buffer(len(block) + HEADER_GO_ROOM)
+    n = int(lib.h_header_grouped(block, len(block), out, len(out)))
+    return None if n < 0 else out.raw[:n]
+
+
+def name_grouped(path: str):
+    """(bad, n_groups) of a SAM / gzip SAM / BAM file as ``sort-check -n`` sees it (h_read_records + h_name_grouped): bad = -1 where every
+    name's records are consecutive, else the first record whose name was seen in an earlier group; n_groups = runs of one name."""
+    lib = load_library()
+    chr_, r = _CChroms(), _CRecords()
+    lib.h_read_records(path.encode(), C.byref(chr_), C.byref(r), b"name_grouped")
+    g = C.c_int64(0)
+    bad = int(lib.h_name_grouped(C.byref(r), C.byref(g)))
+    lib.h_records_free(C.byref(r)); lib.h_chroms_free(C.byref(chr_))
+    return bad, int(g.value)
 
 
 class Job:
