@@ -465,6 +465,43 @@ typedef struct { int64_t n; const int64_t *name_off /* n + 1 */; const uint8_t *
 int          l2r_name_order(l2r_ctx *ctx, const l2r_name_records *recs, uint32_t *order_out, int64_t *n_groups);
 int          l2r_name_stats(l2r_ctx *ctx, double *out, int n);
 
+/* ---- `sort-gtf`, `sort-gtf-check` (host/gtfsort.c): GTF text merged and put into the order update-gtf, unique-gtf and STAR read it in --
+ * the step the reference pipeline runs as a shell script after every concatenation of GTF files.  Inside the domain below the rows,
+ * written as h_gtf_write_rows writes them, are that script's output byte for byte (tests/golden/sort_gtf).
+ * The text is one byte string (several files: concatenated byte for byte).  Lines end at '\n', a last line without one counts, line
+ * numbers start at 1 and count every line.  Fields are runs of bytes other than space and tab (leading blanks are skipped).
+ *   kept line        byte 0 is not '#', and the third field contains "transcript" anywhere or equals "exon" (case-sensitive)
+ *   transcript line  a kept line whose third field equals "transcript".  It sets the current key (c, s, e): s, e = its fourth and fifth
+ *                    fields as decimal numbers; c = the rank of its first field: chr1..chr22 1..22, chrX 23, chrY 24, chrM 25, any
+ *                    other name 26, 27, ... by its first appearance on a transcript line
+ *   key of a line    every kept line carries the current key of the last transcript line at or before it, (0, 0, 0) before the first;
+ *                    a kept line that is no transcript line never has its own columns 1, 4, 5 looked at
+ *   order            kept lines by (c, s, e, line number)
+ *   domain           on a transcript line fields four and five are non-empty strings of decimal digits of value <= 4294967295 (leading
+ *                    zeros allowed), and the text holds no NUL byte; anything else is an error that names the smallest such line
+ * l2r_gtf_order: *n_rows = kept lines; the rows are held by the context until the next call and fetched with l2r_gtf_rows_out (cap < n
+ * fails and writes nothing).  n_bytes == 0 succeeds with no rows; a negative size or a null text with a positive size fails before
+ * anything is read.  On the device (csrc/l2r_gtf.hip.h): the text is uploaded once; newlines are counted and line starts written per
+ * tile of L2R_GTF_TILE bytes, one thread per line parses its first five fields, scans compact kept lines and transcripts (which is the
+ * carry-forward of the key), the transcripts whose name differs from their predecessor's go to the host to be ranked, and where any row
+ * is below its predecessor two stable radix stages (e, then c << 32 | s) run in the context's sort buffers (L2R_SORT_FORCE=1 as there).
+ * Texts of 2^32 - 64 bytes and more, more kept rows than one sort takes (2^32 - 1 - L2R_SORT_TILE), and L2R_GTF_ROUTE=host (tests) take
+ * the exact host routine (csrc/l2r_gtforder.hip.h): same rows, same errors.
+ * l2r_gtf_check needs no context and no GPU: 0 where the kept lines are in the order already (*line = 0), 1 where not (*line = the
+ * first kept line whose key is below its predecessor's), negative on a domain error.  counts (null, or 4 words): lines, kept rows,
+ * transcript lines, distinct chromosome names.
+ * l2r_gtf_stats, of the last l2r_gtf_order: out[0] bytes, [1] lines, [2] kept rows, [3] transcript lines, [4] heads sent to the host,
+ * [5] distinct names ranked beyond the table, [6] passes of stage 1, [7] passes of stage 2, [8] 1 where the order is the identity,
+ * [9] route (0 device, 1 host); with L2R_SORT_TIMING=1 device milliseconds of [10] k_gtf_count + k_gtf_starts [11] k_gtf_fields
+ * [12] the k_scan_u32 [13] k_gtf_rows + heads + k_gtf_triples [14] the two key kernels and all passes [15] k_gtf_compose. */
+#define L2R_GTF_TILE 16384              /* bytes of text one workgroup of the line kernels takes */
+typedef struct { int64_t n_bytes; const uint8_t *text; } l2r_gtf_text;
+typedef struct { int64_t cap, n; uint64_t *start; uint32_t *len; uint32_t *line; } l2r_gtf_rows;   /* kept lines in the order: offset, length without '\n', 1-based line number */
+int          l2r_gtf_order(l2r_ctx *ctx, const l2r_gtf_text *text, int64_t *n_rows);
+int          l2r_gtf_rows_out(l2r_ctx *ctx, l2r_gtf_rows *rows);          /* of the last l2r_gtf_order; cap < n fails and writes nothing */
+int          l2r_gtf_stats(l2r_ctx *ctx, double *out, int n);
+int          l2r_gtf_check(const l2r_gtf_text *text, int64_t *line, int64_t *counts);
+
 #ifdef __cplusplus
 }
 #endif

@@ -36,6 +36,7 @@ EXPORTS = [
     "l2r_fusion_segments", "l2r_fusion_select", "l2r_fusion_stats",
     "l2r_sort_order", "l2r_sort_stats",
     "l2r_name_order", "l2r_name_stats",
+    "l2r_gtf_order", "l2r_gtf_rows_out", "l2r_gtf_stats", "l2r_gtf_check",
 ]
 SJ_E_UNKNOWN_TID = -3
 
@@ -138,6 +139,14 @@ class CNameRecords(C.Structure):
     _fields_ = [("n", C.c_int64), ("name_off", C.c_void_p), ("names", C.c_void_p)]
 
 
+class CGtfText(C.Structure):
+    _fields_ = [("n_bytes", C.c_int64), ("text", C.c_void_p)]
+
+
+class CGtfRows(C.Structure):
+    _fields_ = [("cap", C.c_int64), ("n", C.c_int64), ("start", C.c_void_p), ("len", C.c_void_p), ("line", C.c_void_p)]
+
+
 class CTiming(C.Structure):
     _fields_ = [("stage_ms", C.c_float * N_STAGES), ("total_ms", C.c_float), ("iters", C.c_int32)]
 
@@ -214,6 +223,10 @@ def load_library():
         lib.l2r_sort_stats.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
         lib.l2r_name_order.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         lib.l2r_name_stats.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
+        lib.l2r_gtf_order.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        lib.l2r_gtf_rows_out.argtypes = [C.c_void_p, C.c_void_p]
+        lib.l2r_gtf_stats.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
+        lib.l2r_gtf_check.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         _lib = lib
     return _lib
 
@@ -267,6 +280,38 @@ SORT_STAT_NAMES = ["rows", "radix_passes", "in_order", "k_radix_keys<SortKeyOf>"
 
 NAME_STAT_NAMES = ["rows", "groups", "radix_passes", "identity", "route", "mismatches", "k_radix_keys<NameHashOf>", "radix passes (hist + scan + scatter)",
                    "k_name_heads", "k_scan_u32 (heads, sizes)", "k_name_firsts + k_name_sizes + k_name_place"]
+
+
+GTF_STAT_NAMES = ["bytes", "lines", "rows", "transcripts", "heads", "names_beyond_table", "passes_stage1", "passes_stage2", "identity", "route",
+                  "k_gtf_count + k_gtf_starts", "k_gtf_fields", "k_scan_u32 (tiles, kept + transcripts, heads)", "k_gtf_rows + heads + k_gtf_triples",
+                  "key kernels + radix passes", "k_gtf_compose", "names"]
+
+
+def header_define(name: str) -> int:
+    """The value of an integer #define of include/lr2rmats_hip.h."""
+    import re
+    text = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "lr2rmats_hip.h")).read()
+    return int(re.search(r"^#define\s+%s\s+(\d+)" % name, text, re.M).group(1))
+
+
+def gtf_bytes(text) -> np.ndarray:
+    """The bytes of a GTF text as an array, without a copy (an empty text gets one byte to point at)."""
+    return np.frombuffer(text, np.uint8) if len(text) else np.zeros(1, np.uint8)
+
+
+def gtf_check(text: bytes):
+    """(in_order, line, counts) of GTF text as ``sort-gtf-check`` sees it (l2r_gtf_check: no context, no GPU): line = the first kept line
+    whose key is below its predecessor's (0: none); counts = lines, kept rows, transcript lines, chromosome names.  A text outside the
+    domain raises RuntimeError with the engine's message."""
+    lib = load_library()
+    buf = gtf_bytes(text)
+    t = CGtfText(len(text), buf.ctypes.data)
+    line = C.c_int64(0)
+    counts = np.zeros(4, np.int64)
+    rc = lib.l2r_gtf_check(C.byref(t), C.byref(line), counts.ctypes.data)
+    if rc < 0:
+        raise RuntimeError(lib.l2r_last_error().decode())
+    return rc == 0, int(line.value), [int(v) for v in counts]
 
 
 def pack_names(names):
@@ -528,6 +573,30 @@ class Engine:
         out = np.zeros(len(NAME_STAT_NAMES), np.float64)
         self._chk(self.lib.l2r_name_stats(self.ctx, out.ctypes.data, len(out)))
         return {k: float(v) for k, v in zip(NAME_STAT_NAMES, out)}
+
+    # ---- `sort-gtf` (include/lr2rmats_hip.h: l2r_gtf_order / l2r_gtf_rows_out / l2r_gtf_stats)
+    def gtf_order(self, text):
+        """(start uint64, length uint32, line uint32): the kept lines of GTF text (bytes, several files concatenated) in the order
+        update-gtf wants -- by (chromosome rank, start, end) of the last transcript line at or before them, then by line number.
+        A text outside the domain raises RuntimeError naming the smallest bad line."""
+        buf = gtf_bytes(text)
+        t = CGtfText(len(text), buf.ctypes.data)
+        n_rows = C.c_int64(0)
+        self._chk(self.lib.l2r_gtf_order(self.ctx, C.byref(t), C.byref(n_rows)))
+        r = int(n_rows.value)
+        start, length, line = np.zeros(max(r, 1), np.uint64), np.zeros(max(r, 1), np.uint32), np.zeros(max(r, 1), np.uint32)
+        rows = CGtfRows(r, 0, start.ctypes.data, length.ctypes.data, line.ctypes.data)
+        self._chk(self.lib.l2r_gtf_rows_out(self.ctx, C.byref(rows)))
+        assert int(rows.n) == r
+        return start[:r], length[:r], line[:r]
+
+    def gtf_stats(self) -> dict:
+        """l2r_gtf_stats of the last gtf_order: bytes, lines, kept rows, transcript lines, heads sent to the host, names ranked beyond the
+        table, passes of both stages, identity, route (0 device, 1 host), with L2R_SORT_TIMING=1 device milliseconds per kernel group,
+        and the distinct chromosome names."""
+        out = np.zeros(len(GTF_STAT_NAMES), np.float64)
+        self._chk(self.lib.l2r_gtf_stats(self.ctx, out.ctypes.data, len(out)))
+        return {k: float(v) for k, v in zip(GTF_STAT_NAMES, out)}
 
     def set_annotation_cache(self, directory) -> None:
         """Keep the annotation tables on disk under ``directory`` (None: off); see include/lr2rmats_hip.h."""

@@ -24,9 +24,11 @@
 #include "l2r_sj.hip.h"
 #include "l2r_sort.hip.h"
 #include "l2r_names.hip.h"
+#include "l2r_gtf.hip.h"
 #include "l2r_plan.hip.h"
 #include "l2r_tables.hip.h"
 #include "l2r_nameorder.hip.h"
+#include "l2r_gtforder.hip.h"
 
 using namespace l2r;
 
@@ -137,6 +139,25 @@ struct NameState {
     double stats[11] = {0};                             // l2r_name_stats
     hipEvent_t ev[2] = {nullptr, nullptr};
     ~NameState() { for (int k = 0; k < 2; ++k) if (ev[k]) (void)hipEventDestroy(ev[k]); }
+};
+
+// `sort-gtf` (l2r_gtf.hip.h): the buffers of l2r_gtf_order beside those of SortState, which hold the keys and the index columns of its
+// two radix stages, and the rows of the last call on the host (l2r_gtf_rows_out).  They belong to the context, grow on demand and are
+// used again by the next call.
+struct GtfState {
+    DevBuf<uint4> text;                                 // the text, 16-byte aligned, GTF_TEXT_ROOM zeroed bytes behind it
+    DevBuf<uint32_t> tile_cnt, start;                   // newlines per tile (scanned in place); line starts
+    DevBuf<uint32_t> kept, tx, l_name_off, l_name_len, l_s, l_e;      // per line
+    DevBuf<uint32_t> r_start, r_len, r_line, r_tx;      // per kept line
+    DevBuf<uint32_t> t_name_off, t_name_len, t_s, t_e, head;          // per transcript line
+    DevBuf<uint32_t> h_off, h_len, rank;                // per head
+    DevBuf<uint32_t> c, s, e, order1, order;            // per kept line: the triple, stage 1's order, the order
+    DevBuf<uint32_t> word;                              // GTFW_*
+    std::vector<uint64_t> res_start; std::vector<uint32_t> res_len, res_line;        // the rows of the last call, in the order
+    bool timing = false;
+    double stats[17] = {0};                             // l2r_gtf_stats
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    ~GtfState() { for (int k = 0; k < 2; ++k) if (ev[k]) (void)hipEventDestroy(ev[k]); }
 };
 
 // What l2r_sync has learned from the counters of a completed run of the tile path (fetch_run_facts): a later run of the same inputs,
@@ -289,6 +310,7 @@ struct l2r_ctx {
     double fusion_stats[5] = {0, 0, 0, 0, 0};        // `fusion`: l2r_fusion_stats
     SortState sort;                         // `sort`, `filter -S`
     NameState name;                         // `sort -n`, `filter -N`, `fusion -N`
+    GtfState gtf;                           // `sort-gtf`
 };
 
 // What completed runs have shown about the tile path's lists and the inexact tiles: forgotten wherever inputs, parameters or outputs change
@@ -2413,6 +2435,237 @@ int l2r_name_stats(l2r_ctx *c, double *out, int n)
     if (!c || !out || n < 0) return fail(-1, "[l2r_name_stats] bad argument");
     for (int k = 0; k < n; ++k) out[k] = k < NAMES_N ? c->name.stats[k] : 0.0;
     return 0;
+}
+
+// ---------------------------------------------------------------------------------------------- sort-gtf
+// slots of l2r_gtf_stats
+enum { GTFS_BYTES = 0, GTFS_LINES, GTFS_ROWS, GTFS_TX, GTFS_HEADS, GTFS_BEYOND, GTFS_PASSES1, GTFS_PASSES2, GTFS_IDENTITY, GTFS_ROUTE,
+       GTFS_K_LINES, GTFS_K_FIELDS, GTFS_K_SCANS, GTFS_K_ROWS, GTFS_K_SORT, GTFS_K_COMPOSE, GTFS_NAMES, GTFS_N };
+static_assert(GTFS_N == sizeof(GtfState::stats) / sizeof(double) && GTFS_K_LINES == 10, "l2r_gtf_stats: the words of include/lr2rmats_hip.h");
+// words of GtfState::word
+enum { GTFW_NEWLINES = 0, GTFW_NUL, GTFW_BAD_LINE, GTFW_ROWS, GTFW_TX, GTFW_HEADS, GTFW_DESCENDS, GTFW_N };
+
+// the host route: the exact routine of l2r_gtforder.hip.h
+static int gtf_order_on_host(l2r_ctx *c, const l2r_gtf_text *t, int64_t *n_rows)
+{
+    GtfState &m = c->gtf;
+    GtfOrder o;
+    std::string msg;
+    if (gtf_order_host(t->text, (uint64_t)t->n_bytes, o, msg)) return fail(-1, "%s", msg.c_str());
+    m.res_start.swap(o.start); m.res_len.swap(o.len); m.res_line.swap(o.line);
+    m.stats[GTFS_LINES] = (double)o.n_lines; m.stats[GTFS_ROWS] = (double)m.res_start.size(); m.stats[GTFS_TX] = (double)o.n_tx;
+    m.stats[GTFS_HEADS] = (double)o.n_heads; m.stats[GTFS_BEYOND] = (double)o.n_beyond; m.stats[GTFS_NAMES] = (double)o.n_names;
+    m.stats[GTFS_IDENTITY] = o.descent_line ? 0 : 1;
+    m.stats[GTFS_ROUTE] = 1;
+    *n_rows = (int64_t)m.res_start.size();
+    return 0;
+}
+
+// One stable stage of the order: the keys are in the sort buffers (k_radix_keys has run); *idx = the order it leaves, null: the identity
+static int gtf_stage(l2r_ctx *c, uint32_t n, int stat, const uint32_t **idx)
+{
+    GtfState &m = c->gtf;
+    int n_pass = 0, src = 0, rc;
+    if ((rc = sort_passes_beside(c, m.timing, &m.stats[GTFS_K_SORT], n, &n_pass, &src))) return rc;
+    m.stats[stat] = n_pass;
+    *idx = n_pass ? c->sort.idx[src].p : nullptr;
+    return 0;
+}
+
+int l2r_gtf_order(l2r_ctx *c, const l2r_gtf_text *t, int64_t *n_rows)
+{
+    if (!c) return fail(-1, "[l2r_gtf_order] null argument");
+    GtfState &m = c->gtf;
+    for (double &v : m.stats) v = 0;
+    m.res_start.clear(); m.res_len.clear(); m.res_line.clear();
+    {   std::string msg;
+        if (gtf_check(t, n_rows, msg)) return fail(-1, "%s", msg.c_str()); }
+    *n_rows = 0;
+    m.stats[GTFS_BYTES] = (double)t->n_bytes;
+    if (t->n_bytes == 0) { m.stats[GTFS_IDENTITY] = 1; return 0; }
+    const char *e = getenv("L2R_GTF_ROUTE");
+    if ((e && strcmp(e, "host") == 0) || !gtf_text_fits_device(t->n_bytes)) return gtf_order_on_host(c, t, n_rows);
+    e = getenv("L2R_SORT_TIMING");
+    m.timing = e && atoi(e) != 0;
+    e = getenv("L2R_SORT_FORCE");
+    const bool force = e && atoi(e) != 0;
+    HIP_TRY(hipSetDevice(c->device));
+    SortState &o = c->sort;
+    for (int k = 0; k < 2; ++k) { if (!m.ev[k]) HIP_TRY(hipEventCreate(&m.ev[k])); if (!o.ev[k]) HIP_TRY(hipEventCreate(&o.ev[k])); }
+    const uint32_t n = (uint32_t)t->n_bytes;
+    const size_t n_words = ((size_t)n + GTF_TEXT_ROOM + 15) / 16;
+    const unsigned n_tiles = (unsigned)(((size_t)n + GTF_TILE - 1) / GTF_TILE);
+    int rc;
+    // ---- lines
+    if (m.text.ensure(n_words) || m.tile_cnt.ensure((size_t)n_tiles + 1) || m.word.ensure(GTFW_N)) return -2;
+    HIP_TRY(hipMemsetAsync((uint8_t *)m.text.p + n, 0, n_words * 16 - n, c->stream));
+    HIP_TRY(hipMemcpyAsync(m.text.p, t->text, n, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemsetAsync(m.word.p, 0, GTFW_N * sizeof(uint32_t), c->stream));
+    HIP_TRY(hipMemsetAsync(m.word.p + GTFW_BAD_LINE, 0xff, sizeof(uint32_t), c->stream));
+    const uint8_t *text8 = (const uint8_t *)m.text.p;
+    if ((rc = timed_launch(c, m.timing, m.ev, &m.stats[GTFS_K_LINES], [&] {
+            hipLaunchKernelGGL(k_gtf_count, dim3(n_tiles), dim3(GTF_THREADS), 0, c->stream, (const uint4 *)m.text.p, n, m.tile_cnt.p, m.word.p + GTFW_NUL);
+        }, c->check_stages))) return rc;
+    if ((rc = timed_launch(c, m.timing, m.ev, &m.stats[GTFS_K_SCANS], [&] { scan_u32(c, m.tile_cnt.p, (int64_t)n_tiles, m.word.p + GTFW_NEWLINES); }, c->check_stages))) return rc;
+    uint32_t w[GTFW_N];
+    HIP_TRY(hipMemcpyAsync(w, m.word.p, sizeof w, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    const uint32_t open_end = t->text[n - 1] != '\n' ? 1u : 0u;
+    if ((uint64_t)w[GTFW_NEWLINES] > (uint64_t)n) return fail(-2, "[l2r_gtf_order] %u newlines in %u bytes", w[GTFW_NEWLINES], n);
+    const uint32_t L = w[GTFW_NEWLINES] + open_end;                 // (>= 1: the text is not empty; <= n < 2^32 - 64)
+    const size_t NL = L;
+    const unsigned grid_l = (unsigned)((NL + GTF_THREADS - 1) / GTF_THREADS);
+    m.stats[GTFS_LINES] = (double)L;
+    if (m.start.ensure(NL + 1) || m.kept.ensure(NL + 1) || m.tx.ensure(NL + 1) || m.l_name_off.ensure(NL) || m.l_name_len.ensure(NL) || m.l_s.ensure(NL) || m.l_e.ensure(NL)) return -2;
+    if ((rc = timed_launch(c, m.timing, m.ev, &m.stats[GTFS_K_LINES], [&] {
+            hipLaunchKernelGGL(k_gtf_starts, dim3(n_tiles), dim3(GTF_THREADS), 0, c->stream, (const uint4 *)m.text.p, n, (const uint32_t *)m.tile_cnt.p, L, open_end, m.start.p);
+        }, c->check_stages))) return rc;
+    // ---- fields
+    const GtfLineCols lines{m.kept.p, m.tx.p, m.l_name_off.p, m.l_name_len.p, m.l_s.p, m.l_e.p};
+    if ((rc = timed_launch(c, m.timing, m.ev, &m.stats[GTFS_K_FIELDS], [&] {
+            hipLaunchKernelGGL(k_gtf_fields, dim3(grid_l), dim3(GTF_THREADS), 0, c->stream, text8, n, (const uint32_t *)m.start.p, L, lines, m.word.p + GTFW_BAD_LINE);
+        }, c->check_stages))) return rc;
+    // ---- compaction and carry: both scans in one launch
+    if ((rc = timed_launch(c, m.timing, m.ev, &m.stats[GTFS_K_SCANS], [&] {
+            ScanJobs jobs = {}; jobs.job[0] = ScanJob{m.kept.p, (int64_t)L, m.word.p + GTFW_ROWS}; jobs.job[1] = ScanJob{m.tx.p, (int64_t)L, m.word.p + GTFW_TX};
+            hipLaunchKernelGGL(k_scan_u32, dim3(2), dim3(1024), 0, c->stream, jobs);
+        }, c->check_stages))) return rc;
+    HIP_TRY(hipMemcpyAsync(w, m.word.p, sizeof w, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    {   // the domain: the smallest of the first line with a NUL byte and the first bad transcript line
+        int64_t bad = w[GTFW_BAD_LINE] == 0xffffffffu ? 0 : (int64_t)w[GTFW_BAD_LINE];
+        if (w[GTFW_NUL]) { const int64_t z = gtf_first_nul_line(t->text, n); if (z && (!bad || z < bad)) bad = z; }
+        if (bad) {
+            uint64_t lb = 0, le = 0;
+            std::string msg;
+            if (!gtf_find_line(t->text, n, bad, &lb, &le)) return fail(-2, "[l2r_gtf_order] the device names line %lld of %u", (long long)bad, L);
+            (void)gtf_line_error(t->text, lb, le, bad, msg);
+            return fail(-1, "%s", msg.c_str());
+        }
+    }
+    const uint32_t R = w[GTFW_ROWS], T = w[GTFW_TX];
+    if (R > L || T > R) return fail(-2, "[l2r_gtf_order] %u rows and %u transcripts of %u lines", R, T, L);
+    m.stats[GTFS_ROWS] = (double)R; m.stats[GTFS_TX] = (double)T;
+    if (R == 0) { m.stats[GTFS_IDENTITY] = 1; return 0; }
+    if (!gtf_rows_fit_device((int64_t)R)) { for (double &v : m.stats) v = 0; m.stats[GTFS_BYTES] = (double)t->n_bytes; return gtf_order_on_host(c, t, n_rows); }
+    const size_t NR = R, NT = T;
+    const unsigned grid_r = (unsigned)((NR + GTF_THREADS - 1) / GTF_THREADS), grid_t = (unsigned)((NT + GTF_THREADS - 1) / GTF_THREADS);
+    if (m.r_start.ensure(NR) || m.r_len.ensure(NR) || m.r_line.ensure(NR) || m.r_tx.ensure(NR) || m.t_name_off.ensure(NT) || m.t_name_len.ensure(NT) || m.t_s.ensure(NT) || m.t_e.ensure(NT) ||
+        m.head.ensure(NT + 1) || m.c.ensure(NR) || m.s.ensure(NR) || m.e.ensure(NR)) return -2;
+    const GtfTxCols txs{m.t_name_off.p, m.t_name_len.p, m.t_s.p, m.t_e.p};
+    if ((rc = timed_launch(c, m.timing, m.ev, &m.stats[GTFS_K_ROWS], [&] {
+            hipLaunchKernelGGL(k_gtf_rows, dim3(grid_l), dim3(GTF_THREADS), 0, c->stream, (const uint32_t *)m.start.p, n, L, (const uint32_t *)m.kept.p, (const uint32_t *)m.tx.p, lines, R, T,
+                               GtfRowCols{m.r_start.p, m.r_len.p, m.r_line.p, m.r_tx.p}, txs);
+            if (T) hipLaunchKernelGGL(k_gtf_chr_heads, dim3(grid_t), dim3(GTF_THREADS), 0, c->stream, text8, n, txs, T, m.head.p);
+        }, c->check_stages))) return rc;
+    // ---- chromosome ranks: the heads to the host, one word per head back
+    uint32_t H = 0;
+    if (T) {
+        if ((rc = timed_launch(c, m.timing, m.ev, &m.stats[GTFS_K_SCANS], [&] { scan_u32(c, m.head.p, (int64_t)T, m.word.p + GTFW_HEADS); }, c->check_stages))) return rc;
+        HIP_TRY(hipMemcpyAsync(&H, m.word.p + GTFW_HEADS, sizeof H, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        if (H == 0 || H > T) return fail(-2, "[l2r_gtf_order] %u heads of %u transcripts", H, T);
+        if (m.h_off.ensure(H) || m.h_len.ensure(H) || m.rank.ensure(H)) return -2;
+        if ((rc = timed_launch(c, m.timing, m.ev, &m.stats[GTFS_K_ROWS], [&] {
+                hipLaunchKernelGGL(k_gtf_head_take, dim3(grid_t), dim3(GTF_THREADS), 0, c->stream, (const uint32_t *)m.head.p, txs, T, H, m.h_off.p, m.h_len.p);
+            }, c->check_stages))) return rc;
+        std::vector<uint32_t> off(H), len(H), rank(H);
+        HIP_TRY(hipMemcpyAsync(off.data(), m.h_off.p, (size_t)H * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipMemcpyAsync(len.data(), m.h_len.p, (size_t)H * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        GtfChrRanks ranks;
+        if (gtf_rank_heads(t->text, n, off.data(), len.data(), H, rank.data(), ranks)) return fail(-2, "[l2r_gtf_order] a head's name reaches beyond the text");
+        m.stats[GTFS_BEYOND] = (double)ranks.beyond; m.stats[GTFS_NAMES] = (double)ranks.distinct();
+        HIP_TRY(hipMemcpyAsync(m.rank.p, rank.data(), (size_t)H * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));                   // (rank is this scope's)
+    }
+    m.stats[GTFS_HEADS] = (double)H;
+    // ---- keys and order
+    if ((rc = timed_launch(c, m.timing, m.ev, &m.stats[GTFS_K_ROWS], [&] {
+            hipLaunchKernelGGL(k_gtf_triples, dim3(grid_r), dim3(GTF_THREADS), 0, c->stream,
+                               GtfTripleIn{m.r_tx.p, m.head.p, m.rank.p, m.t_s.p, m.t_e.p, T, H}, R, m.c.p, m.s.p, m.e.p, m.word.p + GTFW_DESCENDS);
+        }, c->check_stages))) return rc;
+    uint32_t descends = 0;
+    HIP_TRY(hipMemcpyAsync(&descends, m.word.p + GTFW_DESCENDS, sizeof descends, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    m.stats[GTFS_IDENTITY] = descends ? 0 : 1;
+    const bool sorted = descends || force;
+    if (sorted) {
+        if (o.key[0].ensure(NR) || o.hist.ensure(SORT_KEY_BYTES * 256 + 1) || o.word.ensure(4) || m.order1.ensure(NR) || m.order.ensure(NR)) return -2;
+        const unsigned grid_k = std::min(grid_r, 2048u);
+        const uint32_t *order1 = nullptr, *perm2 = nullptr;
+        // stage 1: by e
+        HIP_TRY(hipMemsetAsync(o.hist.p, 0, (SORT_KEY_BYTES * 256 + 1) * sizeof(uint32_t), c->stream));
+        if ((rc = timed_launch(c, m.timing, m.ev, &m.stats[GTFS_K_SORT], [&] {
+                hipLaunchKernelGGL(k_radix_keys<GtfEndKeyOf>, dim3(grid_k), dim3(RADIX_THREADS), 0, c->stream, GtfEndKeyOf{m.e.p}, (int64_t)R, o.key[0].p, o.hist.p, o.hist.p + SORT_KEY_BYTES * 256);
+            }, c->check_stages))) return rc;
+        if ((rc = gtf_stage(c, R, GTFS_PASSES1, &order1))) return rc;
+        if (order1) {                                               // (stage 2 runs in the same index columns)
+            HIP_TRY(hipMemcpyAsync(m.order1.p, order1, NR * sizeof(uint32_t), hipMemcpyDeviceToDevice, c->stream));
+            order1 = m.order1.p;
+        }
+        // stage 2: by c << 32 | s, read through stage 1's order
+        HIP_TRY(hipMemsetAsync(o.hist.p, 0, (SORT_KEY_BYTES * 256 + 1) * sizeof(uint32_t), c->stream));
+        if ((rc = timed_launch(c, m.timing, m.ev, &m.stats[GTFS_K_SORT], [&] {
+                hipLaunchKernelGGL(k_radix_keys<GtfChrStartKeyOf>, dim3(grid_k), dim3(RADIX_THREADS), 0, c->stream, GtfChrStartKeyOf{m.c.p, m.s.p, order1, R}, (int64_t)R, o.key[0].p, o.hist.p,
+                                   o.hist.p + SORT_KEY_BYTES * 256);
+            }, c->check_stages))) return rc;
+        if ((rc = gtf_stage(c, R, GTFS_PASSES2, &perm2))) return rc;
+        if ((rc = timed_launch(c, m.timing, m.ev, &m.stats[GTFS_K_COMPOSE], [&] {
+                hipLaunchKernelGGL(k_gtf_compose, dim3(grid_r), dim3(GTF_THREADS), 0, c->stream, order1, perm2, R, m.order.p);
+            }, c->check_stages))) return rc;
+    }
+    // ---- the rows, in the order
+    std::vector<uint32_t> r_start(NR), r_len(NR), r_line(NR), order(sorted ? NR : 0);
+    HIP_TRY(hipMemcpyAsync(r_start.data(), m.r_start.p, NR * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(r_len.data(), m.r_len.p, NR * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(r_line.data(), m.r_line.p, NR * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    if (sorted) HIP_TRY(hipMemcpyAsync(order.data(), m.order.p, NR * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    m.res_start.resize(NR); m.res_len.resize(NR); m.res_line.resize(NR);
+    for (size_t k = 0; k < NR; ++k) {
+        const size_t r = sorted ? order[k] : k;
+        if (r >= NR) { m.res_start.clear(); m.res_len.clear(); m.res_line.clear(); return fail(-2, "[l2r_gtf_order] rank %zu holds row %zu of %zu", k, r, NR); }
+        m.res_start[k] = r_start[r]; m.res_len[k] = r_len[r]; m.res_line[k] = r_line[r];
+    }
+    *n_rows = (int64_t)R;
+    return 0;
+}
+
+int l2r_gtf_rows_out(l2r_ctx *c, l2r_gtf_rows *rows)
+{
+    if (!c || !rows) return fail(-1, "[l2r_gtf_rows_out] null argument");
+    const GtfState &m = c->gtf;
+    const size_t N = m.res_start.size();
+    if (rows->cap < (int64_t)N) return fail(-1, "[l2r_gtf_rows_out] room for %lld rows, the last l2r_gtf_order left %zu", (long long)rows->cap, N);
+    if (N && (!rows->start || !rows->len || !rows->line)) return fail(-1, "[l2r_gtf_rows_out] null column");
+    if (N) {
+        memcpy(rows->start, m.res_start.data(), N * sizeof(uint64_t));
+        memcpy(rows->len, m.res_len.data(), N * sizeof(uint32_t));
+        memcpy(rows->line, m.res_line.data(), N * sizeof(uint32_t));
+    }
+    rows->n = (int64_t)N;
+    return 0;
+}
+
+int l2r_gtf_stats(l2r_ctx *c, double *out, int n)
+{
+    if (!c || !out || n < 0) return fail(-1, "[l2r_gtf_stats] bad argument");
+    for (int k = 0; k < n; ++k) out[k] = k < GTFS_N ? c->gtf.stats[k] : 0.0;
+    return 0;
+}
+
+int l2r_gtf_check(const l2r_gtf_text *t, int64_t *line, int64_t *counts)
+{
+    std::string msg;
+    int64_t dummy = 0;
+    if (!line) return fail(-1, "[l2r_gtf_check] null argument");
+    if (gtf_check(t, &dummy, msg)) return fail(-1, "%s", msg.c_str());
+    GtfOrder o;
+    if (gtf_order_host(t->text, (uint64_t)t->n_bytes, o, msg, false)) return fail(-1, "%s", msg.c_str());
+    *line = o.descent_line;
+    if (counts) { counts[0] = o.n_lines; counts[1] = (int64_t)o.start.size(); counts[2] = o.n_tx; counts[3] = o.n_names; }
+    return o.descent_line ? 1 : 0;
 }
 
 }  // extern "C"

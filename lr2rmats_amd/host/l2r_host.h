@@ -121,6 +121,21 @@ int64_t h_name_order(l2r_ctx *ctx, const h_records *r, int64_t *order, const cha
 int64_t h_name_grouped(const h_records *r, int64_t *n_groups);
 int  h_sort_run_named(const char *in_fn, int by_name, FILE *out, int64_t *n_written, int64_t *n_groups);
 
+/* ---- `sort-gtf`, `sort-gtf-check` (gtfsort.c).  The order is l2r_gtf_order's (include/lr2rmats_hip.h): kept lines (third field
+ * contains "transcript" or equals "exon", byte 0 not '#') by (chromosome rank, start, end) of the last transcript line at or before
+ * them, then by line number.
+ * h_gtf_read_files: the files concatenated byte for byte in argument order, as the engine wants its text.
+ * h_gtf_write_rows (no GPU): every row, in the order given, as the first nine tab-separated columns of its line, joined by tabs, then
+ * '\n'.  The bytes are split at '\t' only; missing columns are empty (a seven-column line gets two trailing tabs, a line without a tab
+ * eight), columns beyond the ninth are dropped.  start / len / line: the columns of l2r_gtf_rows (`line` is not written and may be
+ * NULL).  -1: a row beyond the text or a write error.  h_gtf_write_rows_path: the same into a file.
+ * h_gtf_sort_run: read, l2r_gtf_order on GPU 0, write; counts (NULL, or 4 words): lines, kept rows, transcript lines, chromosome
+ * names; 1 with the engine's message on stderr where the text is outside the domain. */
+uint8_t *h_gtf_read_files(int n_files, char **fn, int64_t *n_bytes, const char *who);
+int  h_gtf_write_rows(const uint8_t *text, int64_t n_bytes, int64_t n_rows, const uint64_t *start, const uint32_t *len, const uint32_t *line, FILE *out);
+int  h_gtf_write_rows_path(const uint8_t *text, int64_t n_bytes, int64_t n_rows, const uint64_t *start, const uint32_t *len, const uint32_t *line, const char *path);
+int  h_gtf_sort_run(int n_files, char **fn, FILE *out, int64_t *counts);
+
 /* ---- `fusion` (fusion.c).  h_fusion_groups (no GPU): the runs of consecutive MAPPED records with one read name -- rows[k] = record
  * of row k, group g = rows [group_off[g], group_off[g + 1]), rlen[g] = query length (M I S = X) of its first record, taken from
  * `qlen` (one word per record, as l2r_fusion_segments leaves it) or, with qlen NULL, from that record's CIGAR; the three
@@ -238,6 +253,8 @@ int h_cmd_sjtab(int argc, char **argv);
 int h_cmd_fusion(int argc, char **argv);
 int h_cmd_sort(int argc, char **argv);
 int h_cmd_sort_check(int argc, char **argv);            /* no GPU; 0 sorted, 1 not, 2 usage */
+int h_cmd_sort_gtf(int argc, char **argv);              /* 0, 1 on a domain error (the engine's message), 2 usage */
+int h_cmd_sort_gtf_check(int argc, char **argv);        /* no GPU; 0 in order, 1 not, 2 usage */
 int h_main(int argc, char **argv);
 
 /* ---- staged form of update-gtf, used by the CLI itself and by the one-process-per-GPU driver

@@ -14,7 +14,9 @@ int main(int argc, char **argv)
         fprintf(stderr, "         bam2sj       generate splice-junction information based on BAM/SAM file\n");
         fprintf(stderr, "         sjtab        generate the filtered splice-junction table that update-gtf -j reads\n");
         fprintf(stderr, "         sort         sort alignment records by coordinate, the order update-gtf wants (-n: group them by read name)\n");
-        fprintf(stderr, "         sort-check   tell whether alignment records are sorted by coordinate (-n: grouped by read name)\n\n");
+        fprintf(stderr, "         sort-check   tell whether alignment records are sorted by coordinate (-n: grouped by read name)\n");
+        fprintf(stderr, "         sort-gtf     merge GTF files and sort their transcripts, the order update-gtf and unique-gtf want\n");
+        fprintf(stderr, "         sort-gtf-check  tell whether the transcripts of a GTF file are in that order\n\n");
         return 1;
     }
     return h_main(argc - 1, argv + 1);

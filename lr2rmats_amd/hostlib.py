@@ -97,6 +97,8 @@ def load_library():
         lib.h_header_grouped.restype = C.c_int64
         lib.h_name_grouped.argtypes = [C.c_void_p, C.POINTER(C.c_int64)]
         lib.h_name_grouped.restype = C.c_int64
+        lib.h_gtf_write_rows_path.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_char_p]
+        lib.h_gtf_write_rows_path.restype = C.c_int
         _lib = lib
     return _lib
 
@@ -259,6 +261,22 @@ def name_grouped(path: str):
     bad = int(lib.h_name_grouped(C.byref(r), C.byref(g)))
     lib.h_records_free(C.byref(r)); lib.h_chroms_free(C.byref(chr_))
     return bad, int(g.value)
+
+
+# ---- `sort-gtf` (host/gtfsort.c): the writer of the ordered rows (no GPU)
+
+def gtf_write_rows(text: bytes, start, length, line, path: str) -> None:
+    """The rows (the three columns of ``Engine.gtf_order``) of ``text`` into ``path`` as `sort-gtf` writes them (h_gtf_write_rows): the
+    first nine tab-separated columns of every line, missing columns empty."""
+    lib = load_library()
+    buf = capi.gtf_bytes(text)
+    start = np.ascontiguousarray(start, np.uint64)
+    length = np.ascontiguousarray(length, np.uint32)
+    line = np.ascontiguousarray(line, np.uint32)
+    assert start.shape == length.shape == line.shape
+    keep = [x if x.size else np.zeros(1, x.dtype) for x in (start, length, line)]
+    if lib.h_gtf_write_rows_path(buf.ctypes.data, len(text), int(start.shape[0]), keep[0].ctypes.data, keep[1].ctypes.data, keep[2].ctypes.data, path.encode()):
+        raise OSError("h_gtf_write_rows: a row beyond the text, or %s can not be written" % path)
 
 
 class Job:
