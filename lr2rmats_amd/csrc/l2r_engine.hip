@@ -8,6 +8,7 @@
 #include <stdlib.h>
 #include <string.h>
 #include <algorithm>
+#include <initializer_list>
 #include <string>
 #include <type_traits>
 #include <utility>
@@ -82,6 +83,26 @@ struct EventPair {
     ~EventPair() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); }
 };
 
+// The stage timer of a table command (`filter` / `fusion`, `bam2sj` / `sjtab`, `sort`, `sort -n`, `sort-gtf`): its launches go through
+// launch().  on (L2R_FUSION_TIMING=1, L2R_SJ_TIMING=1, L2R_SORT_TIMING=1): a launch is bracketed by the two events and waited for, its
+// device milliseconds are ADDED to *ms -- the caller zeroes its words.  wait: a launch is waited for in any case (the sort paths under
+// L2R_CHECK).  A command arms its timer with begin() before its first launch.
+struct StageTimer {
+    bool on = false, wait = false;
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    StageTimer() = default;
+    StageTimer(const StageTimer &) = delete;
+    StageTimer &operator=(const StageTimer &) = delete;
+    ~StageTimer() { for (int k = 0; k < 2; ++k) if (ev[k]) (void)hipEventDestroy(ev[k]); }
+    int begin(bool on_, bool wait_)
+    {
+        on = on_; wait = wait_;
+        for (int k = 0; k < 2 && on; ++k) if (!ev[k]) HIP_TRY(hipEventCreate(&ev[k]));
+        return 0;
+    }
+    template <typename F> int launch(l2r_ctx *c, double *ms, F f);      // (behind l2r_ctx)
+};
+
 // The three kernel pipelines: classic (l2r_kernels.hip.h, two walks), slab (l2r_slab.hip.h, one walk, two kernels), tile (l2r_tile.hip.h,
 // one kernel per tile).  The upload says which of them its layout allows, choose_pipeline which one a launch takes.
 enum class Pipeline { classic, slab, tile };
@@ -94,7 +115,7 @@ struct SjRowBuf {
     SjCols cols() const { return SjCols{col[0].p, col[1].p, col[2].p, col[3].p, col[4].p, col[5].p}; }
 };
 struct SjState {
-    bool open = false, finished = false, timing = false;
+    bool open = false, finished = false;
     bool over = false;                      // l2r_sj_begin_tab: six columns, the OVER instances of fill / scatter / reduce
     SjPrm prm{3, 1};
     int32_t n_seq = 0;
@@ -107,8 +128,7 @@ struct SjState {
     DevBuf<uint8_t> strand[2], motif[2], anno[2]; int bcur = 0;      // per-row bytes; the filter moves them to the other set
     DevBuf<int32_t> near_acc;               // l2r_sj_filter_rows2: per row the distance to the nearest other acceptor
     double stats[32] = {0};
-    hipEvent_t ev[2] = {nullptr, nullptr};
-    ~SjState() { for (int k = 0; k < 2; ++k) if (ev[k]) (void)hipEventDestroy(ev[k]); }
+    StageTimer clk;
 };
 // the annotation of l2r_sj_annotate on the device, and its introns: a table of their own (five columns), sorted and made unique by sj_compact
 struct SjIntrons {
@@ -122,10 +142,8 @@ struct SortState {
     DevBuf<uint16_t> flag; DevBuf<int32_t> tid, pos;
     DevBuf<uint64_t> key[2]; DevBuf<uint32_t> idx[2];
     DevBuf<uint32_t> hist, tile_hist, word;             // hist: 8 x 256 and, behind them, the descent flag; word[0]: a scan's total
-    bool timing = false;
+    StageTimer clk;
     double stats[7] = {0};                              // l2r_sort_stats
-    hipEvent_t ev[2] = {nullptr, nullptr};
-    ~SortState() { for (int k = 0; k < 2; ++k) if (ev[k]) (void)hipEventDestroy(ev[k]); }
 };
 
 // `sort -n`, `filter -N`, `fusion -N` (l2r_names.hip.h): the buffers of l2r_name_order beside those of SortState, which hold the hashes
@@ -135,10 +153,8 @@ struct NameState {
     DevBuf<int64_t> off;
     DevBuf<uint32_t> head, head_pos, first_idx, sizes, order;
     DevBuf<uint32_t> word;                              // word[0]: groups (the first scan's total), [1]: mismatching pairs, [2]: a record moved, [3]: the second scan's total
-    bool timing = false;
+    StageTimer clk;
     double stats[11] = {0};                             // l2r_name_stats
-    hipEvent_t ev[2] = {nullptr, nullptr};
-    ~NameState() { for (int k = 0; k < 2; ++k) if (ev[k]) (void)hipEventDestroy(ev[k]); }
 };
 
 // `sort-gtf` (l2r_gtf.hip.h): the buffers of l2r_gtf_order beside those of SortState, which hold the keys and the index columns of its
@@ -154,10 +170,8 @@ struct GtfState {
     DevBuf<uint32_t> c, s, e, order1, order;            // per kept line: the triple, stage 1's order, the order
     DevBuf<uint32_t> word;                              // GTFW_*
     std::vector<uint64_t> res_start; std::vector<uint32_t> res_len, res_line;        // the rows of the last call, in the order
-    bool timing = false;
+    StageTimer clk;
     double stats[17] = {0};                             // l2r_gtf_stats
-    hipEvent_t ev[2] = {nullptr, nullptr};
-    ~GtfState() { for (int k = 0; k < 2; ++k) if (ev[k]) (void)hipEventDestroy(ev[k]); }
 };
 
 // What l2r_sync has learned from the counters of a completed run of the tile path (fetch_run_facts): a later run of the same inputs,
@@ -307,11 +321,29 @@ struct l2r_ctx {
     bool totals_valid = false;
     SjState sj;                             // `bam2sj`, `sjtab`
     SjIntrons sj_intr;                      // `sjtab`: l2r_sj_annotate
-    double fusion_stats[5] = {0, 0, 0, 0, 0};        // `fusion`: l2r_fusion_stats
+    double fusion_stats[5] = {0, 0, 0, 0, 0};        // `filter`, `fusion`: l2r_fusion_stats
+    StageTimer fusion_clk;
     SortState sort;                         // `sort`, `filter -S`
     NameState name;                         // `sort -n`, `filter -N`, `fusion -N`
     GtfState gtf;                           // `sort-gtf`
 };
+
+// A launch (or a group of launches) on the context stream
+template <typename F> int StageTimer::launch(l2r_ctx *c, double *ms, F f)
+{
+    if (on) HIP_TRY(hipEventRecord(ev[0], c->stream));
+    f();
+    HIP_TRY(hipGetLastError());
+    if (on) {
+        float t = 0.0f;
+        HIP_TRY(hipEventRecord(ev[1], c->stream));
+        HIP_TRY(hipEventSynchronize(ev[1]));
+        HIP_TRY(hipEventElapsedTime(&t, ev[0], ev[1]));
+        *ms += t;
+    }
+    if (wait) HIP_TRY(hipStreamSynchronize(c->stream));
+    return 0;
+}
 
 // What completed runs have shown about the tile path's lists and the inexact tiles: forgotten wherever inputs, parameters or outputs change
 static void forget_list_state(l2r_ctx *c)
@@ -1511,25 +1543,38 @@ int l2r_classify(l2r_ctx *c, const l2r_reads *reads, l2r_result *res)
 
 // ---------------------------------------------------------------------------------------------- filter
 extern "C++" {
-// a launch of `filter` / `fusion` on the context stream; with L2R_FUSION_TIMING=1 (tools/bench_fusion.py) bracketed by events and waited for: device milliseconds into *ms
-template <typename F> static int fusion_launch(l2r_ctx *c, double *ms, F f)
+static bool env_on(const char *name) { const char *e = getenv(name); return e && atoi(e) != 0; }
+
+// what is behind l2r_fusion_stats, l2r_sj_stats, l2r_sort_stats, l2r_name_stats and l2r_gtf_stats: the `have` words of src, then zeros
+static int stats_out(const double *src, int have, double *out, int n, const char *who)
 {
-    const char *e = getenv("L2R_FUSION_TIMING");
-    const bool timing = e && atoi(e) != 0;
-    hipEvent_t ev[2] = {nullptr, nullptr};
-    if (timing) { HIP_TRY(hipEventCreate(&ev[0])); HIP_TRY(hipEventCreate(&ev[1])); HIP_TRY(hipEventRecord(ev[0], c->stream)); }
-    f();
-    hipError_t err = hipGetLastError();
-    if (timing) {
-        float t = 0.0f;
-        if (err == hipSuccess) err = hipEventRecord(ev[1], c->stream);
-        if (err == hipSuccess) err = hipEventSynchronize(ev[1]);
-        if (err == hipSuccess) err = hipEventElapsedTime(&t, ev[0], ev[1]);
-        (void)hipEventDestroy(ev[0]); (void)hipEventDestroy(ev[1]);
-        *ms = (double)t;
-    }
-    if (err != hipSuccess) return fail(-2, "[kernel launch] %s", hipGetErrorString(err));
+    if (!src || !out || n < 0) return fail(-1, "[%s] bad argument", who);
+    for (int k = 0; k < n; ++k) out[k] = k < have ? src[k] : 0.0;
     return 0;
+}
+
+// slots of l2r_fusion_stats
+enum { FUS_WAVE = 0, FUS_K_SEG, FUS_K_SELECT, FUS_K_FILTER_SCORE, FUS_K_FILTER_SELECT, FUS_N };
+
+// In front of the launch of a `filter` / `fusion` entry point: its word of l2r_fusion_stats starts at 0 (the timer adds), and the timer is
+// armed: with L2R_FUSION_TIMING=1 (tools/bench_fusion.py) the launch is bracketed by events and waited for
+static int fusion_begin(l2r_ctx *c, int slot)
+{
+    c->fusion_stats[slot] = 0;
+    return c->fusion_clk.begin(env_on("L2R_FUSION_TIMING"), false);
+}
+
+// The tail of a `filter` / `fusion` entry point.  rc: what uploads and launch came to; where that is 0 the downloads are queued.  The
+// stream is waited for in any case (the device buffers and host vectors are the caller's locals), and the first error is the result.
+struct Download { void *dst; const void *src; size_t bytes; };
+static int download_all(l2r_ctx *c, int rc, std::initializer_list<Download> list, const char *who)
+{
+    hipError_t e = hipSuccess;
+    if (!rc) for (const Download &d : list) if (e == hipSuccess && d.bytes) e = hipMemcpyAsync(d.dst, d.src, d.bytes, hipMemcpyDeviceToHost, c->stream);
+    const hipError_t sync = hipStreamSynchronize(c->stream);
+    if (e == hipSuccess) e = sync;
+    if (!rc && e != hipSuccess) rc = fail(-2, "[%s] %s", who, hipGetErrorString(e));
+    return rc;
 }
 }
 
@@ -1567,23 +1612,16 @@ int l2r_filter_score(l2r_ctx *c, const l2r_filter_records *r, const l2r_filter_p
         (rc = to_dev(c, d_nm, r->nm, N)) || (rc = to_dev(c, d_off, r->cig_off, N + 1)) || (rc = to_dev(c, d_cig, r->cig, (size_t)r->n_cigar)) ||
         (rc = to_dev(c, d_soff, off.data(), off.size())) || (rc = to_dev(c, d_st, st.data(), st.size())) || (rc = to_dev(c, d_pe, pe.data(), pe.size())) ||
         d_drop.ensure(N ? N : 1) || d_score.ensure(N ? N : 1) || d_in.ensure(N ? N : 1)) { rc = rc ? rc : -2; }
-    if (!rc && N) {
+    if (!rc && N && !(rc = fusion_begin(c, FUS_K_FILTER_SCORE))) {
         const FilterPrm fp{prm->cov_rate, prm->map_qual, prm->sec_rat, prm->min_intron_n};
         const FilterSpans sp{d_soff.p, d_st.p, d_pe.p, n_tid};
-        rc = fusion_launch(c, &c->fusion_stats[3], [&] {
+        rc = c->fusion_clk.launch(c, &c->fusion_stats[FUS_K_FILTER_SCORE], [&] {
             hipLaunchKernelGGL(k_filter_score, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, c->stream, (int64_t)N, (const uint16_t *)d_flag.p, (const int32_t *)d_tid.p,
                                (const int32_t *)d_pos.p, (const int32_t *)d_lq.p, (const int32_t *)d_nm.p, (const int64_t *)d_off.p, (const uint32_t *)d_cig.p, fp, sp,
                                d_drop.p, d_score.p, d_in.p);
         });
-        hipError_t e = hipSuccess;
-        if (!rc) e = hipMemcpyAsync(drop, d_drop.p, N, hipMemcpyDeviceToHost, c->stream);
-        if (!rc && e == hipSuccess) e = hipMemcpyAsync(score, d_score.p, N * 4, hipMemcpyDeviceToHost, c->stream);
-        if (!rc && e == hipSuccess) e = hipMemcpyAsync(intron_n, d_in.p, N * 4, hipMemcpyDeviceToHost, c->stream);
-        if (e != hipSuccess) rc = fail(-2, "[l2r_filter_score] %s", hipGetErrorString(e));
     }
-    hipError_t e = hipStreamSynchronize(c->stream);          // (the host vectors and the DevBufs above are locals)
-    if (!rc && e != hipSuccess) rc = fail(-2, "[l2r_filter_score] %s", hipGetErrorString(e));
-    return rc;
+    return download_all(c, rc, {{drop, d_drop.p, N}, {score, d_score.p, N * 4}, {intron_n, d_in.p, N * 4}}, "l2r_filter_score");
 }
 
 int l2r_filter_select(l2r_ctx *c, int64_t n_groups, const int64_t *group_off, const int32_t *score, const int32_t *intron_n,
@@ -1597,19 +1635,14 @@ int l2r_filter_select(l2r_ctx *c, int64_t n_groups, const int64_t *group_off, co
     DevBuf<int64_t> d_off, d_win; DevBuf<int32_t> d_score, d_in;
     int rc = 0;
     if ((rc = to_dev(c, d_off, group_off, G + 1)) || (rc = to_dev(c, d_score, score, R)) || (rc = to_dev(c, d_in, intron_n, R)) || d_win.ensure(G)) rc = rc ? rc : -2;
-    if (!rc) {
+    if (!rc && !(rc = fusion_begin(c, FUS_K_FILTER_SELECT))) {
         const FilterPrm fp{prm->cov_rate, prm->map_qual, prm->sec_rat, prm->min_intron_n};
-        rc = fusion_launch(c, &c->fusion_stats[4], [&] {
+        rc = c->fusion_clk.launch(c, &c->fusion_stats[FUS_K_FILTER_SELECT], [&] {
             hipLaunchKernelGGL(k_filter_select, dim3((unsigned)((G + 255) / 256)), dim3(256), 0, c->stream, (int64_t)G, (const int64_t *)d_off.p, (const int32_t *)d_score.p,
                                (const int32_t *)d_in.p, fp, d_win.p);
         });
-        hipError_t e = hipSuccess;
-        if (!rc) e = hipMemcpyAsync(winner, d_win.p, G * 8, hipMemcpyDeviceToHost, c->stream);
-        if (e != hipSuccess) rc = fail(-2, "[l2r_filter_select] %s", hipGetErrorString(e));
     }
-    hipError_t e = hipStreamSynchronize(c->stream);
-    if (!rc && e != hipSuccess) rc = fail(-2, "[l2r_filter_select] %s", hipGetErrorString(e));
-    return rc;
+    return download_all(c, rc, {{winner, d_win.p, G * 8}}, "l2r_filter_select");
 }
 
 // ---------------------------------------------------------------------------------------------- fusion
@@ -1631,26 +1664,21 @@ int l2r_fusion_segments(l2r_ctx *c, const l2r_fusion_records *r, int32_t *read_s
     int rc = 0;
     if ((rc = to_dev(c, d_flag, r->flag, N)) || (rc = to_dev(c, d_pos, r->pos, N)) || (rc = to_dev(c, d_off, r->cig_off, N + 1)) ||
         (rc = to_dev(c, d_cig, r->cig, (size_t)r->n_cigar)) || d_out.ensure(5 * N)) rc = rc ? rc : -2;
-    if (!rc) {
-        int32_t *o = d_out.p;
+    if (rc) return download_all(c, rc, {}, "l2r_fusion_segments");
+    int32_t *o = d_out.p;
+    if (!(rc = fusion_begin(c, FUS_K_SEG))) {
         const size_t threads = wave ? N * 64 : N;
         const dim3 grid((unsigned)((threads + 255) / 256));
-        c->fusion_stats[0] = wave ? 1.0 : 0.0;
-        rc = fusion_launch(c, &c->fusion_stats[1], [&] {
+        c->fusion_stats[FUS_WAVE] = wave ? 1.0 : 0.0;
+        rc = c->fusion_clk.launch(c, &c->fusion_stats[FUS_K_SEG], [&] {
             if (wave) hipLaunchKernelGGL(k_fusion_seg<true>, grid, dim3(256), 0, c->stream, (int64_t)N, (const uint16_t *)d_flag.p, (const int32_t *)d_pos.p,
                                          (const int64_t *)d_off.p, (const uint32_t *)d_cig.p, o, o + N, o + 2 * N, o + 3 * N, o + 4 * N);
             else hipLaunchKernelGGL(k_fusion_seg<false>, grid, dim3(256), 0, c->stream, (int64_t)N, (const uint16_t *)d_flag.p, (const int32_t *)d_pos.p,
                                     (const int64_t *)d_off.p, (const uint32_t *)d_cig.p, o, o + N, o + 2 * N, o + 3 * N, o + 4 * N);
         });
-        int32_t *host[5] = {read_start, read_end, ref_start, ref_end, qlen};
-        for (int k = 0; k < 5 && !rc; ++k) {
-            const hipError_t e = hipMemcpyAsync(host[k], o + (size_t)k * N, N * 4, hipMemcpyDeviceToHost, c->stream);
-            if (e != hipSuccess) rc = fail(-2, "[l2r_fusion_segments] %s", hipGetErrorString(e));
-        }
     }
-    hipError_t e = hipStreamSynchronize(c->stream);
-    if (!rc && e != hipSuccess) rc = fail(-2, "[l2r_fusion_segments] %s", hipGetErrorString(e));
-    return rc;
+    return download_all(c, rc, {{read_start, o, N * 4}, {read_end, o + N, N * 4}, {ref_start, o + 2 * N, N * 4}, {ref_end, o + 3 * N, N * 4}, {qlen, o + 4 * N, N * 4}},
+                        "l2r_fusion_segments");
 }
 
 int l2r_fusion_select(l2r_ctx *c, int64_t n_groups, const int64_t *group_off, const int32_t *score, const int32_t *ed, const int32_t *tid,
@@ -1670,50 +1698,22 @@ int l2r_fusion_select(l2r_ctx *c, int64_t n_groups, const int64_t *group_off, co
     if ((rc = to_dev(c, d_off, group_off, G + 1)) || (rc = to_dev(c, d_score, score, R)) || (rc = to_dev(c, d_ed, ed, R)) || (rc = to_dev(c, d_tid, tid, R)) ||
         (rc = to_dev(c, d_rs, read_start, R)) || (rc = to_dev(c, d_re, read_end, R)) || (rc = to_dev(c, d_fs, ref_start, R)) ||
         (rc = to_dev(c, d_fe, ref_end, R)) || (rc = to_dev(c, d_rlen, rlen_of_group, G)) || d_out.ensure(2 * G)) rc = rc ? rc : -2;
-    if (!rc) {
+    if (rc) return download_all(c, rc, {}, "l2r_fusion_select");
+    if (!(rc = fusion_begin(c, FUS_K_SELECT))) {
         const FusionPrm fp{prm->ovlp_frac, prm->each_cov, prm->all_cov, prm->dis};
-        rc = fusion_launch(c, &c->fusion_stats[2], [&] {
+        rc = c->fusion_clk.launch(c, &c->fusion_stats[FUS_K_SELECT], [&] {
             hipLaunchKernelGGL(k_fusion_select, dim3((unsigned)((G + 255) / 256)), dim3(256), 0, c->stream, (int64_t)G, (const int64_t *)d_off.p,
                                (const int32_t *)d_score.p, (const int32_t *)d_ed.p, (const int32_t *)d_tid.p, (const int32_t *)d_rs.p, (const int32_t *)d_re.p,
                                (const int32_t *)d_fs.p, (const int32_t *)d_fe.p, (const int32_t *)d_rlen.p, fp, d_out.p, d_out.p + G);
         });
-        hipError_t e = hipSuccess;
-        if (!rc) e = hipMemcpyAsync(first, d_out.p, G * 8, hipMemcpyDeviceToHost, c->stream);
-        if (!rc && e == hipSuccess) e = hipMemcpyAsync(second, d_out.p + G, G * 8, hipMemcpyDeviceToHost, c->stream);
-        if (e != hipSuccess) rc = fail(-2, "[l2r_fusion_select] %s", hipGetErrorString(e));
     }
-    hipError_t e = hipStreamSynchronize(c->stream);
-    if (!rc && e != hipSuccess) rc = fail(-2, "[l2r_fusion_select] %s", hipGetErrorString(e));
-    return rc;
+    return download_all(c, rc, {{first, d_out.p, G * 8}, {second, d_out.p + G, G * 8}}, "l2r_fusion_select");
 }
 
-int l2r_fusion_stats(l2r_ctx *c, double *out, int n)
-{
-    if (!c || !out || n < 0) return fail(-1, "[l2r_fusion_stats] bad argument");
-    for (int k = 0; k < n; ++k) out[k] = k < 5 ? c->fusion_stats[k] : 0.0;
-    return 0;
-}
+int l2r_fusion_stats(l2r_ctx *c, double *out, int n) { return stats_out(c ? c->fusion_stats : nullptr, FUS_N, out, n, "l2r_fusion_stats"); }
 
 // ---------------------------------------------------------------------------------------------- bam2sj, sjtab
 extern "C++" {
-// A launch (or a group of launches) on the context stream.  timing (L2R_SJ_TIMING=1, L2R_SORT_TIMING=1): bracketed by the two events, waited
-// for, the device milliseconds added to *ms.  wait: waited for in any case (the sort path under L2R_CHECK).
-template <typename F> static int timed_launch(l2r_ctx *c, bool timing, hipEvent_t ev[2], double *ms, F f, bool wait = false)
-{
-    if (timing) HIP_TRY(hipEventRecord(ev[0], c->stream));
-    f();
-    HIP_TRY(hipGetLastError());
-    if (timing) {
-        float t = 0.0f;
-        HIP_TRY(hipEventRecord(ev[1], c->stream));
-        HIP_TRY(hipEventSynchronize(ev[1]));
-        HIP_TRY(hipEventElapsedTime(&t, ev[0], ev[1]));
-        *ms += t;
-    }
-    if (wait) HIP_TRY(hipStreamSynchronize(c->stream));
-    return 0;
-}
-
 // v[0, n] <- the exclusive scan of v[0, n), *total_word <- the sum: one workgroup
 static void scan_u32(l2r_ctx *c, uint32_t *v, int64_t n, uint32_t *total_word)
 {
@@ -1730,33 +1730,92 @@ static bool byte_is_one_value(const uint32_t *hist, uint32_t n)
 
 // The passes of l2r_radix.hip.h over n rows, one per key byte of byte[0, n_pass), least significant first: digit histogram of every
 // tile -> its scan -> scatter.  The caller owns the rows and their two sides: hist(b, p, n_tiles) and scatter(b, p, last, n_tiles)
-// launch pass p over byte b, which reads the side pass p - 1 wrote; launch(k, f) is the caller's timed launch of f, k = 0 the digit
-// histogram, 1 the scan, 2 the scatter.  Which bytes run is the caller's rule.
-template <typename Launch, typename Hist, typename Scatter>
-static int radix_passes(l2r_ctx *c, const int *byte, int n_pass, uint32_t n, DevBuf<uint32_t> &tile_hist, uint32_t *total_word, Launch launch, Hist hist, Scatter scatter)
+// launch pass p over byte b, which reads the side pass p - 1 wrote.  The launches go through the caller's timer, which adds the time of
+// the digit histogram to *ms[0], of the scan to *ms[1], of the scatter to *ms[2].  Which bytes run is the caller's rule.
+template <typename Hist, typename Scatter>
+static int radix_passes(l2r_ctx *c, StageTimer &clk, double *const ms[3], const int *byte, int n_pass, uint32_t n, DevBuf<uint32_t> &tile_hist, uint32_t *total_word,
+                        Hist hist, Scatter scatter)
 {
     const uint32_t n_tiles = (uint32_t)(((size_t)n + RADIX_TILE - 1) / RADIX_TILE);
     if (n_pass && tile_hist.ensure((size_t)256 * n_tiles + 1)) return -2;
     int rc;
     for (int p = 0; p < n_pass; ++p) {
-        if ((rc = launch(0, [&] { hist(byte[p], p, n_tiles); }))) return rc;
-        if ((rc = launch(1, [&] { scan_u32(c, tile_hist.p, (int64_t)256 * n_tiles, total_word); }))) return rc;
-        if ((rc = launch(2, [&] { scatter(byte[p], p, p == n_pass - 1, n_tiles); }))) return rc;
+        if ((rc = clk.launch(c, ms[0], [&] { hist(byte[p], p, n_tiles); }))) return rc;
+        if ((rc = clk.launch(c, ms[1], [&] { scan_u32(c, tile_hist.p, (int64_t)256 * n_tiles, total_word); }))) return rc;
+        if ((rc = clk.launch(c, ms[2], [&] { scatter(byte[p], p, p == n_pass - 1, n_tiles); }))) return rc;
     }
+    return 0;
+}
+
+// The radix passes over the keys in c->sort.key[0][0, n), behind a keys kernel that left the histograms of the eight key bytes and the
+// descent word in c->sort.hist.  A byte that is equal in every key is a pass that is not run, keys that never descend run none
+// (L2R_SORT_FORCE=1: all eight, whatever the keys).  *n_pass_out: passes run; the order is then in c->sort.idx[*src_out], and with no
+// pass it is the identity and no index column is written.  in_order_out may be null.  clk, ms: the caller's, as radix_passes takes them
+// -- the sort buffers are lent to `sjtab -d`, `sort -n` and `sort-gtf`, the words of l2r_sort_stats are not.
+static int sort_passes(l2r_ctx *c, StageTimer &clk, double *const ms[3], uint32_t n, int *n_pass_out, bool *in_order_out, int *src_out)
+{
+    SortState &s = c->sort;
+    const bool force = env_on("L2R_SORT_FORCE");
+    const size_t N = n;
+    uint32_t h8[SORT_KEY_BYTES * 256 + 1];
+    HIP_TRY(hipMemcpyAsync(h8, s.hist.p, sizeof h8, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    const bool in_order = h8[SORT_KEY_BYTES * 256] == 0u;
+    int pass_byte[SORT_KEY_BYTES], n_pass = 0;
+    for (int b = 0; b < SORT_KEY_BYTES; ++b) if (force || (!in_order && !byte_is_one_value(h8 + b * 256, n))) pass_byte[n_pass++] = b;
+    *n_pass_out = n_pass; *src_out = n_pass & 1;
+    if (in_order_out) *in_order_out = in_order;
+    if (n_pass == 0) return 0;
+    if (s.idx[0].ensure(N) || s.idx[1].ensure(N) || (n_pass > 1 && s.key[1].ensure(N))) return -2;
+    return radix_passes(c, clk, ms, pass_byte, n_pass, n, s.tile_hist, s.word.p,
+        [&](int b, int p, uint32_t n_tiles) {
+            hipLaunchKernelGGL((k_radix_digit_hist<SortRows<false, false>>), dim3(n_tiles), dim3(RADIX_THREADS), 0, c->stream,
+                               SortRows<false, false>{s.key[p & 1].p, nullptr, nullptr, nullptr}, n, b, n_tiles, s.tile_hist.p);
+        },
+        [&](int b, int p, bool last, uint32_t n_tiles) {
+            const int from = p & 1;
+#define SORT_SCATTER(F, L) hipLaunchKernelGGL((k_radix_scatter<SortRows<F, L>>), dim3(n_tiles), dim3(RADIX_THREADS), 0, c->stream, \
+                                              SortRows<F, L>{s.key[from].p, s.idx[from].p, s.key[1 - from].p, s.idx[1 - from].p}, n, b, n_tiles, (const uint32_t *)s.tile_hist.p)
+            if (p == 0 && last) SORT_SCATTER(true, true); else if (p == 0) SORT_SCATTER(true, false); else if (last) SORT_SCATTER(false, true); else SORT_SCATTER(false, false);
+#undef SORT_SCATTER
+        });
+}
+
+static_assert(SORT_THREADS == RADIX_THREADS && NAME_THREADS == RADIX_THREADS && SJ_THREADS == RADIX_THREADS && GTF_THREADS == RADIX_THREADS,
+              "order_by_keys: one grid of k_radix_keys, whichever command's rows the keys are made of");
+
+// The stable order of n rows by the 64-bit keys key_of makes of them, in the context's sort buffers: k_radix_keys<KeyOf> (the keys, which
+// of their bytes differ at all, whether they descend anywhere), then sort_passes.  *idx: the order, null where no pass ran (the
+// identity).  keys_copy: null, or where the keys go in row order before the passes use both key columns in turn.  clk: the caller's
+// timer; the keys kernel's time is added to *ms_keys, the passes' to *ms_passes[0 .. 2].
+template <typename KeyOf>
+static int order_by_keys(l2r_ctx *c, StageTimer &clk, KeyOf key_of, uint32_t n, double *ms_keys, double *const ms_passes[3], int *n_pass, bool *in_order,
+                         const uint32_t **idx, uint64_t *keys_copy = nullptr)
+{
+    SortState &o = c->sort;
+    if (o.key[0].ensure(n) || o.hist.ensure(SORT_KEY_BYTES * 256 + 1) || o.word.ensure(4)) return -2;
+    HIP_TRY(hipMemsetAsync(o.hist.p, 0, (SORT_KEY_BYTES * 256 + 1) * sizeof(uint32_t), c->stream));
+    const unsigned grid = (unsigned)std::min<size_t>(((size_t)n + RADIX_THREADS - 1) / RADIX_THREADS, 2048);
+    int rc, src = 0;
+    if ((rc = clk.launch(c, ms_keys, [&] {
+            hipLaunchKernelGGL(k_radix_keys<KeyOf>, dim3(grid), dim3(RADIX_THREADS), 0, c->stream, key_of, (int64_t)n, o.key[0].p, o.hist.p, o.hist.p + SORT_KEY_BYTES * 256);
+        }))) return rc;
+    if (keys_copy) HIP_TRY(hipMemcpyAsync(keys_copy, o.key[0].p, (size_t)n * sizeof(uint64_t), hipMemcpyDeviceToDevice, c->stream));
+    if ((rc = sort_passes(c, clk, ms_passes, n, n_pass, in_order, &src))) return rc;
+    *idx = *n_pass ? o.idx[src].p : nullptr;
     return 0;
 }
 }
 
-// slots of l2r_sort_stats (the acceptor order of `sjtab` runs the passes of `sort`)
+// slots of l2r_sort_stats
 enum { SORTS_ROWS = 0, SORTS_PASSES, SORTS_IN_ORDER, SORTS_K_KEYS, SORTS_K_HIST, SORTS_K_SCAN, SORTS_K_SCATTER, SORTS_N };
-static_assert(SORTS_K_SCAN == SORTS_K_HIST + 1 && SORTS_K_SCATTER == SORTS_K_HIST + 2, "radix_passes: digit histogram, scan and scatter are three slots in a row");
 
-// slots of l2r_sj_stats: of the fifteen of `bam2sj` the three of a radix pass, in the row radix_passes counts them in
-enum { SJS_K_HIST = 9, SJS_K_HIST_SCAN, SJS_K_SCATTER };
-// slots of l2r_sj_stats behind the fifteen of `bam2sj`
-enum { SJS_DROPPED = 15, SJS_INTRONS, SJS_K_INTRONS, SJS_K_ANNOTATE, SJS_K_KEEP, SJS_K_KEEP_SCAN, SJS_K_TAKE, SJS_INTRON_SORT,
+// slots of l2r_sj_stats, in the order of SJ_STAT_NAMES (capi.py): the fifteen of `bam2sj`, behind them those of `sjtab`
+enum { SJS_ROWS_MADE = 0, SJS_ROUNDS, SJS_PASSES, SJS_ROWS_IN, SJS_ROWS_OUT, SJS_K_COUNT, SJS_K_COUNT_SCAN, SJS_K_FILL, SJS_K_HIST12,
+       SJS_K_HIST, SJS_K_HIST_SCAN, SJS_K_SCATTER, SJS_K_HEADS, SJS_K_REDUCE, SJS_K_MOTIF,
+       SJS_DROPPED, SJS_INTRONS, SJS_K_INTRONS, SJS_K_ANNOTATE, SJS_K_KEEP, SJS_K_KEEP_SCAN, SJS_K_TAKE, SJS_INTRON_SORT,
        SJS_NEAR_DROPPED, SJS_ACC_PASSES, SJS_K_ACC_KEYS, SJS_K_ACC_ORDER, SJS_K_NEAR_ACC, SJS_K_KEEP_NEAR, SJS_LONG_DROPPED, SJS_N };
-static_assert(SJS_NEAR_DROPPED == 23 && SJS_N <= 32, "l2r_sj_stats: the words of include/lr2rmats_hip.h");
+static_assert(SJS_K_HIST == 9 && SJS_DROPPED == 15 && SJS_NEAR_DROPPED == 23 && SJS_N <= 32, "l2r_sj_stats: the words of include/lr2rmats_hip.h");
 
 // room for `want` rows; the first `keep` rows stay (DevBuf::ensure carries nothing over, so the columns are moved here)
 static int sj_rows_reserve(l2r_ctx *c, const SjState &s, SjRowBuf &b, size_t want, size_t keep)
@@ -1784,7 +1843,7 @@ static int sj_rows_reserve(l2r_ctx *c, const SjState &s, SjRowBuf &b, size_t wan
 static int sj_compact(l2r_ctx *c, SjState &s)
 {
     const int64_t n64 = s.n_rows;
-    s.stats[1] += 1; s.stats[2] = 0; s.stats[3] = (double)n64; s.stats[4] = 0;
+    s.stats[SJS_ROUNDS] += 1; s.stats[SJS_PASSES] = 0; s.stats[SJS_ROWS_IN] = (double)n64; s.stats[SJS_ROWS_OUT] = 0;
     if (n64 == 0) return 0;
     if (n64 >= ((int64_t)1 << 31)) return fail(-1, "[l2r_sj] %lld junction rows in one sort (2^31 at most)", (long long)n64);
     const uint32_t n = (uint32_t)n64;
@@ -1793,15 +1852,15 @@ static int sj_compact(l2r_ctx *c, SjState &s)
     // which key bytes differ at all
     uint32_t h12[SJ_KEY_BYTES * 256];
     HIP_TRY(hipMemsetAsync(s.hist12.p, 0, sizeof h12, c->stream));
-    int rc = timed_launch(c, s.timing, s.ev, &s.stats[8], [&] { hipLaunchKernelGGL(k_sj_hist12, dim3(std::min(grid, 2048u)), dim3(SJ_THREADS), 0, c->stream, s.rows[s.cur].cols(), n, s.hist12.p); });
+    int rc = s.clk.launch(c, &s.stats[SJS_K_HIST12], [&] { hipLaunchKernelGGL(k_sj_hist12, dim3(std::min(grid, 2048u)), dim3(SJ_THREADS), 0, c->stream, s.rows[s.cur].cols(), n, s.hist12.p); });
     if (rc) return rc;
     HIP_TRY(hipMemcpyAsync(h12, s.hist12.p, sizeof h12, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     int pass_byte[SJ_KEY_BYTES], passes = 0;
     for (int b = 0; b < SJ_KEY_BYTES; ++b) if (!byte_is_one_value(h12 + b * 256, n)) pass_byte[passes++] = b;
     auto rows = [&](int p) { const int from = s.cur ^ (p & 1); return SjRows<false>{s.rows[from].cols(), s.rows[1 - from].cols()}; };
-    rc = radix_passes(c, pass_byte, passes, n, s.tile_hist, s.word.p,
-        [&](int k, auto f) { return timed_launch(c, s.timing, s.ev, &s.stats[SJS_K_HIST + k], f); },
+    double *const ms[3] = {&s.stats[SJS_K_HIST], &s.stats[SJS_K_HIST_SCAN], &s.stats[SJS_K_SCATTER]};
+    rc = radix_passes(c, s.clk, ms, pass_byte, passes, n, s.tile_hist, s.word.p,
         [&](int b, int p, uint32_t n_tiles) { hipLaunchKernelGGL(k_radix_digit_hist<SjRows<false>>, dim3(n_tiles), dim3(RADIX_THREADS), 0, c->stream, rows(p), n, b, n_tiles, s.tile_hist.p); },
         [&](int b, int p, bool, uint32_t n_tiles) {
             const SjRows<false> r = rows(p);
@@ -1811,8 +1870,8 @@ static int sj_compact(l2r_ctx *c, SjState &s)
     if (rc) return rc;
     const int src = s.cur ^ (passes & 1);
     // runs of equal keys
-    if ((rc = timed_launch(c, s.timing, s.ev, &s.stats[12], [&] { hipLaunchKernelGGL(k_sj_heads, dim3(grid), dim3(SJ_THREADS), 0, c->stream, s.rows[src].cols(), n, s.head.p); }))) return rc;
-    if ((rc = timed_launch(c, s.timing, s.ev, &s.stats[12], [&] { scan_u32(c, s.head.p, (int64_t)n, s.word.p); }))) return rc;
+    if ((rc = s.clk.launch(c, &s.stats[SJS_K_HEADS], [&] { hipLaunchKernelGGL(k_sj_heads, dim3(grid), dim3(SJ_THREADS), 0, c->stream, s.rows[src].cols(), n, s.head.p); }))) return rc;
+    if ((rc = s.clk.launch(c, &s.stats[SJS_K_HEADS], [&] { scan_u32(c, s.head.p, (int64_t)n, s.word.p); }))) return rc;
     uint32_t n_runs = 0;
     HIP_TRY(hipMemcpyAsync(&n_runs, s.word.p, 4, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
@@ -1821,28 +1880,27 @@ static int sj_compact(l2r_ctx *c, SjState &s)
     HIP_TRY(hipMemsetAsync(s.rows[dst].col[3].p, 0, (size_t)n_runs * 4, c->stream));
     HIP_TRY(hipMemsetAsync(s.rows[dst].col[4].p, 0, (size_t)n_runs * 4, c->stream));
     if (s.over) { HIP_TRY(hipMemsetAsync(s.rows[dst].col[5].p, 0, (size_t)n_runs * 4, c->stream)); }
-    if ((rc = timed_launch(c, s.timing, s.ev, &s.stats[13], [&] {
+    if ((rc = s.clk.launch(c, &s.stats[SJS_K_REDUCE], [&] {
             if (s.over) hipLaunchKernelGGL(k_sj_reduce<true>, dim3(grid), dim3(SJ_THREADS), 0, c->stream, s.rows[src].cols(), n, (const uint32_t *)s.head.p, s.rows[dst].cols(), n_runs);
             else hipLaunchKernelGGL(k_sj_reduce<false>, dim3(grid), dim3(SJ_THREADS), 0, c->stream, s.rows[src].cols(), n, (const uint32_t *)s.head.p, s.rows[dst].cols(), n_runs);
         }))) return rc;
     s.cur = dst; s.n_rows = n_runs;
-    s.stats[2] = passes; s.stats[4] = n_runs;
+    s.stats[SJS_PASSES] = passes; s.stats[SJS_ROWS_OUT] = n_runs;
     s.compact_at = std::max(s.compact_rows, 2 * s.n_rows);
     return 0;
 }
 
-// what l2r_sj_begin and l2r_sj_begin_tab share; `intr`: the state of the annotation introns (no genome, no batches)
-static int sj_state_begin(l2r_ctx *c, SjState &s, bool over)
+// what l2r_sj_begin and l2r_sj_begin_tab share, and the state of the annotation's introns (no genome, no batches).  timing: L2R_SJ_TIMING=1
+// as l2r_sj_begin found it
+static int sj_state_begin(l2r_ctx *c, SjState &s, bool over, bool timing)
 {
     s.open = false; s.finished = false; s.n_rows = 0; s.cur = 0; s.bcur = 0; s.n_seq = 0; s.over = over;
     for (double &v : s.stats) v = 0;
     const char *e = getenv("L2R_SJ_COMPACT_ROWS");
     s.compact_rows = e && atoll(e) > 0 ? atoll(e) : (int64_t)1 << 24;
     s.compact_at = s.compact_rows;
-    s.timing = getenv("L2R_SJ_TIMING") != nullptr && atoi(getenv("L2R_SJ_TIMING")) != 0;
-    for (int k = 0; k < 2; ++k) if (!s.ev[k]) HIP_TRY(hipEventCreate(&s.ev[k]));
     if (s.word.ensure(4)) return -2;
-    return 0;
+    return s.clk.begin(timing, false);
 }
 
 static int sj_begin(l2r_ctx *c, const l2r_sj_params *prm, const l2r_sj_genome *g, bool over, const char *who)
@@ -1852,7 +1910,7 @@ static int sj_begin(l2r_ctx *c, const l2r_sj_params *prm, const l2r_sj_genome *g
     HIP_TRY(hipSetDevice(c->device));
     SjState &s = c->sj;
     int rc;
-    if ((rc = sj_state_begin(c, s, over))) return rc;
+    if ((rc = sj_state_begin(c, s, over, env_on("L2R_SJ_TIMING")))) return rc;
     s.prm = SjPrm{prm->min_intron, prm->pair_only};
     if (g && g->n_seq > 0) {
         for (int32_t k = 0; k < g->n_seq; ++k) if (g->seq_off[k + 1] < g->seq_off[k] || g->seq_off[0] != 0) return fail(-1, "[%s] sequence offsets do not ascend from 0", who);
@@ -1870,7 +1928,7 @@ int l2r_sj_begin_tab(l2r_ctx *c, const l2r_sj_params *prm, const l2r_sj_genome *
 static int sj_after_add(l2r_ctx *c, int64_t added)
 {
     SjState &s = c->sj;
-    s.n_rows += added; s.stats[0] += (double)added; s.finished = false;
+    s.n_rows += added; s.stats[SJS_ROWS_MADE] += (double)added; s.finished = false;
     return s.n_rows > s.compact_at ? sj_compact(c, s) : 0;
 }
 
@@ -1892,14 +1950,14 @@ int l2r_sj_add(l2r_ctx *c, const l2r_sj_records *r)
     if (s.cnt.ensure(N + 1)) return -2;
     const SjRecs recs{(int64_t)N, s.flag.p, s.tid.p, s.pos.p, s.uniq.p, s.cig_off.p, s.cig.p};
     const unsigned grid = (unsigned)((N + SJ_THREADS - 1) / SJ_THREADS);
-    if ((rc = timed_launch(c, s.timing, s.ev, &s.stats[5], [&] { hipLaunchKernelGGL(k_sj_count, dim3(grid), dim3(SJ_THREADS), 0, c->stream, recs, s.prm, s.cnt.p); }))) return rc;
-    if ((rc = timed_launch(c, s.timing, s.ev, &s.stats[6], [&] { scan_u32(c, s.cnt.p, (int64_t)N, s.word.p); }))) return rc;
+    if ((rc = s.clk.launch(c, &s.stats[SJS_K_COUNT], [&] { hipLaunchKernelGGL(k_sj_count, dim3(grid), dim3(SJ_THREADS), 0, c->stream, recs, s.prm, s.cnt.p); }))) return rc;
+    if ((rc = s.clk.launch(c, &s.stats[SJS_K_COUNT_SCAN], [&] { scan_u32(c, s.cnt.p, (int64_t)N, s.word.p); }))) return rc;
     uint32_t total = 0;
     HIP_TRY(hipMemcpyAsync(&total, s.word.p, 4, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     if (total == 0) return 0;
     if ((rc = sj_rows_reserve(c, s, s.rows[s.cur], (size_t)s.n_rows + total, (size_t)s.n_rows))) return rc;
-    if ((rc = timed_launch(c, s.timing, s.ev, &s.stats[7], [&] {
+    if ((rc = s.clk.launch(c, &s.stats[SJS_K_FILL], [&] {
             if (s.over) hipLaunchKernelGGL(k_sj_fill<true>, dim3(grid), dim3(SJ_THREADS), 0, c->stream, recs, s.prm, (const uint32_t *)s.cnt.p, s.rows[s.cur].cols(), s.n_rows, s.n_rows + (int64_t)total);
             else hipLaunchKernelGGL(k_sj_fill<false>, dim3(grid), dim3(SJ_THREADS), 0, c->stream, recs, s.prm, (const uint32_t *)s.cnt.p, s.rows[s.cur].cols(), s.n_rows, s.n_rows + (int64_t)total);
         }))) return rc;
@@ -1964,7 +2022,7 @@ int l2r_sj_finish(l2r_ctx *c, int64_t *n_rows)
         HIP_TRY(hipMemcpyAsync(s.word.p + 1, &bad, 4, hipMemcpyHostToDevice, c->stream));
         const SjGenome g{s.n_seq, s.seq_off.p, s.bases.p};
         const SjCols t = s.rows[s.cur].cols();
-        if ((rc = timed_launch(c, s.timing, s.ev, &s.stats[14], [&] { hipLaunchKernelGGL(k_sj_motif, dim3((n + SJ_THREADS - 1) / SJ_THREADS), dim3(SJ_THREADS), 0, c->stream, (const int32_t *)t.tid, (const int32_t *)t.don,
+        if ((rc = s.clk.launch(c, &s.stats[SJS_K_MOTIF], [&] { hipLaunchKernelGGL(k_sj_motif, dim3((n + SJ_THREADS - 1) / SJ_THREADS), dim3(SJ_THREADS), 0, c->stream, (const int32_t *)t.tid, (const int32_t *)t.don,
                                                              (const int32_t *)t.acc, n, g, s.strand[0].p, s.motif[0].p, s.word.p + 1); }))) return rc;
         HIP_TRY(hipMemcpyAsync(&bad, s.word.p + 1, 4, hipMemcpyDeviceToHost, c->stream));
         HIP_TRY(hipStreamSynchronize(c->stream));
@@ -2004,8 +2062,7 @@ int l2r_sj_annotate(l2r_ctx *c, const l2r_annotation *a)
     SjState &s = c->sj;
     SjIntrons &in = c->sj_intr;
     SjState &is = in.st;
-    if ((rc = sj_state_begin(c, is, false))) return rc;
-    is.timing = s.timing;
+    if ((rc = sj_state_begin(c, is, false, s.clk.on))) return rc;
     uint32_t n_in = 0;
     if (a->n_exon > 0) {
         const size_t T = (size_t)a->n_tx, E = (size_t)a->n_exon;
@@ -2014,7 +2071,7 @@ int l2r_sj_annotate(l2r_ctx *c, const l2r_annotation *a)
         if ((rc = sj_rows_reserve(c, is, is.rows[0], E, 0))) return rc;
         HIP_TRY(hipMemsetAsync(is.word.p + 2, 0, 4, c->stream));
         const SjAnno an{a->n_tx, a->n_exon, in.tx_tid.p, in.tx_ex_off.p, in.ex_start.p, in.ex_end.p};
-        if ((rc = timed_launch(c, s.timing, s.ev, &s.stats[SJS_K_INTRONS], [&] { hipLaunchKernelGGL(k_sj_introns, dim3((unsigned)((E + SJ_THREADS - 1) / SJ_THREADS)), dim3(SJ_THREADS), 0, c->stream, an, is.rows[0].cols(),
+        if ((rc = s.clk.launch(c, &s.stats[SJS_K_INTRONS], [&] { hipLaunchKernelGGL(k_sj_introns, dim3((unsigned)((E + SJ_THREADS - 1) / SJ_THREADS)), dim3(SJ_THREADS), 0, c->stream, an, is.rows[0].cols(),
                                                                           is.word.p + 2, (uint32_t)E); }))) return rc;
         HIP_TRY(hipMemcpyAsync(&n_in, is.word.p + 2, 4, hipMemcpyDeviceToHost, c->stream));
         HIP_TRY(hipStreamSynchronize(c->stream));
@@ -2022,13 +2079,13 @@ int l2r_sj_annotate(l2r_ctx *c, const l2r_annotation *a)
         is.n_rows = n_in;
         if ((rc = sj_compact(c, is))) return rc;
         n_in = (uint32_t)is.n_rows;
-        for (int k = 8; k <= 13; ++k) s.stats[SJS_INTRON_SORT] += is.stats[k];
+        for (int k = SJS_K_HIST12; k <= SJS_K_REDUCE; ++k) s.stats[SJS_INTRON_SORT] += is.stats[k];
     }
     s.stats[SJS_INTRONS] = n_in;
     const uint32_t n = (uint32_t)s.n_rows;
     if (n) {
         const SjCols t = s.rows[s.cur].cols();
-        if ((rc = timed_launch(c, s.timing, s.ev, &s.stats[SJS_K_ANNOTATE], [&] { hipLaunchKernelGGL(k_sj_annotate, dim3((n + SJ_THREADS - 1) / SJ_THREADS), dim3(SJ_THREADS), 0, c->stream, (const int32_t *)t.tid,
+        if ((rc = s.clk.launch(c, &s.stats[SJS_K_ANNOTATE], [&] { hipLaunchKernelGGL(k_sj_annotate, dim3((n + SJ_THREADS - 1) / SJ_THREADS), dim3(SJ_THREADS), 0, c->stream, (const int32_t *)t.tid,
                                                                            (const int32_t *)t.don, (const int32_t *)t.acc, n, is.rows[is.cur].cols(), n_in, s.anno[s.bcur].p); }))) return rc;
         HIP_TRY(hipStreamSynchronize(c->stream));
     }
@@ -2041,14 +2098,14 @@ static int sj_take_kept(l2r_ctx *c, SjState &s, uint32_t n, const char *who, uin
     int rc;
     const unsigned grid = (n + SJ_THREADS - 1) / SJ_THREADS;
     const int bsrc = s.bcur, bdst = 1 - s.bcur, src = s.cur, dst = 1 - s.cur;
-    if ((rc = timed_launch(c, s.timing, s.ev, &s.stats[SJS_K_KEEP_SCAN], [&] { scan_u32(c, s.head.p, (int64_t)n, s.word.p); }))) return rc;
+    if ((rc = s.clk.launch(c, &s.stats[SJS_K_KEEP_SCAN], [&] { scan_u32(c, s.head.p, (int64_t)n, s.word.p); }))) return rc;
     uint32_t kept = 0;
     HIP_TRY(hipMemcpyAsync(&kept, s.word.p, 4, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     if (kept > n) return fail(-2, "[%s] %u of %u rows kept", who, kept, n);
     if (kept) {
         const SjBytes bin{s.strand[bsrc].p, s.motif[bsrc].p, s.anno[bsrc].p}, bout{s.strand[bdst].p, s.motif[bdst].p, s.anno[bdst].p};
-        if ((rc = timed_launch(c, s.timing, s.ev, &s.stats[SJS_K_TAKE], [&] { hipLaunchKernelGGL(k_sj_take, dim3(grid), dim3(SJ_THREADS), 0, c->stream, s.rows[src].cols(), bin, n, (const uint32_t *)s.head.p,
+        if ((rc = s.clk.launch(c, &s.stats[SJS_K_TAKE], [&] { hipLaunchKernelGGL(k_sj_take, dim3(grid), dim3(SJ_THREADS), 0, c->stream, s.rows[src].cols(), bin, n, (const uint32_t *)s.head.p,
                                                                        s.rows[dst].cols(), bout, kept); }))) return rc;
         HIP_TRY(hipStreamSynchronize(c->stream));
     }
@@ -2079,7 +2136,7 @@ static int sj_filter_local(l2r_ctx *c, const l2r_sj_filter *f, const SjFilter2 *
     if ((rc = sj_filter_reserve(c, s, n))) return rc;
     const SjFilter2 none = {};
     if (g) HIP_TRY(hipMemsetAsync(s.word.p + 3, 0, 4, c->stream));
-    if ((rc = timed_launch(c, s.timing, s.ev, &s.stats[SJS_K_KEEP], [&] {
+    if ((rc = s.clk.launch(c, &s.stats[SJS_K_KEEP], [&] {
             if (g) hipLaunchKernelGGL(k_sj_keep<true>, dim3(grid), dim3(SJ_THREADS), 0, c->stream, s.rows[s.cur].cols(), (const uint8_t *)s.motif[s.bcur].p,
                                       (const uint8_t *)s.anno[s.bcur].p, n, flt, *g, s.head.p, s.word.p + 3);
             else hipLaunchKernelGGL(k_sj_keep<false>, dim3(grid), dim3(SJ_THREADS), 0, c->stream, s.rows[s.cur].cols(), (const uint8_t *)s.motif[s.bcur].p,
@@ -2109,52 +2166,26 @@ int l2r_sj_filter_rows(l2r_ctx *c, const l2r_sj_filter *f, int64_t *n_rows)
     return 0;
 }
 
-static int sort_passes(l2r_ctx *c, SortState &s, uint32_t n, int *n_pass_out, bool *in_order_out, int *src_out);
-
-// sort_passes in the context's sort buffers for another entry point (the acceptor order of `sjtab -d`, the hash order of `sort -n`): what
-// l2r_sort_stats says of the last l2r_sort_order stays, and with `timing` the device milliseconds of the passes are added to *ms
-static int sort_passes_beside(l2r_ctx *c, bool timing, double *ms, uint32_t n, int *n_pass_out, int *src_out)
-{
-    SortState &o = c->sort;
-    double sort_stats[sizeof o.stats / sizeof o.stats[0]];
-    const bool sort_timing = o.timing;
-    std::copy(std::begin(o.stats), std::end(o.stats), sort_stats);
-    for (double &v : o.stats) v = 0;
-    o.timing = timing;
-    bool in_order = false;
-    const int rc = sort_passes(c, o, n, n_pass_out, &in_order, src_out);
-    *ms += o.stats[SORTS_K_HIST] + o.stats[SORTS_K_SCAN] + o.stats[SORTS_K_SCATTER];
-    std::copy(std::begin(sort_stats), std::end(sort_stats), o.stats);
-    o.timing = sort_timing;
-    return rc;
-}
-
 // The neighbour stage over the rows the row-local stage left (s.rows[s.cur], sorted by (tid, don, acc)).
 static int sj_filter_near(l2r_ctx *c, const SjFilter2 &g)
 {
     SjState &s = c->sj;
-    SortState &o = c->sort;
     const uint32_t n = (uint32_t)s.n_rows;
     if (!n) return 0;
     const unsigned grid = (n + SJ_THREADS - 1) / SJ_THREADS;
     int rc;
     if ((rc = sj_filter_reserve(c, s, n))) return rc;
-    if (s.near_acc.ensure(n) || o.key[0].ensure(n) || o.hist.ensure(SORT_KEY_BYTES * 256 + 1) || o.word.ensure(4)) return -2;
-    for (int k = 0; k < 2; ++k) if (!o.ev[k]) HIP_TRY(hipEventCreate(&o.ev[k]));
+    if (s.near_acc.ensure(n)) return -2;
     const SjCols t = s.rows[s.cur].cols();
-    HIP_TRY(hipMemsetAsync(o.hist.p, 0, (SORT_KEY_BYTES * 256 + 1) * sizeof(uint32_t), c->stream));
-    if ((rc = timed_launch(c, s.timing, s.ev, &s.stats[SJS_K_ACC_KEYS], [&] {
-            hipLaunchKernelGGL(k_radix_keys<SjAccKeyOf>, dim3(std::min(grid, 2048u)), dim3(RADIX_THREADS), 0, c->stream, SjAccKeyOf{t.tid, t.acc}, (int64_t)n, o.key[0].p, o.hist.p,
-                               o.hist.p + SORT_KEY_BYTES * 256);
-        }))) return rc;
-    int n_pass = 0, src = 0;
-    if ((rc = sort_passes_beside(c, s.timing, &s.stats[SJS_K_ACC_ORDER], n, &n_pass, &src))) return rc;
+    double *const ms[3] = {&s.stats[SJS_K_ACC_ORDER], &s.stats[SJS_K_ACC_ORDER], &s.stats[SJS_K_ACC_ORDER]};
+    int n_pass = 0;
+    const uint32_t *idx = nullptr;
+    if ((rc = order_by_keys(c, s.clk, SjAccKeyOf{t.tid, t.acc}, n, &s.stats[SJS_K_ACC_KEYS], ms, &n_pass, nullptr, &idx))) return rc;
     s.stats[SJS_ACC_PASSES] = n_pass;
-    const uint32_t *idx = n_pass ? o.idx[src].p : nullptr;
-    if ((rc = timed_launch(c, s.timing, s.ev, &s.stats[SJS_K_NEAR_ACC], [&] {
+    if ((rc = s.clk.launch(c, &s.stats[SJS_K_NEAR_ACC], [&] {
             hipLaunchKernelGGL(k_sj_near_acc, dim3(grid), dim3(SJ_THREADS), 0, c->stream, (const int32_t *)t.tid, (const int32_t *)t.acc, idx, n, s.near_acc.p);
         }))) return rc;
-    if ((rc = timed_launch(c, s.timing, s.ev, &s.stats[SJS_K_KEEP_NEAR], [&] {
+    if ((rc = s.clk.launch(c, &s.stats[SJS_K_KEEP_NEAR], [&] {
             hipLaunchKernelGGL(k_sj_keep_near, dim3(grid), dim3(SJ_THREADS), 0, c->stream, (const int32_t *)t.tid, (const int32_t *)t.don, (const int32_t *)s.near_acc.p,
                                (const uint8_t *)s.motif[s.bcur].p, (const uint8_t *)s.anno[s.bcur].p, n, g, s.head.p);
         }))) return rc;
@@ -2243,47 +2274,9 @@ int l2r_sj_download_tab(l2r_ctx *c, l2r_sj_tab *t)
     return sj_download(c, t->cap, &t->n, dst, bytes, "l2r_sj_download_tab");
 }
 
-int l2r_sj_stats(l2r_ctx *c, double *out, int n)
-{
-    if (!c || !out || n < 0) return fail(-1, "[l2r_sj_stats] bad argument");
-    for (int k = 0; k < n; ++k) out[k] = k < SJS_N ? c->sj.stats[k] : 0.0;
-    return 0;
-}
+int l2r_sj_stats(l2r_ctx *c, double *out, int n) { return stats_out(c ? c->sj.stats : nullptr, SJS_N, out, n, "l2r_sj_stats"); }
 
 // ---------------------------------------------------------------------------------------------- sort, filter -S
-// The radix passes over the keys in s.key[0][0, n), behind a keys kernel that left the histograms of the eight key bytes and the descent
-// word in s.hist: l2r_sort_order's, and the acceptor order of l2r_sj_filter_rows2.  A byte that is equal in every key is a pass that is
-// not run, keys that never descend run none (L2R_SORT_FORCE=1: all eight, whatever the keys).  *n_pass_out: passes run; the order is
-// then in s.idx[*src_out], and with no pass it is the identity and no index column is written.
-static int sort_passes(l2r_ctx *c, SortState &s, uint32_t n, int *n_pass_out, bool *in_order_out, int *src_out)
-{
-    const char *e = getenv("L2R_SORT_FORCE");
-    const bool force = e && atoi(e) != 0;
-    const size_t N = n;
-    uint32_t h8[SORT_KEY_BYTES * 256 + 1];
-    HIP_TRY(hipMemcpyAsync(h8, s.hist.p, sizeof h8, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    const bool in_order = h8[SORT_KEY_BYTES * 256] == 0u;
-    int pass_byte[SORT_KEY_BYTES], n_pass = 0;
-    for (int b = 0; b < SORT_KEY_BYTES; ++b) if (force || (!in_order && !byte_is_one_value(h8 + b * 256, n))) pass_byte[n_pass++] = b;
-    *n_pass_out = n_pass; *in_order_out = in_order; *src_out = n_pass & 1;
-    if (n_pass == 0) return 0;
-    if (s.idx[0].ensure(N) || s.idx[1].ensure(N) || (n_pass > 1 && s.key[1].ensure(N))) return -2;
-    return radix_passes(c, pass_byte, n_pass, n, s.tile_hist, s.word.p,
-        [&](int k, auto f) { return timed_launch(c, s.timing, s.ev, &s.stats[SORTS_K_HIST + k], f, c->check_stages); },
-        [&](int b, int p, uint32_t n_tiles) {
-            hipLaunchKernelGGL((k_radix_digit_hist<SortRows<false, false>>), dim3(n_tiles), dim3(RADIX_THREADS), 0, c->stream,
-                               SortRows<false, false>{s.key[p & 1].p, nullptr, nullptr, nullptr}, n, b, n_tiles, s.tile_hist.p);
-        },
-        [&](int b, int p, bool last, uint32_t n_tiles) {
-            const int from = p & 1;
-#define SORT_SCATTER(F, L) hipLaunchKernelGGL((k_radix_scatter<SortRows<F, L>>), dim3(n_tiles), dim3(RADIX_THREADS), 0, c->stream, \
-                                              SortRows<F, L>{s.key[from].p, s.idx[from].p, s.key[1 - from].p, s.idx[1 - from].p}, n, b, n_tiles, (const uint32_t *)s.tile_hist.p)
-            if (p == 0 && last) SORT_SCATTER(true, true); else if (p == 0) SORT_SCATTER(true, false); else if (last) SORT_SCATTER(false, true); else SORT_SCATTER(false, false);
-#undef SORT_SCATTER
-        });
-}
-
 int l2r_sort_order(l2r_ctx *c, const l2r_sort_records *r, uint32_t *order_out)
 {
     if (!c || !r) return fail(-1, "[l2r_sort_order] null argument");
@@ -2294,42 +2287,28 @@ int l2r_sort_order(l2r_ctx *c, const l2r_sort_records *r, uint32_t *order_out)
         return fail(-1, "[l2r_sort_order] %lld records: one sort takes 2^32 - 1 - %d at most (the index of a record is a 32-bit word)", (long long)r->n, L2R_SORT_TILE);
     if (r->n == 0) { s.stats[SORTS_IN_ORDER] = 1; return 0; }
     if (!r->flag || !r->tid || !r->pos || !order_out) return fail(-1, "[l2r_sort_order] null column");
-    const char *e = getenv("L2R_SORT_TIMING");
-    s.timing = e && atoi(e) != 0;
     HIP_TRY(hipSetDevice(c->device));
-    for (int k = 0; k < 2; ++k) if (!s.ev[k]) HIP_TRY(hipEventCreate(&s.ev[k]));
-    const size_t N = (size_t)r->n;
-    const uint32_t n = (uint32_t)r->n;
-    s.stats[SORTS_ROWS] = (double)r->n;
     int rc;
+    if ((rc = s.clk.begin(env_on("L2R_SORT_TIMING"), c->check_stages))) return rc;
+    const size_t N = (size_t)r->n;
+    s.stats[SORTS_ROWS] = (double)r->n;
     if ((rc = to_dev(c, s.flag, r->flag, N)) || (rc = to_dev(c, s.tid, r->tid, N)) || (rc = to_dev(c, s.pos, r->pos, N))) return rc;
-    if (s.key[0].ensure(N) || s.hist.ensure(SORT_KEY_BYTES * 256 + 1) || s.word.ensure(4)) return -2;
-    // the keys, which of their bytes differ at all, whether they descend anywhere
-    HIP_TRY(hipMemsetAsync(s.hist.p, 0, (SORT_KEY_BYTES * 256 + 1) * sizeof(uint32_t), c->stream));
-    const unsigned grid = (unsigned)std::min<size_t>((N + SORT_THREADS - 1) / SORT_THREADS, 2048);
-    if ((rc = timed_launch(c, s.timing, s.ev, &s.stats[SORTS_K_KEYS], [&] {
-            hipLaunchKernelGGL(k_radix_keys<SortKeyOf>, dim3(grid), dim3(RADIX_THREADS), 0, c->stream, SortKeyOf{s.flag.p, s.tid.p, s.pos.p}, r->n, s.key[0].p, s.hist.p,
-                               s.hist.p + SORT_KEY_BYTES * 256);
-        }, c->check_stages))) return rc;
-    int n_pass = 0, src = 0; bool in_order = false;
-    if ((rc = sort_passes(c, s, n, &n_pass, &in_order, &src))) return rc;
+    double *const ms[3] = {&s.stats[SORTS_K_HIST], &s.stats[SORTS_K_SCAN], &s.stats[SORTS_K_SCATTER]};
+    int n_pass = 0; bool in_order = false;
+    const uint32_t *idx = nullptr;
+    if ((rc = order_by_keys(c, s.clk, SortKeyOf{s.flag.p, s.tid.p, s.pos.p}, (uint32_t)r->n, &s.stats[SORTS_K_KEYS], ms, &n_pass, &in_order, &idx))) return rc;
     s.stats[SORTS_IN_ORDER] = in_order ? 1 : 0;
     if (n_pass == 0) {                                              // (keys that never descend: the order is the identity)
         for (size_t i = 0; i < N; ++i) order_out[i] = (uint32_t)i;
         return 0;
     }
     s.stats[SORTS_PASSES] = n_pass;
-    HIP_TRY(hipMemcpyAsync(order_out, s.idx[src].p, N * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(order_out, idx, N * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     return 0;
 }
 
-int l2r_sort_stats(l2r_ctx *c, double *out, int n)
-{
-    if (!c || !out || n < 0) return fail(-1, "[l2r_sort_stats] bad argument");
-    for (int k = 0; k < n; ++k) out[k] = k < SORTS_N ? c->sort.stats[k] : 0.0;
-    return 0;
-}
+int l2r_sort_stats(l2r_ctx *c, double *out, int n) { return stats_out(c ? c->sort.stats : nullptr, SORTS_N, out, n, "l2r_sort_stats"); }
 
 // ---------------------------------------------------------------------------------------------- sort -n, filter -N, fusion -N
 // slots of l2r_name_stats
@@ -2341,38 +2320,31 @@ static_assert(NAMES_N == sizeof(NameState::stats) / sizeof(double), "l2r_name_st
 static int name_order_seeded(l2r_ctx *c, uint32_t n, int64_t off0, uint64_t seed, uint64_t mask, uint32_t *groups, uint32_t *mismatch, uint32_t *moved)
 {
     NameState &m = c->name;
-    SortState &o = c->sort;
     const size_t N = n;
     const unsigned grid = (unsigned)((N + NAME_THREADS - 1) / NAME_THREADS);
     const NameCols cols{m.blob.p, m.off.p, off0};
     int rc;
-    HIP_TRY(hipMemsetAsync(o.hist.p, 0, (SORT_KEY_BYTES * 256 + 1) * sizeof(uint32_t), c->stream));
     HIP_TRY(hipMemsetAsync(m.word.p, 0, 4 * sizeof(uint32_t), c->stream));
-    // the hashes, which of their bytes differ at all, whether they descend anywhere; a copy in record order for k_name_heads (the passes
-    // use both key columns in turn)
-    if ((rc = timed_launch(c, m.timing, m.ev, &m.stats[NAMES_K_HASH], [&] {
-            hipLaunchKernelGGL(k_radix_keys<NameHashOf>, dim3(std::min(grid, 2048u)), dim3(RADIX_THREADS), 0, c->stream, NameHashOf{cols, seed, mask}, (int64_t)n, o.key[0].p, o.hist.p,
-                               o.hist.p + SORT_KEY_BYTES * 256);
-        }, c->check_stages))) return rc;
-    HIP_TRY(hipMemcpyAsync(m.hkey.p, o.key[0].p, N * sizeof(uint64_t), hipMemcpyDeviceToDevice, c->stream));
-    int n_pass = 0, src = 0;
-    if ((rc = sort_passes_beside(c, m.timing, &m.stats[NAMES_K_PASSES], n, &n_pass, &src))) return rc;
+    // the order by the hashes; a copy of them in record order for k_name_heads
+    double *const ms[3] = {&m.stats[NAMES_K_PASSES], &m.stats[NAMES_K_PASSES], &m.stats[NAMES_K_PASSES]};
+    int n_pass = 0;
+    const uint32_t *idx = nullptr;
+    if ((rc = order_by_keys(c, m.clk, NameHashOf{cols, seed, mask}, n, &m.stats[NAMES_K_HASH], ms, &n_pass, nullptr, &idx, m.hkey.p))) return rc;
     m.stats[NAMES_PASSES] = n_pass;
-    const uint32_t *idx = n_pass ? o.idx[src].p : nullptr;
-    if ((rc = timed_launch(c, m.timing, m.ev, &m.stats[NAMES_K_HEADS], [&] {
+    if ((rc = m.clk.launch(c, &m.stats[NAMES_K_HEADS], [&] {
             hipLaunchKernelGGL(k_name_heads, dim3(grid), dim3(NAME_THREADS), 0, c->stream, cols, (const uint64_t *)m.hkey.p, idx, n, m.head.p, m.word.p + 1);
-        }, c->check_stages))) return rc;
-    if ((rc = timed_launch(c, m.timing, m.ev, &m.stats[NAMES_K_SCANS], [&] { scan_u32(c, m.head.p, (int64_t)n, m.word.p); }, c->check_stages))) return rc;
+        }))) return rc;
+    if ((rc = m.clk.launch(c, &m.stats[NAMES_K_SCANS], [&] { scan_u32(c, m.head.p, (int64_t)n, m.word.p); }))) return rc;
     HIP_TRY(hipMemsetAsync(m.sizes.p, 0, (N + 1) * sizeof(uint32_t), c->stream));
-    if ((rc = timed_launch(c, m.timing, m.ev, &m.stats[NAMES_K_PLACE], [&] {
+    if ((rc = m.clk.launch(c, &m.stats[NAMES_K_PLACE], [&] {
             hipLaunchKernelGGL(k_name_firsts, dim3(grid), dim3(NAME_THREADS), 0, c->stream, (const uint32_t *)m.head.p, idx, n, m.head_pos.p, m.first_idx.p);
             hipLaunchKernelGGL(k_name_sizes, dim3(grid), dim3(NAME_THREADS), 0, c->stream, (const uint32_t *)m.head.p, (const uint32_t *)m.head_pos.p, (const uint32_t *)m.first_idx.p, n, m.sizes.p);
-        }, c->check_stages))) return rc;
-    if ((rc = timed_launch(c, m.timing, m.ev, &m.stats[NAMES_K_SCANS], [&] { scan_u32(c, m.sizes.p, (int64_t)n, m.word.p + 3); }, c->check_stages))) return rc;
-    if ((rc = timed_launch(c, m.timing, m.ev, &m.stats[NAMES_K_PLACE], [&] {
+        }))) return rc;
+    if ((rc = m.clk.launch(c, &m.stats[NAMES_K_SCANS], [&] { scan_u32(c, m.sizes.p, (int64_t)n, m.word.p + 3); }))) return rc;
+    if ((rc = m.clk.launch(c, &m.stats[NAMES_K_PLACE], [&] {
             hipLaunchKernelGGL(k_name_place, dim3(grid), dim3(NAME_THREADS), 0, c->stream, (const uint32_t *)m.head.p, idx, (const uint32_t *)m.head_pos.p, (const uint32_t *)m.first_idx.p,
                                (const uint32_t *)m.sizes.p, n, m.order.p, m.word.p + 2);
-        }, c->check_stages))) return rc;
+        }))) return rc;
     uint32_t w[4];
     HIP_TRY(hipMemcpyAsync(w, m.word.p, sizeof w, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
@@ -2389,24 +2361,20 @@ int l2r_name_order(l2r_ctx *c, const l2r_name_records *r, uint32_t *order_out, i
         if (name_check(r, order_out, n_groups, msg)) return fail(-1, "%s", msg.c_str()); }
     *n_groups = 0;
     if (r->n == 0) { m.stats[NAMES_IDENTITY] = 1; return 0; }
-    const char *e = getenv("L2R_SORT_TIMING");
-    m.timing = e && atoi(e) != 0;
     uint64_t mask = ~0ull;
-    if ((e = getenv("L2R_NAME_HASH_BITS"))) { const int b = atoi(e); mask = b >= 64 ? ~0ull : b <= 0 ? 0ull : (1ull << b) - 1ull; }
+    if (const char *e = getenv("L2R_NAME_HASH_BITS")) { const int b = atoi(e); mask = b >= 64 ? ~0ull : b <= 0 ? 0ull : (1ull << b) - 1ull; }
     HIP_TRY(hipSetDevice(c->device));
-    SortState &o = c->sort;
-    for (int k = 0; k < 2; ++k) { if (!m.ev[k]) HIP_TRY(hipEventCreate(&m.ev[k])); if (!o.ev[k]) HIP_TRY(hipEventCreate(&o.ev[k])); }
+    int rc;
+    if ((rc = m.clk.begin(env_on("L2R_SORT_TIMING"), c->check_stages))) return rc;
     const size_t N = (size_t)r->n;
     const uint32_t n = (uint32_t)r->n;
     const int64_t off0 = r->name_off[0];
     const size_t bytes = (size_t)(r->name_off[N] - off0);
     m.stats[NAMES_ROWS] = (double)r->n;
-    int rc;
     if ((rc = to_dev(c, m.off, r->name_off, N + 1))) return rc;
     if (m.blob.ensure((bytes + NAME_BLOB_ROOM + 7) / 8)) return -2;
     if (bytes) HIP_TRY(hipMemcpyAsync(m.blob.p, r->names + off0, bytes, hipMemcpyHostToDevice, c->stream));
-    if (o.key[0].ensure(N) || o.hist.ensure(SORT_KEY_BYTES * 256 + 1) || o.word.ensure(4) || m.hkey.ensure(N) || m.head.ensure(N + 1) || m.head_pos.ensure(N + 1) ||
-        m.first_idx.ensure(N) || m.sizes.ensure(N + 1) || m.order.ensure(N) || m.word.ensure(4)) return -2;
+    if (m.hkey.ensure(N) || m.head.ensure(N + 1) || m.head_pos.ensure(N + 1) || m.first_idx.ensure(N) || m.sizes.ensure(N + 1) || m.order.ensure(N) || m.word.ensure(4)) return -2;
     static const uint64_t seeds[2] = {0x243f6a8885a308d3ull, 0x13198a2e03707344ull};
     uint32_t groups = 0, mismatch = 1, moved = 1;
     int route = 0;
@@ -2430,12 +2398,7 @@ int l2r_name_order(l2r_ctx *c, const l2r_name_records *r, uint32_t *order_out, i
     return 0;
 }
 
-int l2r_name_stats(l2r_ctx *c, double *out, int n)
-{
-    if (!c || !out || n < 0) return fail(-1, "[l2r_name_stats] bad argument");
-    for (int k = 0; k < n; ++k) out[k] = k < NAMES_N ? c->name.stats[k] : 0.0;
-    return 0;
-}
+int l2r_name_stats(l2r_ctx *c, double *out, int n) { return stats_out(c ? c->name.stats : nullptr, NAMES_N, out, n, "l2r_name_stats"); }
 
 // ---------------------------------------------------------------------------------------------- sort-gtf
 // slots of l2r_gtf_stats
@@ -2461,17 +2424,6 @@ static int gtf_order_on_host(l2r_ctx *c, const l2r_gtf_text *t, int64_t *n_rows)
     return 0;
 }
 
-// One stable stage of the order: the keys are in the sort buffers (k_radix_keys has run); *idx = the order it leaves, null: the identity
-static int gtf_stage(l2r_ctx *c, uint32_t n, int stat, const uint32_t **idx)
-{
-    GtfState &m = c->gtf;
-    int n_pass = 0, src = 0, rc;
-    if ((rc = sort_passes_beside(c, m.timing, &m.stats[GTFS_K_SORT], n, &n_pass, &src))) return rc;
-    m.stats[stat] = n_pass;
-    *idx = n_pass ? c->sort.idx[src].p : nullptr;
-    return 0;
-}
-
 int l2r_gtf_order(l2r_ctx *c, const l2r_gtf_text *t, int64_t *n_rows)
 {
     if (!c) return fail(-1, "[l2r_gtf_order] null argument");
@@ -2485,17 +2437,13 @@ int l2r_gtf_order(l2r_ctx *c, const l2r_gtf_text *t, int64_t *n_rows)
     if (t->n_bytes == 0) { m.stats[GTFS_IDENTITY] = 1; return 0; }
     const char *e = getenv("L2R_GTF_ROUTE");
     if ((e && strcmp(e, "host") == 0) || !gtf_text_fits_device(t->n_bytes)) return gtf_order_on_host(c, t, n_rows);
-    e = getenv("L2R_SORT_TIMING");
-    m.timing = e && atoi(e) != 0;
-    e = getenv("L2R_SORT_FORCE");
-    const bool force = e && atoi(e) != 0;
+    const bool force = env_on("L2R_SORT_FORCE");
     HIP_TRY(hipSetDevice(c->device));
-    SortState &o = c->sort;
-    for (int k = 0; k < 2; ++k) { if (!m.ev[k]) HIP_TRY(hipEventCreate(&m.ev[k])); if (!o.ev[k]) HIP_TRY(hipEventCreate(&o.ev[k])); }
+    int rc;
+    if ((rc = m.clk.begin(env_on("L2R_SORT_TIMING"), c->check_stages))) return rc;
     const uint32_t n = (uint32_t)t->n_bytes;
     const size_t n_words = ((size_t)n + GTF_TEXT_ROOM + 15) / 16;
     const unsigned n_tiles = (unsigned)(((size_t)n + GTF_TILE - 1) / GTF_TILE);
-    int rc;
     // ---- lines
     if (m.text.ensure(n_words) || m.tile_cnt.ensure((size_t)n_tiles + 1) || m.word.ensure(GTFW_N)) return -2;
     HIP_TRY(hipMemsetAsync((uint8_t *)m.text.p + n, 0, n_words * 16 - n, c->stream));
@@ -2503,10 +2451,10 @@ int l2r_gtf_order(l2r_ctx *c, const l2r_gtf_text *t, int64_t *n_rows)
     HIP_TRY(hipMemsetAsync(m.word.p, 0, GTFW_N * sizeof(uint32_t), c->stream));
     HIP_TRY(hipMemsetAsync(m.word.p + GTFW_BAD_LINE, 0xff, sizeof(uint32_t), c->stream));
     const uint8_t *text8 = (const uint8_t *)m.text.p;
-    if ((rc = timed_launch(c, m.timing, m.ev, &m.stats[GTFS_K_LINES], [&] {
+    if ((rc = m.clk.launch(c, &m.stats[GTFS_K_LINES], [&] {
             hipLaunchKernelGGL(k_gtf_count, dim3(n_tiles), dim3(GTF_THREADS), 0, c->stream, (const uint4 *)m.text.p, n, m.tile_cnt.p, m.word.p + GTFW_NUL);
-        }, c->check_stages))) return rc;
-    if ((rc = timed_launch(c, m.timing, m.ev, &m.stats[GTFS_K_SCANS], [&] { scan_u32(c, m.tile_cnt.p, (int64_t)n_tiles, m.word.p + GTFW_NEWLINES); }, c->check_stages))) return rc;
+        }))) return rc;
+    if ((rc = m.clk.launch(c, &m.stats[GTFS_K_SCANS], [&] { scan_u32(c, m.tile_cnt.p, (int64_t)n_tiles, m.word.p + GTFW_NEWLINES); }))) return rc;
     uint32_t w[GTFW_N];
     HIP_TRY(hipMemcpyAsync(w, m.word.p, sizeof w, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
@@ -2517,19 +2465,19 @@ int l2r_gtf_order(l2r_ctx *c, const l2r_gtf_text *t, int64_t *n_rows)
     const unsigned grid_l = (unsigned)((NL + GTF_THREADS - 1) / GTF_THREADS);
     m.stats[GTFS_LINES] = (double)L;
     if (m.start.ensure(NL + 1) || m.kept.ensure(NL + 1) || m.tx.ensure(NL + 1) || m.l_name_off.ensure(NL) || m.l_name_len.ensure(NL) || m.l_s.ensure(NL) || m.l_e.ensure(NL)) return -2;
-    if ((rc = timed_launch(c, m.timing, m.ev, &m.stats[GTFS_K_LINES], [&] {
+    if ((rc = m.clk.launch(c, &m.stats[GTFS_K_LINES], [&] {
             hipLaunchKernelGGL(k_gtf_starts, dim3(n_tiles), dim3(GTF_THREADS), 0, c->stream, (const uint4 *)m.text.p, n, (const uint32_t *)m.tile_cnt.p, L, open_end, m.start.p);
-        }, c->check_stages))) return rc;
+        }))) return rc;
     // ---- fields
     const GtfLineCols lines{m.kept.p, m.tx.p, m.l_name_off.p, m.l_name_len.p, m.l_s.p, m.l_e.p};
-    if ((rc = timed_launch(c, m.timing, m.ev, &m.stats[GTFS_K_FIELDS], [&] {
+    if ((rc = m.clk.launch(c, &m.stats[GTFS_K_FIELDS], [&] {
             hipLaunchKernelGGL(k_gtf_fields, dim3(grid_l), dim3(GTF_THREADS), 0, c->stream, text8, n, (const uint32_t *)m.start.p, L, lines, m.word.p + GTFW_BAD_LINE);
-        }, c->check_stages))) return rc;
+        }))) return rc;
     // ---- compaction and carry: both scans in one launch
-    if ((rc = timed_launch(c, m.timing, m.ev, &m.stats[GTFS_K_SCANS], [&] {
+    if ((rc = m.clk.launch(c, &m.stats[GTFS_K_SCANS], [&] {
             ScanJobs jobs = {}; jobs.job[0] = ScanJob{m.kept.p, (int64_t)L, m.word.p + GTFW_ROWS}; jobs.job[1] = ScanJob{m.tx.p, (int64_t)L, m.word.p + GTFW_TX};
             hipLaunchKernelGGL(k_scan_u32, dim3(2), dim3(1024), 0, c->stream, jobs);
-        }, c->check_stages))) return rc;
+        }))) return rc;
     HIP_TRY(hipMemcpyAsync(w, m.word.p, sizeof w, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     {   // the domain: the smallest of the first line with a NUL byte and the first bad transcript line
@@ -2553,22 +2501,22 @@ int l2r_gtf_order(l2r_ctx *c, const l2r_gtf_text *t, int64_t *n_rows)
     if (m.r_start.ensure(NR) || m.r_len.ensure(NR) || m.r_line.ensure(NR) || m.r_tx.ensure(NR) || m.t_name_off.ensure(NT) || m.t_name_len.ensure(NT) || m.t_s.ensure(NT) || m.t_e.ensure(NT) ||
         m.head.ensure(NT + 1) || m.c.ensure(NR) || m.s.ensure(NR) || m.e.ensure(NR)) return -2;
     const GtfTxCols txs{m.t_name_off.p, m.t_name_len.p, m.t_s.p, m.t_e.p};
-    if ((rc = timed_launch(c, m.timing, m.ev, &m.stats[GTFS_K_ROWS], [&] {
+    if ((rc = m.clk.launch(c, &m.stats[GTFS_K_ROWS], [&] {
             hipLaunchKernelGGL(k_gtf_rows, dim3(grid_l), dim3(GTF_THREADS), 0, c->stream, (const uint32_t *)m.start.p, n, L, (const uint32_t *)m.kept.p, (const uint32_t *)m.tx.p, lines, R, T,
                                GtfRowCols{m.r_start.p, m.r_len.p, m.r_line.p, m.r_tx.p}, txs);
             if (T) hipLaunchKernelGGL(k_gtf_chr_heads, dim3(grid_t), dim3(GTF_THREADS), 0, c->stream, text8, n, txs, T, m.head.p);
-        }, c->check_stages))) return rc;
+        }))) return rc;
     // ---- chromosome ranks: the heads to the host, one word per head back
     uint32_t H = 0;
     if (T) {
-        if ((rc = timed_launch(c, m.timing, m.ev, &m.stats[GTFS_K_SCANS], [&] { scan_u32(c, m.head.p, (int64_t)T, m.word.p + GTFW_HEADS); }, c->check_stages))) return rc;
+        if ((rc = m.clk.launch(c, &m.stats[GTFS_K_SCANS], [&] { scan_u32(c, m.head.p, (int64_t)T, m.word.p + GTFW_HEADS); }))) return rc;
         HIP_TRY(hipMemcpyAsync(&H, m.word.p + GTFW_HEADS, sizeof H, hipMemcpyDeviceToHost, c->stream));
         HIP_TRY(hipStreamSynchronize(c->stream));
         if (H == 0 || H > T) return fail(-2, "[l2r_gtf_order] %u heads of %u transcripts", H, T);
         if (m.h_off.ensure(H) || m.h_len.ensure(H) || m.rank.ensure(H)) return -2;
-        if ((rc = timed_launch(c, m.timing, m.ev, &m.stats[GTFS_K_ROWS], [&] {
+        if ((rc = m.clk.launch(c, &m.stats[GTFS_K_ROWS], [&] {
                 hipLaunchKernelGGL(k_gtf_head_take, dim3(grid_t), dim3(GTF_THREADS), 0, c->stream, (const uint32_t *)m.head.p, txs, T, H, m.h_off.p, m.h_len.p);
-            }, c->check_stages))) return rc;
+            }))) return rc;
         std::vector<uint32_t> off(H), len(H), rank(H);
         HIP_TRY(hipMemcpyAsync(off.data(), m.h_off.p, (size_t)H * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
         HIP_TRY(hipMemcpyAsync(len.data(), m.h_len.p, (size_t)H * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
@@ -2581,39 +2529,33 @@ int l2r_gtf_order(l2r_ctx *c, const l2r_gtf_text *t, int64_t *n_rows)
     }
     m.stats[GTFS_HEADS] = (double)H;
     // ---- keys and order
-    if ((rc = timed_launch(c, m.timing, m.ev, &m.stats[GTFS_K_ROWS], [&] {
+    if ((rc = m.clk.launch(c, &m.stats[GTFS_K_ROWS], [&] {
             hipLaunchKernelGGL(k_gtf_triples, dim3(grid_r), dim3(GTF_THREADS), 0, c->stream,
                                GtfTripleIn{m.r_tx.p, m.head.p, m.rank.p, m.t_s.p, m.t_e.p, T, H}, R, m.c.p, m.s.p, m.e.p, m.word.p + GTFW_DESCENDS);
-        }, c->check_stages))) return rc;
+        }))) return rc;
     uint32_t descends = 0;
     HIP_TRY(hipMemcpyAsync(&descends, m.word.p + GTFW_DESCENDS, sizeof descends, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     m.stats[GTFS_IDENTITY] = descends ? 0 : 1;
     const bool sorted = descends || force;
     if (sorted) {
-        if (o.key[0].ensure(NR) || o.hist.ensure(SORT_KEY_BYTES * 256 + 1) || o.word.ensure(4) || m.order1.ensure(NR) || m.order.ensure(NR)) return -2;
-        const unsigned grid_k = std::min(grid_r, 2048u);
+        if (m.order1.ensure(NR) || m.order.ensure(NR)) return -2;
+        double *const ms[3] = {&m.stats[GTFS_K_SORT], &m.stats[GTFS_K_SORT], &m.stats[GTFS_K_SORT]};
         const uint32_t *order1 = nullptr, *perm2 = nullptr;
+        int n_pass = 0;
         // stage 1: by e
-        HIP_TRY(hipMemsetAsync(o.hist.p, 0, (SORT_KEY_BYTES * 256 + 1) * sizeof(uint32_t), c->stream));
-        if ((rc = timed_launch(c, m.timing, m.ev, &m.stats[GTFS_K_SORT], [&] {
-                hipLaunchKernelGGL(k_radix_keys<GtfEndKeyOf>, dim3(grid_k), dim3(RADIX_THREADS), 0, c->stream, GtfEndKeyOf{m.e.p}, (int64_t)R, o.key[0].p, o.hist.p, o.hist.p + SORT_KEY_BYTES * 256);
-            }, c->check_stages))) return rc;
-        if ((rc = gtf_stage(c, R, GTFS_PASSES1, &order1))) return rc;
+        if ((rc = order_by_keys(c, m.clk, GtfEndKeyOf{m.e.p}, R, ms[0], ms, &n_pass, nullptr, &order1))) return rc;
+        m.stats[GTFS_PASSES1] = n_pass;
         if (order1) {                                               // (stage 2 runs in the same index columns)
             HIP_TRY(hipMemcpyAsync(m.order1.p, order1, NR * sizeof(uint32_t), hipMemcpyDeviceToDevice, c->stream));
             order1 = m.order1.p;
         }
         // stage 2: by c << 32 | s, read through stage 1's order
-        HIP_TRY(hipMemsetAsync(o.hist.p, 0, (SORT_KEY_BYTES * 256 + 1) * sizeof(uint32_t), c->stream));
-        if ((rc = timed_launch(c, m.timing, m.ev, &m.stats[GTFS_K_SORT], [&] {
-                hipLaunchKernelGGL(k_radix_keys<GtfChrStartKeyOf>, dim3(grid_k), dim3(RADIX_THREADS), 0, c->stream, GtfChrStartKeyOf{m.c.p, m.s.p, order1, R}, (int64_t)R, o.key[0].p, o.hist.p,
-                                   o.hist.p + SORT_KEY_BYTES * 256);
-            }, c->check_stages))) return rc;
-        if ((rc = gtf_stage(c, R, GTFS_PASSES2, &perm2))) return rc;
-        if ((rc = timed_launch(c, m.timing, m.ev, &m.stats[GTFS_K_COMPOSE], [&] {
+        if ((rc = order_by_keys(c, m.clk, GtfChrStartKeyOf{m.c.p, m.s.p, order1, R}, R, ms[0], ms, &n_pass, nullptr, &perm2))) return rc;
+        m.stats[GTFS_PASSES2] = n_pass;
+        if ((rc = m.clk.launch(c, &m.stats[GTFS_K_COMPOSE], [&] {
                 hipLaunchKernelGGL(k_gtf_compose, dim3(grid_r), dim3(GTF_THREADS), 0, c->stream, order1, perm2, R, m.order.p);
-            }, c->check_stages))) return rc;
+            }))) return rc;
     }
     // ---- the rows, in the order
     std::vector<uint32_t> r_start(NR), r_len(NR), r_line(NR), order(sorted ? NR : 0);
@@ -2648,12 +2590,7 @@ int l2r_gtf_rows_out(l2r_ctx *c, l2r_gtf_rows *rows)
     return 0;
 }
 
-int l2r_gtf_stats(l2r_ctx *c, double *out, int n)
-{
-    if (!c || !out || n < 0) return fail(-1, "[l2r_gtf_stats] bad argument");
-    for (int k = 0; k < n; ++k) out[k] = k < GTFS_N ? c->gtf.stats[k] : 0.0;
-    return 0;
-}
+int l2r_gtf_stats(l2r_ctx *c, double *out, int n) { return stats_out(c ? c->gtf.stats : nullptr, GTFS_N, out, n, "l2r_gtf_stats"); }
 
 int l2r_gtf_check(const l2r_gtf_text *t, int64_t *line, int64_t *counts)
 {

@@ -18,8 +18,9 @@
 //     uint32_t digit_at(uint32_t i, int b)      the digit alone, from the one column byte b lives in (the histogram)
 //     void store(uint32_t o, const Row &)
 //     HIST_UNROLL               rounds of a tile the histogram issues together
-// The host side of a pass (which bytes run, digit hist -> scan -> scatter) is radix_passes in l2r_engine.hip.  No kernel waits for
-// another workgroup.
+// The host side is in l2r_engine.hip: radix_passes is the pass loop (digit hist -> scan -> scatter over the bytes it is given), and
+// order_by_keys is k_radix_keys and the passes over SortRows that follow it (sort_passes: which bytes run), for every command that wants
+// rows in the order of 64-bit keys.  No kernel waits for another workgroup.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
