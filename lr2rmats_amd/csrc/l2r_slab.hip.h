@@ -163,6 +163,16 @@ __device__ __forceinline__ bool tw_vec_used(int i, uint32_t n_win)
     if (i < 2 * WIN_TX + WIN_TX / 4) return (uint32_t)(4 * (i - 2 * WIN_TX)) < n_win;
     return true;
 }
+// The thread's vector of tile record *w on its way into LDS: an unconditional load (nothing for the compiler to merge or to wait for:
+// see load_dict_slices, l2r_window.hip.h).  `used`: the vector carries something and the thread has one; every other thread asks for
+// the record's LAST vector, which is always written and lies on a line that travels anyway -- the unwritten part of a record (1.2 KB of a
+// small window's) is not fetched.  Such a thread's LDS vector is zero as before: tw_vec_lds.
+__device__ __forceinline__ int4 load_tw_vec(const TileWin *w, uint32_t n_win, bool &used)
+{
+    used = (int)threadIdx.x < SLAB_TW_VECS && tw_vec_used((int)threadIdx.x, n_win);
+    return reinterpret_cast<const int4 *>(w)[used ? (int)threadIdx.x : SLAB_TW_VECS - 1];
+}
+__device__ __forceinline__ int4 tw_vec_lds(const int4 &v, bool used) { return used ? v : make_int4(0, 0, 0, 0); }
 // Workgroup -> tile.  Workgroups are handed to the 8 XCDs round robin (workgroup b runs on XCD b % 8), each XCD has an L2 of its
 // own: with this mapping an XCD works through ONE contiguous eighth of the tiles, so the dictionary slices of neighbouring
 // tiles (they overlap) are fetched into one L2 instead of all eight.
@@ -1173,7 +1183,9 @@ void k_probe_slab(SlabArgs kernarg_block, const TileSpan *__restrict__ u_span, c
     const uint32_t rot = (ablate & 8) ? 0u : ((t ^ (t >> 3) ^ (t >> 7)) & 3u);
     const uint32_t slot = (threadIdx.x + (rot << 6)) & (uint32_t)(TILE_THREADS - 1);
     const uint32_t row_max = max((rows_w >> (8u * (uint32_t)__builtin_amdgcn_readfirstlane((int)(slot >> 6)))) & 0xffu, 1u) - 1u;
-    const DictRegs dv = load_dict_slices(a, d);
+    // (the conditional forms of these loads: with k_tile's unconditional ones -- load_dict_slices<true>, load_tw_vec -- the instances
+    //  of this kernel that run over a tile list spill one or two registers more)
+    const DictRegs dv = load_dict_slices<false>(a, d);
     int4 twv = make_int4(0, 0, 0, 0);
     if ((int)threadIdx.x < SLAB_TW_VECS && tw_vec_used((int)threadIdx.x, (d.flags & TD_FAST) ? d.n_win : 0u)) twv = reinterpret_cast<const int4 *>(u_tw + t)[threadIdx.x];
     const bool active = slot < n_act;

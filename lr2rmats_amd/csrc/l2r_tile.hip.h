@@ -9,7 +9,12 @@
 //                           op statistics settle under this run's thresholds (tile_exact: nearly all) -- the count itself, written into
 //                           the words the later tiles read (lb_tile / lb_blk / lb_sup, l2r_slab.hip.h).
 //   k_tile                  per tile: the slot records (one load by tile number), CIGAR heads into registers, dictionary slices and
-//                           window into LDS; the CIGAR registers are walked once to PLACE the read's exons as row words at their
+//                           window into LDS.  The front's round trips as compiled: the argument block's words in one wait; then the
+//                           slot record (HBM) beside the scalar loads of tile record / descriptor / statistics, in front of every
+//                           early return (the returns "use" it: slot_unused, below); behind the descriptor one batch of
+//                           unconditional loads -- look-back words, both slices, directory words, window vector: clamped indices,
+//                           load_dict_slices / load_tw_vec -- with no wait between them; one wait for the slot record; the CIGAR heads.
+//                           The CIGAR registers are walked once to PLACE the read's exons as row words at their
 //                           read-order positions in LDS -- the image k_probe_slab builds from slab rows (an exact tile knows every
 //                           read's place from its slot record; any other tile walks twice: once to COUNT, a scan, then to place).
 //                           Window pass, probes, verdicts, the junction check (-j: rows staged over the dead dictionary slices) and
@@ -589,13 +594,23 @@ void k_tile(SlabArgs kernarg_block, const TileRec *__restrict__ u_rec, const Til
     const SlabArgsK sa = slab_args();
     const PipeArgsK a = pipe_args();
     const int lane = threadIdx.x & (WAVE - 1), wv = threadIdx.x >> 6;
+    // The words of the argument block that the front needs come in ONE batch with one wait.  A workgroup behind the last tile (the grid
+    // is a whole number of rounds, fused_grid) does not return here: a return in front of the loads had the compiler fetch the tile
+    // count, then -- behind the branch -- the stamps and the arrays' addresses, then -- behind the next return -- the slot records'
+    // address, a wait each.  It asks for tile 0's records instead and leaves with the tiles that are not this instance's, below.
+    // (The arrays' addresses must not be operands of an asm statement: a `__restrict__` pointer handed to one counts as escaped, every
+    //  later asm statement as a possible store through it, and the scalar loads of the prologue turn into vector loads.)
+    const uint32_t n_tiles = sa->n_tiles;
+    unsigned long long *const stamp_buf = a->f.stamps;
+    asm volatile("" :: "s"(n_tiles), "s"(stamp_buf));
     uint32_t t;
+    bool behind = false;
     if (WIDE) { if (blockIdx.x >= sa->list_cnt[LC_WIDE]) return; t = sa->wide_list[blockIdx.x]; }
     else if (!EXACT && sa->split_on == SPLIT_ON) { if (blockIdx.x >= sa->list_cnt[LC_REST]) return; t = sa->rest_list[blockIdx.x]; }
-    else { t = fused_tile(blockIdx.x); if (t >= sa->n_tiles) return; }
+    else { t = fused_tile(blockIdx.x); behind = t >= n_tiles; t = behind ? 0u : t; }
     // diagnostics (L2R_STAMPS=1), wave 0: [0] records, CIGAR heads asked for, staging  [1] (count walk + barrier)  [6] scan, count
     // published, place walk  [2] window pass  [3] probe rounds  [4] verdicts  [7] the tile's first slot (exon counts in front)  [5] write-out
-    SlabStamp stamp; stamp.start(a->f.stamps); if (stamp.who == 3) stamp.who = -1;
+    SlabStamp stamp; stamp.start(stamp_buf); if (stamp.who == 3) stamp.who = -1;
     // Issue priority: a wave is above the others everywhere but in its classification (window pass, probe rounds, verdicts: the part of a
     // tile that is bound by vector and LDS issue).  The waves that are asking for their records and CIGARs, walking, waiting for the
     // counts in front or writing out get their few instructions in first -- their round trips start earlier, the probing waves lose
@@ -603,23 +618,30 @@ void k_tile(SlabArgs kernarg_block, const TileRec *__restrict__ u_rec, const Til
     // end of the staging: 0.478).
     __builtin_amdgcn_s_setprio(TILE_PRIO);
     const uint32_t clk0 = stamp.p ? (uint32_t)__builtin_amdgcn_s_memrealtime() : 0u;
-    // The thread's slot record lies at a place the tile number alone says (k_tile_index): asked for beside the scalar loads below.
+    // The thread's slot record lies at a place the tile number alone says (k_tile_index): asked for HERE, beside the scalar loads below and
+    // in front of every early return.  What keeps it here: every path that returns early "uses" the record too (slot_unused: an empty
+    // asm), so there is no block further down that the compiler could sink the load into -- with the returns as its only other
+    // successors it was sunk below them, and its trip to HBM began only when the descriptor's had ended -- and inside this block it stays
+    // in front of the `asm volatile` below, where the scalar loads are waited for.  (A volatile load holds its place as well, but it
+    // counts as a possible store for every load behind it: the tile record, the descriptor and the statistics became vector loads.)
+    // A tile that returns has asked for 3 KB it does not use, and waits for them.
     const v3u_a4 srec = *reinterpret_cast<const v3u_a4 *>(u_slot + ((size_t)t * TILE_THREADS + threadIdx.x));
+    auto slot_unused = [&]() { asm volatile("" :: "v"(srec.x), "v"(srec.y), "v"(srec.z)); };
     // The tile's record from the upload and its descriptor from k_describe_scan: every scalar load of the prologue leaves before the
     // first one is waited for (see k_probe_slab).
     const TileRec rec = u_rec[t];
     const TileDesc d0 = WIDE ? sa->tw64[t].d : u_tw[t].d;
     const TileStat tst = u_stat[t];
     const uint32_t chunk_on = sa->chunk_on; const int32_t ablate = a->f.p.ablate;
-    const uint32_t n_tiles = sa->n_tiles;
     if constexpr (EXACT)      // (of the statistics only the N operations, of the record no slab)
         asm volatile("" :: "s"(tst.n_ops_n), "s"(ablate), "s"(n_tiles), "s"(rec.r0), "s"(rec.n_act), "s"(rec.tid0), "s"(rec.lo),
                            "s"(d0.j_lo), "s"(d0.b_off), "s"(d0.nb), "s"(d0.b0), "s"(d0.nbk), "s"(d0.st_r0), "s"(d0.st_nk), "s"(d0.en_r0), "s"(d0.en_nk), "s"(d0.flags), "s"(d0.n_win));
     else
     asm volatile("" :: "s"(tst.n_ops_n), "s"(tst.min_n), "s"(tst.max_d), "s"(tst.min_seg), "s"(chunk_on), "s"(ablate), "s"(n_tiles), "s"(rec.r0), "s"(rec.n_act), "s"(rec.sbase), "s"(rec.rows), "s"(rec.tid0), "s"(rec.lo),
                        "s"(d0.j_lo), "s"(d0.b_off), "s"(d0.nb), "s"(d0.b0), "s"(d0.nbk), "s"(d0.st_r0), "s"(d0.st_nk), "s"(d0.en_r0), "s"(d0.en_nk), "s"(d0.flags), "s"(d0.n_win));
+    if (behind) { slot_unused(); return; }                       // (a workgroup behind the last tile: see the top of the kernel)
     // the EXACT instance's tiles carry k_describe_scan's mark (every other tile is on the general instance's list)
-    if (EXACT && (d0.flags & TD_XDIRECT) == 0u) return;
+    if (EXACT && (d0.flags & TD_XDIRECT) == 0u) { slot_unused(); return; }
     const uint32_t r0 = rec.r0, n_act = rec.n_act;
     const int32_t tid0 = rec.tid0, pos0 = rec.lo - 1;
     const int32_t tile_lo = rec.lo;                              // the base of the tile's row words: its first read's first base
@@ -630,9 +652,9 @@ void k_tile(SlabArgs kernarg_block, const TileRec *__restrict__ u_rec, const Til
     const bool counted = EXACT || (tile_exact(tst, a->f.p.min_exon, a->f.p.min_intron, a->f.p.max_delet) && !(ablate & 256));
     if constexpr (!EXACT) {   // (a wide tile that the WIDE instance takes whole, behind this launch: nothing of it happens in the plain one -- and the other way round)
         const bool direct = tile_wide_direct(sa->wide_direct_on, d0.flags, chunk_on, tst, n_act, a->f.p.min_exon, a->f.p.min_intron, a->f.p.max_delet, ablate);
-        if (WIDE ? !direct : direct) return;
+        if (WIDE ? !direct : direct) { slot_unused(); return; }
         // (... or k_tile_chunk, l2r_tchunk.hip.h: an exact tile of the chunked kernel)
-        if (!WIDE && (d0.flags & TD_CDIRECT) != 0u) return;
+        if (!WIDE && (d0.flags & TD_CDIRECT) != 0u) { slot_unused(); return; }
     }
     TileDesc d = d0;
     if (pre_slab) d.flags = 0u;
@@ -645,11 +667,14 @@ void k_tile(SlabArgs kernarg_block, const TileRec *__restrict__ u_rec, const Til
     LbLevel lv{nullptr, 0u, 0u};
     unsigned long long ev = 0ull;
     if (wv < 3 && !pre_slab) { lv = lb_level(sa, t, wv); if ((uint32_t)lane < lv.cnt) ev = lv.p[lane]; }
-    // the dictionary slices and the window record: they travel while the CIGAR heads are asked for
+    // the dictionary slices and the window record: ONE batch of unconditional loads behind the look-back words (load_dict_slices,
+    // load_tw_vec: clamped indices instead of conditions, so nothing is waited for between them); they travel beside the slot record
+    // and while the CIGAR heads are asked for
     const DictRegs dv = load_dict_slices(a, d);
-    int4 twv = make_int4(0, 0, 0, 0);
-    if (WIDE) { if ((int)threadIdx.x < WIDE_TW_VECS) twv = reinterpret_cast<const int4 *>(sa->tw64 + t)[threadIdx.x]; }
-    else if ((int)threadIdx.x < SLAB_TW_VECS && tw_vec_used((int)threadIdx.x, (d.flags & TD_FAST) ? d.n_win : 0u)) twv = reinterpret_cast<const int4 *>(u_tw + t)[threadIdx.x];
+    bool tw_used = (int)threadIdx.x < WIDE_TW_VECS;
+    int4 twv;
+    if (WIDE) twv = reinterpret_cast<const int4 *>(sa->tw64 + t)[min((int)threadIdx.x, WIDE_TW_VECS - 1)];
+    else twv = load_tw_vec(u_tw + t, (d.flags & TD_FAST) ? d.n_win : 0u, tw_used);
     // ---- the thread's slot record (asked for at the top of the kernel) and the head of its read's CIGAR: six 16-byte vectors, all in
     //      flight at once; words behind the last op become "I, length 0"
     const uint32_t c_lo = srec.x, xs = srec.z;
@@ -677,7 +702,7 @@ void k_tile(SlabArgs kernarg_block, const TileRec *__restrict__ u_rec, const Til
         first_share = wave_sum(in ? (uint32_t)ev : 0u);
     }
     // ---- window and dictionary slices into LDS, re-based to the tile's window (the CIGAR words travel)
-    if (!pre_slab && (int)threadIdx.x < (WIDE ? WIDE_TW_VECS : SLAB_TW_VECS)) reinterpret_cast<int4 *>(&s_tw)[threadIdx.x] = twv;
+    if (!pre_slab && (int)threadIdx.x < (WIDE ? WIDE_TW_VECS : SLAB_TW_VECS)) reinterpret_cast<int4 *>(&s_tw)[threadIdx.x] = tw_vec_lds(twv, tw_used);
     int my_wide = 0;
     if constexpr (WIDE) wide_stage_dict(d, dv, reinterpret_cast<const int *>(sa->tw64[t].win), s_ent0, s_ent1, s_dir0, s_dir1, s_rdir);
     else if (EXACT) (void)slab_stage_dict(d, dv, reinterpret_cast<const int *>(u_tw[t].win), SlabLds{nullptr, s_ent0, s_ent1, s_dir0, s_dir1, s_rdir});      // (no key in several entries anywhere: tile_exact_direct)

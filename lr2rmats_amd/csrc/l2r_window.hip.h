@@ -181,22 +181,52 @@ __device__ __forceinline__ void st32(T *base, uint32_t idx, T v)
 }
 
 // a tile's dictionary entries / bucket directory words as loaded, one START and one END entry per thread
+//
+// Ten loads per thread, ALL of them unconditional: straight-line code that the compiler issues back to back and counts exactly.  A
+// thread behind the end of a slice asks for the slice's last entry once more (entry 0 of the dictionary for an empty slice or a tile
+// that stages nothing), a thread behind the last staged bucket for that bucket's word (word 0 likewise): an address that exists,
+// on a line the wave fetches anyway.  What such a thread gets is never used -- the staging (slab_stage_dict, wide_stage_dict,
+// k_probe_slab_wide) looks at xa .. xd under `thread < st_nk` / `thread < en_nk` and at dd under `i <= nbk` only.
+// (The earlier form -- each load under its own condition, zero otherwise -- had the compiler merge every loaded value with a zero at the
+//  end of its branch: a wait for the load right there, i.e. one round trip per slice, and `s_waitcnt vmcnt(0)` behind the directory
+//  words' branches.  In bounds: every dictionary and directory is allocated with one element at least; [r0, r0 + nk) and
+//  [b0, b0 + nbk] are the ranges the conditional form read.)
+// CLAMPED = false: that earlier form, kept for k_probe_slab, whose instances over a tile list spill two registers more with this one.
 struct DictRegs { int4 xa, xb, xc, xd; uint32_t dd[3][2]; };
+template <bool CLAMPED = true>
 __device__ __forceinline__ DictRegs load_dict_slices(PipeArgsK a, const TileDesc &d)
 {
     DictRegs v;
-    v.xa = v.xb = v.xc = v.xd = make_int4(0, 0, 0, 0);
     const bool fast = (d.flags & (TD_FAST | TD_WIDE)) != 0;
-    if (fast && threadIdx.x < d.st_nk) { const int4 *q = reinterpret_cast<const int4 *>(a->f.st.ent + d.st_r0 + threadIdx.x); v.xa = q[0]; v.xb = q[1]; }
-    if (fast && threadIdx.x < d.en_nk) { const int4 *q = reinterpret_cast<const int4 *>(a->f.en.ent + d.en_r0 + threadIdx.x); v.xc = q[0]; v.xd = q[1]; }
+    if constexpr (!CLAMPED) {
+        v.xa = v.xb = v.xc = v.xd = make_int4(0, 0, 0, 0);
+        if (fast && threadIdx.x < d.st_nk) { const int4 *q = reinterpret_cast<const int4 *>(a->f.st.ent + d.st_r0 + threadIdx.x); v.xa = q[0]; v.xb = q[1]; }
+        if (fast && threadIdx.x < d.en_nk) { const int4 *q = reinterpret_cast<const int4 *>(a->f.en.ent + d.en_r0 + threadIdx.x); v.xc = q[0]; v.xd = q[1]; }
+#pragma unroll
+        for (int q = 0; q < 2; ++q) {
+            const int i = (int)threadIdx.x + q * TILE_THREADS;
+            v.dd[0][q] = v.dd[1][q] = v.dd[2][q] = 0u;
+            if (fast && d.nbk > 0 && i <= d.nbk) {
+                const uint32_t b = (uint32_t)(d.b0 + i);
+                v.dd[0][q] = ld32(a->f.st.dir, b); v.dd[1][q] = ld32(a->f.en.dir, b); v.dd[2][q] = ld32(a->f.st.rdir, b);
+            }
+        }
+        return v;
+    }
+    // (wave-uniform: first entry and last index of each slice, {0, 0} for a slice without entries)
+    const bool any_st = fast && d.st_nk > 0u, any_en = fast && d.en_nk > 0u;
+    const uint32_t st_first = any_st ? d.st_r0 : 0u, st_last = any_st ? d.st_nk - 1u : 0u;
+    const uint32_t en_first = any_en ? d.en_r0 : 0u, en_last = any_en ? d.en_nk - 1u : 0u;
+    const int4 *const qs = reinterpret_cast<const int4 *>(a->f.st.ent + st_first + min(threadIdx.x, st_last));
+    const int4 *const qe = reinterpret_cast<const int4 *>(a->f.en.ent + en_first + min(threadIdx.x, en_last));
+    v.xa = qs[0]; v.xb = qs[1];
+    v.xc = qe[0]; v.xd = qe[1];
+    const bool any_bk = fast && d.nbk > 0;
+    const uint32_t bk_first = any_bk ? (uint32_t)d.b0 : 0u, bk_last = any_bk ? (uint32_t)d.nbk : 0u;
 #pragma unroll
     for (int q = 0; q < 2; ++q) {
-        const int i = (int)threadIdx.x + q * TILE_THREADS;
-        v.dd[0][q] = v.dd[1][q] = v.dd[2][q] = 0u;
-        if (fast && d.nbk > 0 && i <= d.nbk) {
-            const uint32_t b = (uint32_t)(d.b0 + i);
-            v.dd[0][q] = ld32(a->f.st.dir, b); v.dd[1][q] = ld32(a->f.en.dir, b); v.dd[2][q] = ld32(a->f.st.rdir, b);
-        }
+        const uint32_t b = bk_first + min(threadIdx.x + (uint32_t)(q * TILE_THREADS), bk_last);
+        v.dd[0][q] = ld32(a->f.st.dir, b); v.dd[1][q] = ld32(a->f.en.dir, b); v.dd[2][q] = ld32(a->f.st.rdir, b);
     }
     return v;
 }
