@@ -34,7 +34,7 @@ constexpr int CHUNK_SCAN_TRIPS = 4096;                              // 64-transc
 
 struct ChunkVisit { m64_t vpre, lmask, rmask, k1mask; bool redo, stopped; };
 
-// visit_window64 on one chunk; `stopped`: a member of the chunk lies behind the read (src/update_gtf.c:799-800 ends the sweep)
+// visit_window<LEVEL, m64_t> on one chunk; `stopped`: a member of the chunk lies behind the read (src/update_gtf.c:799-800 ends the sweep)
 template <int LEVEL>
 __device__ __forceinline__ ChunkVisit visit_chunk64(const ChunkLds &L, int w_n, bool work, uint32_t n, const ReadEnds &re, const m64_t *tilemask)
 {
@@ -80,7 +80,7 @@ __device__ __forceinline__ void probe_parts64(const WEnt *ent, uint32_t lo, uint
     pm = 0ull; sm = 0ull;
     for (uint32_t r = lo; r < hi; ++r) {
         const WEnt q = ent[r];
-        if (q.k1 == k1) { sm |= q.sm; if (q.k2 == k2) pm |= q.pm; }
+        if (q.x == k1) { sm |= q.w; if (q.y == k2) pm |= q.z; }
     }
 }
 
@@ -93,31 +93,31 @@ __device__ __forceinline__ void probe_near_parts64(const WEnt *ent, uint32_t lo,
     int first = INT32_MIN; bool several = false;
     for (uint32_t r = lo; r < hi; ++r) {
         const WEnt q = ent[r];
-        if (__builtin_abs(q.k1 - k1) > dis) continue;
-        if (q.k1 >= rs && q.k1 <= re) {
-            if (first == INT32_MIN) first = q.k1; else several = several || q.k1 != first;
-            sm |= q.sm;
+        if (__builtin_abs(q.x - k1) > dis) continue;
+        if (q.x >= rs && q.x <= re) {
+            if (first == INT32_MIN) first = q.x; else several = several || q.x != first;
+            sm |= q.w;
         }
-        if (__builtin_abs(q.k2 - k2) <= dis) pm |= q.pm;
+        if (__builtin_abs(q.y - k2) <= dis) pm |= q.z;
     }
     if (several)                                             // (rare: two annotation sites within 2 dis + 1 bases -- which members have both?)
         for (uint32_t r = lo; r < hi; ++r) {
             const WEnt q = ent[r];
-            if (__builtin_abs(q.k1 - k1) > dis || q.k1 < rs || q.k1 > re) continue;
+            if (__builtin_abs(q.x - k1) > dis || q.x < rs || q.x > re) continue;
             for (uint32_t u = r + 1u; u < hi; ++u) {
                 const WEnt w = ent[u];
-                if (__builtin_abs(w.k1 - k1) > dis || w.k1 < rs || w.k1 > re || w.k1 == q.k1) continue;
-                amb |= q.sm & w.sm;
+                if (__builtin_abs(w.x - k1) > dis || w.x < rs || w.x > re || w.x == q.x) continue;
+                amb |= q.w & w.w;
             }
         }
 }
 
 // map_exons_slab64 with the read's exons at their staged positions in LDS (A: start relative to the tile's base, L: length); the
 // chunk's work word goes into the upper bits of A
-__device__ __forceinline__ SiteMasks64 map_exons_lds64(const ChunkLds &L, const TileDesc &d, bool mapping, uint32_t *Ap, const uint16_t *Lp,
+__device__ __forceinline__ SiteMasks<m64_t> map_exons_lds64(const ChunkLds &L, const TileDesc &d, bool mapping, uint32_t *Ap, const uint16_t *Lp,
                                                        int32_t lo, uint32_t n, m64_t vpre, int dis = 0, int rs = 0, int re = 0)
 {
-    SiteMasks64 m{~0ull, 0ull, 0ull, 0ull, 0ull};
+    SiteMasks<m64_t> m{~0ull, 0ull, 0ull, 0ull, 0ull};
     const uint32_t none = (uint32_t)d.nbk + 1u;
     const int k_max = wave_max(mapping ? (int)n : 0);
     int s = 0, e = 0;
@@ -145,8 +145,8 @@ __device__ __forceinline__ SiteMasks64 map_exons_lds64(const ChunkLds &L, const 
             probe_parts64(L.ent1, le, he, e, s2, jm, dm);
         }
         const m64_t amj = junc ? am : 0ull;
-        uint32_t word = first_member64(xm & vpre);
-        word |= first_member64(jm & vpre) << 6;
+        uint32_t word = first_member(xm & vpre);
+        word |= first_member(jm & vpre) << 6;
         word |= ((dm & vpre) ? 1u : 0u) << 12;
         word |= ((amj & vpre) ? 1u : 0u) << 13;
         m.kand &= junc ? (am & dm) : ~0ull;            // Q1: the acceptor probed with exon k is ITS OWN start, k < n-1
@@ -375,16 +375,16 @@ void k_probe_slab_chunked(SlabArgs kernarg_block, const uint32_t *__restrict__ u
                     const bool has_st = i < d.st_nk && relevant(xa.z), has_en = i < d.en_nk && relevant(xc.z);
                     if (!has_st && !has_en) continue;
                     WEnt e0, e1;
-                    e0.k1 = xa.x; e0.k2 = xa.y; e1.k1 = xc.x; e1.k2 = xc.y;
+                    e0.x = xa.x; e0.y = xa.y; e1.x = xc.x; e1.y = xc.y;
                     const m64_t pm0 = ((m64_t)(uint32_t)xb.y << 32) | (uint32_t)xb.x, sm0 = ((m64_t)(uint32_t)xb.w << 32) | (uint32_t)xb.z;
                     const m64_t pm1 = ((m64_t)(uint32_t)xd.y << 32) | (uint32_t)xd.x, sm1 = ((m64_t)(uint32_t)xd.w << 32) | (uint32_t)xd.z;
                     if (dc.flags & TD_CONTIG) {
-                        e0.pm = rebase64(pm0, xa.z - dc.j_lo); e0.sm = rebase64(sm0, xa.z - dc.j_lo);
-                        e1.pm = rebase64(pm1, xc.z - dc.j_lo); e1.sm = rebase64(sm1, xc.z - dc.j_lo);
+                        e0.z = rebase64(pm0, xa.z - dc.j_lo); e0.w = rebase64(sm0, xa.z - dc.j_lo);
+                        e1.z = rebase64(pm1, xc.z - dc.j_lo); e1.w = rebase64(sm1, xc.z - dc.j_lo);
                     } else {
                         m64_t mm[4] = {pm0, sm0, pm1, sm1};
                         rebase_gaps64(s_tw.win, w_n, mm, xa.z, xc.z);
-                        e0.pm = mm[0]; e0.sm = mm[1]; e1.pm = mm[2]; e1.sm = mm[3];
+                        e0.z = mm[0]; e0.w = mm[1]; e1.z = mm[2]; e1.w = mm[3];
                     }
                     // (places are handed out from the end of the group downwards: afterwards X[g] is the group's FIRST entry)
                     if (has_st) s_ent0[atomicSub(&X0[group_of(xa.x)], 1u) - 1u] = e0;
@@ -408,39 +408,26 @@ void k_probe_slab_chunked(SlabArgs kernarg_block, const uint32_t *__restrict__ u
             const ChunkVisit vm = visit_chunk64<LEVEL>(L, (abl & 8192) ? 0 : w_n, work, n, re, s_tw.mask);
             redo = redo || vm.redo;
             const bool mapping = work && !vm.redo && n > 1 && !(abl & 4096);
-            const SiteMasks64 sm = map_exons_lds64(L, dc, mapping, Ap, Lp, tile_lo, n, vm.vpre, dis, re.s0, re.el);
+            const SiteMasks<m64_t> sm = map_exons_lds64(L, dc, mapping, Ap, Lp, tile_lo, n, vm.vpre, dis, re.s0, re.el);
             // (-d > 0: a visited member with two sites within the tolerance of one read site -- its pair count is the generic kernel's)
             const bool amb = dis > 0 && mapping && (sm.amb & vm.vpre) != 0ull;
             redo = redo || amb;
             if (work && !vm.redo && !amb) {
-                int jstar = -1;
-                if (n > 1) {
-                    m64_t c = sm.kand & vm.vpre;
-                    while (c) {
-                        const int j = __ffsll((long long)c) - 1;
-                        c &= c - 1ull;
-                        const int4 hk = L.hk[j];
-                        if (hk.x <= re.e0 && re.sl <= hk.y) { jstar = j; break; }
-                    }
-                } else if (vm.k1mask) jstar = __ffsll((long long)vm.k1mask) - 1;
+                const Known<m64_t> kn = pick_known(L.hk, n, re, vm.vpre, vm.k1mask, sm.kand, sm.kor);
+                const int jstar = kn.jstar, jref = kn.jref;
                 const bool known_c = jstar >= 0;
-                const m64_t upto = jstar >= 63 ? ~0ull : ((2ull << (known_c ? jstar : 0)) - 1ull);
-                const m64_t V = known_c ? (vm.vpre & upto) : vm.vpre;
-                const m64_t ks = (n > 1) ? (sm.kor & V) : 0ull;
-                ksite = ksite || (ks & ~(known_c ? (1ull << jstar) : 0ull)) != 0ull;
-                int jref = -1;
-                if (n > 1) { if (ks) jref = 63 - __clzll((long long)ks); }
-                else jref = jstar;
+                const m64_t V = kn.V;
+                ksite = ksite || kn.ksite;
                 if (jref >= 0) { ref = L.win[jref]; out_rev = ((L.hk[jref].w >> 8) & 1) != 0; }     // :825-831 (a later chunk's member is a later transcript)
                 if (LEVEL >= 1 && LEVEL <= 4) { lfull = lfull || (vm.lmask & V) != 0ull; rfull = rfull || (vm.rmask & V) != 0ull; }
                 if (LEVEL == 3 || LEVEL == 4) {
                     if (lnoth) {
                         if (sm.dm_first & V) lnoth = false;
-                        else if (V) lnoth = (overlapping_exon_members64(L.rdir, L.dir0, L.ent0, dc.b_off, dc.nb, re.s0, re.e0) & V) == 0ull;
+                        else if (V) lnoth = (overlapping_exon_members<m64_t>(L.rdir, L.dir0, L.ent0, dc.b_off, dc.nb, re.s0, re.e0) & V) == 0ull;
                     }
                     if (LEVEL == 3 && rnoth) {
                         if (sm.am_last & V) rnoth = false;
-                        else if (V) rnoth = (overlapping_exon_members64(L.rdir, L.dir0, L.ent0, dc.b_off, dc.nb, re.sl, re.el) & V) == 0ull;
+                        else if (V) rnoth = (overlapping_exon_members<m64_t>(L.rdir, L.dir0, L.ent0, dc.b_off, dc.nb, re.sl, re.el) & V) == 0ull;
                     }
                 }
                 if (n > 1) {
@@ -470,25 +457,13 @@ void k_probe_slab_chunked(SlabArgs kernarg_block, const uint32_t *__restrict__ u
                     Ap[k] = (Ap[k] & SLAB_REL_MASK) | (f << SLAB_REL_BITS);
                 }
             } else Ap[0] = (Ap[0] & SLAB_REL_MASK) | ((uint32_t)F_EXON << SLAB_REL_BITS);
-            if (known) info |= I_KNOWN;
-            if (ksite) info |= I_KSITE;
-            if (full_decision(LEVEL, lfull, lnoth, rfull, rnoth)) info |= I_FULL;
-            if (out_rev) info |= I_REV;
-            if (fast_args()->p.n_sj == 0 && (info & (I_FULL | I_KNOWN | I_KSITE)) == (I_FULL | I_KSITE)) info |= I_ACCEPT;
+            info = verdict_info(LEVEL, n << 8, known, ksite, lfull, lnoth, rfull, rnoth, out_rev);
         } else {
             ref = -1;
             if (work0) for (uint32_t k = 0; k < n; ++k) Ap[k] &= SLAB_REL_MASK;             // (flags 0: the generic kernel writes them)
         }
         redo = redo && active;
-        {
-            const unsigned long long m = __ballot(redo);
-            if (m) {
-                uint32_t pos_r = 0;
-                if (lane == 0) pos_r = atomicAdd(a->f.redo_count, (uint32_t)__popcll(m));
-                pos_r = __shfl(pos_r, 0, WAVE);
-                if (redo) a->f.redo[pos_r + (uint32_t)__popcll(m & ((1ull << lane) - 1ull))] = r;
-            }
-        }
+        redo_append(&a->f, redo, r);
         if (active) { a->f.info[r] = info; a->f.ref_tx[r] = ref; a->f.ex_off[r] = out.dst; }
         __syncthreads();
         slab_write_out(SlabOut{out.start, out.end, out.flag, xbase}, s_A, s_L, tile_lo, s_lim);

@@ -1239,63 +1239,12 @@ __device__ __forceinline__ void probe_rest(const v4i_t *ent, uint32_t lo, uint32
     }
 }
 
-// -d > 0 (src/update_gtf.c:717-779 with dis > 0): a read site matches EVERY annotation site within `dis` of it, and identical_site_n
-// counts the matching (annotation site, read site) PAIRS.  One probe of a staged slice with a tolerance: entries [lo, hi) are the
-// buckets of k1 - dis .. k1 + dis (one or two of them: 2 dis + 1 <= 129 bases with dis <= DIS_MASK_MAX; the range arithmetic of
-// near_range would take more -- lo = the first bucket's first entry, hi = the last bucket's end), sorted by (key 1, key 2).  The staged
-// directories are bytes: a slice holds at most SLAB_KEY_CAP / KEY_CAP (< 256) entries whatever the tolerance adds to its span.
-//   sm |= site members of every entry whose first key lies within dis of k1 AND inside the read's span [rs, re] -- an annotation site
-//         counts only inside the overlap span (:732,742); inside the transcript's own span it always is (TX_COMPACT);
-//   pm |= pair members of every entry with both keys within dis (the exon / junction flags know no overlap span, :753-768);
-//   amb |= members that have TWO different sites within dis of this one read site: for them the pair count is not the number of
-//         matched read sites, the masks cannot say whether the read is known -- such a read goes to the generic kernel (it takes a
-//         transcript with two donors or two acceptors less than 2 dis + 1 bases apart).
-static_assert(2 * DIS_MASK_MAX + 1 <= (1 << SITE_SHIFT) && KEY_CAP < 256, "a tolerance window spans two buckets at most; byte directories");
-__device__ __forceinline__ void probe_near(const v4i_t *ent, uint32_t lo, uint32_t hi, int32_t k1, int32_t k2, int dis, int rs, int re,
-                                           uint32_t &pm, uint32_t &sm, uint32_t &amb)
-{
-    pm = 0u; sm = 0u;
-    int last = INT32_MIN;
-    const uint32_t span = 2u * (uint32_t)dis, b1 = (uint32_t)k1 - (uint32_t)dis, b2 = (uint32_t)k2 - (uint32_t)dis;
-    // (no branch per entry: selects; an entry outside the tolerance adds nothing, sorted or not)
-    auto one = [&](const v4i_t q, bool on) {
-        const bool in = on && (uint32_t)q.x - b1 <= span;
-        const bool sp = in && q.x >= rs && q.x <= re;
-        const uint32_t w = sp ? (uint32_t)q.w : 0u;
-        amb |= q.x != last ? (sm & w) : 0u;
-        last = sp ? q.x : last;
-        sm |= w;
-        pm |= (in && (uint32_t)q.y - b2 <= span) ? (uint32_t)q.z : 0u;
-    };
-    // the first NEAR_FIRST entries without a loop (most tolerance windows hold no more), the others only where some lane has them
-    const v4i_t q0 = lds_entry(ent, lo), q1 = lds_entry(ent, lo + 1u);
-    one(q0, lo < hi); one(q1, lo + 1u < hi);
-    if (__any(hi > lo + 2u))
-        for (uint32_t r = lo + 2u; r < hi; ++r) one(lds_entry(ent, r), true);
-}
 // the staged entries of the buckets of x - dis .. x + dis: [lo, hi)  (none: the empty bucket behind the staged ones)
 __device__ __forceinline__ void near_range(const uint8_t *dir, int b_off, uint32_t none, bool live, int x, int dis, uint32_t &lo, uint32_t &hi)
 {
     const uint32_t i0 = live ? min((uint32_t)((max(x - dis, 0) >> SITE_SHIFT) + b_off), none) : none;
     const uint32_t i1 = live ? min((uint32_t)(((x + dis) >> SITE_SHIFT) + b_off), none) : none;
     lo = dir[i0]; hi = dir[i1 + 1u];
-}
-
-// Transcripts (tile frame) that have an exon overlapping [s, e]: union of the exon masks of the START entries
-// from the first one that reaches into the bucket of s up to the last one that starts in the bucket of e.
-__device__ __forceinline__ uint32_t overlapping_exon_members(const uint8_t *rdir, const uint8_t *dir, const v4i_t *ent,
-                                                             int b_off, int nb, int s, int e)
-{
-    const int bs = s >> SITE_SHIFT;
-    if (bs >= nb) return 0u;                                 // beyond the last annotated site of the chromosome
-    const int be = min(e >> SITE_SHIFT, nb - 1);
-    uint32_t m = 0u;
-    const uint32_t i1 = dir[be + b_off + 1];
-    for (uint32_t i = rdir[bs + b_off]; i < i1; ++i) {
-        const v4i_t q = ent[i];
-        if (q.x <= e && q.y >= s) m |= (uint32_t)q.z;
-    }
-    return m;
 }
 
 // The kernel is PERSISTENT and software pipelined: a workgroup walks over tiles t, t + grid, ... and holds the
@@ -1447,14 +1396,10 @@ __device__ __forceinline__ void settle_vectors(const TileVectors &v)
                  "v"(v.xc.x), "v"(v.xc.y), "v"(v.xc.z), "v"(v.xc.w), "v"(v.xd.x), "v"(v.xd.y), "v"(v.xd.z), "v"(v.xd.w));
 }
 
-// ---- the three classification phases of a tile (all lanes of a wave call them together) -------------------------
+}  // namespace l2r
+#include "l2r_masks.hip.h"      // the one-window classification functions, one body for 32- and 64-bit masks
+namespace l2r {
 
-struct TileLds {                 // the tile's LDS image (layout in k_classify_fast)
-    int *S, *E; uint16_t *W;
-    const v4i_t *ent0, *ent1; const uint8_t *dir0, *dir1, *rdir;
-    const int4 *hk, *hx;
-    const int *win;              // window member -> annotation index
-};
 // m = m << 1 | predicate, as ONE compare and ONE add-with-carry (m + m + carry): the member passes collect their per-member predicates
 // highest member first -- the select-and-or form costs three vector instructions per predicate on 32-bit masks, five on 64-bit ones.
 __device__ __forceinline__ void shift_in_le(uint32_t &m, int a, int b)          // m = m << 1 | (a <= b)
@@ -1471,85 +1416,11 @@ __device__ __forceinline__ void shift_in_le2(uint32_t &m, int a, int b, int c, i
     asm volatile("v_cmp_le_i32 vcc, %2, %3\n\tv_cmp_le_i32 %1, %4, %5\n\ts_and_b64 vcc, vcc, %1\n\tv_addc_co_u32 %0, vcc, %0, %0, vcc"
                  : "+v"(m), "=&s"(t) : "v"(a), "v"(b), "v"(c), "v"(d) : "vcc", "scc");
 }
-struct VisitMasks { uint32_t vpre, lmask, rmask, k1mask; bool redo; };
-struct SiteMasks { uint32_t kand, kor, dm_first, am_last; uint32_t amb; };      // amb (-d > 0 only): members with TWO sites within the tolerance of one read site (probe_near)
-
-// V' = window transcripts j >= j0 up to the first one the read lies before (src/update_gtf.c:799-800), minus the ones
-// that lie before the read (:801); terminal-exon masks of check_full (:629-681); single-exon known candidates (:806-811).
-// One pass over the window with a wave-uniform member index (header words broadcast from LDS) that only BUILDS per-read
-// bit masks -- "the read lies before member j", "member j lies before the read", "first / last exons overlap" -- with no
-// per-member branch; the sweep's stop (:799) and the cursor (:801-802) are applied to the masks afterwards:
-//     V' = ~before & (members below the first "read lies before") & (members from the cursor value on).
-// tilemask[0] / [1]: the tile's members with one exon / without TX_COMPACT (set where the headers are staged).
-template <int LEVEL>
-__device__ __forceinline__ VisitMasks visit_window(const TileLds &L, const TileDesc &d, int w_n, bool work, uint32_t n, int j0,
-                                                   const ReadEnds &re, const uint32_t *tilemask)
-{
-    VisitMasks m{0u, 0u, 0u, 0u, false};
-    // (a wave without a read to classify -- the upper waves of a tile of few reads -- has nothing to visit: the pass below would
-    //  still cost it a dozen instructions per member)
-    if (!__any(work)) return m;
-    uint32_t m_aft = 0u, m_bef = 0u;
-    for (int j = 0; j < w_n; ++j) {
-        const int4 hk = L.hk[j];
-        const uint32_t bit = 1u << j;
-        m_aft |= re.el <= hk.x ? bit : 0u;                                   // comp_trans <= (Q5): the read lies before the member
-        m_bef |= hk.y <= re.s0 ? bit : 0u;                                   // the member lies before the read
-        if (LEVEL >= 1 && LEVEL <= 4) {
-            const int4 hx = L.hx[j];
-            if (LEVEL == 1) {
-                m.lmask |= re.e0 == hx.y ? bit : 0u;
-                m.rmask |= re.sl == hx.z ? bit : 0u;
-            } else {
-                m.lmask |= closed_overlap(re.s0, re.e0, hx.x, hx.y) ? bit : 0u;
-                if (LEVEL != 4) m.rmask |= closed_overlap(re.sl, re.el, hx.z, hx.w) ? bit : 0u;
-            }
-        }
-    }
-    int jrel0 = j0 - d.j_lo;                       // first member the read's sweep reaches
-    if (!(d.flags & TD_CONTIG)) {
-        jrel0 = 0;
-        for (int j = 0; j < w_n; ++j) jrel0 += L.win[j] < j0 ? 1 : 0;
-    }
-    // members the sweep reaches: index >= jrel0 (which may be negative or beyond the window)
-    const uint32_t reach = jrel0 <= 0 ? 0xffffffffu : (jrel0 >= 32 ? 0u : ~((1u << jrel0) - 1u));
-    const uint32_t stop = m_aft & reach;                                     // the sweep ends at the lowest of these (:799-800)
-    const uint32_t below = (stop & (0u - stop)) - 1u;                        // all ones when there is none
-    m.vpre = work ? (~m_bef & below & reach & (w_n >= 32 ? 0xffffffffu : ((1u << w_n) - 1u))) : 0u;
-    m.lmask &= m.vpre; m.rmask &= m.vpre;
-    // single-exon members only count against single-exon reads (:806-811); a member without TX_COMPACT needs the literal loops
-    const uint32_t single = tilemask[0];
-    if (n == 1) {
-        uint32_t c = m.vpre & single;
-        while (c) {
-            const int j = __ffs((int)c) - 1;
-            c &= c - 1u;
-            const int4 hx = L.hx[j];
-            if (overlap_frac(re.s0, re.e0, hx.x, hx.y) >= fast_args()->p.frac) m.k1mask |= 1u << j;
-        }
-    } else if (m.vpre & tilemask[1] & ~single) m.redo = true;
-    return m;
-}
-
-// index of the lowest set bit, 63 when there is none
-__device__ __forceinline__ uint32_t first_member(uint32_t x)
-{
-    return (uint32_t)(__ffs((int)x) - 1) & 63u;                         // v_ffbl_b32 (-1 for 0), masked to 63
-}
-
-// x != 0 as 0 / 1 in one VALU instruction (the compiler turns min(x, 1) into compare + select + a literal move)
-__device__ __forceinline__ uint32_t nonzero(uint32_t x)
-{
-    uint32_t r;
-    asm("v_min_u32 %0, 1, %1" : "=v"(r) : "v"(x));
-    return r;
-}
-
 // -d > 0: the loop of map_exons (below) with every probe looking at the entries within the tolerance of its coordinate (probe_near); [rs, re] = the
 // read's span.  (A loop of its own: a wave-uniform branch inside the exact loop cost k_classify_fast 5 % on config 5's shard.)
-__device__ __forceinline__ SiteMasks map_exons_near(const TileLds &L, const TileDesc &d, bool mapping, uint32_t local, uint32_t n, uint32_t vpre, int dis, int rs, int re)
+__device__ __forceinline__ SiteMasks<uint32_t> map_exons_near(const TileLds<uint32_t> &L, const TileDesc &d, bool mapping, uint32_t local, uint32_t n, uint32_t vpre, int dis, int rs, int re)
 {
-    SiteMasks m{0xffffffffu, 0u, 0u, 0u, 0u};
+    SiteMasks<uint32_t> m{0xffffffffu, 0u, 0u, 0u, 0u};
     const int *S = L.S + local, *E = L.E + local;
     uint16_t *W = L.W + local;
     int s = 0, e = 0;
@@ -1582,9 +1453,9 @@ __device__ __forceinline__ SiteMasks map_exons_near(const TileLds &L, const Tile
 // One START and one END probe per exon; the wave runs as many rounds as its longest read has exons.  Per round
 // {next exon, both bucket ranges} are read together, then the first entries of both buckets.  Leaves per exon in W:
 // first member of V' with the exon / the junction (6 bits each, 63: none), "donor / acceptor is in V'" (bits 12, 13).
-__device__ __forceinline__ SiteMasks map_exons(const TileLds &L, const TileDesc &d, bool mapping, uint32_t local, uint32_t n, uint32_t vpre)
+__device__ __forceinline__ SiteMasks<uint32_t> map_exons(const TileLds<uint32_t> &L, const TileDesc &d, bool mapping, uint32_t local, uint32_t n, uint32_t vpre)
 {
-    SiteMasks m{0xffffffffu, 0u, 0u, 0u, 0u};
+    SiteMasks<uint32_t> m{0xffffffffu, 0u, 0u, 0u, 0u};
     const int *S = L.S + local, *E = L.E + local;
     uint16_t *W = L.W + local;
     int s = 0, e = 0;
@@ -1623,73 +1494,6 @@ __device__ __forceinline__ SiteMasks map_exons(const TileLds &L, const TileDesc 
         s = s2; e = e2;
     }
     return m;
-}
-
-// Known / known site / reference transcript / full-length / flag bytes of one read from its masks.
-// getw(k) = the work word map_exons left for exon k, emit(k, flag byte) receives the exons' flags (the classic kernel keeps both in its
-// 16-bit W array, the slab kernel in the upper bits of its staged positions).
-template <int LEVEL, typename GetW, typename Emit>
-__device__ __forceinline__ Verdict decide(const TileLds &L, const TileDesc &d, uint32_t n, const ReadEnds &re,
-                                          const VisitMasks &vm, const SiteMasks &sm, bool rev_in, GetW getw, Emit emit)
-{
-    // ---- first known transcript in visiting order
-    int jstar = -1;
-    if (n > 1) {
-        // every probed site is in the transcript; known also needs every read site inside the overlap span:
-        // donors e_0..e_{n-2} and acceptors s_1..s_{n-1} increase, so e_0 >= a.start and s_{n-1} <= a.end suffice
-        uint32_t c = sm.kand & vm.vpre;
-        while (c) {
-            const int j = __ffs((int)c) - 1;
-            c &= c - 1u;
-            const int4 hk = L.hk[j];
-            if (hk.x <= re.e0 && re.sl <= hk.y) { jstar = j; break; }
-        }
-    } else if (vm.k1mask) jstar = __ffs((int)vm.k1mask) - 1;
-    const bool known = jstar >= 0;
-    const uint32_t V = known ? (vm.vpre & ((2u << jstar) - 1u)) : vm.vpre;
-    const uint32_t ks = (n > 1) ? (sm.kor & V) : 0u;
-    const bool ksite = (ks & ~(known ? (1u << jstar) : 0u)) != 0u;
-    int jref = -1;
-    if (n > 1) { if (ks) jref = 31 - __clz((int)ks); }
-    else jref = jstar;
-    // ---- full-length evidence (:629-681) over V.  lfull: the first exon of a member of V overlaps the read's first
-    // exon.  lnoth stays set unless SOME exon of a member of V overlaps it; that is certain when the read's first donor
-    // is a donor of a member (the exon that ends there), else the START slice decides.
-    bool lfull = false, rfull = false, lnoth = true, rnoth = true;
-    if (LEVEL >= 1 && LEVEL <= 4) { lfull = (vm.lmask & V) != 0u; rfull = (vm.rmask & V) != 0u; }
-    if (LEVEL == 3 || LEVEL == 4) {
-        if (!lfull) {
-            if (sm.dm_first & V) lnoth = false;
-            else if (V) lnoth = (overlapping_exon_members(L.rdir, L.dir0, L.ent0, d.b_off, d.nb, re.s0, re.e0) & V) == 0u;
-        }
-        if (LEVEL == 3 && !rfull) {
-            if (sm.am_last & V) rnoth = false;
-            else if (V) rnoth = (overlapping_exon_members(L.rdir, L.dir0, L.ent0, d.b_off, d.nb, re.sl, re.el) & V) == 0u;
-        }
-    }
-    // ---- flags: an exon / junction is no longer novel iff the first member of V' that has it comes no later than
-    // j*; a known read has every probed donor and acceptor in transcript j*
-    const uint32_t lim = known ? (uint32_t)jstar : 62u;
-    const uint32_t site_bits = known ? 0u : (uint32_t)(F_DON | F_ACC);         // bits 12, 13 of a work word: the site is in V' (F_DON = 2, F_ACC = 4)
-    if (n > 1) {
-        for (int k = 0; k < (int)n; ++k) {
-            const uint32_t w = getw(k);
-            uint32_t f = ((w & 63u) > lim ? (uint32_t)F_EXON : 0u) | (((w >> 6) & 63u) > lim ? (uint32_t)F_JUNC : 0u) | ((~w >> 11) & site_bits);
-            f &= (k + 1 == (int)n) ? (uint32_t)F_EXON : 0xffu;                   // the last exon has no junction behind it
-            emit(k, f);
-        }
-    } else emit(0, (uint32_t)F_EXON);
-    int ref = -1;
-    bool out_rev = rev_in;
-    if (jref >= 0) { ref = L.win[jref]; out_rev = ((L.hk[jref].w >> 8) & 1) != 0; }     // :825-831
-    uint32_t info = 0;
-    if (known) info |= I_KNOWN;
-    if (ksite) info |= I_KSITE;
-    if (full_decision(LEVEL, lfull, lnoth, rfull, rnoth)) info |= I_FULL;
-    if (out_rev) info |= I_REV;
-    // routing of update_gtf.c:943-950 when there is no junction table (finish_info)
-    if (fast_args()->p.n_sj == 0 && (info & (I_FULL | I_KNOWN | I_KSITE)) == (I_FULL | I_KSITE)) info |= I_ACCEPT;
-    return Verdict{info | (n << 8), ref};
 }
 
 template <int LEVEL, bool WIDE>
@@ -1870,12 +1674,12 @@ void k_classify_fast(FastArgs kernarg_block /* read through fast_args() */, int6
         uint32_t info = n << 8; int ref = -1;
         bool redo = active && (!fast || !in_lds || any_wide != 0 || tid != d.tid || (n > 1 && !sane));
         const bool work = active && !redo;
-        const TileLds L{s_S, s_E, s_W, s_ent0, s_ent1, s_dir0, s_dir1, s_rdir, s_hk, s_hx, s_win};
-        const VisitMasks vm = visit_window<LEVEL>(L, d, w_n, work, n, j0, re, s_tilemask);
+        const TileLds<uint32_t> L{s_S, s_E, s_W, s_ent0, s_ent1, s_dir0, s_dir1, s_rdir, s_hk, s_hx, s_win};
+        const VisitMasks<uint32_t> vm = visit_window<LEVEL>(L, d, w_n, work, n, j0, re, s_tilemask);
         redo = redo || vm.redo;
         L2R_STAMP(2);
         const int o_dis = fast_args()->p.ss_dis;
-        const SiteMasks sm = o_dis > 0 ? map_exons_near(L, d, work && !redo && n > 1, local, n, vm.vpre, o_dis, re.s0, re.el)
+        const SiteMasks<uint32_t> sm = o_dis > 0 ? map_exons_near(L, d, work && !redo && n > 1, local, n, vm.vpre, o_dis, re.s0, re.el)
                                        : map_exons(L, d, work && !redo && n > 1, local, n, vm.vpre);
         // (-d > 0: a visited member with two sites within the tolerance of one read site -- its pair count is the generic kernel's)
         if (work && !redo && (sm.amb & vm.vpre) != 0u) redo = true;
@@ -1908,13 +1712,7 @@ void k_classify_fast(FastArgs kernarg_block /* read through fast_args() */, int6
                      "s"(o_ex_start), "s"(o_ex_end), "s"(o_ref), "s"(o_acc_start), "s"(o_acc_end), "s"(o_ex_flag), "s"(o_acc_flag), "s"(o_n_sj), "s"(o_ablate),
                      "s"(o_tile_rchunk), "s"(o_acc_ex_off), "s"(o_acc_rec), "s"(o_first_read));
         {
-            const unsigned long long m = __ballot(redo);
-            if (m) {
-                uint32_t at = 0;
-                if (lane == 0) at = atomicAdd(o_redo_count, (uint32_t)__popcll(m));
-                at = __shfl(at, 0, WAVE);
-                if (redo) o_redo[at + (uint32_t)__popcll(m & ((1ull << lane) - 1ull))] = (uint32_t)r;
-            }
+            const unsigned long long m = redo_append(ao, redo, (uint32_t)r);
             if (want_acc) {                  // (uniform) the accepted list is compacted only when somebody asked for it
                 const bool acc = (info & I_ACCEPT) != 0;
                 const uint32_t ca = (uint32_t)__popcll(__ballot(acc)), cx = wave_sum(acc ? n : 0u);

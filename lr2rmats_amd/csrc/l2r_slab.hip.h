@@ -862,10 +862,10 @@ struct SlabStage { uint32_t *A; uint16_t *Ln; uint32_t loc; int32_t lo; bool fit
 // DIS: -d > 0 -- every probe looks at the entries within the tolerance of its coordinate (probe_near), `dis` is the tolerance and [rs, re]
 // the read's span.
 template <bool DIS>
-__device__ __forceinline__ SiteMasks map_exons_slab(const TileLds &L, const TileDesc &d, bool mapping, const uint32_t *__restrict__ xw,
+__device__ __forceinline__ SiteMasks<uint32_t> map_exons_slab(const TileLds<uint32_t> &L, const TileDesc &d, bool mapping, const uint32_t *__restrict__ xw,
                                                     uint32_t off, uint32_t n, uint32_t vpre, const SlabRows &q, const SlabStage &st, int dis = 0, int rs = 0, int re = 0)
 {
-    SiteMasks m{0xffffffffu, 0u, 0u, 0u, 0u};
+    SiteMasks<uint32_t> m{0xffffffffu, 0u, 0u, 0u, 0u};
     uint32_t *const Ap = st.A + st.loc; uint16_t *const Lp = st.Ln + st.loc;
     // exon j of the read: row j + 1, the last one row 0
     SlabRow R[SLAB_AHEAD];
@@ -1040,12 +1040,25 @@ __device__ __forceinline__ void slab_copy_exons(SlabArgsK sa, PipeArgsK a, const
 // on slab-resident exons; exons, work words and then flag bytes at their positions in LDS (or, for a read that does not fit
 // there, in the result arrays), info / ref_tx / ex_off per read, redo list.
 struct SlabVerdict { uint32_t info; int ref; bool redo; };
+// decide on a read whose probe rounds have left its exons at their staged positions: work words = the upper 14 bits of the read's A
+// words, replaced by the flag byte.  (The read's ends once more, from its staged exons: four registers that need not live through the
+// probe rounds.)
+template <int LEVEL, typename M>
+__device__ __forceinline__ Verdict decide_staged(const TileLds<M> &L, const TileDesc &d, uint32_t n, const SlabStage &st, const VisitMasks<M> &vm, const SiteMasks<M> &sm, bool rev_in)
+{
+    uint32_t *const Ap = st.A + st.loc;
+    const uint16_t *const Lq = st.Ln + st.loc;
+    ReadEnds re2;
+    re2.s0 = st.lo + (int)(Ap[0] & SLAB_REL_MASK); re2.e0 = re2.s0 + (int)Lq[0] - 1;
+    re2.sl = st.lo + (int)(Ap[n - 1u] & SLAB_REL_MASK); re2.el = re2.sl + (int)Lq[n - 1u] - 1;
+    return decide<LEVEL>(L, d, n, re2, vm, sm, rev_in, [&](int k) { return Ap[k] >> SLAB_REL_BITS; },
+                         [&](int k, uint32_t f) { Ap[k] = (Ap[k] & SLAB_REL_MASK) | (f << SLAB_REL_BITS); });
+}
 template <int LEVEL, bool DIS>
 __device__ __forceinline__ SlabVerdict slab_classify(SlabArgsK sa, PipeArgsK a, const TileDesc &d, const SlabLds &S, const int4 *hk, const int4 *hx, const int *win,
                                               const uint32_t *tilemask, bool active, uint32_t pre, uint32_t r, uint32_t off, const SlabRows &q,
                                               const ReadEnds &re, const SlabOut &out, const SlabStage &st, int any_wide, SlabStamp &stamp)
 {
-    const int lane = threadIdx.x & (WAVE - 1);
     const bool fast = (d.flags & TD_FAST) != 0;
     const int w_n = fast ? (int)d.n_win : 0;
     const uint32_t n = pre >> PRE_N_SHIFT;
@@ -1056,39 +1069,23 @@ __device__ __forceinline__ SlabVerdict slab_classify(SlabArgsK sa, PipeArgsK a, 
     // (sorted input: a tile is of one chromosome, the descriptor's)
     bool redo = active && (!fast || outlier || !st.fits || any_wide != 0 || (n > 1 && (pre & PRE_INSANE) != 0u));
     const bool work = active && !redo;
-    const TileLds L{nullptr, nullptr, nullptr, S.ent0, S.ent1, S.dir0, S.dir1, S.rdir, hk, hx, win};
-    const VisitMasks vm = visit_window<LEVEL>(L, d, w_n, work, n, d.j_lo, re, tilemask);
+    const TileLds<uint32_t> L{nullptr, nullptr, nullptr, S.ent0, S.ent1, S.dir0, S.dir1, S.rdir, hk, hx, win};
+    const VisitMasks<uint32_t> vm = visit_window<LEVEL>(L, d, w_n, work, n, d.j_lo, re, tilemask);
     redo = redo || vm.redo;
     stamp.mark(2);
     const bool mapping = work && !redo && n > 1;
-    const SiteMasks sm = map_exons_slab<DIS>(L, d, mapping, xw, off, n, vm.vpre, q, st, DIS ? a->f.p.ss_dis : 0, re.s0, re.el);
+    const SiteMasks<uint32_t> sm = map_exons_slab<DIS>(L, d, mapping, xw, off, n, vm.vpre, q, st, DIS ? a->f.p.ss_dis : 0, re.s0, re.el);
     stamp.mark(3);
     if (active && !mapping) slab_copy_exons(sa, a, out, st, q, off, n, pre, r);
     // (-d > 0: a visited member with two sites within the tolerance of one read site -- its pair count is the generic kernel's)
     if (DIS && mapping && (sm.amb & vm.vpre) != 0u) redo = true;
     if (work && !redo) {
-        // work words: the upper 14 bits of the read's A words, replaced by the flag byte
-        uint32_t *const Ap = st.A + st.loc;
-        // (the read's ends once more, from its staged exons: four registers that need not live through the probe rounds)
-        const uint16_t *const Lq = st.Ln + st.loc;
-        ReadEnds re2;
-        re2.s0 = st.lo + (int)(Ap[0] & SLAB_REL_MASK); re2.e0 = re2.s0 + (int)Lq[0] - 1;
-        re2.sl = st.lo + (int)(Ap[n - 1u] & SLAB_REL_MASK); re2.el = re2.sl + (int)Lq[n - 1u] - 1;
-        const Verdict vd = decide<LEVEL>(L, d, n, re2, vm, sm, rev_in, [&](int k) { return Ap[k] >> SLAB_REL_BITS; },
-                                         [&](int k, uint32_t f) { Ap[k] = (Ap[k] & SLAB_REL_MASK) | (f << SLAB_REL_BITS); });
+        const Verdict vd = decide_staged<LEVEL>(L, d, n, st, vm, sm, rev_in);
         info = vd.info; ref = vd.ref;
     }
     stamp.mark(4);
     redo = redo && active;
-    {
-        const unsigned long long m = __ballot(redo);
-        if (m) {
-            uint32_t at = 0;
-            if (lane == 0) at = atomicAdd(a->f.redo_count, (uint32_t)__popcll(m));
-            at = __shfl(at, 0, WAVE);
-            if (redo) a->f.redo[at + (uint32_t)__popcll(m & ((1ull << lane) - 1ull))] = r;
-        }
-    }
+    redo_append(&a->f, redo, r);
     if (active) { a->f.info[r] = info; a->f.ref_tx[r] = ref; a->f.ex_off[r] = out.dst; }
     return SlabVerdict{info, ref, redo};
 }

@@ -117,7 +117,7 @@ __device__ __forceinline__ uint32_t tc_lookup2(const TcKey &K0, const TcKey &K1,
     return tc_half(K0.key, lo0, hi0, l0, T0, zero0, over) | (tc_half(K1.key, lo1, hi1, l1, T1, zero1, over) << TC_HALF_BITS);
 }
 
-// overlapping_exon_members64 (l2r_wide.hip.h) on the split key / mask arrays
+// overlapping_exon_members<m64_t> (l2r_masks.hip.h) on the split key / mask arrays
 __device__ __forceinline__ m64_t tc_overlapping_exon_members(const TcLds &L, int b_off, int nb, int s, int e)
 {
     const int bs = s >> SITE_SHIFT;
@@ -254,9 +254,9 @@ __device__ __forceinline__ uint32_t tc_flag_clears(uint32_t w, uint32_t lim, boo
     if (sites) clr |= (((w >> 12) & 1u) ? (uint32_t)F_DON : 0u) | (((w >> 13) & 1u) ? (uint32_t)F_ACC : 0u);
     return clr << TC_F_SHIFT;
 }
-__device__ __forceinline__ SiteMasks64 tc_map_exons(const TcLds &L, bool mapping, bool pend, uint32_t *Ap, uint32_t *Rp, uint32_t n, m64_t vpre, uint32_t zero0, uint32_t zero1)
+__device__ __forceinline__ SiteMasks<m64_t> tc_map_exons(const TcLds &L, bool mapping, bool pend, uint32_t *Ap, uint32_t *Rp, uint32_t n, m64_t vpre, uint32_t zero0, uint32_t zero1)
 {
-    SiteMasks64 m{~0ull, 0ull, 0ull, 0ull, 0ull};
+    SiteMasks<m64_t> m{~0ull, 0ull, 0ull, 0ull, 0ull};
     const int k_max = wave_max(mapping ? (int)n : 0);
     const uint32_t nm1 = mapping ? n - 1u : 0u;
     uint32_t R = mapping ? Rp[0] : 0u;
@@ -276,8 +276,8 @@ __device__ __forceinline__ SiteMasks64 tc_map_exons(const TcLds &L, bool mapping
         if (!((R0 >> 13) & 1u)) xm = 0ull;
         if (!((R1 >> 13) & 1u)) jm = 0ull;
         const m64_t amj = junc ? am : 0ull;
-        uint32_t word = first_member64(xm & vpre);
-        word |= first_member64(jm & vpre) << 6;
+        uint32_t word = first_member(xm & vpre);
+        word |= first_member(jm & vpre) << 6;
         word |= ((dm & vpre) ? 1u : 0u) << 12;
         word |= ((amj & vpre) ? 1u : 0u) << 13;
         m.kand &= junc ? (am & dm) : ~0ull;            // Q1: the acceptor probed with exon k is ITS OWN start, k < n-1
@@ -612,27 +612,14 @@ void k_tile_chunk(SlabArgs kernarg_block, const TileRec *__restrict__ u_rec, con
         redo = redo || vm.redo;
         stamp.mark(4);
         const bool mapping = work && !vm.redo && n > 1 && !(ablate & 4096);
-        const SiteMasks64 sm = tc_map_exons(L, mapping, pend, Ap, Rp, n, vm.vpre, d.st_nk, d.en_nk);
+        const SiteMasks<m64_t> sm = tc_map_exons(L, mapping, pend, Ap, Rp, n, vm.vpre, d.st_nk, d.en_nk);
         stamp.mark(5);
         if (work && !vm.redo) {
-            int jstar = -1;
-            if (n > 1) {
-                m64_t c = sm.kand & vm.vpre;
-                while (c) {
-                    const int j = __ffsll((long long)c) - 1;
-                    c &= c - 1ull;
-                    const int4 hk = s_hk[j];
-                    if (hk.x <= re.e0 && re.sl <= hk.y) { jstar = j; break; }
-                }
-            } else if (vm.k1mask) jstar = __ffsll((long long)vm.k1mask) - 1;
+            const Known<m64_t> kn = pick_known(s_hk, n, re, vm.vpre, vm.k1mask, sm.kand, sm.kor);
+            const int jstar = kn.jstar, jref = kn.jref;
             const bool known_c = jstar >= 0;
-            const m64_t upto = jstar >= 63 ? ~0ull : ((2ull << (known_c ? jstar : 0)) - 1ull);
-            const m64_t V = known_c ? (vm.vpre & upto) : vm.vpre;
-            const m64_t ks = (n > 1) ? (sm.kor & V) : 0ull;
-            ksite = ksite || (ks & ~(known_c ? (1ull << jstar) : 0ull)) != 0ull;
-            int jref = -1;
-            if (n > 1) { if (ks) jref = 63 - __clzll((long long)ks); }
-            else jref = jstar;
+            const m64_t V = kn.V;
+            ksite = ksite || kn.ksite;
             if (jref >= 0) { ref = cb + jref; out_rev = ((s_hk[jref].w >> 8) & 1) != 0; }     // :825-831 (a later chunk's member is a later transcript)
             if (LEVEL >= 1 && LEVEL <= 4) { lfull = lfull || (vm.lmask & V) != 0ull; rfull = rfull || (vm.rmask & V) != 0ull; }
             if (LEVEL == 3 || LEVEL == 4) {
@@ -669,25 +656,13 @@ void k_tile_chunk(SlabArgs kernarg_block, const TileRec *__restrict__ u_rec, con
                 Ap[k] = (Ap[k] & SLAB_REL_MASK) | (f << SLAB_REL_BITS);
             }
         } else Ap[0] = (Ap[0] & SLAB_REL_MASK) | ((uint32_t)F_EXON << SLAB_REL_BITS);
-        if (known) info |= I_KNOWN;
-        if (ksite) info |= I_KSITE;
-        if (full_decision(LEVEL, lfull, lnoth, rfull, rnoth)) info |= I_FULL;
-        if (out_rev) info |= I_REV;
-        if (a->f.p.n_sj == 0 && (info & (I_FULL | I_KNOWN | I_KSITE)) == (I_FULL | I_KSITE)) info |= I_ACCEPT;
+        info = verdict_info(LEVEL, n << 8, known, ksite, lfull, lnoth, rfull, rnoth, out_rev);
     } else {
         ref = -1;
         if (active) for (uint32_t k = 0; k < n; ++k) Ap[k] = big ? SLAB_POS_SKIP : (Ap[k] & SLAB_REL_MASK);      // (flags 0: the generic kernel writes them)
     }
     redo = redo && active;
-    {
-        const unsigned long long m = __ballot(redo);
-        if (m) {
-            uint32_t at = 0;
-            if (lane == 0) at = atomicAdd(a->f.redo_count, (uint32_t)__popcll(m));
-            at = __shfl(at, 0, WAVE);
-            if (redo) a->f.redo[at + (uint32_t)__popcll(m & ((1ull << lane) - 1ull))] = r;
-        }
-    }
+    redo_append(&a->f, redo, r);
     if (active) { a->f.info[r] = info; a->f.ref_tx[r] = ref; }
     // ---- the tile's first result slot (every tile in front exact: the first look was all of it)
     {

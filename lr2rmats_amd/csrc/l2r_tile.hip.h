@@ -275,9 +275,9 @@ constexpr int TILE_AHEAD = L2R_TILE_AHEAD;
 constexpr int TILE_PRIO = L2R_TILE_PRIO;                // k_tile: a wave's issue priority outside its classification (0 inside)
 constexpr int TILE_NS = L2R_TILE_NS, TILE_NE = L2R_TILE_NE;      // entries of a START / END bucket every probe round looks at without a loop
 template <bool DIS>
-__device__ __forceinline__ SiteMasks map_exons_lds(const TileLds &L, const TileDesc &d, bool mapping, uint32_t n, uint32_t vpre, const SlabStage &st, int dis = 0, int rs = 0, int re = 0)
+__device__ __forceinline__ SiteMasks<uint32_t> map_exons_lds(const TileLds<uint32_t> &L, const TileDesc &d, bool mapping, uint32_t n, uint32_t vpre, const SlabStage &st, int dis = 0, int rs = 0, int re = 0)
 {
-    SiteMasks m{0xffffffffu, 0u, 0u, 0u, 0u};
+    SiteMasks<uint32_t> m{0xffffffffu, 0u, 0u, 0u, 0u};
     uint32_t *const Ap = st.A + st.loc; uint16_t *const Lp = st.Ln + st.loc;
     const uint32_t nm1 = mapping ? n - 1u : 0u;
     SlabRow R[TILE_AHEAD];
@@ -351,65 +351,7 @@ __device__ __forceinline__ SiteMasks map_exons_lds(const TileLds &L, const TileD
     return m;
 }
 
-// Verdicts of the tile's reads from the staged window + dictionaries (slab_classify with the exons in LDS).  big: the read has an exon
-// the row word cannot say (16 kb or longer, or 2^18 - 1 bases or more behind the tile's first base): the generic kernel classifies it,
-// its exons are written from a literal walk once the tile's first slot is known, its positions are marked.
-template <int LEVEL, bool DIS>
-__device__ __forceinline__ SlabVerdict tile_classify(PipeArgsK a, const TileDesc &d, const SlabLds &S, const int4 *hk, const int4 *hx, const int *win, const uint32_t *tilemask,
-                                                    bool active, uint32_t pre, bool big, uint32_t r, const ReadEnds &re, const SlabStage &st, int any_wide, SlabStamp &stamp)
-{
-    const int lane = threadIdx.x & (WAVE - 1);
-    const bool fast = (d.flags & TD_FAST) != 0;
-    const int w_n = (fast && !(a->f.p.ablate & 8192)) ? (int)d.n_win : 0;          // (bits 12, 13: timing diagnostics -- no probe rounds, no member pass; results wrong)
-    const uint32_t n = pre >> PRE_N_SHIFT;
-    const bool rev_in = (pre & PRE_REV) != 0u;
-    uint32_t info = n << 8; int ref = -1;
-    bool redo = active && (!fast || big || any_wide != 0 || (n > 1 && (pre & PRE_INSANE) != 0u));
-    const bool work = active && !redo;
-    const TileLds L{nullptr, nullptr, nullptr, S.ent0, S.ent1, S.dir0, S.dir1, S.rdir, hk, hx, win};
-    const VisitMasks vm = visit_window<LEVEL>(L, d, w_n, work, n, d.j_lo, re, tilemask);
-    redo = redo || vm.redo;
-    stamp.mark(2);
-    const bool mapping = work && !redo && n > 1 && !(a->f.p.ablate & 4096);
-    const SiteMasks sm = map_exons_lds<DIS>(L, d, mapping, n, vm.vpre, st, DIS ? a->f.p.ss_dis : 0, re.s0, re.el);
-    stamp.mark(3);
-    if (active && !mapping) {
-        // no probe round has rewritten this read's row words: {start, flags 0} and the length apart, as the write-out reads them
-        uint32_t *const Ap = st.A + st.loc; uint16_t *const Lp = st.Ln + st.loc;
-        for (uint32_t k = 0; k < n; ++k) {
-            const uint32_t w = Ap[k];
-            Ap[k] = big ? SLAB_POS_SKIP : (w & SLAB_REL_MASK); Lp[k] = (uint16_t)(w >> SLAB_REL_BITS);
-        }
-    }
-    // (-d > 0: a visited member with two sites within the tolerance of one read site -- its pair count is the generic kernel's)
-    if (DIS && mapping && (sm.amb & vm.vpre) != 0u) redo = true;
-    if (work && !redo) {
-        uint32_t *const Ap = st.A + st.loc;
-        // (the read's ends once more, from its staged exons: four registers that need not live through the probe rounds)
-        const uint16_t *const Lq = st.Ln + st.loc;
-        ReadEnds re2;
-        re2.s0 = st.lo + (int)(Ap[0] & SLAB_REL_MASK); re2.e0 = re2.s0 + (int)Lq[0] - 1;
-        re2.sl = st.lo + (int)(Ap[n - 1u] & SLAB_REL_MASK); re2.el = re2.sl + (int)Lq[n - 1u] - 1;
-        const Verdict vd = decide<LEVEL>(L, d, n, re2, vm, sm, rev_in, [&](int k) { return Ap[k] >> SLAB_REL_BITS; },
-                                         [&](int k, uint32_t f) { Ap[k] = (Ap[k] & SLAB_REL_MASK) | (f << SLAB_REL_BITS); });
-        info = vd.info; ref = vd.ref;
-    }
-    stamp.mark(4);
-    redo = redo && active;
-    {
-        const unsigned long long m = __ballot(redo);
-        if (m) {
-            uint32_t at = 0;
-            if (lane == 0) at = atomicAdd(a->f.redo_count, (uint32_t)__popcll(m));
-            at = __shfl(at, 0, WAVE);
-            if (redo) a->f.redo[at + (uint32_t)__popcll(m & ((1ull << lane) - 1ull))] = r;
-        }
-    }
-    if (active) a->f.ref_tx[r] = ref;                           // (info: by the caller, behind the junction check)
-    return SlabVerdict{info, ref, redo};
-}
-
-// ---- the same for a tile whose window holds 33 .. 63 transcripts (k_tile<..., WIDE>): 64-bit masks, 24-byte entries
+// ---- the probe rounds of a tile whose window holds 33 .. 63 transcripts (k_tile<..., WIDE>): 64-bit masks, 24-byte entries
 // probe_all64 (l2r_wide.hip.h) for keys that may come in several entries (SE_WIDE: the key's transcripts lie more than 64 apart in the
 // annotation): the parts' masks are ORed, each re-based to the window -- a part that has nothing to say about it re-bases to nothing
 // (k_probe_slab_chunked's rule, probe_parts64); such a tile need not be handed on.
@@ -418,13 +360,14 @@ __device__ __forceinline__ void probe_or64(const WEnt *ent, uint32_t lo, uint32_
     pm = 0ull; sm = 0ull;
     for (uint32_t r = lo; r < hi; ++r) {
         const WEnt q = ent[r];
-        if (q.k1 == k1) { sm |= q.sm; if (q.k2 == k2) pm |= q.pm; }
+        if (q.x == k1) { sm |= q.w; if (q.y == k2) pm |= q.z; }
     }
 }
-// map_exons_lds on 64-bit masks (map_exons_slab64 with the exons at their read-order positions in LDS)
-__device__ __forceinline__ SiteMasks64 map_exons_lds_wide(const WideLds &L, const TileDesc &d, bool mapping, uint32_t n, m64_t vpre, const SlabStage &st, int dis, int rs, int re)
+// map_exons_lds on 64-bit masks (map_exons_slab's 64-bit form with the exons at their read-order positions in LDS; -d is the wave-uniform `dis`)
+template <bool DIS>
+__device__ __forceinline__ SiteMasks<m64_t> map_exons_lds(const TileLds<m64_t> &L, const TileDesc &d, bool mapping, uint32_t n, m64_t vpre, const SlabStage &st, int dis, int rs, int re)
 {
-    SiteMasks64 m{~0ull, 0ull, 0ull, 0ull, 0ull};
+    SiteMasks<m64_t> m{~0ull, 0ull, 0ull, 0ull, 0ull};
     uint32_t *const Ap = st.A + st.loc; uint16_t *const Lp = st.Ln + st.loc;
     const uint32_t none = (uint32_t)d.nbk + 1u;         // a bucket behind the staged ones: the staging leaves it empty
     const int k_max = wave_max(mapping ? (int)n : 0);
@@ -439,8 +382,8 @@ __device__ __forceinline__ SiteMasks64 map_exons_lds_wide(const WideLds &L, cons
         if (dis > 0) {                                  // (wave-uniform: -d)
             uint32_t ls, hs, le, he;
             near_range(L.dir0, d.b_off, none, live, s, dis, ls, hs); near_range(L.dir1, d.b_off, none, junc, e, dis, le, he);
-            probe_near64(L.ent0, ls, hs, s, e, dis, rs, re, xm, am, m.amb);
-            probe_near64(L.ent1, le, he, e, s2, dis, rs, re, jm, dm, m.amb);
+            probe_near(L.ent0, ls, hs, s, e, dis, rs, re, xm, am, m.amb);
+            probe_near(L.ent1, le, he, e, s2, dis, rs, re, jm, dm, m.amb);
         } else {
             const uint32_t is = live ? min((uint32_t)((s >> SITE_SHIFT) + d.b_off), none) : none;
             const uint32_t ie = junc ? min((uint32_t)((e >> SITE_SHIFT) + d.b_off), none) : none;
@@ -449,8 +392,8 @@ __device__ __forceinline__ SiteMasks64 map_exons_lds_wide(const WideLds &L, cons
             probe_or64(L.ent1, le, he, e, s2, jm, dm);
         }
         const m64_t amj = junc ? am : 0ull;
-        uint32_t word = first_member64(xm & vpre);
-        word |= first_member64(jm & vpre) << 6;
+        uint32_t word = first_member(xm & vpre);
+        word |= first_member(jm & vpre) << 6;
         word |= ((dm & vpre) ? 1u : 0u) << 12;
         word |= ((amj & vpre) ? 1u : 0u) << 13;
         m.kand &= junc ? (am & dm) : ~0ull;            // Q1: the acceptor probed with exon k is ITS OWN start, k < n-1
@@ -462,59 +405,31 @@ __device__ __forceinline__ SiteMasks64 map_exons_lds_wide(const WideLds &L, cons
     }
     return m;
 }
-// slab_stage_dict on 64-bit masks (k_probe_slab_wide's staging): entries re-based to the tile's window, byte directories
-__device__ __forceinline__ void wide_stage_dict(const TileDesc &d, const DictRegs &dv, const int *win, WEnt *s_ent0, WEnt *s_ent1, uint8_t *s_dir0, uint8_t *s_dir1, uint8_t *s_rdir)
+
+// Verdicts of the tile's reads from the staged window + dictionaries (slab_classify with the exons in LDS).  big: the read has an exon
+// the row word cannot say (16 kb or longer, or 2^18 - 1 bases or more behind the tile's first base): the generic kernel classifies it,
+// its exons are written from a literal walk once the tile's first slot is known, its positions are marked.
+// M = uint32_t: k_tile's plain and EXACT instances; M = m64_t: its WIDE instance (a window of 33 .. 63 transcripts, 24-byte entries).
+template <int LEVEL, bool DIS, typename M>
+__device__ __forceinline__ SlabVerdict tile_classify(PipeArgsK a, const TileDesc &d, const TileLds<M> &L, const M *tilemask,
+                                                    bool active, uint32_t pre, bool big, uint32_t r, const ReadEnds &re, const SlabStage &st, int any_wide, SlabStamp &stamp)
 {
-    const int w_n = (int)d.n_win;
-    if ((int)threadIdx.x < WIDE_KEY_CAP) {
-        const bool has_st = threadIdx.x < d.st_nk, has_en = threadIdx.x < d.en_nk;
-        WEnt e0, e1;
-        e0.k1 = dv.xa.x; e0.k2 = dv.xa.y; e1.k1 = dv.xc.x; e1.k2 = dv.xc.y;
-        const m64_t pm0 = ((m64_t)(uint32_t)dv.xb.y << 32) | (uint32_t)dv.xb.x, sm0 = ((m64_t)(uint32_t)dv.xb.w << 32) | (uint32_t)dv.xb.z;
-        const m64_t pm1 = ((m64_t)(uint32_t)dv.xd.y << 32) | (uint32_t)dv.xd.x, sm1 = ((m64_t)(uint32_t)dv.xd.w << 32) | (uint32_t)dv.xd.z;
-        if (d.flags & TD_CONTIG) {
-            e0.pm = rebase64(pm0, dv.xa.z - d.j_lo); e0.sm = rebase64(sm0, dv.xa.z - d.j_lo);
-            e1.pm = rebase64(pm1, dv.xc.z - d.j_lo); e1.sm = rebase64(sm1, dv.xc.z - d.j_lo);
-        } else {
-            m64_t mm[4] = {pm0, sm0, pm1, sm1};
-            rebase_gaps64(win, w_n, mm, dv.xa.z, dv.xc.z);
-            e0.pm = mm[0]; e0.sm = mm[1]; e1.pm = mm[2]; e1.sm = mm[3];
-        }
-        if (has_st) s_ent0[threadIdx.x] = e0;
-        if (has_en) s_ent1[threadIdx.x] = e1;
-    }
-    if (d.nbk > 0) {
-#pragma unroll
-        for (int qq = 0; qq < 2; ++qq) {
-            const int i = (int)threadIdx.x + qq * TILE_THREADS;
-            if (i <= d.nbk) {
-                s_dir0[i] = (uint8_t)(dv.dd[0][qq] - d.st_r0); s_dir1[i] = (uint8_t)(dv.dd[1][qq] - d.en_r0);
-                s_rdir[i] = (uint8_t)(dv.dd[2][qq] - d.st_r0);
-            }
-        }
-    }
-    if (threadIdx.x < 3u && (threadIdx.x > 0u || d.nbk == 0)) {
-        s_dir0[d.nbk + (int)threadIdx.x] = (uint8_t)d.st_nk; s_dir1[d.nbk + (int)threadIdx.x] = (uint8_t)d.en_nk;
-    }
-}
-// tile_classify on 64-bit masks
-template <int LEVEL, bool DIS>
-__device__ __forceinline__ SlabVerdict tile_classify_wide(PipeArgsK a, const TileDesc &d, const WideLds &L, const m64_t *tilemask,
-                                                         bool active, uint32_t pre, bool big, uint32_t r, const ReadEnds &re, const SlabStage &st)
-{
-    const int lane = threadIdx.x & (WAVE - 1);
-    const bool fast = (d.flags & TD_WIDE) != 0;
-    const int w_n = (fast && !(a->f.p.ablate & 8192)) ? (int)d.n_win : 0;          // (bits 12, 13: timing diagnostics as in tile_classify)
+    constexpr bool WIDE = sizeof(M) == 8;
+    const bool fast = (d.flags & (WIDE ? TD_WIDE : TD_FAST)) != 0;                  // (the mark of the tiles that this width's instances take)
+    const int w_n = (fast && !(a->f.p.ablate & 8192)) ? (int)d.n_win : 0;          // (bits 12, 13: timing diagnostics -- no probe rounds, no member pass; results wrong)
     const uint32_t n = pre >> PRE_N_SHIFT;
     const bool rev_in = (pre & PRE_REV) != 0u;
     uint32_t info = n << 8; int ref = -1;
-    bool redo = active && (!fast || big || (n > 1 && (pre & PRE_INSANE) != 0u));
+    // (any_wide, a key in several entries: the 32-bit probes read one of them -- the 64-bit ones OR the parts, probe_or64)
+    bool redo = active && (!fast || big || (!WIDE && any_wide != 0) || (n > 1 && (pre & PRE_INSANE) != 0u));
     const bool work = active && !redo;
-    const VisitMasks64 vm = visit_window64<LEVEL>(L, d, w_n, work, n, d.j_lo, re, tilemask);
+    const VisitMasks<M> vm = visit_window<LEVEL>(L, d, w_n, work, n, d.j_lo, re, tilemask);
     redo = redo || vm.redo;
+    // (the WIDE instance does not stamp the three phases apart: their cycles count with the caller's next mark)
+    if constexpr (!WIDE) stamp.mark(2);
     const bool mapping = work && !redo && n > 1 && !(a->f.p.ablate & 4096);
-    const int dis = DIS ? a->f.p.ss_dis : 0;
-    const SiteMasks64 sm = map_exons_lds_wide(L, d, mapping, n, vm.vpre, st, dis, re.s0, re.el);
+    const SiteMasks<M> sm = map_exons_lds<DIS>(L, d, mapping, n, vm.vpre, st, DIS ? a->f.p.ss_dis : 0, re.s0, re.el);
+    if constexpr (!WIDE) stamp.mark(3);
     if (active && !mapping) {
         // no probe round has rewritten this read's row words: {start, flags 0} and the length apart, as the write-out reads them
         uint32_t *const Ap = st.A + st.loc; uint16_t *const Lp = st.Ln + st.loc;
@@ -523,31 +438,22 @@ __device__ __forceinline__ SlabVerdict tile_classify_wide(PipeArgsK a, const Til
             Ap[k] = big ? SLAB_POS_SKIP : (w & SLAB_REL_MASK); Lp[k] = (uint16_t)(w >> SLAB_REL_BITS);
         }
     }
-    if (DIS && mapping && (sm.amb & vm.vpre) != 0ull) redo = true;
+    // (-d > 0: a visited member with two sites within the tolerance of one read site -- its pair count is the generic kernel's)
+    if (DIS && mapping && (sm.amb & vm.vpre) != 0) redo = true;
     if (work && !redo) {
-        uint32_t *const Ap = st.A + st.loc;
-        const uint16_t *const Lq = st.Ln + st.loc;
-        ReadEnds re2;
-        re2.s0 = st.lo + (int)(Ap[0] & SLAB_REL_MASK); re2.e0 = re2.s0 + (int)Lq[0] - 1;
-        re2.sl = st.lo + (int)(Ap[n - 1u] & SLAB_REL_MASK); re2.el = re2.sl + (int)Lq[n - 1u] - 1;
-        const Verdict vd = decide64<LEVEL>(L, d, n, re2, vm, sm, rev_in, [&](int k) { return Ap[k] >> SLAB_REL_BITS; },
-                                           [&](int k, uint32_t f) { Ap[k] = (Ap[k] & SLAB_REL_MASK) | (f << SLAB_REL_BITS); });
+        const Verdict vd = decide_staged<LEVEL>(L, d, n, st, vm, sm, rev_in);
         info = vd.info; ref = vd.ref;
-    } else if (work && mapping) {
-        // (probed, then found ambiguous: the work words go, flags 0 -- the generic kernel writes them)
-        uint32_t *const Ap = st.A + st.loc;
-        for (uint32_t k = 0; k < n; ++k) Ap[k] &= SLAB_REL_MASK;
-    }
-    redo = redo && active;
-    {
-        const unsigned long long m = __ballot(redo);
-        if (m) {
-            uint32_t at = 0;
-            if (lane == 0) at = atomicAdd(a->f.redo_count, (uint32_t)__popcll(m));
-            at = __shfl(at, 0, WAVE);
-            if (redo) a->f.redo[at + (uint32_t)__popcll(m & ((1ull << lane) - 1ull))] = r;
+    } else if constexpr (WIDE) {
+        // (probed, then found ambiguous: the work words go, flags 0 -- the generic kernel writes them.  The 32-bit instances leave them
+        //  for it to overwrite.)
+        if (work && mapping) {
+            uint32_t *const Ap = st.A + st.loc;
+            for (uint32_t k = 0; k < n; ++k) Ap[k] &= SLAB_REL_MASK;
         }
     }
+    if constexpr (!WIDE) stamp.mark(4);
+    redo = redo && active;
+    redo_append(&a->f, redo, r);
     if (active) a->f.ref_tx[r] = ref;                           // (info: by the caller, behind the junction check)
     return SlabVerdict{info, ref, redo};
 }
@@ -575,7 +481,8 @@ void k_tile(SlabArgs kernarg_block, const TileRec *__restrict__ u_rec, const Til
     static_assert(!(WIDE && EXACT), "the EXACT instance is a plain one");
     constexpr int DIR_BYTES = FAST_DIR_BYTES;
     using WinT = typename std::conditional<WIDE, TileWin64, TileWin>::type;
-    using EntT = typename std::conditional<WIDE, WEnt, v4i_t>::type;
+    using MaskT = typename std::conditional<WIDE, m64_t, uint32_t>::type;
+    using EntT = typename ent_of<MaskT>::type;
     constexpr int AUX_BYTES = SLAB_DIR_BYTES + (int)sizeof(WinT);
     static_assert(AUX_BYTES >= SLAB_AUX_BYTES && WIDE_KEY_CAP == SLAB_KEY_CAP, "the WIDE instance's arrays hold what the plain one's do");
     __shared__ __attribute__((aligned(16))) uint32_t s_A[TILE_POS_CAP];
@@ -872,9 +779,8 @@ void k_tile(SlabArgs kernarg_block, const TileRec *__restrict__ u_rec, const Til
     const uint32_t r = r0 + idx;
     // ---- classification (a lane probes the positions it has placed itself; the dictionary slices were whole at the barrier above)
     __builtin_amdgcn_s_setprio(0);
-    SlabVerdict vd;
-    if constexpr (WIDE) vd = tile_classify_wide<LEVEL, DIS>(a, d, WideLds{s_ent0, s_ent1, s_dir0, s_dir1, s_rdir, s_tw.hk, s_tw.hx, s_tw.win}, s_tw.mask, active, pre, big, r, re, st);
-    else vd = tile_classify<LEVEL, DIS>(a, d, SlabLds{nullptr, s_ent0, s_ent1, s_dir0, s_dir1, s_rdir}, s_tw.hk, s_tw.hx, s_tw.win, s_tw.mask, active, pre, big, r, re, st, any_wide, stamp);
+    SlabVerdict vd = tile_classify<LEVEL, DIS>(a, d, TileLds<MaskT>{nullptr, nullptr, nullptr, s_ent0, s_ent1, s_dir0, s_dir1, s_rdir, s_tw.hk, s_tw.hx, s_tw.win},
+                                                     s_tw.mask, active, pre, big, r, re, st, any_wide, stamp);
     __builtin_amdgcn_s_setprio(TILE_PRIO);
     if (ACC) { const int w_redo = __any(vd.redo) ? 1 : 0; if (lane == 0) s_redow[wv] = (uint32_t)w_redo; }
     // ---- short-read junction support (-j: src/update_gtf.c:698-709 check_with_short_sj, :609-627 check_short_sj) for the reads whose

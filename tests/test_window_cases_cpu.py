@@ -81,7 +81,7 @@ def test_window_size(oracle, name):
     if case.family == "dis":
         return
     if m["shorts"] == 0:
-        k1, k2 = np.array(kinds[1]), np.array(kinds[2])
+        k1, k2 = np.array(kinds[1]), np.array(sorted(set(kinds[2]) - set(m.get("between", ()))))
         assert ((want.info[k1] & 1) != 0).all() and (want.ref_tx[k1] == members[0]).all()
         if m["edge"] != "single":                                  # the last member's chain: known through it and nobody else
             assert ((want.info[k2] & 1) != 0).all() and (want.ref_tx[k2] == last).all()
@@ -94,6 +94,22 @@ def test_window_size(oracle, name):
         ex = case.txs[last][2]
         assert any(ex[k + 1][0] <= ex[k][0] for k in range(len(ex) - 1))
         assert all(all(ex[k + 1][0] > ex[k][0] for k in range(len(ex) - 1)) for _t, _r, ex in case.txs[:last])
+    if m["edge"] == "twin":
+        # the last member has two donors within 2 * dis of each other; the reads between them have X's donor strictly between the two, and
+        # those within the tolerance of both are not known through the member -- they are as soon as the second donor is out of reach
+        dis, (d0, d1), rows = case.params["ss_dis"], m["twin"], np.array(m["between"])
+        donors = {e for s, e in case.txs[last][2][:-1]}
+        assert dis > 0 and 0 < d1 - d0 <= 2 * dis and {d0, d1} <= donors and len(rows) >= 40
+        read_donor = np.array([[int(e) for e in want.ex_end[want.ex_off[i]:want.ex_off[i + 1] - 1] if d0 < e < d1] for i in rows])
+        assert read_donor.shape == (len(rows), 1)
+        both = (read_donor[:, 0] - d0 <= dis) & (d1 - read_donor[:, 0] <= dis)
+        assert both.sum() >= 15 and ((want.info[rows[both]] & 3) == 2).all() and ((want.info[rows[~both]] & 1) != 0).all()
+        far = wc.window_case(m["n_win"], edge="twin", dis=dis, twin_gap=2 * dis + 1)
+        assert far.rows == case.rows and len(wc.describe(far.txs, far.rows, dis=dis)[0].members) == m["n_win"]
+        moved = _oracle(oracle, far)
+        assert ((moved.info[rows] & 1) != 0).all() and (moved.ref_tx[rows] == last).all()
+        rest = np.setdiff1d(np.arange(len(case.rows)), rows[both])
+        assert np.array_equal(moved.info[rest], want.info[rest]) and np.array_equal(moved.ref_tx[rest], want.ref_tx[rest])
     if m["shorts"]:
         # the early reads' sweep begins at member 0, the late reads' at member `shorts`: behind every short transcript
         first = {t.first for t in tiles}

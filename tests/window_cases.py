@@ -255,10 +255,13 @@ def _window_name(n, gapped=False, edge="plain", dis=0):
     return "win_%d_%s%s%s" % (n, "gapped" if gapped else "contig", "" if edge == "plain" else "_" + edge, "_d%d" % dis if dis else "")
 
 
-def window_case(n, gapped=False, edge="plain", shorts=0, dis=0, levels=(1, 3, 5), n_reads=840, name=None):
+def window_case(n, gapped=False, edge="plain", shorts=0, dis=0, levels=(1, 3, 5), n_reads=840, name=None, twin_gap=None):
     """A locus whose window has n members: `shorts` short transcripts at the left end of LO_B, then isoforms; edge = what the last
     member is: "plain" an isoform, "single" a single-exon transcript in HI_B with single-exon reads ending over it on both sides of
-    single_exon_ovlp_frac, "loose" an isoform whose exons are not in order (no TX_COMPACT)."""
+    single_exon_ovlp_frac, "loose" an isoform whose exons are not in order (no TX_COMPACT), "twin" (-d > 0) an isoform with a micro-exon
+    behind its own exon X: a second donor twin_gap (2 * dis: the most that one read donor can be within the tolerance of both) bases
+    behind X's.  Half of the reads with its chain skip the micro-exon and end X one to twin_gap - 1 bases behind X's donor: those in
+    the middle make two (annotation site, read site) pairs with the member, which the masks cannot count."""
     n_iso = n - shorts - (1 if edge == "single" else 0)
     isos = [_isoform(i) for i in range(max(n_iso, 2))]
     txs = []
@@ -270,6 +273,10 @@ def window_case(n, gapped=False, edge="plain", shorts=0, dis=0, levels=(1, 3, 5)
         if edge == "loose" and i == n_iso - 1:
             ex = [P(i // 8), F(i // 8), inner(76), inner(75), L(i // 8)]
             edge_chain = [F(i // 8), inner(75), inner(76), L(i // 8)]
+        if edge == "twin" and i == n_iso - 1:
+            x = 1 + (i % 4 & 1)                                      # X in the chain: the exon of its own
+            twin = (isos[i][x][1], isos[i][x][1] + (2 * dis if twin_gap is None else twin_gap))
+            ex.insert(len(ex) - len(isos[i]) + x + 1, (twin[0] + 2, twin[1]))
         txs.append((0, i & 1, ex))
         if gapped and i % 3 == 2 and i + 1 < n_iso:
             txs.append(GAP)
@@ -281,9 +288,19 @@ def window_case(n, gapped=False, edge="plain", shorts=0, dis=0, levels=(1, 3, 5)
     late = 60 if shorts else 0
     donors = [B0 + 15 + q for q in range(1, shorts, 2)]
     rows, kinds = _locus_rows(isos[:max(n_iso, 2)], n_reads, 1000 * n + shorts, edge_chain, late=late, single_end=single_end, phantom_donors=donors)
+    between = []
+    if edge == "twin":                                           # every other read with the edge's chain: X's donor between the twins
+        for q, i in enumerate(kinds[2][1::2]):
+            ex = list(edge_chain)
+            ex[x] = (ex[x][0], twin[0] + 1 + q % (2 * dis - 1))
+            ex[-1] = (ex[-1][0], ex[-1][1] - q % 40)
+            rows[i] = _chain(ex)
+            between.append(i)
     rows, at = _finish(rows)
     name = name or _window_name(n, gapped, edge, dis)
     meta = dict(n_win=n, edge=edge, shorts=shorts, gapped=gapped, n_iso=n_iso, kinds={k: [at[i] for i in v] for k, v in kinds.items()})
+    if edge == "twin":
+        meta.update(twin=twin, between=sorted(at[i] for i in between))
     return Case(name, "window", txs, rows, dict(ss_dis=dis), levels, meta)
 
 
@@ -293,7 +310,7 @@ def window_cases():
         for kw in (dict(), dict(gapped=True), dict(edge="single"), dict(edge="loose")):
             out.append(_spec(_window_name(n, **kw), window_case, n, **kw))
     for n in (32, 63):
-        for kw in (dict(dis=2), dict(gapped=True, dis=2)):
+        for kw in (dict(dis=2), dict(gapped=True, dis=2), dict(edge="twin", dis=2)):
             out.append(_spec(_window_name(n, **kw), window_case, n, **kw))
         for k in (n - 1, n):                                     # the late reads' cursor: the last member / behind the window
             name = "win_%d_cursor_%d" % (n, k)
