@@ -502,6 +502,50 @@ int          l2r_gtf_rows_out(l2r_ctx *ctx, l2r_gtf_rows *rows);          /* of 
 int          l2r_gtf_stats(l2r_ctx *ctx, double *out, int n);
 int          l2r_gtf_check(const l2r_gtf_text *text, int64_t *line, int64_t *counts);
 
+/* ---- `bam2bed` (host/bed.c): alignment records as BED12 text, one line per mapped record with the blocks between its introns -- what the
+ * reference pipeline gets from `bedtools bamtobed -bed12` (Snakefile, rule minimap_map).  The rule below is the whole definition: no byte
+ * equality with the output of any bedtools release is claimed.
+ * A record with FLAG & 4 writes nothing.  Every other record, in input order, writes twelve tab-separated columns and '\n':
+ *    1 the reference name of tid    2 pos (0-based)    3 pos + span    4 QNAME, followed by "/1" where FLAG & 0x40, else "/2" where FLAG & 0x80
+ *    5 MAPQ    6 '-' where FLAG & 16, else '+'    7 pos    8 pos + span    9 the colour string    10 the block count
+ *    11 the block sizes, commas between them and none behind the last    12 the block starts relative to pos, likewise
+ * The blocks come from one walk over the CIGAR: cur = 0, len = 0, starts = [0]; M = X D add their length to cur and len; N appends len to
+ * the sizes, adds its length to cur, appends cur to the starts and sets len = 0; I S H P do nothing; at the end len is appended to the
+ * sizes and span = cur.  A block may be 0 long (a CIGAR that begins with N, two N in a row, no CIGAR at all).  Sums are 64 bit.
+ * Domain errors fail the call and write nothing: a mapped record whose tid is outside [0, n_ref) or whose pos is negative, a CIGAR
+ * operation code above 8, an end beyond 2147483647.  l2r_last_error() names the smallest such record (0-based within the call) and the kind.
+ *     l2r_bed_begin     once: the reference names (name t = ref_names[ref_off[t], ref_off[t + 1])) and the colour, copied to HBM
+ *     l2r_bed_lines     one batch: *n_lines = lines, *n_bytes = bytes of its text, which stays in HBM until the next call.  The columns may
+ *                       be a window of larger ones: cig_off[0] and name_off[0] need not be 0 (names as in l2r_name_records, 0..254 bytes).
+ *                       The texts of consecutive batches, concatenated, are the text of the whole input however the records were cut.  A
+ *                       batch whose summed line bounds (below) reach 2^32 - 64 bytes fails with an error of its own, before any launch
+ *     l2r_bed_text_out  the text of the last l2r_bed_lines; cap < n_bytes fails and writes nothing, as does a call behind a failed batch
+ *     l2r_bed_cut       no GPU, no context: *n_take = how many records from `first` one batch takes -- at most max_records, their summed
+ *                       bounds below max_bytes, but always one.  A line's bound is made of its name length, its reference name's length,
+ *                       the colour length and its operation count alone and is never below the line's bytes.  One record whose bound
+ *                       alone reaches 2^32 - 64 is an error.  Only flag, tid, cig_off and name_off of the records are read
+ * On the device (csrc/l2r_bed.hip.h): k_bed_measure -- per record the bytes of its line, its block count and span; one thread per record,
+ * or one wave per record where the batch has more than 32 operations per record on average (L2R_BED_WAVE=0|1 forces one) -- k_scan_u32
+ * over the lengths, and k_bed_write: one workgroup per L2R_BED_TILE records composes their text in an LDS image of L2R_BED_LDS_BYTES
+ * and streams it out in aligned 16-byte stores; a tile with more text writes its lines directly.  The text buffer has 64 bytes of slack;
+ * with L2R_CHECK=1 they are filled with a pattern in front of k_bed_write and looked at behind it.  L2R_BED_ROUTE=host (tests, the
+ * comparator of tools/bench_bed.py): the exact host routine of csrc/l2r_bedplan.hip.h, same bytes, same errors.
+ * l2r_bed_stats, of the last l2r_bed_lines: out[0] records, [1] lines, [2] bytes, [3] form of k_bed_measure (0 thread, 1 wave), [4] tiles
+ * on the LDS path, [5] tiles on the direct path, [6] route (0 device, 1 host), [7] 1 where the guard bytes are intact or were not
+ * checked; with L2R_BED_TIMING=1 in the environment (every launch is then waited for) device milliseconds of [8] k_bed_measure
+ * [9] k_scan_u32 [10] k_bed_write; n = words of out (up to 11). */
+#define L2R_BED_TILE 128                /* records, and threads, of one workgroup of k_bed_write */
+#define L2R_BED_LDS_BYTES 32768         /* bytes of a tile's text its LDS image holds; a tile with more takes the direct path */
+typedef struct { int64_t n, n_cigar; const uint16_t *flag; const int32_t *tid, *pos; const uint8_t *mapq;
+                 const int64_t *cig_off; const uint32_t *cig;           /* len << 4 | op */
+                 const int64_t *name_off; const uint8_t *names; } l2r_bed_records;   /* names as in l2r_name_records */
+typedef struct { int32_t n_ref; const int64_t *ref_off; const uint8_t *ref_names; int32_t color_len; uint8_t color[12]; } l2r_bed_params;
+int          l2r_bed_begin(l2r_ctx *ctx, const l2r_bed_params *prm);                         /* reference names and colour to HBM, once */
+int          l2r_bed_lines(l2r_ctx *ctx, const l2r_bed_records *recs, int64_t *n_lines, int64_t *n_bytes);   /* one batch; the text stays in HBM */
+int          l2r_bed_text_out(l2r_ctx *ctx, uint8_t *text, int64_t cap);                     /* of the last l2r_bed_lines; cap < n_bytes fails and writes nothing */
+int          l2r_bed_cut(const l2r_bed_records *recs, const l2r_bed_params *prm, int64_t first, int64_t max_records, int64_t max_bytes, int64_t *n_take);  /* no GPU */
+int          l2r_bed_stats(l2r_ctx *ctx, double *out, int n);
+
 #ifdef __cplusplus
 }
 #endif

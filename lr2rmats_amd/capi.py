@@ -37,6 +37,7 @@ EXPORTS = [
     "l2r_sort_order", "l2r_sort_stats",
     "l2r_name_order", "l2r_name_stats",
     "l2r_gtf_order", "l2r_gtf_rows_out", "l2r_gtf_stats", "l2r_gtf_check",
+    "l2r_bed_begin", "l2r_bed_lines", "l2r_bed_text_out", "l2r_bed_cut", "l2r_bed_stats",
 ]
 SJ_E_UNKNOWN_TID = -3
 
@@ -147,6 +148,15 @@ class CGtfRows(C.Structure):
     _fields_ = [("cap", C.c_int64), ("n", C.c_int64), ("start", C.c_void_p), ("len", C.c_void_p), ("line", C.c_void_p)]
 
 
+class CBedRecords(C.Structure):
+    _fields_ = [("n", C.c_int64), ("n_cigar", C.c_int64), ("flag", C.c_void_p), ("tid", C.c_void_p), ("pos", C.c_void_p), ("mapq", C.c_void_p),
+                ("cig_off", C.c_void_p), ("cig", C.c_void_p), ("name_off", C.c_void_p), ("names", C.c_void_p)]
+
+
+class CBedParams(C.Structure):
+    _fields_ = [("n_ref", C.c_int32), ("ref_off", C.c_void_p), ("ref_names", C.c_void_p), ("color_len", C.c_int32), ("color", C.c_uint8 * 12)]
+
+
 class CTiming(C.Structure):
     _fields_ = [("stage_ms", C.c_float * N_STAGES), ("total_ms", C.c_float), ("iters", C.c_int32)]
 
@@ -227,6 +237,11 @@ def load_library():
         lib.l2r_gtf_rows_out.argtypes = [C.c_void_p, C.c_void_p]
         lib.l2r_gtf_stats.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
         lib.l2r_gtf_check.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        lib.l2r_bed_begin.argtypes = [C.c_void_p, C.c_void_p]
+        lib.l2r_bed_lines.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        lib.l2r_bed_text_out.argtypes = [C.c_void_p, C.c_void_p, C.c_int64]
+        lib.l2r_bed_cut.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_void_p]
+        lib.l2r_bed_stats.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
         _lib = lib
     return _lib
 
@@ -329,6 +344,46 @@ def sort_keys(flag, tid, pos) -> np.ndarray:
     t = np.where(t < 0, 0x7fffffff, t).astype(np.uint64)
     p = (np.asarray(pos, np.int64) + 1).astype(np.uint32).astype(np.uint64)
     return (t << np.uint64(33)) | (p << np.uint64(1)) | ((np.asarray(flag, np.uint64) >> np.uint64(4)) & np.uint64(1))
+
+
+BED_STAT_NAMES = ["records", "lines", "bytes", "wave_form", "tiles_lds", "tiles_direct", "route", "guard_intact", "k_bed_measure", "k_scan_u32", "k_bed_write"]
+
+
+def _bed_params(ref_names, color):
+    """(CBedParams, arrays to keep alive) of a sequence of reference names (byte strings) and a colour string."""
+    color = bytes(color)
+    if len(color) > 12:
+        raise ValueError("a colour of %d bytes (at most 12)" % len(color))
+    off, blob = pack_names(ref_names)
+    keep = blob if blob.size else np.zeros(1, np.uint8)
+    return CBedParams(len(off) - 1, off.ctypes.data, keep.ctypes.data, len(color), (C.c_uint8 * 12)(*color)), (off, keep)
+
+
+def _bed_records(flag, tid, pos, mapq, cigars, names):
+    """(CBedRecords, arrays to keep alive).  ``cigars``: (cig_off int64 [n + 1], cig uint32); ``names``: byte strings, or (name_off, blob).
+    The offset columns may be windows of larger ones (they need not start at 0)."""
+    cig_off, cig = cigars
+    name_off, blob = names if isinstance(names, tuple) else pack_names(names)
+    a = [np.ascontiguousarray(flag, np.uint16), np.ascontiguousarray(tid, np.int32), np.ascontiguousarray(pos, np.int32), np.ascontiguousarray(mapq, np.uint8),
+         np.ascontiguousarray(cig_off, np.int64), np.ascontiguousarray(cig, np.uint32), np.ascontiguousarray(name_off, np.int64), np.ascontiguousarray(blob, np.uint8)]
+    n, n_cigar = int(a[0].shape[0]), int(a[5].shape[0])
+    for k in (5, 7):
+        if a[k].size == 0:
+            a[k] = np.zeros(1, a[k].dtype)
+    return CBedRecords(n, n_cigar, *[x.ctypes.data for x in a]), a
+
+
+def bed_cut(flag, tid, cigars, names, ref_names, first: int, max_records: int, max_bytes: int, color=b"255,0,0") -> int:
+    """l2r_bed_cut (no context, no GPU): how many records from ``first`` one batch of at most ``max_records`` records and ``max_bytes``
+    summed line bounds takes (always one).  A record whose bound alone is beyond one batch raises RuntimeError."""
+    lib = load_library()
+    n = len(flag)
+    recs, keep = _bed_records(flag, tid, np.zeros(n, np.int32), np.zeros(n, np.uint8), cigars, names)
+    prm, keep2 = _bed_params(ref_names, color)
+    take = C.c_int64(0)
+    if lib.l2r_bed_cut(C.byref(recs), C.byref(prm), first, max_records, max_bytes, C.byref(take)):
+        raise RuntimeError(lib.l2r_last_error().decode())
+    return int(take.value)
 
 
 FUSION_STAT_NAMES = ["wave_form", "k_fusion_seg", "k_fusion_select", "k_filter_score", "k_filter_select"]
@@ -597,6 +652,35 @@ class Engine:
         out = np.zeros(len(GTF_STAT_NAMES), np.float64)
         self._chk(self.lib.l2r_gtf_stats(self.ctx, out.ctypes.data, len(out)))
         return {k: float(v) for k, v in zip(GTF_STAT_NAMES, out)}
+
+    # ---- `bam2bed` (include/lr2rmats_hip.h: l2r_bed_begin / _lines / _text_out / _stats)
+    def bed_begin(self, ref_names, color=b"255,0,0") -> None:
+        """The reference names (byte strings, by tid) and the colour string of the lines that follow."""
+        prm, _keep = _bed_params(ref_names, color)
+        self._chk(self.lib.l2r_bed_begin(self.ctx, C.byref(prm)))
+
+    def bed_lines(self, flag, tid, pos, mapq, cigars, names) -> bytes:
+        """The BED12 text of one batch of records: ``cigars`` = (cig_off int64 [n + 1], cig uint32 words len << 4 | op), ``names`` = byte
+        strings or (name_off, blob).  A record outside the domain raises L2RError naming the smallest such record and the kind."""
+        recs, _keep = _bed_records(flag, tid, pos, mapq, cigars, names)
+        n_lines, n_bytes = C.c_int64(0), C.c_int64(0)
+        self._chk(self.lib.l2r_bed_lines(self.ctx, C.byref(recs), C.byref(n_lines), C.byref(n_bytes)))
+        self.bed_n_lines = int(n_lines.value)
+        return self.bed_text_out(int(n_bytes.value))
+
+    def bed_text_out(self, cap: int) -> bytes:
+        """l2r_bed_text_out into room for ``cap`` bytes: the text of the last bed_lines (L2RError where that failed or cap is too small)."""
+        buf = np.zeros(max(int(cap), 1), np.uint8)
+        self._chk(self.lib.l2r_bed_text_out(self.ctx, buf.ctypes.data, int(cap)))
+        n = int(self.bed_stats()["bytes"])
+        return buf[:n].tobytes()
+
+    def bed_stats(self) -> dict:
+        """l2r_bed_stats of the last bed_lines: records, lines, bytes, the form of k_bed_measure (0 thread, 1 wave), tiles on the LDS and on
+        the direct path, route (0 device, 1 host), guard_intact, and with L2R_BED_TIMING=1 device milliseconds per kernel."""
+        out = np.zeros(len(BED_STAT_NAMES), np.float64)
+        self._chk(self.lib.l2r_bed_stats(self.ctx, out.ctypes.data, len(out)))
+        return {k: float(v) for k, v in zip(BED_STAT_NAMES, out)}
 
     def set_annotation_cache(self, directory) -> None:
         """Keep the annotation tables on disk under ``directory`` (None: off); see include/lr2rmats_hip.h."""

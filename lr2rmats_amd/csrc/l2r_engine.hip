@@ -26,10 +26,12 @@
 #include "l2r_sort.hip.h"
 #include "l2r_names.hip.h"
 #include "l2r_gtf.hip.h"
+#include "l2r_bed.hip.h"
 #include "l2r_plan.hip.h"
 #include "l2r_tables.hip.h"
 #include "l2r_nameorder.hip.h"
 #include "l2r_gtforder.hip.h"
+#include "l2r_bedplan.hip.h"
 
 using namespace l2r;
 
@@ -172,6 +174,25 @@ struct GtfState {
     std::vector<uint64_t> res_start; std::vector<uint32_t> res_len, res_line;        // the rows of the last call, in the order
     StageTimer clk;
     double stats[17] = {0};                             // l2r_gtf_stats
+};
+
+// `bam2bed` (l2r_bed.hip.h): the reference names and the colour of l2r_bed_begin, the columns of one batch, what k_bed_measure leaves per
+// record, and the text of the last l2r_bed_lines (in HBM, or on the host where the host route made it) until l2r_bed_text_out fetches it.
+// The buffers belong to the context, grow on demand and are used again by the next batch.
+struct BedState {
+    bool begun = false;
+    l2r_bed_params prm{};                               // ref_off / ref_names point into the two vectors
+    std::vector<int64_t> h_ref_off; std::vector<uint8_t> h_ref_names;
+    DevBuf<int64_t> ref_off; DevBuf<uint8_t> ref_names;
+    DevBuf<uint16_t> flag; DevBuf<int32_t> tid, pos; DevBuf<uint8_t> mapq, names; DevBuf<int64_t> cig_off, name_off; DevBuf<uint32_t> cig;      // one batch
+    DevBuf<uint32_t> off, n_blocks, span, size_len;     // per record; off: the line lengths, scanned in place (n + 1 words)
+    DevBuf<uint32_t> word;                              // BEDW_*
+    DevBuf<uint4> text;                                 // the text, 16-byte aligned, BED_SLACK bytes behind it
+    bool have_text = false, text_on_host = false;
+    int64_t n_bytes = 0;
+    std::vector<uint8_t> host_text;                     // the host route's text
+    StageTimer clk;
+    double stats[11] = {0};                             // l2r_bed_stats
 };
 
 // What l2r_sync has learned from the counters of a completed run of the tile path (fetch_run_facts): a later run of the same inputs,
@@ -326,6 +347,7 @@ struct l2r_ctx {
     SortState sort;                         // `sort`, `filter -S`
     NameState name;                         // `sort -n`, `filter -N`, `fusion -N`
     GtfState gtf;                           // `sort-gtf`
+    BedState bed;                           // `bam2bed`
 };
 
 // A launch (or a group of launches) on the context stream
@@ -2604,6 +2626,156 @@ int l2r_gtf_check(const l2r_gtf_text *t, int64_t *line, int64_t *counts)
     if (counts) { counts[0] = o.n_lines; counts[1] = (int64_t)o.start.size(); counts[2] = o.n_tx; counts[3] = o.n_names; }
     return o.descent_line ? 1 : 0;
 }
+
+// ---------------------------------------------------------------------------------------------- bam2bed
+// slots of l2r_bed_stats
+enum { BEDS_RECORDS = 0, BEDS_LINES, BEDS_BYTES, BEDS_WAVE, BEDS_TILES_LDS, BEDS_TILES_DIRECT, BEDS_ROUTE, BEDS_GUARD, BEDS_K_MEASURE, BEDS_K_SCAN, BEDS_K_WRITE, BEDS_N };
+static_assert(BEDS_N == sizeof(BedState::stats) / sizeof(double) && BEDS_K_MEASURE == 8, "l2r_bed_stats: the words of include/lr2rmats_hip.h");
+// words of BedState::word
+enum { BEDW_BAD = 0, BEDW_TOTAL, BEDW_DIRECT, BEDW_N };
+constexpr size_t BED_SLACK = 64;                        // bytes behind the text; L2R_CHECK: a pattern k_bed_write must leave alone
+constexpr uint8_t BED_GUARD_BYTE = 0xa5;
+
+int l2r_bed_begin(l2r_ctx *c, const l2r_bed_params *p)
+{
+    if (!c) return fail(-1, "[l2r_bed_begin] null argument");
+    BedState &m = c->bed;
+    m.begun = false; m.have_text = false;
+    {   std::string msg;
+        if (bed_check_params(p, msg)) return fail(-1, "%s", msg.c_str()); }
+    const size_t R = (size_t)p->n_ref, NB = R ? (size_t)p->ref_off[R] : 0;
+    m.h_ref_off.assign(R + 1, 0);
+    for (size_t k = 0; k <= R && R; ++k) m.h_ref_off[k] = p->ref_off[k];
+    m.h_ref_names.assign(NB + 1, 0);
+    if (NB) memcpy(m.h_ref_names.data(), p->ref_names, NB);
+    m.prm = *p;
+    m.prm.ref_off = m.h_ref_off.data(); m.prm.ref_names = m.h_ref_names.data();
+    HIP_TRY(hipSetDevice(c->device));
+    int rc;
+    if ((rc = put_dev(c, m.ref_off, m.h_ref_off)) || (rc = put_dev(c, m.ref_names, m.h_ref_names))) return rc;
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    m.begun = true;
+    return 0;
+}
+
+int l2r_bed_lines(l2r_ctx *c, const l2r_bed_records *r, int64_t *n_lines, int64_t *n_bytes)
+{
+    if (!c || !n_lines || !n_bytes) return fail(-1, "[l2r_bed_lines] null argument");
+    BedState &m = c->bed;
+    for (double &v : m.stats) v = 0;
+    m.have_text = false; m.text_on_host = false; m.n_bytes = 0; m.host_text.clear();
+    if (!m.begun) return fail(-1, "[l2r_bed_lines] no l2r_bed_begin in front");
+    {   std::string msg;
+        if (bed_check_records(r, msg)) return fail(-1, "%s", msg.c_str()); }
+    *n_lines = 0; *n_bytes = 0;
+    const size_t N = (size_t)r->n;
+    m.stats[BEDS_RECORDS] = (double)N; m.stats[BEDS_GUARD] = 1;
+    const char *route = getenv("L2R_BED_ROUTE");
+    const bool on_host = route && strcmp(route, "host") == 0;
+    m.stats[BEDS_ROUTE] = on_host ? 1 : 0;
+    if (N == 0) { m.have_text = true; m.text_on_host = true; return 0; }
+    if (N > (size_t)0xffffffffu - 1u) return fail(-1, "[l2r_bed_lines] a batch of %zu records (at most 2^32 - 2)", N);
+    if (bed_batch_bound(r, &m.prm) >= BED_BATCH_BYTES)
+        return fail(-1, "[l2r_bed_lines] the batch: the summed bounds of its %zu lines reach 2^32 - 64 bytes (cut it with l2r_bed_cut)", N);
+    int64_t lines = 0;
+    for (size_t i = 0; i < N; ++i) lines += (r->flag[i] & 4u) ? 0 : 1;
+    if (on_host) {
+        std::string msg;
+        if (bed_lines_host(r, &m.prm, m.host_text, nullptr, msg)) { m.host_text.clear(); return fail(-1, "%s", msg.c_str()); }
+        m.have_text = true; m.text_on_host = true; m.n_bytes = (int64_t)m.host_text.size();
+        m.stats[BEDS_LINES] = (double)lines; m.stats[BEDS_BYTES] = (double)m.n_bytes;
+        *n_lines = lines; *n_bytes = m.n_bytes;
+        return 0;
+    }
+    HIP_TRY(hipSetDevice(c->device));
+    int rc;
+    if ((rc = m.clk.begin(env_on("L2R_BED_TIMING"), c->check_stages))) return rc;
+    const int64_t cig_base = r->cig_off[0], name_base = r->name_off[0];
+    const size_t n_cig = (size_t)(r->cig_off[N] - cig_base), n_name = (size_t)(r->name_off[N] - name_base);
+    // one wave per record where the CIGARs are long (the bound of l2r_upload_reads' wide_cigar); L2R_BED_WAVE=0|1: tests, tools/bench_bed.py
+    bool wave = (double)n_cig / (double)N > 32.0;
+    if (const char *e = getenv("L2R_BED_WAVE")) wave = atoi(e) != 0;
+    m.stats[BEDS_WAVE] = wave ? 1 : 0;
+    if ((rc = to_dev(c, m.flag, r->flag, N)) || (rc = to_dev(c, m.tid, r->tid, N)) || (rc = to_dev(c, m.pos, r->pos, N)) || (rc = to_dev(c, m.mapq, r->mapq, N)) ||
+        (rc = to_dev(c, m.cig_off, r->cig_off, N + 1)) || (rc = to_dev(c, m.cig, n_cig ? r->cig + cig_base : nullptr, n_cig)) ||
+        (rc = to_dev(c, m.name_off, r->name_off, N + 1)) || (rc = to_dev(c, m.names, n_name ? r->names + name_base : nullptr, n_name)) ||
+        m.off.ensure(N + 1) || m.n_blocks.ensure(N) || m.span.ensure(N) || m.size_len.ensure(N) || m.word.ensure(BEDW_N)) rc = rc ? rc : -2;
+    if (rc) { (void)hipStreamSynchronize(c->stream); return rc; }      // (the columns are the caller's)
+    HIP_TRY(hipMemsetAsync(m.word.p, 0, BEDW_N * sizeof(uint32_t), c->stream));
+    HIP_TRY(hipMemsetAsync(m.word.p + BEDW_BAD, 0xff, sizeof(uint32_t), c->stream));
+    BedIn in{};
+    in.n = (int64_t)N; in.flag = m.flag.p; in.tid = m.tid.p; in.pos = m.pos.p; in.mapq = m.mapq.p;
+    in.cig_off = m.cig_off.p; in.cig = m.cig.p; in.cig_base = cig_base; in.name_off = m.name_off.p; in.names = m.names.p; in.name_base = name_base;
+    in.n_ref = m.prm.n_ref; in.ref_off = m.ref_off.p; in.ref_names = m.ref_names.p;
+    in.color_len = (uint32_t)m.prm.color_len;
+    {   uint32_t w[3] = {0, 0, 0};
+        memcpy(w, m.prm.color, 12);
+        in.color_w0 = w[0]; in.color_w1 = w[1]; in.color_w2 = w[2]; }
+    const BedMeasure meas{m.off.p, m.n_blocks.p, m.span.p, m.size_len.p};
+    rc = m.clk.launch(c, &m.stats[BEDS_K_MEASURE], [&] {
+        const dim3 grid((unsigned)(((wave ? N * 64 : N) + 255) / 256));
+        if (wave) hipLaunchKernelGGL(k_bed_measure<true>, grid, dim3(256), 0, c->stream, in, meas, m.word.p + BEDW_BAD);
+        else hipLaunchKernelGGL(k_bed_measure<false>, grid, dim3(256), 0, c->stream, in, meas, m.word.p + BEDW_BAD);
+    });
+    if (!rc) rc = m.clk.launch(c, &m.stats[BEDS_K_SCAN], [&] { scan_u32(c, m.off.p, (int64_t)N, m.word.p + BEDW_TOTAL); });
+    uint32_t w[BEDW_N] = {0, 0, 0};
+    hipError_t e = rc ? hipSuccess : hipMemcpyAsync(w, m.word.p, sizeof w, hipMemcpyDeviceToHost, c->stream);
+    const hipError_t sync = hipStreamSynchronize(c->stream);
+    if (rc) return rc;
+    if (e == hipSuccess) e = sync;
+    if (e != hipSuccess) return fail(-2, "[l2r_bed_lines] %s", hipGetErrorString(e));
+    if (w[BEDW_BAD] != 0xffffffffu) {
+        std::string msg;
+        if ((size_t)w[BEDW_BAD] >= N || bed_record_error(r, &m.prm, (int64_t)w[BEDW_BAD], msg) == BED_OK) return fail(-2, "[l2r_bed_lines] the device names record %u of %zu", w[BEDW_BAD], N);
+        return fail(-1, "%s", msg.c_str());
+    }
+    const size_t B = w[BEDW_TOTAL];
+    if ((uint64_t)B >= BED_BATCH_BYTES) return fail(-2, "[l2r_bed_lines] %zu bytes of text behind a bound below 2^32 - 64", B);
+    const unsigned n_tiles = (unsigned)((N + BED_TILE - 1) / BED_TILE);
+    if (m.text.ensure((B + BED_SLACK + 15) / 16)) return -2;
+    uint8_t *text8 = reinterpret_cast<uint8_t *>(m.text.p);
+    if (c->check_stages) HIP_TRY(hipMemsetAsync(text8 + B, BED_GUARD_BYTE, BED_SLACK, c->stream));
+    if (B && (rc = m.clk.launch(c, &m.stats[BEDS_K_WRITE], [&] {
+            hipLaunchKernelGGL(k_bed_write, dim3(n_tiles), dim3(BED_TILE), 0, c->stream, in, (const uint32_t *)m.off.p, (const uint32_t *)m.n_blocks.p, (const uint32_t *)m.span.p,
+                               (const uint32_t *)m.size_len.p, text8, m.word.p + BEDW_DIRECT);
+        }))) { (void)hipStreamSynchronize(c->stream); return rc; }
+    uint8_t guard[BED_SLACK];
+    uint32_t n_direct = 0;
+    HIP_TRY(hipMemcpyAsync(&n_direct, m.word.p + BEDW_DIRECT, sizeof n_direct, hipMemcpyDeviceToHost, c->stream));
+    if (c->check_stages) HIP_TRY(hipMemcpyAsync(guard, text8 + B, BED_SLACK, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    if (c->check_stages) for (size_t k = 0; k < BED_SLACK; ++k) if (guard[k] != BED_GUARD_BYTE) m.stats[BEDS_GUARD] = 0;
+    if (n_direct > n_tiles) return fail(-2, "[l2r_bed_lines] %u direct tiles of %u", n_direct, n_tiles);
+    m.stats[BEDS_LINES] = (double)lines; m.stats[BEDS_BYTES] = (double)B;
+    m.stats[BEDS_TILES_DIRECT] = (double)n_direct; m.stats[BEDS_TILES_LDS] = (double)(n_tiles - n_direct);
+    m.have_text = true; m.n_bytes = (int64_t)B;
+    *n_lines = lines; *n_bytes = (int64_t)B;
+    return 0;
+}
+
+int l2r_bed_text_out(l2r_ctx *c, uint8_t *text, int64_t cap)
+{
+    if (!c) return fail(-1, "[l2r_bed_text_out] null argument");
+    const BedState &m = c->bed;
+    if (!m.have_text) return fail(-1, "[l2r_bed_text_out] no text: the last l2r_bed_lines failed, or none was made");
+    if (cap < m.n_bytes) return fail(-1, "[l2r_bed_text_out] room for %lld bytes, the last l2r_bed_lines left %lld", (long long)cap, (long long)m.n_bytes);
+    if (m.n_bytes == 0) return 0;
+    if (!text) return fail(-1, "[l2r_bed_text_out] null text");
+    if (m.text_on_host) { memcpy(text, m.host_text.data(), (size_t)m.n_bytes); return 0; }
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipMemcpyAsync(text, m.text.p, (size_t)m.n_bytes, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+int l2r_bed_cut(const l2r_bed_records *r, const l2r_bed_params *p, int64_t first, int64_t max_records, int64_t max_bytes, int64_t *n_take)
+{
+    std::string msg;
+    if (bed_cut(r, p, first, max_records, max_bytes, n_take, msg)) return fail(-1, "%s", msg.c_str());
+    return 0;
+}
+
+int l2r_bed_stats(l2r_ctx *c, double *out, int n) { return stats_out(c ? c->bed.stats : nullptr, BEDS_N, out, n, "l2r_bed_stats"); }
 
 }  // extern "C"
 

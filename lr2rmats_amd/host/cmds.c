@@ -1481,6 +1481,7 @@ int h_main(int argc, char **argv)
     if (strcmp(argv[0], "sort-check") == 0) return h_cmd_sort_check(argc, argv);
     if (strcmp(argv[0], "sort-gtf") == 0) return h_cmd_sort_gtf(argc, argv);
     if (strcmp(argv[0], "sort-gtf-check") == 0) return h_cmd_sort_gtf_check(argc, argv);
+    if (strcmp(argv[0], "bam2bed") == 0) return h_cmd_bam2bed(argc, argv);
     /* (diagnostics, no GPU: every record of a SAM / BAM file written out as BAM -- reader, encoder and BGZF writer of `filter`) */
     if (strcmp(argv[0], "records2bam") == 0 && argc == 3) return h_records_to_bam(argv[1], argv[2]) ? 1 : 0;
     /* (diagnostics, no GPU: the block ranges `world` ranks of a multi-process run would inflate of a BAM file, one line per rank:

@@ -136,6 +136,17 @@ int  h_gtf_write_rows(const uint8_t *text, int64_t n_bytes, int64_t n_rows, cons
 int  h_gtf_write_rows_path(const uint8_t *text, int64_t n_bytes, int64_t n_rows, const uint64_t *start, const uint32_t *len, const uint32_t *line, const char *path);
 int  h_gtf_sort_run(int n_files, char **fn, FILE *out, int64_t *counts);
 
+/* ---- `bam2bed` (bed.c): every mapped record as one BED12 line, the text composed by the engine (l2r_bed_lines, include/lr2rmats_hip.h).
+ * h_bed_color_ok (no GPU): 1 where the string is three decimal numbers 0..255 with commas between them and nothing else.
+ * h_bed_run: read (h_read_records), cut into batches (l2r_bed_cut: L2R_BED_BATCH records, default 1 Mi, and L2R_BED_TEXT_MAX bytes of
+ * summed line bounds, default 1 GiB), l2r_bed_lines on GPU 0 batch by batch, each batch's text written to `out` as it arrives.  color:
+ * NULL for "255,0,0".  counts (NULL, or 4 words): records, lines, bytes, batches.  1 with the engine's message and the record's number in
+ * the file on stderr where a record is outside the domain; 2 where the colour is none.  h_bed_run_path: the same into a file (-1: the
+ * file can not be written). */
+int  h_bed_color_ok(const char *s);
+int  h_bed_run(const char *in_fn, const char *color, FILE *out, int64_t *counts);
+int  h_bed_run_path(const char *in_fn, const char *color, const char *out_path, int64_t *counts);
+
 /* ---- `fusion` (fusion.c).  h_fusion_groups (no GPU): the runs of consecutive MAPPED records with one read name -- rows[k] = record
  * of row k, group g = rows [group_off[g], group_off[g + 1]), rlen[g] = query length (M I S = X) of its first record, taken from
  * `qlen` (one word per record, as l2r_fusion_segments leaves it) or, with qlen NULL, from that record's CIGAR; the three
@@ -255,6 +266,7 @@ int h_cmd_sort(int argc, char **argv);
 int h_cmd_sort_check(int argc, char **argv);            /* no GPU; 0 sorted, 1 not, 2 usage */
 int h_cmd_sort_gtf(int argc, char **argv);              /* 0, 1 on a domain error (the engine's message), 2 usage */
 int h_cmd_sort_gtf_check(int argc, char **argv);        /* no GPU; 0 in order, 1 not, 2 usage */
+int h_cmd_bam2bed(int argc, char **argv);               /* 0, 1 on a domain error (the engine's message), 2 usage */
 int h_main(int argc, char **argv);
 
 /* ---- staged form of update-gtf, used by the CLI itself and by the one-process-per-GPU driver

@@ -99,6 +99,10 @@ def load_library():
         lib.h_name_grouped.restype = C.c_int64
         lib.h_gtf_write_rows_path.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_char_p]
         lib.h_gtf_write_rows_path.restype = C.c_int
+        lib.h_bed_run_path.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.POINTER(C.c_int64)]
+        lib.h_bed_run_path.restype = C.c_int
+        lib.h_bed_color_ok.argtypes = [C.c_char_p]
+        lib.h_bed_color_ok.restype = C.c_int
         _lib = lib
     return _lib
 
@@ -279,6 +283,20 @@ def gtf_write_rows(text: bytes, start, length, line, path: str) -> None:
         raise OSError("h_gtf_write_rows: a row beyond the text, or %s can not be written" % path)
 
 
+# ---- `bam2bed` (host/bed.c)
+
+def bed_color_ok(text: str) -> bool:
+    """Whether ``text`` is a colour of `bam2bed -c`: three decimal numbers 0..255 with commas and nothing else (no GPU)."""
+    return bool(load_library().h_bed_color_ok(text.encode()))
+
+
+def bed_run(in_path: str, out_path: str, color: str = "255,0,0"):
+    """`lr2rmats bam2bed -o out_path -c color in_path` in this process (h_bed_run; needs a GPU): (rc, [records, lines, bytes, batches])."""
+    counts = (C.c_int64 * 4)()
+    rc = load_library().h_bed_run_path(in_path.encode(), color.encode(), out_path.encode(), counts)
+    return int(rc), [int(v) for v in counts]
+
+
 class Job:
     """One ``update-gtf`` invocation: argv = ["update-gtf", options..., in.bam, old.gtf]."""
 
@@ -419,7 +437,7 @@ def records_to_bam(in_path: str, out_path: str) -> int:
 
 
 def run_cli(args, stdout_path=None, cwd=None, env=None) -> subprocess.CompletedProcess:
-    """Run the C binary ``lr2rmats <args>`` (needs a GPU for update-gtf / bam2gtf / unique-gtf -m b / filter / bam2sj / sjtab / fusion / sort).
+    """Run the C binary ``lr2rmats <args>`` (needs a GPU for update-gtf / bam2gtf / unique-gtf -m b / filter / bam2sj / sjtab / fusion / sort / bam2bed).
     ``env``: extra environment variables (L2R_CHUNK_READS, L2R_ROUTE, L2R_THREADS ...)."""
     full_env = None
     if env:
