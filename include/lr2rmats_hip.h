@@ -546,6 +546,34 @@ int          l2r_bed_text_out(l2r_ctx *ctx, uint8_t *text, int64_t cap);        
 int          l2r_bed_cut(const l2r_bed_records *recs, const l2r_bed_params *prm, int64_t first, int64_t max_records, int64_t max_bytes, int64_t *n_take);  /* no GPU */
 int          l2r_bed_stats(l2r_ctx *ctx, double *out, int n);
 
+/* ---- `unique-gtf` (host/tail.c, host/cmds.c): merge_trans (src/update_gtf.c:98-163, check_iden src/gtf.c:54-92) over a list of
+ * transcripts, exact to the host loop.  Transcript i has tid[i], strand rev[i] and the exons [ex_off[i], ex_off[i + 1]) of xs / xe
+ * (1-based closed, ascending); its start is xs[ex_off[i]], its end xe[ex_off[i + 1] - 1].  The rule, stated once in
+ * csrc/l2r_uniqplan.hip.h: every transcript in input order is offered to a growing list, which is scanned newest entry first; an entry
+ * T stops the scan where t.tid > T.tid or t.start > T.end (the offer is then pushed as a new entry with coverage 1), is skipped under -s
+ * where the strands differ, and otherwise is judged: single exon against single exon by -D on both ends and the overlap fraction >= -f
+ * (a hit: coverage + 1, the entry's start lowered and end raised to the offer's), multi against multi by check_iden (identical: the same
+ * mutation; the shorter chain contained in the longer: merged, nothing changes), mixed exon counts and everything else: skipped.  An
+ * offer that reaches the front of the list is pushed.
+ * Arguments that fail the call (-1): n of 2^31 or more, ex_off that does not start at 0 or descends, a transcript without exons or with
+ * 2^31 or more, tid below -1, a negative coordinate.
+ *     l2r_uniq_merge   the verdicts of all n offers; *n_unique = entries of the list.  The results stay with the context
+ *     l2r_uniq_out     of the last l2r_uniq_merge: merged[i] = 1 where offer i merged, uniq_of[i] = the rank of the entry it created or
+ *                      merged into; per entry, in list order, u_src (the offer that created it), u_start / u_end (first start and last
+ *                      end as the hits left them) and u_cov.  Any pointer may be null: that array is not written
+ * On the device (csrc/l2r_uniq.hip.h) where (tid, start) does not descend over the input: a transcript that starts beyond every earlier
+ * end on its chromosome heads a cluster, clusters are independent, and one wave merges one cluster with its lanes on the list entries.
+ * Other input, and every input under L2R_UNIQ_ROUTE=host, takes the exact host routine uniq_host: same arrays.
+ * l2r_uniq_stats, of the last l2r_uniq_merge: out[0] rows, [1] unique, [2] clusters, [3] offers of the largest cluster (both 0 where the
+ * input is not in order), [4] route (0 device, 1 host), [5] hits identical, [6] hits contained, [7] hits single, [8] end extensions;
+ * with L2R_SORT_TIMING=1 in the environment device milliseconds of [9] k_uniq_heads + the cluster cut, [10] k_uniq_merge, [11] the
+ * scan of the list lengths + k_uniq_take; n = words of out (up to 12). */
+#define L2R_UNIQ_PMAX_TILE 256          /* transcripts of one tile of the prefix maximum behind the cluster cut */
+typedef struct { int64_t n; const int32_t *tid; const uint8_t *rev; const int64_t *ex_off /* n + 1 */; const int32_t *xs, *xe; } l2r_uniq_trans;
+int          l2r_uniq_merge(l2r_ctx *ctx, const l2r_params *prm, const l2r_uniq_trans *trans, int64_t *n_unique);   /* results stay with the context */
+int          l2r_uniq_out(l2r_ctx *ctx, uint8_t *merged /* n */, int32_t *uniq_of /* n */, int32_t *u_src, int32_t *u_start, int32_t *u_end, int32_t *u_cov /* n_unique each */);
+int          l2r_uniq_stats(l2r_ctx *ctx, double *out, int n);
+
 #ifdef __cplusplus
 }
 #endif

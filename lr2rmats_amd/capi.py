@@ -38,6 +38,7 @@ EXPORTS = [
     "l2r_name_order", "l2r_name_stats",
     "l2r_gtf_order", "l2r_gtf_rows_out", "l2r_gtf_stats", "l2r_gtf_check",
     "l2r_bed_begin", "l2r_bed_lines", "l2r_bed_text_out", "l2r_bed_cut", "l2r_bed_stats",
+    "l2r_uniq_merge", "l2r_uniq_out", "l2r_uniq_stats",
 ]
 SJ_E_UNKNOWN_TID = -3
 
@@ -157,6 +158,10 @@ class CBedParams(C.Structure):
     _fields_ = [("n_ref", C.c_int32), ("ref_off", C.c_void_p), ("ref_names", C.c_void_p), ("color_len", C.c_int32), ("color", C.c_uint8 * 12)]
 
 
+class CUniqTrans(C.Structure):
+    _fields_ = [("n", C.c_int64), ("tid", C.c_void_p), ("rev", C.c_void_p), ("ex_off", C.c_void_p), ("xs", C.c_void_p), ("xe", C.c_void_p)]
+
+
 class CTiming(C.Structure):
     _fields_ = [("stage_ms", C.c_float * N_STAGES), ("total_ms", C.c_float), ("iters", C.c_int32)]
 
@@ -242,6 +247,9 @@ def load_library():
         lib.l2r_bed_text_out.argtypes = [C.c_void_p, C.c_void_p, C.c_int64]
         lib.l2r_bed_cut.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_void_p]
         lib.l2r_bed_stats.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
+        lib.l2r_uniq_merge.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        lib.l2r_uniq_out.argtypes = [C.c_void_p] + [C.c_void_p] * 6
+        lib.l2r_uniq_stats.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
         _lib = lib
     return _lib
 
@@ -384,6 +392,10 @@ def bed_cut(flag, tid, cigars, names, ref_names, first: int, max_records: int, m
     if lib.l2r_bed_cut(C.byref(recs), C.byref(prm), first, max_records, max_bytes, C.byref(take)):
         raise RuntimeError(lib.l2r_last_error().decode())
     return int(take.value)
+
+
+UNIQ_STAT_NAMES = ["rows", "unique", "clusters", "largest_cluster", "route", "hits_identical", "hits_contained", "hits_single", "end_extensions",
+                   "k_uniq_heads + cluster cut", "k_uniq_merge", "k_scan_u32 (list lengths) + k_uniq_take"]
 
 
 FUSION_STAT_NAMES = ["wave_form", "k_fusion_seg", "k_fusion_select", "k_filter_score", "k_filter_select"]
@@ -681,6 +693,32 @@ class Engine:
         out = np.zeros(len(BED_STAT_NAMES), np.float64)
         self._chk(self.lib.l2r_bed_stats(self.ctx, out.ctypes.data, len(out)))
         return {k: float(v) for k, v in zip(BED_STAT_NAMES, out)}
+
+    # ---- `unique-gtf` (include/lr2rmats_hip.h: l2r_uniq_merge / _out / _stats)
+    def uniq_merge(self, tid, rev, ex_off, xs, xe, force_strand=0, ss_dis=0, end_dis=0x7fffffff, frac=0.8) -> dict:
+        """merge_trans over the transcripts (tid, rev, exons [ex_off[i], ex_off[i + 1]) of xs / xe) in input order: a dict of ``merged``,
+        ``uniq_of`` (per offer) and ``u_src``, ``u_start``, ``u_end``, ``u_cov`` (per list entry).  -s, -d, -D, -f as the command's."""
+        a = [np.ascontiguousarray(tid, np.int32), np.ascontiguousarray(rev, np.uint8), np.ascontiguousarray(ex_off, np.int64),
+             np.ascontiguousarray(xs, np.int32), np.ascontiguousarray(xe, np.int32)]
+        n = int(a[0].shape[0])
+        ptr = [x.ctypes.data if x.size else None for x in a]
+        trans = CUniqTrans(n, *ptr)
+        prm = Params(3, 3, 50, int(ss_dis), int(end_dis), 5, 0, 0, 1, int(force_strand), float(frac))
+        n_unique = C.c_int64(0)
+        self._chk(self.lib.l2r_uniq_merge(self.ctx, C.byref(prm), C.byref(trans), C.byref(n_unique)))
+        u = int(n_unique.value)
+        out = {"merged": np.zeros(n, np.uint8), "uniq_of": np.zeros(n, np.int32)}
+        for k in ("u_src", "u_start", "u_end", "u_cov"):
+            out[k] = np.zeros(u, np.int32)
+        self._chk(self.lib.l2r_uniq_out(self.ctx, *[out[k].ctypes.data if out[k].size else None for k in ("merged", "uniq_of", "u_src", "u_start", "u_end", "u_cov")]))
+        return out
+
+    def uniq_stats(self) -> dict:
+        """l2r_uniq_stats of the last uniq_merge: rows, unique, clusters, largest cluster, route (0 device, 1 host), hits by kind, end
+        extensions, and with L2R_SORT_TIMING=1 device milliseconds per kernel group."""
+        out = np.zeros(len(UNIQ_STAT_NAMES), np.float64)
+        self._chk(self.lib.l2r_uniq_stats(self.ctx, out.ctypes.data, len(out)))
+        return {k: float(v) for k, v in zip(UNIQ_STAT_NAMES, out)}
 
     def set_annotation_cache(self, directory) -> None:
         """Keep the annotation tables on disk under ``directory`` (None: off); see include/lr2rmats_hip.h."""

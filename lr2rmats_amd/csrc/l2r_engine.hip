@@ -27,6 +27,7 @@
 #include "l2r_names.hip.h"
 #include "l2r_gtf.hip.h"
 #include "l2r_bed.hip.h"
+#include "l2r_uniq.hip.h"
 #include "l2r_plan.hip.h"
 #include "l2r_tables.hip.h"
 #include "l2r_nameorder.hip.h"
@@ -195,6 +196,21 @@ struct BedState {
     double stats[11] = {0};                             // l2r_bed_stats
 };
 
+// `unique-gtf` (l2r_uniq.hip.h): the columns of the last l2r_uniq_merge, what its kernels leave, and its results -- in HBM, or in `host` where
+// uniq_host made them -- until l2r_uniq_out fetches them.  The buffers belong to the context and grow on demand.
+struct UniqState {
+    DevBuf<int32_t> tid, xs, xe; DevBuf<uint8_t> rev; DevBuf<int64_t> ex_off;      // the input
+    DevBuf<UniqRec> rec; DevBuf<uint64_t> tile_max;
+    DevBuf<uint32_t> head, first, len, word;            // head: flags, scanned in place (n + 1); len: list lengths, scanned in place; word: UQW_*
+    DevBuf<int32_t> l_src, l_start, l_end, l_cov;       // the clusters' lists
+    DevBuf<int32_t> uniq_of, u_src, u_start, u_end, u_cov; DevBuf<uint8_t> merged;
+    bool have = false, on_host = false;
+    int64_t n = 0, n_unique = 0;
+    UniqResult host;
+    StageTimer clk;
+    double stats[UQS_N] = {0};                          // l2r_uniq_stats
+};
+
 // What l2r_sync has learned from the counters of a completed run of the tile path (fetch_run_facts): a later run of the same inputs,
 // parameters and outputs sizes its list-driven launches by the counts and skips those whose list was empty.  One record, forgotten as a
 // whole wherever one of those changes (forget_list_state).  LC_*: the list counter a field is a copy of (l2r_kernels.hip.h).
@@ -348,6 +364,7 @@ struct l2r_ctx {
     NameState name;                         // `sort -n`, `filter -N`, `fusion -N`
     GtfState gtf;                           // `sort-gtf`
     BedState bed;                           // `bam2bed`
+    UniqState uniq;                         // `unique-gtf`
 };
 
 // A launch (or a group of launches) on the context stream
@@ -2776,6 +2793,120 @@ int l2r_bed_cut(const l2r_bed_records *r, const l2r_bed_params *p, int64_t first
 }
 
 int l2r_bed_stats(l2r_ctx *c, double *out, int n) { return stats_out(c ? c->bed.stats : nullptr, BEDS_N, out, n, "l2r_bed_stats"); }
+
+// ---------------------------------------------------------------------------------------------- unique-gtf
+static void uniq_on_host(UniqState &m, const l2r_uniq_trans *t, const UniqPrm &p, bool in_order)
+{
+    uniq_host(t, p, m.host);
+    m.on_host = true; m.have = true; m.n_unique = (int64_t)m.host.u_src.size();
+    m.stats[UQS_ROUTE] = 1; m.stats[UQS_UNIQUE] = (double)m.n_unique;
+    m.stats[UQS_IDENT] = (double)m.host.hits[0]; m.stats[UQS_CONTAINED] = (double)m.host.hits[1]; m.stats[UQS_SINGLE] = (double)m.host.hits[2];
+    m.stats[UQS_END_EXT] = (double)m.host.end_ext;
+    if (in_order) {
+        std::vector<uint8_t> head;
+        int64_t n_c = 0, big = 0;
+        uniq_clusters(t, head, &n_c, &big);
+        m.stats[UQS_CLUSTERS] = (double)n_c; m.stats[UQS_LARGEST] = (double)big;
+    }
+}
+
+int l2r_uniq_merge(l2r_ctx *c, const l2r_params *prm, const l2r_uniq_trans *t, int64_t *n_unique)
+{
+    if (!c || !prm || !n_unique) return fail(-1, "[l2r_uniq_merge] null argument");
+    UniqState &m = c->uniq;
+    for (double &v : m.stats) v = 0;
+    m.have = false; m.on_host = false; m.n = 0; m.n_unique = 0; m.host = UniqResult();
+    {   std::string msg;
+        if (uniq_check(t, msg)) return fail(-1, "%s", msg.c_str()); }
+    *n_unique = 0;
+    const size_t N = (size_t)t->n;
+    const UniqPrm p = uniq_prm(prm);
+    m.n = t->n; m.stats[UQS_ROWS] = (double)N;
+    const char *route = getenv("L2R_UNIQ_ROUTE");
+    const bool want_host = route && strcmp(route, "host") == 0;     // (tests, the comparator; the device route is the default: DESIGN section 12)
+    if (N == 0) { m.have = true; m.on_host = true; m.stats[UQS_ROUTE] = want_host ? 1 : 0; return 0; }
+    if (want_host) { uniq_on_host(m, t, p, uniq_in_order(t)); *n_unique = m.n_unique; return 0; }
+    HIP_TRY(hipSetDevice(c->device));
+    int rc;
+    if ((rc = m.clk.begin(env_on("L2R_SORT_TIMING"), c->check_stages))) return rc;
+    const size_t NX = (size_t)t->ex_off[N], n_tiles = (N + UNIQ_TILE - 1) / UNIQ_TILE;
+    if ((rc = to_dev(c, m.tid, t->tid, N)) || (rc = to_dev(c, m.rev, t->rev, N)) || (rc = to_dev(c, m.ex_off, t->ex_off, N + 1)) ||
+        (rc = to_dev(c, m.xs, t->xs, NX)) || (rc = to_dev(c, m.xe, t->xe, NX)) ||
+        m.rec.ensure(N) || m.tile_max.ensure(n_tiles) || m.head.ensure(N + 1) || m.first.ensure(N + 1) || m.len.ensure(N + 1) || m.word.ensure(UQW_N) ||
+        m.l_src.ensure(N) || m.l_start.ensure(N) || m.l_end.ensure(N) || m.l_cov.ensure(N) || m.uniq_of.ensure(N) || m.merged.ensure(N) ||
+        m.u_src.ensure(N) || m.u_start.ensure(N) || m.u_end.ensure(N) || m.u_cov.ensure(N)) rc = rc ? rc : -2;
+    if (rc) { (void)hipStreamSynchronize(c->stream); return rc; }      // (the columns are the caller's)
+    HIP_TRY(hipMemsetAsync(m.word.p, 0, UQW_N * sizeof(uint32_t), c->stream));
+    const UniqIn in{(int64_t)N, m.tid.p, m.rev.p, m.ex_off.p, m.xs.p, m.xe.p};
+    rc = m.clk.launch(c, &m.stats[UQS_K_CUT], [&] {
+        hipLaunchKernelGGL(k_uniq_heads, dim3((unsigned)n_tiles), dim3(UNIQ_TILE), 0, c->stream, in, m.rec.p, m.tile_max.p, m.word.p);
+        hipLaunchKernelGGL(k_uniq_pmax, dim3(1), dim3(1024), 0, c->stream, m.tile_max.p, (int64_t)n_tiles);
+        hipLaunchKernelGGL(k_uniq_cut, dim3((unsigned)n_tiles), dim3(UNIQ_TILE), 0, c->stream, (int64_t)N, (const int32_t *)m.tid.p, (const UniqRec *)m.rec.p,
+                           (const uint64_t *)m.tile_max.p, m.head.p);
+        scan_u32(c, m.head.p, (int64_t)N, m.word.p + UQW_CLUSTERS);
+        hipLaunchKernelGGL(k_uniq_firsts, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, c->stream, (int64_t)N, (const uint32_t *)m.head.p, m.first.p);
+    });
+    uint32_t w[UQW_N] = {0};
+    hipError_t e = rc ? hipSuccess : hipMemcpyAsync(w, m.word.p, sizeof w, hipMemcpyDeviceToHost, c->stream);
+    hipError_t sync = hipStreamSynchronize(c->stream);
+    if (rc) return rc;
+    if (e == hipSuccess) e = sync;
+    if (e != hipSuccess) return fail(-2, "[l2r_uniq_merge] %s", hipGetErrorString(e));
+    if (w[UQW_UNSORTED]) {                              // (tid, start) descends somewhere: the exact host routine
+        for (int k = UQS_K_CUT; k < UQS_N; ++k) m.stats[k] = 0;
+        uniq_on_host(m, t, p, false);
+        *n_unique = m.n_unique;
+        return 0;
+    }
+    const uint32_t C = w[UQW_CLUSTERS];
+    if (C == 0 || (size_t)C > N) return fail(-2, "[l2r_uniq_merge] %u clusters of %zu transcripts", C, N);
+    const UniqList L{m.l_src.p, m.l_start.p, m.l_end.p, m.l_cov.p};
+    rc = m.clk.launch(c, &m.stats[UQS_K_MERGE], [&] {
+        hipLaunchKernelGGL(k_uniq_merge, dim3((C + UNIQ_WAVES - 1) / UNIQ_WAVES), dim3(UNIQ_WAVES * 64), 0, c->stream, in, (const UniqRec *)m.rec.p, (const uint32_t *)m.first.p, C, p, L,
+                           m.len.p, m.merged.p, m.uniq_of.p, m.word.p);
+    });
+    if (!rc) rc = m.clk.launch(c, &m.stats[UQS_K_TAKE], [&] {
+        scan_u32(c, m.len.p, (int64_t)C, m.word.p + UQW_UNIQUE);
+        hipLaunchKernelGGL(k_uniq_take, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, c->stream, (int64_t)N, (const uint32_t *)m.head.p, (const uint32_t *)m.first.p,
+                           (const uint32_t *)m.len.p, L, m.uniq_of.p, m.u_src.p, m.u_start.p, m.u_end.p, m.u_cov.p);
+    });
+    e = rc ? hipSuccess : hipMemcpyAsync(w, m.word.p, sizeof w, hipMemcpyDeviceToHost, c->stream);
+    sync = hipStreamSynchronize(c->stream);
+    if (rc) return rc;
+    if (e == hipSuccess) e = sync;
+    if (e != hipSuccess) return fail(-2, "[l2r_uniq_merge] %s", hipGetErrorString(e));
+    const uint64_t hits = (uint64_t)w[UQW_IDENT] + w[UQW_CONTAINED] + w[UQW_SINGLE];
+    if ((size_t)w[UQW_UNIQUE] > N || w[UQW_UNIQUE] < C || hits + w[UQW_UNIQUE] != N) return fail(-2, "[l2r_uniq_merge] %u entries and %llu hits of %zu offers", w[UQW_UNIQUE], (unsigned long long)hits, N);
+    m.n_unique = (int64_t)w[UQW_UNIQUE];
+    m.stats[UQS_UNIQUE] = (double)w[UQW_UNIQUE]; m.stats[UQS_CLUSTERS] = (double)C; m.stats[UQS_LARGEST] = (double)w[UQW_LARGEST]; m.stats[UQS_ROUTE] = 0;
+    m.stats[UQS_IDENT] = (double)w[UQW_IDENT]; m.stats[UQS_CONTAINED] = (double)w[UQW_CONTAINED]; m.stats[UQS_SINGLE] = (double)w[UQW_SINGLE]; m.stats[UQS_END_EXT] = (double)w[UQW_END_EXT];
+    m.have = true;
+    *n_unique = m.n_unique;
+    return 0;
+}
+
+int l2r_uniq_out(l2r_ctx *c, uint8_t *merged, int32_t *uniq_of, int32_t *u_src, int32_t *u_start, int32_t *u_end, int32_t *u_cov)
+{
+    if (!c) return fail(-1, "[l2r_uniq_out] null argument");
+    const UniqState &m = c->uniq;
+    if (!m.have) return fail(-1, "[l2r_uniq_out] no results: the last l2r_uniq_merge failed, or none was made");
+    const size_t N = (size_t)m.n, U = (size_t)m.n_unique;
+    if (m.on_host) {
+        const UniqResult &r = m.host;
+        if (merged && N) memcpy(merged, r.merged.data(), N);
+        if (uniq_of && N) memcpy(uniq_of, r.uniq_of.data(), N * 4);
+        if (u_src && U) memcpy(u_src, r.u_src.data(), U * 4);
+        if (u_start && U) memcpy(u_start, r.u_start.data(), U * 4);
+        if (u_end && U) memcpy(u_end, r.u_end.data(), U * 4);
+        if (u_cov && U) memcpy(u_cov, r.u_cov.data(), U * 4);
+        return 0;
+    }
+    HIP_TRY(hipSetDevice(c->device));
+    return download_all(c, 0, {{merged, m.merged.p, merged ? N : 0}, {uniq_of, m.uniq_of.p, uniq_of ? N * 4 : 0}, {u_src, m.u_src.p, u_src ? U * 4 : 0},
+                               {u_start, m.u_start.p, u_start ? U * 4 : 0}, {u_end, m.u_end.p, u_end ? U * 4 : 0}, {u_cov, m.u_cov.p, u_cov ? U * 4 : 0}}, "l2r_uniq_out");
+}
+
+int l2r_uniq_stats(l2r_ctx *c, double *out, int n) { return stats_out(c ? c->uniq.stats : nullptr, UQS_N, out, n, "l2r_uniq_stats"); }
 
 }  // extern "C"
 

@@ -1449,16 +1449,22 @@ int h_cmd_unique_gtf(int argc, char **argv)
         h_reads reads; h_result res;
         exons_only("unique_gtf", argv[optind], &p, &chr, &reads, &res, 0);
         /* strand as gen_exon gives it; all four names = QNAME (src/bam2gtf.c:104) */
-        h_unique_tail(&p, src, out, intersect, &chr, res.n, reads.tid, reads.rev, res.ex_off, res.ex_start, res.ex_end,
+        l2r_ctx *ctx = l2r_create(0);
+        if (!ctx) engine_fail("unique_gtf");
+        h_unique_tail(ctx, &p, src, out, intersect, &chr, res.n, reads.tid, reads.rev, res.ex_off, res.ex_start, res.ex_end,
                       &reads.names, reads.qname, reads.qname, reads.qname, reads.qname);
+        l2r_destroy(ctx);
         h_result_free(&res); h_reads_free(&reads);
     } else {
         if (!hdr_file) h_fatal("unique_gtf", "Couldn't read header of provided BAM file.\n");
         h_read_header_only(hdr_file, &chr, "unique_gtf");
         h_gtf g;
         h_read_gtf(argv[optind], &chr, &g, 1);
-        h_unique_tail(&p, src, out, intersect, &chr, g.n_tx, g.tid, g.rev, g.ex_off, g.ex_start, g.ex_end,
+        /* (this mode needs no device: where no context can be made, the host loop gives the verdicts) */
+        l2r_ctx *ctx = l2r_create(0);
+        h_unique_tail(ctx, &p, src, out, intersect, &chr, g.n_tx, g.tid, g.rev, g.ex_off, g.ex_start, g.ex_end,
                       &g.names, g.gid, g.tids, g.gname, g.tname);
+        if (ctx) l2r_destroy(ctx);
         h_gtf_free(&g);
     }
     if (out != stdout) fclose(out); else fflush(stdout);

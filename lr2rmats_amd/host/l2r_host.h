@@ -250,7 +250,7 @@ void h_update_tail(const h_update_opts *o, const h_chroms *chr, const h_reads *r
 
 void h_write_summary_text(FILE *s, int anno_genes, int anno_tx, const int64_t *counters);
 
-void h_unique_tail(const l2r_params *p, const char *source, FILE *out, int intersect, const h_chroms *chr,
+void h_unique_tail(l2r_ctx *ctx /* NULL: the host loop */, const l2r_params *p, const char *source, FILE *out, int intersect, const h_chroms *chr,
                    int64_t n, const int32_t *tid, const uint8_t *rev, const int64_t *ex_off, const int32_t *xs, const int32_t *xe,
                    const h_strtab *names, const uint32_t *gid, const uint32_t *tids, const uint32_t *gname, const uint32_t *tname);
 

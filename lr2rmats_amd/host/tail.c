@@ -529,29 +529,70 @@ void h_update_tail(const h_update_opts *o, const h_chroms *chr, const h_reads *r
 /* ------------------------------------------------------------------ unique-gtf */
 
 /* src/unique_gtf.c:73-84 uniq_trans + :147-148: every input transcript is offered to merge_trans on the
- * growing unique list; the ones that merged form the "shared" list (-I). */
-void h_unique_tail(const l2r_params *p, const char *source, FILE *out, int intersect, const h_chroms *chr,
-                   int64_t n, const int32_t *tid, const uint8_t *rev, const int64_t *ex_off, const int32_t *xs, const int32_t *xe,
-                   const h_strtab *names, const uint32_t *gid, const uint32_t *tids, const uint32_t *gname, const uint32_t *tname)
+ * growing unique list; the ones that merged form the "shared" list (-I).  Two steps: the verdicts -- which offers
+ * merged, and the list entries with their mutated first start, last end and coverage -- and the print.  With a
+ * context the verdicts are l2r_uniq_merge's (the same rule, csrc/l2r_uniqplan.hip.h); without one, m_merge's. */
+typedef struct { int64_t n_unique; uint8_t *merged; int32_t *u_src, *u_start, *u_end, *u_cov; } uniq_verdicts;
+
+static void uniq_verdicts_host(const l2r_params *p, int64_t n, const int32_t *tid, const uint8_t *rev, const int64_t *ex_off,
+                               const int32_t *xs, const int32_t *xe, uniq_verdicts *v)
 {
     m_list U; memset(&U, 0, sizeof U);
-    obuf o; ob_init(&o, out);
     for (int64_t i = 0; i < n; ++i) {
         const int64_t off = ex_off[i]; const int k = (int)(ex_off[i + 1] - off);
         m_cand t = { tid[i], xs[off], xe[off + k - 1], k, rev[i], xs + off, xe + off, NULL };
         if (!m_merge(&t, &U, p)) { m_ent *e = m_push(&U, &t); e->read = i; }
-        else if (intersect) {
-            if (tid[i] < 0) h_fatal("unique_gtf", "transcript on a chromosome that is not in the BAM header");
-            emit_gtf_named(&o, source, chr->name[tid[i]], t.start, t.end, rev[i], 1, h_str(names, gid[i]), h_str(names, tids[i]),
-                           h_str(names, gname[i]), h_str(names, tname[i]), chr->name[tid[i]], rev[i], t.xs, t.xe, k);
-        }
+        else v->merged[i] = 1;
     }
-    if (!intersect) for (int64_t i = 0; i < U.n; ++i) {
-        const m_ent *e = &U.e[i]; const int64_t r = e->read;
-        if (e->tid < 0) h_fatal("unique_gtf", "transcript on a chromosome that is not in the BAM header");
-        emit_gtf_named(&o, source, chr->name[e->tid], e->start, e->end, e->rev, e->cov, h_str(names, gid[r]), h_str(names, tids[r]),
-                       h_str(names, gname[r]), h_str(names, tname[r]), chr->name[e->tid], e->rev, U.xs + e->ex, U.xe + e->ex, e->n);
+    v->n_unique = U.n;
+    for (int64_t k = 0; k < U.n; ++k) { v->u_src[k] = (int32_t)U.e[k].read; v->u_start[k] = U.e[k].start; v->u_end[k] = U.e[k].end; v->u_cov[k] = U.e[k].cov; }
+    m_free(&U);
+}
+
+void h_unique_tail(l2r_ctx *ctx, const l2r_params *p, const char *source, FILE *out, int intersect, const h_chroms *chr,
+                   int64_t n, const int32_t *tid, const uint8_t *rev, const int64_t *ex_off, const int32_t *xs, const int32_t *xe,
+                   const h_strtab *names, const uint32_t *gid, const uint32_t *tids, const uint32_t *gname, const uint32_t *tname)
+{
+    const size_t room = (size_t)(n > 0 ? n : 1);
+    uniq_verdicts v; memset(&v, 0, sizeof v);
+    v.merged = (uint8_t *)h_malloc(room); memset(v.merged, 0, room);
+    v.u_src = (int32_t *)h_malloc(room * 4); v.u_start = (int32_t *)h_malloc(room * 4); v.u_end = (int32_t *)h_malloc(room * 4); v.u_cov = (int32_t *)h_malloc(room * 4);
+    const l2r_uniq_trans t = { n, tid, rev, ex_off, xs, xe };
+    /* (-1: transcripts outside l2r_uniq_merge's domain, a negative coordinate for one -- they keep the host loop) */
+    const int rc = ctx ? l2r_uniq_merge(ctx, p, &t, &v.n_unique) : -1;
+    if (rc == 0 || rc != -1) {
+        if (rc || l2r_uniq_out(ctx, v.merged, NULL, v.u_src, v.u_start, v.u_end, v.u_cov)) h_fatal("unique_gtf", "%s", l2r_last_error());
+        const char *tm = getenv("L2R_TIMING");
+        if (tm && atoi(tm) != 0) {
+            double st[5] = {0, 0, 0, 0, 0};
+            (void)l2r_uniq_stats(ctx, st, 5);
+            fprintf(stderr, "[unique_gtf] merge_trans: route %s, %lld transcripts, %lld unique, %lld clusters, largest cluster %lld\n", st[4] != 0 ? "host" : "device",
+                    (long long)n, (long long)v.n_unique, (long long)st[2], (long long)st[3]);
+        }
+    } else {
+        uniq_verdicts_host(p, n, tid, rev, ex_off, xs, xe, &v);
+    }
+    obuf o; ob_init(&o, out);
+    if (intersect) {
+        for (int64_t i = 0; i < n; ++i) if (v.merged[i]) {
+            const int64_t off = ex_off[i]; const int k = (int)(ex_off[i + 1] - off);
+            if (tid[i] < 0) h_fatal("unique_gtf", "transcript on a chromosome that is not in the BAM header");
+            emit_gtf_named(&o, source, chr->name[tid[i]], xs[off], xe[off + k - 1], rev[i], 1, h_str(names, gid[i]), h_str(names, tids[i]),
+                           h_str(names, gname[i]), h_str(names, tname[i]), chr->name[tid[i]], rev[i], xs + off, xe + off, k);
+        }
+    } else {
+        int32_t *cs = NULL, *ce = NULL; int cap = 0;            /* an entry's chain: the creating offer's, first start and last end as the hits left them */
+        for (int64_t q = 0; q < v.n_unique; ++q) {
+            const int64_t r = v.u_src[q], off = ex_off[r]; const int k = (int)(ex_off[r + 1] - off);
+            if (tid[r] < 0) h_fatal("unique_gtf", "transcript on a chromosome that is not in the BAM header");
+            if (k > cap) { cap = k + 64; cs = (int32_t *)h_realloc(cs, (size_t)cap * 4); ce = (int32_t *)h_realloc(ce, (size_t)cap * 4); }
+            memcpy(cs, xs + off, (size_t)k * 4); memcpy(ce, xe + off, (size_t)k * 4);
+            cs[0] = v.u_start[q]; ce[k - 1] = v.u_end[q];
+            emit_gtf_named(&o, source, chr->name[tid[r]], v.u_start[q], v.u_end[q], rev[r], v.u_cov[q], h_str(names, gid[r]), h_str(names, tids[r]),
+                           h_str(names, gname[r]), h_str(names, tname[r]), chr->name[tid[r]], rev[r], cs, ce, k);
+        }
+        free(cs); free(ce);
     }
     ob_done(&o);
-    m_free(&U);
+    free(v.merged); free(v.u_src); free(v.u_start); free(v.u_end); free(v.u_cov);
 }
