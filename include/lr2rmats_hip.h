@@ -574,6 +574,64 @@ int          l2r_uniq_merge(l2r_ctx *ctx, const l2r_params *prm, const l2r_uniq_
 int          l2r_uniq_out(l2r_ctx *ctx, uint8_t *merged /* n */, int32_t *uniq_of /* n */, int32_t *u_src, int32_t *u_start, int32_t *u_end, int32_t *u_cov /* n_unique each */);
 int          l2r_uniq_stats(l2r_ctx *ctx, double *out, int n);
 
+/* ---- the GTF block of `bam2gtf` and `unique-gtf` (host/cmds.c, host/tail.c): transcripts as GTF text, the text composed on the device.
+ * The rule, stated here once.  A block describes one transcript: a reference tid, a strand rev, n >= 1 exons xs[k]..xe[k] in ascending
+ * order, up to four names -- gene id g, transcript id t, gene name G, transcript name T -- and optionally the overrides start, end and
+ * cov.  S = xs[0] and E = xe[n - 1]; where start / end are given, S = start and E = end, and they replace the first exon's start and the
+ * last exon's end in the exon lines too.  Numbers are printed as %d.  With A the attribute text:
+ *     transcript line   <ref>\t<src>\ttranscript\t<S>\t<E>\t.\t<+|->\t.\t<A><C>\n
+ *     exon line         <ref>\t<src>\texon\t<xs>\t<xe>\t.\t<+|->\t.\t<A>\n
+ * Form L2R_GTX_PLAIN (print_trans, src/gtf.c:597-604; `bam2gtf`): A = gene_id "<g>"; transcript_id "<t>"; -- both parts always, also for an
+ * empty name -- <C> is empty, and the exons are written ascending whatever the strand.
+ * Form L2R_GTX_READ (print_read_trans, src/gtf.c:607-632; `unique-gtf`): A = the concatenation, in the order gene_id, transcript_id,
+ * gene_name, transcript_name, of ` <key> "<s>";` for every non-empty name, with the first space removed; <C> = ` transcript_cov "<cov>";`
+ * (cov = 1 where no column is given); the exons are written descending where rev is set.  (With all four names empty the transcript line
+ * holds `\t transcript_cov ...` with a blank in front, as host/tail.c's emit_gtf_named writes it; the reference would write none.)
+ * Domain errors fail the call with -1 -- distinct from the other failures, as in l2r_uniq_merge -- and write nothing; l2r_last_error()
+ * names the smallest block (0-based) and the kind: a selection index outside the transcripts, a tid outside [0, n_ref), a transcript
+ * with no exon, a name id at or beyond names_len, a name of 255 or more bytes, a name without a NUL inside the table, a negative S, E,
+ * xs, xe or cov; and a block whose text reaches 2^32 - 64 bytes.
+ *     l2r_gtftext_begin   once: the reference names (as in l2r_bed_params), the source string (0..1023 bytes, no tab, newline or NUL) and
+ *                         the form, copied to HBM
+ *     l2r_gtftext_rows    the transcripts to HBM: tid, rev, the exons [ex_off[i], ex_off[i + 1]) of xs / xe, a table names[0, names_len)
+ *                         of NUL-terminated strings and the id columns (byte offsets into it; gid and tids always, gname and tname in form
+ *                         READ; they may alias).  xs == NULL: the exon chains of the context's last l2r_run, taken where they lie in HBM,
+ *                         in read order -- n must equal the run's reads, ex_off and xe are not read and no exon crosses the bus
+ *     l2r_gtftext_blocks  the selection: m blocks, block q is transcript sel[q] (sel == NULL: q), with the optional columns start, end and
+ *                         cov.  k_gtx_measure runs over all m blocks, the lengths (4 bytes per block) come to the host; *n_lines and
+ *                         *n_bytes are the totals.  The domain errors surface here
+ *     l2r_gtftext_lines   one batch: blocks from `first` while their count stays within max_blocks and the sum of their measured bytes
+ *                         within max_bytes and below 2^32 - 64 -- always at least one.  *n_taken blocks, *n_bytes of text, which stays in
+ *                         HBM until the next call.  Batches concatenated are the text of the selection however it was cut
+ *     l2r_gtftext_out     the text of the last l2r_gtftext_lines; cap < n_bytes fails and writes nothing, as does a call behind a failure
+ * On the device (csrc/l2r_gtftext.hip.h): k_gtx_measure -- one thread per block, or one wave per block where the selection has more than 32
+ * exons per block on average (L2R_GTX_WAVE=0|1 forces one) -- k_scan_u32 over the batch's lengths, and k_gtx_write: one workgroup per
+ * L2R_GTX_TILE blocks spreads their lines over its lanes, composes the text in an LDS image of L2R_GTX_LDS_BYTES and streams it out in
+ * aligned 16-byte stores; a tile with more text writes its lines directly.  The text buffer has 64 bytes of slack; with L2R_CHECK=1 they
+ * are filled with a pattern in front of k_gtx_write and looked at behind it.  L2R_GTX_ROUTE=host: the exact host routine of
+ * csrc/l2r_gtftextplan.hip.h, same bytes, same errors.
+ * l2r_gtftext_stats: out[0] blocks of the selection, [1] lines and [2] bytes of the last batch, [3] form of k_gtx_measure (0 thread,
+ * 1 wave), [4] tiles on the LDS path, [5] tiles on the direct path (both of the last batch), [6] route (0 device, 1 host), [7] 1 where the
+ * guard bytes are intact or were not checked, [8] batches since l2r_gtftext_blocks; with L2R_GTX_TIMING=1 in the environment (every
+ * launch is then waited for) device milliseconds of [9] k_gtx_measure, [10] k_scan_u32 and [11] k_gtx_write, the latter two summed over
+ * the batches; n = words of out (up to 12). */
+#define L2R_GTX_TILE 32                 /* blocks of one workgroup of k_gtx_write: about 300 lines, 28 KB of text at eight exons per block */
+#define L2R_GTX_LDS_BYTES 32768         /* bytes of a tile's text its LDS image holds; a tile with more takes the direct path */
+#define L2R_GTX_PLAIN 0
+#define L2R_GTX_READ 1
+#define L2R_GTX_NAME_MAX 254            /* bytes of a name */
+#define L2R_GTX_SRC_MAX 1023            /* bytes of the source string */
+typedef struct { int32_t n_ref; const int64_t *ref_off; const uint8_t *ref_names; int32_t form, src_len; const uint8_t *src; } l2r_gtx_params;
+typedef struct { int64_t n; const int32_t *tid; const uint8_t *rev; const int64_t *ex_off /* n + 1 */; const int32_t *xs, *xe;
+                 int64_t names_len; const uint8_t *names; const uint32_t *gid, *tids, *gname, *tname; } l2r_gtx_rows;
+typedef struct { int64_t m; const int32_t *sel, *start, *end, *cov; } l2r_gtx_blocks;      /* any of the four may be null */
+int          l2r_gtftext_begin(l2r_ctx *ctx, const l2r_gtx_params *prm);
+int          l2r_gtftext_rows(l2r_ctx *ctx, const l2r_gtx_rows *rows);
+int          l2r_gtftext_blocks(l2r_ctx *ctx, const l2r_gtx_blocks *sel, int64_t *n_lines, int64_t *n_bytes);
+int          l2r_gtftext_lines(l2r_ctx *ctx, int64_t first, int64_t max_blocks, int64_t max_bytes, int64_t *n_taken, int64_t *n_bytes);
+int          l2r_gtftext_out(l2r_ctx *ctx, uint8_t *text, int64_t cap);
+int          l2r_gtftext_stats(l2r_ctx *ctx, double *out, int n);
+
 #ifdef __cplusplus
 }
 #endif

@@ -39,6 +39,7 @@ EXPORTS = [
     "l2r_gtf_order", "l2r_gtf_rows_out", "l2r_gtf_stats", "l2r_gtf_check",
     "l2r_bed_begin", "l2r_bed_lines", "l2r_bed_text_out", "l2r_bed_cut", "l2r_bed_stats",
     "l2r_uniq_merge", "l2r_uniq_out", "l2r_uniq_stats",
+    "l2r_gtftext_begin", "l2r_gtftext_rows", "l2r_gtftext_blocks", "l2r_gtftext_lines", "l2r_gtftext_out", "l2r_gtftext_stats",
 ]
 SJ_E_UNKNOWN_TID = -3
 
@@ -162,6 +163,19 @@ class CUniqTrans(C.Structure):
     _fields_ = [("n", C.c_int64), ("tid", C.c_void_p), ("rev", C.c_void_p), ("ex_off", C.c_void_p), ("xs", C.c_void_p), ("xe", C.c_void_p)]
 
 
+class CGtxParams(C.Structure):
+    _fields_ = [("n_ref", C.c_int32), ("ref_off", C.c_void_p), ("ref_names", C.c_void_p), ("form", C.c_int32), ("src_len", C.c_int32), ("src", C.c_void_p)]
+
+
+class CGtxRows(C.Structure):
+    _fields_ = [("n", C.c_int64), ("tid", C.c_void_p), ("rev", C.c_void_p), ("ex_off", C.c_void_p), ("xs", C.c_void_p), ("xe", C.c_void_p),
+                ("names_len", C.c_int64), ("names", C.c_void_p), ("gid", C.c_void_p), ("tids", C.c_void_p), ("gname", C.c_void_p), ("tname", C.c_void_p)]
+
+
+class CGtxBlocks(C.Structure):
+    _fields_ = [("m", C.c_int64), ("sel", C.c_void_p), ("start", C.c_void_p), ("end", C.c_void_p), ("cov", C.c_void_p)]
+
+
 class CTiming(C.Structure):
     _fields_ = [("stage_ms", C.c_float * N_STAGES), ("total_ms", C.c_float), ("iters", C.c_int32)]
 
@@ -250,6 +264,12 @@ def load_library():
         lib.l2r_uniq_merge.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         lib.l2r_uniq_out.argtypes = [C.c_void_p] + [C.c_void_p] * 6
         lib.l2r_uniq_stats.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
+        lib.l2r_gtftext_begin.argtypes = [C.c_void_p, C.c_void_p]
+        lib.l2r_gtftext_rows.argtypes = [C.c_void_p, C.c_void_p]
+        lib.l2r_gtftext_blocks.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        lib.l2r_gtftext_lines.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p]
+        lib.l2r_gtftext_out.argtypes = [C.c_void_p, C.c_void_p, C.c_int64]
+        lib.l2r_gtftext_stats.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
         _lib = lib
     return _lib
 
@@ -392,6 +412,11 @@ def bed_cut(flag, tid, cigars, names, ref_names, first: int, max_records: int, m
     if lib.l2r_bed_cut(C.byref(recs), C.byref(prm), first, max_records, max_bytes, C.byref(take)):
         raise RuntimeError(lib.l2r_last_error().decode())
     return int(take.value)
+
+
+GTX_PLAIN, GTX_READ = 0, 1
+GTX_TILE, GTX_LDS_BYTES = 32, 32768         # L2R_GTX_TILE, L2R_GTX_LDS_BYTES (include/lr2rmats_hip.h)
+GTX_STAT_NAMES = ["blocks", "lines", "bytes", "wave_form", "tiles_lds", "tiles_direct", "route", "guard_intact", "batches", "k_gtx_measure", "k_scan_u32", "k_gtx_write"]
 
 
 UNIQ_STAT_NAMES = ["rows", "unique", "clusters", "largest_cluster", "route", "hits_identical", "hits_contained", "hits_single", "end_extensions",
@@ -693,6 +718,81 @@ class Engine:
         out = np.zeros(len(BED_STAT_NAMES), np.float64)
         self._chk(self.lib.l2r_bed_stats(self.ctx, out.ctypes.data, len(out)))
         return {k: float(v) for k, v in zip(BED_STAT_NAMES, out)}
+
+    # ---- the GTF text of `bam2gtf` / `unique-gtf` (include/lr2rmats_hip.h: l2r_gtftext_begin / _rows / _blocks / _lines / _out / _stats)
+    def gtftext_begin(self, ref_names, source=b"lr2rmats", form=GTX_PLAIN) -> None:
+        """The reference names (byte strings, by tid), the source string and the form (GTX_PLAIN, GTX_READ) of the blocks that follow."""
+        off, blob = pack_names(ref_names)
+        keep = blob if blob.size else np.zeros(1, np.uint8)
+        src = np.frombuffer(bytes(source) + b"\0", np.uint8)
+        prm = CGtxParams(len(off) - 1, off.ctypes.data, keep.ctypes.data, int(form), len(bytes(source)), src.ctypes.data)
+        self._chk(self.lib.l2r_gtftext_begin(self.ctx, C.byref(prm)))
+
+    def gtftext_rows(self, tid, rev, ex_off, xs, xe, names, gid, tids, gname=None, tname=None, n=None) -> None:
+        """The transcripts: tid, rev, exons [ex_off[i], ex_off[i + 1]) of xs / xe, the table ``names`` (bytes: NUL-terminated strings) and
+        the id columns (byte offsets into it; an array passed twice is sent once).  ``xs`` None: the exon chains of the last run, where
+        they lie in HBM (ex_off and xe are not read; ``n`` overrides the transcript count, which must equal the run's reads)."""
+        names = np.frombuffer(bytes(names), np.uint8) if not isinstance(names, np.ndarray) else np.ascontiguousarray(names, np.uint8)
+        cols = {}
+
+        def col(a, t):
+            if a is None:
+                return None
+            if id(a) not in cols:
+                cols[id(a)] = np.ascontiguousarray(a, t)
+            return cols[id(a)]
+        a = [col(tid, np.int32), col(rev, np.uint8), None if xs is None else col(ex_off, np.int64), None if xs is None else col(xs, np.int32),
+             None if xs is None else col(xe, np.int32)]
+        ids = [col(gid, np.uint32), col(tids, np.uint32), col(gname, np.uint32), col(tname, np.uint32)]
+        n = int(a[0].shape[0]) if n is None else int(n)
+        ptr = [None if x is None else (x.ctypes.data if x.size else None) for x in a + ids]
+        rows = CGtxRows(n, ptr[0], ptr[1], ptr[2], ptr[3], ptr[4], int(names.size), names.ctypes.data if names.size else None, *ptr[5:])
+        self._chk(self.lib.l2r_gtftext_rows(self.ctx, C.byref(rows)))
+
+    def gtftext_blocks(self, m=None, sel=None, start=None, end=None, cov=None):
+        """The selection: block q is transcript sel[q] (None: q, ``m`` blocks), with the optional overrides.  (n_lines, n_bytes) of its
+        text; a block outside the domain raises L2RError (rc=-1) naming the smallest such block and the kind."""
+        a = [None if x is None else np.ascontiguousarray(x, np.int32) for x in (sel, start, end, cov)]
+        sizes = {int(x.shape[0]) for x in a if x is not None}
+        if m is None:
+            if len(sizes) != 1:
+                raise ValueError("gtftext_blocks: m, or columns of one length")
+            m = sizes.pop()
+        keep = [np.zeros(1, np.int32) if (x is not None and x.size == 0) else x for x in a]
+        blk = CGtxBlocks(int(m), *[None if x is None else x.ctypes.data for x in keep])
+        n_lines, n_bytes = C.c_int64(0), C.c_int64(0)
+        self._chk(self.lib.l2r_gtftext_blocks(self.ctx, C.byref(blk), C.byref(n_lines), C.byref(n_bytes)))
+        return int(n_lines.value), int(n_bytes.value)
+
+    def gtftext_lines(self, first: int, max_blocks: int = 1 << 20, max_bytes: int = 1 << 30, cap=None, buf=None):
+        """One batch from block ``first``: (blocks taken, its text).  ``cap``: the room offered to l2r_gtftext_out (None: the batch's bytes).
+        ``buf``: a uint8 array the text is fetched into -- the text is then a view of it, not a copy (tools/bench_gtx.py)."""
+        n_taken, n_bytes = C.c_int64(0), C.c_int64(0)
+        self._chk(self.lib.l2r_gtftext_lines(self.ctx, int(first), int(max_blocks), int(max_bytes), C.byref(n_taken), C.byref(n_bytes)))
+        if buf is not None:
+            self._chk(self.lib.l2r_gtftext_out(self.ctx, buf.ctypes.data, int(buf.size)))
+            return int(n_taken.value), buf[:int(n_bytes.value)]
+        cap = int(n_bytes.value) if cap is None else int(cap)
+        out = np.zeros(max(cap, 1), np.uint8)
+        self._chk(self.lib.l2r_gtftext_out(self.ctx, out.ctypes.data, cap))
+        return int(n_taken.value), out[:int(n_bytes.value)].tobytes()
+
+    def gtftext_all(self, m: int, max_blocks: int = 1 << 20, max_bytes: int = 1 << 30) -> bytes:
+        """The text of the whole selection of ``m`` blocks, batch by batch."""
+        out, first = [], 0
+        while first < m:
+            k, t = self.gtftext_lines(first, max_blocks, max_bytes)
+            out.append(t)
+            first += k
+        return b"".join(out)
+
+    def gtftext_stats(self) -> dict:
+        """l2r_gtftext_stats: blocks of the selection, lines and bytes of the last batch, the form of k_gtx_measure (0 thread, 1 wave), tiles
+        on the LDS and on the direct path, route (0 device, 1 host), guard_intact, batches, and with L2R_GTX_TIMING=1 device milliseconds
+        per kernel."""
+        out = np.zeros(len(GTX_STAT_NAMES), np.float64)
+        self._chk(self.lib.l2r_gtftext_stats(self.ctx, out.ctypes.data, len(out)))
+        return {k: float(v) for k, v in zip(GTX_STAT_NAMES, out)}
 
     # ---- `unique-gtf` (include/lr2rmats_hip.h: l2r_uniq_merge / _out / _stats)
     def uniq_merge(self, tid, rev, ex_off, xs, xe, force_strand=0, ss_dis=0, end_dis=0x7fffffff, frac=0.8) -> dict:

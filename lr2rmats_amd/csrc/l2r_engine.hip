@@ -28,11 +28,13 @@
 #include "l2r_gtf.hip.h"
 #include "l2r_bed.hip.h"
 #include "l2r_uniq.hip.h"
+#include "l2r_gtftext.hip.h"
 #include "l2r_plan.hip.h"
 #include "l2r_tables.hip.h"
 #include "l2r_nameorder.hip.h"
 #include "l2r_gtforder.hip.h"
 #include "l2r_bedplan.hip.h"
+#include "l2r_gtftextplan.hip.h"
 
 using namespace l2r;
 
@@ -211,6 +213,36 @@ struct UniqState {
     double stats[UQS_N] = {0};                          // l2r_uniq_stats
 };
 
+// The GTF block of `bam2gtf` / `unique-gtf` (l2r_gtftext.hip.h): the reference names, source string and form of l2r_gtftext_begin, the
+// transcripts of l2r_gtftext_rows, the selection of l2r_gtftext_blocks with what k_gtx_measure left per block, and the text of the last
+// l2r_gtftext_lines (in HBM, or on the host where the host route made it) until l2r_gtftext_out fetches it.  The route is read at
+// l2r_gtftext_rows and holds until the next; only the host route keeps copies of the columns (h).  The buffers belong to the context,
+// grow on demand and are used again.
+struct GtxState {
+    bool begun = false, have_rows = false, have_blocks = false, have_text = false, text_on_host = false, on_host = false;
+    bool run_chains = false;                            // rows came with xs == NULL: the exon chains of the context's last l2r_run
+    l2r_gtx_params prm{};                               // ref_off / ref_names / src point into the three vectors
+    std::vector<int64_t> h_ref_off; std::vector<uint8_t> h_ref_names, h_src;
+    DevBuf<int64_t> ref_off; DevBuf<uint8_t> ref_names, src;
+    int64_t n = 0, m = 0, names_len = 0;
+    double exons_per_row = 0;                           // of the run's chains (the host does not see them)
+    std::vector<uint32_t> h_nex;                        // uploaded rows: exons per transcript (the form of k_gtx_measure)
+    DevBuf<int32_t> tid, xs, xe, sel, start, end, cov; DevBuf<uint8_t> rev, names; DevBuf<int64_t> ex_off; DevBuf<uint32_t> id[4];
+    const uint32_t *id_p[4] = {nullptr, nullptr, nullptr, nullptr};     // aliasing columns share one buffer
+    bool has_sel = false, has_start = false, has_end = false, has_cov = false;
+    struct Host {                                       // the host route's copies
+        std::vector<int32_t> tid, xs, xe, sel, start, end, cov; std::vector<uint8_t> rev, names; std::vector<int64_t> ex_off; std::vector<uint32_t> id[4];
+    } h;
+    std::vector<uint32_t> h_len;                        // the measured bytes of every block of the selection
+    DevBuf<uint32_t> len, fix, off, word;               // per block; off: one batch's lengths, scanned in place; word: GTXC_* and the scan's total
+    DevBuf<unsigned long long> word64;                  // k_gtx_measure: the smallest bad block << 4 | kind, the lines
+    DevBuf<uint4> text;                                 // the text, 16-byte aligned, GTX_SLACK bytes behind it
+    int64_t n_bytes = 0;
+    std::vector<uint8_t> host_text;
+    StageTimer clk;
+    double stats[12] = {0};                             // l2r_gtftext_stats
+};
+
 // What l2r_sync has learned from the counters of a completed run of the tile path (fetch_run_facts): a later run of the same inputs,
 // parameters and outputs sizes its list-driven launches by the counts and skips those whose list was empty.  One record, forgotten as a
 // whole wherever one of those changes (forget_list_state).  LC_*: the list counter a field is a copy of (l2r_kernels.hip.h).
@@ -365,6 +397,7 @@ struct l2r_ctx {
     GtfState gtf;                           // `sort-gtf`
     BedState bed;                           // `bam2bed`
     UniqState uniq;                         // `unique-gtf`
+    GtxState gtx;                           // `bam2gtf`, `unique-gtf`: the GTF text
 };
 
 // A launch (or a group of launches) on the context stream
@@ -2907,6 +2940,285 @@ int l2r_uniq_out(l2r_ctx *c, uint8_t *merged, int32_t *uniq_of, int32_t *u_src, 
 }
 
 int l2r_uniq_stats(l2r_ctx *c, double *out, int n) { return stats_out(c ? c->uniq.stats : nullptr, UQS_N, out, n, "l2r_uniq_stats"); }
+
+// ---------------------------------------------------------------------------------------------- the GTF text of bam2gtf / unique-gtf
+// slots of l2r_gtftext_stats
+enum { GXS_BLOCKS = 0, GXS_LINES, GXS_BYTES, GXS_WAVE, GXS_TILES_LDS, GXS_TILES_DIRECT, GXS_ROUTE, GXS_GUARD, GXS_BATCHES, GXS_K_MEASURE, GXS_K_SCAN, GXS_K_WRITE, GXS_N };
+static_assert(GXS_N == sizeof(GtxState::stats) / sizeof(double) && GXS_K_MEASURE == 9, "l2r_gtftext_stats: the words of include/lr2rmats_hip.h");
+constexpr int GTXC_TOTAL = GTXC_N;                      // GtxState::word: k_gtx_write's counters, then the scan's total
+constexpr size_t GTX_SLACK = 64;                        // bytes behind the text; L2R_CHECK: a pattern k_gtx_write must leave alone
+constexpr uint8_t GTX_GUARD_BYTE = 0xa5;
+constexpr int GTX_E_ARG = -4;                           // arguments, order of calls: not -1, which is a domain error (the commands fall back on it)
+
+int l2r_gtftext_begin(l2r_ctx *c, const l2r_gtx_params *p)
+{
+    if (!c) return fail(GTX_E_ARG, "[l2r_gtftext_begin] null argument");
+    GtxState &m = c->gtx;
+    m.begun = false; m.have_rows = false; m.have_blocks = false; m.have_text = false;
+    for (double &v : m.stats) v = 0;
+    {   std::string msg;
+        if (gtx_check_params(p, msg)) return fail(GTX_E_ARG, "%s", msg.c_str()); }
+    const size_t R = (size_t)p->n_ref, NB = R ? (size_t)p->ref_off[R] : 0;
+    m.h_ref_off.assign(R + 1, 0);
+    for (size_t k = 0; k <= R && R; ++k) m.h_ref_off[k] = p->ref_off[k];
+    m.h_ref_names.assign(NB + 1, 0);
+    if (NB) memcpy(m.h_ref_names.data(), p->ref_names, NB);
+    m.h_src.assign((size_t)p->src_len + 1, 0);
+    if (p->src_len) memcpy(m.h_src.data(), p->src, (size_t)p->src_len);
+    m.prm = *p;
+    m.prm.ref_off = m.h_ref_off.data(); m.prm.ref_names = m.h_ref_names.data(); m.prm.src = m.h_src.data();
+    HIP_TRY(hipSetDevice(c->device));
+    int rc;
+    if ((rc = put_dev(c, m.ref_off, m.h_ref_off)) || (rc = put_dev(c, m.ref_names, m.h_ref_names)) || (rc = put_dev(c, m.src, m.h_src))) return rc;
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    m.begun = true;
+    return 0;
+}
+
+// the exon chains of the last run for the host route: ex_off from the exon counts, xs / xe as they lie
+static int gtx_fetch_chains(l2r_ctx *c, GtxState &m)
+{
+    const size_t N = (size_t)c->n_reads, X = c->h_totals[0];
+    std::vector<uint32_t> info(N ? N : 1);
+    m.h.xs.assign(X ? X : 1, 0); m.h.xe.assign(X ? X : 1, 0);
+    if (N) HIP_TRY(hipMemcpyAsync(info.data(), c->info.p, N * 4, hipMemcpyDeviceToHost, c->stream));
+    if (X) {
+        HIP_TRY(hipMemcpyAsync(m.h.xs.data(), c->ex_start.p, X * 4, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipMemcpyAsync(m.h.xe.data(), c->ex_end.p, X * 4, hipMemcpyDeviceToHost, c->stream));
+    }
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    m.h.ex_off.assign(N + 1, 0);
+    for (size_t i = 0; i < N; ++i) m.h.ex_off[i + 1] = m.h.ex_off[i] + (int64_t)(info[i] >> 8);
+    if ((size_t)m.h.ex_off[N] != X) return fail(-5, "[l2r_gtftext_rows] exon counts (%lld) do not add up to the exon total (%zu)", (long long)m.h.ex_off[N], X);
+    return 0;
+}
+
+int l2r_gtftext_rows(l2r_ctx *c, const l2r_gtx_rows *r)
+{
+    if (!c) return fail(GTX_E_ARG, "[l2r_gtftext_rows] null argument");
+    GtxState &m = c->gtx;
+    m.have_rows = false; m.have_blocks = false; m.have_text = false;
+    if (!m.begun) return fail(GTX_E_ARG, "[l2r_gtftext_rows] no l2r_gtftext_begin in front");
+    {   std::string msg;
+        if (gtx_check_rows(r, m.prm.form, msg)) return fail(GTX_E_ARG, "%s", msg.c_str()); }
+    const char *route = getenv("L2R_GTX_ROUTE");
+    m.on_host = route && strcmp(route, "host") == 0;
+    m.stats[GXS_ROUTE] = m.on_host ? 1 : 0;
+    const size_t N = (size_t)r->n, NL = (size_t)r->names_len;
+    const int n_names = m.prm.form == L2R_GTX_READ ? 4 : 2;
+    const uint32_t *col[4] = {r->gid, r->tids, r->gname, r->tname};
+    m.n = r->n; m.names_len = r->names_len; m.run_chains = N > 0 && !r->xs;
+    HIP_TRY(hipSetDevice(c->device));
+    int rc = 0;
+    if (m.run_chains) {
+        if ((rc = fetch_totals(c))) return rc;
+        if (!(c->want & L2R_WANT_RESULTS)) return fail(GTX_E_ARG, "[l2r_gtftext_rows] the last run kept no exon chains (l2r_set_outputs without L2R_WANT_RESULTS)");
+        if (r->n != c->n_reads) return fail(GTX_E_ARG, "[l2r_gtftext_rows] %lld transcripts, the last run had %lld reads", (long long)r->n, (long long)c->n_reads);
+        m.exons_per_row = (double)c->h_totals[0] / (double)N;
+        m.h_nex.clear();
+    } else {
+        m.h_nex.resize(N);
+        for (size_t i = 0; i < N; ++i) m.h_nex[i] = (uint32_t)(r->ex_off[i + 1] - r->ex_off[i]);
+    }
+    if (m.on_host) {
+        GtxState::Host &h = m.h;
+        h.tid.assign(r->tid, r->tid + N); h.rev.assign(r->rev, r->rev + N);
+        h.names.assign(r->names, r->names + NL);
+        for (int k = 0; k < 4; ++k) { if (k < n_names && N) h.id[k].assign(col[k], col[k] + N); else h.id[k].clear(); }
+        if (m.run_chains) { if ((rc = gtx_fetch_chains(c, m))) return rc; }
+        else if (N) { const size_t X = (size_t)r->ex_off[N]; h.ex_off.assign(r->ex_off, r->ex_off + N + 1); h.xs.assign(r->xs, r->xs + X); h.xe.assign(r->xe, r->xe + X); }
+        m.have_rows = true;
+        return 0;
+    }
+    if ((rc = to_dev(c, m.tid, r->tid, N)) || (rc = to_dev(c, m.rev, r->rev, N)) || (rc = to_dev(c, m.names, r->names, NL))) { (void)hipStreamSynchronize(c->stream); return rc; }
+    for (int k = 0; k < 4 && !rc; ++k) {
+        m.id_p[k] = nullptr;
+        if (k >= n_names || !N) continue;
+        for (int j = 0; j < k; ++j) if (col[j] == col[k]) m.id_p[k] = m.id_p[j];
+        if (!m.id_p[k]) { rc = to_dev(c, m.id[k], col[k], N); m.id_p[k] = m.id[k].p; }
+    }
+    if (!rc && !m.run_chains && N) {
+        const size_t X = (size_t)r->ex_off[N];
+        if ((rc = to_dev(c, m.ex_off, r->ex_off, N + 1)) || (rc = to_dev(c, m.xs, r->xs, X)) || (rc = to_dev(c, m.xe, r->xe, X))) {}
+    }
+    const hipError_t sync = hipStreamSynchronize(c->stream);           // (the columns are the caller's)
+    if (rc) return rc;
+    if (sync != hipSuccess) return fail(-2, "[l2r_gtftext_rows] %s", hipGetErrorString(sync));
+    m.have_rows = true;
+    return 0;
+}
+
+// the kernels' view of the rows and the selection
+static GtxIn gtx_in(const l2r_ctx *c, const GtxState &m)
+{
+    GtxIn in{};
+    in.n = m.n; in.m = m.m; in.tid = m.tid.p; in.rev = m.rev.p;
+    if (m.run_chains) { in.ex_off32 = c->ex_off.p; in.info = c->info.p; in.xs = c->ex_start.p; in.xe = c->ex_end.p; }
+    else { in.ex_off64 = m.ex_off.p; in.xs = m.xs.p; in.xe = m.xe.p; }
+    in.names = m.names.p; in.names_len = m.names_len;
+    for (int k = 0; k < 4; ++k) in.id[k] = m.id_p[k];
+    in.sel = m.has_sel ? m.sel.p : nullptr; in.start = m.has_start ? m.start.p : nullptr; in.end = m.has_end ? m.end.p : nullptr; in.cov = m.has_cov ? m.cov.p : nullptr;
+    in.n_ref = m.prm.n_ref; in.ref_off = m.ref_off.p; in.ref_names = m.ref_names.p; in.src = m.src.p; in.src_len = (uint32_t)m.prm.src_len; in.form = m.prm.form;
+    return in;
+}
+// ... and the host route's, over its copies
+static void gtx_host_view(const GtxState &m, l2r_gtx_rows &r, GtxChains &cx, l2r_gtx_blocks &b)
+{
+    const GtxState::Host &h = m.h;
+    r = l2r_gtx_rows{m.n, h.tid.data(), h.rev.data(), h.ex_off.data(), h.xs.data(), h.xe.data(), m.names_len, h.names.data(),
+                     h.id[0].data(), h.id[1].data(), h.id[2].data(), h.id[3].data()};
+    cx = GtxChains{h.ex_off.data(), h.xs.data(), h.xe.data()};
+    b = l2r_gtx_blocks{m.m, m.has_sel ? h.sel.data() : nullptr, m.has_start ? h.start.data() : nullptr, m.has_end ? h.end.data() : nullptr, m.has_cov ? h.cov.data() : nullptr};
+}
+
+int l2r_gtftext_blocks(l2r_ctx *c, const l2r_gtx_blocks *b, int64_t *n_lines, int64_t *n_bytes)
+{
+    if (!c || !n_lines || !n_bytes) return fail(GTX_E_ARG, "[l2r_gtftext_blocks] null argument");
+    GtxState &m = c->gtx;
+    m.have_blocks = false; m.have_text = false;
+    for (int k = 0; k < GXS_N; ++k) if (k != GXS_ROUTE) m.stats[k] = 0;
+    m.stats[GXS_GUARD] = 1;
+    if (!m.have_rows) return fail(GTX_E_ARG, "[l2r_gtftext_blocks] no l2r_gtftext_rows in front");
+    {   std::string msg;
+        if (gtx_check_blocks(b, msg)) return fail(GTX_E_ARG, "%s", msg.c_str()); }
+    *n_lines = 0; *n_bytes = 0;
+    const size_t M = (size_t)b->m;
+    m.m = b->m; m.has_sel = M && b->sel; m.has_start = M && b->start; m.has_end = M && b->end; m.has_cov = M && b->cov;
+    m.stats[GXS_BLOCKS] = (double)M;
+    m.h_len.assign(M, 0u);
+    if (M == 0) { m.have_blocks = true; return 0; }
+    if (m.run_chains && c->n_reads != m.n) return fail(GTX_E_ARG, "[l2r_gtftext_blocks] the rows stand for a run of %lld reads, the context now holds %lld", (long long)m.n, (long long)c->n_reads);
+    uint64_t lines = 0, bytes = 0;
+    if (m.on_host) {
+        GtxState::Host &h = m.h;
+        if (m.has_sel) h.sel.assign(b->sel, b->sel + M); if (m.has_start) h.start.assign(b->start, b->start + M);
+        if (m.has_end) h.end.assign(b->end, b->end + M); if (m.has_cov) h.cov.assign(b->cov, b->cov + M);
+        l2r_gtx_rows hr; GtxChains cx; l2r_gtx_blocks hb;
+        gtx_host_view(m, hr, cx, hb);
+        for (size_t q = 0; q < M; ++q) {
+            uint64_t by = 0, nl = 0;
+            const int kind = gtx_block_bytes(&m.prm, &hr, cx, &hb, (int64_t)q, &by, &nl);
+            if (kind) { std::string msg; gtx_block_fail(msg, (int64_t)q, kind); return fail(-1, "%s", msg.c_str()); }
+            m.h_len[q] = (uint32_t)by; lines += nl; bytes += by;
+        }
+    } else {
+        HIP_TRY(hipSetDevice(c->device));
+        int rc;
+        if ((rc = m.clk.begin(env_on("L2R_GTX_TIMING"), c->check_stages))) return rc;
+        // one wave per block where the selection has more than 32 exons per block on average; L2R_GTX_WAVE=0|1: tests, tools/bench_gtx.py
+        double per_block = m.exons_per_row;
+        if (!m.run_chains) {
+            uint64_t x = 0;
+            for (size_t q = 0; q < M; ++q) { const int64_t t = b->sel ? (int64_t)b->sel[q] : (int64_t)q; if (t >= 0 && t < m.n) x += m.h_nex[(size_t)t]; }
+            per_block = (double)x / (double)M;
+        }
+        bool wave = per_block > 32.0;
+        if (const char *e = getenv("L2R_GTX_WAVE")) wave = atoi(e) != 0;
+        m.stats[GXS_WAVE] = wave ? 1 : 0;
+        if ((m.has_sel && (rc = to_dev(c, m.sel, b->sel, M))) || (m.has_start && (rc = to_dev(c, m.start, b->start, M))) || (m.has_end && (rc = to_dev(c, m.end, b->end, M))) ||
+            (m.has_cov && (rc = to_dev(c, m.cov, b->cov, M))) || m.len.ensure(M) || m.fix.ensure(M) || m.word64.ensure(2) || m.word.ensure(GTXC_TOTAL + 1)) rc = rc ? rc : -2;
+        if (rc) { (void)hipStreamSynchronize(c->stream); return rc; }  // (the columns are the caller's)
+        HIP_TRY(hipMemsetAsync(m.word64.p, 0xff, sizeof(unsigned long long), c->stream));
+        HIP_TRY(hipMemsetAsync(m.word64.p + 1, 0, sizeof(unsigned long long), c->stream));
+        const GtxIn in = gtx_in(c, m);
+        const GtxMeasure meas{m.len.p, m.fix.p, m.word64.p, m.word64.p + 1};
+        rc = m.clk.launch(c, &m.stats[GXS_K_MEASURE], [&] {
+            const dim3 grid((unsigned)(((wave ? M * 64 : M) + 255) / 256));
+            if (wave) hipLaunchKernelGGL(k_gtx_measure<true>, grid, dim3(256), 0, c->stream, in, meas);
+            else hipLaunchKernelGGL(k_gtx_measure<false>, grid, dim3(256), 0, c->stream, in, meas);
+        });
+        unsigned long long w[2] = {0, 0};
+        hipError_t e = rc ? hipSuccess : hipMemcpyAsync(w, m.word64.p, sizeof w, hipMemcpyDeviceToHost, c->stream);
+        if (!rc && e == hipSuccess) e = hipMemcpyAsync(m.h_len.data(), m.len.p, M * 4, hipMemcpyDeviceToHost, c->stream);
+        const hipError_t sync = hipStreamSynchronize(c->stream);
+        if (rc) return rc;
+        if (e == hipSuccess) e = sync;
+        if (e != hipSuccess) return fail(-2, "[l2r_gtftext_blocks] %s", hipGetErrorString(e));
+        if (w[0] != ~0ull) {
+            const unsigned long long q = w[0] >> 4; const int kind = (int)(w[0] & 15ull);
+            if (q >= M || kind <= GTX_OK || kind >= GTX_E_N) return fail(-2, "[l2r_gtftext_blocks] the device names block %llu of %zu, kind %d", q, M, kind);
+            std::string msg; gtx_block_fail(msg, (int64_t)q, kind);
+            return fail(-1, "%s", msg.c_str());
+        }
+        lines = w[1];
+        for (size_t q = 0; q < M; ++q) bytes += m.h_len[q];
+    }
+    m.have_blocks = true;
+    *n_lines = (int64_t)lines; *n_bytes = (int64_t)bytes;
+    return 0;
+}
+
+int l2r_gtftext_lines(l2r_ctx *c, int64_t first, int64_t max_blocks, int64_t max_bytes, int64_t *n_taken, int64_t *n_bytes)
+{
+    if (!c || !n_taken || !n_bytes) return fail(GTX_E_ARG, "[l2r_gtftext_lines] null argument");
+    GtxState &m = c->gtx;
+    m.have_text = false; m.text_on_host = false; m.n_bytes = 0; m.host_text.clear();
+    *n_taken = 0; *n_bytes = 0;
+    if (!m.have_blocks) return fail(GTX_E_ARG, "[l2r_gtftext_lines] no l2r_gtftext_blocks in front, or it failed");
+    int64_t take = 0, sum = 0;
+    {   std::string msg;
+        if (gtx_cut(m.h_len.data(), m.m, first, max_blocks, max_bytes, &take, &sum, msg)) return fail(GTX_E_ARG, "%s", msg.c_str()); }
+    const size_t B = (size_t)sum, K = (size_t)take;
+    m.stats[GXS_LINES] = 0; m.stats[GXS_BYTES] = 0; m.stats[GXS_TILES_LDS] = 0; m.stats[GXS_TILES_DIRECT] = 0;
+    if (m.on_host) {
+        l2r_gtx_rows hr; GtxChains cx; l2r_gtx_blocks hb;
+        gtx_host_view(m, hr, cx, hb);
+        std::string msg;
+        int64_t lines = 0;
+        if (gtx_text_host(&m.prm, &hr, cx, &hb, first, take, m.host_text, &lines, msg)) { m.host_text.clear(); return fail(-1, "%s", msg.c_str()); }
+        if (m.host_text.size() != B) return fail(-5, "[l2r_gtftext_lines] %zu bytes of text, measured %zu", m.host_text.size(), B);
+        m.have_text = true; m.text_on_host = true; m.n_bytes = sum;
+        m.stats[GXS_LINES] = (double)lines; m.stats[GXS_BYTES] = (double)B; m.stats[GXS_BATCHES] += 1;
+        *n_taken = take; *n_bytes = sum;
+        return 0;
+    }
+    if (m.run_chains && c->n_reads != m.n) return fail(GTX_E_ARG, "[l2r_gtftext_lines] the rows stand for a run of %lld reads, the context now holds %lld", (long long)m.n, (long long)c->n_reads);
+    HIP_TRY(hipSetDevice(c->device));
+    int rc;
+    if ((rc = m.clk.begin(env_on("L2R_GTX_TIMING"), c->check_stages))) return rc;
+    if (m.off.ensure(K + 1) || m.text.ensure((B + GTX_SLACK + 15) / 16) || m.word.ensure(GTXC_TOTAL + 1)) return -2;
+    uint8_t *text8 = reinterpret_cast<uint8_t *>(m.text.p);
+    HIP_TRY(hipMemcpyAsync(m.off.p, m.len.p + first, K * 4, hipMemcpyDeviceToDevice, c->stream));
+    HIP_TRY(hipMemsetAsync(m.word.p, 0, (GTXC_TOTAL + 1) * sizeof(uint32_t), c->stream));
+    if ((rc = m.clk.launch(c, &m.stats[GXS_K_SCAN], [&] { scan_u32(c, m.off.p, (int64_t)K, m.word.p + GTXC_TOTAL); }))) { (void)hipStreamSynchronize(c->stream); return rc; }
+    if (c->check_stages) HIP_TRY(hipMemsetAsync(text8 + B, GTX_GUARD_BYTE, GTX_SLACK, c->stream));
+    const unsigned n_tiles = (unsigned)((K + GTX_TILE - 1) / GTX_TILE);
+    const GtxIn in = gtx_in(c, m);
+    if ((rc = m.clk.launch(c, &m.stats[GXS_K_WRITE], [&] {
+            hipLaunchKernelGGL(k_gtx_write, dim3(n_tiles), dim3(GTX_THREADS), 0, c->stream, in, first, take, (const uint32_t *)m.off.p, (const uint32_t *)m.fix.p, text8, m.word.p);
+        }))) { (void)hipStreamSynchronize(c->stream); return rc; }
+    uint8_t guard[GTX_SLACK];
+    uint32_t w[GTXC_TOTAL + 1] = {0};
+    HIP_TRY(hipMemcpyAsync(w, m.word.p, sizeof w, hipMemcpyDeviceToHost, c->stream));
+    if (c->check_stages) HIP_TRY(hipMemcpyAsync(guard, text8 + B, GTX_SLACK, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    if (c->check_stages) for (size_t k = 0; k < GTX_SLACK; ++k) if (guard[k] != GTX_GUARD_BYTE) m.stats[GXS_GUARD] = 0;
+    if ((size_t)w[GTXC_TOTAL] != B) return fail(-5, "[l2r_gtftext_lines] the scan left %u bytes, the cut %zu", w[GTXC_TOTAL], B);
+    if (w[GTXC_OUTSIDE]) return fail(-5, "[l2r_gtftext_lines] %u lines would have left their tile's span: k_gtx_measure and k_gtx_write disagree", w[GTXC_OUTSIDE]);
+    if (w[GTXC_DIRECT] > n_tiles) return fail(-5, "[l2r_gtftext_lines] %u direct tiles of %u", w[GTXC_DIRECT], n_tiles);
+    m.stats[GXS_LINES] = (double)w[GTXC_LINES]; m.stats[GXS_BYTES] = (double)B; m.stats[GXS_BATCHES] += 1;
+    m.stats[GXS_TILES_DIRECT] = (double)w[GTXC_DIRECT]; m.stats[GXS_TILES_LDS] = (double)(n_tiles - w[GTXC_DIRECT]);
+    m.have_text = true; m.n_bytes = sum;
+    *n_taken = take; *n_bytes = sum;
+    return 0;
+}
+
+int l2r_gtftext_out(l2r_ctx *c, uint8_t *text, int64_t cap)
+{
+    if (!c) return fail(GTX_E_ARG, "[l2r_gtftext_out] null argument");
+    const GtxState &m = c->gtx;
+    if (!m.have_text) return fail(GTX_E_ARG, "[l2r_gtftext_out] no text: the last l2r_gtftext_lines failed, or none was made");
+    if (cap < m.n_bytes) return fail(GTX_E_ARG, "[l2r_gtftext_out] room for %lld bytes, the last l2r_gtftext_lines left %lld", (long long)cap, (long long)m.n_bytes);
+    if (m.n_bytes == 0) return 0;
+    if (!text) return fail(GTX_E_ARG, "[l2r_gtftext_out] null text");
+    if (m.text_on_host) { memcpy(text, m.host_text.data(), (size_t)m.n_bytes); return 0; }
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipMemcpyAsync(text, m.text.p, (size_t)m.n_bytes, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+int l2r_gtftext_stats(l2r_ctx *c, double *out, int n) { return stats_out(c ? c->gtx.stats : nullptr, GXS_N, out, n, "l2r_gtftext_stats"); }
 
 }  // extern "C"
 

@@ -629,6 +629,23 @@ static int64_t shard_end(const l2r_reads *r, int64_t lo)
     return a;
 }
 
+/* the records [lo, hi) of r as an upload of their own; *off_tmp: room the caller keeps and frees */
+static l2r_reads shard_reads(const l2r_reads *r, int64_t lo, int64_t hi, int64_t **off_tmp)
+{
+    const int64_t n = hi - lo;
+    l2r_reads sub = *r;
+    sub.n_reads = n; sub.n_cigar = r->cig_off[hi] - r->cig_off[lo];
+    sub.tid = r->tid + lo; sub.pos = r->pos + lo; sub.rev = r->rev + lo; sub.cig = r->cig + r->cig_off[lo];
+    sub.cig_summary = r->cig_summary ? r->cig_summary + 3 * (size_t)lo : NULL;
+    sub.first_read_index = r->first_read_index + lo;
+    if (lo > 0) {                                            /* the engine wants offsets that start at 0 */
+        *off_tmp = (int64_t *)h_realloc(*off_tmp, (size_t)(n + 1) * 8);
+        for (int64_t i = 0; i <= n; ++i) (*off_tmp)[i] = r->cig_off[lo + i] - r->cig_off[lo];
+        sub.cig_off = *off_tmp;
+    } else sub.cig_off = r->cig_off;
+    return sub;
+}
+
 static void result_reserve(h_result *r, int64_t reads_cap, int64_t ex_cap)
 {
     r->ex_off = (int64_t *)h_realloc(r->ex_off, (size_t)(reads_cap + 1) * 8);
@@ -735,17 +752,8 @@ static void run_engine(const char *who, const l2r_params *prm, const l2r_annotat
     l2r_accepted_read *rec = NULL; int64_t rec_cap = 0;
     int64_t lo = 0;
     do {
-        const int64_t hi = shard_end(r, lo), n = hi - lo;
-        l2r_reads sub = *r;
-        sub.n_reads = n; sub.n_cigar = r->cig_off[hi] - r->cig_off[lo];
-        sub.tid = r->tid + lo; sub.pos = r->pos + lo; sub.rev = r->rev + lo; sub.cig = r->cig + r->cig_off[lo];
-        sub.cig_summary = r->cig_summary ? r->cig_summary + 3 * (size_t)lo : NULL;
-        sub.first_read_index = r->first_read_index + lo;
-        if (lo > 0) {                                        /* the engine wants offsets that start at 0 */
-            off_tmp = (int64_t *)h_realloc(off_tmp, (size_t)(n + 1) * 8);
-            for (int64_t i = 0; i <= n; ++i) off_tmp[i] = r->cig_off[lo + i] - r->cig_off[lo];
-            sub.cig_off = off_tmp;
-        } else sub.cig_off = r->cig_off;
+        const int64_t hi = shard_end(r, lo);
+        const l2r_reads sub = shard_reads(r, lo, hi, &off_tmp);
         if (l2r_upload_reads(ctx, &sub)) engine_fail(who);
         if (l2r_run(ctx) || l2r_sync(ctx)) engine_fail(who);
         int64_t nr = 0, nx = 0, na = 0, nax = 0;
@@ -1342,6 +1350,28 @@ static void bam2gtf_print(const h_reads *reads, const h_result *out, const h_chr
     }
 }
 
+/* The blocks of the records the context has just run (reads: a window of n records, its columns starting at the run's first record):
+ * the text is composed from the exon chains where l2r_run left them -- no exon comes to the host.  With L2R_GTX_ROUTE=off, or where a
+ * record is outside the engine's domain, the chains are downloaded and bam2gtf_print writes them. */
+static void bam2gtf_emit(l2r_ctx *ctx, const h_reads *reads, const h_chroms *chr, const char *src)
+{
+    const l2r_gtx_rows rows = { reads->n, reads->tid, reads->rev, NULL, NULL, NULL, (int64_t)reads->names.len, (const uint8_t *)reads->names.buf,
+                                reads->qname, reads->qname, NULL, NULL };
+    const l2r_gtx_blocks blk = { reads->n, NULL, NULL, NULL, NULL };
+    if (reads->n == 0) return;
+    fflush(stdout);
+    if (!h_gtf_text(ctx, "bam2gtf", stdout, chr, src, L2R_GTX_PLAIN, &rows, &blk)) return;
+    int64_t nr = 0, nx = 0;
+    if (l2r_result_sizes(ctx, &nr, &nx, NULL, NULL)) engine_fail("bam2gtf");
+    h_result out; memset(&out, 0, sizeof out);
+    result_reserve(&out, nr, nx);
+    l2r_result res = { nr, nx, 0, out.ex_off, out.ex_start, out.ex_end, out.ex_flag, out.info, out.ref_tx };
+    if (l2r_download(ctx, &res)) engine_fail("bam2gtf");
+    out.n = nr; out.n_ex = nx;
+    bam2gtf_print(reads, &out, chr, src);
+    h_result_free(&out);
+}
+
 int h_cmd_bam2gtf(int argc, char **argv)
 {
     static const struct option lopt[] = {{"exon-min", 1, 0, 'e'}, {"intron-len", 1, 0, 'i'}, {"source", 1, 0, 's'}, {0, 0, 0, 0}};
@@ -1376,15 +1406,7 @@ int h_cmd_bam2gtf(int argc, char **argv)
             if (got > 0) {
                 l2r_reads r = { reads.n, reads.n_cig, reads.tid, reads.pos, reads.rev, reads.cig_off, reads.cig, 0, reads.cig_sum };
                 if (l2r_upload_reads(ctx, &r) || l2r_run(ctx) || l2r_sync(ctx)) engine_fail("bam2gtf");
-                int64_t nr = 0, nx = 0;
-                if (l2r_result_sizes(ctx, &nr, &nx, NULL, NULL)) engine_fail("bam2gtf");
-                h_result out; memset(&out, 0, sizeof out);
-                result_reserve(&out, nr, nx);
-                l2r_result res = { nr, nx, 0, out.ex_off, out.ex_start, out.ex_end, out.ex_flag, out.info, out.ref_tx };
-                if (l2r_download(ctx, &res)) engine_fail("bam2gtf");
-                out.n = nr; out.n_ex = nx;
-                bam2gtf_print(&reads, &out, &chr, src);
-                h_result_free(&out);
+                bam2gtf_emit(ctx, &reads, &chr, src);
             }
             h_reads_free(&reads);
             if (got < 0) break;
@@ -1395,11 +1417,30 @@ int h_cmd_bam2gtf(int argc, char **argv)
         h_chroms_free(&chr);
         return 0;
     }
-    h_reads reads; h_result out;
-    exons_only("bam2gtf", argv[optind], &p, &chr, &reads, &out, 1);
-    bam2gtf_print(&reads, &out, &chr, src);
+    /* the whole file at once: the engine shard by shard (run_engine), every shard's blocks written behind its run */
+    h_reads reads;
+    h_read_alignments(argv[optind], &chr, &reads, 1, "bam2gtf");
+    l2r_ctx *ctx = l2r_create(0);
+    if (!ctx) engine_fail("bam2gtf");
+    (void)l2r_hint_single_run(ctx, 1);
+    l2r_annotation a; memset(&a, 0, sizeof a);
+    int64_t zero_off = 0; a.tx_ex_off = &zero_off;
+    if (l2r_set_params(ctx, &p) || l2r_set_outputs(ctx, L2R_WANT_RESULTS) || l2r_set_annotation(ctx, &a) || l2r_set_junctions(ctx, NULL)) engine_fail("bam2gtf");
+    const l2r_reads r = { reads.n, reads.n_cig, reads.tid, reads.pos, reads.rev, reads.cig_off, reads.cig, 0, reads.cig_sum };
+    int64_t *off_tmp = NULL;
+    for (int64_t lo = 0; lo < r.n_reads;) {
+        const int64_t hi = shard_end(&r, lo);
+        const l2r_reads sub = shard_reads(&r, lo, hi, &off_tmp);
+        if (l2r_upload_reads(ctx, &sub) || l2r_run(ctx) || l2r_sync(ctx)) engine_fail("bam2gtf");
+        h_reads win = reads;                                    /* (a view: nothing of it is freed) */
+        win.n = hi - lo; win.tid = reads.tid + lo; win.rev = reads.rev + lo; win.qname = reads.qname + lo;
+        bam2gtf_emit(ctx, &win, &chr, src);
+        lo = hi;
+    }
+    free(off_tmp);
+    l2r_destroy(ctx);
     fflush(stdout);
-    h_result_free(&out); h_reads_free(&reads); h_chroms_free(&chr);
+    h_reads_free(&reads); h_chroms_free(&chr);
     return 0;
 }
 

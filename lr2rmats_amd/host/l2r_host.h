@@ -250,6 +250,12 @@ void h_update_tail(const h_update_opts *o, const h_chroms *chr, const h_reads *r
 
 void h_write_summary_text(FILE *s, int anno_genes, int anno_tx, const int64_t *counters);
 
+/* The GTF text of a selection of blocks through the engine (l2r_gtftext_*: composed on the device, or by the engine's host routine with
+ * L2R_GTX_ROUTE=host), written to fp batch by batch (L2R_GTX_BATCH blocks, default 1 Mi, and L2R_GTX_TEXT_MAX bytes, default 1 GiB).
+ * 0: written.  1: nothing was written and the caller's own writer takes over -- L2R_GTX_ROUTE=off, or a block outside the engine's
+ * domain (-1).  Any other failure is fatal.  L2R_TIMING=1: one line on stderr. */
+int h_gtf_text(l2r_ctx *ctx, const char *who, FILE *fp, const h_chroms *chr, const char *source, int form, const l2r_gtx_rows *rows, const l2r_gtx_blocks *blk);
+
 void h_unique_tail(l2r_ctx *ctx /* NULL: the host loop */, const l2r_params *p, const char *source, FILE *out, int intersect, const h_chroms *chr,
                    int64_t n, const int32_t *tid, const uint8_t *rev, const int64_t *ex_off, const int32_t *xs, const int32_t *xe,
                    const h_strtab *names, const uint32_t *gid, const uint32_t *tids, const uint32_t *gname, const uint32_t *tname);

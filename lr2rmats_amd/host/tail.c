@@ -526,6 +526,60 @@ void h_update_tail(const h_update_opts *o, const h_chroms *chr, const h_reads *r
     m_free(&U); free(K.v); free(N.v); free(X.v);
 }
 
+/* ------------------------------------------------------------------ the GTF text through the engine */
+
+static int64_t gtx_env_count(const char *name, int64_t dflt)
+{
+    const char *e = getenv(name);
+    if (!e || !*e) return dflt;
+    const long long v = atoll(e);
+    return v >= 1 ? (int64_t)v : dflt;
+}
+
+int h_gtf_text(l2r_ctx *ctx, const char *who, FILE *fp, const h_chroms *chr, const char *source, int form, const l2r_gtx_rows *rows, const l2r_gtx_blocks *blk)
+{
+    const char *tm = getenv("L2R_TIMING"), *route = getenv("L2R_GTX_ROUTE");
+    const int timing = tm && atoi(tm) != 0;
+    int64_t n_lines = 0, n_bytes = 0, n_batches = 0;
+    int own = route && strcmp(route, "off") == 0;           /* the caller's own writer */
+    int64_t *ref_off = NULL; uint8_t *ref_names = NULL, *text = NULL;
+    if (!own) {
+        const int n_ref = chr->n;
+        ref_off = (int64_t *)h_malloc((size_t)(n_ref + 1) * 8);
+        ref_off[0] = 0;
+        for (int t = 0; t < n_ref; ++t) ref_off[t + 1] = ref_off[t] + (int64_t)strlen(chr->name[t]);
+        ref_names = (uint8_t *)h_malloc((size_t)ref_off[n_ref] + 1);
+        for (int t = 0; t < n_ref; ++t) memcpy(ref_names + ref_off[t], chr->name[t], (size_t)(ref_off[t + 1] - ref_off[t]));
+        const l2r_gtx_params prm = { n_ref, ref_off, ref_names, form, (int32_t)strlen(source), (const uint8_t *)source };
+        if (l2r_gtftext_begin(ctx, &prm) || l2r_gtftext_rows(ctx, rows)) h_fatal(who, "%s", l2r_last_error());
+        const int rc = l2r_gtftext_blocks(ctx, blk, &n_lines, &n_bytes);
+        if (rc == -1) own = 1;                              /* (nothing has been written) */
+        else if (rc) h_fatal(who, "%s", l2r_last_error());
+    }
+    if (!own) {
+        const int64_t max_blocks = gtx_env_count("L2R_GTX_BATCH", (int64_t)1 << 20), max_bytes = gtx_env_count("L2R_GTX_TEXT_MAX", (int64_t)1 << 30);
+        int64_t text_cap = 0;
+        for (int64_t first = 0; first < blk->m;) {
+            int64_t take = 0, bytes = 0;
+            if (l2r_gtftext_lines(ctx, first, max_blocks, max_bytes, &take, &bytes) || take < 1) h_fatal(who, "%s", l2r_last_error());
+            if (bytes > text_cap) { free(text); text_cap = bytes + bytes / 4 + 64; text = (uint8_t *)h_malloc((size_t)text_cap); }
+            if (bytes) {
+                if (l2r_gtftext_out(ctx, text, text_cap)) h_fatal(who, "%s", l2r_last_error());
+                if (fwrite(text, 1, (size_t)bytes, fp) != (size_t)bytes) h_fatal(who, "Error in writing GTF text\n");
+            }
+            ++n_batches; first += take;
+        }
+    }
+    if (timing) {
+        double st[7] = {0, 0, 0, 0, 0, 0, 0};
+        if (!own) (void)l2r_gtftext_stats(ctx, st, 7);
+        fprintf(stderr, "[%s] gtf text: route %s, %lld blocks, %lld lines, %lld bytes, %lld batches\n", who, own ? "off" : st[6] != 0 ? "host" : "device",
+                (long long)blk->m, (long long)(own ? 0 : n_lines), (long long)(own ? 0 : n_bytes), (long long)n_batches);
+    }
+    free(text); free(ref_off); free(ref_names);
+    return own;
+}
+
 /* ------------------------------------------------------------------ unique-gtf */
 
 /* src/unique_gtf.c:73-84 uniq_trans + :147-148: every input transcript is offered to merge_trans on the
@@ -571,6 +625,24 @@ void h_unique_tail(l2r_ctx *ctx, const l2r_params *p, const char *source, FILE *
         }
     } else {
         uniq_verdicts_host(p, n, tid, rev, ex_off, xs, xe, &v);
+    }
+    /* the print: with a context the text is the engine's (form READ: the list with its mutated first starts, last ends and coverages;
+     * -I: the merged offers as they are); without one, or where a block is outside its domain, emit_gtf_named */
+    if (ctx) {
+        const l2r_gtx_rows rows = { n, tid, rev, ex_off, xs, xe, (int64_t)names->len, (const uint8_t *)names->buf, gid, tids, gname, tname };
+        int32_t *sel = NULL;
+        l2r_gtx_blocks blk = { v.n_unique, v.u_src, v.u_start, v.u_end, v.u_cov };
+        if (intersect) {
+            sel = (int32_t *)h_malloc(room * 4);
+            int64_t k = 0;
+            for (int64_t i = 0; i < n; ++i) if (v.merged[i]) sel[k++] = (int32_t)i;
+            const l2r_gtx_blocks shared = { k, sel, NULL, NULL, NULL };
+            blk = shared;
+        }
+        fflush(out);
+        const int own = h_gtf_text(ctx, "unique_gtf", out, chr, source, L2R_GTX_READ, &rows, &blk);
+        free(sel);
+        if (!own) { free(v.merged); free(v.u_src); free(v.u_start); free(v.u_end); free(v.u_cov); return; }
     }
     obuf o; ob_init(&o, out);
     if (intersect) {
