@@ -294,7 +294,8 @@ typedef struct {
     const int64_t *cig_off;         /* n + 1 */
     const uint32_t *cig;            /* len << 4 | op */
 } l2r_filter_records;
-/* transcripts of the -r GTF in FILE order, as read_anno_trans() leaves them (tid -1: chromosome not in the header) */
+/* transcripts of the -r GTF in FILE order, as read_anno_trans() leaves them (tid -1: chromosome not in the header; the reference
+ * compares tids as numbers, so a mapped record of tid -1 meets such a transcript where it lies in front of the first tid >= 0) */
 typedef struct { int64_t n; const int32_t *tid, *start, *end; } l2r_filter_spans;
 /* drop[i] = gtf_filter() != 0; score[i] / intron_n[i] = its two outputs (score 0 for dropped records) */
 int          l2r_filter_score(l2r_ctx *ctx, const l2r_filter_records *recs, const l2r_filter_params *prm,

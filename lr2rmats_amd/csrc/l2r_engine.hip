@@ -1653,38 +1653,23 @@ static int download_all(l2r_ctx *c, int rc, std::initializer_list<Download> list
 int l2r_filter_score(l2r_ctx *c, const l2r_filter_records *r, const l2r_filter_params *prm, const l2r_filter_spans *rm,
                      uint8_t *drop, int32_t *score, int32_t *intron_n)
 {
-    if (!c || !r || !prm || !drop || !score || !intron_n) return fail(-1, "[l2r_filter_score] null argument");
-    if (r->n < 0 || r->n_cigar < 0) return fail(-1, "[l2r_filter_score] negative size");
-    HIP_TRY(hipSetDevice(c->device));
+    {   std::string msg;
+        if (filter_score_check(c, r, prm, rm, drop, score, intron_n, msg)) return fail(-1, "%s", msg.c_str()); }
     const size_t N = (size_t)r->n;
-    if (N && (r->cig_off[0] != 0 || r->cig_off[N] != r->n_cigar)) return fail(-1, "[l2r_filter_score] cig_off does not span the CIGAR array");
-    // the -r transcripts a record of every chromosome can meet (l2r_filter.hip.h FilterSpans), on the host
-    std::vector<int64_t> off; std::vector<int32_t> st, pe;
-    int32_t n_tid = 0;
-    if (rm && rm->n > 0) {
-        for (int64_t j = 0; j < rm->n; ++j) n_tid = std::max(n_tid, rm->tid[j] + 1);
-        // first_gt[v]: first transcript (file order) with tid > v = where remove_overlap() stops for a record of tid v
-        std::vector<int64_t> first_gt((size_t)n_tid, rm->n);
-        int32_t seen = -1;                                 // largest tid so far
-        for (int64_t j = 0; j < rm->n; ++j) if (rm->tid[j] > seen) { for (int32_t v = std::max(seen, 0); v < rm->tid[j]; ++v) first_gt[(size_t)v] = std::min(first_gt[(size_t)v], j); seen = rm->tid[j]; }
-        std::vector<std::vector<std::pair<int32_t, int32_t>>> per((size_t)n_tid);
-        for (int64_t j = 0; j < rm->n; ++j) { const int32_t t = rm->tid[j]; if (t >= 0 && j < first_gt[(size_t)t]) per[(size_t)t].push_back({rm->start[j], rm->end[j]}); }
-        off.assign((size_t)n_tid + 1, 0);
-        for (int32_t t = 0; t < n_tid; ++t) {
-            auto &v = per[(size_t)t];
-            std::sort(v.begin(), v.end());
-            int32_t run = INT32_MIN;
-            for (auto &se : v) { run = std::max(run, se.second); st.push_back(se.first); pe.push_back(run); }
-            off[(size_t)t + 1] = (int64_t)st.size();
-        }
-    }
+    if (N == 0) return 0;
+    HIP_TRY(hipSetDevice(c->device));
+    // the -r transcripts a record of every chromosome can meet (l2r_filterplan.hip.h), on the host
+    FilterSpanTable tab;
+    filter_spans_build(rm, tab);
+    const std::vector<int64_t> &off = tab.off; const std::vector<int32_t> &st = tab.start, &pe = tab.pmax_end;
+    const int32_t n_tid = tab.n_tid;
     DevBuf<uint16_t> d_flag; DevBuf<int32_t> d_tid, d_pos, d_lq, d_nm, d_score, d_in, d_st, d_pe; DevBuf<int64_t> d_off, d_soff; DevBuf<uint32_t> d_cig; DevBuf<uint8_t> d_drop;
     int rc = 0;
     if ((rc = to_dev(c, d_flag, r->flag, N)) || (rc = to_dev(c, d_tid, r->tid, N)) || (rc = to_dev(c, d_pos, r->pos, N)) || (rc = to_dev(c, d_lq, r->l_qseq, N)) ||
         (rc = to_dev(c, d_nm, r->nm, N)) || (rc = to_dev(c, d_off, r->cig_off, N + 1)) || (rc = to_dev(c, d_cig, r->cig, (size_t)r->n_cigar)) ||
         (rc = to_dev(c, d_soff, off.data(), off.size())) || (rc = to_dev(c, d_st, st.data(), st.size())) || (rc = to_dev(c, d_pe, pe.data(), pe.size())) ||
-        d_drop.ensure(N ? N : 1) || d_score.ensure(N ? N : 1) || d_in.ensure(N ? N : 1)) { rc = rc ? rc : -2; }
-    if (!rc && N && !(rc = fusion_begin(c, FUS_K_FILTER_SCORE))) {
+        d_drop.ensure(N) || d_score.ensure(N) || d_in.ensure(N)) { rc = rc ? rc : -2; }
+    if (!rc && !(rc = fusion_begin(c, FUS_K_FILTER_SCORE))) {
         const FilterPrm fp{prm->cov_rate, prm->map_qual, prm->sec_rat, prm->min_intron_n};
         const FilterSpans sp{d_soff.p, d_st.p, d_pe.p, n_tid};
         rc = c->fusion_clk.launch(c, &c->fusion_stats[FUS_K_FILTER_SCORE], [&] {
@@ -1699,11 +1684,11 @@ int l2r_filter_score(l2r_ctx *c, const l2r_filter_records *r, const l2r_filter_p
 int l2r_filter_select(l2r_ctx *c, int64_t n_groups, const int64_t *group_off, const int32_t *score, const int32_t *intron_n,
                       const l2r_filter_params *prm, int64_t *winner)
 {
-    if (!c || !prm || n_groups < 0 || (n_groups && (!group_off || !score || !intron_n || !winner))) return fail(-1, "[l2r_filter_select] bad argument");
+    {   std::string msg;
+        if (filter_select_check(c, n_groups, group_off, score, intron_n, prm, winner, msg)) return fail(-1, "%s", msg.c_str()); }
     if (n_groups == 0) return 0;
     HIP_TRY(hipSetDevice(c->device));
     const size_t G = (size_t)n_groups, R = (size_t)group_off[G];
-    for (size_t g = 0; g < G; ++g) if (group_off[g + 1] <= group_off[g]) return fail(-1, "[l2r_filter_select] group %lld is empty", (long long)g);
     DevBuf<int64_t> d_off, d_win; DevBuf<int32_t> d_score, d_in;
     int rc = 0;
     if ((rc = to_dev(c, d_off, group_off, G + 1)) || (rc = to_dev(c, d_score, score, R)) || (rc = to_dev(c, d_in, intron_n, R)) || d_win.ensure(G)) rc = rc ? rc : -2;
@@ -1721,13 +1706,10 @@ int l2r_filter_select(l2r_ctx *c, int64_t n_groups, const int64_t *group_off, co
 int l2r_fusion_segments(l2r_ctx *c, const l2r_fusion_records *r, int32_t *read_start, int32_t *read_end, int32_t *ref_start, int32_t *ref_end,
                         int32_t *qlen)
 {
-    if (!c || !r || !read_start || !read_end || !ref_start || !ref_end || !qlen) return fail(-1, "[l2r_fusion_segments] null argument");
-    if (r->n < 0 || r->n_cigar < 0) return fail(-1, "[l2r_fusion_segments] negative size");
+    {   std::string msg;
+        if (fusion_segments_check(c, r, read_start, read_end, ref_start, ref_end, qlen, msg)) return fail(-1, "%s", msg.c_str()); }
     const size_t N = (size_t)r->n;
     if (N == 0) return 0;
-    if (!r->flag || !r->pos || !r->cig_off || (r->n_cigar && !r->cig)) return fail(-1, "[l2r_fusion_segments] null column");
-    if (r->cig_off[0] != 0 || r->cig_off[N] != r->n_cigar) return fail(-1, "[l2r_fusion_segments] cig_off does not span the CIGAR array");
-    for (size_t i = 0; i < N; ++i) if (r->cig_off[i + 1] < r->cig_off[i]) return fail(-1, "[l2r_fusion_segments] cig_off descends at record %lld", (long long)i);
     HIP_TRY(hipSetDevice(c->device));
     // one wave per record where the CIGARs are long (the bound of l2r_upload_reads' wide_cigar); L2R_FUSION_WAVE=0|1: tests, tools/bench_fusion.py
     bool wave = (double)r->n_cigar / (double)N > 32.0;
@@ -1757,13 +1739,12 @@ int l2r_fusion_select(l2r_ctx *c, int64_t n_groups, const int64_t *group_off, co
                       const int32_t *read_start, const int32_t *read_end, const int32_t *ref_start, const int32_t *ref_end,
                       const int32_t *rlen_of_group, const l2r_fusion_params *prm, int64_t *first, int64_t *second)
 {
-    if (!c || !prm || n_groups < 0 || (n_groups && (!group_off || !score || !ed || !tid || !read_start || !read_end || !ref_start || !ref_end ||
-                                                    !rlen_of_group || !first || !second))) return fail(-1, "[l2r_fusion_select] bad argument");
+    {   std::string msg;
+        if (fusion_select_check(c, n_groups, group_off, score, ed, tid, read_start, read_end, ref_start, ref_end, rlen_of_group, prm, first, second, msg))
+            return fail(-1, "%s", msg.c_str()); }
     if (n_groups == 0) return 0;
     HIP_TRY(hipSetDevice(c->device));
     const size_t G = (size_t)n_groups;
-    if (group_off[0] < 0) return fail(-1, "[l2r_fusion_select] negative group offset");
-    for (size_t g = 0; g < G; ++g) if (group_off[g + 1] <= group_off[g]) return fail(-1, "[l2r_fusion_select] group %lld is empty", (long long)g);
     const size_t R = (size_t)group_off[G];
     DevBuf<int64_t> d_off, d_out; DevBuf<int32_t> d_score, d_ed, d_tid, d_rs, d_re, d_fs, d_fe, d_rlen;
     int rc = 0;

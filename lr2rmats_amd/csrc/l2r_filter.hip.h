@@ -12,6 +12,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "l2r_filterplan.hip.h"
+
 namespace l2r {
 
 struct FilterPrm { float cov_rate, map_qual, sec_rat; int32_t min_intron_n; };
@@ -19,7 +21,9 @@ struct FilterPrm { float cov_rate, map_qual, sec_rat; int32_t min_intron_n; };
 // Transcripts of the -r GTF a record of chromosome `tid` can meet: remove_overlap() walks the transcripts in FILE order
 // and stops at the first one of a larger tid, so they are the transcripts of that tid in front of that stop.  Per tid they
 // are kept sorted by start with the running maximum of their ends: "some transcript with start <= hi and end >= lo" is one
-// binary search (the reference compares the 0-based position with 1-based transcript coordinates: kept as is).
+// binary search (the reference compares the 0-based position with 1-based transcript coordinates: kept as is).  The table is
+// built by filter_spans_build and read by filter_span_hit, both of l2r_filterplan.hip.h: off holds n_tid + 2 words, the
+// first row is that of tid -1.
 struct FilterSpans { const int64_t *off; const int32_t *start, *pmax_end; int32_t n_tid; };
 
 __global__ __launch_bounds__(256)
@@ -53,15 +57,8 @@ void k_filter_score(int64_t n, const uint16_t *__restrict__ flag, const int32_t 
             const int32_t s = qlen - nm[i] + del;
             if ((float)s < p.map_qual * (float)qlen) d = 1;
             else {
-                const int32_t t = tid[i];
-                if (sp.n_tid > 0 && t >= 0 && t < sp.n_tid) {
-                    // some transcript with end >= pos and start <= pos + rlen - 1
-                    const int64_t a = sp.off[t], b = sp.off[t + 1];
-                    const int32_t lo = pos[i], hi = pos[i] + rlen - 1;
-                    int64_t l = a, r = b;                          // first index with start > hi
-                    while (l < r) { const int64_t m = (l + r) >> 1; if (sp.start[m] <= hi) l = m + 1; else r = m; }
-                    if (l > a && sp.pmax_end[l - 1] >= lo) d = 1;
-                }
+                // some transcript with end >= pos and start <= pos + rlen - 1
+                if (filter_span_hit(sp.off, sp.start, sp.pmax_end, sp.n_tid, tid[i], pos[i], pos[i] + rlen - 1)) d = 1;
                 sc = s;
             }
         }
