@@ -557,7 +557,8 @@ int          l2r_bed_stats(l2r_ctx *ctx, double *out, int n);
  * mutation; the shorter chain contained in the longer: merged, nothing changes), mixed exon counts and everything else: skipped.  An
  * offer that reaches the front of the list is pushed.
  * Arguments that fail the call (-1): n of 2^31 or more, ex_off that does not start at 0 or descends, a transcript without exons or with
- * 2^31 or more, tid below -1, a negative coordinate.
+ * 2^31 or more, tid below -1, a negative coordinate.  Every other tid, 2147483647 included, is in the domain.  An exon of 2^31 bases
+ * (start 0, end 2147483647) lies outside it: its length is formed in int, as exon_overlap_frac (src/update_gtf.c:80-89) forms it.
  *     l2r_uniq_merge   the verdicts of all n offers; *n_unique = entries of the list.  The results stay with the context
  *     l2r_uniq_out     of the last l2r_uniq_merge: merged[i] = 1 where offer i merged, uniq_of[i] = the rank of the entry it created or
  *                      merged into; per entry, in list order, u_src (the offer that created it), u_start / u_end (first start and last

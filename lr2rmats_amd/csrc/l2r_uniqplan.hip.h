@@ -117,8 +117,9 @@ __host__ __device__ inline int uniq_apply(int verdict, const UniqChain &t, int32
     return 0;
 }
 
-// the keys of the route test and of the cluster cut: (tid + 1) in the high word (tid >= -1), a coordinate in the low one
-__host__ __device__ inline uint64_t uniq_key(int32_t tid, int32_t coord) { return (uint64_t)(uint32_t)(tid + 1) << 32 | (uint32_t)coord; }
+// the keys of the route test and of the cluster cut: (tid + 1) in the high word (tid >= -1), a coordinate in the low one.  The sum is
+// formed unsigned: tid -1 gives 0 and tid 2147483647 gives 0x80000000
+__host__ __device__ inline uint64_t uniq_key(int32_t tid, int32_t coord) { return (uint64_t)((uint32_t)tid + 1u) << 32 | (uint32_t)coord; }
 
 static int uniq_fail(std::string &msg, const char *fmt, ...)
 {

@@ -1,6 +1,7 @@
 """`unique-gtf`'s merge_trans on the GPU: l2r_uniq_merge on the device route (k_uniq_heads, the prefix maximum and the cluster cut,
 k_uniq_merge, k_uniq_take) against the exact host routine behind L2R_UNIQ_ROUTE=host on every output array, over the cases of
-tests/uniq_cases.py, and the command against the oracle CLI."""
+tests/uniq_cases.py -- among them reaches carried over the edges of a wave, a tile, a wave and a round of the prefix maximum, and lists
+walked in several lane rounds, against their closed-form and literal answers -- and the command against the oracle CLI."""
 import filecmp
 
 import numpy as np
@@ -25,7 +26,8 @@ def eng():
 
 
 def merge(e, trans, opts):
-    tid, rev, ex_off, xs, xe = ur.columns(trans)
+    """trans: a list of transcripts, or their columns (tid, rev, ex_off, xs, xe) as a tuple."""
+    tid, rev, ex_off, xs, xe = trans if isinstance(trans, tuple) else ur.columns(trans)
     out = e.uniq_merge(tid, rev, ex_off, xs, xe, force_strand=opts.get("s", 0), ss_dis=opts.get("d", 0), end_dis=opts.get("D", ur.INT_MAX),
                        frac=np.float32(opts.get("f", 0.8)))
     return out, e.uniq_stats()
@@ -43,7 +45,7 @@ def both_routes(e, monkeypatch, trans, opts, name=""):
         assert dev[k].dtype == host[k].dtype and np.array_equal(dev[k], host[k]), (name, k, dev[k][:20], host[k][:20])
     for k in COUNTS:
         assert dst[k] == hst[k], (name, k, dst[k], hst[k])
-    assert dst["rows"] == len(trans) and dst["unique"] == len(dev["u_src"])
+    assert dst["rows"] == (len(trans[0]) if isinstance(trans, tuple) else len(trans)) and dst["unique"] == len(dev["u_src"])
     return dev, dst
 
 
@@ -90,6 +92,106 @@ def test_generated_set(eng, monkeypatch):
     assert min(hst["hits_identical"], hst["hits_contained"], hst["hits_single"], hst["end_extensions"]) >= 1 and 0.2 <= host["merged"].mean() <= 0.8
     dev, st = both_routes(eng, monkeypatch, trans, uc.GENERATED_OPTS)
     assert st["route"] == 0 and st["clusters"] > 100
+
+
+# ---------------------------------------------------------------------------------------------------- beyond three tiles
+
+def closed_form(eng, monkeypatch, cols, head, clusters, largest, name):
+    """A case of columns in which nothing merges: the host route on every array, and the answer as it is built."""
+    n = len(cols[0])
+    assert np.array_equal(ur.heads_columns(cols), head), name
+    dev, st = both_routes(eng, monkeypatch, cols, {}, name)
+    assert st["route"] == 0, name
+    assert (st["clusters"], st["largest_cluster"], st["unique"]) == (clusters, largest, n), (name, st["clusters"], st["largest_cluster"], st["unique"])
+    assert not dev["merged"].any() and np.array_equal(dev["uniq_of"], np.arange(n)) and np.array_equal(dev["u_src"], np.arange(n)), name
+    return st
+
+
+@pytest.mark.parametrize("p, r", uc.REACH_PAIRS)
+def test_reach_over_tile_wave_and_round_edges(eng, monkeypatch, p, r):
+    cols = uc.reach_columns(p, r)
+    closed_form(eng, monkeypatch, cols, *uc.reach_expected(p, r, len(cols[0])), name=(p, r))
+
+
+@pytest.mark.parametrize("p, r", uc.REACH_ROUND_PAIRS)
+def test_reach_one_cluster_across_the_round_edge(eng, monkeypatch, p, r):
+    """More than 262 144 offers through one wave of k_uniq_merge, every one stopped by the newest entry in its first lane round.  The
+    device time of k_uniq_merge is printed (pytest -s)."""
+    monkeypatch.setenv("L2R_SORT_TIMING", "1")
+    cols = uc.reach_columns(p, r)
+    st = closed_form(eng, monkeypatch, cols, *uc.reach_expected(p, r, len(cols[0])), name=(p, r))
+    print("reach (%d, %d): n = %d, k_uniq_merge %.1f ms, cluster cut %.2f ms" % (p, r, len(cols[0]), st["k_uniq_merge"], st["k_uniq_heads + cluster cut"]))
+
+
+@pytest.mark.parametrize("long_end", uc.STEP_ENDS)
+@pytest.mark.parametrize("chroms", uc.STEP_CHROMS)
+@pytest.mark.parametrize("p", uc.STEP_SLOTS)
+def test_chromosome_step_behind_a_long_transcript(eng, monkeypatch, p, chroms, long_end):
+    """The key carried over the edge has the larger low word (the end) and the smaller high word (the chromosome)."""
+    cols = uc.step_columns(p, chroms, long_end)
+    n = len(cols[0])
+    assert int(cols[4][2 * p + 1]) >= int(cols[3][2 * p + 2::2].max()) and n == p + 1 + uc.N_TAIL
+    closed_form(eng, monkeypatch, cols, np.ones(n, np.uint8), n, 1, name=(p, chroms, long_end))
+
+
+WALK = uc.walk_cases()
+
+
+@pytest.mark.parametrize("name", sorted(WALK))
+def test_walk_cases(eng, monkeypatch, name):
+    trans, opts, (merged, uniq_of) = WALK[name]
+    assert ur.in_order(trans)
+    dev, st = both_routes(eng, monkeypatch, trans, opts, name)
+    k = len(merged)
+    assert st["route"] == 0 and (list(dev["merged"][-k:]), list(dev["uniq_of"][-k:])) == (merged, uniq_of), (name, dev["merged"][-k:], dev["uniq_of"][-k:])
+    assert int(dev["merged"].sum()) == sum(merged) * (st["clusters"] if name.startswith("several") else 1)
+    if name.startswith("deep_mutation"):
+        j, end = uniq_of[0], trans[0][2][-1][1]
+        assert (int(dev["u_end"][j]), int(dev["u_cov"][j]), st["end_extensions"], st["hits_identical"]) == (end + 750, 4, 3, 3)
+        assert list(dev["u_end"][:j]) + list(dev["u_end"][j + 1:-1]) == [end] * (len(dev["u_end"]) - 2) and int(dev["u_end"][-1]) == end + 1300
+    if name.startswith("several"):
+        c = int(name.rsplit("_", 1)[1])
+        assert (st["clusters"], st["largest_cluster"], st["unique"]) == (c, 65 + len(merged), 65 * c)
+        assert np.array_equal(dev["uniq_of"].reshape(c, -1)[:, 65:] - 65 * np.arange(c)[:, None], np.tile(np.asarray(uniq_of) - 65 * (c - 1), (c, 1)))
+
+
+def largest_list(cols, u_src):
+    """Entries of the longest list of one cluster."""
+    cluster = np.cumsum(ur.heads_columns(cols)) - 1
+    return int(np.bincount(cluster[u_src]).max())
+
+
+@pytest.mark.parametrize("which", ["dense", "wide"])
+def test_larger_generated_sets(eng, monkeypatch, which):
+    trans, cols = getattr(uc, which)()
+    monkeypatch.setenv("L2R_UNIQ_ROUTE", "host")
+    host, hst = merge(eng, cols, uc.GENERATED_OPTS)
+    # the host alone: every kind of hit, an end raised, a merged share between 20 % and 80 %; lists of several lane rounds (dense), more
+    # clusters than one round of the scan holds (wide)
+    assert min(hst["hits_identical"], hst["hits_contained"], hst["hits_single"], hst["end_extensions"]) >= 1 and 0.2 <= host["merged"].mean() <= 0.8
+    if which == "dense":
+        assert largest_list(cols, host["u_src"]) >= 130
+    else:
+        assert hst["clusters"] > 16384
+    dev, st = both_routes(eng, monkeypatch, cols, uc.GENERATED_OPTS, which)
+    assert st["route"] == 0 and st["clusters"] == int(ur.heads_columns(cols).sum())
+
+
+def test_one_context_sizes_up_and_down(monkeypatch):
+    """The context's buffers grow on demand and stay: a large call, small ones, a larger one, then small ones again."""
+    c = uc.cases()
+    e = capi.Engine(0)
+    try:
+        for name, trans, opts in (("reach", uc.reach_columns(5, uc.WAVE + 1), {}), ("n1",) + c["n1"], ("lanes_129",) + c["lanes_129"],
+                                  ("wide", uc.wide()[1], uc.GENERATED_OPTS), ("n0",) + c["n0"], ("cluster_edge",) + c["cluster_edge"]):
+            dev, st = both_routes(e, monkeypatch, trans, opts, name)
+            assert st["route"] == 0, name
+            if name == "reach":
+                assert (st["clusters"], st["largest_cluster"]) == uc.reach_expected(5, uc.WAVE + 1, len(trans[0]))[1:]
+            if name == "cluster_edge":
+                assert (st["clusters"], st["largest_cluster"]) == (2, 3)
+    finally:
+        e.close()
 
 
 def test_unsorted_input_takes_the_host_routine(eng, monkeypatch):

@@ -221,6 +221,133 @@ def test_argument_checks(uniq_dump, tmp_path):
     assert int(got[-1]["rc"][0]) == 0                                # tid -1 (a chromosome outside the header) is in the domain
 
 
+# ---------------------------------------------------------------------------------------------------- beyond three tiles
+
+WALK = uc.walk_cases()
+GOLDEN = os.path.join(ROOT, "tests", "golden", "uniq")
+
+
+def list_sizes(cols, u_src):
+    """Entries of every cluster's list."""
+    return np.bincount((np.cumsum(ur.heads_columns(cols)) - 1)[u_src])
+
+
+def test_the_generator_is_unchanged():
+    """loci() took one more parameter: generated() is, element for element, the set recorded before (tests/golden/uniq)."""
+    want = np.load(os.path.join(GOLDEN, "generated_columns.npz"))
+    for got, k in zip(ur.columns(uc.generated()), ("tid", "rev", "ex_off", "xs", "xe")):
+        assert got.dtype == want[k].dtype and np.array_equal(got, want[k]), k
+
+
+def test_heads_of_columns_is_heads():
+    for trans, _o in list(CASES.values()) + [c[:2] for c in WALK.values()]:
+        assert np.array_equal(ur.heads_columns(ur.columns(trans)), ur.heads(trans))
+    for cols in (uc.reach_columns(3, 2 * uc.TILE + 5), uc.step_columns(63, (-1, 0), None), uc.step_columns(uc.TILE - 1, (2147483646, 2147483647), 2147483646)):
+        assert np.array_equal(ur.heads_columns(cols), ur.heads(ur.as_list(cols)))
+
+
+def test_restatement_on_the_walk_cases():
+    """What the walk cases are built to show, written down from the rule."""
+    for name, (trans, opts, (merged, uniq_of)) in WALK.items():
+        assert ur.in_order(trans), name
+        r = ur.merge(trans, **opts)
+        k = len(merged)
+        assert (list(r["merged"][-k:]), list(r["uniq_of"][-k:])) == (merged, uniq_of), name
+        if name.startswith("deep_mutation"):
+            j, end = uniq_of[0], trans[0][2][-1][1]
+            assert (int(r["u_end"][j]), int(r["u_cov"][j]), r["end_ext"], list(r["hits"])) == (end + 750, 4, 3, [3, 0, 0]) and int(ur.heads(trans).sum()) == 1
+        elif name.startswith("several"):
+            c = int(name.rsplit("_", 1)[1])
+            assert int(ur.heads(trans).sum()) == c and len(r["u_src"]) == 65 * c and int(r["merged"].sum()) == k * c
+        else:                                                       # one cluster, and the last offer alone may merge
+            assert int(ur.heads(trans).sum()) == 1 and int(r["merged"].sum()) == sum(merged)
+    # the lanes of the pair in front of the fillers: the list holds n_fill + 2 entries when the offer comes, entry k is judged by lane
+    # (n_fill + 1 - k) % 64 of round (n_fill + 1 - k) // 64
+    assert [((f + 0) % 64, (f + 1) % 64, (f + 1) // 64) for f in uc.STOP_HIT_FILL] == [(0, 1, 0), (61, 62, 0), (62, 63, 0), (63, 0, 1), (0, 1, 1), (62, 63, 1), (63, 0, 2), (0, 1, 2)]
+
+
+def test_restatement_on_the_reach_and_step_cases():
+    """The closed form against the running maximum, at every size."""
+    for p, r in uc.REACH_PAIRS + uc.REACH_ROUND_PAIRS:
+        cols = uc.reach_columns(p, r)
+        n = len(cols[0])
+        head, clusters, largest = uc.reach_expected(p, r, n)
+        assert n >= r + 1 + uc.TILE + 3 and np.array_equal(ur.heads_columns(cols), head) and clusters == int(head.sum()) == n - (r - p)
+        assert largest == int(np.diff(np.append(np.flatnonzero(head), n)).max()) == r - p + 1
+        assert int(cols[4][2 * p + 1]) == int(cols[3][2 * r]) and int(cols[3].min()) >= 1       # the long end EQUALS r's start
+    for p in uc.STEP_SLOTS:
+        for chroms in uc.STEP_CHROMS:
+            for long_end in uc.STEP_ENDS:
+                cols = uc.step_columns(p, chroms, long_end)
+                assert ur.heads_columns(cols).all() and int(cols[4][2 * p + 1]) >= int(cols[3][2 * p + 2::2].max()) and int(cols[0][p]) < int(cols[0][p + 1])
+    small = uc.reach_columns(0, 1)
+    r = ur.merge(ur.as_list(small))
+    assert not r["merged"].any() and list(r["u_src"]) == list(range(len(small[0])))
+
+
+def closed_form(got, cols, head, name):
+    """A case of columns in which nothing merges, as uniq_dump answers it."""
+    n = len(cols[0])
+    assert int(got["rc"][0]) == 0 and int(got["in_order"][0]) == 1, name
+    assert np.array_equal(got["head"], head) and int(got["n_clusters"][0]) == int(head.sum()), (name, int(got["n_clusters"][0]))
+    assert int(got["largest"][0]) == int(np.diff(np.append(np.flatnonzero(head), n)).max()), name
+
+
+def nothing_merges(got, cols, name):
+    n = len(cols[0])
+    assert not got["merged"].any() and np.array_equal(got["uniq_of"], np.arange(n)) and np.array_equal(got["u_src"], np.arange(n)), name
+    assert np.array_equal(got["u_start"], cols[3][0::2]) and np.array_equal(got["u_end"], cols[4][1::2]) and (got["u_cov"] == 1).all(), name
+    assert not got["hits"].any() and int(got["end_ext"][0]) == 0, name
+
+
+def test_walk_cases(uniq_dump, tmp_path):
+    names = sorted(WALK)
+    got = dump(uniq_dump, tmp_path, [case_bytes(WALK[k][0], **WALK[k][1]) for k in names])
+    for k, g in zip(names, got):
+        check(g, WALK[k][0], WALK[k][1], k)
+
+
+def test_reach_and_step_cases_up_to_the_wave(uniq_dump, tmp_path):
+    """... tid 2147483647 among them: (uint32_t)tid + 1u in uniq_key, where tid + 1 overflowed."""
+    cases = [((p, r), uc.reach_columns(p, r), uc.reach_expected(p, r, r + 1 + uc.N_TAIL)[0]) for p, r in uc.REACH_PAIRS if r < uc.ROUND]
+    for p in uc.STEP_SLOTS[:-1]:
+        for chroms in uc.STEP_CHROMS:
+            for long_end in uc.STEP_ENDS:
+                cols = uc.step_columns(p, chroms, long_end)
+                cases.append(((p, chroms, long_end), cols, np.ones(len(cols[0]), np.uint8)))
+    assert any(int(cols[0].max()) == 2147483647 for _n, cols, _h in cases)
+    got = dump(uniq_dump, tmp_path, [case_bytes(None, columns=cols) for _n, cols, _h in cases])
+    for (name, cols, head), g in zip(cases, got):
+        closed_form(g, cols, head, name)
+        nothing_merges(g, cols, name)
+
+
+def test_reach_and_step_cases_at_the_round(uniq_dump, tmp_path):
+    """head, n_clusters and largest alone."""
+    cases = [((p, r), uc.reach_columns(p, r), uc.reach_expected(p, r, r + 1 + uc.N_TAIL)[0]) for p, r in uc.REACH_PAIRS + uc.REACH_ROUND_PAIRS if r >= uc.ROUND]
+    for chroms in uc.STEP_CHROMS:
+        for long_end in uc.STEP_ENDS:
+            cols = uc.step_columns(uc.STEP_SLOTS[-1], chroms, long_end)
+            cases.append(((chroms, long_end), cols, np.ones(len(cols[0]), np.uint8)))
+    got = dump(uniq_dump, tmp_path, [case_bytes(None, columns=cols) for _n, cols, _h in cases])
+    for (name, cols, head), g in zip(cases, got):
+        closed_form(g, cols, head, name)
+
+
+@pytest.mark.parametrize("which", ["dense", "wide"])
+def test_larger_generated_sets(uniq_dump, tmp_path, which):
+    trans, cols = getattr(uc, which)()
+    assert ur.in_order(trans) and {t[0] for t in trans} == {0, 1, 2} and 0.99 * getattr(uc, which.upper() + "_N") <= len(trans)
+    (got,) = dump(uniq_dump, tmp_path, [case_bytes(None, columns=cols, **uc.GENERATED_OPTS)])
+    # the host alone: every kind of hit, an end raised, and a merged share between 20 % and 80 %
+    assert min(got["hits"]) >= 1 and int(got["end_ext"][0]) >= 1 and 0.2 <= got["merged"].mean() <= 0.8
+    if which == "dense":                                            # lists of more than two lane rounds
+        assert list_sizes(cols, got["u_src"]).max() >= 130
+    else:                                                           # both scans beyond their first round of 16 384 words
+        assert int(got["n_clusters"][0]) > 16384 and len(got["u_src"]) > 16384
+    check(got, trans, uc.GENERATED_OPTS, which)
+
+
 # ---------------------------------------------------------------------------------------------------- the command's own loop
 
 def write_gtf(path, trans, refs):

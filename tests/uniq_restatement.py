@@ -108,6 +108,24 @@ def in_order(trans):
     return all(keys[i - 1] <= keys[i] for i in range(1, len(keys)))
 
 
+def as_list(cols):
+    """The transcripts of columns (tid, rev, ex_off, xs, xe) as a list: small cases only."""
+    tid, rev, ex_off, xs, xe = cols
+    return [(int(tid[i]), int(rev[i]), [(int(xs[k]), int(xe[k])) for k in range(int(ex_off[i]), int(ex_off[i + 1]))]) for i in range(len(tid))]
+
+
+def heads_columns(cols):
+    """heads() of columns in order, by a running maximum over (tid, end) written as tid * 2^32 + end (coordinates are below 2^31)."""
+    tid, _rev, ex_off, xs, xe = cols
+    if len(tid) == 0:
+        return np.zeros(0, np.uint8)
+    t = tid.astype(np.int64) * (1 << 32)                       # tid in [-1, 2^31): the product stays inside int64
+    start, end = t + xs[ex_off[:-1]], t + xe[ex_off[1:] - 1]
+    out = np.ones(len(tid), np.uint8)
+    out[1:] = start[1:] > np.maximum.accumulate(end)[:-1]
+    return out
+
+
 def heads(trans):
     """Of input in order: 1 where a transcript starts beyond every earlier end on its chromosome (or is the first of all)."""
     out, reach = [], None
