@@ -9,9 +9,8 @@
 //   (k_scan_u32 over the line lengths: line offsets and the batch's byte count)
 //   k_bed_write           one workgroup per L2R_BED_TILE consecutive records, whose text is one contiguous span of the output.  One thread
 //                         per record walks its CIGAR again (cheaper than storing every block) and writes digits, names and punctuation
-//                         into an LDS image of the span; the workgroup then streams the image out in aligned 16-byte stores, byte stores
-//                         only for the span's head and tail.  A span beyond L2R_BED_LDS_BYTES (long names, hundreds of blocks) is written
-//                         line by line straight to the text.
+//                         into the LDS image of the span, which the workgroup then streams out (l2r_text.hip.h).  A span beyond
+//                         L2R_BED_LDS_BYTES (long names, hundreds of blocks) is written line by line straight to the text.
 //
 // The rule of a line is stated in l2r_bedplan.hip.h.  A domain error (reference outside the table, negative position, operation code above
 // 8, end beyond 2147483647) goes into one word by atomicMin on the record index; the host names its kind.  Sums are 64 bit in the measure
@@ -22,12 +21,13 @@
 #include <stdint.h>
 
 #include "../../include/lr2rmats_hip.h"
+#include "l2r_bedplan.hip.h"
+#include "l2r_text.hip.h"
 
 namespace l2r {
 
 constexpr int BED_TILE = L2R_BED_TILE;                  // records, and threads, of one workgroup of k_bed_write
 constexpr uint32_t BED_LDS = L2R_BED_LDS_BYTES;         // bytes of a tile's text the LDS image holds
-constexpr uint32_t BED_ADV = 0x18du;                    // bit op: M D N = X move along the reference
 static_assert(BED_TILE % 64 == 0 && BED_TILE <= 1024 && BED_LDS % 16 == 0 && BED_LDS + 16 <= 65536, "k_bed_write: one workgroup, one LDS image");
 
 // One batch on the device.  cig / names hold the batch's own words and bytes: record i's are [cig_off[i] - cig_base, cig_off[i + 1] - cig_base).
@@ -41,13 +41,6 @@ struct BedIn {
 };
 // what k_bed_measure leaves per record: len is scanned in place into the line offsets (n + 1 words)
 struct BedMeasure { uint32_t *len, *n_blocks, *span, *size_len; };
-
-__device__ __forceinline__ uint32_t bed_digits(uint32_t v)
-{
-    return v < 10u ? 1u : v < 100u ? 2u : v < 1000u ? 3u : v < 10000u ? 4u : v < 100000u ? 5u : v < 1000000u ? 6u : v < 10000000u ? 7u : v < 100000000u ? 8u : v < 1000000000u ? 9u : 10u;
-}
-// (a number beyond 32 bits belongs to a record whose end is an error: any count will do)
-__device__ __forceinline__ uint32_t bed_digits64(uint64_t v) { return v > 0xffffffffull ? 10u : bed_digits((uint32_t)v); }
 
 __device__ __forceinline__ uint64_t bed_shfl64(uint64_t v, int lane)
 {
@@ -78,10 +71,10 @@ void k_bed_measure(BedIn in, BedMeasure out, uint32_t *__restrict__ bad_record)
         for (int64_t k = c0; k < c1; ++k) {
             const uint32_t w = in.cig[k], op = w & 0xfu, l = w >> 4;
             bad |= op > 8u;
-            if (op == 3u) { size_len += bed_digits64(blen) + 1u; cur += l; start_len += bed_digits64(cur) + 1u; blen = 0; ++n_blocks; }
-            else if ((BED_ADV >> op) & 1u) { cur += l; blen += l; }
+            if (op == 3u) { size_len += text_digits64(blen) + 1u; cur += l; start_len += text_digits64(cur) + 1u; blen = 0; ++n_blocks; }
+            else if ((BED_ADVANCE >> op) & 1u) { cur += l; blen += l; }
         }
-        size_len += bed_digits64(blen);
+        size_len += text_digits64(blen);
     } else {
         uint64_t block_start = 0;                                   // where the block that is open at the round's start began
         uint32_t my_size = 0u, my_start = 0u;
@@ -90,7 +83,7 @@ void k_bed_measure(BedIn in, BedMeasure out, uint32_t *__restrict__ bad_record)
             const bool valid = k < c1;
             const uint32_t w = valid ? in.cig[k] : 0u, op = w & 0xfu, l = w >> 4;
             bad |= op > 8u;
-            const uint32_t adv = ((BED_ADV >> op) & 1u) ? l : 0u;
+            const uint32_t adv = ((BED_ADVANCE >> op) & 1u) ? l : 0u;
             const bool is_n = valid && op == 3u;
             // 64 advances of up to 2^28 - 1: two 32-bit scans of their halves are exact
             const uint64_t incl = cur + (uint64_t)wave_inclusive_scan(adv & 0xffffu) + ((uint64_t)wave_inclusive_scan(adv >> 16) << 16);
@@ -98,13 +91,13 @@ void k_bed_measure(BedIn in, BedMeasure out, uint32_t *__restrict__ bad_record)
             const unsigned long long below = m & ((1ull << lane) - 1ull);
             const uint64_t prev = bed_shfl64(incl, below ? 63 - __clzll((long long)below) : 0);
             if (is_n) {
-                my_size += bed_digits64(incl - l - (below ? prev : block_start)) + 1u;
-                my_start += bed_digits64(incl) + 1u;
+                my_size += text_digits64(incl - l - (below ? prev : block_start)) + 1u;
+                my_start += text_digits64(incl) + 1u;
             }
             if (m) { block_start = bed_shfl64(incl, 63 - __clzll((long long)m)); n_blocks += (uint32_t)__popcll(m); }
             cur = bed_shfl64(incl, 63);
         }
-        size_len = wave_sum(my_size) + bed_digits64(cur - block_start);
+        size_len = wave_sum(my_size) + text_digits64(cur - block_start);
         start_len += wave_sum(my_start);
         bad = __any(bad) != 0;
         if (lane) return;
@@ -115,19 +108,10 @@ void k_bed_measure(BedIn in, BedMeasure out, uint32_t *__restrict__ bad_record)
     if (bad) atomicMin(bad_record, (uint32_t)i);
     else {
         const uint32_t chrom = (uint32_t)(in.ref_off[tid + 1] - in.ref_off[tid]), name = (uint32_t)(in.name_off[i + 1] - in.name_off[i]);
-        len = chrom + 2u * (bed_digits((uint32_t)pos) + bed_digits((uint32_t)end)) + name + ((f & 0xc0u) ? 2u : 0u) + bed_digits(in.mapq[i]) + 1u + in.color_len +
-              bed_digits(n_blocks) + size_len + start_len + 12u;
+        len = chrom + 2u * (text_digits((uint32_t)pos) + text_digits((uint32_t)end)) + name + ((f & 0xc0u) ? 2u : 0u) + text_digits(in.mapq[i]) + 1u + in.color_len +
+              text_digits(n_blocks) + size_len + start_len + 12u;
     }
     out.len[i] = len; out.n_blocks[i] = n_blocks; out.span[i] = (uint32_t)cur; out.size_len[i] = size_len;
-}
-
-// the decimal digits of v at p; returns the byte behind them
-__device__ __forceinline__ uint8_t *bed_put_num(uint8_t *p, uint32_t v)
-{
-    const uint32_t d = bed_digits(v);
-    uint8_t *q = p + d;
-    do { *--q = (uint8_t)('0' + v % 10u); v /= 10u; } while (v);
-    return p + d;
 }
 
 // The line of the mapped record i at dst (LDS or the text itself): exactly the bytes k_bed_measure counted.
@@ -137,26 +121,26 @@ __device__ __forceinline__ void bed_put_line(uint8_t *dst, const BedIn &in, int6
     const int32_t tid = in.tid[i];
     uint8_t *p = dst;
     for (int64_t k = in.ref_off[tid]; k < in.ref_off[tid + 1]; ++k) *p++ = in.ref_names[k];
-    *p++ = '\t'; p = bed_put_num(p, pos); *p++ = '\t'; p = bed_put_num(p, end); *p++ = '\t';
+    *p++ = '\t'; p = text_put_num(p, pos); *p++ = '\t'; p = text_put_num(p, end); *p++ = '\t';
     for (int64_t k = in.name_off[i] - in.name_base; k < in.name_off[i + 1] - in.name_base; ++k) *p++ = in.names[k];
     if (f & 0xc0u) { *p++ = '/'; *p++ = (f & 0x40u) ? '1' : '2'; }
-    *p++ = '\t'; p = bed_put_num(p, in.mapq[i]); *p++ = '\t'; *p++ = (f & 16u) ? '-' : '+';
-    *p++ = '\t'; p = bed_put_num(p, pos); *p++ = '\t'; p = bed_put_num(p, end); *p++ = '\t';
+    *p++ = '\t'; p = text_put_num(p, in.mapq[i]); *p++ = '\t'; *p++ = (f & 16u) ? '-' : '+';
+    *p++ = '\t'; p = text_put_num(p, pos); *p++ = '\t'; p = text_put_num(p, end); *p++ = '\t';
     for (uint32_t k = 0; k < in.color_len; ++k) {
         const uint32_t w = k < 4u ? in.color_w0 : k < 8u ? in.color_w1 : in.color_w2;
         *p++ = (uint8_t)(w >> ((k & 3u) * 8u));
     }
-    *p++ = '\t'; p = bed_put_num(p, n_blocks); *p++ = '\t';
+    *p++ = '\t'; p = text_put_num(p, n_blocks); *p++ = '\t';
     // the sizes from p on, the starts behind them: one walk, two cursors
     uint8_t *q = p + size_len;
     *q++ = '\t'; *q++ = '0';
     uint32_t cur = 0u, blen = 0u;
     for (int64_t k = in.cig_off[i] - in.cig_base; k < in.cig_off[i + 1] - in.cig_base; ++k) {
         const uint32_t w = in.cig[k], op = w & 0xfu, l = w >> 4;
-        if (op == 3u) { p = bed_put_num(p, blen); *p++ = ','; cur += l; *q++ = ','; q = bed_put_num(q, cur); blen = 0u; }
-        else if ((BED_ADV >> op) & 1u) { cur += l; blen += l; }
+        if (op == 3u) { p = text_put_num(p, blen); *p++ = ','; cur += l; *q++ = ','; q = text_put_num(q, cur); blen = 0u; }
+        else if ((BED_ADVANCE >> op) & 1u) { cur += l; blen += l; }
     }
-    (void)bed_put_num(p, blen);
+    (void)text_put_num(p, blen);
     *q = '\n';
 }
 
@@ -164,30 +148,23 @@ __global__ __launch_bounds__(BED_TILE)
 void k_bed_write(BedIn in, const uint32_t *__restrict__ off, const uint32_t *__restrict__ n_blocks, const uint32_t *__restrict__ span,
                  const uint32_t *__restrict__ size_len, uint8_t *__restrict__ text, uint32_t *__restrict__ n_direct)
 {
-    __shared__ uint4 s_img[BED_LDS / 16 + 1];           // the span from its 16-byte boundary: `head` unused bytes, then the text
+    __shared__ uint4 s_img[BED_LDS / 16 + 1];           // the image of the tile's span (l2r_text.hip.h)
     const int64_t i0 = (int64_t)blockIdx.x * BED_TILE, i1 = i0 + BED_TILE < in.n ? i0 + BED_TILE : in.n;
     const uint32_t b0 = off[i0], b1 = off[i1], bytes = b1 - b0;
     if (bytes == 0u) return;                            // (a tile of unmapped records)
     const bool direct = bytes > BED_LDS;                // (workgroup-uniform)
-    const uint32_t head = b0 & 15u;
-    uint8_t *img = reinterpret_cast<uint8_t *>(s_img);
+    const uint32_t head = text_head(b0);
     const int64_t i = i0 + threadIdx.x;
     if (i < i1) {
         const uint32_t o = off[i];
         if (off[i + 1] > o) {
             if (direct) bed_put_line(text + o, in, i, n_blocks[i], span[i], size_len[i]);
-            else bed_put_line(img + head + (o - b0), in, i, n_blocks[i], span[i], size_len[i]);
+            else bed_put_line(text_image(s_img, head) + (o - b0), in, i, n_blocks[i], span[i], size_len[i]);
         }
     }
     if (direct) { if (threadIdx.x == 0) atomicAdd(n_direct, 1u); return; }
     __syncthreads();
-    uint8_t *g = text + (b0 - head);                    // 16-byte aligned (the text buffer is)
-    const uint32_t img_end = head + bytes, n_chunk = (img_end + 15u) / 16u;
-    for (uint32_t c = threadIdx.x; c < n_chunk; c += BED_TILE) {
-        const uint32_t lo = c * 16u, hi = lo + 16u;
-        if (lo >= head && hi <= img_end) *reinterpret_cast<uint4 *>(g + lo) = s_img[c];
-        else for (uint32_t b = lo < head ? head : lo; b < (hi < img_end ? hi : img_end); ++b) g[b] = img[b];
-    }
+    text_stream_out<BED_TILE>(s_img, b0, bytes, text);
 }
 
 }  // namespace l2r

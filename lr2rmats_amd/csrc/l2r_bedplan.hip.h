@@ -22,7 +22,7 @@ namespace l2r {
 
 constexpr uint64_t BED_BATCH_BYTES = 0xffffffffull - 63;  // 2^32 - 64: the summed bounds of one device batch stay below it (32-bit line offsets)
 constexpr int64_t BED_POS_MAX = 2147483647;               // BAM's own limit of a coordinate
-constexpr uint32_t BED_ADVANCE = 0x18du;                  // bit op: M D N = X move along the reference
+constexpr uint32_t BED_ADVANCE = 0x18du;                  // bit op: M D N = X move along the reference (the kernels of l2r_bed.hip.h too)
 constexpr uint32_t BED_OP_N = 3u;
 
 enum { BED_OK = 0, BED_E_TID, BED_E_POS, BED_E_OP, BED_E_END };     // kinds of a record's domain error, in the order they are looked for

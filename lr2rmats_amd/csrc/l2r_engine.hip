@@ -179,21 +179,55 @@ struct GtfState {
     double stats[17] = {0};                             // l2r_gtf_stats
 };
 
+// The reference-name table of a text command (l2r_bed_begin, l2r_gtftext_begin): a copy on the host, which the command's parameters are
+// re-pointed at and its host route reads, and one on the device
+struct RefNames {
+    std::vector<int64_t> h_off; std::vector<uint8_t> h_names;
+    DevBuf<int64_t> off; DevBuf<uint8_t> names;
+    void set(int32_t n_ref, const int64_t *ref_off, const uint8_t *ref_names)
+    {
+        const size_t R = (size_t)n_ref, NB = R ? (size_t)ref_off[R] : 0;
+        h_off.assign(R + 1, 0);
+        for (size_t k = 0; k <= R && R; ++k) h_off[k] = ref_off[k];
+        h_names.assign(NB + 1, 0);
+        if (NB) memcpy(h_names.data(), ref_names, NB);
+    }
+    int upload(l2r_ctx *c);                             // (behind l2r_ctx) queued on the context stream
+};
+
+// The text a command has produced (l2r_bed_lines, l2r_gtftext_lines), in HBM or on the host where the host route made it, until text_out
+// fetches it.  TEXT_SLACK bytes lie behind the text in HBM; under L2R_CHECK they hold a pattern that the write kernel must leave alone.
+constexpr size_t TEXT_SLACK = 64;
+constexpr uint8_t TEXT_GUARD_BYTE = 0xa5;
+struct TextOut {
+    DevBuf<uint4> text;                                 // 16-byte aligned (text_stream_out of l2r_text.hip.h relies on it)
+    std::vector<uint8_t> host_text;
+    bool have = false, on_host = false;
+    int64_t n_bytes = 0;
+    uint8_t guard[TEXT_SLACK];                          // fetch_guard's copy
+    void reset() { have = false; on_host = false; n_bytes = 0; host_text.clear(); }
+    int reserve(size_t B) { return text.ensure((B + TEXT_SLACK + 15) / 16); }
+    uint8_t *bytes() const { return reinterpret_cast<uint8_t *>(text.p); }
+    void take_host() { have = true; on_host = true; n_bytes = (int64_t)host_text.size(); }
+    void take_device(size_t B) { have = true; n_bytes = (int64_t)B; }
+    // (behind l2r_ctx) the guard behind B bytes of text: filled in front of the write kernel, fetched behind it -- queued on the context
+    // stream -- and compared once the stream has been waited for.  Without L2R_CHECK none of them touches the device.
+    hipError_t arm_guard(const l2r_ctx *c, size_t B);
+    hipError_t fetch_guard(const l2r_ctx *c, size_t B);
+    bool guard_intact(const l2r_ctx *c) const;
+};
+
 // `bam2bed` (l2r_bed.hip.h): the reference names and the colour of l2r_bed_begin, the columns of one batch, what k_bed_measure leaves per
 // record, and the text of the last l2r_bed_lines (in HBM, or on the host where the host route made it) until l2r_bed_text_out fetches it.
 // The buffers belong to the context, grow on demand and are used again by the next batch.
 struct BedState {
     bool begun = false;
-    l2r_bed_params prm{};                               // ref_off / ref_names point into the two vectors
-    std::vector<int64_t> h_ref_off; std::vector<uint8_t> h_ref_names;
-    DevBuf<int64_t> ref_off; DevBuf<uint8_t> ref_names;
+    l2r_bed_params prm{};                               // ref_off / ref_names point into ref's vectors
+    RefNames ref;
     DevBuf<uint16_t> flag; DevBuf<int32_t> tid, pos; DevBuf<uint8_t> mapq, names; DevBuf<int64_t> cig_off, name_off; DevBuf<uint32_t> cig;      // one batch
     DevBuf<uint32_t> off, n_blocks, span, size_len;     // per record; off: the line lengths, scanned in place (n + 1 words)
     DevBuf<uint32_t> word;                              // BEDW_*
-    DevBuf<uint4> text;                                 // the text, 16-byte aligned, BED_SLACK bytes behind it
-    bool have_text = false, text_on_host = false;
-    int64_t n_bytes = 0;
-    std::vector<uint8_t> host_text;                     // the host route's text
+    TextOut out;
     StageTimer clk;
     double stats[11] = {0};                             // l2r_bed_stats
 };
@@ -219,11 +253,11 @@ struct UniqState {
 // l2r_gtftext_rows and holds until the next; only the host route keeps copies of the columns (h).  The buffers belong to the context,
 // grow on demand and are used again.
 struct GtxState {
-    bool begun = false, have_rows = false, have_blocks = false, have_text = false, text_on_host = false, on_host = false;
+    bool begun = false, have_rows = false, have_blocks = false, on_host = false;
     bool run_chains = false;                            // rows came with xs == NULL: the exon chains of the context's last l2r_run
-    l2r_gtx_params prm{};                               // ref_off / ref_names / src point into the three vectors
-    std::vector<int64_t> h_ref_off; std::vector<uint8_t> h_ref_names, h_src;
-    DevBuf<int64_t> ref_off; DevBuf<uint8_t> ref_names, src;
+    l2r_gtx_params prm{};                               // ref_off / ref_names point into ref's vectors, src into h_src
+    RefNames ref;
+    std::vector<uint8_t> h_src; DevBuf<uint8_t> src;
     int64_t n = 0, m = 0, names_len = 0;
     double exons_per_row = 0;                           // of the run's chains (the host does not see them)
     std::vector<uint32_t> h_nex;                        // uploaded rows: exons per transcript (the form of k_gtx_measure)
@@ -236,9 +270,7 @@ struct GtxState {
     std::vector<uint32_t> h_len;                        // the measured bytes of every block of the selection
     DevBuf<uint32_t> len, fix, off, word;               // per block; off: one batch's lengths, scanned in place; word: GTXC_* and the scan's total
     DevBuf<unsigned long long> word64;                  // k_gtx_measure: the smallest bad block << 4 | kind, the lines
-    DevBuf<uint4> text;                                 // the text, 16-byte aligned, GTX_SLACK bytes behind it
-    int64_t n_bytes = 0;
-    std::vector<uint8_t> host_text;
+    TextOut out;
     StageTimer clk;
     double stats[12] = {0};                             // l2r_gtftext_stats
 };
@@ -505,6 +537,66 @@ template <typename T> static int to_dev(l2r_ctx *c, DevBuf<T> &b, const T *src, 
     return 0;
 }
 template <typename T> static int put_dev(l2r_ctx *c, DevBuf<T> &b, const std::vector<T> &v) { return to_dev(c, b, v.data(), v.size()); }
+
+// The tail of an entry point of a table command.  rc: what uploads and launches came to; where that is 0 the downloads are queued.  The
+// stream is waited for in any case (the host columns are the caller's, device buffers may be the caller's locals), and the first error is
+// the result.
+struct Download { void *dst; const void *src; size_t bytes; };
+static int download_all(l2r_ctx *c, int rc, std::initializer_list<Download> list, const char *who)
+{
+    hipError_t e = hipSuccess;
+    if (!rc) for (const Download &d : list) if (e == hipSuccess && d.bytes) e = hipMemcpyAsync(d.dst, d.src, d.bytes, hipMemcpyDeviceToHost, c->stream);
+    const hipError_t sync = hipStreamSynchronize(c->stream);
+    if (e == hipSuccess) e = sync;
+    if (!rc && e != hipSuccess) rc = fail(-2, "[%s] %s", who, hipGetErrorString(e));
+    return rc;
+}
+
+static bool env_on(const char *name) { const char *e = getenv(name); return e && atoi(e) != 0; }
+
+// The form of a measure kernel (k_fusion_seg, k_bed_measure, k_gtx_measure): one wave per item where the items are long, above 32 words
+// on average -- the bound of l2r_upload_reads' wide_cigar (upload_plan, l2r_plan.hip.h).  env (L2R_FUSION_WAVE, L2R_BED_WAVE,
+// L2R_GTX_WAVE) = 0|1 says otherwise: tests, tools/bench_*.py
+static bool wave_form(double per_item, const char *env)
+{
+    if (const char *e = getenv(env)) return atoi(e) != 0;
+    return per_item > 32.0;
+}
+
+// what is behind the l2r_*_stats of the table commands: the `have` words of src, then zeros
+static int stats_out(const double *src, int have, double *out, int n, const char *who)
+{
+    if (!src || !out || n < 0) return fail(-1, "[%s] bad argument", who);
+    for (int k = 0; k < n; ++k) out[k] = k < have ? src[k] : 0.0;
+    return 0;
+}
+
+int RefNames::upload(l2r_ctx *c)
+{
+    if (int rc = put_dev(c, off, h_off)) return rc;
+    return put_dev(c, names, h_names);
+}
+
+hipError_t TextOut::arm_guard(const l2r_ctx *c, size_t B) { return c->check_stages ? hipMemsetAsync(bytes() + B, TEXT_GUARD_BYTE, TEXT_SLACK, c->stream) : hipSuccess; }
+hipError_t TextOut::fetch_guard(const l2r_ctx *c, size_t B) { return c->check_stages ? hipMemcpyAsync(guard, bytes() + B, TEXT_SLACK, hipMemcpyDeviceToHost, c->stream) : hipSuccess; }
+bool TextOut::guard_intact(const l2r_ctx *c) const
+{
+    if (c->check_stages) for (size_t k = 0; k < TEXT_SLACK; ++k) if (guard[k] != TEXT_GUARD_BYTE) return false;
+    return true;
+}
+
+// What is behind l2r_bed_text_out and l2r_gtftext_out: the text into the caller's `cap` bytes.  arg_code: of an argument or order error.
+static int text_out(l2r_ctx *c, const TextOut &t, uint8_t *text, int64_t cap, const char *who, const char *lines, int arg_code)
+{
+    if (!t.have) return fail(arg_code, "[%s] no text: the last %s failed, or none was made", who, lines);
+    if (cap < t.n_bytes) return fail(arg_code, "[%s] room for %lld bytes, the last %s left %lld", who, (long long)cap, lines, (long long)t.n_bytes);
+    if (t.n_bytes == 0) return 0;
+    if (!text) return fail(arg_code, "[%s] null text", who);
+    if (t.on_host) { memcpy(text, t.host_text.data(), (size_t)t.n_bytes); return 0; }
+    const hipError_t e = hipSetDevice(c->device);
+    if (e != hipSuccess) return fail(-2, "[%s] hipSetDevice: %s", who, hipGetErrorString(e));
+    return download_all(c, 0, {{text, t.text.p, (size_t)t.n_bytes}}, who);
+}
 
 extern "C" {
 
@@ -1614,17 +1706,6 @@ int l2r_classify(l2r_ctx *c, const l2r_reads *reads, l2r_result *res)
 }
 
 // ---------------------------------------------------------------------------------------------- filter
-extern "C++" {
-static bool env_on(const char *name) { const char *e = getenv(name); return e && atoi(e) != 0; }
-
-// what is behind l2r_fusion_stats, l2r_sj_stats, l2r_sort_stats, l2r_name_stats and l2r_gtf_stats: the `have` words of src, then zeros
-static int stats_out(const double *src, int have, double *out, int n, const char *who)
-{
-    if (!src || !out || n < 0) return fail(-1, "[%s] bad argument", who);
-    for (int k = 0; k < n; ++k) out[k] = k < have ? src[k] : 0.0;
-    return 0;
-}
-
 // slots of l2r_fusion_stats
 enum { FUS_WAVE = 0, FUS_K_SEG, FUS_K_SELECT, FUS_K_FILTER_SCORE, FUS_K_FILTER_SELECT, FUS_N };
 
@@ -1634,20 +1715,6 @@ static int fusion_begin(l2r_ctx *c, int slot)
 {
     c->fusion_stats[slot] = 0;
     return c->fusion_clk.begin(env_on("L2R_FUSION_TIMING"), false);
-}
-
-// The tail of a `filter` / `fusion` entry point.  rc: what uploads and launch came to; where that is 0 the downloads are queued.  The
-// stream is waited for in any case (the device buffers and host vectors are the caller's locals), and the first error is the result.
-struct Download { void *dst; const void *src; size_t bytes; };
-static int download_all(l2r_ctx *c, int rc, std::initializer_list<Download> list, const char *who)
-{
-    hipError_t e = hipSuccess;
-    if (!rc) for (const Download &d : list) if (e == hipSuccess && d.bytes) e = hipMemcpyAsync(d.dst, d.src, d.bytes, hipMemcpyDeviceToHost, c->stream);
-    const hipError_t sync = hipStreamSynchronize(c->stream);
-    if (e == hipSuccess) e = sync;
-    if (!rc && e != hipSuccess) rc = fail(-2, "[%s] %s", who, hipGetErrorString(e));
-    return rc;
-}
 }
 
 int l2r_filter_score(l2r_ctx *c, const l2r_filter_records *r, const l2r_filter_params *prm, const l2r_filter_spans *rm,
@@ -1711,9 +1778,7 @@ int l2r_fusion_segments(l2r_ctx *c, const l2r_fusion_records *r, int32_t *read_s
     const size_t N = (size_t)r->n;
     if (N == 0) return 0;
     HIP_TRY(hipSetDevice(c->device));
-    // one wave per record where the CIGARs are long (the bound of l2r_upload_reads' wide_cigar); L2R_FUSION_WAVE=0|1: tests, tools/bench_fusion.py
-    bool wave = (double)r->n_cigar / (double)N > 32.0;
-    if (const char *e = getenv("L2R_FUSION_WAVE")) wave = atoi(e) != 0;
+    const bool wave = wave_form((double)r->n_cigar / (double)N, "L2R_FUSION_WAVE");
     DevBuf<uint16_t> d_flag; DevBuf<int32_t> d_pos, d_out; DevBuf<int64_t> d_off; DevBuf<uint32_t> d_cig;
     int rc = 0;
     if ((rc = to_dev(c, d_flag, r->flag, N)) || (rc = to_dev(c, d_pos, r->pos, N)) || (rc = to_dev(c, d_off, r->cig_off, N + 1)) ||
@@ -2664,26 +2729,19 @@ enum { BEDS_RECORDS = 0, BEDS_LINES, BEDS_BYTES, BEDS_WAVE, BEDS_TILES_LDS, BEDS
 static_assert(BEDS_N == sizeof(BedState::stats) / sizeof(double) && BEDS_K_MEASURE == 8, "l2r_bed_stats: the words of include/lr2rmats_hip.h");
 // words of BedState::word
 enum { BEDW_BAD = 0, BEDW_TOTAL, BEDW_DIRECT, BEDW_N };
-constexpr size_t BED_SLACK = 64;                        // bytes behind the text; L2R_CHECK: a pattern k_bed_write must leave alone
-constexpr uint8_t BED_GUARD_BYTE = 0xa5;
 
 int l2r_bed_begin(l2r_ctx *c, const l2r_bed_params *p)
 {
     if (!c) return fail(-1, "[l2r_bed_begin] null argument");
     BedState &m = c->bed;
-    m.begun = false; m.have_text = false;
+    m.begun = false; m.out.have = false;
     {   std::string msg;
         if (bed_check_params(p, msg)) return fail(-1, "%s", msg.c_str()); }
-    const size_t R = (size_t)p->n_ref, NB = R ? (size_t)p->ref_off[R] : 0;
-    m.h_ref_off.assign(R + 1, 0);
-    for (size_t k = 0; k <= R && R; ++k) m.h_ref_off[k] = p->ref_off[k];
-    m.h_ref_names.assign(NB + 1, 0);
-    if (NB) memcpy(m.h_ref_names.data(), p->ref_names, NB);
+    m.ref.set(p->n_ref, p->ref_off, p->ref_names);
     m.prm = *p;
-    m.prm.ref_off = m.h_ref_off.data(); m.prm.ref_names = m.h_ref_names.data();
+    m.prm.ref_off = m.ref.h_off.data(); m.prm.ref_names = m.ref.h_names.data();
     HIP_TRY(hipSetDevice(c->device));
-    int rc;
-    if ((rc = put_dev(c, m.ref_off, m.h_ref_off)) || (rc = put_dev(c, m.ref_names, m.h_ref_names))) return rc;
+    if (int rc = m.ref.upload(c)) return rc;
     HIP_TRY(hipStreamSynchronize(c->stream));
     m.begun = true;
     return 0;
@@ -2694,7 +2752,7 @@ int l2r_bed_lines(l2r_ctx *c, const l2r_bed_records *r, int64_t *n_lines, int64_
     if (!c || !n_lines || !n_bytes) return fail(-1, "[l2r_bed_lines] null argument");
     BedState &m = c->bed;
     for (double &v : m.stats) v = 0;
-    m.have_text = false; m.text_on_host = false; m.n_bytes = 0; m.host_text.clear();
+    m.out.reset();
     if (!m.begun) return fail(-1, "[l2r_bed_lines] no l2r_bed_begin in front");
     {   std::string msg;
         if (bed_check_records(r, msg)) return fail(-1, "%s", msg.c_str()); }
@@ -2704,7 +2762,7 @@ int l2r_bed_lines(l2r_ctx *c, const l2r_bed_records *r, int64_t *n_lines, int64_
     const char *route = getenv("L2R_BED_ROUTE");
     const bool on_host = route && strcmp(route, "host") == 0;
     m.stats[BEDS_ROUTE] = on_host ? 1 : 0;
-    if (N == 0) { m.have_text = true; m.text_on_host = true; return 0; }
+    if (N == 0) { m.out.take_host(); return 0; }
     if (N > (size_t)0xffffffffu - 1u) return fail(-1, "[l2r_bed_lines] a batch of %zu records (at most 2^32 - 2)", N);
     if (bed_batch_bound(r, &m.prm) >= BED_BATCH_BYTES)
         return fail(-1, "[l2r_bed_lines] the batch: the summed bounds of its %zu lines reach 2^32 - 64 bytes (cut it with l2r_bed_cut)", N);
@@ -2712,10 +2770,10 @@ int l2r_bed_lines(l2r_ctx *c, const l2r_bed_records *r, int64_t *n_lines, int64_
     for (size_t i = 0; i < N; ++i) lines += (r->flag[i] & 4u) ? 0 : 1;
     if (on_host) {
         std::string msg;
-        if (bed_lines_host(r, &m.prm, m.host_text, nullptr, msg)) { m.host_text.clear(); return fail(-1, "%s", msg.c_str()); }
-        m.have_text = true; m.text_on_host = true; m.n_bytes = (int64_t)m.host_text.size();
-        m.stats[BEDS_LINES] = (double)lines; m.stats[BEDS_BYTES] = (double)m.n_bytes;
-        *n_lines = lines; *n_bytes = m.n_bytes;
+        if (bed_lines_host(r, &m.prm, m.out.host_text, nullptr, msg)) { m.out.host_text.clear(); return fail(-1, "%s", msg.c_str()); }
+        m.out.take_host();
+        m.stats[BEDS_LINES] = (double)lines; m.stats[BEDS_BYTES] = (double)m.out.n_bytes;
+        *n_lines = lines; *n_bytes = m.out.n_bytes;
         return 0;
     }
     HIP_TRY(hipSetDevice(c->device));
@@ -2723,9 +2781,7 @@ int l2r_bed_lines(l2r_ctx *c, const l2r_bed_records *r, int64_t *n_lines, int64_
     if ((rc = m.clk.begin(env_on("L2R_BED_TIMING"), c->check_stages))) return rc;
     const int64_t cig_base = r->cig_off[0], name_base = r->name_off[0];
     const size_t n_cig = (size_t)(r->cig_off[N] - cig_base), n_name = (size_t)(r->name_off[N] - name_base);
-    // one wave per record where the CIGARs are long (the bound of l2r_upload_reads' wide_cigar); L2R_BED_WAVE=0|1: tests, tools/bench_bed.py
-    bool wave = (double)n_cig / (double)N > 32.0;
-    if (const char *e = getenv("L2R_BED_WAVE")) wave = atoi(e) != 0;
+    const bool wave = wave_form((double)n_cig / (double)N, "L2R_BED_WAVE");
     m.stats[BEDS_WAVE] = wave ? 1 : 0;
     if ((rc = to_dev(c, m.flag, r->flag, N)) || (rc = to_dev(c, m.tid, r->tid, N)) || (rc = to_dev(c, m.pos, r->pos, N)) || (rc = to_dev(c, m.mapq, r->mapq, N)) ||
         (rc = to_dev(c, m.cig_off, r->cig_off, N + 1)) || (rc = to_dev(c, m.cig, n_cig ? r->cig + cig_base : nullptr, n_cig)) ||
@@ -2737,7 +2793,7 @@ int l2r_bed_lines(l2r_ctx *c, const l2r_bed_records *r, int64_t *n_lines, int64_
     BedIn in{};
     in.n = (int64_t)N; in.flag = m.flag.p; in.tid = m.tid.p; in.pos = m.pos.p; in.mapq = m.mapq.p;
     in.cig_off = m.cig_off.p; in.cig = m.cig.p; in.cig_base = cig_base; in.name_off = m.name_off.p; in.names = m.names.p; in.name_base = name_base;
-    in.n_ref = m.prm.n_ref; in.ref_off = m.ref_off.p; in.ref_names = m.ref_names.p;
+    in.n_ref = m.prm.n_ref; in.ref_off = m.ref.off.p; in.ref_names = m.ref.names.p;
     in.color_len = (uint32_t)m.prm.color_len;
     {   uint32_t w[3] = {0, 0, 0};
         memcpy(w, m.prm.color, 12);
@@ -2750,11 +2806,7 @@ int l2r_bed_lines(l2r_ctx *c, const l2r_bed_records *r, int64_t *n_lines, int64_
     });
     if (!rc) rc = m.clk.launch(c, &m.stats[BEDS_K_SCAN], [&] { scan_u32(c, m.off.p, (int64_t)N, m.word.p + BEDW_TOTAL); });
     uint32_t w[BEDW_N] = {0, 0, 0};
-    hipError_t e = rc ? hipSuccess : hipMemcpyAsync(w, m.word.p, sizeof w, hipMemcpyDeviceToHost, c->stream);
-    const hipError_t sync = hipStreamSynchronize(c->stream);
-    if (rc) return rc;
-    if (e == hipSuccess) e = sync;
-    if (e != hipSuccess) return fail(-2, "[l2r_bed_lines] %s", hipGetErrorString(e));
+    if ((rc = download_all(c, rc, {{w, m.word.p, sizeof w}}, "l2r_bed_lines"))) return rc;
     if (w[BEDW_BAD] != 0xffffffffu) {
         std::string msg;
         if ((size_t)w[BEDW_BAD] >= N || bed_record_error(r, &m.prm, (int64_t)w[BEDW_BAD], msg) == BED_OK) return fail(-2, "[l2r_bed_lines] the device names record %u of %zu", w[BEDW_BAD], N);
@@ -2763,23 +2815,22 @@ int l2r_bed_lines(l2r_ctx *c, const l2r_bed_records *r, int64_t *n_lines, int64_
     const size_t B = w[BEDW_TOTAL];
     if ((uint64_t)B >= BED_BATCH_BYTES) return fail(-2, "[l2r_bed_lines] %zu bytes of text behind a bound below 2^32 - 64", B);
     const unsigned n_tiles = (unsigned)((N + BED_TILE - 1) / BED_TILE);
-    if (m.text.ensure((B + BED_SLACK + 15) / 16)) return -2;
-    uint8_t *text8 = reinterpret_cast<uint8_t *>(m.text.p);
-    if (c->check_stages) HIP_TRY(hipMemsetAsync(text8 + B, BED_GUARD_BYTE, BED_SLACK, c->stream));
+    if (m.out.reserve(B)) return -2;
+    uint8_t *text8 = m.out.bytes();
+    HIP_TRY(m.out.arm_guard(c, B));
     if (B && (rc = m.clk.launch(c, &m.stats[BEDS_K_WRITE], [&] {
             hipLaunchKernelGGL(k_bed_write, dim3(n_tiles), dim3(BED_TILE), 0, c->stream, in, (const uint32_t *)m.off.p, (const uint32_t *)m.n_blocks.p, (const uint32_t *)m.span.p,
                                (const uint32_t *)m.size_len.p, text8, m.word.p + BEDW_DIRECT);
         }))) { (void)hipStreamSynchronize(c->stream); return rc; }
-    uint8_t guard[BED_SLACK];
     uint32_t n_direct = 0;
     HIP_TRY(hipMemcpyAsync(&n_direct, m.word.p + BEDW_DIRECT, sizeof n_direct, hipMemcpyDeviceToHost, c->stream));
-    if (c->check_stages) HIP_TRY(hipMemcpyAsync(guard, text8 + B, BED_SLACK, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(m.out.fetch_guard(c, B));
     HIP_TRY(hipStreamSynchronize(c->stream));
-    if (c->check_stages) for (size_t k = 0; k < BED_SLACK; ++k) if (guard[k] != BED_GUARD_BYTE) m.stats[BEDS_GUARD] = 0;
+    if (!m.out.guard_intact(c)) m.stats[BEDS_GUARD] = 0;
     if (n_direct > n_tiles) return fail(-2, "[l2r_bed_lines] %u direct tiles of %u", n_direct, n_tiles);
     m.stats[BEDS_LINES] = (double)lines; m.stats[BEDS_BYTES] = (double)B;
     m.stats[BEDS_TILES_DIRECT] = (double)n_direct; m.stats[BEDS_TILES_LDS] = (double)(n_tiles - n_direct);
-    m.have_text = true; m.n_bytes = (int64_t)B;
+    m.out.take_device(B);
     *n_lines = lines; *n_bytes = (int64_t)B;
     return 0;
 }
@@ -2787,16 +2838,7 @@ int l2r_bed_lines(l2r_ctx *c, const l2r_bed_records *r, int64_t *n_lines, int64_
 int l2r_bed_text_out(l2r_ctx *c, uint8_t *text, int64_t cap)
 {
     if (!c) return fail(-1, "[l2r_bed_text_out] null argument");
-    const BedState &m = c->bed;
-    if (!m.have_text) return fail(-1, "[l2r_bed_text_out] no text: the last l2r_bed_lines failed, or none was made");
-    if (cap < m.n_bytes) return fail(-1, "[l2r_bed_text_out] room for %lld bytes, the last l2r_bed_lines left %lld", (long long)cap, (long long)m.n_bytes);
-    if (m.n_bytes == 0) return 0;
-    if (!text) return fail(-1, "[l2r_bed_text_out] null text");
-    if (m.text_on_host) { memcpy(text, m.host_text.data(), (size_t)m.n_bytes); return 0; }
-    HIP_TRY(hipSetDevice(c->device));
-    HIP_TRY(hipMemcpyAsync(text, m.text.p, (size_t)m.n_bytes, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    return 0;
+    return text_out(c, c->bed.out, text, cap, "l2r_bed_text_out", "l2r_bed_lines", -1);
 }
 
 int l2r_bed_cut(const l2r_bed_records *r, const l2r_bed_params *p, int64_t first, int64_t max_records, int64_t max_bytes, int64_t *n_take)
@@ -2861,11 +2903,7 @@ int l2r_uniq_merge(l2r_ctx *c, const l2r_params *prm, const l2r_uniq_trans *t, i
         hipLaunchKernelGGL(k_uniq_firsts, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, c->stream, (int64_t)N, (const uint32_t *)m.head.p, m.first.p);
     });
     uint32_t w[UQW_N] = {0};
-    hipError_t e = rc ? hipSuccess : hipMemcpyAsync(w, m.word.p, sizeof w, hipMemcpyDeviceToHost, c->stream);
-    hipError_t sync = hipStreamSynchronize(c->stream);
-    if (rc) return rc;
-    if (e == hipSuccess) e = sync;
-    if (e != hipSuccess) return fail(-2, "[l2r_uniq_merge] %s", hipGetErrorString(e));
+    if ((rc = download_all(c, rc, {{w, m.word.p, sizeof w}}, "l2r_uniq_merge"))) return rc;
     if (w[UQW_UNSORTED]) {                              // (tid, start) descends somewhere: the exact host routine
         for (int k = UQS_K_CUT; k < UQS_N; ++k) m.stats[k] = 0;
         uniq_on_host(m, t, p, false);
@@ -2884,11 +2922,7 @@ int l2r_uniq_merge(l2r_ctx *c, const l2r_params *prm, const l2r_uniq_trans *t, i
         hipLaunchKernelGGL(k_uniq_take, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, c->stream, (int64_t)N, (const uint32_t *)m.head.p, (const uint32_t *)m.first.p,
                            (const uint32_t *)m.len.p, L, m.uniq_of.p, m.u_src.p, m.u_start.p, m.u_end.p, m.u_cov.p);
     });
-    e = rc ? hipSuccess : hipMemcpyAsync(w, m.word.p, sizeof w, hipMemcpyDeviceToHost, c->stream);
-    sync = hipStreamSynchronize(c->stream);
-    if (rc) return rc;
-    if (e == hipSuccess) e = sync;
-    if (e != hipSuccess) return fail(-2, "[l2r_uniq_merge] %s", hipGetErrorString(e));
+    if ((rc = download_all(c, rc, {{w, m.word.p, sizeof w}}, "l2r_uniq_merge"))) return rc;
     const uint64_t hits = (uint64_t)w[UQW_IDENT] + w[UQW_CONTAINED] + w[UQW_SINGLE];
     if ((size_t)w[UQW_UNIQUE] > N || w[UQW_UNIQUE] < C || hits + w[UQW_UNIQUE] != N) return fail(-2, "[l2r_uniq_merge] %u entries and %llu hits of %zu offers", w[UQW_UNIQUE], (unsigned long long)hits, N);
     m.n_unique = (int64_t)w[UQW_UNIQUE];
@@ -2927,30 +2961,24 @@ int l2r_uniq_stats(l2r_ctx *c, double *out, int n) { return stats_out(c ? c->uni
 enum { GXS_BLOCKS = 0, GXS_LINES, GXS_BYTES, GXS_WAVE, GXS_TILES_LDS, GXS_TILES_DIRECT, GXS_ROUTE, GXS_GUARD, GXS_BATCHES, GXS_K_MEASURE, GXS_K_SCAN, GXS_K_WRITE, GXS_N };
 static_assert(GXS_N == sizeof(GtxState::stats) / sizeof(double) && GXS_K_MEASURE == 9, "l2r_gtftext_stats: the words of include/lr2rmats_hip.h");
 constexpr int GTXC_TOTAL = GTXC_N;                      // GtxState::word: k_gtx_write's counters, then the scan's total
-constexpr size_t GTX_SLACK = 64;                        // bytes behind the text; L2R_CHECK: a pattern k_gtx_write must leave alone
-constexpr uint8_t GTX_GUARD_BYTE = 0xa5;
 constexpr int GTX_E_ARG = -4;                           // arguments, order of calls: not -1, which is a domain error (the commands fall back on it)
 
 int l2r_gtftext_begin(l2r_ctx *c, const l2r_gtx_params *p)
 {
     if (!c) return fail(GTX_E_ARG, "[l2r_gtftext_begin] null argument");
     GtxState &m = c->gtx;
-    m.begun = false; m.have_rows = false; m.have_blocks = false; m.have_text = false;
+    m.begun = false; m.have_rows = false; m.have_blocks = false; m.out.have = false;
     for (double &v : m.stats) v = 0;
     {   std::string msg;
         if (gtx_check_params(p, msg)) return fail(GTX_E_ARG, "%s", msg.c_str()); }
-    const size_t R = (size_t)p->n_ref, NB = R ? (size_t)p->ref_off[R] : 0;
-    m.h_ref_off.assign(R + 1, 0);
-    for (size_t k = 0; k <= R && R; ++k) m.h_ref_off[k] = p->ref_off[k];
-    m.h_ref_names.assign(NB + 1, 0);
-    if (NB) memcpy(m.h_ref_names.data(), p->ref_names, NB);
+    m.ref.set(p->n_ref, p->ref_off, p->ref_names);
     m.h_src.assign((size_t)p->src_len + 1, 0);
     if (p->src_len) memcpy(m.h_src.data(), p->src, (size_t)p->src_len);
     m.prm = *p;
-    m.prm.ref_off = m.h_ref_off.data(); m.prm.ref_names = m.h_ref_names.data(); m.prm.src = m.h_src.data();
+    m.prm.ref_off = m.ref.h_off.data(); m.prm.ref_names = m.ref.h_names.data(); m.prm.src = m.h_src.data();
     HIP_TRY(hipSetDevice(c->device));
     int rc;
-    if ((rc = put_dev(c, m.ref_off, m.h_ref_off)) || (rc = put_dev(c, m.ref_names, m.h_ref_names)) || (rc = put_dev(c, m.src, m.h_src))) return rc;
+    if ((rc = m.ref.upload(c)) || (rc = put_dev(c, m.src, m.h_src))) return rc;
     HIP_TRY(hipStreamSynchronize(c->stream));
     m.begun = true;
     return 0;
@@ -2978,7 +3006,7 @@ int l2r_gtftext_rows(l2r_ctx *c, const l2r_gtx_rows *r)
 {
     if (!c) return fail(GTX_E_ARG, "[l2r_gtftext_rows] null argument");
     GtxState &m = c->gtx;
-    m.have_rows = false; m.have_blocks = false; m.have_text = false;
+    m.have_rows = false; m.have_blocks = false; m.out.have = false;
     if (!m.begun) return fail(GTX_E_ARG, "[l2r_gtftext_rows] no l2r_gtftext_begin in front");
     {   std::string msg;
         if (gtx_check_rows(r, m.prm.form, msg)) return fail(GTX_E_ARG, "%s", msg.c_str()); }
@@ -3039,7 +3067,7 @@ static GtxIn gtx_in(const l2r_ctx *c, const GtxState &m)
     in.names = m.names.p; in.names_len = m.names_len;
     for (int k = 0; k < 4; ++k) in.id[k] = m.id_p[k];
     in.sel = m.has_sel ? m.sel.p : nullptr; in.start = m.has_start ? m.start.p : nullptr; in.end = m.has_end ? m.end.p : nullptr; in.cov = m.has_cov ? m.cov.p : nullptr;
-    in.n_ref = m.prm.n_ref; in.ref_off = m.ref_off.p; in.ref_names = m.ref_names.p; in.src = m.src.p; in.src_len = (uint32_t)m.prm.src_len; in.form = m.prm.form;
+    in.n_ref = m.prm.n_ref; in.ref_off = m.ref.off.p; in.ref_names = m.ref.names.p; in.src = m.src.p; in.src_len = (uint32_t)m.prm.src_len; in.form = m.prm.form;
     return in;
 }
 // ... and the host route's, over its copies
@@ -3056,7 +3084,7 @@ int l2r_gtftext_blocks(l2r_ctx *c, const l2r_gtx_blocks *b, int64_t *n_lines, in
 {
     if (!c || !n_lines || !n_bytes) return fail(GTX_E_ARG, "[l2r_gtftext_blocks] null argument");
     GtxState &m = c->gtx;
-    m.have_blocks = false; m.have_text = false;
+    m.have_blocks = false; m.out.have = false;
     for (int k = 0; k < GXS_N; ++k) if (k != GXS_ROUTE) m.stats[k] = 0;
     m.stats[GXS_GUARD] = 1;
     if (!m.have_rows) return fail(GTX_E_ARG, "[l2r_gtftext_blocks] no l2r_gtftext_rows in front");
@@ -3086,15 +3114,13 @@ int l2r_gtftext_blocks(l2r_ctx *c, const l2r_gtx_blocks *b, int64_t *n_lines, in
         HIP_TRY(hipSetDevice(c->device));
         int rc;
         if ((rc = m.clk.begin(env_on("L2R_GTX_TIMING"), c->check_stages))) return rc;
-        // one wave per block where the selection has more than 32 exons per block on average; L2R_GTX_WAVE=0|1: tests, tools/bench_gtx.py
         double per_block = m.exons_per_row;
         if (!m.run_chains) {
             uint64_t x = 0;
             for (size_t q = 0; q < M; ++q) { const int64_t t = b->sel ? (int64_t)b->sel[q] : (int64_t)q; if (t >= 0 && t < m.n) x += m.h_nex[(size_t)t]; }
             per_block = (double)x / (double)M;
         }
-        bool wave = per_block > 32.0;
-        if (const char *e = getenv("L2R_GTX_WAVE")) wave = atoi(e) != 0;
+        const bool wave = wave_form(per_block, "L2R_GTX_WAVE");    // (exons per block of the selection)
         m.stats[GXS_WAVE] = wave ? 1 : 0;
         if ((m.has_sel && (rc = to_dev(c, m.sel, b->sel, M))) || (m.has_start && (rc = to_dev(c, m.start, b->start, M))) || (m.has_end && (rc = to_dev(c, m.end, b->end, M))) ||
             (m.has_cov && (rc = to_dev(c, m.cov, b->cov, M))) || m.len.ensure(M) || m.fix.ensure(M) || m.word64.ensure(2) || m.word.ensure(GTXC_TOTAL + 1)) rc = rc ? rc : -2;
@@ -3109,12 +3135,7 @@ int l2r_gtftext_blocks(l2r_ctx *c, const l2r_gtx_blocks *b, int64_t *n_lines, in
             else hipLaunchKernelGGL(k_gtx_measure<false>, grid, dim3(256), 0, c->stream, in, meas);
         });
         unsigned long long w[2] = {0, 0};
-        hipError_t e = rc ? hipSuccess : hipMemcpyAsync(w, m.word64.p, sizeof w, hipMemcpyDeviceToHost, c->stream);
-        if (!rc && e == hipSuccess) e = hipMemcpyAsync(m.h_len.data(), m.len.p, M * 4, hipMemcpyDeviceToHost, c->stream);
-        const hipError_t sync = hipStreamSynchronize(c->stream);
-        if (rc) return rc;
-        if (e == hipSuccess) e = sync;
-        if (e != hipSuccess) return fail(-2, "[l2r_gtftext_blocks] %s", hipGetErrorString(e));
+        if ((rc = download_all(c, rc, {{w, m.word64.p, sizeof w}, {m.h_len.data(), m.len.p, M * 4}}, "l2r_gtftext_blocks"))) return rc;
         if (w[0] != ~0ull) {
             const unsigned long long q = w[0] >> 4; const int kind = (int)(w[0] & 15ull);
             if (q >= M || kind <= GTX_OK || kind >= GTX_E_N) return fail(-2, "[l2r_gtftext_blocks] the device names block %llu of %zu, kind %d", q, M, kind);
@@ -3133,7 +3154,7 @@ int l2r_gtftext_lines(l2r_ctx *c, int64_t first, int64_t max_blocks, int64_t max
 {
     if (!c || !n_taken || !n_bytes) return fail(GTX_E_ARG, "[l2r_gtftext_lines] null argument");
     GtxState &m = c->gtx;
-    m.have_text = false; m.text_on_host = false; m.n_bytes = 0; m.host_text.clear();
+    m.out.reset();
     *n_taken = 0; *n_bytes = 0;
     if (!m.have_blocks) return fail(GTX_E_ARG, "[l2r_gtftext_lines] no l2r_gtftext_blocks in front, or it failed");
     int64_t take = 0, sum = 0;
@@ -3146,9 +3167,9 @@ int l2r_gtftext_lines(l2r_ctx *c, int64_t first, int64_t max_blocks, int64_t max
         gtx_host_view(m, hr, cx, hb);
         std::string msg;
         int64_t lines = 0;
-        if (gtx_text_host(&m.prm, &hr, cx, &hb, first, take, m.host_text, &lines, msg)) { m.host_text.clear(); return fail(-1, "%s", msg.c_str()); }
-        if (m.host_text.size() != B) return fail(-5, "[l2r_gtftext_lines] %zu bytes of text, measured %zu", m.host_text.size(), B);
-        m.have_text = true; m.text_on_host = true; m.n_bytes = sum;
+        if (gtx_text_host(&m.prm, &hr, cx, &hb, first, take, m.out.host_text, &lines, msg)) { m.out.host_text.clear(); return fail(-1, "%s", msg.c_str()); }
+        if (m.out.host_text.size() != B) return fail(-5, "[l2r_gtftext_lines] %zu bytes of text, measured %zu", m.out.host_text.size(), B);
+        m.out.take_host();
         m.stats[GXS_LINES] = (double)lines; m.stats[GXS_BYTES] = (double)B; m.stats[GXS_BATCHES] += 1;
         *n_taken = take; *n_bytes = sum;
         return 0;
@@ -3157,29 +3178,28 @@ int l2r_gtftext_lines(l2r_ctx *c, int64_t first, int64_t max_blocks, int64_t max
     HIP_TRY(hipSetDevice(c->device));
     int rc;
     if ((rc = m.clk.begin(env_on("L2R_GTX_TIMING"), c->check_stages))) return rc;
-    if (m.off.ensure(K + 1) || m.text.ensure((B + GTX_SLACK + 15) / 16) || m.word.ensure(GTXC_TOTAL + 1)) return -2;
-    uint8_t *text8 = reinterpret_cast<uint8_t *>(m.text.p);
+    if (m.off.ensure(K + 1) || m.out.reserve(B) || m.word.ensure(GTXC_TOTAL + 1)) return -2;
+    uint8_t *text8 = m.out.bytes();
     HIP_TRY(hipMemcpyAsync(m.off.p, m.len.p + first, K * 4, hipMemcpyDeviceToDevice, c->stream));
     HIP_TRY(hipMemsetAsync(m.word.p, 0, (GTXC_TOTAL + 1) * sizeof(uint32_t), c->stream));
     if ((rc = m.clk.launch(c, &m.stats[GXS_K_SCAN], [&] { scan_u32(c, m.off.p, (int64_t)K, m.word.p + GTXC_TOTAL); }))) { (void)hipStreamSynchronize(c->stream); return rc; }
-    if (c->check_stages) HIP_TRY(hipMemsetAsync(text8 + B, GTX_GUARD_BYTE, GTX_SLACK, c->stream));
+    HIP_TRY(m.out.arm_guard(c, B));
     const unsigned n_tiles = (unsigned)((K + GTX_TILE - 1) / GTX_TILE);
     const GtxIn in = gtx_in(c, m);
     if ((rc = m.clk.launch(c, &m.stats[GXS_K_WRITE], [&] {
             hipLaunchKernelGGL(k_gtx_write, dim3(n_tiles), dim3(GTX_THREADS), 0, c->stream, in, first, take, (const uint32_t *)m.off.p, (const uint32_t *)m.fix.p, text8, m.word.p);
         }))) { (void)hipStreamSynchronize(c->stream); return rc; }
-    uint8_t guard[GTX_SLACK];
     uint32_t w[GTXC_TOTAL + 1] = {0};
     HIP_TRY(hipMemcpyAsync(w, m.word.p, sizeof w, hipMemcpyDeviceToHost, c->stream));
-    if (c->check_stages) HIP_TRY(hipMemcpyAsync(guard, text8 + B, GTX_SLACK, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(m.out.fetch_guard(c, B));
     HIP_TRY(hipStreamSynchronize(c->stream));
-    if (c->check_stages) for (size_t k = 0; k < GTX_SLACK; ++k) if (guard[k] != GTX_GUARD_BYTE) m.stats[GXS_GUARD] = 0;
+    if (!m.out.guard_intact(c)) m.stats[GXS_GUARD] = 0;
     if ((size_t)w[GTXC_TOTAL] != B) return fail(-5, "[l2r_gtftext_lines] the scan left %u bytes, the cut %zu", w[GTXC_TOTAL], B);
     if (w[GTXC_OUTSIDE]) return fail(-5, "[l2r_gtftext_lines] %u lines would have left their tile's span: k_gtx_measure and k_gtx_write disagree", w[GTXC_OUTSIDE]);
     if (w[GTXC_DIRECT] > n_tiles) return fail(-5, "[l2r_gtftext_lines] %u direct tiles of %u", w[GTXC_DIRECT], n_tiles);
     m.stats[GXS_LINES] = (double)w[GTXC_LINES]; m.stats[GXS_BYTES] = (double)B; m.stats[GXS_BATCHES] += 1;
     m.stats[GXS_TILES_DIRECT] = (double)w[GTXC_DIRECT]; m.stats[GXS_TILES_LDS] = (double)(n_tiles - w[GTXC_DIRECT]);
-    m.have_text = true; m.n_bytes = sum;
+    m.out.take_device(B);
     *n_taken = take; *n_bytes = sum;
     return 0;
 }
@@ -3187,16 +3207,7 @@ int l2r_gtftext_lines(l2r_ctx *c, int64_t first, int64_t max_blocks, int64_t max
 int l2r_gtftext_out(l2r_ctx *c, uint8_t *text, int64_t cap)
 {
     if (!c) return fail(GTX_E_ARG, "[l2r_gtftext_out] null argument");
-    const GtxState &m = c->gtx;
-    if (!m.have_text) return fail(GTX_E_ARG, "[l2r_gtftext_out] no text: the last l2r_gtftext_lines failed, or none was made");
-    if (cap < m.n_bytes) return fail(GTX_E_ARG, "[l2r_gtftext_out] room for %lld bytes, the last l2r_gtftext_lines left %lld", (long long)cap, (long long)m.n_bytes);
-    if (m.n_bytes == 0) return 0;
-    if (!text) return fail(GTX_E_ARG, "[l2r_gtftext_out] null text");
-    if (m.text_on_host) { memcpy(text, m.host_text.data(), (size_t)m.n_bytes); return 0; }
-    HIP_TRY(hipSetDevice(c->device));
-    HIP_TRY(hipMemcpyAsync(text, m.text.p, (size_t)m.n_bytes, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    return 0;
+    return text_out(c, c->gtx.out, text, cap, "l2r_gtftext_out", "l2r_gtftext_lines", GTX_E_ARG);
 }
 
 int l2r_gtftext_stats(l2r_ctx *c, double *out, int n) { return stats_out(c ? c->gtx.stats : nullptr, GXS_N, out, n, "l2r_gtftext_stats"); }

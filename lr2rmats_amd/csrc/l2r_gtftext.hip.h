@@ -10,9 +10,9 @@
 //                         the output.  Blocks differ a hundredfold in size, so the tile's LINES are spread over the lanes, not its
 //                         blocks: a scan of the blocks' line counts (LDS) numbers the lines; round by round every lane takes one line,
 //                         finds its block by bisection, its length from `fix` and the digits of its two numbers, and its place by a
-//                         workgroup scan of the round's lengths behind the bytes of the rounds before.  The lines go into an LDS image
-//                         of the span, which the workgroup streams out in aligned 16-byte stores (byte stores only for the span's head
-//                         and tail); a span beyond L2R_GTX_LDS_BYTES is written line by line straight to the text.
+//                         workgroup scan of the round's lengths behind the bytes of the rounds before.  The lines go into the LDS image
+//                         of the span, which the workgroup then streams out (l2r_text.hip.h); a span beyond L2R_GTX_LDS_BYTES is written
+//                         line by line straight to the text.
 //
 // The rule of a block, the order its domain errors are looked for and the length pieces are in l2r_gtftextplan.hip.h.  A domain error goes
 // into one 64-bit word by atomicMin on block << 4 | kind.  The exon chains are either the uploaded ones (ex_off64) or those of the last
@@ -24,8 +24,8 @@
 #include <stdint.h>
 
 #include "../../include/lr2rmats_hip.h"
-#include "l2r_bed.hip.h"
 #include "l2r_gtftextplan.hip.h"
+#include "l2r_text.hip.h"
 
 namespace l2r {
 
@@ -107,19 +107,19 @@ void k_gtx_measure(GtxIn in, GtxMeasure out)
                         for (int64_t j = 0; j < n; ++j) {
                             const int32_t s = j == 0 ? S : in.xs[off + j], x = j == n - 1 ? E : in.xe[off + j];
                             neg |= (s | x) < 0;
-                            dig += bed_digits((uint32_t)s) + bed_digits((uint32_t)x);
+                            dig += text_digits((uint32_t)s) + text_digits((uint32_t)x);
                         }
                     } else {
                         uint32_t mine = 0u;                         // (at most 2^25 exons of 20 digits per lane)
                         for (int64_t j = lane; j < n; j += 64) {
                             const int32_t s = j == 0 ? S : in.xs[off + j], x = j == n - 1 ? E : in.xe[off + j];
                             neg |= (s | x) < 0;
-                            mine += bed_digits((uint32_t)s) + bed_digits((uint32_t)x);
+                            mine += text_digits((uint32_t)s) + text_digits((uint32_t)x);
                         }
                         dig = (uint64_t)wave_sum(mine & 0xffffu) + ((uint64_t)wave_sum(mine >> 16) << 16);
                         neg = __any(neg) != 0;
                     }
-                    bytes = (uint64_t)(n + 1) * fix + gtx_head_extra(in.form, (uint32_t)cov) + bed_digits((uint32_t)S) + bed_digits((uint32_t)E) + dig;
+                    bytes = (uint64_t)(n + 1) * fix + gtx_head_extra(in.form, (uint32_t)cov) + text_digits((uint32_t)S) + text_digits((uint32_t)E) + dig;
                     lines = (uint64_t)n + 1u;
                     if (neg) kind = GTX_E_NEG;
                     else if (bytes >= GTX_BATCH_BYTES) kind = GTX_E_BIG;
@@ -141,13 +141,6 @@ void k_gtx_measure(GtxIn in, GtxMeasure out)
     out.len[q] = (uint32_t)bytes; out.fix[q] = fix;
 }
 
-// s[0 .. N) at p; returns the byte behind them
-template <int N> __device__ __forceinline__ uint8_t *gtx_put_lit(uint8_t *p, const char (&s)[N])
-{
-#pragma unroll
-    for (int k = 0; k < N - 1; ++k) p[k] = (uint8_t)s[k];
-    return p + (N - 1);
-}
 // the name at names + id up to its NUL (k_gtx_measure has found one within 255 bytes)
 __device__ __forceinline__ uint8_t *gtx_put_name(uint8_t *p, const uint8_t *__restrict__ s)
 {
@@ -164,13 +157,13 @@ __device__ __forceinline__ void gtx_put_line(uint8_t *dst, const GtxIn &in, int6
     *p++ = '\t';
     for (uint32_t k = 0; k < in.src_len; ++k) *p++ = in.src[k];
     *p++ = '\t';
-    p = head ? gtx_put_lit(p, "transcript\t") : gtx_put_lit(p, "exon\t");
-    p = bed_put_num(p, a); *p++ = '\t'; p = bed_put_num(p, e);
-    p = gtx_put_lit(p, "\t.\t"); *p++ = in.rev[t] ? '-' : '+'; p = gtx_put_lit(p, "\t.\t");
+    p = head ? text_put_lit(p, "transcript\t") : text_put_lit(p, "exon\t");
+    p = text_put_num(p, a); *p++ = '\t'; p = text_put_num(p, e);
+    p = text_put_lit(p, "\t.\t"); *p++ = in.rev[t] ? '-' : '+'; p = text_put_lit(p, "\t.\t");
     if (in.form == L2R_GTX_PLAIN) {
-        p = gtx_put_lit(p, "gene_id \""); p = gtx_put_name(p, in.names + in.id[0][t]);
-        p = gtx_put_lit(p, "\"; transcript_id \""); p = gtx_put_name(p, in.names + in.id[1][t]);
-        p = gtx_put_lit(p, "\";");
+        p = text_put_lit(p, "gene_id \""); p = gtx_put_name(p, in.names + in.id[0][t]);
+        p = text_put_lit(p, "\"; transcript_id \""); p = gtx_put_name(p, in.names + in.id[1][t]);
+        p = text_put_lit(p, "\";");
     } else {
         bool any = false;
 #pragma unroll
@@ -179,12 +172,12 @@ __device__ __forceinline__ void gtx_put_line(uint8_t *dst, const GtxIn &in, int6
             if (!s[0]) continue;
             if (any) *p++ = ' ';
             any = true;
-            p = c == 0 ? gtx_put_lit(p, "gene_id \"") : c == 1 ? gtx_put_lit(p, "transcript_id \"") : c == 2 ? gtx_put_lit(p, "gene_name \"") : gtx_put_lit(p, "transcript_name \"");
+            p = c == 0 ? text_put_lit(p, "gene_id \"") : c == 1 ? text_put_lit(p, "transcript_id \"") : c == 2 ? text_put_lit(p, "gene_name \"") : text_put_lit(p, "transcript_name \"");
             p = gtx_put_name(p, s);
-            p = gtx_put_lit(p, "\";");
+            p = text_put_lit(p, "\";");
         }
         // (all four names empty: the blank of <C> then stands behind the tab, as emit_gtf_named writes it; the reference would write none)
-        if (head) { p = gtx_put_lit(p, " transcript_cov \""); p = bed_put_num(p, cov); p = gtx_put_lit(p, "\";"); }
+        if (head) { p = text_put_lit(p, " transcript_cov \""); p = text_put_num(p, cov); p = text_put_lit(p, "\";"); }
     }
     *p = '\n';
 }
@@ -197,15 +190,14 @@ __global__ __launch_bounds__(GTX_THREADS)
 void k_gtx_write(GtxIn in, int64_t first, int64_t count, const uint32_t *__restrict__ off, const uint32_t *__restrict__ fix, uint8_t *__restrict__ text,
                  uint32_t *__restrict__ counters)
 {
-    __shared__ uint4 s_img[GTX_LDS / 16 + 1];           // the span from its 16-byte boundary: `head` unused bytes, then the text
+    __shared__ uint4 s_img[GTX_LDS / 16 + 1];           // the image of the tile's span (l2r_text.hip.h)
     __shared__ uint32_t s_line[GTX_TILE + 1];           // lines in front of the tile's blocks; the tile's lines last
     __shared__ uint32_t s_wave[4];
     const int64_t i0 = (int64_t)blockIdx.x * GTX_TILE, i1 = i0 + GTX_TILE < count ? i0 + GTX_TILE : count;
     const uint32_t nb = (uint32_t)(i1 - i0);
     const uint32_t b0 = off[i0], b1 = off[i1], bytes = b1 - b0;
     const bool direct = bytes > GTX_LDS;                // (workgroup-uniform)
-    const uint32_t head = b0 & 15u;
-    uint8_t *img = reinterpret_cast<uint8_t *>(s_img);
+    const uint32_t head = text_head(b0);
     uint32_t n_lines = 0u;
     {   uint32_t nl = 0u;
         if (threadIdx.x < nb) {
@@ -244,26 +236,20 @@ void k_gtx_write(GtxIn in, int64_t first, int64_t count, const uint32_t *__restr
                 a = (uint32_t)(j == 0 && in.start ? in.start[q] : in.xs[o + j]);
                 e = (uint32_t)(j == n - 1 && in.end ? in.end[q] : in.xe[o + j]);
             }
-            len = fix[q] + extra + bed_digits(a) + bed_digits(e);
+            len = fix[q] + extra + text_digits(a) + text_digits(e);
         }
         uint32_t round_bytes;
         const uint32_t pos = run + block_exclusive_scan(len, s_wave, round_bytes);
         run += round_bytes;
         if (valid) {
             if ((uint64_t)pos + len > bytes) atomicAdd(counters + GTXC_OUTSIDE, 1u);
-            else gtx_put_line(direct ? text + b0 + pos : img + head + pos, in, t, is_head, a, e, cov);
+            else gtx_put_line(direct ? text + b0 + pos : text_image(s_img, head) + pos, in, t, is_head, a, e, cov);
         }
     }
     if (threadIdx.x == 0) { atomicAdd(counters + GTXC_LINES, n_lines); if (direct) atomicAdd(counters + GTXC_DIRECT, 1u); }
     if (direct) return;
     __syncthreads();
-    uint8_t *g = text + (b0 - head);                    // 16-byte aligned (the text buffer is)
-    const uint32_t img_end = head + bytes, n_chunk = (img_end + 15u) / 16u;
-    for (uint32_t c = threadIdx.x; c < n_chunk; c += GTX_THREADS) {
-        const uint32_t lo = c * 16u, hi = lo + 16u;
-        if (lo >= head && hi <= img_end) *reinterpret_cast<uint4 *>(g + lo) = s_img[c];
-        else for (uint32_t b = lo < head ? head : lo; b < (hi < img_end ? hi : img_end); ++b) g[b] = img[b];
-    }
+    text_stream_out<GTX_THREADS>(s_img, b0, bytes, text);
 }
 
 }  // namespace l2r

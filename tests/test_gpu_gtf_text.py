@@ -180,6 +180,29 @@ def test_tile_text_at_the_lds_edge(eng, delta):
         assert (st["tiles_lds"], st["tiles_direct"]) == ((2, 0) if delta <= 0 else (1, 1))
 
 
+def tile_offset_case(r):
+    """2 x TILE + 1 PLAIN blocks of two exons; the gene name of block 0 is lengthened until the first tile's bytes are r modulo 16."""
+    case = gc.make_case(47, [2] * (2 * TILE + 1), gr.PLAIN, name_len=(4, 4))
+    first = sum(len(gr.block_text(case, q)) for q in range(TILE))
+    k = (r - first) * 11 % 16                           # the name stands once in each of the block's three lines: 3 k bytes more, and 3 * 11 = 33
+    case["table"] = bytes(case["table"]) + b"G" * (4 + k) + b"\0"
+    case["gid"][0] = len(case["table"]) - (4 + k) - 1
+    return case
+
+
+def test_tile_offsets_take_every_residue(eng):
+    """The stream-out of k_gtx_write (text_stream_out) with the second tile's span beginning at every offset modulo 16."""
+    seen = set()
+    for r in range(16):
+        case = tile_offset_case(r)
+        second = sum(len(t) for t in gr.texts(case)[:TILE])          # where the second tile's span begins
+        assert second % 16 == r
+        seen.add(second % 16)
+        st = check(eng, case)
+        assert (st["tiles_lds"], st["tiles_direct"], st["batches"]) == (3, 0, 1)
+    assert seen == set(range(16))
+
+
 def test_oversized_tiles_take_the_direct_path(eng, monkeypatch):
     for f in FORMS:
         case = gc.make_case(43, [300] * 3 + [1] * (TILE - 3) + [2] * 5, f, name_len=(100, 254))
