@@ -634,6 +634,60 @@ int          l2r_gtftext_lines(l2r_ctx *ctx, int64_t first, int64_t max_blocks, 
 int          l2r_gtftext_out(l2r_ctx *ctx, uint8_t *text, int64_t cap);
 int          l2r_gtftext_stats(l2r_ctx *ctx, double *out, int n);
 
+/* ---- the per-read detail table of `update-gtf -A` (host/cmds.c, host/tail.c print_detail): one text line per read, the text composed on
+ * the device.  The rule, stated here once (print_bam_detail_trans, src/update_gtf.c:297-419).  For read i: n = info >> 8 exons with the
+ * starts xs[0..n), the ends xe[0..n) and the flags f[0..n); ref = ref_tx[i].  Numbers are printed as %d.
+ *     <qname>\t<chr>\t<+|->\t<cls>\t<gid>\t<gname>\t<n>\t<xs, comma separated>\t<xe, comma separated>\t<L1><L2><L3><L4>\n
+ * +|- is L2R_INFO_REV (the strand after classification, not the record's); cls is 0 with L2R_INFO_KNOWN, else 1 with
+ * L2R_INFO_KNOWN_SITE, else 2; gid and gname are the gene id and gene name of the annotation transcript ref, both `NA` where ref < 0.
+ *     L1   over the exons j of [0, n) with L2R_EXF_NOVEL_EXON: j
+ *     L2   over the junctions j of [0, n - 1): 2j where L2R_EXF_NOVEL_DON and 2j + 1 where L2R_EXF_NOVEL_ACC, in that order
+ *     L3   over j of [0, n - 1) with L2R_EXF_NOVEL_JUNC: j
+ *     L4   the same with L2R_EXF_UNREL_JUNC
+ * A list is <count>\t and its members comma separated, or `NA` where the count is 0.  L1, L2 and L3 are followed by a tab.  L4 is followed
+ * by a tab ONLY WHERE IT IS EMPTY (host/tail.c's index_list writes `NA\t` whatever its trailing_tab says, as the reference does): a line
+ * ends `...\t0\tNA\t\n` or `...\t1\t1\n`.  This is the behaviour to keep.  A flag of the last exon that belongs to a junction list does
+ * not appear: those lists stop at n - 1.  The header line (`ReadName\tchr\t...`) is the command's to write.
+ * Domain errors fail the call with -1 and write nothing; l2r_last_error() names the smallest read (0-based) and the kind, in the order
+ * they are looked for: a tid outside [0, n_ref); a read-name id at or beyond names_len, a read name of 255 or more bytes, or one without a
+ * NUL; ref at or beyond the annotation's transcripts; a gene id or gene name with an id, length or NUL fault in the annotation's table; a
+ * read with no exon; a negative start or end; a line of 2^32 - 64 bytes or more.
+ *     l2r_detail_begin   once: the reference names (as in l2r_bed_params) and the annotation's gene tables -- anno_names[0, anno_names_len)
+ *                        of NUL-terminated strings, tx_gid / tx_gname the byte offsets of transcript t's gene id / gene name -- to HBM
+ *     l2r_detail_rows    the reads (struct l2r_detail_reads: C has one name space for typedefs and functions): tid, a table names[0, names_len) of NUL-terminated strings, qname the byte offsets of the read names,
+ *                        and res, the arrays of an l2r_download (n_reads == n), which are uploaded; res == NULL: the results of the
+ *                        context's last l2r_run where they lie in HBM -- n must equal the run's reads, the run must have kept its
+ *                        results (L2R_WANT_RESULTS), and no exon, flag or result word crosses the bus.  k_detail_measure runs over all n
+ *                        reads, the lengths (4 bytes per read) come to the host; *n_bytes is the total.  The domain errors surface here
+ *     l2r_detail_lines   one batch: reads from `first` while their count stays within max_rows and the sum of their bytes within max_bytes
+ *                        and below 2^32 - 64 -- always at least one.  *n_taken reads, *n_bytes of text, which stays in HBM until the next
+ *                        call.  Batches concatenated are the text of the rows however it was cut
+ *     l2r_detail_out     the text of the last l2r_detail_lines; cap < n_bytes fails and writes nothing, as does a call behind a failure
+ * On the device (csrc/l2r_detail.hip.h): k_detail_measure -- one thread per read, or one wave per read where the rows have more than 32
+ * exons per read on average (L2R_DETAIL_WAVE=0|1 forces one) -- leaves a line's length and where its seven segments (head, starts, ends,
+ * L1..L4) begin; k_scan_u32 over the batch's lengths; k_detail_write: one workgroup per L2R_DETAIL_TILE reads takes their segments as its
+ * work items, a lane per segment of a short read, a wave per segment of a long one, composes the text in an LDS image of
+ * L2R_DETAIL_LDS_BYTES and streams it out in aligned 16-byte stores; a tile with more text writes straight to the text.  The text buffer
+ * has 64 bytes of slack; with L2R_CHECK=1 they are filled with a pattern in front of k_detail_write and looked at behind it.
+ * L2R_DETAIL_ROUTE=host: the exact host routine of csrc/l2r_detailplan.hip.h, same bytes, same errors.
+ * l2r_detail_stats: out[0] rows, [1] lines and [2] bytes of the last batch, [3] form of k_detail_measure (0 thread, 1 wave), [4] tiles on
+ * the LDS path, [5] tiles on the direct path (both of the last batch), [6] route (0 device, 1 host), [7] 1 where the guard bytes are intact
+ * or were not checked, [8] batches since l2r_detail_rows; with L2R_DETAIL_TIMING=1 in the environment (every launch is then waited for)
+ * device milliseconds of [9] k_detail_measure, [10] k_scan_u32 and [11] k_detail_write, the latter two summed over the batches; n = words
+ * of out (up to 12). */
+#define L2R_DETAIL_TILE 32              /* reads of one workgroup of k_detail_write: 224 segments, about 6 KB of text at eight exons per read */
+#define L2R_DETAIL_LDS_BYTES 32768      /* bytes of a tile's text its LDS image holds; a tile with more takes the direct path */
+#define L2R_DETAIL_NAME_MAX 254         /* bytes of a read name, a gene id, a gene name */
+typedef struct { int32_t n_ref; const int64_t *ref_off; const uint8_t *ref_names;          /* as l2r_bed_params */
+                 int64_t n_tx, anno_names_len; const uint8_t *anno_names; const uint32_t *tx_gid, *tx_gname; } l2r_detail_params;
+typedef struct { int64_t n; const int32_t *tid; int64_t names_len; const uint8_t *names; const uint32_t *qname;
+                 const l2r_result *res; /* NULL: the results of the context's last l2r_run where they lie in HBM */ } l2r_detail_reads;
+int          l2r_detail_begin(l2r_ctx *ctx, const l2r_detail_params *prm);
+int          l2r_detail_rows(l2r_ctx *ctx, const l2r_detail_reads *rows, int64_t *n_bytes);
+int          l2r_detail_lines(l2r_ctx *ctx, int64_t first, int64_t max_rows, int64_t max_bytes, int64_t *n_taken, int64_t *n_bytes);
+int          l2r_detail_out(l2r_ctx *ctx, uint8_t *text, int64_t cap);
+int          l2r_detail_stats(l2r_ctx *ctx, double *out, int n);
+
 #ifdef __cplusplus
 }
 #endif

@@ -40,6 +40,7 @@ EXPORTS = [
     "l2r_bed_begin", "l2r_bed_lines", "l2r_bed_text_out", "l2r_bed_cut", "l2r_bed_stats",
     "l2r_uniq_merge", "l2r_uniq_out", "l2r_uniq_stats",
     "l2r_gtftext_begin", "l2r_gtftext_rows", "l2r_gtftext_blocks", "l2r_gtftext_lines", "l2r_gtftext_out", "l2r_gtftext_stats",
+    "l2r_detail_begin", "l2r_detail_rows", "l2r_detail_lines", "l2r_detail_out", "l2r_detail_stats",
 ]
 SJ_E_UNKNOWN_TID = -3
 
@@ -176,6 +177,15 @@ class CGtxBlocks(C.Structure):
     _fields_ = [("m", C.c_int64), ("sel", C.c_void_p), ("start", C.c_void_p), ("end", C.c_void_p), ("cov", C.c_void_p)]
 
 
+class CDetailParams(C.Structure):
+    _fields_ = [("n_ref", C.c_int32), ("ref_off", C.c_void_p), ("ref_names", C.c_void_p), ("n_tx", C.c_int64), ("anno_names_len", C.c_int64),
+                ("anno_names", C.c_void_p), ("tx_gid", C.c_void_p), ("tx_gname", C.c_void_p)]
+
+
+class CDetailReads(C.Structure):
+    _fields_ = [("n", C.c_int64), ("tid", C.c_void_p), ("names_len", C.c_int64), ("names", C.c_void_p), ("qname", C.c_void_p), ("res", C.c_void_p)]
+
+
 class CTiming(C.Structure):
     _fields_ = [("stage_ms", C.c_float * N_STAGES), ("total_ms", C.c_float), ("iters", C.c_int32)]
 
@@ -270,6 +280,11 @@ def load_library():
         lib.l2r_gtftext_lines.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p]
         lib.l2r_gtftext_out.argtypes = [C.c_void_p, C.c_void_p, C.c_int64]
         lib.l2r_gtftext_stats.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
+        lib.l2r_detail_begin.argtypes = [C.c_void_p, C.c_void_p]
+        lib.l2r_detail_rows.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        lib.l2r_detail_lines.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p]
+        lib.l2r_detail_out.argtypes = [C.c_void_p, C.c_void_p, C.c_int64]
+        lib.l2r_detail_stats.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
         _lib = lib
     return _lib
 
@@ -416,6 +431,8 @@ def bed_cut(flag, tid, cigars, names, ref_names, first: int, max_records: int, m
 
 GTX_PLAIN, GTX_READ = 0, 1
 GTX_TILE, GTX_LDS_BYTES = 32, 32768         # L2R_GTX_TILE, L2R_GTX_LDS_BYTES (include/lr2rmats_hip.h)
+DETAIL_TILE, DETAIL_LDS_BYTES = 32, 32768   # L2R_DETAIL_TILE, L2R_DETAIL_LDS_BYTES (include/lr2rmats_hip.h)
+DETAIL_STAT_NAMES = ["rows", "lines", "bytes", "wave_form", "tiles_lds", "tiles_direct", "route", "guard_intact", "batches", "k_detail_measure", "k_scan_u32", "k_detail_write"]
 GTX_STAT_NAMES = ["blocks", "lines", "bytes", "wave_form", "tiles_lds", "tiles_direct", "route", "guard_intact", "batches", "k_gtx_measure", "k_scan_u32", "k_gtx_write"]
 
 
@@ -793,6 +810,71 @@ class Engine:
         out = np.zeros(len(GTX_STAT_NAMES), np.float64)
         self._chk(self.lib.l2r_gtftext_stats(self.ctx, out.ctypes.data, len(out)))
         return {k: float(v) for k, v in zip(GTX_STAT_NAMES, out)}
+
+    # ---- the detail table of `update-gtf -A` (include/lr2rmats_hip.h: l2r_detail_begin / _rows / _lines / _out / _stats)
+    def detail_begin(self, ref_names, anno_names=b"", tx_gid=(), tx_gname=()) -> None:
+        """The reference names (byte strings, by tid) and the annotation's gene tables: ``anno_names`` (bytes: NUL-terminated strings) and
+        per annotation transcript the byte offsets of its gene id and gene name."""
+        off, blob = pack_names(ref_names)
+        keep = blob if blob.size else np.zeros(1, np.uint8)
+        anno = np.frombuffer(bytes(anno_names), np.uint8) if not isinstance(anno_names, np.ndarray) else np.ascontiguousarray(anno_names, np.uint8)
+        gid, gname = np.ascontiguousarray(tx_gid, np.uint32), np.ascontiguousarray(tx_gname, np.uint32)
+        if gid.shape != gname.shape:
+            raise ValueError("detail_begin: tx_gid and tx_gname of one length")
+        prm = CDetailParams(len(off) - 1, off.ctypes.data, keep.ctypes.data, int(gid.size), int(anno.size), anno.ctypes.data if anno.size else None,
+                            gid.ctypes.data if gid.size else None, gname.ctypes.data if gname.size else None)
+        self._chk(self.lib.l2r_detail_begin(self.ctx, C.byref(prm)))
+
+    def detail_rows(self, tid, names, qname, res=None, n=None) -> int:
+        """The reads: tid, the table ``names`` (bytes: NUL-terminated strings), ``qname`` (byte offsets of the read names) and ``res``, a
+        Result (the arrays of a download), which is uploaded; None: the results of the last run where they lie in HBM (``n`` overrides the
+        row count, which must equal the run's reads).  The bytes of the whole text; a read outside the domain raises L2RError (rc=-1)
+        naming the smallest such read and the kind."""
+        names = np.frombuffer(bytes(names), np.uint8) if not isinstance(names, np.ndarray) else np.ascontiguousarray(names, np.uint8)
+        tid, qname = np.ascontiguousarray(tid, np.int32), np.ascontiguousarray(qname, np.uint32)
+        n = int(tid.shape[0]) if n is None else int(n)
+        keep, cres = [], None
+        if res is not None:
+            a = [np.ascontiguousarray(res.ex_off, np.int64), np.ascontiguousarray(res.ex_start, np.int32), np.ascontiguousarray(res.ex_end, np.int32),
+                 np.ascontiguousarray(res.ex_flag, np.uint8), np.ascontiguousarray(res.info, np.uint32), np.ascontiguousarray(res.ref_tx, np.int32)]
+            x = int(a[0][-1]) if a[0].size else 0
+            keep = [v if v.size else np.zeros(1, v.dtype) for v in a]
+            cres = CResult(n, x, x, keep[0].ctypes.data_as(_i64p), keep[1].ctypes.data_as(_i32p), keep[2].ctypes.data_as(_i32p), keep[3].ctypes.data_as(_u8p),
+                           keep[4].ctypes.data_as(_u32p), keep[5].ctypes.data_as(_i32p))
+        rows = CDetailReads(n, tid.ctypes.data if tid.size else None, int(names.size), names.ctypes.data if names.size else None,
+                            qname.ctypes.data if qname.size else None, None if cres is None else C.addressof(cres))
+        n_bytes = C.c_int64(0)
+        self._chk(self.lib.l2r_detail_rows(self.ctx, C.byref(rows), C.byref(n_bytes)))
+        return int(n_bytes.value)
+
+    def detail_lines(self, first: int, max_rows: int = 1 << 20, max_bytes: int = 1 << 30, cap=None, buf=None):
+        """One batch from read ``first``: (reads taken, its text).  ``cap``: the room offered to l2r_detail_out (None: the batch's bytes).
+        ``buf``: a uint8 array the text is fetched into -- the text is then a view of it, not a copy (tools/bench_detail.py)."""
+        n_taken, n_bytes = C.c_int64(0), C.c_int64(0)
+        self._chk(self.lib.l2r_detail_lines(self.ctx, int(first), int(max_rows), int(max_bytes), C.byref(n_taken), C.byref(n_bytes)))
+        if buf is not None:
+            self._chk(self.lib.l2r_detail_out(self.ctx, buf.ctypes.data, int(buf.size)))
+            return int(n_taken.value), buf[:int(n_bytes.value)]
+        cap = int(n_bytes.value) if cap is None else int(cap)
+        out = np.zeros(max(cap, 1), np.uint8)
+        self._chk(self.lib.l2r_detail_out(self.ctx, out.ctypes.data, cap))
+        return int(n_taken.value), out[:int(n_bytes.value)].tobytes()
+
+    def detail_all(self, n: int, max_rows: int = 1 << 20, max_bytes: int = 1 << 30) -> bytes:
+        """The text of all ``n`` rows, batch by batch."""
+        out, first = [], 0
+        while first < n:
+            k, t = self.detail_lines(first, max_rows, max_bytes)
+            out.append(t)
+            first += k
+        return b"".join(out)
+
+    def detail_stats(self) -> dict:
+        """l2r_detail_stats: rows, lines and bytes of the last batch, the form of k_detail_measure (0 thread, 1 wave), tiles on the LDS and
+        on the direct path, route (0 device, 1 host), guard_intact, batches, and with L2R_DETAIL_TIMING=1 device milliseconds per kernel."""
+        out = np.zeros(len(DETAIL_STAT_NAMES), np.float64)
+        self._chk(self.lib.l2r_detail_stats(self.ctx, out.ctypes.data, len(out)))
+        return {k: float(v) for k, v in zip(DETAIL_STAT_NAMES, out)}
 
     # ---- `unique-gtf` (include/lr2rmats_hip.h: l2r_uniq_merge / _out / _stats)
     def uniq_merge(self, tid, rev, ex_off, xs, xe, force_strand=0, ss_dis=0, end_dis=0x7fffffff, frac=0.8) -> dict:

@@ -29,12 +29,14 @@
 #include "l2r_bed.hip.h"
 #include "l2r_uniq.hip.h"
 #include "l2r_gtftext.hip.h"
+#include "l2r_detail.hip.h"
 #include "l2r_plan.hip.h"
 #include "l2r_tables.hip.h"
 #include "l2r_nameorder.hip.h"
 #include "l2r_gtforder.hip.h"
 #include "l2r_bedplan.hip.h"
 #include "l2r_gtftextplan.hip.h"
+#include "l2r_detailplan.hip.h"
 
 using namespace l2r;
 
@@ -275,6 +277,31 @@ struct GtxState {
     double stats[12] = {0};                             // l2r_gtftext_stats
 };
 
+// The detail table of `update-gtf -A` (l2r_detail.hip.h): the reference names and the annotation's gene tables of l2r_detail_begin, the
+// reads of l2r_detail_rows with what k_detail_measure left per read, and the text of the last l2r_detail_lines (in HBM, or on the host
+// where the host route made it) until l2r_detail_out fetches it.  The route is read at l2r_detail_rows and holds until the next; only the
+// host route keeps copies of the columns (h).  The buffers belong to the context, grow on demand and are used again.
+struct DetailState {
+    bool begun = false, have_rows = false, on_host = false;
+    bool run_res = false;                               // rows came with res == NULL: the results of the context's last l2r_run
+    l2r_detail_params prm{};                            // ref_off / ref_names point into ref's vectors, the gene tables into h_anno, h_gid, h_gname
+    RefNames ref;
+    std::vector<uint8_t> h_anno; std::vector<uint32_t> h_gid, h_gname;
+    DevBuf<uint8_t> anno; DevBuf<uint32_t> tx_gid, tx_gname;
+    int64_t n = 0, names_len = 0;
+    DevBuf<int32_t> tid, xs, xe, ref_tx; DevBuf<uint8_t> names, f; DevBuf<uint32_t> qname, ex_off, info;        // (the results: uploaded rows only)
+    struct Host {                                       // the host route's copies
+        std::vector<int32_t> tid, xs, xe, ref_tx; std::vector<uint8_t> names, f; std::vector<uint32_t> qname, info; std::vector<int64_t> ex_off;
+        l2r_result res{};
+    } h;
+    std::vector<uint32_t> h_len;                        // the measured bytes of every read
+    DevBuf<uint32_t> len, split, off, word;             // len, split: per read; off: one batch's lengths, scanned in place; word: DETC_* and the scan's total
+    DevBuf<unsigned long long> word64;                  // k_detail_measure: the smallest bad read << 4 | kind
+    TextOut out;
+    StageTimer clk;
+    double stats[12] = {0};                             // l2r_detail_stats
+};
+
 // What l2r_sync has learned from the counters of a completed run of the tile path (fetch_run_facts): a later run of the same inputs,
 // parameters and outputs sizes its list-driven launches by the counts and skips those whose list was empty.  One record, forgotten as a
 // whole wherever one of those changes (forget_list_state).  LC_*: the list counter a field is a copy of (l2r_kernels.hip.h).
@@ -430,6 +457,7 @@ struct l2r_ctx {
     BedState bed;                           // `bam2bed`
     UniqState uniq;                         // `unique-gtf`
     GtxState gtx;                           // `bam2gtf`, `unique-gtf`: the GTF text
+    DetailState detail;                     // `update-gtf -A`: the detail table
 };
 
 // A launch (or a group of launches) on the context stream
@@ -554,9 +582,9 @@ static int download_all(l2r_ctx *c, int rc, std::initializer_list<Download> list
 
 static bool env_on(const char *name) { const char *e = getenv(name); return e && atoi(e) != 0; }
 
-// The form of a measure kernel (k_fusion_seg, k_bed_measure, k_gtx_measure): one wave per item where the items are long, above 32 words
+// The form of a measure kernel (k_fusion_seg, k_bed_measure, k_gtx_measure, k_detail_measure): one wave per item where the items are long, above 32 words
 // on average -- the bound of l2r_upload_reads' wide_cigar (upload_plan, l2r_plan.hip.h).  env (L2R_FUSION_WAVE, L2R_BED_WAVE,
-// L2R_GTX_WAVE) = 0|1 says otherwise: tests, tools/bench_*.py
+// L2R_GTX_WAVE, L2R_DETAIL_WAVE) = 0|1 says otherwise: tests, tools/bench_*.py
 static bool wave_form(double per_item, const char *env)
 {
     if (const char *e = getenv(env)) return atoi(e) != 0;
@@ -585,7 +613,7 @@ bool TextOut::guard_intact(const l2r_ctx *c) const
     return true;
 }
 
-// What is behind l2r_bed_text_out and l2r_gtftext_out: the text into the caller's `cap` bytes.  arg_code: of an argument or order error.
+// What is behind l2r_bed_text_out, l2r_gtftext_out and l2r_detail_out: the text into the caller's `cap` bytes.  arg_code: of an argument or order error.
 static int text_out(l2r_ctx *c, const TextOut &t, uint8_t *text, int64_t cap, const char *who, const char *lines, int arg_code)
 {
     if (!t.have) return fail(arg_code, "[%s] no text: the last %s failed, or none was made", who, lines);
@@ -3211,6 +3239,202 @@ int l2r_gtftext_out(l2r_ctx *c, uint8_t *text, int64_t cap)
 }
 
 int l2r_gtftext_stats(l2r_ctx *c, double *out, int n) { return stats_out(c ? c->gtx.stats : nullptr, GXS_N, out, n, "l2r_gtftext_stats"); }
+
+// ---------------------------------------------------------------------------------------------- the detail table of update-gtf -A
+// slots of l2r_detail_stats
+enum { DTS_ROWS = 0, DTS_LINES, DTS_BYTES, DTS_WAVE, DTS_TILES_LDS, DTS_TILES_DIRECT, DTS_ROUTE, DTS_GUARD, DTS_BATCHES, DTS_K_MEASURE, DTS_K_SCAN, DTS_K_WRITE, DTS_N };
+static_assert(DTS_N == sizeof(DetailState::stats) / sizeof(double) && DTS_K_MEASURE == 9, "l2r_detail_stats: the words of include/lr2rmats_hip.h");
+constexpr int DETC_TOTAL = DETC_N;                      // DetailState::word: k_detail_write's counters, then the scan's total
+constexpr int DETAIL_E_ARG = -4;                        // arguments, order of calls: not -1, which is a domain error (the command falls back on it)
+
+int l2r_detail_begin(l2r_ctx *c, const l2r_detail_params *p)
+{
+    if (!c) return fail(DETAIL_E_ARG, "[l2r_detail_begin] null argument");
+    DetailState &m = c->detail;
+    m.begun = false; m.have_rows = false; m.out.have = false;
+    for (double &v : m.stats) v = 0;
+    {   std::string msg;
+        if (detail_check_params(p, msg)) return fail(DETAIL_E_ARG, "%s", msg.c_str()); }
+    m.ref.set(p->n_ref, p->ref_off, p->ref_names);
+    const size_t T = (size_t)p->n_tx, A = (size_t)p->anno_names_len;
+    m.h_anno.assign(A + 1, 0);
+    if (A) memcpy(m.h_anno.data(), p->anno_names, A);
+    m.h_gid.assign(T + 1, 0); m.h_gname.assign(T + 1, 0);
+    if (T) { memcpy(m.h_gid.data(), p->tx_gid, T * 4); memcpy(m.h_gname.data(), p->tx_gname, T * 4); }
+    m.prm = *p;
+    m.prm.ref_off = m.ref.h_off.data(); m.prm.ref_names = m.ref.h_names.data();
+    m.prm.anno_names = m.h_anno.data(); m.prm.tx_gid = m.h_gid.data(); m.prm.tx_gname = m.h_gname.data();
+    HIP_TRY(hipSetDevice(c->device));
+    int rc;
+    if ((rc = m.ref.upload(c)) || (rc = put_dev(c, m.anno, m.h_anno)) || (rc = put_dev(c, m.tx_gid, m.h_gid)) || (rc = put_dev(c, m.tx_gname, m.h_gname))) { (void)hipStreamSynchronize(c->stream); return rc; }
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    m.begun = true;
+    return 0;
+}
+
+// the kernels' view of the rows
+static DetailIn detail_in(const l2r_ctx *c, const DetailState &m)
+{
+    DetailIn in{};
+    in.n = m.n; in.tid = m.tid.p; in.names = m.names.p; in.names_len = m.names_len; in.qname = m.qname.p;
+    if (m.run_res) { in.ex_off = c->ex_off.p; in.info = c->info.p; in.xs = c->ex_start.p; in.xe = c->ex_end.p; in.ref_tx = c->ref_tx.p; in.f = c->ex_flag.p; }
+    else { in.ex_off = m.ex_off.p; in.info = m.info.p; in.xs = m.xs.p; in.xe = m.xe.p; in.ref_tx = m.ref_tx.p; in.f = m.f.p; }
+    in.n_ref = m.prm.n_ref; in.ref_off = m.ref.off.p; in.ref_names = m.ref.names.p;
+    in.n_tx = m.prm.n_tx; in.anno_names_len = m.prm.anno_names_len; in.anno_names = m.anno.p; in.tx_gid = m.tx_gid.p; in.tx_gname = m.tx_gname.p;
+    return in;
+}
+// ... and the host route's, over its copies
+static l2r_detail_reads detail_host_view(const DetailState &m)
+{
+    const DetailState::Host &h = m.h;
+    return l2r_detail_reads{m.n, h.tid.data(), m.names_len, h.names.data(), h.qname.data(), &h.res};
+}
+
+int l2r_detail_rows(l2r_ctx *c, const l2r_detail_reads *r, int64_t *n_bytes)
+{
+    if (!c || !n_bytes) return fail(DETAIL_E_ARG, "[l2r_detail_rows] null argument");
+    DetailState &m = c->detail;
+    m.have_rows = false; m.out.have = false;
+    *n_bytes = 0;
+    if (!m.begun) return fail(DETAIL_E_ARG, "[l2r_detail_rows] no l2r_detail_begin in front");
+    {   std::string msg;
+        if (detail_check_rows(r, msg)) return fail(DETAIL_E_ARG, "%s", msg.c_str()); }
+    const char *route = getenv("L2R_DETAIL_ROUTE");
+    m.on_host = route && strcmp(route, "host") == 0;
+    for (int k = 0; k < DTS_N; ++k) m.stats[k] = 0;
+    m.stats[DTS_ROUTE] = m.on_host ? 1 : 0; m.stats[DTS_GUARD] = 1;
+    const size_t N = (size_t)r->n, NL = (size_t)r->names_len;
+    m.n = r->n; m.names_len = r->names_len; m.run_res = !r->res;
+    m.stats[DTS_ROWS] = (double)N;
+    m.h_len.assign(N, 0u);
+    HIP_TRY(hipSetDevice(c->device));
+    int rc = 0;
+    double exons_per_row = 0;
+    if (m.run_res) {
+        if (!c->ran) return fail(DETAIL_E_ARG, "[l2r_detail_rows] no completed run on this context");
+        if ((rc = fetch_totals(c))) return rc;
+        if (!(c->want & L2R_WANT_RESULTS)) return fail(DETAIL_E_ARG, "[l2r_detail_rows] the last run kept no results (l2r_set_outputs without L2R_WANT_RESULTS)");
+        if (r->n != c->n_reads) return fail(DETAIL_E_ARG, "[l2r_detail_rows] %lld rows, the last run had %lld reads", (long long)r->n, (long long)c->n_reads);
+        if (N) exons_per_row = (double)c->h_totals[0] / (double)N;
+    } else if (N) exons_per_row = (double)r->res->n_exons / (double)N;
+    if (N == 0) { m.have_rows = true; return 0; }
+    const l2r_result *s = r->res;
+    uint64_t bytes = 0;
+    if (m.on_host) {
+        DetailState::Host &h = m.h;
+        h.tid.assign(r->tid, r->tid + N); h.qname.assign(r->qname, r->qname + N); h.names.assign(r->names, r->names + NL);
+        const size_t X = m.run_res ? (size_t)c->h_totals[0] : (size_t)s->n_exons;
+        h.ex_off.assign(N + 1, 0); h.info.assign(N, 0u); h.ref_tx.assign(N, 0); h.xs.assign(X ? X : 1, 0); h.xe.assign(X ? X : 1, 0); h.f.assign(X ? X : 1, 0);
+        h.res = l2r_result{(int64_t)N, (int64_t)X, (int64_t)X, h.ex_off.data(), h.xs.data(), h.xe.data(), h.f.data(), h.info.data(), h.ref_tx.data()};
+        if (m.run_res) { if ((rc = l2r_download(c, &h.res))) return rc; }
+        else {
+            memcpy(h.ex_off.data(), s->ex_off, (N + 1) * 8); memcpy(h.info.data(), s->info, N * 4); memcpy(h.ref_tx.data(), s->ref_tx, N * 4);
+            if (X) { memcpy(h.xs.data(), s->ex_start, X * 4); memcpy(h.xe.data(), s->ex_end, X * 4); memcpy(h.f.data(), s->ex_flag, X); }
+        }
+        const l2r_detail_reads hr = detail_host_view(m);
+        for (size_t i = 0; i < N; ++i) {
+            uint64_t by = 0; uint32_t split[DETAIL_SPLIT];
+            const int kind = detail_line_bytes(&m.prm, &hr, (int64_t)i, &by, split);
+            if (kind) { std::string msg; detail_row_fail(msg, (int64_t)i, kind); return fail(-1, "%s", msg.c_str()); }
+            m.h_len[i] = (uint32_t)by; bytes += by;
+        }
+    } else {
+        if ((rc = m.clk.begin(env_on("L2R_DETAIL_TIMING"), c->check_stages))) return rc;
+        const bool wave = wave_form(exons_per_row, "L2R_DETAIL_WAVE");
+        m.stats[DTS_WAVE] = wave ? 1 : 0;
+        std::vector<uint32_t> off32;
+        if ((rc = to_dev(c, m.tid, r->tid, N)) || (rc = to_dev(c, m.qname, r->qname, N)) || (rc = to_dev(c, m.names, r->names, NL))) {}
+        if (!rc && !m.run_res) {
+            const size_t X = (size_t)s->n_exons;
+            off32.resize(N);
+            for (size_t i = 0; i < N; ++i) off32[i] = (uint32_t)s->ex_off[i];
+            if ((rc = put_dev(c, m.ex_off, off32)) || (rc = to_dev(c, m.info, (const uint32_t *)s->info, N)) || (rc = to_dev(c, m.ref_tx, (const int32_t *)s->ref_tx, N)) ||
+                (rc = to_dev(c, m.xs, (const int32_t *)s->ex_start, X)) || (rc = to_dev(c, m.xe, (const int32_t *)s->ex_end, X)) || (rc = to_dev(c, m.f, (const uint8_t *)s->ex_flag, X))) {}
+        }
+        if (!rc && (m.len.ensure(N) || m.split.ensure(N * DETAIL_SPLIT) || m.word64.ensure(1) || m.word.ensure(DETC_TOTAL + 1))) rc = -2;
+        if (rc) { (void)hipStreamSynchronize(c->stream); return rc; }  // (the columns are the caller's)
+        HIP_TRY(hipMemsetAsync(m.word64.p, 0xff, sizeof(unsigned long long), c->stream));
+        const DetailIn in = detail_in(c, m);
+        const DetailMeasure meas{m.len.p, m.split.p, m.word64.p};
+        rc = m.clk.launch(c, &m.stats[DTS_K_MEASURE], [&] {
+            const dim3 grid((unsigned)(((wave ? N * 64 : N) + 255) / 256));
+            if (wave) hipLaunchKernelGGL(k_detail_measure<true>, grid, dim3(256), 0, c->stream, in, meas);
+            else hipLaunchKernelGGL(k_detail_measure<false>, grid, dim3(256), 0, c->stream, in, meas);
+        });
+        unsigned long long w = 0;
+        if ((rc = download_all(c, rc, {{&w, m.word64.p, sizeof w}, {m.h_len.data(), m.len.p, N * 4}}, "l2r_detail_rows"))) return rc;
+        if (w != ~0ull) {
+            const unsigned long long i = w >> 4; const int kind = (int)(w & 15ull);
+            if (i >= N || kind <= DET_OK || kind >= DET_E_N) return fail(-2, "[l2r_detail_rows] the device names read %llu of %zu, kind %d", i, N, kind);
+            std::string msg; detail_row_fail(msg, (int64_t)i, kind);
+            return fail(-1, "%s", msg.c_str());
+        }
+        for (size_t i = 0; i < N; ++i) bytes += m.h_len[i];
+    }
+    m.have_rows = true;
+    *n_bytes = (int64_t)bytes;
+    return 0;
+}
+
+int l2r_detail_lines(l2r_ctx *c, int64_t first, int64_t max_rows, int64_t max_bytes, int64_t *n_taken, int64_t *n_bytes)
+{
+    if (!c || !n_taken || !n_bytes) return fail(DETAIL_E_ARG, "[l2r_detail_lines] null argument");
+    DetailState &m = c->detail;
+    m.out.reset();
+    *n_taken = 0; *n_bytes = 0;
+    if (!m.have_rows) return fail(DETAIL_E_ARG, "[l2r_detail_lines] no l2r_detail_rows in front, or it failed");
+    int64_t take = 0, sum = 0;
+    {   std::string msg;
+        if (detail_cut(m.h_len.data(), m.n, first, max_rows, max_bytes, &take, &sum, msg)) return fail(DETAIL_E_ARG, "%s", msg.c_str()); }
+    const size_t B = (size_t)sum, K = (size_t)take;
+    m.stats[DTS_LINES] = 0; m.stats[DTS_BYTES] = 0; m.stats[DTS_TILES_LDS] = 0; m.stats[DTS_TILES_DIRECT] = 0;
+    if (m.on_host) {
+        const l2r_detail_reads hr = detail_host_view(m);
+        std::string msg;
+        if (detail_text_host(&m.prm, &hr, first, take, m.out.host_text, msg)) { m.out.host_text.clear(); return fail(-1, "%s", msg.c_str()); }
+        if (m.out.host_text.size() != B) return fail(-5, "[l2r_detail_lines] %zu bytes of text, measured %zu", m.out.host_text.size(), B);
+        m.out.take_host();
+        m.stats[DTS_LINES] = (double)K; m.stats[DTS_BYTES] = (double)B; m.stats[DTS_BATCHES] += 1;
+        *n_taken = take; *n_bytes = sum;
+        return 0;
+    }
+    if (m.run_res && (c->n_reads != m.n || !c->ran)) return fail(DETAIL_E_ARG, "[l2r_detail_lines] the rows stand for a run of %lld reads, the context now holds %lld", (long long)m.n, (long long)c->n_reads);
+    HIP_TRY(hipSetDevice(c->device));
+    int rc;
+    if ((rc = m.clk.begin(env_on("L2R_DETAIL_TIMING"), c->check_stages))) return rc;
+    if (m.off.ensure(K + 1) || m.out.reserve(B) || m.word.ensure(DETC_TOTAL + 1)) return -2;
+    uint8_t *text8 = m.out.bytes();
+    HIP_TRY(hipMemcpyAsync(m.off.p, m.len.p + first, K * 4, hipMemcpyDeviceToDevice, c->stream));
+    HIP_TRY(hipMemsetAsync(m.word.p, 0, (DETC_TOTAL + 1) * sizeof(uint32_t), c->stream));
+    if ((rc = m.clk.launch(c, &m.stats[DTS_K_SCAN], [&] { scan_u32(c, m.off.p, (int64_t)K, m.word.p + DETC_TOTAL); }))) { (void)hipStreamSynchronize(c->stream); return rc; }
+    HIP_TRY(m.out.arm_guard(c, B));
+    const unsigned n_tiles = (unsigned)((K + DETAIL_TILE - 1) / DETAIL_TILE);
+    const DetailIn in = detail_in(c, m);
+    if ((rc = m.clk.launch(c, &m.stats[DTS_K_WRITE], [&] {
+            hipLaunchKernelGGL(k_detail_write, dim3(n_tiles), dim3(DETAIL_THREADS), 0, c->stream, in, first, take, (const uint32_t *)m.off.p, (const uint32_t *)m.split.p, text8, m.word.p);
+        }))) { (void)hipStreamSynchronize(c->stream); return rc; }
+    uint32_t w[DETC_TOTAL + 1] = {0};
+    HIP_TRY(hipMemcpyAsync(w, m.word.p, sizeof w, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(m.out.fetch_guard(c, B));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    if (!m.out.guard_intact(c)) m.stats[DTS_GUARD] = 0;
+    if ((size_t)w[DETC_TOTAL] != B) return fail(-5, "[l2r_detail_lines] the scan left %u bytes, the cut %zu", w[DETC_TOTAL], B);
+    if (w[DETC_OUTSIDE]) return fail(-5, "[l2r_detail_lines] %u bytes or segments would have left their place: k_detail_measure and k_detail_write disagree", w[DETC_OUTSIDE]);
+    if (w[DETC_DIRECT] > n_tiles) return fail(-5, "[l2r_detail_lines] %u direct tiles of %u", w[DETC_DIRECT], n_tiles);
+    m.stats[DTS_LINES] = (double)K; m.stats[DTS_BYTES] = (double)B; m.stats[DTS_BATCHES] += 1;
+    m.stats[DTS_TILES_DIRECT] = (double)w[DETC_DIRECT]; m.stats[DTS_TILES_LDS] = (double)(n_tiles - w[DETC_DIRECT]);
+    m.out.take_device(B);
+    *n_taken = take; *n_bytes = sum;
+    return 0;
+}
+
+int l2r_detail_out(l2r_ctx *c, uint8_t *text, int64_t cap)
+{
+    if (!c) return fail(DETAIL_E_ARG, "[l2r_detail_out] null argument");
+    return text_out(c, c->detail.out, text, cap, "l2r_detail_out", "l2r_detail_lines", DETAIL_E_ARG);
+}
+
+int l2r_detail_stats(l2r_ctx *c, double *out, int n) { return stats_out(c ? c->detail.stats : nullptr, DTS_N, out, n, "l2r_detail_stats"); }
 
 }  // extern "C"
 

@@ -141,13 +141,6 @@ void k_gtx_measure(GtxIn in, GtxMeasure out)
     out.len[q] = (uint32_t)bytes; out.fix[q] = fix;
 }
 
-// the name at names + id up to its NUL (k_gtx_measure has found one within 255 bytes)
-__device__ __forceinline__ uint8_t *gtx_put_name(uint8_t *p, const uint8_t *__restrict__ s)
-{
-    for (int k = 0; k <= L2R_GTX_NAME_MAX; ++k) { const uint8_t c = s[k]; if (!c) break; *p++ = c; }
-    return p;
-}
-
 // One line at dst (LDS or the text itself): exactly the bytes its length says.  head: the transcript line (then a = S, e = E).
 __device__ __forceinline__ void gtx_put_line(uint8_t *dst, const GtxIn &in, int64_t t, bool head, uint32_t a, uint32_t e, uint32_t cov)
 {
@@ -161,8 +154,8 @@ __device__ __forceinline__ void gtx_put_line(uint8_t *dst, const GtxIn &in, int6
     p = text_put_num(p, a); *p++ = '\t'; p = text_put_num(p, e);
     p = text_put_lit(p, "\t.\t"); *p++ = in.rev[t] ? '-' : '+'; p = text_put_lit(p, "\t.\t");
     if (in.form == L2R_GTX_PLAIN) {
-        p = text_put_lit(p, "gene_id \""); p = gtx_put_name(p, in.names + in.id[0][t]);
-        p = text_put_lit(p, "\"; transcript_id \""); p = gtx_put_name(p, in.names + in.id[1][t]);
+        p = text_put_lit(p, "gene_id \""); p = text_put_name(p, in.names + in.id[0][t], L2R_GTX_NAME_MAX);
+        p = text_put_lit(p, "\"; transcript_id \""); p = text_put_name(p, in.names + in.id[1][t], L2R_GTX_NAME_MAX);
         p = text_put_lit(p, "\";");
     } else {
         bool any = false;
@@ -173,7 +166,7 @@ __device__ __forceinline__ void gtx_put_line(uint8_t *dst, const GtxIn &in, int6
             if (any) *p++ = ' ';
             any = true;
             p = c == 0 ? text_put_lit(p, "gene_id \"") : c == 1 ? text_put_lit(p, "transcript_id \"") : c == 2 ? text_put_lit(p, "gene_name \"") : text_put_lit(p, "transcript_name \"");
-            p = gtx_put_name(p, s);
+            p = text_put_name(p, s, L2R_GTX_NAME_MAX);
             p = text_put_lit(p, "\";");
         }
         // (all four names empty: the blank of <C> then stands behind the tab, as emit_gtf_named writes it; the reference would write none)

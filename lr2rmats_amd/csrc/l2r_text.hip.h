@@ -1,5 +1,5 @@
-// l2r_text.hip.h -- what composing text on the device needs, for the write kernels of l2r_bed.hip.h and l2r_gtftext.hip.h: decimal digits,
-// literals, and the way a tile's text leaves the workgroup.
+// l2r_text.hip.h -- what composing text on the device needs, for the write kernels of l2r_bed.hip.h, l2r_gtftext.hip.h and l2r_detail.hip.h: decimal
+// digits, literals, names, and the way a tile's text leaves the workgroup.
 //
 // The LDS image and the stream-out.  A workgroup's text is one contiguous span [b0, b0 + bytes) of the output.  Its lines are composed in
 // an LDS image that starts at the span's 16-byte boundary: `head` = b0 & 15 unused bytes, then the text (text_head, text_image), so that image and
@@ -35,6 +35,14 @@ template <int N> __device__ __forceinline__ uint8_t *text_put_lit(uint8_t *p, co
 #pragma unroll
     for (int k = 0; k < N - 1; ++k) p[k] = (uint8_t)s[k];
     return p + (N - 1);
+}
+
+// The name at s up to its NUL, max_len bytes at the most (its measure kernel has found a NUL within them), at p; returns the byte behind
+// the name.  With `end`, a byte at or beyond it is not written -- the name still counts in full.
+__device__ __forceinline__ uint8_t *text_put_name(uint8_t *p, const uint8_t *__restrict__ s, int max_len, const uint8_t *end = nullptr)
+{
+    for (int k = 0; k <= max_len; ++k) { const uint8_t c = s[k]; if (!c) break; if (!end || p < end) *p = c; ++p; }
+    return p;
 }
 
 // the unused bytes in front of the text in the image of the span that begins at b0, and where the span's first byte stands in the image

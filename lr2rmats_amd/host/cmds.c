@@ -200,7 +200,7 @@ h_job *h_job_open(int argc, char **argv, int *exit_code)
     const char *hdr_file = NULL;
     int c;
     *exit_code = 0;
-    optind = 1;
+    optind = 0;                                            /* (0, not 1: a second job of one process -- hostlib.Job -- makes getopt forget the permutation of the first) */
     while ((c = getopt_long(argc, argv, "m:b:j:J:M:e:i:t:sd:D:f:cl:o:nE:a:A:k:v:u:y:S:", lopt, NULL)) >= 0) {
         switch (c) {
         case 'm': if (optarg[0] == 'b') j->mode = 0; else if (optarg[0] == 'g') j->mode = 1; else { *exit_code = update_usage(); free(j); return NULL; } break;
@@ -289,6 +289,13 @@ void h_job_views(h_job *j, l2r_params *prm, l2r_annotation *a, l2r_junctions *s,
     s->n = j->sj.n; s->tid = j->sj.tid; s->don = j->sj.don; s->acc = j->sj.acc; s->uniq_c = j->sj.uniq; s->multi_c = j->sj.multi;
     r->n_reads = j->reads.n; r->n_cigar = j->reads.n_cig; r->tid = j->reads.tid; r->pos = j->reads.pos; r->rev = j->reads.rev;
     r->cig_off = j->reads.cig_off; r->cig = j->reads.cig; r->first_read_index = 0; r->cig_summary = j->reads.cig_sum;
+}
+
+void h_job_detail_views(const h_job *j, h_detail_views *v)
+{
+    v->n_chr = j->chr.n; v->chr = (const char *const *)j->chr.name;
+    v->names_len = (int64_t)j->reads.names.len; v->names = (const uint8_t *)j->reads.names.buf; v->qname = j->reads.qname;
+    v->anno_names_len = (int64_t)j->anno.names.len; v->anno_names = (const uint8_t *)j->anno.names.buf; v->tx_gid = j->anno.gid; v->tx_gname = j->anno.gname;
 }
 
 static int tail_threads(const h_job *j, const h_reads *reads);
@@ -738,8 +745,83 @@ static void early_engine_drop(void)
     if (g_early.ctx) { l2r_destroy(g_early.ctx); g_early.ctx = NULL; }
 }
 
+/* The detail table (-A) through the engine (l2r_detail_*, include/lr2rmats_hip.h): every engine shard's lines are composed while the
+ * shard's results still lie in HBM (rows with res == NULL) and written batch by batch -- L2R_DETAIL_BATCH rows (default 1 Mi) and
+ * L2R_DETAIL_TEXT_MAX bytes (default 1 GiB) -- behind the column line.  L2R_DETAIL_ROUTE=host: the engine's host routine.  A shard with a
+ * read outside the engine's domain (-1 from l2r_detail_rows: nothing of the shard has been written) goes through the tail's own writer
+ * (h_detail_rows), shard by shard: the file's bytes are the same.  Any other failure is fatal.  L2R_TIMING=1: one line on stderr. */
+typedef struct {
+    FILE *fp; int no_header;
+    const h_chroms *chr; const h_reads *reads; const h_gtf *anno;
+    int begun, engine_host;
+    int64_t rows, own_rows, bytes, batches;
+    int64_t *ref_off; uint8_t *ref_names, *text; int64_t text_cap;
+} detail_sink;
+
+static int64_t detail_env_count(const char *name, int64_t dflt)
+{
+    const char *e = getenv(name);
+    if (!e || !*e) return dflt;
+    const long long v = atoll(e);
+    return v >= 1 ? (int64_t)v : dflt;
+}
+
+/* the reads [lo, hi) -- the shard the context has just run; res: the results of the whole input so far, for the tail's writer */
+static void detail_shard(l2r_ctx *ctx, const char *who, detail_sink *d, int64_t lo, int64_t hi, const h_result *res)
+{
+    if (!d->begun) {
+        const int n_ref = d->chr->n;
+        d->ref_off = (int64_t *)h_malloc((size_t)(n_ref + 1) * 8);
+        d->ref_off[0] = 0;
+        for (int t = 0; t < n_ref; ++t) d->ref_off[t + 1] = d->ref_off[t] + (int64_t)strlen(d->chr->name[t]);
+        d->ref_names = (uint8_t *)h_malloc((size_t)d->ref_off[n_ref] + 1);
+        for (int t = 0; t < n_ref; ++t) memcpy(d->ref_names + d->ref_off[t], d->chr->name[t], (size_t)(d->ref_off[t + 1] - d->ref_off[t]));
+        const l2r_detail_params prm = { n_ref, d->ref_off, d->ref_names, d->anno->n_tx, (int64_t)d->anno->names.len, (const uint8_t *)d->anno->names.buf,
+                                        d->anno->gid, d->anno->gname };
+        if (l2r_detail_begin(ctx, &prm)) engine_fail(who);
+        if (!d->no_header) h_detail_header(d->fp);
+        d->begun = 1;
+    }
+    const int64_t n = hi - lo;
+    if (n <= 0) return;
+    const l2r_detail_reads rows = { n, d->reads->tid + lo, (int64_t)d->reads->names.len, (const uint8_t *)d->reads->names.buf, d->reads->qname + lo, NULL };
+    int64_t total = 0;
+    const int rc = l2r_detail_rows(ctx, &rows, &total);
+    if (rc == -1) {                                         /* (nothing of the shard has been written) */
+        h_detail_rows(d->fp, d->chr, d->reads, d->anno, res, lo, hi);
+        d->own_rows += n;
+        return;
+    }
+    if (rc) engine_fail(who);
+    const int64_t max_rows = detail_env_count("L2R_DETAIL_BATCH", (int64_t)1 << 20), max_bytes = detail_env_count("L2R_DETAIL_TEXT_MAX", (int64_t)1 << 30);
+    for (int64_t first = 0; first < n;) {
+        int64_t take = 0, bytes = 0;
+        if (l2r_detail_lines(ctx, first, max_rows, max_bytes, &take, &bytes) || take < 1) engine_fail(who);
+        if (bytes > d->text_cap) { free(d->text); d->text_cap = bytes + bytes / 4 + 64; d->text = (uint8_t *)h_malloc((size_t)d->text_cap); }
+        if (bytes) {
+            if (l2r_detail_out(ctx, d->text, d->text_cap)) engine_fail(who);
+            if (fwrite(d->text, 1, (size_t)bytes, d->fp) != (size_t)bytes) h_fatal(who, "Error in writing the detail table\n");
+        }
+        ++d->batches; d->bytes += bytes; first += take;
+    }
+    d->rows += n;
+    {   double st[7] = {0, 0, 0, 0, 0, 0, 0};
+        (void)l2r_detail_stats(ctx, st, 7);
+        d->engine_host = st[6] != 0; }
+}
+
+static void detail_done(const char *who, detail_sink *d)
+{
+    const char *tm = getenv("L2R_TIMING");
+    if (tm && atoi(tm) != 0)
+        fprintf(stderr, "[%s] detail text: route %s, %lld rows, %lld bytes, %lld batches\n", who,
+                d->own_rows ? (d->rows ? "mixed" : "off") : d->engine_host ? "host" : "device", (long long)d->rows, (long long)d->bytes, (long long)d->batches);
+    free(d->ref_off); free(d->ref_names); free(d->text);
+    d->ref_off = NULL; d->ref_names = NULL; d->text = NULL;
+}
+
 static void run_engine(const char *who, const l2r_params *prm, const l2r_annotation *a, const l2r_junctions *s,
-                       const l2r_reads *r, h_result *out, int64_t **acc_read)
+                       const l2r_reads *r, h_result *out, int64_t **acc_read, detail_sink *detail /* NULL: none; only with acc_read == NULL */)
 {
     int anno_set = 0;
     l2r_ctx *ctx = engine_take(who, &anno_set);
@@ -780,6 +862,7 @@ static void run_engine(const char *who, const l2r_params *prm, const l2r_annotat
             }
         }
         if (exons) for (int64_t k = 0; k <= add_rows; ++k) out->ex_off[rows + k] += exons;          /* shard-local -> global offsets */
+        if (detail && !acc_read) detail_shard(ctx, who, detail, lo, hi, out);
         rows += add_rows; exons += add_ex;
         lo = hi;
     } while (lo < r->n_reads);
@@ -788,6 +871,10 @@ static void run_engine(const char *who, const l2r_params *prm, const l2r_annotat
     out->ex_off[rows] = exons;
     if (acc_read) *acc_read = idx;
     free(off_tmp); free(rec);
+    if (detail && !acc_read) {
+        if (!detail->begun) detail_shard(ctx, who, detail, 0, 0, out);      /* (no record: the column line alone) */
+        detail_done(who, detail);
+    }
     h_stage_time("engine: upload, kernels, download");
     l2r_destroy(ctx);
 }
@@ -1168,7 +1255,7 @@ static int update_gtf_multi(h_job *j, int n_gpus, int gathered)
                 off = (int64_t *)h_malloc((size_t)(hi - lo + 1) * 8);
                 for (int64_t i = 0; i <= hi - lo; ++i) off[i] = r.cig_off[lo + i] - r.cig_off[lo];
                 sub.cig_off = off; sub.first_read_index = lo;
-                run_engine("update_gtf", &prm, &a, &s, &sub, &out, NULL);
+                run_engine("update_gtf", &prm, &a, &s, &sub, &out, NULL, NULL);
             } else result_reserve(&out, 0, 0);
             l2r_result res = { out.n, out.n_ex, out.n_ex, out.ex_off, out.ex_start, out.ex_end, out.ex_flag, out.info, out.ref_tx };
             h_job_finish_part(j, lo, hi, &res, suffix, tmp_base, k == 0, cnt);
@@ -1296,12 +1383,21 @@ int h_cmd_update_gtf(int argc, char **argv)
     const char *force = getenv("L2R_ROUTE");                 /* diagnostics / tests: "full" or "accepted" */
     const int accepted_only = force ? !strcmp(force, "accepted") && !needs_all_reads(j) : !needs_all_reads(j);
     if (!accepted_only) {
-        run_engine("update_gtf", &prm, &a, &s, &r, &out, NULL);
+        /* the detail table: the engine writes it shard by shard (detail_shard) and the tail is given no detail file; L2R_DETAIL_ROUTE=off:
+         * the tail's print_detail */
+        const char *dr = getenv("L2R_DETAIL_ROUTE");
+        const int detail_off = dr && !strcmp(dr, "off");
+        detail_sink sink; memset(&sink, 0, sizeof sink);
+        sink.fp = j->o.bam_detail; sink.no_header = j->o.no_detail_header; sink.chr = &j->chr; sink.reads = &j->reads; sink.anno = &j->anno;
+        const int by_engine = j->o.bam_detail && !detail_off;
+        run_engine("update_gtf", &prm, &a, &s, &r, &out, NULL, by_engine ? &sink : NULL);
+        if (by_engine) { fclose(j->o.bam_detail); j->o.bam_detail = NULL; }
+        else if (j->o.bam_detail) { const char *tm = getenv("L2R_TIMING"); if (tm && atoi(tm) != 0) fprintf(stderr, "[update_gtf] detail text: route off, 0 rows, 0 bytes, 0 batches\n"); }
         l2r_result res = { out.n, out.n_ex, out.n_ex, out.ex_off, out.ex_start, out.ex_end, out.ex_flag, out.info, out.ref_tx };
         rc = h_job_finish(j, &res);
     } else {
         int64_t *idx = NULL;
-        run_engine("update_gtf", &prm, &a, &s, &r, &out, &idx);
+        run_engine("update_gtf", &prm, &a, &s, &r, &out, &idx, NULL);
         l2r_result res = { out.n, out.n_ex, out.n_ex, out.ex_off, out.ex_start, out.ex_end, out.ex_flag, out.info, out.ref_tx };
         rc = h_job_finish_accepted(j, &res, idx);
         free(idx);
@@ -1330,7 +1426,7 @@ static void exons_only(const char *who, const char *fn, const l2r_params *prm, h
     int64_t zero_off = 0; a.tx_ex_off = &zero_off;
     l2r_junctions s; memset(&s, 0, sizeof s);
     l2r_reads r = { reads->n, reads->n_cig, reads->tid, reads->pos, reads->rev, reads->cig_off, reads->cig, 0, reads->cig_sum };
-    run_engine(who, prm, &a, &s, &r, out, NULL);
+    run_engine(who, prm, &a, &s, &r, out, NULL, NULL);
 }
 
 /* src/gtf.c:597-604 print_trans: gene_id + transcript_id only, exons always ascending */

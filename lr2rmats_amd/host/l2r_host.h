@@ -248,6 +248,11 @@ typedef struct {
 void h_update_tail(const h_update_opts *o, const h_chroms *chr, const h_reads *reads, const h_gtf *anno,
                    const h_result *res, int64_t n_sj);
 
+/* The detail table (-A) outside the tail (cmds.c writes it shard by shard through the engine, l2r_detail_*): its column line, and the
+ * rows [lo, hi) of `res` by the tail's own writer (print_detail) -- reads, offsets and rows are the whole input's. */
+void h_detail_header(FILE *fp);
+void h_detail_rows(FILE *fp, const h_chroms *chr, const h_reads *reads, const h_gtf *anno, const h_result *res, int64_t lo, int64_t hi);
+
 void h_write_summary_text(FILE *s, int anno_genes, int anno_tx, const int64_t *counters);
 
 /* The GTF text of a selection of blocks through the engine (l2r_gtftext_*: composed on the device, or by the engine's host routine with
@@ -289,6 +294,11 @@ int    h_job_shard(const h_job *j, int64_t *lo, int64_t *hi, int64_t *n_total);
 /* h_job_shard() == 2: the rank loaded the BGZF blocks of its own records only (h_read_alignments_blocks); info as there */
 void   h_job_shard_blocks(const h_job *j, int64_t info[8]);
 void   h_job_views(h_job *j, l2r_params *prm, l2r_annotation *anno, l2r_junctions *sj, l2r_reads *reads);
+/* what a detail line needs beside the results (l2r_detail_params, l2r_detail_reads): the chromosome names by tid, the read names and
+ * the annotation's gene ids / gene names as tables of NUL-terminated strings with their id columns.  Valid until h_job_free */
+typedef struct { int32_t n_chr; const char *const *chr; int64_t names_len; const uint8_t *names; const uint32_t *qname;
+                 int64_t anno_names_len; const uint8_t *anno_names; const uint32_t *tx_gid, *tx_gname; } h_detail_views;
+void   h_job_detail_views(const h_job *j, h_detail_views *v);
 int    h_job_finish(h_job *j, const l2r_result *res);
 void   h_job_free(h_job *j);
 /* 1: an output of this run lists every read (detail.txt, -a / -k / -u, summary.txt); 0: the accepted reads are all the

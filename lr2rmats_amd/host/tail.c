@@ -278,36 +278,51 @@ static void index_list(obuf *o, const uint8_t *f, int n, uint8_t bit, int two_pe
     if (trailing_tab) ob_c(o, '\t');
 }
 
-static void print_detail(FILE *fp, const tail_ctx *c)
+static const char DETAIL_HEADER[] = "ReadName\tchr\tstrand\tNovel\tGeneID\tGeneName\tExonCount\tExonStart\tExonEnd\tNovelExonCount\tNovelExonIndex\tNovelSiteCount\tNovelSiteIndex\tNovelJunctionCount\tNovelJunctionIndex\tUnreliableJunctionCount\tUnreliableJunctionIndex\n";
+
+/* the rows [lo, hi) of the detail table: src/update_gtf.c:297-419 print_bam_detail_trans */
+static void detail_rows(obuf *o, const tail_ctx *c, int64_t lo, int64_t hi)
 {
-    /* src/update_gtf.c:297-419 print_bam_detail_trans */
-    obuf o; ob_init(&o, fp);
     const h_result *r = c->res;
-    if (!c->o->no_detail_header) {
-        ob_s(&o, "ReadName\tchr\tstrand\tNovel\tGeneID\tGeneName\tExonCount\tExonStart\tExonEnd\tNovelExonCount\tNovelExonIndex\tNovelSiteCount\tNovelSiteIndex\tNovelJunctionCount\tNovelJunctionIndex\tUnreliableJunctionCount\tUnreliableJunctionIndex\n");
-    }
-    for (int64_t i = 0; i < r->n; ++i) {
+    for (int64_t i = lo; i < hi; ++i) {
         const int64_t off = r->ex_off[i];
         const uint32_t info = r->info[i];
         const int n = (int)L2R_INFO_NEXON(info);
         const int cls = (info & L2R_INFO_KNOWN) ? 0 : ((info & L2R_INFO_KNOWN_SITE) ? 1 : 2);
         const uint8_t *f = r->ex_flag + off;
-        ob_s(&o, h_str(&c->reads->names, c->reads->qname[i])); ob_c(&o, '\t');
-        ob_s(&o, c->chr->name[c->reads->tid[i]]); ob_c(&o, '\t');
-        ob_c(&o, "+-"[(info & L2R_INFO_REV) != 0]); ob_c(&o, '\t');
-        ob_i(&o, cls); ob_c(&o, '\t');
-        ob_s(&o, gene_id_of(c, r->ref_tx[i])); ob_c(&o, '\t'); ob_s(&o, gene_name_of(c, r->ref_tx[i])); ob_c(&o, '\t');
-        ob_i(&o, n); ob_c(&o, '\t');
-        for (int j = 0; j < n; ++j) { if (j) ob_c(&o, ','); ob_i(&o, r->ex_start[off + j]); }
-        ob_c(&o, '\t');
-        for (int j = 0; j < n; ++j) { if (j) ob_c(&o, ','); ob_i(&o, r->ex_end[off + j]); }
-        ob_c(&o, '\t');
-        index_list(&o, f, n, L2R_EXF_NOVEL_EXON, 0, 1);
-        index_list(&o, f, n - 1, 0, 1, 1);
-        index_list(&o, f, n - 1, L2R_EXF_NOVEL_JUNC, 0, 1);
-        index_list(&o, f, n - 1, L2R_EXF_UNREL_JUNC, 0, 0);
-        ob_c(&o, '\n');
+        ob_s(o, h_str(&c->reads->names, c->reads->qname[i])); ob_c(o, '\t');
+        ob_s(o, c->chr->name[c->reads->tid[i]]); ob_c(o, '\t');
+        ob_c(o, "+-"[(info & L2R_INFO_REV) != 0]); ob_c(o, '\t');
+        ob_i(o, cls); ob_c(o, '\t');
+        ob_s(o, gene_id_of(c, r->ref_tx[i])); ob_c(o, '\t'); ob_s(o, gene_name_of(c, r->ref_tx[i])); ob_c(o, '\t');
+        ob_i(o, n); ob_c(o, '\t');
+        for (int j = 0; j < n; ++j) { if (j) ob_c(o, ','); ob_i(o, r->ex_start[off + j]); }
+        ob_c(o, '\t');
+        for (int j = 0; j < n; ++j) { if (j) ob_c(o, ','); ob_i(o, r->ex_end[off + j]); }
+        ob_c(o, '\t');
+        index_list(o, f, n, L2R_EXF_NOVEL_EXON, 0, 1);
+        index_list(o, f, n - 1, 0, 1, 1);
+        index_list(o, f, n - 1, L2R_EXF_NOVEL_JUNC, 0, 1);
+        index_list(o, f, n - 1, L2R_EXF_UNREL_JUNC, 0, 0);
+        ob_c(o, '\n');
     }
+}
+
+static void print_detail(FILE *fp, const tail_ctx *c)
+{
+    obuf o; ob_init(&o, fp);
+    if (!c->o->no_detail_header) ob_s(&o, DETAIL_HEADER);
+    detail_rows(&o, c, 0, c->res->n);
+    ob_done(&o);
+}
+
+void h_detail_header(FILE *fp) { if (fputs(DETAIL_HEADER, fp) < 0) h_fatal("update_gtf", "Error in writing the detail table\n"); }
+
+void h_detail_rows(FILE *fp, const h_chroms *chr, const h_reads *reads, const h_gtf *anno, const h_result *res, int64_t lo, int64_t hi)
+{
+    const tail_ctx c = { NULL, chr, reads, anno, res };
+    obuf o; ob_init(&o, fp);
+    detail_rows(&o, &c, lo, hi);
     ob_done(&o);
 }
 

@@ -40,6 +40,7 @@ def load_library():
         lib.h_job_shard_blocks.argtypes = [C.c_void_p, C.POINTER(C.c_int64)]
         lib.h_job_shard_blocks.restype = None
         lib.h_job_views.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        lib.h_job_detail_views.argtypes = [C.c_void_p, C.c_void_p]
         lib.h_job_finish.argtypes = [C.c_void_p, C.c_void_p]
         lib.h_job_finish.restype = C.c_int
         lib.h_job_free.argtypes = [C.c_void_p]
@@ -297,6 +298,11 @@ def bed_run(in_path: str, out_path: str, color: str = "255,0,0"):
     return int(rc), [int(v) for v in counts]
 
 
+class _CDetailViews(C.Structure):
+    _fields_ = [("n_chr", C.c_int32), ("chr", C.POINTER(C.c_char_p)), ("names_len", C.c_int64), ("names", C.c_void_p), ("qname", C.POINTER(C.c_uint32)),
+                ("anno_names_len", C.c_int64), ("anno_names", C.c_void_p), ("tx_gid", C.POINTER(C.c_uint32)), ("tx_gname", C.POINTER(C.c_uint32))]
+
+
 class Job:
     """One ``update-gtf`` invocation: argv = ["update-gtf", options..., in.bam, old.gtf]."""
 
@@ -353,6 +359,15 @@ class Job:
         sm = _arr(r.cig_summary, 3 * r.n_reads, np.uint32).reshape(-1, 3) if r.cig_summary else None
         return dict(tid=_arr(r.tid, r.n_reads, np.int32), pos=_arr(r.pos, r.n_reads, np.int32), rev=_arr(r.rev, r.n_reads, np.uint8),
                     cig_off=_arr(r.cig_off, r.n_reads + 1, np.int64), cig=_arr(r.cig, r.n_cigar, np.uint32), cig_summary=sm)
+
+    def detail_views(self):
+        """What a detail line needs beside the results (capi.Engine.detail_begin / detail_rows): ``refs`` (chromosome names by tid), the
+        read-name table ``names`` with ``qname``, the annotation's table ``anno`` with ``tx_gid`` and ``tx_gname`` (copies)."""
+        v = _CDetailViews()
+        self.lib.h_job_detail_views(self.h, C.byref(v))
+        return dict(refs=[v.chr[k] for k in range(v.n_chr)], names=C.string_at(v.names, v.names_len) if v.names else b"", qname=_arr(v.qname, self.reads.n_reads, np.uint32).copy(),
+                    anno=C.string_at(v.anno_names, v.anno_names_len) if v.anno_names else b"", tx_gid=_arr(v.tx_gid, self.anno.n_tx, np.uint32).copy(),
+                    tx_gname=_arr(v.tx_gname, self.anno.n_tx, np.uint32).copy())
 
     def finish(self, ex_off, ex_start, ex_end, ex_flag, info, ref_tx) -> int:
         """Sequential tail + writers.  Arrays as in ``capi.Result`` (info carries the exon count in bits 8..31)."""
