@@ -634,6 +634,57 @@ int          l2r_gtftext_lines(l2r_ctx *ctx, int64_t first, int64_t max_blocks, 
 int          l2r_gtftext_out(l2r_ctx *ctx, uint8_t *text, int64_t cap);
 int          l2r_gtftext_stats(l2r_ctx *ctx, double *out, int n);
 
+/* ---- the read lists of `update-gtf -a / -k / -v / -u`: classified reads as GTF blocks of form L2R_GTX_READ, selected by class on the
+ * device.  The rule, stated here once (src/update_gtf.c:837-913 and :939-964; host/tail.c).  Read i of a run, or of an uploaded
+ * l2r_result, has n = info >> 8 exons xs[0..n), xe[0..n) with the flags f[0..n), ref = ref_tx[i], rev = (info & L2R_INFO_REV) != 0, its
+ * reference tid[i] and its names qname[i] and tid_name[i] (byte offsets into the reads' table; tid_name == NULL: qname stands for it).
+ * Two scalars come with the reads: has_sj (a junction table was set) and split (l2r_params.split_trans).
+ * Lists, in read order:
+ *     L2R_GTX_LIST_ALL      every read, whole
+ *     L2R_GTX_LIST_KNOWN    reads with FULL && KNOWN, whole
+ *     L2R_GTX_LIST_UNRECOG  reads with FULL && !KNOWN && !KNOWN_SITE, whole
+ *     L2R_GTX_LIST_NOVEL    reads with FULL && !KNOWN && KNOWN_SITE: whole where !has_sj || SJ_PASS; else, where split, the read's pieces
+ *                           k = 0, 1, ... in ascending order; else nothing
+ * Pieces: walk j = 0 .. n - 1 with first = 0 and seen_novel = seen_known = 0.  For j < n - 1, L2R_EXF_NOVEL_JUNC of f[j] sets seen_novel,
+ * its absence seen_known.  At j == n - 1, or where f[j] has L2R_EXF_UNREL_JUNC: if seen_novel && seen_known && j - first >= 1 the exons
+ * [first, j] are piece k, and k += 1; in every case first = j + 1 and both flags are cleared.
+ * A whole read is the block of form L2R_GTX_READ with ref = tid[i], S = xs[0], E = xe[n - 1], strand rev, cov 1, g = the gene id of
+ * annotation transcript ref (`NA` where ref < 0), t = tid_name[i], G = the gene name of ref (or `NA`), T = qname[i], the exons descending
+ * where rev; an empty name drops its attribute.  Piece k over the exons [first, last] (quirk Q2): its TRANSCRIPT line is that of a block
+ * with reference 0, S = E = 0 and strand `+`; its EXON lines carry tid[i] and rev, and are ascending whatever the strand (the order follows
+ * the transcript line's strand); t and T carry the suffix `.split.<k>` (%d); g, G and cov as for the whole read.
+ * Domain errors, as for the GTF block (-1, nothing written, the smallest block of the list and its kind named), looked for in this order:
+ * a tid outside [0, n_ref); a read with no exon; ref at or beyond the annotation's transcripts; the four names in the order g, t, G, T,
+ * each with the id / 255-byte / NUL tests (g and G in the annotation's table, t and T in the reads'); a piece whose t or T with its suffix
+ * has 100 or more bytes; a negative coordinate; a block of 2^32 - 64 bytes or more.
+ *     l2r_gtftext_anno      once behind l2r_gtftext_begin with form READ: the annotation's gene tables, as in l2r_detail_params, to HBM
+ *     l2r_gtftext_reads     the reads -- tid, the names table, qname, tid_name (may be NULL) -- to HBM, with res, the arrays of an
+ *                           l2r_download (n_reads == n), which are uploaded; res == NULL: the results of the context's last l2r_run where
+ *                           they lie in HBM (n must equal the run's reads, which must have kept its results).  It takes the place of
+ *                           l2r_gtftext_rows
+ *     l2r_gtftext_list      one list of the reads: k_rl_count (one thread per read: 0, 1 or its pieces), k_scan_u32, k_rl_take (read, first
+ *                           exon, exon count, piece number or -1 per block, in read order) and k_rl_measure, all on the device; *m blocks,
+ *                           and the totals.  It takes the place of l2r_gtftext_blocks, the domain errors surface here, and it may be
+ *                           called for each list in turn on the same reads
+ *     l2r_gtftext_list_out  the selection of the last l2r_gtftext_list (tests, tools): any column may be NULL
+ * l2r_gtftext_lines, _out and _stats serve both; behind a list k_rl_write (csrc/l2r_readlist.hip.h) composes the text as k_gtx_write does,
+ * with a per-block length of the transcript line beside that of the exon lines.  L2R_GTX_ROUTE=host: the exact host routine of
+ * csrc/l2r_readlistplan.hip.h.  l2r_gtftext_stats has two more words behind a list: [12] device milliseconds of the selection (k_rl_count,
+ * k_scan_u32, k_rl_take; with L2R_GTX_TIMING=1) and [13] the piece blocks of the list. */
+#define L2R_GTX_LIST_ALL 0
+#define L2R_GTX_LIST_KNOWN 1
+#define L2R_GTX_LIST_NOVEL 2
+#define L2R_GTX_LIST_UNRECOG 3
+#define L2R_GTX_PIECE_NAME_MAX 100      /* bytes a piece's name with its suffix stays below */
+typedef struct { int64_t n_tx, anno_names_len; const uint8_t *anno_names; const uint32_t *tx_gid, *tx_gname; } l2r_gtx_anno;
+typedef struct { int64_t n; const int32_t *tid; int64_t names_len; const uint8_t *names; const uint32_t *qname, *tid_name /* may be NULL */;
+                 const l2r_result *res; /* NULL: the results of the context's last l2r_run where they lie in HBM */
+                 int32_t has_sj, split; } l2r_gtx_reads;
+int          l2r_gtftext_anno(l2r_ctx *ctx, const l2r_gtx_anno *anno);
+int          l2r_gtftext_reads(l2r_ctx *ctx, const l2r_gtx_reads *reads);
+int          l2r_gtftext_list(l2r_ctx *ctx, int list, int64_t *m, int64_t *n_lines, int64_t *n_bytes);
+int          l2r_gtftext_list_out(l2r_ctx *ctx, int32_t *read, int32_t *first, int32_t *count, int32_t *piece);
+
 /* ---- the per-read detail table of `update-gtf -A` (host/cmds.c, host/tail.c print_detail): one text line per read, the text composed on
  * the device.  The rule, stated here once (print_bam_detail_trans, src/update_gtf.c:297-419).  For read i: n = info >> 8 exons with the
  * starts xs[0..n), the ends xe[0..n) and the flags f[0..n); ref = ref_tx[i].  Numbers are printed as %d.

@@ -40,6 +40,7 @@ EXPORTS = [
     "l2r_bed_begin", "l2r_bed_lines", "l2r_bed_text_out", "l2r_bed_cut", "l2r_bed_stats",
     "l2r_uniq_merge", "l2r_uniq_out", "l2r_uniq_stats",
     "l2r_gtftext_begin", "l2r_gtftext_rows", "l2r_gtftext_blocks", "l2r_gtftext_lines", "l2r_gtftext_out", "l2r_gtftext_stats",
+    "l2r_gtftext_anno", "l2r_gtftext_reads", "l2r_gtftext_list", "l2r_gtftext_list_out",
     "l2r_detail_begin", "l2r_detail_rows", "l2r_detail_lines", "l2r_detail_out", "l2r_detail_stats",
 ]
 SJ_E_UNKNOWN_TID = -3
@@ -177,6 +178,15 @@ class CGtxBlocks(C.Structure):
     _fields_ = [("m", C.c_int64), ("sel", C.c_void_p), ("start", C.c_void_p), ("end", C.c_void_p), ("cov", C.c_void_p)]
 
 
+class CGtxAnno(C.Structure):
+    _fields_ = [("n_tx", C.c_int64), ("anno_names_len", C.c_int64), ("anno_names", C.c_void_p), ("tx_gid", C.c_void_p), ("tx_gname", C.c_void_p)]
+
+
+class CGtxReads(C.Structure):
+    _fields_ = [("n", C.c_int64), ("tid", C.c_void_p), ("names_len", C.c_int64), ("names", C.c_void_p), ("qname", C.c_void_p), ("tid_name", C.c_void_p),
+                ("res", C.c_void_p), ("has_sj", C.c_int32), ("split", C.c_int32)]
+
+
 class CDetailParams(C.Structure):
     _fields_ = [("n_ref", C.c_int32), ("ref_off", C.c_void_p), ("ref_names", C.c_void_p), ("n_tx", C.c_int64), ("anno_names_len", C.c_int64),
                 ("anno_names", C.c_void_p), ("tx_gid", C.c_void_p), ("tx_gname", C.c_void_p)]
@@ -280,6 +290,10 @@ def load_library():
         lib.l2r_gtftext_lines.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p]
         lib.l2r_gtftext_out.argtypes = [C.c_void_p, C.c_void_p, C.c_int64]
         lib.l2r_gtftext_stats.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
+        lib.l2r_gtftext_anno.argtypes = [C.c_void_p, C.c_void_p]
+        lib.l2r_gtftext_reads.argtypes = [C.c_void_p, C.c_void_p]
+        lib.l2r_gtftext_list.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+        lib.l2r_gtftext_list_out.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         lib.l2r_detail_begin.argtypes = [C.c_void_p, C.c_void_p]
         lib.l2r_detail_rows.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         lib.l2r_detail_lines.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p]
@@ -433,7 +447,9 @@ GTX_PLAIN, GTX_READ = 0, 1
 GTX_TILE, GTX_LDS_BYTES = 32, 32768         # L2R_GTX_TILE, L2R_GTX_LDS_BYTES (include/lr2rmats_hip.h)
 DETAIL_TILE, DETAIL_LDS_BYTES = 32, 32768   # L2R_DETAIL_TILE, L2R_DETAIL_LDS_BYTES (include/lr2rmats_hip.h)
 DETAIL_STAT_NAMES = ["rows", "lines", "bytes", "wave_form", "tiles_lds", "tiles_direct", "route", "guard_intact", "batches", "k_detail_measure", "k_scan_u32", "k_detail_write"]
-GTX_STAT_NAMES = ["blocks", "lines", "bytes", "wave_form", "tiles_lds", "tiles_direct", "route", "guard_intact", "batches", "k_gtx_measure", "k_scan_u32", "k_gtx_write"]
+GTX_STAT_NAMES = ["blocks", "lines", "bytes", "wave_form", "tiles_lds", "tiles_direct", "route", "guard_intact", "batches", "k_gtx_measure", "k_scan_u32", "k_gtx_write",
+                  "k_rl_select", "piece_blocks"]
+GTX_LIST_ALL, GTX_LIST_KNOWN, GTX_LIST_NOVEL, GTX_LIST_UNRECOG = 0, 1, 2, 3
 
 
 UNIQ_STAT_NAMES = ["rows", "unique", "clusters", "largest_cluster", "route", "hits_identical", "hits_contained", "hits_single", "end_extensions",
@@ -810,6 +826,49 @@ class Engine:
         out = np.zeros(len(GTX_STAT_NAMES), np.float64)
         self._chk(self.lib.l2r_gtftext_stats(self.ctx, out.ctypes.data, len(out)))
         return {k: float(v) for k, v in zip(GTX_STAT_NAMES, out)}
+
+    # ---- the read lists of `update-gtf -a / -k / -v / -u` (include/lr2rmats_hip.h: l2r_gtftext_anno / _reads / _list / _list_out)
+    def gtftext_anno(self, anno_names=b"", tx_gid=(), tx_gname=()) -> None:
+        """Behind gtftext_begin with form GTX_READ: the annotation's gene tables, as in detail_begin."""
+        anno = np.frombuffer(bytes(anno_names), np.uint8) if not isinstance(anno_names, np.ndarray) else np.ascontiguousarray(anno_names, np.uint8)
+        gid, gname = np.ascontiguousarray(tx_gid, np.uint32), np.ascontiguousarray(tx_gname, np.uint32)
+        if gid.shape != gname.shape:
+            raise ValueError("gtftext_anno: tx_gid and tx_gname of one length")
+        a = CGtxAnno(int(gid.size), int(anno.size), anno.ctypes.data if anno.size else None, gid.ctypes.data if gid.size else None, gname.ctypes.data if gname.size else None)
+        self._chk(self.lib.l2r_gtftext_anno(self.ctx, C.byref(a)))
+
+    def gtftext_reads(self, tid, names, qname, tid_name=None, res=None, has_sj=False, split=False, n=None) -> None:
+        """The classified reads: tid, the table ``names``, ``qname`` and ``tid_name`` (byte offsets; None: qname stands for it) and ``res``,
+        a Result (the arrays of a download), which is uploaded; None: the results of the last run where they lie in HBM (``n`` overrides
+        the read count, which must equal the run's reads)."""
+        names = np.frombuffer(bytes(names), np.uint8) if not isinstance(names, np.ndarray) else np.ascontiguousarray(names, np.uint8)
+        tid, qname = np.ascontiguousarray(tid, np.int32), np.ascontiguousarray(qname, np.uint32)
+        tn = None if tid_name is None else np.ascontiguousarray(tid_name, np.uint32)
+        n = int(tid.shape[0]) if n is None else int(n)
+        keep, cres = [], None
+        if res is not None:
+            a = [np.ascontiguousarray(res.ex_off, np.int64), np.ascontiguousarray(res.ex_start, np.int32), np.ascontiguousarray(res.ex_end, np.int32),
+                 np.ascontiguousarray(res.ex_flag, np.uint8), np.ascontiguousarray(res.info, np.uint32), np.ascontiguousarray(res.ref_tx, np.int32)]
+            x = int(a[0][-1]) if a[0].size else 0
+            keep = [v if v.size else np.zeros(1, v.dtype) for v in a]
+            cres = CResult(n, x, x, keep[0].ctypes.data_as(_i64p), keep[1].ctypes.data_as(_i32p), keep[2].ctypes.data_as(_i32p), keep[3].ctypes.data_as(_u8p),
+                           keep[4].ctypes.data_as(_u32p), keep[5].ctypes.data_as(_i32p))
+        rd = CGtxReads(n, tid.ctypes.data if tid.size else None, int(names.size), names.ctypes.data if names.size else None, qname.ctypes.data if qname.size else None,
+                       None if tn is None or not tn.size else tn.ctypes.data, None if cres is None else C.addressof(cres), int(bool(has_sj)), int(bool(split)))
+        self._chk(self.lib.l2r_gtftext_reads(self.ctx, C.byref(rd)))
+
+    def gtftext_list(self, which: int):
+        """One list (GTX_LIST_*) of the reads: (blocks, n_lines, n_bytes) of its text; a block outside the domain raises L2RError (rc=-1)
+        naming the smallest such block of the list and the kind.  gtftext_lines / gtftext_all then give its text."""
+        m, n_lines, n_bytes = C.c_int64(0), C.c_int64(0), C.c_int64(0)
+        self._chk(self.lib.l2r_gtftext_list(self.ctx, int(which), C.byref(m), C.byref(n_lines), C.byref(n_bytes)))
+        return int(m.value), int(n_lines.value), int(n_bytes.value)
+
+    def gtftext_list_out(self, m: int):
+        """The selection of the last gtftext_list of ``m`` blocks: the columns read, first, count, piece (int32 each)."""
+        cols = [np.zeros(max(int(m), 1), np.int32) for _ in range(4)]
+        self._chk(self.lib.l2r_gtftext_list_out(self.ctx, *[c.ctypes.data for c in cols]))
+        return tuple(c[:int(m)] for c in cols)
 
     # ---- the detail table of `update-gtf -A` (include/lr2rmats_hip.h: l2r_detail_begin / _rows / _lines / _out / _stats)
     def detail_begin(self, ref_names, anno_names=b"", tx_gid=(), tx_gname=()) -> None:

@@ -29,6 +29,7 @@
 #include "l2r_bed.hip.h"
 #include "l2r_uniq.hip.h"
 #include "l2r_gtftext.hip.h"
+#include "l2r_readlist.hip.h"
 #include "l2r_detail.hip.h"
 #include "l2r_plan.hip.h"
 #include "l2r_tables.hip.h"
@@ -36,6 +37,7 @@
 #include "l2r_gtforder.hip.h"
 #include "l2r_bedplan.hip.h"
 #include "l2r_gtftextplan.hip.h"
+#include "l2r_readlistplan.hip.h"
 #include "l2r_detailplan.hip.h"
 
 using namespace l2r;
@@ -274,7 +276,29 @@ struct GtxState {
     DevBuf<unsigned long long> word64;                  // k_gtx_measure: the smallest bad block << 4 | kind, the lines
     TextOut out;
     StageTimer clk;
-    double stats[12] = {0};                             // l2r_gtftext_stats
+    double stats[14] = {0};                             // l2r_gtftext_stats
+    // The read lists of `update-gtf -a / -k / -v / -u` (l2r_readlist.hip.h): the annotation's gene tables of l2r_gtftext_anno, the reads of
+    // l2r_gtftext_reads and the selection of the last l2r_gtftext_list.  While `active`, the blocks of len / fix / h_len are those of
+    // the list and l2r_gtftext_lines composes them with k_rl_write (or rl_text_host); l2r_gtftext_rows ends that.
+    struct Lists {
+        bool have_anno = false, have_reads = false, active = false;
+        bool run_res = false;                           // reads came with res == NULL: the results of the context's last l2r_run
+        bool has_sj = false, split = false;
+        l2r_gtx_anno anno{};                            // points into h_anno, h_gid, h_gname
+        std::vector<uint8_t> h_anno; std::vector<uint32_t> h_gid, h_gname;
+        DevBuf<uint8_t> d_anno; DevBuf<uint32_t> d_gid, d_gname;
+        int64_t n = 0, names_len = 0, n_pieces = 0;
+        int list = 0;
+        double exons_per_read = 0;
+        DevBuf<int32_t> tid, xs, xe, ref_tx; DevBuf<uint8_t> names, f; DevBuf<uint32_t> qname, tid_name, ex_off, info;   // (the results: uploaded reads only)
+        const uint32_t *tid_name_p = nullptr;           // qname's buffer where no tid_name came
+        struct Host {                                   // the host route's copies, and its selection
+            std::vector<int32_t> tid, xs, xe, ref_tx; std::vector<uint8_t> names, f; std::vector<uint32_t> qname, tid_name, info; std::vector<int64_t> ex_off;
+            RlSel sel;
+        } h;
+        DevBuf<uint32_t> cnt, hfix, word;               // cnt: blocks per read, scanned in place (n + 1); hfix: per block; word[0]: the blocks, [1]: the piece blocks
+        DevBuf<int32_t> b_read, b_first, b_count, b_piece;      // the selection
+    } rl;
 };
 
 // The detail table of `update-gtf -A` (l2r_detail.hip.h): the reference names and the annotation's gene tables of l2r_detail_begin, the
@@ -2986,7 +3010,7 @@ int l2r_uniq_stats(l2r_ctx *c, double *out, int n) { return stats_out(c ? c->uni
 
 // ---------------------------------------------------------------------------------------------- the GTF text of bam2gtf / unique-gtf
 // slots of l2r_gtftext_stats
-enum { GXS_BLOCKS = 0, GXS_LINES, GXS_BYTES, GXS_WAVE, GXS_TILES_LDS, GXS_TILES_DIRECT, GXS_ROUTE, GXS_GUARD, GXS_BATCHES, GXS_K_MEASURE, GXS_K_SCAN, GXS_K_WRITE, GXS_N };
+enum { GXS_BLOCKS = 0, GXS_LINES, GXS_BYTES, GXS_WAVE, GXS_TILES_LDS, GXS_TILES_DIRECT, GXS_ROUTE, GXS_GUARD, GXS_BATCHES, GXS_K_MEASURE, GXS_K_SCAN, GXS_K_WRITE, GXS_K_SELECT, GXS_PIECES, GXS_N };
 static_assert(GXS_N == sizeof(GtxState::stats) / sizeof(double) && GXS_K_MEASURE == 9, "l2r_gtftext_stats: the words of include/lr2rmats_hip.h");
 constexpr int GTXC_TOTAL = GTXC_N;                      // GtxState::word: k_gtx_write's counters, then the scan's total
 constexpr int GTX_E_ARG = -4;                           // arguments, order of calls: not -1, which is a domain error (the commands fall back on it)
@@ -2996,6 +3020,7 @@ int l2r_gtftext_begin(l2r_ctx *c, const l2r_gtx_params *p)
     if (!c) return fail(GTX_E_ARG, "[l2r_gtftext_begin] null argument");
     GtxState &m = c->gtx;
     m.begun = false; m.have_rows = false; m.have_blocks = false; m.out.have = false;
+    m.rl.have_anno = false; m.rl.have_reads = false; m.rl.active = false;
     for (double &v : m.stats) v = 0;
     {   std::string msg;
         if (gtx_check_params(p, msg)) return fail(GTX_E_ARG, "%s", msg.c_str()); }
@@ -3035,6 +3060,7 @@ int l2r_gtftext_rows(l2r_ctx *c, const l2r_gtx_rows *r)
     if (!c) return fail(GTX_E_ARG, "[l2r_gtftext_rows] null argument");
     GtxState &m = c->gtx;
     m.have_rows = false; m.have_blocks = false; m.out.have = false;
+    m.rl.have_reads = false; m.rl.active = false;
     if (!m.begun) return fail(GTX_E_ARG, "[l2r_gtftext_rows] no l2r_gtftext_begin in front");
     {   std::string msg;
         if (gtx_check_rows(r, m.prm.form, msg)) return fail(GTX_E_ARG, "%s", msg.c_str()); }
@@ -3108,11 +3134,33 @@ static void gtx_host_view(const GtxState &m, l2r_gtx_rows &r, GtxChains &cx, l2r
     b = l2r_gtx_blocks{m.m, m.has_sel ? h.sel.data() : nullptr, m.has_start ? h.start.data() : nullptr, m.has_end ? h.end.data() : nullptr, m.has_cov ? h.cov.data() : nullptr};
 }
 
+// the kernels' view of the reads and the selection of a list
+static RlIn rl_in(const l2r_ctx *c, const GtxState &m)
+{
+    const GtxState::Lists &l = m.rl;
+    RlIn in{};
+    in.n = l.n; in.m = m.m; in.tid = l.tid.p; in.names = l.names.p; in.names_len = l.names_len; in.qname = l.qname.p; in.tid_name = l.tid_name_p;
+    if (l.run_res) { in.ex_off = c->ex_off.p; in.info = c->info.p; in.xs = c->ex_start.p; in.xe = c->ex_end.p; in.ref_tx = c->ref_tx.p; in.f = c->ex_flag.p; }
+    else { in.ex_off = l.ex_off.p; in.info = l.info.p; in.xs = l.xs.p; in.xe = l.xe.p; in.ref_tx = l.ref_tx.p; in.f = l.f.p; }
+    in.n_tx = l.anno.n_tx; in.anno_len = l.anno.anno_names_len; in.anno = l.d_anno.p; in.tx_gid = l.d_gid.p; in.tx_gname = l.d_gname.p;
+    in.b_read = l.b_read.p; in.b_first = l.b_first.p; in.b_count = l.b_count.p; in.b_piece = l.b_piece.p;
+    in.n_ref = m.prm.n_ref; in.ref_off = m.ref.off.p; in.ref_names = m.ref.names.p; in.src = m.src.p; in.src_len = (uint32_t)m.prm.src_len;
+    in.list = l.list; in.has_sj = l.has_sj; in.split = l.split;
+    return in;
+}
+// ... and the host route's, over its copies
+static RlReads rl_host_view(const GtxState &m)
+{
+    const GtxState::Lists::Host &h = m.rl.h;
+    return RlReads{m.rl.n, h.tid.data(), m.rl.names_len, h.names.data(), h.qname.data(), h.tid_name.data(), h.ex_off.data(), h.info.data(), h.ref_tx.data(),
+                   h.xs.data(), h.xe.data(), h.f.data(), m.rl.has_sj, m.rl.split};
+}
+
 int l2r_gtftext_blocks(l2r_ctx *c, const l2r_gtx_blocks *b, int64_t *n_lines, int64_t *n_bytes)
 {
     if (!c || !n_lines || !n_bytes) return fail(GTX_E_ARG, "[l2r_gtftext_blocks] null argument");
     GtxState &m = c->gtx;
-    m.have_blocks = false; m.out.have = false;
+    m.have_blocks = false; m.out.have = false; m.rl.active = false;
     for (int k = 0; k < GXS_N; ++k) if (k != GXS_ROUTE) m.stats[k] = 0;
     m.stats[GXS_GUARD] = 1;
     if (!m.have_rows) return fail(GTX_E_ARG, "[l2r_gtftext_blocks] no l2r_gtftext_rows in front");
@@ -3184,7 +3232,8 @@ int l2r_gtftext_lines(l2r_ctx *c, int64_t first, int64_t max_blocks, int64_t max
     GtxState &m = c->gtx;
     m.out.reset();
     *n_taken = 0; *n_bytes = 0;
-    if (!m.have_blocks) return fail(GTX_E_ARG, "[l2r_gtftext_lines] no l2r_gtftext_blocks in front, or it failed");
+    if (!m.have_blocks) return fail(GTX_E_ARG, "[l2r_gtftext_lines] no l2r_gtftext_blocks or l2r_gtftext_list in front, or it failed");
+    const bool list = m.rl.active;                      // the blocks of l2r_gtftext_list: the row source of l2r_readlist.hip.h
     int64_t take = 0, sum = 0;
     {   std::string msg;
         if (gtx_cut(m.h_len.data(), m.m, first, max_blocks, max_bytes, &take, &sum, msg)) return fail(GTX_E_ARG, "%s", msg.c_str()); }
@@ -3195,14 +3244,16 @@ int l2r_gtftext_lines(l2r_ctx *c, int64_t first, int64_t max_blocks, int64_t max
         gtx_host_view(m, hr, cx, hb);
         std::string msg;
         int64_t lines = 0;
-        if (gtx_text_host(&m.prm, &hr, cx, &hb, first, take, m.out.host_text, &lines, msg)) { m.out.host_text.clear(); return fail(-1, "%s", msg.c_str()); }
+        if (list ? rl_text_host(&m.prm, &m.rl.anno, rl_host_view(m), m.rl.h.sel, first, take, m.out.host_text, &lines, msg)
+                 : gtx_text_host(&m.prm, &hr, cx, &hb, first, take, m.out.host_text, &lines, msg)) { m.out.host_text.clear(); return fail(-1, "%s", msg.c_str()); }
         if (m.out.host_text.size() != B) return fail(-5, "[l2r_gtftext_lines] %zu bytes of text, measured %zu", m.out.host_text.size(), B);
         m.out.take_host();
         m.stats[GXS_LINES] = (double)lines; m.stats[GXS_BYTES] = (double)B; m.stats[GXS_BATCHES] += 1;
         *n_taken = take; *n_bytes = sum;
         return 0;
     }
-    if (m.run_chains && c->n_reads != m.n) return fail(GTX_E_ARG, "[l2r_gtftext_lines] the rows stand for a run of %lld reads, the context now holds %lld", (long long)m.n, (long long)c->n_reads);
+    if (!list && m.run_chains && c->n_reads != m.n) return fail(GTX_E_ARG, "[l2r_gtftext_lines] the rows stand for a run of %lld reads, the context now holds %lld", (long long)m.n, (long long)c->n_reads);
+    if (list && m.rl.run_res && (c->n_reads != m.rl.n || !c->ran)) return fail(GTX_E_ARG, "[l2r_gtftext_lines] the reads stand for a run of %lld reads, the context now holds %lld", (long long)m.rl.n, (long long)c->n_reads);
     HIP_TRY(hipSetDevice(c->device));
     int rc;
     if ((rc = m.clk.begin(env_on("L2R_GTX_TIMING"), c->check_stages))) return rc;
@@ -3214,8 +3265,10 @@ int l2r_gtftext_lines(l2r_ctx *c, int64_t first, int64_t max_blocks, int64_t max
     HIP_TRY(m.out.arm_guard(c, B));
     const unsigned n_tiles = (unsigned)((K + GTX_TILE - 1) / GTX_TILE);
     const GtxIn in = gtx_in(c, m);
+    const RlIn lin = rl_in(c, m);
     if ((rc = m.clk.launch(c, &m.stats[GXS_K_WRITE], [&] {
-            hipLaunchKernelGGL(k_gtx_write, dim3(n_tiles), dim3(GTX_THREADS), 0, c->stream, in, first, take, (const uint32_t *)m.off.p, (const uint32_t *)m.fix.p, text8, m.word.p);
+            if (list) hipLaunchKernelGGL(k_rl_write, dim3(n_tiles), dim3(GTX_THREADS), 0, c->stream, lin, first, take, (const uint32_t *)m.off.p, (const uint32_t *)m.fix.p, (const uint32_t *)m.rl.hfix.p, text8, m.word.p);
+            else hipLaunchKernelGGL(k_gtx_write, dim3(n_tiles), dim3(GTX_THREADS), 0, c->stream, in, first, take, (const uint32_t *)m.off.p, (const uint32_t *)m.fix.p, text8, m.word.p);
         }))) { (void)hipStreamSynchronize(c->stream); return rc; }
     uint32_t w[GTXC_TOTAL + 1] = {0};
     HIP_TRY(hipMemcpyAsync(w, m.word.p, sizeof w, hipMemcpyDeviceToHost, c->stream));
@@ -3239,6 +3292,190 @@ int l2r_gtftext_out(l2r_ctx *c, uint8_t *text, int64_t cap)
 }
 
 int l2r_gtftext_stats(l2r_ctx *c, double *out, int n) { return stats_out(c ? c->gtx.stats : nullptr, GXS_N, out, n, "l2r_gtftext_stats"); }
+
+// ---------------------------------------------------------------------------------------------- the read lists of update-gtf -a / -k / -v / -u
+int l2r_gtftext_anno(l2r_ctx *c, const l2r_gtx_anno *a)
+{
+    if (!c) return fail(GTX_E_ARG, "[l2r_gtftext_anno] null argument");
+    GtxState &m = c->gtx;
+    GtxState::Lists &l = m.rl;
+    l.have_anno = false; l.have_reads = false; l.active = false; m.have_blocks = false; m.out.have = false;
+    if (!m.begun) return fail(GTX_E_ARG, "[l2r_gtftext_anno] no l2r_gtftext_begin in front");
+    if (m.prm.form != L2R_GTX_READ) return fail(GTX_E_ARG, "[l2r_gtftext_anno] the read lists are blocks of form READ, l2r_gtftext_begin had form %d", m.prm.form);
+    {   std::string msg;
+        if (rl_check_anno(a, msg)) return fail(GTX_E_ARG, "%s", msg.c_str()); }
+    const size_t T = (size_t)a->n_tx, A = (size_t)a->anno_names_len;
+    l.h_anno.assign(A + 1, 0);
+    if (A) memcpy(l.h_anno.data(), a->anno_names, A);
+    l.h_gid.assign(T + 1, 0); l.h_gname.assign(T + 1, 0);
+    if (T) { memcpy(l.h_gid.data(), a->tx_gid, T * 4); memcpy(l.h_gname.data(), a->tx_gname, T * 4); }
+    l.anno = l2r_gtx_anno{a->n_tx, a->anno_names_len, l.h_anno.data(), l.h_gid.data(), l.h_gname.data()};
+    HIP_TRY(hipSetDevice(c->device));
+    int rc;
+    if ((rc = put_dev(c, l.d_anno, l.h_anno)) || (rc = put_dev(c, l.d_gid, l.h_gid)) || (rc = put_dev(c, l.d_gname, l.h_gname))) { (void)hipStreamSynchronize(c->stream); return rc; }
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    l.have_anno = true;
+    return 0;
+}
+
+int l2r_gtftext_reads(l2r_ctx *c, const l2r_gtx_reads *r)
+{
+    if (!c) return fail(GTX_E_ARG, "[l2r_gtftext_reads] null argument");
+    GtxState &m = c->gtx;
+    GtxState::Lists &l = m.rl;
+    l.have_reads = false; l.active = false; m.have_rows = false; m.have_blocks = false; m.out.have = false;
+    if (!l.have_anno) return fail(GTX_E_ARG, "[l2r_gtftext_reads] no l2r_gtftext_anno in front");
+    {   std::string msg;
+        if (rl_check_reads(r, msg)) return fail(GTX_E_ARG, "%s", msg.c_str()); }
+    const char *route = getenv("L2R_GTX_ROUTE");
+    m.on_host = route && strcmp(route, "host") == 0;
+    m.stats[GXS_ROUTE] = m.on_host ? 1 : 0;
+    const size_t N = (size_t)r->n, NL = (size_t)r->names_len;
+    l.n = r->n; l.names_len = r->names_len; l.run_res = !r->res; l.has_sj = r->has_sj != 0; l.split = r->split != 0;
+    l.exons_per_read = 0;
+    HIP_TRY(hipSetDevice(c->device));
+    int rc = 0;
+    if (l.run_res) {
+        if (!c->ran) return fail(GTX_E_ARG, "[l2r_gtftext_reads] no completed run on this context");
+        if ((rc = fetch_totals(c))) return rc;
+        if (!(c->want & L2R_WANT_RESULTS)) return fail(GTX_E_ARG, "[l2r_gtftext_reads] the last run kept no results (l2r_set_outputs without L2R_WANT_RESULTS)");
+        if (r->n != c->n_reads) return fail(GTX_E_ARG, "[l2r_gtftext_reads] %lld reads, the last run had %lld reads", (long long)r->n, (long long)c->n_reads);
+        if (N) l.exons_per_read = (double)c->h_totals[0] / (double)N;
+    } else if (N) l.exons_per_read = (double)r->res->n_exons / (double)N;
+    const l2r_result *s = r->res;
+    const uint32_t *tid_name = r->tid_name ? r->tid_name : r->qname;
+    if (m.on_host) {
+        GtxState::Lists::Host &h = l.h;
+        h.tid.assign(r->tid, r->tid + N); h.qname.assign(r->qname, r->qname + N); h.tid_name.assign(tid_name, tid_name + N); h.names.assign(r->names, r->names + NL);
+        const size_t X = l.run_res ? (size_t)c->h_totals[0] : (size_t)s->n_exons;
+        h.ex_off.assign(N + 1, 0); h.info.assign(N ? N : 1, 0u); h.ref_tx.assign(N ? N : 1, 0); h.xs.assign(X ? X : 1, 0); h.xe.assign(X ? X : 1, 0); h.f.assign(X ? X : 1, 0);
+        if (l.run_res) {
+            l2r_result res{(int64_t)N, (int64_t)X, (int64_t)X, h.ex_off.data(), h.xs.data(), h.xe.data(), h.f.data(), h.info.data(), h.ref_tx.data()};
+            if (N && (rc = l2r_download(c, &res))) return rc;
+        } else if (N) {
+            memcpy(h.ex_off.data(), s->ex_off, (N + 1) * 8); memcpy(h.info.data(), s->info, N * 4); memcpy(h.ref_tx.data(), s->ref_tx, N * 4);
+            if (X) { memcpy(h.xs.data(), s->ex_start, X * 4); memcpy(h.xe.data(), s->ex_end, X * 4); memcpy(h.f.data(), s->ex_flag, X); }
+        }
+        l.have_reads = true;
+        return 0;
+    }
+    std::vector<uint32_t> off32;
+    if ((rc = to_dev(c, l.tid, r->tid, N)) || (rc = to_dev(c, l.qname, r->qname, N)) || (rc = to_dev(c, l.names, r->names, NL))) {}
+    l.tid_name_p = l.qname.p;
+    if (!rc && r->tid_name && r->tid_name != r->qname) { rc = to_dev(c, l.tid_name, r->tid_name, N); l.tid_name_p = l.tid_name.p; }
+    if (!rc && !l.run_res) {
+        const size_t X = (size_t)s->n_exons;
+        off32.resize(N);
+        for (size_t i = 0; i < N; ++i) off32[i] = (uint32_t)s->ex_off[i];
+        if ((rc = put_dev(c, l.ex_off, off32)) || (rc = to_dev(c, l.info, (const uint32_t *)s->info, N)) || (rc = to_dev(c, l.ref_tx, (const int32_t *)s->ref_tx, N)) ||
+            (rc = to_dev(c, l.xs, (const int32_t *)s->ex_start, X)) || (rc = to_dev(c, l.xe, (const int32_t *)s->ex_end, X)) || (rc = to_dev(c, l.f, (const uint8_t *)s->ex_flag, X))) {}
+    }
+    const hipError_t sync = hipStreamSynchronize(c->stream);           // (the columns are the caller's)
+    if (rc) return rc;
+    if (sync != hipSuccess) return fail(-2, "[l2r_gtftext_reads] %s", hipGetErrorString(sync));
+    l.have_reads = true;
+    return 0;
+}
+
+int l2r_gtftext_list(l2r_ctx *c, int list, int64_t *n_blocks, int64_t *n_lines, int64_t *n_bytes)
+{
+    if (!c || !n_blocks || !n_lines || !n_bytes) return fail(GTX_E_ARG, "[l2r_gtftext_list] null argument");
+    GtxState &m = c->gtx;
+    GtxState::Lists &l = m.rl;
+    m.have_blocks = false; m.out.have = false; l.active = false;
+    for (int k = 0; k < GXS_N; ++k) if (k != GXS_ROUTE) m.stats[k] = 0;
+    m.stats[GXS_GUARD] = 1;
+    *n_blocks = 0; *n_lines = 0; *n_bytes = 0;
+    if (!l.have_reads) return fail(GTX_E_ARG, "[l2r_gtftext_list] no l2r_gtftext_reads in front");
+    {   std::string msg;
+        if (rl_check_list(list, msg)) return fail(GTX_E_ARG, "%s", msg.c_str()); }
+    l.list = list; l.n_pieces = 0;
+    m.m = 0; m.h_len.clear();
+    const size_t N = (size_t)l.n;
+    uint64_t lines = 0, bytes = 0;
+    if (m.on_host) {
+        const RlReads hr = rl_host_view(m);
+        rl_select(hr, list, l.h.sel);
+        const size_t M = (size_t)l.h.sel.m();
+        m.m = (int64_t)M; l.n_pieces = l.h.sel.n_pieces;
+        m.h_len.assign(M, 0u);
+        for (size_t q = 0; q < M; ++q) {
+            uint64_t by = 0, nl = 0;
+            const int kind = rl_block_bytes(&m.prm, &l.anno, hr, l.h.sel, (int64_t)q, &by, &nl);
+            if (kind) { std::string msg; rl_block_fail(msg, (int64_t)q, kind); return fail(-1, "%s", msg.c_str()); }
+            m.h_len[q] = (uint32_t)by; lines += nl; bytes += by;
+        }
+    } else if (N) {
+        if (l.run_res && (c->n_reads != l.n || !c->ran)) return fail(GTX_E_ARG, "[l2r_gtftext_list] the reads stand for a run of %lld reads, the context now holds %lld", (long long)l.n, (long long)c->n_reads);
+        HIP_TRY(hipSetDevice(c->device));
+        int rc;
+        if ((rc = m.clk.begin(env_on("L2R_GTX_TIMING"), c->check_stages))) return rc;
+        if (l.cnt.ensure(N + 1) || l.word.ensure(2) || m.word64.ensure(2) || m.word.ensure(GTXC_TOTAL + 1)) return -2;
+        HIP_TRY(hipMemsetAsync(l.word.p, 0, 2 * sizeof(uint32_t), c->stream));
+        RlIn in = rl_in(c, m);
+        const dim3 per_read((unsigned)((N + 255) / 256));
+        if ((rc = m.clk.launch(c, &m.stats[GXS_K_SELECT], [&] {
+                hipLaunchKernelGGL(k_rl_count, per_read, dim3(256), 0, c->stream, in, l.cnt.p, l.word.p + 1);
+                scan_u32(c, l.cnt.p, (int64_t)N, l.word.p);
+            }))) { (void)hipStreamSynchronize(c->stream); return rc; }
+        uint32_t w32[2] = {0, 0};
+        if ((rc = download_all(c, 0, {{w32, l.word.p, sizeof w32}}, "l2r_gtftext_list"))) return rc;
+        const size_t M = (size_t)w32[0];
+        if ((uint64_t)w32[1] > (uint64_t)M) return fail(-5, "[l2r_gtftext_list] %u piece blocks of %zu blocks", w32[1], M);
+        m.m = (int64_t)M; l.n_pieces = (int64_t)w32[1];
+        m.h_len.assign(M, 0u);
+        if (M) {
+            if (l.b_read.ensure(M) || l.b_first.ensure(M) || l.b_count.ensure(M) || l.b_piece.ensure(M) || m.len.ensure(M) || m.fix.ensure(M) || l.hfix.ensure(M)) return -2;
+            in = rl_in(c, m);
+            if ((rc = m.clk.launch(c, &m.stats[GXS_K_SELECT], [&] {
+                    hipLaunchKernelGGL(k_rl_take, per_read, dim3(256), 0, c->stream, in, (const uint32_t *)l.cnt.p, l.b_read.p, l.b_first.p, l.b_count.p, l.b_piece.p);
+                }))) { (void)hipStreamSynchronize(c->stream); return rc; }
+            const bool wave = wave_form(l.exons_per_read, "L2R_GTX_WAVE");     // (exons per read: the lists are not looked at)
+            m.stats[GXS_WAVE] = wave ? 1 : 0;
+            HIP_TRY(hipMemsetAsync(m.word64.p, 0xff, sizeof(unsigned long long), c->stream));
+            HIP_TRY(hipMemsetAsync(m.word64.p + 1, 0, sizeof(unsigned long long), c->stream));
+            const RlMeasure meas{m.len.p, m.fix.p, l.hfix.p, m.word64.p, m.word64.p + 1};
+            rc = m.clk.launch(c, &m.stats[GXS_K_MEASURE], [&] {
+                const dim3 grid((unsigned)(((wave ? M * 64 : M) + 255) / 256));
+                if (wave) hipLaunchKernelGGL(k_rl_measure<true>, grid, dim3(256), 0, c->stream, in, meas);
+                else hipLaunchKernelGGL(k_rl_measure<false>, grid, dim3(256), 0, c->stream, in, meas);
+            });
+            unsigned long long w[2] = {0, 0};
+            if ((rc = download_all(c, rc, {{w, m.word64.p, sizeof w}, {m.h_len.data(), m.len.p, M * 4}}, "l2r_gtftext_list"))) return rc;
+            if (w[0] != ~0ull) {
+                const unsigned long long q = w[0] >> 4; const int kind = (int)(w[0] & 15ull);
+                if (q >= M || kind <= RL_OK || kind >= RL_E_N) return fail(-2, "[l2r_gtftext_list] the device names block %llu of %zu, kind %d", q, M, kind);
+                std::string msg; rl_block_fail(msg, (int64_t)q, kind);
+                return fail(-1, "%s", msg.c_str());
+            }
+            lines = w[1];
+            for (size_t q = 0; q < M; ++q) bytes += m.h_len[q];
+        }
+    }
+    m.stats[GXS_BLOCKS] = (double)m.m; m.stats[GXS_PIECES] = (double)l.n_pieces;
+    l.active = true; m.have_blocks = true;
+    *n_blocks = m.m; *n_lines = (int64_t)lines; *n_bytes = (int64_t)bytes;
+    return 0;
+}
+
+int l2r_gtftext_list_out(l2r_ctx *c, int32_t *read, int32_t *first, int32_t *count, int32_t *piece)
+{
+    if (!c) return fail(GTX_E_ARG, "[l2r_gtftext_list_out] null argument");
+    GtxState &m = c->gtx;
+    const GtxState::Lists &l = m.rl;
+    if (!l.active || !m.have_blocks) return fail(GTX_E_ARG, "[l2r_gtftext_list_out] no selection: the last l2r_gtftext_list failed, or none was made");
+    const size_t M = (size_t)m.m;
+    if (!M) return 0;
+    if (m.on_host) {
+        const RlSel &s = l.h.sel;
+        if (read) memcpy(read, s.read.data(), M * 4); if (first) memcpy(first, s.first.data(), M * 4);
+        if (count) memcpy(count, s.count.data(), M * 4); if (piece) memcpy(piece, s.piece.data(), M * 4);
+        return 0;
+    }
+    HIP_TRY(hipSetDevice(c->device));
+    return download_all(c, 0, {{read, l.b_read.p, read ? M * 4 : 0}, {first, l.b_first.p, first ? M * 4 : 0}, {count, l.b_count.p, count ? M * 4 : 0},
+                               {piece, l.b_piece.p, piece ? M * 4 : 0}}, "l2r_gtftext_list_out");
+}
 
 // ---------------------------------------------------------------------------------------------- the detail table of update-gtf -A
 // slots of l2r_detail_stats

@@ -750,12 +750,89 @@ static void early_engine_drop(void)
  * L2R_DETAIL_TEXT_MAX bytes (default 1 GiB) -- behind the column line.  L2R_DETAIL_ROUTE=host: the engine's host routine.  A shard with a
  * read outside the engine's domain (-1 from l2r_detail_rows: nothing of the shard has been written) goes through the tail's own writer
  * (h_detail_rows), shard by shard: the file's bytes are the same.  Any other failure is fatal.  L2R_TIMING=1: one line on stderr. */
+/* Where the text of the detail table and of the read lists goes: two buffers per file -- l2r_*_out fills one while a writer thread
+ * fwrite()s the other, so batch k is written while batch k + 1 is composed.  text_sink_room: the buffer to fill, with room for `bytes`;
+ * text_sink_put: it goes to the writer (the one before it is waited for first: the bytes keep their order); text_sink_wait: in front of
+ * anything else that writes to the file, and of closing it. */
 typedef struct {
-    FILE *fp; int no_header;
+    FILE *fp; const char *what;
+    uint8_t *buf[2]; int64_t cap[2], pending;
+    int cur, busy, failed;
+    pthread_t th;
+} text_sink;
+
+static void *text_sink_main(void *arg)
+{
+    text_sink *s = (text_sink *)arg;
+    if (s->pending && fwrite(s->buf[s->cur ^ 1], 1, (size_t)s->pending, s->fp) != (size_t)s->pending) s->failed = 1;
+    return NULL;
+}
+static void text_sink_wait(const char *who, text_sink *s)
+{
+    if (s->busy) { pthread_join(s->th, NULL); s->busy = 0; }
+    if (s->failed) h_fatal(who, "Error in writing %s\n", s->what);
+}
+static uint8_t *text_sink_room(text_sink *s, int64_t bytes)
+{
+    const int k = s->cur;                                   /* (the writer has the other one) */
+    if (bytes > s->cap[k]) { free(s->buf[k]); s->cap[k] = bytes + bytes / 4 + 64; s->buf[k] = (uint8_t *)h_malloc((size_t)s->cap[k]); }
+    return s->buf[k];
+}
+static void text_sink_put(const char *who, text_sink *s, int64_t bytes)
+{
+    text_sink_wait(who, s);
+    s->pending = bytes; s->cur ^= 1;
+    if (pthread_create(&s->th, NULL, text_sink_main, s) == 0) s->busy = 1;
+    else { (void)text_sink_main(s); text_sink_wait(who, s); }      /* (no thread: written here) */
+}
+static void text_sink_done(const char *who, text_sink *s)
+{
+    text_sink_wait(who, s);
+    free(s->buf[0]); free(s->buf[1]);
+    s->buf[0] = s->buf[1] = NULL; s->cap[0] = s->cap[1] = 0;
+}
+
+/* The files the engine stage has written are closed beside the tail, each on a thread of its own (closing a file of gigabytes can wait
+ * for its dirty pages): files_close_start takes them over, files_close_join waits and reports a failed close. */
+typedef struct { FILE *fp[5]; pthread_t th[5]; int started[5], n; } file_closer;
+static void *file_close_main(void *arg) { return fclose((FILE *)arg) ? arg : NULL; }
+static void files_close_start(file_closer *c, FILE **fp)
+{
+    if (!*fp) return;
+    const int k = c->n++;
+    c->fp[k] = *fp; *fp = NULL;
+    c->started[k] = pthread_create(&c->th[k], NULL, file_close_main, c->fp[k]) == 0;
+}
+static void files_close_join(const char *who, file_closer *c)
+{
+    int bad = 0;
+    for (int k = 0; k < c->n; ++k) {
+        void *r = NULL;
+        if (c->started[k]) pthread_join(c->th[k], &r); else r = file_close_main(c->fp[k]);
+        bad |= r != NULL;
+    }
+    c->n = 0;
+    if (bad) h_fatal(who, "Error in closing an output file\n");
+}
+
+/* the reference names of the command as l2r_bed_params wants them */
+static void ref_table(const h_chroms *chr, int64_t **ref_off, uint8_t **ref_names)
+{
+    const int n_ref = chr->n;
+    int64_t *off = (int64_t *)h_malloc((size_t)(n_ref + 1) * 8);
+    off[0] = 0;
+    for (int t = 0; t < n_ref; ++t) off[t + 1] = off[t] + (int64_t)strlen(chr->name[t]);
+    uint8_t *names = (uint8_t *)h_malloc((size_t)off[n_ref] + 1);
+    for (int t = 0; t < n_ref; ++t) memcpy(names + off[t], chr->name[t], (size_t)(off[t + 1] - off[t]));
+    *ref_off = off; *ref_names = names;
+}
+
+typedef struct {
+    text_sink out; int no_header;
     const h_chroms *chr; const h_reads *reads; const h_gtf *anno;
     int begun, engine_host;
     int64_t rows, own_rows, bytes, batches;
-    int64_t *ref_off; uint8_t *ref_names, *text; int64_t text_cap;
+    int64_t *ref_off; uint8_t *ref_names;
 } detail_sink;
 
 static int64_t detail_env_count(const char *name, int64_t dflt)
@@ -770,16 +847,12 @@ static int64_t detail_env_count(const char *name, int64_t dflt)
 static void detail_shard(l2r_ctx *ctx, const char *who, detail_sink *d, int64_t lo, int64_t hi, const h_result *res)
 {
     if (!d->begun) {
-        const int n_ref = d->chr->n;
-        d->ref_off = (int64_t *)h_malloc((size_t)(n_ref + 1) * 8);
-        d->ref_off[0] = 0;
-        for (int t = 0; t < n_ref; ++t) d->ref_off[t + 1] = d->ref_off[t] + (int64_t)strlen(d->chr->name[t]);
-        d->ref_names = (uint8_t *)h_malloc((size_t)d->ref_off[n_ref] + 1);
-        for (int t = 0; t < n_ref; ++t) memcpy(d->ref_names + d->ref_off[t], d->chr->name[t], (size_t)(d->ref_off[t + 1] - d->ref_off[t]));
-        const l2r_detail_params prm = { n_ref, d->ref_off, d->ref_names, d->anno->n_tx, (int64_t)d->anno->names.len, (const uint8_t *)d->anno->names.buf,
+        ref_table(d->chr, &d->ref_off, &d->ref_names);
+        const l2r_detail_params prm = { d->chr->n, d->ref_off, d->ref_names, d->anno->n_tx, (int64_t)d->anno->names.len, (const uint8_t *)d->anno->names.buf,
                                         d->anno->gid, d->anno->gname };
         if (l2r_detail_begin(ctx, &prm)) engine_fail(who);
-        if (!d->no_header) h_detail_header(d->fp);
+        d->out.what = "the detail table";
+        if (!d->no_header) h_detail_header(d->out.fp);
         d->begun = 1;
     }
     const int64_t n = hi - lo;
@@ -788,7 +861,8 @@ static void detail_shard(l2r_ctx *ctx, const char *who, detail_sink *d, int64_t 
     int64_t total = 0;
     const int rc = l2r_detail_rows(ctx, &rows, &total);
     if (rc == -1) {                                         /* (nothing of the shard has been written) */
-        h_detail_rows(d->fp, d->chr, d->reads, d->anno, res, lo, hi);
+        text_sink_wait(who, &d->out);
+        h_detail_rows(d->out.fp, d->chr, d->reads, d->anno, res, lo, hi);
         d->own_rows += n;
         return;
     }
@@ -797,10 +871,9 @@ static void detail_shard(l2r_ctx *ctx, const char *who, detail_sink *d, int64_t 
     for (int64_t first = 0; first < n;) {
         int64_t take = 0, bytes = 0;
         if (l2r_detail_lines(ctx, first, max_rows, max_bytes, &take, &bytes) || take < 1) engine_fail(who);
-        if (bytes > d->text_cap) { free(d->text); d->text_cap = bytes + bytes / 4 + 64; d->text = (uint8_t *)h_malloc((size_t)d->text_cap); }
         if (bytes) {
-            if (l2r_detail_out(ctx, d->text, d->text_cap)) engine_fail(who);
-            if (fwrite(d->text, 1, (size_t)bytes, d->fp) != (size_t)bytes) h_fatal(who, "Error in writing the detail table\n");
+            if (l2r_detail_out(ctx, text_sink_room(&d->out, bytes), bytes)) engine_fail(who);
+            text_sink_put(who, &d->out, bytes);
         }
         ++d->batches; d->bytes += bytes; first += take;
     }
@@ -816,12 +889,86 @@ static void detail_done(const char *who, detail_sink *d)
     if (tm && atoi(tm) != 0)
         fprintf(stderr, "[%s] detail text: route %s, %lld rows, %lld bytes, %lld batches\n", who,
                 d->own_rows ? (d->rows ? "mixed" : "off") : d->engine_host ? "host" : "device", (long long)d->rows, (long long)d->bytes, (long long)d->batches);
-    free(d->ref_off); free(d->ref_names); free(d->text);
-    d->ref_off = NULL; d->ref_names = NULL; d->text = NULL;
+    text_sink_done(who, &d->out);
+    free(d->ref_off); free(d->ref_names);
+    d->ref_off = NULL; d->ref_names = NULL;
+}
+
+/* The read lists (-a / -k / -v / -u) through the engine (l2r_gtftext_anno / _reads / _list, include/lr2rmats_hip.h): for every engine
+ * shard the reads are given once while the shard's results still lie in HBM (res == NULL), and every requested list is selected on the
+ * device, composed and written batch by batch -- L2R_GTX_BATCH blocks (default 1 Mi) and L2R_GTX_TEXT_MAX bytes (default 256 MiB here).
+ * L2R_GTX_ROUTE=host: the engine's host routine.  A list of a shard with a block outside the engine's domain (-1 from l2r_gtftext_list:
+ * nothing of it has been written) goes through the tail's own writer (h_list_rows): the file's bytes are the same.  Any other failure is
+ * fatal.  L2R_TIMING=1: one line on stderr. */
+typedef struct {
+    text_sink out[4];                                       /* by L2R_GTX_LIST_*; fp == NULL: not asked for */
+    const h_update_opts *o; const h_chroms *chr; const h_reads *reads; const h_gtf *anno; int64_t n_sj;
+    int begun, engine_host;
+    int64_t blocks[4], pieces, by_engine, by_tail, bytes, batches;
+    int64_t *ref_off; uint8_t *ref_names;
+} lists_sink;
+
+static void lists_shard(l2r_ctx *ctx, const char *who, lists_sink *d, int64_t lo, int64_t hi, const h_result *res)
+{
+    static const char *const what[4] = {"the GTF of all reads", "the GTF of the known reads", "the GTF of the novel reads", "the GTF of the unrecognised reads"};
+    if (!d->begun) {
+        ref_table(d->chr, &d->ref_off, &d->ref_names);
+        const l2r_gtx_params prm = { d->chr->n, d->ref_off, d->ref_names, L2R_GTX_READ, (int32_t)strlen(d->o->source), (const uint8_t *)d->o->source };
+        const l2r_gtx_anno anno = { d->anno->n_tx, (int64_t)d->anno->names.len, (const uint8_t *)d->anno->names.buf, d->anno->gid, d->anno->gname };
+        if (l2r_gtftext_begin(ctx, &prm) || l2r_gtftext_anno(ctx, &anno)) engine_fail(who);
+        for (int k = 0; k < 4; ++k) d->out[k].what = what[k];
+        d->begun = 1;
+    }
+    const int64_t n = hi - lo;
+    if (n <= 0) return;
+    const l2r_gtx_reads rd = { n, d->reads->tid + lo, (int64_t)d->reads->names.len, (const uint8_t *)d->reads->names.buf, d->reads->qname + lo,
+                               d->reads->tid_name ? d->reads->tid_name + lo : NULL, NULL, d->n_sj > 0, d->o->prm.split_trans != 0 };
+    if (l2r_gtftext_reads(ctx, &rd)) engine_fail(who);
+    /* (a quarter of the GTF text's default batch: a file has two buffers of a batch's bytes, and there are four files) */
+    const int64_t max_blocks = detail_env_count("L2R_GTX_BATCH", (int64_t)1 << 20), max_bytes = detail_env_count("L2R_GTX_TEXT_MAX", (int64_t)1 << 28);
+    for (int list = 0; list < 4; ++list) {
+        text_sink *s = &d->out[list];
+        if (!s->fp) continue;
+        int64_t m = 0, n_lines = 0, total = 0;
+        const int rc = l2r_gtftext_list(ctx, list, &m, &n_lines, &total);
+        if (rc == -1) {                                     /* (nothing of this list of the shard has been written) */
+            text_sink_wait(who, s);
+            h_list_rows(s->fp, d->o, d->chr, d->reads, d->anno, res, d->n_sj, list, lo, hi);
+            ++d->by_tail;
+            continue;
+        }
+        if (rc) engine_fail(who);
+        for (int64_t first = 0; first < m;) {
+            int64_t take = 0, bytes = 0;
+            if (l2r_gtftext_lines(ctx, first, max_blocks, max_bytes, &take, &bytes) || take < 1) engine_fail(who);
+            if (bytes) {
+                if (l2r_gtftext_out(ctx, text_sink_room(s, bytes), bytes)) engine_fail(who);
+                text_sink_put(who, s, bytes);
+            }
+            ++d->batches; d->bytes += bytes; first += take;
+        }
+        double st[14] = {0};
+        (void)l2r_gtftext_stats(ctx, st, 14);
+        d->engine_host = st[6] != 0;
+        d->blocks[list] += m; d->pieces += (int64_t)st[13]; ++d->by_engine;
+    }
+}
+
+static void lists_done(const char *who, lists_sink *d)
+{
+    const char *tm = getenv("L2R_TIMING");
+    if (tm && atoi(tm) != 0)
+        fprintf(stderr, "[%s] read lists: route %s, all %lld, known %lld, novel %lld (%lld pieces), unrecognised %lld blocks, %lld bytes, %lld batches\n", who,
+                d->by_tail ? (d->by_engine ? "mixed" : "off") : d->engine_host ? "host" : "device", (long long)d->blocks[0], (long long)d->blocks[1],
+                (long long)d->blocks[2], (long long)d->pieces, (long long)d->blocks[3], (long long)d->bytes, (long long)d->batches);
+    for (int k = 0; k < 4; ++k) text_sink_done(who, &d->out[k]);
+    free(d->ref_off); free(d->ref_names);
+    d->ref_off = NULL; d->ref_names = NULL;
 }
 
 static void run_engine(const char *who, const l2r_params *prm, const l2r_annotation *a, const l2r_junctions *s,
-                       const l2r_reads *r, h_result *out, int64_t **acc_read, detail_sink *detail /* NULL: none; only with acc_read == NULL */)
+                       const l2r_reads *r, h_result *out, int64_t **acc_read, detail_sink *detail /* NULL: none; only with acc_read == NULL */,
+                       lists_sink *lists /* likewise */)
 {
     int anno_set = 0;
     l2r_ctx *ctx = engine_take(who, &anno_set);
@@ -863,6 +1010,7 @@ static void run_engine(const char *who, const l2r_params *prm, const l2r_annotat
         }
         if (exons) for (int64_t k = 0; k <= add_rows; ++k) out->ex_off[rows + k] += exons;          /* shard-local -> global offsets */
         if (detail && !acc_read) detail_shard(ctx, who, detail, lo, hi, out);
+        if (lists && !acc_read) lists_shard(ctx, who, lists, lo, hi, out);
         rows += add_rows; exons += add_ex;
         lo = hi;
     } while (lo < r->n_reads);
@@ -875,8 +1023,10 @@ static void run_engine(const char *who, const l2r_params *prm, const l2r_annotat
         if (!detail->begun) detail_shard(ctx, who, detail, 0, 0, out);      /* (no record: the column line alone) */
         detail_done(who, detail);
     }
+    if (lists && !acc_read) lists_done(who, lists);
     h_stage_time("engine: upload, kernels, download");
     l2r_destroy(ctx);
+    if ((detail || lists) && !acc_read) h_stage_time("engine: context destroyed");
 }
 
 /* which outputs need every read (detail.txt, the all / known / unrecognised lists, summary.txt) -- without them only
@@ -887,6 +1037,19 @@ static int needs_all_reads(const h_job *j)
            j->out_path[2] || j->out_path[3] || j->out_path[4] || j->out_path[6] || j->out_path[7];
 }
 int h_job_needs_all_reads(const h_job *j) { return needs_all_reads(j); }
+
+/* tests: list `list` (L2R_GTX_LIST_*) of the reads [lo, hi) by the fall-back writer of lists_shard (h_list_rows), appended to `path` */
+int h_job_list_rows(h_job *j, const l2r_result *res, int list, int64_t lo, int64_t hi, const char *path)
+{
+    if (lo < 0 || hi < lo || hi > j->reads.n || res->n_reads != j->reads.n) return 1;
+    FILE *fp = fopen(path, "a");
+    if (!fp) return 1;
+    h_result hr;
+    hr.n = res->n_reads; hr.n_ex = res->n_exons; hr.ex_off = res->ex_off; hr.ex_start = res->ex_start; hr.ex_end = res->ex_end;
+    hr.ex_flag = res->ex_flag; hr.info = res->info; hr.ref_tx = res->ref_tx;
+    h_list_rows(fp, &j->o, &j->chr, &j->reads, &j->anno, &hr, j->sj.n, list, lo, hi);
+    return fclose(fp) ? 1 : 0;
+}
 
 /* The tail over the accepted reads alone: `res` = their rows in input order, read_idx[k] = input index of row k.  The
  * tail sees a view of the input records that keeps just them (routing, split, merge and the writers of the updated GTF /
@@ -1255,7 +1418,7 @@ static int update_gtf_multi(h_job *j, int n_gpus, int gathered)
                 off = (int64_t *)h_malloc((size_t)(hi - lo + 1) * 8);
                 for (int64_t i = 0; i <= hi - lo; ++i) off[i] = r.cig_off[lo + i] - r.cig_off[lo];
                 sub.cig_off = off; sub.first_read_index = lo;
-                run_engine("update_gtf", &prm, &a, &s, &sub, &out, NULL, NULL);
+                run_engine("update_gtf", &prm, &a, &s, &sub, &out, NULL, NULL, NULL);
             } else result_reserve(&out, 0, 0);
             l2r_result res = { out.n, out.n_ex, out.n_ex, out.ex_off, out.ex_start, out.ex_end, out.ex_flag, out.info, out.ref_tx };
             h_job_finish_part(j, lo, hi, &res, suffix, tmp_base, k == 0, cnt);
@@ -1388,16 +1551,29 @@ int h_cmd_update_gtf(int argc, char **argv)
         const char *dr = getenv("L2R_DETAIL_ROUTE");
         const int detail_off = dr && !strcmp(dr, "off");
         detail_sink sink; memset(&sink, 0, sizeof sink);
-        sink.fp = j->o.bam_detail; sink.no_header = j->o.no_detail_header; sink.chr = &j->chr; sink.reads = &j->reads; sink.anno = &j->anno;
+        sink.out.fp = j->o.bam_detail; sink.no_header = j->o.no_detail_header; sink.chr = &j->chr; sink.reads = &j->reads; sink.anno = &j->anno;
         const int by_engine = j->o.bam_detail && !detail_off;
-        run_engine("update_gtf", &prm, &a, &s, &r, &out, NULL, by_engine ? &sink : NULL);
-        if (by_engine) { fclose(j->o.bam_detail); j->o.bam_detail = NULL; }
+        /* the read lists likewise (lists_shard): the tail is given none of -a / -k / -v / -u; L2R_GTX_ROUTE=off: the tail's writers */
+        const char *lr = getenv("L2R_GTX_ROUTE");
+        FILE **list_fp[4] = {&j->o.bam_gtf, &j->o.known_gtf, &j->o.novel_gtf, &j->o.unrecog_gtf};      /* by L2R_GTX_LIST_* */
+        const int any_list = j->o.bam_gtf || j->o.known_gtf || j->o.novel_gtf || j->o.unrecog_gtf;
+        const int lists_by_engine = any_list && !(lr && !strcmp(lr, "off"));
+        lists_sink lsink; memset(&lsink, 0, sizeof lsink);
+        for (int k = 0; k < 4; ++k) lsink.out[k].fp = *list_fp[k];
+        lsink.o = &j->o; lsink.chr = &j->chr; lsink.reads = &j->reads; lsink.anno = &j->anno; lsink.n_sj = s.n;
+        run_engine("update_gtf", &prm, &a, &s, &r, &out, NULL, by_engine ? &sink : NULL, lists_by_engine ? &lsink : NULL);
+        file_closer closer; memset(&closer, 0, sizeof closer);
+        if (by_engine) files_close_start(&closer, &j->o.bam_detail);
         else if (j->o.bam_detail) { const char *tm = getenv("L2R_TIMING"); if (tm && atoi(tm) != 0) fprintf(stderr, "[update_gtf] detail text: route off, 0 rows, 0 bytes, 0 batches\n"); }
+        if (lists_by_engine) { for (int k = 0; k < 4; ++k) files_close_start(&closer, list_fp[k]); }
+        else if (any_list) { const char *tm = getenv("L2R_TIMING"); if (tm && atoi(tm) != 0) fprintf(stderr, "[update_gtf] read lists: route off, all 0, known 0, novel 0 (0 pieces), unrecognised 0 blocks, 0 bytes, 0 batches\n"); }
         l2r_result res = { out.n, out.n_ex, out.n_ex, out.ex_off, out.ex_start, out.ex_end, out.ex_flag, out.info, out.ref_tx };
         rc = h_job_finish(j, &res);
+        files_close_join("update_gtf", &closer);
+        if (by_engine || lists_by_engine) h_stage_time("engine-written files closed");
     } else {
         int64_t *idx = NULL;
-        run_engine("update_gtf", &prm, &a, &s, &r, &out, &idx, NULL);
+        run_engine("update_gtf", &prm, &a, &s, &r, &out, &idx, NULL, NULL);
         l2r_result res = { out.n, out.n_ex, out.n_ex, out.ex_off, out.ex_start, out.ex_end, out.ex_flag, out.info, out.ref_tx };
         rc = h_job_finish_accepted(j, &res, idx);
         free(idx);
@@ -1426,7 +1602,7 @@ static void exons_only(const char *who, const char *fn, const l2r_params *prm, h
     int64_t zero_off = 0; a.tx_ex_off = &zero_off;
     l2r_junctions s; memset(&s, 0, sizeof s);
     l2r_reads r = { reads->n, reads->n_cig, reads->tid, reads->pos, reads->rev, reads->cig_off, reads->cig, 0, reads->cig_sum };
-    run_engine(who, prm, &a, &s, &r, out, NULL, NULL);
+    run_engine(who, prm, &a, &s, &r, out, NULL, NULL, NULL);
 }
 
 /* src/gtf.c:597-604 print_trans: gene_id + transcript_id only, exons always ascending */

@@ -252,6 +252,11 @@ void h_update_tail(const h_update_opts *o, const h_chroms *chr, const h_reads *r
  * rows [lo, hi) of `res` by the tail's own writer (print_detail) -- reads, offsets and rows are the whole input's. */
 void h_detail_header(FILE *fp);
 void h_detail_rows(FILE *fp, const h_chroms *chr, const h_reads *reads, const h_gtf *anno, const h_result *res, int64_t lo, int64_t hi);
+/* The read lists (-a / -k / -v / -u) outside the tail (cmds.c writes them shard by shard through the engine, l2r_gtftext_reads / _list):
+ * list `list` (L2R_GTX_LIST_*) of the reads [lo, hi) of `res` by the tail's own rule and writer -- reads, offsets and rows are the whole
+ * input's; o gives the source string and -s, n_sj the rows of the junction table. */
+void h_list_rows(FILE *fp, const h_update_opts *o, const h_chroms *chr, const h_reads *reads, const h_gtf *anno, const h_result *res, int64_t n_sj,
+                 int list, int64_t lo, int64_t hi);
 
 void h_write_summary_text(FILE *s, int anno_genes, int anno_tx, const int64_t *counters);
 
@@ -304,6 +309,8 @@ void   h_job_free(h_job *j);
 /* 1: an output of this run lists every read (detail.txt, -a / -k / -u, summary.txt); 0: the accepted reads are all the
  * tail needs (`update-gtf ... > new.gtf`, -v, -E) and h_job_finish_accepted() may be used */
 int    h_job_needs_all_reads(const h_job *j);
+/* tests: one read list of the reads [lo, hi) by h_list_rows, appended to `path`; res: the results of the whole input */
+int    h_job_list_rows(h_job *j, const l2r_result *res, int list, int64_t lo, int64_t hi, const char *path);
 /* finish with the rows of the accepted reads only (l2r_download_accepted, or the records gathered from several GPUs):
  * res->n_reads rows in input order, read_idx[k] = input index of row k */
 int    h_job_finish_accepted(h_job *j, const l2r_result *res, const int64_t *read_idx);

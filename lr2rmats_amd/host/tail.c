@@ -207,29 +207,61 @@ static void emit_gtf(obuf *o, const tail_ctx *c, const char *tchr, int start, in
     emit_gtf_named(o, c->o->source, tchr, start, end, rev, cov, gid, ni, gname, nm, xchr, ex_rev, xs, xe, n);
 }
 
+/* One member of a read list (include/lr2rmats_hip.h, the read lists): read `read` whole (piece < 0), or its piece over the exons [first, last] */
+static void emit_member(obuf *o, const tail_ctx *c, int64_t read, int first, int last, int piece)
+{
+    const h_result *r = c->res;
+    const int64_t off = r->ex_off[read];
+    const uint32_t info = r->info[read];
+    const int rev = (info & L2R_INFO_REV) != 0;
+    const int32_t ref = r->ref_tx[read];
+    const char *xc = c->chr->name[c->reads->tid[read]];
+    if (piece < 0) {
+        const int n = (int)L2R_INFO_NEXON(info);
+        emit_gtf(o, c, xc, r->ex_start[off], r->ex_end[off + n - 1], rev, 1, gene_id_of(c, ref), gene_name_of(c, ref), read, -1,
+                 xc, rev, r->ex_start + off, r->ex_end + off, n);
+    } else {
+        /* Q2: a split piece keeps tid = start = end = 0 and strand '+' on its transcript line */
+        emit_gtf(o, c, c->chr->name[0], 0, 0, 0, 1, gene_id_of(c, ref), gene_name_of(c, ref), read, piece,
+                 xc, rev, r->ex_start + off + first, r->ex_end + off + first, last - first + 1);
+    }
+}
+
 static void print_ref_list(FILE *fp, const tail_ctx *c, const l_list *L)
 {
     obuf o; ob_init(&o, fp);
-    const h_result *r = c->res;
-    for (int64_t i = 0; i < L->n; ++i) {
-        const l_ref *x = &L->v[i];
-        const int64_t off = r->ex_off[x->read];
-        const uint32_t info = r->info[x->read];
-        const int rev = (info & L2R_INFO_REV) != 0;
-        const int32_t ref = r->ref_tx[x->read];
-        const int64_t q = x->read;
-        const char *xc = c->chr->name[c->reads->tid[x->read]];
-        if (x->piece < 0) {
-            const int n = (int)L2R_INFO_NEXON(info);
-            emit_gtf(&o, c, xc, r->ex_start[off], r->ex_end[off + n - 1], rev, 1, gene_id_of(c, ref), gene_name_of(c, ref), q, -1,
-                     xc, rev, r->ex_start + off, r->ex_end + off, n);
-        } else {
-            /* Q2: a split piece keeps tid = start = end = 0 and strand '+' on its transcript line */
-            emit_gtf(&o, c, c->chr->name[0], 0, 0, 0, 1, gene_id_of(c, ref), gene_name_of(c, ref), q, x->piece,
-                     xc, rev, r->ex_start + off + x->first, r->ex_end + off + x->first, x->last - x->first + 1);
+    for (int64_t i = 0; i < L->n; ++i) emit_member(&o, c, L->v[i].read, L->v[i].first, L->v[i].last, L->v[i].piece);
+    ob_done(&o);
+}
+
+/* Where a read goes (src/update_gtf.c:939-964): nowhere (not FULL, Q3), the known list, the unrecognised list, or -- FULL, not KNOWN,
+ * with a known site -- the novel list: whole, as its split pieces, or dropped */
+enum { T_NONE = 0, T_KNOWN, T_UNRECOG, T_NOVEL_WHOLE, T_NOVEL_SPLIT, T_NOVEL_DROP };
+static int read_route(uint32_t info, int64_t n_sj, int split)
+{
+    if (!(info & L2R_INFO_FULL)) return T_NONE;
+    if (info & L2R_INFO_KNOWN) return T_KNOWN;
+    if (!(info & L2R_INFO_KNOWN_SITE)) return T_UNRECOG;
+    if (n_sj == 0 || (info & L2R_INFO_SJ_PASS)) return T_NOVEL_WHOLE;
+    return split ? T_NOVEL_SPLIT : T_NOVEL_DROP;
+}
+
+/* src/update_gtf.c:837-913 split_trans, as a cursor over the exon flags xf[0, n): cut at unreliable junctions; a piece has >= 2 exons
+ * and saw both a novel and a known junction.  *j = 0 in front of the first call; 1 and the piece [*first, *last], or 0 at the end. */
+static int next_piece(const uint8_t *xf, int n, int *j, int *first, int *last)
+{
+    int from = *j, seen_novel = 0, seen_known = 0;
+    for (int k = from; k < n; ++k) {
+        const int at_end = (k == n - 1);
+        if (!at_end) { if (xf[k] & L2R_EXF_NOVEL_JUNC) seen_novel = 1; else seen_known = 1; }
+        if (at_end || (xf[k] & L2R_EXF_UNREL_JUNC)) {
+            const int ok = seen_novel && seen_known && k - from >= 1;
+            if (ok) { *first = from; *last = k; *j = k + 1; return 1; }
+            from = k + 1; seen_novel = seen_known = 0;
         }
     }
-    ob_done(&o);
+    *j = n;
+    return 0;
 }
 
 static void print_merged(FILE *fp, const tail_ctx *c, const m_list *U)
@@ -248,16 +280,28 @@ static void print_all_reads(FILE *fp, const tail_ctx *c)
 {
     /* `-a`: bam_T after classification (strand possibly flipped, gene names set) */
     obuf o; ob_init(&o, fp);
-    const h_result *r = c->res;
-    for (int64_t i = 0; i < r->n; ++i) {
-        const int64_t off = r->ex_off[i];
-        const uint32_t info = r->info[i];
-        const int n = (int)L2R_INFO_NEXON(info), rev = (info & L2R_INFO_REV) != 0;
-        const char *xc = c->chr->name[c->reads->tid[i]];
-        emit_gtf(&o, c, xc, r->ex_start[off], r->ex_end[off + n - 1], rev, 1, gene_id_of(c, r->ref_tx[i]), gene_name_of(c, r->ref_tx[i]),
-                 i, -1, xc, rev, r->ex_start + off, r->ex_end + off, n);
-    }
+    for (int64_t i = 0; i < c->res->n; ++i) emit_member(&o, c, i, 0, 0, -1);
     ob_done(&o);
+}
+
+/* One read list (L2R_GTX_LIST_*) of the reads [lo, hi) outside the tail: cmds.c writes the lists shard by shard through the engine
+ * (l2r_gtftext_reads / _list) and comes here for a shard with a block outside the engine's domain.  The same rule as h_update_tail's. */
+void h_list_rows(FILE *fp, const h_update_opts *o, const h_chroms *chr, const h_reads *reads, const h_gtf *anno, const h_result *res, int64_t n_sj,
+                 int list, int64_t lo, int64_t hi)
+{
+    const tail_ctx c = { o, chr, reads, anno, res };
+    obuf ob; ob_init(&ob, fp);
+    for (int64_t i = lo; i < hi; ++i) {
+        const uint32_t info = res->info[i];
+        const int route = read_route(info, n_sj, o->prm.split_trans);
+        if (list == L2R_GTX_LIST_ALL || (list == L2R_GTX_LIST_KNOWN && route == T_KNOWN) || (list == L2R_GTX_LIST_UNRECOG && route == T_UNRECOG) ||
+            (list == L2R_GTX_LIST_NOVEL && route == T_NOVEL_WHOLE)) emit_member(&ob, &c, i, 0, 0, -1);
+        else if (list == L2R_GTX_LIST_NOVEL && route == T_NOVEL_SPLIT) {
+            int j = 0, first = 0, last = 0, k = 0;
+            while (next_piece(res->ex_flag + res->ex_off[i], (int)L2R_INFO_NEXON(info), &j, &first, &last)) emit_member(&ob, &c, i, first, last, k++);
+        }
+    }
+    ob_done(&ob);
 }
 
 static void index_list(obuf *o, const uint8_t *f, int n, uint8_t bit, int two_per_exon, int trailing_tab)
@@ -484,49 +528,41 @@ void h_update_tail(const h_update_opts *o, const h_chroms *chr, const h_reads *r
 
     for (int64_t i = 0; i < res->n; ++i) {                         /* src/update_gtf.c:939-964 */
         const uint32_t info = res->info[i];
-        if (!(info & L2R_INFO_FULL)) continue;                     /* Q3 */
-        if (info & L2R_INFO_KNOWN) { if (want_k) l_push(&K, i, 0, 0, -1); continue; }
-        if (!(info & L2R_INFO_KNOWN_SITE)) { if (want_x) l_push(&X, i, 0, 0, -1); continue; }
+        const int route = read_route(info, n_sj, p->split_trans);
+        if (route == T_NONE || route == T_NOVEL_DROP) continue;    /* Q3 */
+        if (route == T_KNOWN) { if (want_k) l_push(&K, i, 0, 0, -1); continue; }
+        if (route == T_UNRECOG) { if (want_x) l_push(&X, i, 0, 0, -1); continue; }
         const int64_t off = res->ex_off[i];
         const int n = (int)L2R_INFO_NEXON(info);
         const uint8_t rev = (info & L2R_INFO_REV) != 0;
         const int32_t *xs = res->ex_start + off, *xe = res->ex_end + off; const uint8_t *xf = res->ex_flag + off;
-        if (n_sj == 0 || (info & L2R_INFO_SJ_PASS)) {
+        if (route == T_NOVEL_WHOLE) {
             if (want_n) l_push(&N, i, 0, n - 1, -1);
             m_cand t = { reads->tid[i], xs[0], xe[n - 1], n, rev, xs, xe, xf };
             if (!m_merge(&t, &U, p)) {
                 m_ent *e = m_push(&U, &t);
                 e->read = i; e->ex_rev = rev; e->ex_tid = reads->tid[i]; e->gene_tx = res->ref_tx[i];
             }
-        } else if (p->split_trans) {
-            /* src/update_gtf.c:837-913 split_trans: cut at unreliable junctions; keep pieces with >= 2 exons
-             * that saw both a novel and a known junction */
-            int first = 0, seen_novel = 0, seen_known = 0, k = 0, j;
-            for (j = 0; j < n; ++j) {
-                const int at_end = (j == n - 1);
-                if (!at_end) { if (xf[j] & L2R_EXF_NOVEL_JUNC) seen_novel = 1; else seen_known = 1; }
-                if (at_end || (xf[j] & L2R_EXF_UNREL_JUNC)) {
-                    if (seen_novel && seen_known && j - first >= 1) {
-                        if (want_n) l_push(&N, i, first, j, k);
-                        uint8_t pf[4096], *fl = pf; const int pn = j - first + 1;
-                        if (pn > 4096) fl = (uint8_t *)h_malloc((size_t)pn);
-                        /* flags of the piece: exon flags copied; site/junction flags of junctions first..j-1 copied,
-                         * the piece has no junction after its last exon, unreliable flags start at 0 */
-                        for (int q = 0; q < pn; ++q) {
-                            uint8_t f = xf[first + q] & L2R_EXF_NOVEL_EXON;
-                            if (q + 1 < pn) f |= xf[first + q] & (L2R_EXF_NOVEL_DON | L2R_EXF_NOVEL_ACC | L2R_EXF_NOVEL_JUNC);
-                            fl[q] = f;
-                        }
-                        m_cand t = { 0, 0, 0, pn, 0, xs + first, xe + first, fl };          /* Q2: tid/start/end/strand stay 0 */
-                        if (!m_merge(&t, &U, p)) {
-                            m_ent *e = m_push(&U, &t);
-                            e->read = i; e->piece = k; e->partial = 1; e->ex_rev = rev; e->ex_tid = reads->tid[i]; e->gene_tx = res->ref_tx[i];
-                        }
-                        if (fl != pf) free(fl);
-                        ++k;
-                    }
-                    first = j + 1; seen_novel = seen_known = 0;
+        } else {                                                   /* T_NOVEL_SPLIT: the pieces of next_piece */
+            int first = 0, k = 0, at = 0, j = 0;
+            while (next_piece(xf, n, &at, &first, &j)) {
+                if (want_n) l_push(&N, i, first, j, k);
+                uint8_t pf[4096], *fl = pf; const int pn = j - first + 1;
+                if (pn > 4096) fl = (uint8_t *)h_malloc((size_t)pn);
+                /* flags of the piece: exon flags copied; site/junction flags of junctions first..j-1 copied,
+                 * the piece has no junction after its last exon, unreliable flags start at 0 */
+                for (int q = 0; q < pn; ++q) {
+                    uint8_t f = xf[first + q] & L2R_EXF_NOVEL_EXON;
+                    if (q + 1 < pn) f |= xf[first + q] & (L2R_EXF_NOVEL_DON | L2R_EXF_NOVEL_ACC | L2R_EXF_NOVEL_JUNC);
+                    fl[q] = f;
                 }
+                m_cand t = { 0, 0, 0, pn, 0, xs + first, xe + first, fl };          /* Q2: tid/start/end/strand stay 0 */
+                if (!m_merge(&t, &U, p)) {
+                    m_ent *e = m_push(&U, &t);
+                    e->read = i; e->piece = k; e->partial = 1; e->ex_rev = rev; e->ex_tid = reads->tid[i]; e->gene_tx = res->ref_tx[i];
+                }
+                if (fl != pf) free(fl);
+                ++k;
             }
         }
     }

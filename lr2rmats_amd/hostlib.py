@@ -52,6 +52,8 @@ def load_library():
         lib.h_records_to_bam.restype = C.c_int
         lib.h_job_needs_all_reads.argtypes = [C.c_void_p]
         lib.h_job_needs_all_reads.restype = C.c_int
+        lib.h_job_list_rows.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_int64, C.c_char_p]
+        lib.h_job_list_rows.restype = C.c_int
         lib.h_job_finish_accepted.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_int64)]
         lib.h_job_finish_accepted.restype = C.c_int
         lib.h_job_finish_part.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_char_p, C.c_char_p, C.c_int, C.POINTER(C.c_int64)]
@@ -378,6 +380,16 @@ class Job:
         res = capi.CResult(n, x, x, keep[0].ctypes.data_as(capi._i64p), keep[1].ctypes.data_as(capi._i32p), keep[2].ctypes.data_as(capi._i32p),
                            keep[3].ctypes.data_as(capi._u8p), keep[4].ctypes.data_as(capi._u32p), keep[5].ctypes.data_as(capi._i32p))
         return self.lib.h_job_finish(self.h, C.byref(res))
+
+    def list_rows(self, which: int, lo: int, hi: int, path: str, ex_off, ex_start, ex_end, ex_flag, info, ref_tx) -> int:
+        """Read list ``which`` (capi.GTX_LIST_*) of the reads [lo, hi) by the writer the command falls back on (h_list_rows), appended to
+        ``path``.  Arrays as in ``finish``, of the whole input."""
+        n, x = int(info.shape[0]), int(ex_start.shape[0])
+        keep = [np.ascontiguousarray(ex_off, np.int64), np.ascontiguousarray(ex_start, np.int32), np.ascontiguousarray(ex_end, np.int32),
+                np.ascontiguousarray(ex_flag, np.uint8), np.ascontiguousarray(info, np.uint32), np.ascontiguousarray(ref_tx, np.int32)]
+        res = capi.CResult(n, x, x, keep[0].ctypes.data_as(capi._i64p), keep[1].ctypes.data_as(capi._i32p), keep[2].ctypes.data_as(capi._i32p),
+                           keep[3].ctypes.data_as(capi._u8p), keep[4].ctypes.data_as(capi._u32p), keep[5].ctypes.data_as(capi._i32p))
+        return self.lib.h_job_list_rows(self.h, C.byref(res), int(which), int(lo), int(hi), path.encode())
 
     def needs_all_reads(self) -> bool:
         """An output of this run lists every read (detail.txt, -a / -k / -u, summary.txt)."""
