@@ -1,8 +1,9 @@
 // l2r_detailplan.hip.h -- the host side of l2r_detail_* (the per-read detail table of `update-gtf -A`): the argument checks, the kinds of a
 // read's domain error in the order they are looked for and their one text, detail_line_bytes (the exact bytes of one line and where its
-// segments begin, or its error kind), detail_cut (the batch cut over the measured lengths) and detail_text_host, the exact routine that
-// writes the same bytes on one core (L2R_DETAIL_ROUTE=host, and the comparator of tools/bench_detail.py).  Host arithmetic only: no HIP
-// call, no context, no environment.  tests/detail_dump.hip runs it as a stand-alone program for tests/test_detail_cpu.py.
+// segments begin, or its error kind) and detail_text_host, the exact routine that writes the same bytes on one core
+// (L2R_DETAIL_ROUTE=host, and the comparator of tools/bench_detail.py).  The checks themselves and the batch cut are those of
+// l2r_gtftextplan.hip.h (text_check_*, batch_cut).  Host arithmetic only: no HIP call, no context, no environment.  tests/detail_dump.hip
+// runs it as a stand-alone program for tests/test_detail_cpu.py.
 //
 // The rule is stated in include/lr2rmats_hip.h.  What both sides share beyond it, in functions the host and the kernels both compile: the
 // class of a read (detail_cls), the members an exon brings to one of the four index lists (detail_members), the bytes of a list
@@ -21,7 +22,7 @@
 #include <hip/hip_runtime.h>
 
 #include "../../include/lr2rmats_hip.h"
-#include "l2r_gtftextplan.hip.h"                        // gtx_digits, gtx_name_len, GTX_BATCH_BYTES, GTX_REF_NAME_MAX
+#include "l2r_gtftextplan.hip.h"                        // gtx_digits, gtx_name_len, GTX_BATCH_BYTES, text_check_*, batch_cut
 
 namespace l2r {
 
@@ -63,45 +64,15 @@ static int detail_check_params(const l2r_detail_params *p, std::string &msg, con
     if (p->n_ref < 0) { gtx_fail(msg, "[%s] %d reference names", who, p->n_ref); return -2; }
     if (p->n_ref > 0) {
         if (!p->ref_off) { gtx_fail(msg, "[%s] null ref_off", who); return -2; }
-        if (p->ref_off[0] != 0) { gtx_fail(msg, "[%s] ref_off does not start at 0", who); return -2; }
-        for (int32_t k = 0; k < p->n_ref; ++k) {
-            const int64_t l = p->ref_off[k + 1] - p->ref_off[k];
-            if (l < 0) { gtx_fail(msg, "[%s] ref_off descends at name %d", who, k); return -2; }
-            if (l > GTX_REF_NAME_MAX) { gtx_fail(msg, "[%s] reference name %d has %lld bytes (at most %lld)", who, k, (long long)l, (long long)GTX_REF_NAME_MAX); return -2; }
-        }
-        if (p->ref_off[p->n_ref] > 0 && !p->ref_names) { gtx_fail(msg, "[%s] null ref_names", who); return -2; }
+        if (text_check_ref_off(p->n_ref, p->ref_off, p->ref_names, msg, who)) return -2;
     }
-    if (p->n_tx < 0 || p->n_tx >= ((int64_t)1 << 31)) { gtx_fail(msg, "[%s] %lld annotation transcripts (below 2^31)", who, (long long)p->n_tx); return -2; }
-    if (p->anno_names_len < 0 || p->anno_names_len > 0xffffffffll) { gtx_fail(msg, "[%s] an annotation names table of %lld bytes (at most 2^32 - 1)", who, (long long)p->anno_names_len); return -2; }
-    if (p->anno_names_len > 0 && !p->anno_names) { gtx_fail(msg, "[%s] null anno_names", who); return -2; }
-    if (p->n_tx > 0 && (!p->tx_gid || !p->tx_gname)) { gtx_fail(msg, "[%s] null gene column", who); return -2; }
-    return 0;
+    return text_check_genes(p->n_tx, p->anno_names_len, p->anno_names, p->tx_gid, p->tx_gname, msg, who);
 }
 
-// 0, or -2 and the text.  Sizes and pointers; with results (res != NULL) their sizes, and ex_off against the exon counts of info.  What
-// a read holds is the lines' business (detail_line_bytes).
 static int detail_check_rows(const l2r_detail_reads *r, std::string &msg, const char *who = "l2r_detail_rows")
 {
     if (!r) { gtx_fail(msg, "[%s] null argument", who); return -2; }
-    if (r->n < 0 || r->n >= ((int64_t)1 << 31)) { gtx_fail(msg, "[%s] %lld reads (below 2^31)", who, (long long)r->n); return -2; }
-    if (r->names_len < 0 || r->names_len > 0xffffffffll) { gtx_fail(msg, "[%s] a names table of %lld bytes (at most 2^32 - 1)", who, (long long)r->names_len); return -2; }
-    if (r->names_len > 0 && !r->names) { gtx_fail(msg, "[%s] null names", who); return -2; }
-    if (r->n > 0 && (!r->tid || !r->qname)) { gtx_fail(msg, "[%s] null column", who); return -2; }
-    const l2r_result *s = r->res;
-    if (!s) return 0;                                       // (the results of the last l2r_run)
-    if (s->n_reads != r->n) { gtx_fail(msg, "[%s] results of %lld reads for %lld rows", who, (long long)s->n_reads, (long long)r->n); return -2; }
-    if (s->n_exons < 0 || s->n_exons > 0xffffffffll) { gtx_fail(msg, "[%s] results of %lld exons (at most 2^32 - 1)", who, (long long)s->n_exons); return -2; }
-    if (!s->ex_off) { gtx_fail(msg, "[%s] null ex_off", who); return -2; }
-    if (r->n > 0 && (!s->info || !s->ref_tx)) { gtx_fail(msg, "[%s] null result column", who); return -2; }
-    if (s->n_exons > 0 && (!s->ex_start || !s->ex_end || !s->ex_flag)) { gtx_fail(msg, "[%s] null exon column", who); return -2; }
-    if (s->ex_off[0] != 0) { gtx_fail(msg, "[%s] ex_off does not start at 0", who); return -2; }
-    for (int64_t i = 0; i < r->n; ++i)
-        if (s->ex_off[i + 1] - s->ex_off[i] != (int64_t)L2R_INFO_NEXON(s->info[i])) {
-            gtx_fail(msg, "[%s] read %lld: ex_off gives %lld exons, info %u", who, (long long)i, (long long)(s->ex_off[i + 1] - s->ex_off[i]), L2R_INFO_NEXON(s->info[i]));
-            return -2;
-        }
-    if (s->ex_off[r->n] != s->n_exons) { gtx_fail(msg, "[%s] ex_off ends at %lld, the results hold %lld exons", who, (long long)s->ex_off[r->n], (long long)s->n_exons); return -2; }
-    return 0;
+    return text_check_reads(r->n, r->names_len, r->names, r->tid, r->qname, r->res, msg, who, "rows");
 }
 
 // ---- what the host and the kernels both compile
@@ -203,24 +174,9 @@ static int detail_line_bytes(const l2r_detail_params *p, const l2r_detail_reads 
     return DET_OK;
 }
 
-// How many rows from `first` one batch takes, over the measured lengths len[0, n): while their count stays within max_rows and the
-// 64-bit sum of their bytes within max_bytes and below 2^32 - 64 -- but always one.  *n_bytes = their sum.  0, or -2 and the text.
+// the batch cut over the measured lengths of the rows of l2r_detail_lines
 static int detail_cut(const uint32_t *len, int64_t n, int64_t first, int64_t max_rows, int64_t max_bytes, int64_t *n_take, int64_t *n_bytes, std::string &msg)
-{
-    if (!n_take || !n_bytes) { gtx_fail(msg, "[l2r_detail_lines] null argument"); return -2; }
-    *n_take = 0; *n_bytes = 0;
-    if (first < 0 || first >= n) { gtx_fail(msg, "[l2r_detail_lines] first row %lld of %lld", (long long)first, (long long)n); return -2; }
-    if (max_rows < 1 || max_bytes < 1) { gtx_fail(msg, "[l2r_detail_lines] a batch of %lld rows and %lld bytes", (long long)max_rows, (long long)max_bytes); return -2; }
-    uint64_t sum = 0;
-    int64_t k = 0;
-    for (; first + k < n && k < max_rows; ++k) {
-        const uint64_t b = len[first + k];
-        if (k > 0 && (sum + b > (uint64_t)max_bytes || sum + b >= DETAIL_BATCH_BYTES)) break;
-        sum += b;
-    }
-    *n_take = k; *n_bytes = (int64_t)sum;
-    return 0;
-}
+{ return batch_cut(len, n, first, max_rows, max_bytes, n_take, n_bytes, msg, "l2r_detail_lines", "row"); }
 
 // list k of a read: <cnt>\t, the members comma separated or NA, and what stands behind (a tab; behind L4 only where it is empty)
 static void detail_put_list(std::vector<uint8_t> &out, const uint8_t *f, uint32_t n, int k)

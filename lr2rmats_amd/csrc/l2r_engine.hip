@@ -53,11 +53,12 @@ static int fail(int code, const char *fmt, ...)
     return code;
 }
 
-#define HIP_TRY(expr)                                                                                   \
+#define HIP_TRY_AS(who, expr)                                                                           \
     do {                                                                                                \
         hipError_t e_ = (expr);                                                                         \
-        if (e_ != hipSuccess) return fail(-2, "[%s] %s: %s", __func__, #expr, hipGetErrorString(e_));   \
+        if (e_ != hipSuccess) return fail(-2, "[%s] %s: %s", who, #expr, hipGetErrorString(e_));        \
     } while (0)
+#define HIP_TRY(expr) HIP_TRY_AS(__func__, expr)        // (HIP_TRY_AS: in a helper, under the entry point's name)
 
 template <typename T>
 struct DevBuf {
@@ -199,6 +200,37 @@ struct RefNames {
     int upload(l2r_ctx *c);                             // (behind l2r_ctx) queued on the context stream
 };
 
+// The annotation's gene tables of a per-read text command (l2r_detail_begin, l2r_gtftext_anno), in the manner of RefNames; one element of
+// padding behind each, so that no vector is empty.  Each command keeps its own: the two may be given different tables.
+struct GeneTables {
+    std::vector<uint8_t> h_names; std::vector<uint32_t> h_gid, h_gname;
+    DevBuf<uint8_t> names; DevBuf<uint32_t> gid, gname;
+    void set(int64_t n_tx, int64_t names_len, const uint8_t *anno_names, const uint32_t *tx_gid, const uint32_t *tx_gname)
+    {
+        const size_t T = (size_t)n_tx, A = (size_t)names_len;
+        h_names.assign(A + 1, 0);
+        if (A) memcpy(h_names.data(), anno_names, A);
+        h_gid.assign(T + 1, 0); h_gname.assign(T + 1, 0);
+        if (T) { memcpy(h_gid.data(), tx_gid, T * 4); memcpy(h_gname.data(), tx_gname, T * 4); }
+    }
+    int upload(l2r_ctx *c);                             // (behind l2r_ctx) queued on the context stream
+};
+
+// The reads of a shard and their results as l2r_detail_rows and l2r_gtftext_reads keep them (take_reads): on the device or, the host route
+// alone, on the host.  run_res: they came with res == NULL, the results are those of the context's last l2r_run in HBM (result_cols).
+struct ReadRows {
+    bool run_res = false;
+    int64_t n = 0, names_len = 0; double exons_per_read = 0;
+    DevBuf<int32_t> tid, xs, xe, ref_tx; DevBuf<uint8_t> names, f; DevBuf<uint32_t> qname, tid_name, ex_off, info;
+    const uint32_t *tid_name_p = nullptr;               // qname's buffer where no tid_name came
+    struct Host {                                       // the host route's copies; tid_name is empty where none came (tid_name_or_qname)
+        std::vector<int32_t> tid, xs, xe, ref_tx; std::vector<uint8_t> names, f; std::vector<uint32_t> qname, tid_name, info; std::vector<int64_t> ex_off;
+        l2r_result res{};                               // points into the vectors
+        const uint32_t *tid_name_or_qname() const { return tid_name.empty() ? qname.data() : tid_name.data(); }
+    } h;
+    std::vector<uint32_t> off32;                        // ex_off narrowed for the upload; it lives until the stream has been waited for
+};
+
 // The text a command has produced (l2r_bed_lines, l2r_gtftext_lines), in HBM or on the host where the host route made it, until text_out
 // fetches it.  TEXT_SLACK bytes lie behind the text in HBM; under L2R_CHECK they hold a pattern that the write kernel must leave alone.
 constexpr size_t TEXT_SLACK = 64;
@@ -282,20 +314,13 @@ struct GtxState {
     // the list and l2r_gtftext_lines composes them with k_rl_write (or rl_text_host); l2r_gtftext_rows ends that.
     struct Lists {
         bool have_anno = false, have_reads = false, active = false;
-        bool run_res = false;                           // reads came with res == NULL: the results of the context's last l2r_run
         bool has_sj = false, split = false;
-        l2r_gtx_anno anno{};                            // points into h_anno, h_gid, h_gname
-        std::vector<uint8_t> h_anno; std::vector<uint32_t> h_gid, h_gname;
-        DevBuf<uint8_t> d_anno; DevBuf<uint32_t> d_gid, d_gname;
-        int64_t n = 0, names_len = 0, n_pieces = 0;
+        l2r_gtx_anno anno{};                            // points into genes' vectors
+        GeneTables genes;
+        ReadRows reads;
+        int64_t n_pieces = 0;
         int list = 0;
-        double exons_per_read = 0;
-        DevBuf<int32_t> tid, xs, xe, ref_tx; DevBuf<uint8_t> names, f; DevBuf<uint32_t> qname, tid_name, ex_off, info;   // (the results: uploaded reads only)
-        const uint32_t *tid_name_p = nullptr;           // qname's buffer where no tid_name came
-        struct Host {                                   // the host route's copies, and its selection
-            std::vector<int32_t> tid, xs, xe, ref_tx; std::vector<uint8_t> names, f; std::vector<uint32_t> qname, tid_name, info; std::vector<int64_t> ex_off;
-            RlSel sel;
-        } h;
+        RlSel h_sel;                                    // the host route's selection
         DevBuf<uint32_t> cnt, hfix, word;               // cnt: blocks per read, scanned in place (n + 1); hfix: per block; word[0]: the blocks, [1]: the piece blocks
         DevBuf<int32_t> b_read, b_first, b_count, b_piece;      // the selection
     } rl;
@@ -304,20 +329,13 @@ struct GtxState {
 // The detail table of `update-gtf -A` (l2r_detail.hip.h): the reference names and the annotation's gene tables of l2r_detail_begin, the
 // reads of l2r_detail_rows with what k_detail_measure left per read, and the text of the last l2r_detail_lines (in HBM, or on the host
 // where the host route made it) until l2r_detail_out fetches it.  The route is read at l2r_detail_rows and holds until the next; only the
-// host route keeps copies of the columns (h).  The buffers belong to the context, grow on demand and are used again.
+// host route keeps copies of the columns (rows.h).  The buffers belong to the context, grow on demand and are used again.
 struct DetailState {
     bool begun = false, have_rows = false, on_host = false;
-    bool run_res = false;                               // rows came with res == NULL: the results of the context's last l2r_run
-    l2r_detail_params prm{};                            // ref_off / ref_names point into ref's vectors, the gene tables into h_anno, h_gid, h_gname
+    l2r_detail_params prm{};                            // ref_off / ref_names point into ref's vectors, the gene tables into genes'
     RefNames ref;
-    std::vector<uint8_t> h_anno; std::vector<uint32_t> h_gid, h_gname;
-    DevBuf<uint8_t> anno; DevBuf<uint32_t> tx_gid, tx_gname;
-    int64_t n = 0, names_len = 0;
-    DevBuf<int32_t> tid, xs, xe, ref_tx; DevBuf<uint8_t> names, f; DevBuf<uint32_t> qname, ex_off, info;        // (the results: uploaded rows only)
-    struct Host {                                       // the host route's copies
-        std::vector<int32_t> tid, xs, xe, ref_tx; std::vector<uint8_t> names, f; std::vector<uint32_t> qname, info; std::vector<int64_t> ex_off;
-        l2r_result res{};
-    } h;
+    GeneTables genes;
+    ReadRows rows;
     std::vector<uint32_t> h_len;                        // the measured bytes of every read
     DevBuf<uint32_t> len, split, off, word;             // len, split: per read; off: one batch's lengths, scanned in place; word: DETC_* and the scan's total
     DevBuf<unsigned long long> word64;                  // k_detail_measure: the smallest bad read << 4 | kind
@@ -605,6 +623,8 @@ static int download_all(l2r_ctx *c, int rc, std::initializer_list<Download> list
 }
 
 static bool env_on(const char *name) { const char *e = getenv(name); return e && atoi(e) != 0; }
+// L2R_BED_ROUTE, L2R_UNIQ_ROUTE, L2R_GTX_ROUTE, L2R_DETAIL_ROUTE = host: the exact host routine instead of the kernels (tests, comparators)
+static bool route_is_host(const char *env) { const char *e = getenv(env); return e && strcmp(e, "host") == 0; }
 
 // The form of a measure kernel (k_fusion_seg, k_bed_measure, k_gtx_measure, k_detail_measure): one wave per item where the items are long, above 32 words
 // on average -- the bound of l2r_upload_reads' wide_cigar (upload_plan, l2r_plan.hip.h).  env (L2R_FUSION_WAVE, L2R_BED_WAVE,
@@ -628,6 +648,8 @@ int RefNames::upload(l2r_ctx *c)
     if (int rc = put_dev(c, off, h_off)) return rc;
     return put_dev(c, names, h_names);
 }
+
+int GeneTables::upload(l2r_ctx *c) { int rc; return (rc = put_dev(c, names, h_names)) || (rc = put_dev(c, gid, h_gid)) || (rc = put_dev(c, gname, h_gname)) ? rc : 0; }
 
 hipError_t TextOut::arm_guard(const l2r_ctx *c, size_t B) { return c->check_stages ? hipMemsetAsync(bytes() + B, TEXT_GUARD_BYTE, TEXT_SLACK, c->stream) : hipSuccess; }
 hipError_t TextOut::fetch_guard(const l2r_ctx *c, size_t B) { return c->check_stages ? hipMemcpyAsync(guard, bytes() + B, TEXT_SLACK, hipMemcpyDeviceToHost, c->stream) : hipSuccess; }
@@ -2811,8 +2833,7 @@ int l2r_bed_lines(l2r_ctx *c, const l2r_bed_records *r, int64_t *n_lines, int64_
     *n_lines = 0; *n_bytes = 0;
     const size_t N = (size_t)r->n;
     m.stats[BEDS_RECORDS] = (double)N; m.stats[BEDS_GUARD] = 1;
-    const char *route = getenv("L2R_BED_ROUTE");
-    const bool on_host = route && strcmp(route, "host") == 0;
+    const bool on_host = route_is_host("L2R_BED_ROUTE");
     m.stats[BEDS_ROUTE] = on_host ? 1 : 0;
     if (N == 0) { m.out.take_host(); return 0; }
     if (N > (size_t)0xffffffffu - 1u) return fail(-1, "[l2r_bed_lines] a batch of %zu records (at most 2^32 - 2)", N);
@@ -2930,8 +2951,7 @@ int l2r_uniq_merge(l2r_ctx *c, const l2r_params *prm, const l2r_uniq_trans *t, i
     const size_t N = (size_t)t->n;
     const UniqPrm p = uniq_prm(prm);
     m.n = t->n; m.stats[UQS_ROWS] = (double)N;
-    const char *route = getenv("L2R_UNIQ_ROUTE");
-    const bool want_host = route && strcmp(route, "host") == 0;     // (tests, the comparator; the device route is the default: DESIGN section 12)
+    const bool want_host = route_is_host("L2R_UNIQ_ROUTE");         // (tests, the comparator; the device route is the default: DESIGN section 12)
     if (N == 0) { m.have = true; m.on_host = true; m.stats[UQS_ROUTE] = want_host ? 1 : 0; return 0; }
     if (want_host) { uniq_on_host(m, t, p, uniq_in_order(t)); *n_unique = m.n_unique; return 0; }
     HIP_TRY(hipSetDevice(c->device));
@@ -3008,6 +3028,138 @@ int l2r_uniq_out(l2r_ctx *c, uint8_t *merged, int32_t *uniq_of, int32_t *u_src, 
 
 int l2r_uniq_stats(l2r_ctx *c, double *out, int n) { return stats_out(c ? c->uniq.stats : nullptr, UQS_N, out, n, "l2r_uniq_stats"); }
 
+}  // extern "C"
+
+// ---------------------------------------------------------------------------------------------- what the text commands below share (outside the C linkage block: two take a callable)
+// The reads of l2r_detail_rows (noun "rows") and of l2r_gtftext_reads ("reads", which alone has a tid_name) into `rr`: the checks against
+// the last run where they came without results, the host route's copies or the uploads.  The uploads are queued (with no reads still a
+// names table's) and the columns the caller's: it waits for the stream on every path out; a failure here has waited.  arg_code: of an
+// error of arguments or order.
+static int take_reads(l2r_ctx *c, ReadRows &rr, const l2r_gtx_reads &r, bool on_host, const char *who, int arg_code, const char *noun)
+{
+    const size_t N = (size_t)r.n, NL = (size_t)r.names_len;
+    rr.n = r.n; rr.names_len = r.names_len; rr.run_res = !r.res; rr.exons_per_read = 0;
+    int rc = 0;
+    if (rr.run_res) {
+        if (!c->ran) return fail(arg_code, "[%s] no completed run on this context", who);
+        if ((rc = fetch_totals(c))) return rc;
+        if (!(c->want & L2R_WANT_RESULTS)) return fail(arg_code, "[%s] the last run kept no results (l2r_set_outputs without L2R_WANT_RESULTS)", who);
+        if (r.n != c->n_reads) return fail(arg_code, "[%s] %lld %s, the last run had %lld reads", who, (long long)r.n, noun, (long long)c->n_reads);
+        if (N) rr.exons_per_read = (double)c->h_totals[0] / (double)N;
+    } else if (N) rr.exons_per_read = (double)r.res->n_exons / (double)N;
+    const l2r_result *s = r.res; const bool two_names = r.tid_name && r.tid_name != r.qname;
+    if (on_host) {
+        ReadRows::Host &h = rr.h;
+        h.tid.assign(r.tid, r.tid + N); h.qname.assign(r.qname, r.qname + N); h.names.assign(r.names, r.names + NL);
+        if (two_names) h.tid_name.assign(r.tid_name, r.tid_name + N); else h.tid_name.clear();
+        const size_t X = rr.run_res ? (size_t)c->h_totals[0] : (size_t)s->n_exons;
+        h.ex_off.assign(N + 1, 0); h.info.assign(N ? N : 1, 0u); h.ref_tx.assign(N ? N : 1, 0); h.xs.assign(X ? X : 1, 0); h.xe.assign(X ? X : 1, 0); h.f.assign(X ? X : 1, 0);
+        h.res = l2r_result{(int64_t)N, (int64_t)X, (int64_t)X, h.ex_off.data(), h.xs.data(), h.xe.data(), h.f.data(), h.info.data(), h.ref_tx.data()};
+        if (rr.run_res) { if (N && (rc = l2r_download(c, &h.res))) return rc; }
+        else if (N) {
+            memcpy(h.ex_off.data(), s->ex_off, (N + 1) * 8); memcpy(h.info.data(), s->info, N * 4); memcpy(h.ref_tx.data(), s->ref_tx, N * 4);
+            if (X) { memcpy(h.xs.data(), s->ex_start, X * 4); memcpy(h.xe.data(), s->ex_end, X * 4); memcpy(h.f.data(), s->ex_flag, X); }
+        }
+        return 0;
+    }
+    if ((rc = to_dev(c, rr.tid, r.tid, N)) || (rc = to_dev(c, rr.qname, r.qname, N)) || (rc = to_dev(c, rr.names, r.names, NL))) {}
+    rr.tid_name_p = rr.qname.p;
+    if (!rc && two_names) { rc = to_dev(c, rr.tid_name, r.tid_name, N); rr.tid_name_p = rr.tid_name.p; }
+    if (!rc && !rr.run_res) {
+        const size_t X = (size_t)s->n_exons;
+        rr.off32.resize(N);
+        for (size_t i = 0; i < N; ++i) rr.off32[i] = (uint32_t)s->ex_off[i];
+        if ((rc = put_dev(c, rr.ex_off, rr.off32)) || (rc = to_dev(c, rr.info, (const uint32_t *)s->info, N)) || (rc = to_dev(c, rr.ref_tx, (const int32_t *)s->ref_tx, N)) ||
+            (rc = to_dev(c, rr.xs, (const int32_t *)s->ex_start, X)) || (rc = to_dev(c, rr.xe, (const int32_t *)s->ex_end, X)) || (rc = to_dev(c, rr.f, (const uint8_t *)s->ex_flag, X))) {}
+    }
+    if (rc) (void)hipStreamSynchronize(c->stream);                  // (the columns are the caller's)
+    return rc;
+}
+
+// The result columns the kernels read: those of the context's last run, or the uploaded ones in the same layout
+struct ResultCols { const uint32_t *ex_off, *info; const int32_t *xs, *xe, *ref_tx; const uint8_t *f; };
+static ResultCols result_cols(const l2r_ctx *c, const ReadRows &r)
+{
+    return r.run_res ? ResultCols{c->ex_off.p, c->info.p, c->ex_start.p, c->ex_end.p, c->ref_tx.p, c->ex_flag.p} : ResultCols{r.ex_off.p, r.info.p, r.xs.p, r.xe.p, r.ref_tx.p, r.f.p};
+}
+
+// The tail of a measure step (k_gtx_measure, k_rl_measure, k_detail_measure).  The kernels leave the smallest bad item << 4 | the kind of
+// its domain error in d_word[0], by atomicMin over a word of ones: the word is armed (the words behind it, n_words in all, are zeroed: the
+// GTF measures count their lines in a second one), `launch` runs under the stage timer, the words come back to w with the lengths of
+// h_len's items, *bytes is their sum.  A word that names no item or no kind is the device's inconsistency (-2); a domain error is -1 and
+// the text of item_fail, as on the host route.  The stream has been waited for in any case.
+template <typename Launch>
+static int measure_tail(l2r_ctx *c, StageTimer &clk, double *ms, unsigned long long *d_word, unsigned long long *w, size_t n_words, std::vector<uint32_t> &h_len, const uint32_t *d_len,
+                        const char *who, const char *item, int n_kinds, int (*item_fail)(std::string &, int64_t, int), uint64_t *bytes, Launch launch)
+{
+    const size_t M = h_len.size();
+    hipError_t e = hipMemsetAsync(d_word, 0xff, sizeof(unsigned long long), c->stream);
+    if (e == hipSuccess && n_words > 1) e = hipMemsetAsync(d_word + 1, 0, (n_words - 1) * sizeof(unsigned long long), c->stream);
+    int rc = e == hipSuccess ? clk.launch(c, ms, launch) : fail(-2, "[%s] %s", who, hipGetErrorString(e));
+    if ((rc = download_all(c, rc, {{w, d_word, n_words * sizeof(unsigned long long)}, {h_len.data(), d_len, M * 4}}, who))) return rc;
+    if (w[0] != ~0ull) {
+        const unsigned long long q = w[0] >> 4; const int kind = (int)(w[0] & 15ull);
+        if (q >= M || kind <= 0 || kind >= n_kinds) return fail(-2, "[%s] the device names %s %llu of %zu, kind %d", who, item, q, M, kind);
+        std::string msg; item_fail(msg, (int64_t)q, kind);
+        return fail(-1, "%s", msg.c_str());
+    }
+    for (size_t q = 0; q < M; ++q) *bytes += h_len[q];
+    return 0;
+}
+
+// slots that l2r_gtftext_stats and l2r_detail_stats have in common: those of a batch
+enum { TXS_LINES = 1, TXS_BYTES, TXS_WAVE, TXS_TILES_LDS, TXS_TILES_DIRECT, TXS_ROUTE, TXS_GUARD, TXS_BATCHES, TXS_K_MEASURE, TXS_K_SCAN, TXS_K_WRITE };
+
+// What l2r_gtftext_lines and l2r_detail_lines differ in, beside their write kernels and host routines
+struct TextBatch {
+    const char *who, *timing, *disagree;    // the entry point; the switch of its stage timer; what a count of `outside` says
+    int tile, total, outside, direct;       // items of a workgroup of the write kernel; counter words: the scan's total (behind the kernel's own), what left its place, the direct tiles
+};
+
+// One batch of text, behind l2r_gtftext_lines and l2r_detail_lines: the items [first, first + take) of `sum` bytes, as the caller cut them
+// from the measured lengths, into `out`.  Host route: compose(host_text, msg) is the exact host routine.  Device route: the batch's
+// lengths are scanned into `off`, the guard armed, write(n_tiles, text) launches the write kernel, and its counters come back to
+// w[0 .. t.total] with the guard; three of them are checked here, the rest is the caller's.  stats: the TXS_* slots but the lines.
+template <typename Compose, typename Write>
+static int text_batch(l2r_ctx *c, const TextBatch &t, TextOut &out, StageTimer &clk, const DevBuf<uint32_t> &len, DevBuf<uint32_t> &off, DevBuf<uint32_t> &word, double *stats,
+                      bool on_host, int64_t first, int64_t take, int64_t sum, uint32_t *w, Compose compose, Write write)
+{
+    const size_t B = (size_t)sum, K = (size_t)take, W = (size_t)t.total + 1;
+    stats[TXS_LINES] = 0; stats[TXS_BYTES] = 0; stats[TXS_TILES_LDS] = 0; stats[TXS_TILES_DIRECT] = 0;
+    if (on_host) {
+        std::string msg;
+        if (compose(out.host_text, msg)) { out.host_text.clear(); return fail(-1, "%s", msg.c_str()); }
+        if (out.host_text.size() != B) return fail(-5, "[%s] %zu bytes of text, measured %zu", t.who, out.host_text.size(), B);
+        out.take_host();
+        stats[TXS_BYTES] = (double)B; stats[TXS_BATCHES] += 1;
+        return 0;
+    }
+    HIP_TRY_AS(t.who, hipSetDevice(c->device));
+    int rc;
+    if ((rc = clk.begin(env_on(t.timing), c->check_stages))) return rc;
+    if (off.ensure(K + 1) || out.reserve(B) || word.ensure(W)) return -2;
+    HIP_TRY_AS(t.who, hipMemcpyAsync(off.p, len.p + first, K * 4, hipMemcpyDeviceToDevice, c->stream));
+    HIP_TRY_AS(t.who, hipMemsetAsync(word.p, 0, W * sizeof(uint32_t), c->stream));
+    if ((rc = clk.launch(c, &stats[TXS_K_SCAN], [&] { scan_u32(c, off.p, (int64_t)K, word.p + t.total); }))) { (void)hipStreamSynchronize(c->stream); return rc; }
+    HIP_TRY_AS(t.who, out.arm_guard(c, B));
+    const unsigned n_tiles = (unsigned)((K + (size_t)t.tile - 1) / (size_t)t.tile);
+    if ((rc = clk.launch(c, &stats[TXS_K_WRITE], [&] { write(n_tiles, out.bytes()); }))) { (void)hipStreamSynchronize(c->stream); return rc; }
+    hipError_t e = hipMemcpyAsync(w, word.p, W * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = out.fetch_guard(c, B);
+    const hipError_t sync = hipStreamSynchronize(c->stream);       // (w is the caller's)
+    if (e == hipSuccess) e = sync;
+    if (e != hipSuccess) return fail(-2, "[%s] %s", t.who, hipGetErrorString(e));
+    if (!out.guard_intact(c)) stats[TXS_GUARD] = 0;
+    if ((size_t)w[t.total] != B) return fail(-5, "[%s] the scan left %u bytes, the cut %zu", t.who, w[t.total], B);
+    if (w[t.outside]) return fail(-5, "[%s] %u %s", t.who, w[t.outside], t.disagree);
+    if (w[t.direct] > n_tiles) return fail(-5, "[%s] %u direct tiles of %u", t.who, w[t.direct], n_tiles);
+    stats[TXS_BYTES] = (double)B; stats[TXS_BATCHES] += 1;
+    stats[TXS_TILES_DIRECT] = (double)w[t.direct]; stats[TXS_TILES_LDS] = (double)(n_tiles - w[t.direct]);
+    out.take_device(B);
+    return 0;
+}
+
+extern "C" {
 // ---------------------------------------------------------------------------------------------- the GTF text of bam2gtf / unique-gtf
 // slots of l2r_gtftext_stats
 enum { GXS_BLOCKS = 0, GXS_LINES, GXS_BYTES, GXS_WAVE, GXS_TILES_LDS, GXS_TILES_DIRECT, GXS_ROUTE, GXS_GUARD, GXS_BATCHES, GXS_K_MEASURE, GXS_K_SCAN, GXS_K_WRITE, GXS_K_SELECT, GXS_PIECES, GXS_N };
@@ -3064,8 +3216,7 @@ int l2r_gtftext_rows(l2r_ctx *c, const l2r_gtx_rows *r)
     if (!m.begun) return fail(GTX_E_ARG, "[l2r_gtftext_rows] no l2r_gtftext_begin in front");
     {   std::string msg;
         if (gtx_check_rows(r, m.prm.form, msg)) return fail(GTX_E_ARG, "%s", msg.c_str()); }
-    const char *route = getenv("L2R_GTX_ROUTE");
-    m.on_host = route && strcmp(route, "host") == 0;
+    m.on_host = route_is_host("L2R_GTX_ROUTE");
     m.stats[GXS_ROUTE] = m.on_host ? 1 : 0;
     const size_t N = (size_t)r->n, NL = (size_t)r->names_len;
     const int n_names = m.prm.form == L2R_GTX_READ ? 4 : 2;
@@ -3139,10 +3290,11 @@ static RlIn rl_in(const l2r_ctx *c, const GtxState &m)
 {
     const GtxState::Lists &l = m.rl;
     RlIn in{};
-    in.n = l.n; in.m = m.m; in.tid = l.tid.p; in.names = l.names.p; in.names_len = l.names_len; in.qname = l.qname.p; in.tid_name = l.tid_name_p;
-    if (l.run_res) { in.ex_off = c->ex_off.p; in.info = c->info.p; in.xs = c->ex_start.p; in.xe = c->ex_end.p; in.ref_tx = c->ref_tx.p; in.f = c->ex_flag.p; }
-    else { in.ex_off = l.ex_off.p; in.info = l.info.p; in.xs = l.xs.p; in.xe = l.xe.p; in.ref_tx = l.ref_tx.p; in.f = l.f.p; }
-    in.n_tx = l.anno.n_tx; in.anno_len = l.anno.anno_names_len; in.anno = l.d_anno.p; in.tx_gid = l.d_gid.p; in.tx_gname = l.d_gname.p;
+    const ReadRows &r = l.reads;
+    const ResultCols v = result_cols(c, r);
+    in.n = r.n; in.m = m.m; in.tid = r.tid.p; in.names = r.names.p; in.names_len = r.names_len; in.qname = r.qname.p; in.tid_name = r.tid_name_p;
+    in.ex_off = v.ex_off; in.info = v.info; in.xs = v.xs; in.xe = v.xe; in.ref_tx = v.ref_tx; in.f = v.f;
+    in.n_tx = l.anno.n_tx; in.anno_len = l.anno.anno_names_len; in.anno = l.genes.names.p; in.tx_gid = l.genes.gid.p; in.tx_gname = l.genes.gname.p;
     in.b_read = l.b_read.p; in.b_first = l.b_first.p; in.b_count = l.b_count.p; in.b_piece = l.b_piece.p;
     in.n_ref = m.prm.n_ref; in.ref_off = m.ref.off.p; in.ref_names = m.ref.names.p; in.src = m.src.p; in.src_len = (uint32_t)m.prm.src_len;
     in.list = l.list; in.has_sj = l.has_sj; in.split = l.split;
@@ -3151,8 +3303,9 @@ static RlIn rl_in(const l2r_ctx *c, const GtxState &m)
 // ... and the host route's, over its copies
 static RlReads rl_host_view(const GtxState &m)
 {
-    const GtxState::Lists::Host &h = m.rl.h;
-    return RlReads{m.rl.n, h.tid.data(), m.rl.names_len, h.names.data(), h.qname.data(), h.tid_name.data(), h.ex_off.data(), h.info.data(), h.ref_tx.data(),
+    const ReadRows &r = m.rl.reads;
+    const ReadRows::Host &h = r.h;
+    return RlReads{r.n, h.tid.data(), r.names_len, h.names.data(), h.qname.data(), h.tid_name_or_qname(), h.ex_off.data(), h.info.data(), h.ref_tx.data(),
                    h.xs.data(), h.xe.data(), h.f.data(), m.rl.has_sj, m.rl.split};
 }
 
@@ -3201,25 +3354,15 @@ int l2r_gtftext_blocks(l2r_ctx *c, const l2r_gtx_blocks *b, int64_t *n_lines, in
         if ((m.has_sel && (rc = to_dev(c, m.sel, b->sel, M))) || (m.has_start && (rc = to_dev(c, m.start, b->start, M))) || (m.has_end && (rc = to_dev(c, m.end, b->end, M))) ||
             (m.has_cov && (rc = to_dev(c, m.cov, b->cov, M))) || m.len.ensure(M) || m.fix.ensure(M) || m.word64.ensure(2) || m.word.ensure(GTXC_TOTAL + 1)) rc = rc ? rc : -2;
         if (rc) { (void)hipStreamSynchronize(c->stream); return rc; }  // (the columns are the caller's)
-        HIP_TRY(hipMemsetAsync(m.word64.p, 0xff, sizeof(unsigned long long), c->stream));
-        HIP_TRY(hipMemsetAsync(m.word64.p + 1, 0, sizeof(unsigned long long), c->stream));
         const GtxIn in = gtx_in(c, m);
         const GtxMeasure meas{m.len.p, m.fix.p, m.word64.p, m.word64.p + 1};
-        rc = m.clk.launch(c, &m.stats[GXS_K_MEASURE], [&] {
-            const dim3 grid((unsigned)(((wave ? M * 64 : M) + 255) / 256));
-            if (wave) hipLaunchKernelGGL(k_gtx_measure<true>, grid, dim3(256), 0, c->stream, in, meas);
-            else hipLaunchKernelGGL(k_gtx_measure<false>, grid, dim3(256), 0, c->stream, in, meas);
-        });
         unsigned long long w[2] = {0, 0};
-        if ((rc = download_all(c, rc, {{w, m.word64.p, sizeof w}, {m.h_len.data(), m.len.p, M * 4}}, "l2r_gtftext_blocks"))) return rc;
-        if (w[0] != ~0ull) {
-            const unsigned long long q = w[0] >> 4; const int kind = (int)(w[0] & 15ull);
-            if (q >= M || kind <= GTX_OK || kind >= GTX_E_N) return fail(-2, "[l2r_gtftext_blocks] the device names block %llu of %zu, kind %d", q, M, kind);
-            std::string msg; gtx_block_fail(msg, (int64_t)q, kind);
-            return fail(-1, "%s", msg.c_str());
-        }
+        if ((rc = measure_tail(c, m.clk, &m.stats[GXS_K_MEASURE], m.word64.p, w, 2, m.h_len, m.len.p, "l2r_gtftext_blocks", "block", GTX_E_N, gtx_block_fail, &bytes, [&] {
+                const dim3 grid((unsigned)(((wave ? M * 64 : M) + 255) / 256));
+                if (wave) hipLaunchKernelGGL(k_gtx_measure<true>, grid, dim3(256), 0, c->stream, in, meas);
+                else hipLaunchKernelGGL(k_gtx_measure<false>, grid, dim3(256), 0, c->stream, in, meas);
+            }))) return rc;
         lines = w[1];
-        for (size_t q = 0; q < M; ++q) bytes += m.h_len[q];
     }
     m.have_blocks = true;
     *n_lines = (int64_t)lines; *n_bytes = (int64_t)bytes;
@@ -3237,50 +3380,25 @@ int l2r_gtftext_lines(l2r_ctx *c, int64_t first, int64_t max_blocks, int64_t max
     int64_t take = 0, sum = 0;
     {   std::string msg;
         if (gtx_cut(m.h_len.data(), m.m, first, max_blocks, max_bytes, &take, &sum, msg)) return fail(GTX_E_ARG, "%s", msg.c_str()); }
-    const size_t B = (size_t)sum, K = (size_t)take;
-    m.stats[GXS_LINES] = 0; m.stats[GXS_BYTES] = 0; m.stats[GXS_TILES_LDS] = 0; m.stats[GXS_TILES_DIRECT] = 0;
-    if (m.on_host) {
-        l2r_gtx_rows hr; GtxChains cx; l2r_gtx_blocks hb;
-        gtx_host_view(m, hr, cx, hb);
-        std::string msg;
-        int64_t lines = 0;
-        if (list ? rl_text_host(&m.prm, &m.rl.anno, rl_host_view(m), m.rl.h.sel, first, take, m.out.host_text, &lines, msg)
-                 : gtx_text_host(&m.prm, &hr, cx, &hb, first, take, m.out.host_text, &lines, msg)) { m.out.host_text.clear(); return fail(-1, "%s", msg.c_str()); }
-        if (m.out.host_text.size() != B) return fail(-5, "[l2r_gtftext_lines] %zu bytes of text, measured %zu", m.out.host_text.size(), B);
-        m.out.take_host();
-        m.stats[GXS_LINES] = (double)lines; m.stats[GXS_BYTES] = (double)B; m.stats[GXS_BATCHES] += 1;
-        *n_taken = take; *n_bytes = sum;
-        return 0;
-    }
-    if (!list && m.run_chains && c->n_reads != m.n) return fail(GTX_E_ARG, "[l2r_gtftext_lines] the rows stand for a run of %lld reads, the context now holds %lld", (long long)m.n, (long long)c->n_reads);
-    if (list && m.rl.run_res && (c->n_reads != m.rl.n || !c->ran)) return fail(GTX_E_ARG, "[l2r_gtftext_lines] the reads stand for a run of %lld reads, the context now holds %lld", (long long)m.rl.n, (long long)c->n_reads);
-    HIP_TRY(hipSetDevice(c->device));
-    int rc;
-    if ((rc = m.clk.begin(env_on("L2R_GTX_TIMING"), c->check_stages))) return rc;
-    if (m.off.ensure(K + 1) || m.out.reserve(B) || m.word.ensure(GTXC_TOTAL + 1)) return -2;
-    uint8_t *text8 = m.out.bytes();
-    HIP_TRY(hipMemcpyAsync(m.off.p, m.len.p + first, K * 4, hipMemcpyDeviceToDevice, c->stream));
-    HIP_TRY(hipMemsetAsync(m.word.p, 0, (GTXC_TOTAL + 1) * sizeof(uint32_t), c->stream));
-    if ((rc = m.clk.launch(c, &m.stats[GXS_K_SCAN], [&] { scan_u32(c, m.off.p, (int64_t)K, m.word.p + GTXC_TOTAL); }))) { (void)hipStreamSynchronize(c->stream); return rc; }
-    HIP_TRY(m.out.arm_guard(c, B));
-    const unsigned n_tiles = (unsigned)((K + GTX_TILE - 1) / GTX_TILE);
-    const GtxIn in = gtx_in(c, m);
-    const RlIn lin = rl_in(c, m);
-    if ((rc = m.clk.launch(c, &m.stats[GXS_K_WRITE], [&] {
-            if (list) hipLaunchKernelGGL(k_rl_write, dim3(n_tiles), dim3(GTX_THREADS), 0, c->stream, lin, first, take, (const uint32_t *)m.off.p, (const uint32_t *)m.fix.p, (const uint32_t *)m.rl.hfix.p, text8, m.word.p);
-            else hipLaunchKernelGGL(k_gtx_write, dim3(n_tiles), dim3(GTX_THREADS), 0, c->stream, in, first, take, (const uint32_t *)m.off.p, (const uint32_t *)m.fix.p, text8, m.word.p);
-        }))) { (void)hipStreamSynchronize(c->stream); return rc; }
+    const ReadRows &rr = m.rl.reads;
+    if (!m.on_host && !list && m.run_chains && c->n_reads != m.n) return fail(GTX_E_ARG, "[l2r_gtftext_lines] the rows stand for a run of %lld reads, the context now holds %lld", (long long)m.n, (long long)c->n_reads);
+    if (!m.on_host && list && rr.run_res && (c->n_reads != rr.n || !c->ran)) return fail(GTX_E_ARG, "[l2r_gtftext_lines] the reads stand for a run of %lld reads, the context now holds %lld", (long long)rr.n, (long long)c->n_reads);
+    static const TextBatch batch{"l2r_gtftext_lines", "L2R_GTX_TIMING", "lines would have left their tile's span: k_gtx_measure and k_gtx_write disagree", GTX_TILE, GTXC_TOTAL, GTXC_OUTSIDE, GTXC_DIRECT};
+    int64_t host_lines = 0;
     uint32_t w[GTXC_TOTAL + 1] = {0};
-    HIP_TRY(hipMemcpyAsync(w, m.word.p, sizeof w, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(m.out.fetch_guard(c, B));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    if (!m.out.guard_intact(c)) m.stats[GXS_GUARD] = 0;
-    if ((size_t)w[GTXC_TOTAL] != B) return fail(-5, "[l2r_gtftext_lines] the scan left %u bytes, the cut %zu", w[GTXC_TOTAL], B);
-    if (w[GTXC_OUTSIDE]) return fail(-5, "[l2r_gtftext_lines] %u lines would have left their tile's span: k_gtx_measure and k_gtx_write disagree", w[GTXC_OUTSIDE]);
-    if (w[GTXC_DIRECT] > n_tiles) return fail(-5, "[l2r_gtftext_lines] %u direct tiles of %u", w[GTXC_DIRECT], n_tiles);
-    m.stats[GXS_LINES] = (double)w[GTXC_LINES]; m.stats[GXS_BYTES] = (double)B; m.stats[GXS_BATCHES] += 1;
-    m.stats[GXS_TILES_DIRECT] = (double)w[GTXC_DIRECT]; m.stats[GXS_TILES_LDS] = (double)(n_tiles - w[GTXC_DIRECT]);
-    m.out.take_device(B);
+    const int rc = text_batch(c, batch, m.out, m.clk, m.len, m.off, m.word, m.stats, m.on_host, first, take, sum, w,
+        [&](std::vector<uint8_t> &text, std::string &msg) {
+            if (list) return rl_text_host(&m.prm, &m.rl.anno, rl_host_view(m), m.rl.h_sel, first, take, text, &host_lines, msg);
+            l2r_gtx_rows hr; GtxChains cx; l2r_gtx_blocks hb;
+            gtx_host_view(m, hr, cx, hb);
+            return gtx_text_host(&m.prm, &hr, cx, &hb, first, take, text, &host_lines, msg);
+        },
+        [&](unsigned n_tiles, uint8_t *text) {
+            if (list) hipLaunchKernelGGL(k_rl_write, dim3(n_tiles), dim3(GTX_THREADS), 0, c->stream, rl_in(c, m), first, take, (const uint32_t *)m.off.p, (const uint32_t *)m.fix.p, (const uint32_t *)m.rl.hfix.p, text, m.word.p);
+            else hipLaunchKernelGGL(k_gtx_write, dim3(n_tiles), dim3(GTX_THREADS), 0, c->stream, gtx_in(c, m), first, take, (const uint32_t *)m.off.p, (const uint32_t *)m.fix.p, text, m.word.p);
+        });
+    if (rc) return rc;
+    m.stats[GXS_LINES] = m.on_host ? (double)host_lines : (double)w[GTXC_LINES];
     *n_taken = take; *n_bytes = sum;
     return 0;
 }
@@ -3304,15 +3422,10 @@ int l2r_gtftext_anno(l2r_ctx *c, const l2r_gtx_anno *a)
     if (m.prm.form != L2R_GTX_READ) return fail(GTX_E_ARG, "[l2r_gtftext_anno] the read lists are blocks of form READ, l2r_gtftext_begin had form %d", m.prm.form);
     {   std::string msg;
         if (rl_check_anno(a, msg)) return fail(GTX_E_ARG, "%s", msg.c_str()); }
-    const size_t T = (size_t)a->n_tx, A = (size_t)a->anno_names_len;
-    l.h_anno.assign(A + 1, 0);
-    if (A) memcpy(l.h_anno.data(), a->anno_names, A);
-    l.h_gid.assign(T + 1, 0); l.h_gname.assign(T + 1, 0);
-    if (T) { memcpy(l.h_gid.data(), a->tx_gid, T * 4); memcpy(l.h_gname.data(), a->tx_gname, T * 4); }
-    l.anno = l2r_gtx_anno{a->n_tx, a->anno_names_len, l.h_anno.data(), l.h_gid.data(), l.h_gname.data()};
+    l.genes.set(a->n_tx, a->anno_names_len, a->anno_names, a->tx_gid, a->tx_gname);
+    l.anno = l2r_gtx_anno{a->n_tx, a->anno_names_len, l.genes.h_names.data(), l.genes.h_gid.data(), l.genes.h_gname.data()};
     HIP_TRY(hipSetDevice(c->device));
-    int rc;
-    if ((rc = put_dev(c, l.d_anno, l.h_anno)) || (rc = put_dev(c, l.d_gid, l.h_gid)) || (rc = put_dev(c, l.d_gname, l.h_gname))) { (void)hipStreamSynchronize(c->stream); return rc; }
+    if (int rc = l.genes.upload(c)) { (void)hipStreamSynchronize(c->stream); return rc; }
     HIP_TRY(hipStreamSynchronize(c->stream));
     l.have_anno = true;
     return 0;
@@ -3327,52 +3440,12 @@ int l2r_gtftext_reads(l2r_ctx *c, const l2r_gtx_reads *r)
     if (!l.have_anno) return fail(GTX_E_ARG, "[l2r_gtftext_reads] no l2r_gtftext_anno in front");
     {   std::string msg;
         if (rl_check_reads(r, msg)) return fail(GTX_E_ARG, "%s", msg.c_str()); }
-    const char *route = getenv("L2R_GTX_ROUTE");
-    m.on_host = route && strcmp(route, "host") == 0;
+    m.on_host = route_is_host("L2R_GTX_ROUTE");
     m.stats[GXS_ROUTE] = m.on_host ? 1 : 0;
-    const size_t N = (size_t)r->n, NL = (size_t)r->names_len;
-    l.n = r->n; l.names_len = r->names_len; l.run_res = !r->res; l.has_sj = r->has_sj != 0; l.split = r->split != 0;
-    l.exons_per_read = 0;
+    l.has_sj = r->has_sj != 0; l.split = r->split != 0;
     HIP_TRY(hipSetDevice(c->device));
-    int rc = 0;
-    if (l.run_res) {
-        if (!c->ran) return fail(GTX_E_ARG, "[l2r_gtftext_reads] no completed run on this context");
-        if ((rc = fetch_totals(c))) return rc;
-        if (!(c->want & L2R_WANT_RESULTS)) return fail(GTX_E_ARG, "[l2r_gtftext_reads] the last run kept no results (l2r_set_outputs without L2R_WANT_RESULTS)");
-        if (r->n != c->n_reads) return fail(GTX_E_ARG, "[l2r_gtftext_reads] %lld reads, the last run had %lld reads", (long long)r->n, (long long)c->n_reads);
-        if (N) l.exons_per_read = (double)c->h_totals[0] / (double)N;
-    } else if (N) l.exons_per_read = (double)r->res->n_exons / (double)N;
-    const l2r_result *s = r->res;
-    const uint32_t *tid_name = r->tid_name ? r->tid_name : r->qname;
-    if (m.on_host) {
-        GtxState::Lists::Host &h = l.h;
-        h.tid.assign(r->tid, r->tid + N); h.qname.assign(r->qname, r->qname + N); h.tid_name.assign(tid_name, tid_name + N); h.names.assign(r->names, r->names + NL);
-        const size_t X = l.run_res ? (size_t)c->h_totals[0] : (size_t)s->n_exons;
-        h.ex_off.assign(N + 1, 0); h.info.assign(N ? N : 1, 0u); h.ref_tx.assign(N ? N : 1, 0); h.xs.assign(X ? X : 1, 0); h.xe.assign(X ? X : 1, 0); h.f.assign(X ? X : 1, 0);
-        if (l.run_res) {
-            l2r_result res{(int64_t)N, (int64_t)X, (int64_t)X, h.ex_off.data(), h.xs.data(), h.xe.data(), h.f.data(), h.info.data(), h.ref_tx.data()};
-            if (N && (rc = l2r_download(c, &res))) return rc;
-        } else if (N) {
-            memcpy(h.ex_off.data(), s->ex_off, (N + 1) * 8); memcpy(h.info.data(), s->info, N * 4); memcpy(h.ref_tx.data(), s->ref_tx, N * 4);
-            if (X) { memcpy(h.xs.data(), s->ex_start, X * 4); memcpy(h.xe.data(), s->ex_end, X * 4); memcpy(h.f.data(), s->ex_flag, X); }
-        }
-        l.have_reads = true;
-        return 0;
-    }
-    std::vector<uint32_t> off32;
-    if ((rc = to_dev(c, l.tid, r->tid, N)) || (rc = to_dev(c, l.qname, r->qname, N)) || (rc = to_dev(c, l.names, r->names, NL))) {}
-    l.tid_name_p = l.qname.p;
-    if (!rc && r->tid_name && r->tid_name != r->qname) { rc = to_dev(c, l.tid_name, r->tid_name, N); l.tid_name_p = l.tid_name.p; }
-    if (!rc && !l.run_res) {
-        const size_t X = (size_t)s->n_exons;
-        off32.resize(N);
-        for (size_t i = 0; i < N; ++i) off32[i] = (uint32_t)s->ex_off[i];
-        if ((rc = put_dev(c, l.ex_off, off32)) || (rc = to_dev(c, l.info, (const uint32_t *)s->info, N)) || (rc = to_dev(c, l.ref_tx, (const int32_t *)s->ref_tx, N)) ||
-            (rc = to_dev(c, l.xs, (const int32_t *)s->ex_start, X)) || (rc = to_dev(c, l.xe, (const int32_t *)s->ex_end, X)) || (rc = to_dev(c, l.f, (const uint8_t *)s->ex_flag, X))) {}
-    }
-    const hipError_t sync = hipStreamSynchronize(c->stream);           // (the columns are the caller's)
-    if (rc) return rc;
-    if (sync != hipSuccess) return fail(-2, "[l2r_gtftext_reads] %s", hipGetErrorString(sync));
+    if (int rc = take_reads(c, l.reads, *r, m.on_host, "l2r_gtftext_reads", GTX_E_ARG, "reads")) return rc;
+    if (!m.on_host) HIP_TRY(hipStreamSynchronize(c->stream));       // (the columns are the caller's)
     l.have_reads = true;
     return 0;
 }
@@ -3391,22 +3464,22 @@ int l2r_gtftext_list(l2r_ctx *c, int list, int64_t *n_blocks, int64_t *n_lines, 
         if (rl_check_list(list, msg)) return fail(GTX_E_ARG, "%s", msg.c_str()); }
     l.list = list; l.n_pieces = 0;
     m.m = 0; m.h_len.clear();
-    const size_t N = (size_t)l.n;
+    const size_t N = (size_t)l.reads.n;
     uint64_t lines = 0, bytes = 0;
     if (m.on_host) {
         const RlReads hr = rl_host_view(m);
-        rl_select(hr, list, l.h.sel);
-        const size_t M = (size_t)l.h.sel.m();
-        m.m = (int64_t)M; l.n_pieces = l.h.sel.n_pieces;
+        rl_select(hr, list, l.h_sel);
+        const size_t M = (size_t)l.h_sel.m();
+        m.m = (int64_t)M; l.n_pieces = l.h_sel.n_pieces;
         m.h_len.assign(M, 0u);
         for (size_t q = 0; q < M; ++q) {
             uint64_t by = 0, nl = 0;
-            const int kind = rl_block_bytes(&m.prm, &l.anno, hr, l.h.sel, (int64_t)q, &by, &nl);
+            const int kind = rl_block_bytes(&m.prm, &l.anno, hr, l.h_sel, (int64_t)q, &by, &nl);
             if (kind) { std::string msg; rl_block_fail(msg, (int64_t)q, kind); return fail(-1, "%s", msg.c_str()); }
             m.h_len[q] = (uint32_t)by; lines += nl; bytes += by;
         }
     } else if (N) {
-        if (l.run_res && (c->n_reads != l.n || !c->ran)) return fail(GTX_E_ARG, "[l2r_gtftext_list] the reads stand for a run of %lld reads, the context now holds %lld", (long long)l.n, (long long)c->n_reads);
+        if (l.reads.run_res && (c->n_reads != l.reads.n || !c->ran)) return fail(GTX_E_ARG, "[l2r_gtftext_list] the reads stand for a run of %lld reads, the context now holds %lld", (long long)l.reads.n, (long long)c->n_reads);
         HIP_TRY(hipSetDevice(c->device));
         int rc;
         if ((rc = m.clk.begin(env_on("L2R_GTX_TIMING"), c->check_stages))) return rc;
@@ -3430,26 +3503,16 @@ int l2r_gtftext_list(l2r_ctx *c, int list, int64_t *n_blocks, int64_t *n_lines, 
             if ((rc = m.clk.launch(c, &m.stats[GXS_K_SELECT], [&] {
                     hipLaunchKernelGGL(k_rl_take, per_read, dim3(256), 0, c->stream, in, (const uint32_t *)l.cnt.p, l.b_read.p, l.b_first.p, l.b_count.p, l.b_piece.p);
                 }))) { (void)hipStreamSynchronize(c->stream); return rc; }
-            const bool wave = wave_form(l.exons_per_read, "L2R_GTX_WAVE");     // (exons per read: the lists are not looked at)
+            const bool wave = wave_form(l.reads.exons_per_read, "L2R_GTX_WAVE");       // (exons per read: the lists are not looked at)
             m.stats[GXS_WAVE] = wave ? 1 : 0;
-            HIP_TRY(hipMemsetAsync(m.word64.p, 0xff, sizeof(unsigned long long), c->stream));
-            HIP_TRY(hipMemsetAsync(m.word64.p + 1, 0, sizeof(unsigned long long), c->stream));
             const RlMeasure meas{m.len.p, m.fix.p, l.hfix.p, m.word64.p, m.word64.p + 1};
-            rc = m.clk.launch(c, &m.stats[GXS_K_MEASURE], [&] {
-                const dim3 grid((unsigned)(((wave ? M * 64 : M) + 255) / 256));
-                if (wave) hipLaunchKernelGGL(k_rl_measure<true>, grid, dim3(256), 0, c->stream, in, meas);
-                else hipLaunchKernelGGL(k_rl_measure<false>, grid, dim3(256), 0, c->stream, in, meas);
-            });
             unsigned long long w[2] = {0, 0};
-            if ((rc = download_all(c, rc, {{w, m.word64.p, sizeof w}, {m.h_len.data(), m.len.p, M * 4}}, "l2r_gtftext_list"))) return rc;
-            if (w[0] != ~0ull) {
-                const unsigned long long q = w[0] >> 4; const int kind = (int)(w[0] & 15ull);
-                if (q >= M || kind <= RL_OK || kind >= RL_E_N) return fail(-2, "[l2r_gtftext_list] the device names block %llu of %zu, kind %d", q, M, kind);
-                std::string msg; rl_block_fail(msg, (int64_t)q, kind);
-                return fail(-1, "%s", msg.c_str());
-            }
+            if ((rc = measure_tail(c, m.clk, &m.stats[GXS_K_MEASURE], m.word64.p, w, 2, m.h_len, m.len.p, "l2r_gtftext_list", "block", RL_E_N, rl_block_fail, &bytes, [&] {
+                    const dim3 grid((unsigned)(((wave ? M * 64 : M) + 255) / 256));
+                    if (wave) hipLaunchKernelGGL(k_rl_measure<true>, grid, dim3(256), 0, c->stream, in, meas);
+                    else hipLaunchKernelGGL(k_rl_measure<false>, grid, dim3(256), 0, c->stream, in, meas);
+                }))) return rc;
             lines = w[1];
-            for (size_t q = 0; q < M; ++q) bytes += m.h_len[q];
         }
     }
     m.stats[GXS_BLOCKS] = (double)m.m; m.stats[GXS_PIECES] = (double)l.n_pieces;
@@ -3467,7 +3530,7 @@ int l2r_gtftext_list_out(l2r_ctx *c, int32_t *read, int32_t *first, int32_t *cou
     const size_t M = (size_t)m.m;
     if (!M) return 0;
     if (m.on_host) {
-        const RlSel &s = l.h.sel;
+        const RlSel &s = l.h_sel;
         if (read) memcpy(read, s.read.data(), M * 4); if (first) memcpy(first, s.first.data(), M * 4);
         if (count) memcpy(count, s.count.data(), M * 4); if (piece) memcpy(piece, s.piece.data(), M * 4);
         return 0;
@@ -3481,6 +3544,7 @@ int l2r_gtftext_list_out(l2r_ctx *c, int32_t *read, int32_t *first, int32_t *cou
 // slots of l2r_detail_stats
 enum { DTS_ROWS = 0, DTS_LINES, DTS_BYTES, DTS_WAVE, DTS_TILES_LDS, DTS_TILES_DIRECT, DTS_ROUTE, DTS_GUARD, DTS_BATCHES, DTS_K_MEASURE, DTS_K_SCAN, DTS_K_WRITE, DTS_N };
 static_assert(DTS_N == sizeof(DetailState::stats) / sizeof(double) && DTS_K_MEASURE == 9, "l2r_detail_stats: the words of include/lr2rmats_hip.h");
+static_assert(DTS_LINES == TXS_LINES && DTS_K_WRITE == TXS_K_WRITE && GXS_LINES == TXS_LINES && GXS_K_WRITE == TXS_K_WRITE, "text_batch: the slots of a batch are the same words in both");
 constexpr int DETC_TOTAL = DETC_N;                      // DetailState::word: k_detail_write's counters, then the scan's total
 constexpr int DETAIL_E_ARG = -4;                        // arguments, order of calls: not -1, which is a domain error (the command falls back on it)
 
@@ -3493,17 +3557,13 @@ int l2r_detail_begin(l2r_ctx *c, const l2r_detail_params *p)
     {   std::string msg;
         if (detail_check_params(p, msg)) return fail(DETAIL_E_ARG, "%s", msg.c_str()); }
     m.ref.set(p->n_ref, p->ref_off, p->ref_names);
-    const size_t T = (size_t)p->n_tx, A = (size_t)p->anno_names_len;
-    m.h_anno.assign(A + 1, 0);
-    if (A) memcpy(m.h_anno.data(), p->anno_names, A);
-    m.h_gid.assign(T + 1, 0); m.h_gname.assign(T + 1, 0);
-    if (T) { memcpy(m.h_gid.data(), p->tx_gid, T * 4); memcpy(m.h_gname.data(), p->tx_gname, T * 4); }
+    m.genes.set(p->n_tx, p->anno_names_len, p->anno_names, p->tx_gid, p->tx_gname);
     m.prm = *p;
     m.prm.ref_off = m.ref.h_off.data(); m.prm.ref_names = m.ref.h_names.data();
-    m.prm.anno_names = m.h_anno.data(); m.prm.tx_gid = m.h_gid.data(); m.prm.tx_gname = m.h_gname.data();
+    m.prm.anno_names = m.genes.h_names.data(); m.prm.tx_gid = m.genes.h_gid.data(); m.prm.tx_gname = m.genes.h_gname.data();
     HIP_TRY(hipSetDevice(c->device));
     int rc;
-    if ((rc = m.ref.upload(c)) || (rc = put_dev(c, m.anno, m.h_anno)) || (rc = put_dev(c, m.tx_gid, m.h_gid)) || (rc = put_dev(c, m.tx_gname, m.h_gname))) { (void)hipStreamSynchronize(c->stream); return rc; }
+    if ((rc = m.ref.upload(c)) || (rc = m.genes.upload(c))) { (void)hipStreamSynchronize(c->stream); return rc; }
     HIP_TRY(hipStreamSynchronize(c->stream));
     m.begun = true;
     return 0;
@@ -3513,18 +3573,19 @@ int l2r_detail_begin(l2r_ctx *c, const l2r_detail_params *p)
 static DetailIn detail_in(const l2r_ctx *c, const DetailState &m)
 {
     DetailIn in{};
-    in.n = m.n; in.tid = m.tid.p; in.names = m.names.p; in.names_len = m.names_len; in.qname = m.qname.p;
-    if (m.run_res) { in.ex_off = c->ex_off.p; in.info = c->info.p; in.xs = c->ex_start.p; in.xe = c->ex_end.p; in.ref_tx = c->ref_tx.p; in.f = c->ex_flag.p; }
-    else { in.ex_off = m.ex_off.p; in.info = m.info.p; in.xs = m.xs.p; in.xe = m.xe.p; in.ref_tx = m.ref_tx.p; in.f = m.f.p; }
+    const ReadRows &r = m.rows;
+    const ResultCols v = result_cols(c, r);
+    in.n = r.n; in.tid = r.tid.p; in.names = r.names.p; in.names_len = r.names_len; in.qname = r.qname.p;
+    in.ex_off = v.ex_off; in.info = v.info; in.xs = v.xs; in.xe = v.xe; in.ref_tx = v.ref_tx; in.f = v.f;
     in.n_ref = m.prm.n_ref; in.ref_off = m.ref.off.p; in.ref_names = m.ref.names.p;
-    in.n_tx = m.prm.n_tx; in.anno_names_len = m.prm.anno_names_len; in.anno_names = m.anno.p; in.tx_gid = m.tx_gid.p; in.tx_gname = m.tx_gname.p;
+    in.n_tx = m.prm.n_tx; in.anno_names_len = m.prm.anno_names_len; in.anno_names = m.genes.names.p; in.tx_gid = m.genes.gid.p; in.tx_gname = m.genes.gname.p;
     return in;
 }
 // ... and the host route's, over its copies
 static l2r_detail_reads detail_host_view(const DetailState &m)
 {
-    const DetailState::Host &h = m.h;
-    return l2r_detail_reads{m.n, h.tid.data(), m.names_len, h.names.data(), h.qname.data(), &h.res};
+    const ReadRows::Host &h = m.rows.h;
+    return l2r_detail_reads{m.rows.n, h.tid.data(), m.rows.names_len, h.names.data(), h.qname.data(), &h.res};
 }
 
 int l2r_detail_rows(l2r_ctx *c, const l2r_detail_reads *r, int64_t *n_bytes)
@@ -3536,38 +3597,20 @@ int l2r_detail_rows(l2r_ctx *c, const l2r_detail_reads *r, int64_t *n_bytes)
     if (!m.begun) return fail(DETAIL_E_ARG, "[l2r_detail_rows] no l2r_detail_begin in front");
     {   std::string msg;
         if (detail_check_rows(r, msg)) return fail(DETAIL_E_ARG, "%s", msg.c_str()); }
-    const char *route = getenv("L2R_DETAIL_ROUTE");
-    m.on_host = route && strcmp(route, "host") == 0;
+    m.on_host = route_is_host("L2R_DETAIL_ROUTE");
     for (int k = 0; k < DTS_N; ++k) m.stats[k] = 0;
     m.stats[DTS_ROUTE] = m.on_host ? 1 : 0; m.stats[DTS_GUARD] = 1;
-    const size_t N = (size_t)r->n, NL = (size_t)r->names_len;
-    m.n = r->n; m.names_len = r->names_len; m.run_res = !r->res;
+    const size_t N = (size_t)r->n;
     m.stats[DTS_ROWS] = (double)N;
     m.h_len.assign(N, 0u);
     HIP_TRY(hipSetDevice(c->device));
-    int rc = 0;
-    double exons_per_row = 0;
-    if (m.run_res) {
-        if (!c->ran) return fail(DETAIL_E_ARG, "[l2r_detail_rows] no completed run on this context");
-        if ((rc = fetch_totals(c))) return rc;
-        if (!(c->want & L2R_WANT_RESULTS)) return fail(DETAIL_E_ARG, "[l2r_detail_rows] the last run kept no results (l2r_set_outputs without L2R_WANT_RESULTS)");
-        if (r->n != c->n_reads) return fail(DETAIL_E_ARG, "[l2r_detail_rows] %lld rows, the last run had %lld reads", (long long)r->n, (long long)c->n_reads);
-        if (N) exons_per_row = (double)c->h_totals[0] / (double)N;
-    } else if (N) exons_per_row = (double)r->res->n_exons / (double)N;
+    int rc;
+    const l2r_gtx_reads reads{r->n, r->tid, r->names_len, r->names, r->qname, nullptr, r->res, 0, 0};
+    if ((rc = take_reads(c, m.rows, reads, m.on_host, "l2r_detail_rows", DETAIL_E_ARG, "rows"))) return rc;
+    if (N == 0 && !m.on_host) HIP_TRY(hipStreamSynchronize(c->stream));     // (no rows, but take_reads queues a names table where one came: the caller's)
     if (N == 0) { m.have_rows = true; return 0; }
-    const l2r_result *s = r->res;
     uint64_t bytes = 0;
     if (m.on_host) {
-        DetailState::Host &h = m.h;
-        h.tid.assign(r->tid, r->tid + N); h.qname.assign(r->qname, r->qname + N); h.names.assign(r->names, r->names + NL);
-        const size_t X = m.run_res ? (size_t)c->h_totals[0] : (size_t)s->n_exons;
-        h.ex_off.assign(N + 1, 0); h.info.assign(N, 0u); h.ref_tx.assign(N, 0); h.xs.assign(X ? X : 1, 0); h.xe.assign(X ? X : 1, 0); h.f.assign(X ? X : 1, 0);
-        h.res = l2r_result{(int64_t)N, (int64_t)X, (int64_t)X, h.ex_off.data(), h.xs.data(), h.xe.data(), h.f.data(), h.info.data(), h.ref_tx.data()};
-        if (m.run_res) { if ((rc = l2r_download(c, &h.res))) return rc; }
-        else {
-            memcpy(h.ex_off.data(), s->ex_off, (N + 1) * 8); memcpy(h.info.data(), s->info, N * 4); memcpy(h.ref_tx.data(), s->ref_tx, N * 4);
-            if (X) { memcpy(h.xs.data(), s->ex_start, X * 4); memcpy(h.xe.data(), s->ex_end, X * 4); memcpy(h.f.data(), s->ex_flag, X); }
-        }
         const l2r_detail_reads hr = detail_host_view(m);
         for (size_t i = 0; i < N; ++i) {
             uint64_t by = 0; uint32_t split[DETAIL_SPLIT];
@@ -3576,37 +3619,18 @@ int l2r_detail_rows(l2r_ctx *c, const l2r_detail_reads *r, int64_t *n_bytes)
             m.h_len[i] = (uint32_t)by; bytes += by;
         }
     } else {
-        if ((rc = m.clk.begin(env_on("L2R_DETAIL_TIMING"), c->check_stages))) return rc;
-        const bool wave = wave_form(exons_per_row, "L2R_DETAIL_WAVE");
+        const bool wave = wave_form(m.rows.exons_per_read, "L2R_DETAIL_WAVE");
         m.stats[DTS_WAVE] = wave ? 1 : 0;
-        std::vector<uint32_t> off32;
-        if ((rc = to_dev(c, m.tid, r->tid, N)) || (rc = to_dev(c, m.qname, r->qname, N)) || (rc = to_dev(c, m.names, r->names, NL))) {}
-        if (!rc && !m.run_res) {
-            const size_t X = (size_t)s->n_exons;
-            off32.resize(N);
-            for (size_t i = 0; i < N; ++i) off32[i] = (uint32_t)s->ex_off[i];
-            if ((rc = put_dev(c, m.ex_off, off32)) || (rc = to_dev(c, m.info, (const uint32_t *)s->info, N)) || (rc = to_dev(c, m.ref_tx, (const int32_t *)s->ref_tx, N)) ||
-                (rc = to_dev(c, m.xs, (const int32_t *)s->ex_start, X)) || (rc = to_dev(c, m.xe, (const int32_t *)s->ex_end, X)) || (rc = to_dev(c, m.f, (const uint8_t *)s->ex_flag, X))) {}
-        }
-        if (!rc && (m.len.ensure(N) || m.split.ensure(N * DETAIL_SPLIT) || m.word64.ensure(1) || m.word.ensure(DETC_TOTAL + 1))) rc = -2;
+        if ((rc = m.clk.begin(env_on("L2R_DETAIL_TIMING"), c->check_stages)) || m.len.ensure(N) || m.split.ensure(N * DETAIL_SPLIT) || m.word64.ensure(1) || m.word.ensure(DETC_TOTAL + 1)) rc = rc ? rc : -2;
         if (rc) { (void)hipStreamSynchronize(c->stream); return rc; }  // (the columns are the caller's)
-        HIP_TRY(hipMemsetAsync(m.word64.p, 0xff, sizeof(unsigned long long), c->stream));
         const DetailIn in = detail_in(c, m);
         const DetailMeasure meas{m.len.p, m.split.p, m.word64.p};
-        rc = m.clk.launch(c, &m.stats[DTS_K_MEASURE], [&] {
-            const dim3 grid((unsigned)(((wave ? N * 64 : N) + 255) / 256));
-            if (wave) hipLaunchKernelGGL(k_detail_measure<true>, grid, dim3(256), 0, c->stream, in, meas);
-            else hipLaunchKernelGGL(k_detail_measure<false>, grid, dim3(256), 0, c->stream, in, meas);
-        });
         unsigned long long w = 0;
-        if ((rc = download_all(c, rc, {{&w, m.word64.p, sizeof w}, {m.h_len.data(), m.len.p, N * 4}}, "l2r_detail_rows"))) return rc;
-        if (w != ~0ull) {
-            const unsigned long long i = w >> 4; const int kind = (int)(w & 15ull);
-            if (i >= N || kind <= DET_OK || kind >= DET_E_N) return fail(-2, "[l2r_detail_rows] the device names read %llu of %zu, kind %d", i, N, kind);
-            std::string msg; detail_row_fail(msg, (int64_t)i, kind);
-            return fail(-1, "%s", msg.c_str());
-        }
-        for (size_t i = 0; i < N; ++i) bytes += m.h_len[i];
+        if ((rc = measure_tail(c, m.clk, &m.stats[DTS_K_MEASURE], m.word64.p, &w, 1, m.h_len, m.len.p, "l2r_detail_rows", "read", DET_E_N, detail_row_fail, &bytes, [&] {
+                const dim3 grid((unsigned)(((wave ? N * 64 : N) + 255) / 256));
+                if (wave) hipLaunchKernelGGL(k_detail_measure<true>, grid, dim3(256), 0, c->stream, in, meas);
+                else hipLaunchKernelGGL(k_detail_measure<false>, grid, dim3(256), 0, c->stream, in, meas);
+            }))) return rc;
     }
     m.have_rows = true;
     *n_bytes = (int64_t)bytes;
@@ -3622,45 +3646,18 @@ int l2r_detail_lines(l2r_ctx *c, int64_t first, int64_t max_rows, int64_t max_by
     if (!m.have_rows) return fail(DETAIL_E_ARG, "[l2r_detail_lines] no l2r_detail_rows in front, or it failed");
     int64_t take = 0, sum = 0;
     {   std::string msg;
-        if (detail_cut(m.h_len.data(), m.n, first, max_rows, max_bytes, &take, &sum, msg)) return fail(DETAIL_E_ARG, "%s", msg.c_str()); }
-    const size_t B = (size_t)sum, K = (size_t)take;
-    m.stats[DTS_LINES] = 0; m.stats[DTS_BYTES] = 0; m.stats[DTS_TILES_LDS] = 0; m.stats[DTS_TILES_DIRECT] = 0;
-    if (m.on_host) {
-        const l2r_detail_reads hr = detail_host_view(m);
-        std::string msg;
-        if (detail_text_host(&m.prm, &hr, first, take, m.out.host_text, msg)) { m.out.host_text.clear(); return fail(-1, "%s", msg.c_str()); }
-        if (m.out.host_text.size() != B) return fail(-5, "[l2r_detail_lines] %zu bytes of text, measured %zu", m.out.host_text.size(), B);
-        m.out.take_host();
-        m.stats[DTS_LINES] = (double)K; m.stats[DTS_BYTES] = (double)B; m.stats[DTS_BATCHES] += 1;
-        *n_taken = take; *n_bytes = sum;
-        return 0;
-    }
-    if (m.run_res && (c->n_reads != m.n || !c->ran)) return fail(DETAIL_E_ARG, "[l2r_detail_lines] the rows stand for a run of %lld reads, the context now holds %lld", (long long)m.n, (long long)c->n_reads);
-    HIP_TRY(hipSetDevice(c->device));
-    int rc;
-    if ((rc = m.clk.begin(env_on("L2R_DETAIL_TIMING"), c->check_stages))) return rc;
-    if (m.off.ensure(K + 1) || m.out.reserve(B) || m.word.ensure(DETC_TOTAL + 1)) return -2;
-    uint8_t *text8 = m.out.bytes();
-    HIP_TRY(hipMemcpyAsync(m.off.p, m.len.p + first, K * 4, hipMemcpyDeviceToDevice, c->stream));
-    HIP_TRY(hipMemsetAsync(m.word.p, 0, (DETC_TOTAL + 1) * sizeof(uint32_t), c->stream));
-    if ((rc = m.clk.launch(c, &m.stats[DTS_K_SCAN], [&] { scan_u32(c, m.off.p, (int64_t)K, m.word.p + DETC_TOTAL); }))) { (void)hipStreamSynchronize(c->stream); return rc; }
-    HIP_TRY(m.out.arm_guard(c, B));
-    const unsigned n_tiles = (unsigned)((K + DETAIL_TILE - 1) / DETAIL_TILE);
-    const DetailIn in = detail_in(c, m);
-    if ((rc = m.clk.launch(c, &m.stats[DTS_K_WRITE], [&] {
-            hipLaunchKernelGGL(k_detail_write, dim3(n_tiles), dim3(DETAIL_THREADS), 0, c->stream, in, first, take, (const uint32_t *)m.off.p, (const uint32_t *)m.split.p, text8, m.word.p);
-        }))) { (void)hipStreamSynchronize(c->stream); return rc; }
+        if (detail_cut(m.h_len.data(), m.rows.n, first, max_rows, max_bytes, &take, &sum, msg)) return fail(DETAIL_E_ARG, "%s", msg.c_str()); }
+    const ReadRows &rr = m.rows;
+    if (!m.on_host && rr.run_res && (c->n_reads != rr.n || !c->ran)) return fail(DETAIL_E_ARG, "[l2r_detail_lines] the rows stand for a run of %lld reads, the context now holds %lld", (long long)rr.n, (long long)c->n_reads);
+    static const TextBatch batch{"l2r_detail_lines", "L2R_DETAIL_TIMING", "bytes or segments would have left their place: k_detail_measure and k_detail_write disagree", DETAIL_TILE, DETC_TOTAL, DETC_OUTSIDE, DETC_DIRECT};
     uint32_t w[DETC_TOTAL + 1] = {0};
-    HIP_TRY(hipMemcpyAsync(w, m.word.p, sizeof w, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(m.out.fetch_guard(c, B));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    if (!m.out.guard_intact(c)) m.stats[DTS_GUARD] = 0;
-    if ((size_t)w[DETC_TOTAL] != B) return fail(-5, "[l2r_detail_lines] the scan left %u bytes, the cut %zu", w[DETC_TOTAL], B);
-    if (w[DETC_OUTSIDE]) return fail(-5, "[l2r_detail_lines] %u bytes or segments would have left their place: k_detail_measure and k_detail_write disagree", w[DETC_OUTSIDE]);
-    if (w[DETC_DIRECT] > n_tiles) return fail(-5, "[l2r_detail_lines] %u direct tiles of %u", w[DETC_DIRECT], n_tiles);
-    m.stats[DTS_LINES] = (double)K; m.stats[DTS_BYTES] = (double)B; m.stats[DTS_BATCHES] += 1;
-    m.stats[DTS_TILES_DIRECT] = (double)w[DETC_DIRECT]; m.stats[DTS_TILES_LDS] = (double)(n_tiles - w[DETC_DIRECT]);
-    m.out.take_device(B);
+    const int rc = text_batch(c, batch, m.out, m.clk, m.len, m.off, m.word, m.stats, m.on_host, first, take, sum, w,
+        [&](std::vector<uint8_t> &text, std::string &msg) { const l2r_detail_reads hr = detail_host_view(m); return detail_text_host(&m.prm, &hr, first, take, text, msg); },
+        [&](unsigned n_tiles, uint8_t *text) {
+            hipLaunchKernelGGL(k_detail_write, dim3(n_tiles), dim3(DETAIL_THREADS), 0, c->stream, detail_in(c, m), first, take, (const uint32_t *)m.off.p, (const uint32_t *)m.split.p, text, m.word.p);
+        });
+    if (rc) return rc;
+    m.stats[DTS_LINES] = (double)take;
     *n_taken = take; *n_bytes = sum;
     return 0;
 }

@@ -1,8 +1,10 @@
 // l2r_gtftextplan.hip.h -- the host side of l2r_gtftext_* (the GTF block of `bam2gtf` and `unique-gtf`): the argument checks, gtx_block_bytes
-// (the exact bytes and lines of one block, and its domain error), gtx_cut (the batch cut over the measured lengths), the text of a domain
-// error, and gtx_text_host, the exact routine that writes the same bytes on one core (L2R_GTX_ROUTE=host, and the comparator of
-// tools/bench_gtx.py).  Host arithmetic only: no HIP call, no context, no environment.  tests/gtx_dump.hip runs it as a stand-alone
-// program for tests/test_gtf_text_cpu.py.
+// (the exact bytes and lines of one block, and its domain error), the text of a domain error, and gtx_text_host, the exact routine that
+// writes the same bytes on one core (L2R_GTX_ROUTE=host, and the comparator of tools/bench_gtx.py).  In front of them, what the detail
+// table (l2r_detailplan.hip.h) and the read lists (l2r_readlistplan.hip.h) check and cut in the same way, stated once: text_check_ref_off
+// (the walk of a reference-offset table), text_check_genes (the annotation's gene tables), text_check_reads (reads with their results)
+// and batch_cut (the batch cut over the measured lengths).  Host arithmetic only: no HIP call, no context, no environment.
+// tests/gtx_dump.hip runs it as a stand-alone program for tests/test_gtf_text_cpu.py.
 //
 // The rule is stated in include/lr2rmats_hip.h.  What both sides share beyond it: the order in which a block's domain errors are looked for
 // (GTX_E_*: the first that applies is the block's kind; the names in the order gene id, transcript id, gene name, transcript name, each
@@ -56,7 +58,85 @@ static int gtx_fail(std::string &msg, const char *fmt, ...)
 // the one text of a block's domain error, for both routes
 static int gtx_block_fail(std::string &msg, int64_t q, int kind) { return gtx_fail(msg, "[l2r_gtftext_blocks] block %lld: %s", (long long)q, gtx_kind_text(kind)); }
 
-// 0, or -2 (an argument error, not a domain error) and the text of l2r_last_error().  ref_off is walked and the source string read.
+// ---- what the text commands check and cut alike (who: the entry point a message names).  0, or -2 (an argument error, not a domain
+// error) and the text of l2r_last_error().
+
+// The walk of a reference-offset table of n_ref > 0 names, ref_off != NULL: it starts at 0, does not descend, no name is longer than
+// GTX_REF_NAME_MAX, and where there are bytes there is a ref_names.
+static int text_check_ref_off(int32_t n_ref, const int64_t *ref_off, const uint8_t *ref_names, std::string &msg, const char *who)
+{
+    if (ref_off[0] != 0) { gtx_fail(msg, "[%s] ref_off does not start at 0", who); return -2; }
+    for (int32_t k = 0; k < n_ref; ++k) {
+        const int64_t l = ref_off[k + 1] - ref_off[k];
+        if (l < 0) { gtx_fail(msg, "[%s] ref_off descends at name %d", who, k); return -2; }
+        if (l > GTX_REF_NAME_MAX) { gtx_fail(msg, "[%s] reference name %d has %lld bytes (at most %lld)", who, k, (long long)l, (long long)GTX_REF_NAME_MAX); return -2; }
+    }
+    if (ref_off[n_ref] > 0 && !ref_names) { gtx_fail(msg, "[%s] null ref_names", who); return -2; }
+    return 0;
+}
+
+// The annotation's gene tables (l2r_detail_begin, l2r_gtftext_anno): sizes and pointers
+static int text_check_genes(int64_t n_tx, int64_t anno_names_len, const uint8_t *anno_names, const uint32_t *tx_gid, const uint32_t *tx_gname, std::string &msg, const char *who)
+{
+    if (n_tx < 0 || n_tx >= ((int64_t)1 << 31)) { gtx_fail(msg, "[%s] %lld annotation transcripts (below 2^31)", who, (long long)n_tx); return -2; }
+    if (anno_names_len < 0 || anno_names_len > 0xffffffffll) { gtx_fail(msg, "[%s] an annotation names table of %lld bytes (at most 2^32 - 1)", who, (long long)anno_names_len); return -2; }
+    if (anno_names_len > 0 && !anno_names) { gtx_fail(msg, "[%s] null anno_names", who); return -2; }
+    if (n_tx > 0 && (!tx_gid || !tx_gname)) { gtx_fail(msg, "[%s] null gene column", who); return -2; }
+    return 0;
+}
+
+// Reads with their results (l2r_detail_rows: noun "rows", l2r_gtftext_reads: "reads"): sizes and pointers; with results (s != NULL, else
+// those of the last l2r_run) their sizes, and ex_off against the exon counts of info -- the kernels take a read's exons from both.  What
+// a read holds is the business of the lines and blocks (detail_line_bytes, rl_block_bytes).
+static int text_check_reads(int64_t n, int64_t names_len, const uint8_t *names, const int32_t *tid, const uint32_t *qname, const l2r_result *s, std::string &msg,
+                            const char *who, const char *noun)
+{
+    if (n < 0 || n >= ((int64_t)1 << 31)) { gtx_fail(msg, "[%s] %lld reads (below 2^31)", who, (long long)n); return -2; }
+    if (names_len < 0 || names_len > 0xffffffffll) { gtx_fail(msg, "[%s] a names table of %lld bytes (at most 2^32 - 1)", who, (long long)names_len); return -2; }
+    if (names_len > 0 && !names) { gtx_fail(msg, "[%s] null names", who); return -2; }
+    if (n > 0 && (!tid || !qname)) { gtx_fail(msg, "[%s] null column", who); return -2; }
+    if (!s) return 0;                                       // (the results of the last l2r_run)
+    if (s->n_reads != n) { gtx_fail(msg, "[%s] results of %lld reads for %lld %s", who, (long long)s->n_reads, (long long)n, noun); return -2; }
+    if (s->n_exons < 0 || s->n_exons > 0xffffffffll) { gtx_fail(msg, "[%s] results of %lld exons (at most 2^32 - 1)", who, (long long)s->n_exons); return -2; }
+    if (!s->ex_off) { gtx_fail(msg, "[%s] null ex_off", who); return -2; }
+    if (n > 0 && (!s->info || !s->ref_tx)) { gtx_fail(msg, "[%s] null result column", who); return -2; }
+    if (s->n_exons > 0 && (!s->ex_start || !s->ex_end || !s->ex_flag)) { gtx_fail(msg, "[%s] null exon column", who); return -2; }
+    if (s->ex_off[0] != 0) { gtx_fail(msg, "[%s] ex_off does not start at 0", who); return -2; }
+    for (int64_t i = 0; i < n; ++i)
+        if (s->ex_off[i + 1] - s->ex_off[i] != (int64_t)L2R_INFO_NEXON(s->info[i])) {
+            gtx_fail(msg, "[%s] read %lld: ex_off gives %lld exons, info %u", who, (long long)i, (long long)(s->ex_off[i + 1] - s->ex_off[i]), L2R_INFO_NEXON(s->info[i]));
+            return -2;
+        }
+    if (s->ex_off[n] != s->n_exons) { gtx_fail(msg, "[%s] ex_off ends at %lld, the results hold %lld exons", who, (long long)s->ex_off[n], (long long)s->n_exons); return -2; }
+    return 0;
+}
+
+// How many items (noun: "block", "row") from `first` one batch takes, over the measured lengths len[0, m): while their count stays within
+// max_items and the 64-bit sum of their bytes within max_bytes and below 2^32 - 64 -- but always one.  *n_bytes = their sum.
+static int batch_cut(const uint32_t *len, int64_t m, int64_t first, int64_t max_items, int64_t max_bytes, int64_t *n_take, int64_t *n_bytes, std::string &msg,
+                    const char *who, const char *noun)
+{
+    if (!n_take || !n_bytes) { gtx_fail(msg, "[%s] null argument", who); return -2; }
+    *n_take = 0; *n_bytes = 0;
+    if (first < 0 || first >= m) { gtx_fail(msg, "[%s] first %s %lld of %lld", who, noun, (long long)first, (long long)m); return -2; }
+    if (max_items < 1 || max_bytes < 1) { gtx_fail(msg, "[%s] a batch of %lld %ss and %lld bytes", who, (long long)max_items, noun, (long long)max_bytes); return -2; }
+    uint64_t sum = 0;
+    int64_t k = 0;
+    for (; first + k < m && k < max_items; ++k) {
+        const uint64_t b = len[first + k];
+        if (k > 0 && (sum + b > (uint64_t)max_bytes || sum + b >= GTX_BATCH_BYTES)) break;
+        sum += b;
+    }
+    *n_take = k; *n_bytes = (int64_t)sum;
+    return 0;
+}
+// ... of the blocks of l2r_gtftext_lines
+static int gtx_cut(const uint32_t *len, int64_t m, int64_t first, int64_t max_blocks, int64_t max_bytes, int64_t *n_take, int64_t *n_bytes, std::string &msg)
+{ return batch_cut(len, m, first, max_blocks, max_bytes, n_take, n_bytes, msg, "l2r_gtftext_lines", "block"); }
+
+// ---- the GTF text
+
+// 0, or -2 and the text.  The source string is read; ref_off is walked last, behind the form and the source.
 static int gtx_check_params(const l2r_gtx_params *p, std::string &msg, const char *who = "l2r_gtftext_begin")
 {
     if (!p) { gtx_fail(msg, "[%s] null argument", who); return -2; }
@@ -67,15 +147,7 @@ static int gtx_check_params(const l2r_gtx_params *p, std::string &msg, const cha
     if (p->src_len > 0 && !p->src) { gtx_fail(msg, "[%s] null source string", who); return -2; }
     for (int32_t k = 0; k < p->src_len; ++k)
         if (p->src[k] == '\t' || p->src[k] == '\n' || p->src[k] == 0) { gtx_fail(msg, "[%s] the source string holds a tab, a newline or a NUL at byte %d", who, k); return -2; }
-    if (p->n_ref > 0) {
-        if (p->ref_off[0] != 0) { gtx_fail(msg, "[%s] ref_off does not start at 0", who); return -2; }
-        for (int32_t k = 0; k < p->n_ref; ++k) {
-            const int64_t l = p->ref_off[k + 1] - p->ref_off[k];
-            if (l < 0) { gtx_fail(msg, "[%s] ref_off descends at name %d", who, k); return -2; }
-            if (l > GTX_REF_NAME_MAX) { gtx_fail(msg, "[%s] reference name %d has %lld bytes (at most %lld)", who, k, (long long)l, (long long)GTX_REF_NAME_MAX); return -2; }
-        }
-        if (p->ref_off[p->n_ref] > 0 && !p->ref_names) { gtx_fail(msg, "[%s] null ref_names", who); return -2; }
-    }
+    if (p->n_ref > 0 && text_check_ref_off(p->n_ref, p->ref_off, p->ref_names, msg, who)) return -2;
     return 0;
 }
 
@@ -187,25 +259,6 @@ static int gtx_block_bytes(const l2r_gtx_params *p, const l2r_gtx_rows *r, const
     if (sum >= GTX_BATCH_BYTES) return GTX_E_BIG;
     *bytes = sum; *lines = (uint64_t)k.n + 1u;
     return GTX_OK;
-}
-
-// How many blocks from `first` one batch takes, over the measured lengths len[0, m): while their count stays within max_blocks and the
-// 64-bit sum of their bytes within max_bytes and below 2^32 - 64 -- but always one.  *n_bytes = their sum.  0, or -2 and the text.
-static int gtx_cut(const uint32_t *len, int64_t m, int64_t first, int64_t max_blocks, int64_t max_bytes, int64_t *n_take, int64_t *n_bytes, std::string &msg)
-{
-    if (!n_take || !n_bytes) { gtx_fail(msg, "[l2r_gtftext_lines] null argument"); return -2; }
-    *n_take = 0; *n_bytes = 0;
-    if (first < 0 || first >= m) { gtx_fail(msg, "[l2r_gtftext_lines] first block %lld of %lld", (long long)first, (long long)m); return -2; }
-    if (max_blocks < 1 || max_bytes < 1) { gtx_fail(msg, "[l2r_gtftext_lines] a batch of %lld blocks and %lld bytes", (long long)max_blocks, (long long)max_bytes); return -2; }
-    uint64_t sum = 0;
-    int64_t k = 0;
-    for (; first + k < m && k < max_blocks; ++k) {
-        const uint64_t b = len[first + k];
-        if (k > 0 && (sum + b > (uint64_t)max_bytes || sum + b >= GTX_BATCH_BYTES)) break;
-        sum += b;
-    }
-    *n_take = k; *n_bytes = (int64_t)sum;
-    return 0;
 }
 
 static inline void gtx_put_num(std::vector<uint8_t> &out, uint32_t v)

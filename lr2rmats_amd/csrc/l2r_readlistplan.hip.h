@@ -1,7 +1,7 @@
 // l2r_readlistplan.hip.h -- the host side of the read lists of `update-gtf -a / -k / -v / -u` (l2r_gtftext_anno / _reads / _list): the
-// argument checks, what the host and the kernels of l2r_readlist.hip.h both compile (the list a read belongs to, the piece walk, the
-// length pieces of a block), rl_select (the selection of one list), rl_block_bytes (the exact bytes and lines of one block, and its
-// domain error) and rl_text_host, the exact routine that writes the same bytes on one core (L2R_GTX_ROUTE=host, and the comparator of
+// argument checks (over text_check_genes and text_check_reads of l2r_gtftextplan.hip.h, whose batch_cut also cuts the batches), what the
+// host and the kernels of l2r_readlist.hip.h both compile (the list a read belongs to, the piece walk, the length pieces of a block),
+// rl_select (the selection of one list), rl_block_bytes (the exact bytes and lines of one block, and its domain error) and rl_text_host, the exact routine that writes the same bytes on one core (L2R_GTX_ROUTE=host, and the comparator of
 // tools/bench_lists.py).  Host arithmetic only: no HIP call, no context, no environment.  tests/lists_dump.hip runs it as a stand-alone
 // program for tests/test_read_lists_cpu.py.
 //
@@ -43,37 +43,13 @@ static int rl_block_fail(std::string &msg, int64_t q, int kind) { return gtx_fai
 static int rl_check_anno(const l2r_gtx_anno *a, std::string &msg, const char *who = "l2r_gtftext_anno")
 {
     if (!a) { gtx_fail(msg, "[%s] null argument", who); return -2; }
-    if (a->n_tx < 0 || a->n_tx >= ((int64_t)1 << 31)) { gtx_fail(msg, "[%s] %lld annotation transcripts (below 2^31)", who, (long long)a->n_tx); return -2; }
-    if (a->anno_names_len < 0 || a->anno_names_len > 0xffffffffll) { gtx_fail(msg, "[%s] an annotation names table of %lld bytes (at most 2^32 - 1)", who, (long long)a->anno_names_len); return -2; }
-    if (a->anno_names_len > 0 && !a->anno_names) { gtx_fail(msg, "[%s] null anno_names", who); return -2; }
-    if (a->n_tx > 0 && (!a->tx_gid || !a->tx_gname)) { gtx_fail(msg, "[%s] null gene column", who); return -2; }
-    return 0;
+    return text_check_genes(a->n_tx, a->anno_names_len, a->anno_names, a->tx_gid, a->tx_gname, msg, who);
 }
 
-// 0, or -2 and the text.  Sizes, pointers and the agreement of ex_off with the exon counts of info are looked at (the kernels take a
-// read's exons from both); what a read holds is the blocks' business (rl_block_bytes).
 static int rl_check_reads(const l2r_gtx_reads *r, std::string &msg, const char *who = "l2r_gtftext_reads")
 {
     if (!r) { gtx_fail(msg, "[%s] null argument", who); return -2; }
-    if (r->n < 0 || r->n >= ((int64_t)1 << 31)) { gtx_fail(msg, "[%s] %lld reads (below 2^31)", who, (long long)r->n); return -2; }
-    if (r->names_len < 0 || r->names_len > 0xffffffffll) { gtx_fail(msg, "[%s] a names table of %lld bytes (at most 2^32 - 1)", who, (long long)r->names_len); return -2; }
-    if (r->names_len > 0 && !r->names) { gtx_fail(msg, "[%s] null names", who); return -2; }
-    if (r->n > 0 && (!r->tid || !r->qname)) { gtx_fail(msg, "[%s] null column", who); return -2; }
-    const l2r_result *s = r->res;
-    if (!s) return 0;                                       // (the results of the last l2r_run)
-    if (s->n_reads != r->n) { gtx_fail(msg, "[%s] results of %lld reads for %lld reads", who, (long long)s->n_reads, (long long)r->n); return -2; }
-    if (s->n_exons < 0 || s->n_exons > 0xffffffffll) { gtx_fail(msg, "[%s] results of %lld exons (at most 2^32 - 1)", who, (long long)s->n_exons); return -2; }
-    if (!s->ex_off) { gtx_fail(msg, "[%s] null ex_off", who); return -2; }
-    if (r->n > 0 && (!s->info || !s->ref_tx)) { gtx_fail(msg, "[%s] null result column", who); return -2; }
-    if (s->n_exons > 0 && (!s->ex_start || !s->ex_end || !s->ex_flag)) { gtx_fail(msg, "[%s] null exon column", who); return -2; }
-    if (s->ex_off[0] != 0) { gtx_fail(msg, "[%s] ex_off does not start at 0", who); return -2; }
-    for (int64_t i = 0; i < r->n; ++i)
-        if (s->ex_off[i + 1] - s->ex_off[i] != (int64_t)L2R_INFO_NEXON(s->info[i])) {
-            gtx_fail(msg, "[%s] read %lld: ex_off gives %lld exons, info %u", who, (long long)i, (long long)(s->ex_off[i + 1] - s->ex_off[i]), L2R_INFO_NEXON(s->info[i]));
-            return -2;
-        }
-    if (s->ex_off[r->n] != s->n_exons) { gtx_fail(msg, "[%s] ex_off ends at %lld, the results hold %lld exons", who, (long long)s->ex_off[r->n], (long long)s->n_exons); return -2; }
-    return 0;
+    return text_check_reads(r->n, r->names_len, r->names, r->tid, r->qname, r->res, msg, who, "reads");
 }
 
 static int rl_check_list(int list, std::string &msg, const char *who = "l2r_gtftext_list")

@@ -835,12 +835,29 @@ typedef struct {
     int64_t *ref_off; uint8_t *ref_names;
 } detail_sink;
 
-static int64_t detail_env_count(const char *name, int64_t dflt)
+/* a batch cap from the environment (L2R_DETAIL_BATCH, L2R_GTX_TEXT_MAX, ...): a count of at least 1, else the default */
+static int64_t batch_env_count(const char *name, int64_t dflt)
 {
     const char *e = getenv(name);
     if (!e || !*e) return dflt;
     const long long v = atoll(e);
     return v >= 1 ? (int64_t)v : dflt;
+}
+
+/* The n measured items of the detail table or of a read list, composed and written batch by batch: `lines` / `out` are l2r_detail_lines /
+ * l2r_detail_out or l2r_gtftext_lines / l2r_gtftext_out. */
+static void text_batches(l2r_ctx *ctx, const char *who, int (*lines)(l2r_ctx *, int64_t, int64_t, int64_t, int64_t *, int64_t *), int (*out)(l2r_ctx *, uint8_t *, int64_t),
+                         text_sink *s, int64_t n, int64_t max_items, int64_t max_bytes, int64_t *n_batches, int64_t *n_bytes)
+{
+    for (int64_t first = 0; first < n;) {
+        int64_t take = 0, bytes = 0;
+        if (lines(ctx, first, max_items, max_bytes, &take, &bytes) || take < 1) engine_fail(who);
+        if (bytes) {
+            if (out(ctx, text_sink_room(s, bytes), bytes)) engine_fail(who);
+            text_sink_put(who, s, bytes);
+        }
+        ++*n_batches; *n_bytes += bytes; first += take;
+    }
 }
 
 /* the reads [lo, hi) -- the shard the context has just run; res: the results of the whole input so far, for the tail's writer */
@@ -867,16 +884,8 @@ static void detail_shard(l2r_ctx *ctx, const char *who, detail_sink *d, int64_t 
         return;
     }
     if (rc) engine_fail(who);
-    const int64_t max_rows = detail_env_count("L2R_DETAIL_BATCH", (int64_t)1 << 20), max_bytes = detail_env_count("L2R_DETAIL_TEXT_MAX", (int64_t)1 << 30);
-    for (int64_t first = 0; first < n;) {
-        int64_t take = 0, bytes = 0;
-        if (l2r_detail_lines(ctx, first, max_rows, max_bytes, &take, &bytes) || take < 1) engine_fail(who);
-        if (bytes) {
-            if (l2r_detail_out(ctx, text_sink_room(&d->out, bytes), bytes)) engine_fail(who);
-            text_sink_put(who, &d->out, bytes);
-        }
-        ++d->batches; d->bytes += bytes; first += take;
-    }
+    text_batches(ctx, who, l2r_detail_lines, l2r_detail_out, &d->out, n, batch_env_count("L2R_DETAIL_BATCH", (int64_t)1 << 20), batch_env_count("L2R_DETAIL_TEXT_MAX", (int64_t)1 << 30),
+                 &d->batches, &d->bytes);
     d->rows += n;
     {   double st[7] = {0, 0, 0, 0, 0, 0, 0};
         (void)l2r_detail_stats(ctx, st, 7);
@@ -925,7 +934,7 @@ static void lists_shard(l2r_ctx *ctx, const char *who, lists_sink *d, int64_t lo
                                d->reads->tid_name ? d->reads->tid_name + lo : NULL, NULL, d->n_sj > 0, d->o->prm.split_trans != 0 };
     if (l2r_gtftext_reads(ctx, &rd)) engine_fail(who);
     /* (a quarter of the GTF text's default batch: a file has two buffers of a batch's bytes, and there are four files) */
-    const int64_t max_blocks = detail_env_count("L2R_GTX_BATCH", (int64_t)1 << 20), max_bytes = detail_env_count("L2R_GTX_TEXT_MAX", (int64_t)1 << 28);
+    const int64_t max_blocks = batch_env_count("L2R_GTX_BATCH", (int64_t)1 << 20), max_bytes = batch_env_count("L2R_GTX_TEXT_MAX", (int64_t)1 << 28);
     for (int list = 0; list < 4; ++list) {
         text_sink *s = &d->out[list];
         if (!s->fp) continue;
@@ -938,15 +947,7 @@ static void lists_shard(l2r_ctx *ctx, const char *who, lists_sink *d, int64_t lo
             continue;
         }
         if (rc) engine_fail(who);
-        for (int64_t first = 0; first < m;) {
-            int64_t take = 0, bytes = 0;
-            if (l2r_gtftext_lines(ctx, first, max_blocks, max_bytes, &take, &bytes) || take < 1) engine_fail(who);
-            if (bytes) {
-                if (l2r_gtftext_out(ctx, text_sink_room(s, bytes), bytes)) engine_fail(who);
-                text_sink_put(who, s, bytes);
-            }
-            ++d->batches; d->bytes += bytes; first += take;
-        }
+        text_batches(ctx, who, l2r_gtftext_lines, l2r_gtftext_out, s, m, max_blocks, max_bytes, &d->batches, &d->bytes);
         double st[14] = {0};
         (void)l2r_gtftext_stats(ctx, st, 14);
         d->engine_host = st[6] != 0;

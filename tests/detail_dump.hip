@@ -1,6 +1,7 @@
 // detail_dump.hip -- the host side of l2r_detail_* (lr2rmats_amd/csrc/l2r_detailplan.hip.h) as a stand-alone host program, for
 // tests/test_detail_cpu.py:
 //     detail_dump <case file> <output file> [<case file> <output file> ...]
+//     detail_dump faults        (one line per argument fault of l2r_detail_begin, l2r_detail_rows and l2r_detail_lines: tests/text_faults.hip.h)
 // runs the argument checks, detail_line_bytes of every read, detail_cut from the case's first row to the last, and detail_text_host, the
 // exact routine behind L2R_DETAIL_ROUTE=host, over all the rows and batch by batch.  No HIP function is called and no GPU is needed;
 // `make -C lr2rmats_amd/csrc detail-dump` builds it with ASan + UBSan on the host code.
@@ -25,6 +26,7 @@
 #include <vector>
 
 #include "../lr2rmats_amd/csrc/l2r_detailplan.hip.h"
+#include "text_faults.hip.h"
 
 using namespace l2r;
 
@@ -141,8 +143,26 @@ static int run(const char *in_fn, const char *out_fn)
     return fclose(g_out) ? 2 : 0;
 }
 
+// `detail_dump faults`: the argument faults of l2r_detail_begin, l2r_detail_rows and l2r_detail_lines (text_faults.hip.h)
+static int faults()
+{
+    static const int64_t ref_off[3] = {0, 2, 4};
+    static const uint8_t bytes[4] = {'c', '1', 'c', '2'};
+    static const uint32_t ids[2] = {0, 2};
+    const l2r_detail_params sound = {2, ref_off, bytes, 2, 4, bytes, ids, ids};
+    const auto params = [](const l2r_detail_params *p, std::string &msg) { return detail_check_params(p, msg); };
+    { std::string msg; const int rc = detail_check_params(nullptr, msg); text_faults::say("params_null", rc, msg); }
+    text_faults::refs(sound, params);
+    text_faults::genes(sound, params);
+    text_faults::reads<l2r_detail_reads>([](const l2r_detail_reads *r, std::string &msg) { return detail_check_rows(r, msg); });
+    text_faults::cuts([](const uint32_t *len, int64_t m, int64_t first, int64_t max_rows, int64_t max_bytes, int64_t *take, int64_t *sum, std::string &msg) {
+        return detail_cut(len, m, first, max_rows, max_bytes, take, sum, msg); });
+    return 0;
+}
+
 int main(int argc, char **argv)
 {
+    if (argc == 2 && strcmp(argv[1], "faults") == 0) return faults();
     if (argc < 3 || argc % 2 != 1) { fprintf(stderr, "usage: detail_dump <case file> <output file> [<case file> <output file> ...]\n"); return 2; }
     for (int k = 1; k + 1 < argc; k += 2) { const int rc = run(argv[k], argv[k + 1]); if (rc) return rc; }
     return 0;

@@ -1,6 +1,7 @@
 // gtx_dump.hip -- the host side of l2r_gtftext_* (lr2rmats_amd/csrc/l2r_gtftextplan.hip.h) as a stand-alone host program, for
 // tests/test_gtf_text_cpu.py:
 //     gtx_dump <case file> <output file> [<case file> <output file> ...]
+//     gtx_dump faults        (one line per argument fault of l2r_gtftext_begin's reference table and l2r_gtftext_lines: tests/text_faults.hip.h)
 // runs the argument checks, gtx_block_bytes of every block, gtx_cut from the case's first block to the last, and gtx_text_host, the exact
 // routine behind L2R_GTX_ROUTE=host, over the whole selection and batch by batch.  No HIP function is called and no GPU is needed;
 // `make -C lr2rmats_amd/csrc gtx-dump` builds it with ASan + UBSan on the host code.
@@ -23,6 +24,7 @@
 #include <vector>
 
 #include "../lr2rmats_amd/csrc/l2r_gtftextplan.hip.h"
+#include "text_faults.hip.h"
 
 using namespace l2r;
 
@@ -134,8 +136,28 @@ static int run(const char *in_fn, const char *out_fn)
     return fclose(g_out) ? 2 : 0;
 }
 
+// `gtx_dump faults`: the argument faults of l2r_gtftext_begin's reference table and of l2r_gtftext_lines (text_faults.hip.h), and
+// that a bad form is reported in front of a ref_off that descends
+static int faults()
+{
+    static const int64_t ref_off[3] = {0, 2, 4}, down[3] = {0, 3, 2};
+    static const uint8_t bytes[4] = {'c', '1', 'c', '2'};
+    const l2r_gtx_params sound = {2, ref_off, bytes, L2R_GTX_READ, 2, bytes};
+    const auto params = [](const l2r_gtx_params *p, std::string &msg) { return gtx_check_params(p, msg); };
+    text_faults::refs(sound, params);
+    {   l2r_gtx_params p = sound;
+        p.form = 2; p.ref_off = down;
+        std::string msg; const int rc = gtx_check_params(&p, msg); text_faults::say("ref_descends_and_form_2", rc, msg);
+        p.form = L2R_GTX_READ; p.ref_off = nullptr; p.src_len = -1;
+        msg.clear(); const int rc2 = gtx_check_params(&p, msg); text_faults::say("ref_null_off_and_src_len_negative", rc2, msg); }
+    text_faults::cuts([](const uint32_t *len, int64_t m, int64_t first, int64_t max_blocks, int64_t max_bytes, int64_t *take, int64_t *sum, std::string &msg) {
+        return gtx_cut(len, m, first, max_blocks, max_bytes, take, sum, msg); });
+    return 0;
+}
+
 int main(int argc, char **argv)
 {
+    if (argc == 2 && strcmp(argv[1], "faults") == 0) return faults();
     if (argc < 3 || argc % 2 != 1) { fprintf(stderr, "usage: gtx_dump <case file> <output file> [<case file> <output file> ...]\n"); return 2; }
     for (int k = 1; k + 1 < argc; k += 2) { const int rc = run(argv[k], argv[k + 1]); if (rc) return rc; }
     return 0;

@@ -1,6 +1,7 @@
 // lists_dump.hip -- the host side of the read lists of `update-gtf -a / -k / -v / -u` (lr2rmats_amd/csrc/l2r_readlistplan.hip.h) as a
 // stand-alone host program, for tests/test_read_lists_cpu.py:
 //     lists_dump <case file> <output file> [<case file> <output file> ...]
+//     lists_dump faults        (one line per argument fault of l2r_gtftext_anno and l2r_gtftext_reads: tests/text_faults.hip.h)
 // runs the argument checks and then, for each of the four lists, rl_select, rl_block_bytes of every block, gtx_cut from the case's first
 // block to the last, and rl_text_host, the exact routine behind L2R_GTX_ROUTE=host, over the whole list and batch by batch.  No HIP
 // function is called and no GPU is needed; `make -C lr2rmats_amd/csrc lists-dump` builds it with ASan + UBSan on the host code.
@@ -25,6 +26,7 @@
 #include <vector>
 
 #include "../lr2rmats_amd/csrc/l2r_readlistplan.hip.h"
+#include "text_faults.hip.h"
 
 using namespace l2r;
 
@@ -146,8 +148,21 @@ static int run(const char *in_fn, const char *out_fn)
     return fclose(g_out) ? 2 : 0;
 }
 
+// `lists_dump faults`: the argument faults of l2r_gtftext_anno and l2r_gtftext_reads (text_faults.hip.h)
+static int faults()
+{
+    static const uint8_t bytes[4] = {'g', '1', 'g', '2'};
+    static const uint32_t ids[2] = {0, 2};
+    const l2r_gtx_anno sound = {2, 4, bytes, ids, ids};
+    { std::string msg; const int rc = rl_check_anno(nullptr, msg); text_faults::say("anno_null", rc, msg); }
+    text_faults::genes(sound, [](const l2r_gtx_anno *a, std::string &msg) { return rl_check_anno(a, msg); });
+    text_faults::reads<l2r_gtx_reads>([](const l2r_gtx_reads *r, std::string &msg) { return rl_check_reads(r, msg); });
+    return 0;
+}
+
 int main(int argc, char **argv)
 {
+    if (argc == 2 && strcmp(argv[1], "faults") == 0) return faults();
     if (argc < 3 || argc % 2 != 1) { fprintf(stderr, "usage: lists_dump <case file> <output file> [<case file> <output file> ...]\n"); return 2; }
     for (int k = 1; k + 1 < argc; k += 2) { const int rc = run(argv[k], argv[k + 1]); if (rc) return rc; }
     return 0;
