@@ -576,6 +576,33 @@ int          l2r_uniq_merge(l2r_ctx *ctx, const l2r_params *prm, const l2r_uniq_
 int          l2r_uniq_out(l2r_ctx *ctx, uint8_t *merged /* n */, int32_t *uniq_of /* n */, int32_t *u_src, int32_t *u_start, int32_t *u_end, int32_t *u_cov /* n_unique each */);
 int          l2r_uniq_stats(l2r_ctx *ctx, double *out, int n);
 
+/* ---- the read classes of `update-gtf -y` (host/tail.c summary_and_bed; src/update_gtf.c:496-528): how many reads of the input are known,
+ * novel with reliable junctions only, novel with an unreliable junction, and unrecognised, and how long the merge_trans list of every
+ * class gets when its reads are offered to it in input order.  The class of a read, from its info word: L2R_INFO_KNOWN -> 0; else
+ * L2R_INFO_KNOWN_SITE without L2R_INFO_UNREL -> 1; else L2R_INFO_KNOWN_SITE -> 2; else 3.  The merge rule is l2r_uniq_merge's, the strand
+ * of a read is L2R_INFO_REV.  The rule and why one list does for the four: csrc/l2r_summaryplan.hip.h.
+ *     l2r_summary_begin   the merge parameters (-s, -d, -D, -f of prm); the accumulators are emptied
+ *     l2r_summary_add     n reads with their tid and results.  res == NULL: the results of the context's last l2r_run, where they lie in
+ *                         HBM (n = its reads); otherwise the arrays of an l2r_download (n_reads = n, ex_off the running sum of the exon
+ *                         counts in info), which are uploaded.  tid, info and the exon chains are appended to accumulators in HBM;
+ *                         nothing is merged yet -- a shard's end falls inside clusters, and unique counts of shards do not add up.
+ *                         n == 0 is fine.  -2: an allocation failed, the accumulators are as they were
+ *     l2r_summary_finish  counts[0..3] = the reads of class 0..3, counts[4..7] = the unique transcripts of class 0..3
+ * Domain errors fail l2r_summary_finish with -1 and name the smallest read that has one, and of its kinds the first: a tid outside
+ * [0, 2^29), a read with no exon, a negative coordinate.  l2r_summary_add fails with -1 where the totals reach 2^31 reads or
+ * 2^32 - 64 exons, or where the arrays of res do not fit together.
+ * On the device (csrc/l2r_summary.hip.h) where (tid, start) descends inside no class; other input is fetched and takes the exact host
+ * routine summary_host -- four uniq_host lists -- as every input does under L2R_SUMMARY_ROUTE=host (read at l2r_summary_begin: the engine
+ * then keeps host copies).  L2R_SUMMARY_WAVE=0|1 forces the thread or the wave form of the gather kernel.
+ * l2r_summary_stats: out[0] reads, [1] exons, [2] adds, [3] route (0 device, 1 host), [4] clusters, [5] offers of the largest cluster,
+ * [6] 1 where the wave form gathered; with L2R_SORT_TIMING=1 in the environment device milliseconds of [7] k_sum_class + k_sum_place + the
+ * scans, [8] k_sum_gather, [9] the cluster cut, [10] k_uniq_merge, [11] k_uniq_take + k_sum_count; n = words of out (up to 12). */
+typedef struct { int64_t n; const int32_t *tid; const l2r_result *res; /* NULL: the results of the context's last l2r_run where they lie in HBM */ } l2r_summary_reads;
+int          l2r_summary_begin(l2r_ctx *ctx, const l2r_params *prm);
+int          l2r_summary_add(l2r_ctx *ctx, const l2r_summary_reads *reads);
+int          l2r_summary_finish(l2r_ctx *ctx, int64_t counts[8]);
+int          l2r_summary_stats(l2r_ctx *ctx, double *out, int n);
+
 /* ---- the GTF block of `bam2gtf` and `unique-gtf` (host/cmds.c, host/tail.c): transcripts as GTF text, the text composed on the device.
  * The rule, stated here once.  A block describes one transcript: a reference tid, a strand rev, n >= 1 exons xs[k]..xe[k] in ascending
  * order, up to four names -- gene id g, transcript id t, gene name G, transcript name T -- and optionally the overrides start, end and

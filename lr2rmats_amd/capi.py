@@ -42,6 +42,7 @@ EXPORTS = [
     "l2r_gtftext_begin", "l2r_gtftext_rows", "l2r_gtftext_blocks", "l2r_gtftext_lines", "l2r_gtftext_out", "l2r_gtftext_stats",
     "l2r_gtftext_anno", "l2r_gtftext_reads", "l2r_gtftext_list", "l2r_gtftext_list_out",
     "l2r_detail_begin", "l2r_detail_rows", "l2r_detail_lines", "l2r_detail_out", "l2r_detail_stats",
+    "l2r_summary_begin", "l2r_summary_add", "l2r_summary_finish", "l2r_summary_stats",
 ]
 SJ_E_UNKNOWN_TID = -3
 
@@ -299,6 +300,10 @@ def load_library():
         lib.l2r_detail_lines.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p]
         lib.l2r_detail_out.argtypes = [C.c_void_p, C.c_void_p, C.c_int64]
         lib.l2r_detail_stats.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
+        lib.l2r_summary_begin.argtypes = [C.c_void_p, C.c_void_p]
+        lib.l2r_summary_add.argtypes = [C.c_void_p, C.c_void_p]
+        lib.l2r_summary_finish.argtypes = [C.c_void_p, C.c_void_p]
+        lib.l2r_summary_stats.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
         _lib = lib
     return _lib
 
@@ -454,6 +459,15 @@ GTX_LIST_ALL, GTX_LIST_KNOWN, GTX_LIST_NOVEL, GTX_LIST_UNRECOG = 0, 1, 2, 3
 
 UNIQ_STAT_NAMES = ["rows", "unique", "clusters", "largest_cluster", "route", "hits_identical", "hits_contained", "hits_single", "end_extensions",
                    "k_uniq_heads + cluster cut", "k_uniq_merge", "k_scan_u32 (list lengths) + k_uniq_take"]
+
+
+SUMMARY_STAT_NAMES = ["reads", "exons", "adds", "route", "clusters", "largest_cluster", "wave_form",
+                      "k_sum_class + k_sum_place + scans", "k_sum_gather", "cluster cut", "k_uniq_merge", "k_uniq_take + k_sum_count"]
+SUMMARY_COUNT_NAMES = ["known", "reliable", "unreliable", "unrecognised"]
+
+
+class CSummaryReads(C.Structure):
+    _fields_ = [("n", C.c_int64), ("tid", C.c_void_p), ("res", C.c_void_p)]
 
 
 FUSION_STAT_NAMES = ["wave_form", "k_fusion_seg", "k_fusion_select", "k_filter_score", "k_filter_select"]
@@ -960,6 +974,42 @@ class Engine:
         out = np.zeros(len(UNIQ_STAT_NAMES), np.float64)
         self._chk(self.lib.l2r_uniq_stats(self.ctx, out.ctypes.data, len(out)))
         return {k: float(v) for k, v in zip(UNIQ_STAT_NAMES, out)}
+
+    # ---- the read classes of `update-gtf -y` (include/lr2rmats_hip.h: l2r_summary_begin / _add / _finish / _stats)
+    def summary_begin(self, force_strand=0, ss_dis=0, end_dis=0x7fffffff, frac=0.8) -> None:
+        """-s, -d, -D, -f as the command's; the accumulators are emptied."""
+        prm = Params(3, 3, 50, int(ss_dis), int(end_dis), 5, 0, 0, 1, int(force_strand), float(frac))
+        self._chk(self.lib.l2r_summary_begin(self.ctx, C.byref(prm)))
+
+    def summary_add(self, tid, res=None, n=None) -> None:
+        """``tid`` of the reads and ``res``, a Result (the arrays of a download), which is uploaded; None: the results of the last run where
+        they lie in HBM (``n`` overrides the read count, which must equal the run's reads)."""
+        tid = np.ascontiguousarray(tid, np.int32)
+        n = int(tid.shape[0]) if n is None else int(n)
+        keep, cres = [], None
+        if res is not None:
+            keep = [np.ascontiguousarray(res.ex_off, np.int64), np.ascontiguousarray(res.ex_start, np.int32), np.ascontiguousarray(res.ex_end, np.int32),
+                    np.ascontiguousarray(res.ex_flag, np.uint8), np.ascontiguousarray(res.info, np.uint32), np.ascontiguousarray(res.ref_tx, np.int32)]
+            x = int(keep[0][-1]) if keep[0].size else 0
+            keep = [a if a.size else np.zeros(1, a.dtype) for a in keep]
+            cres = CResult(n, x, x, keep[0].ctypes.data_as(_i64p), keep[1].ctypes.data_as(_i32p), keep[2].ctypes.data_as(_i32p), keep[3].ctypes.data_as(_u8p),
+                           keep[4].ctypes.data_as(_u32p), keep[5].ctypes.data_as(_i32p))
+        rd = CSummaryReads(n, tid.ctypes.data if tid.size else None, None if cres is None else C.addressof(cres))
+        self._chk(self.lib.l2r_summary_add(self.ctx, C.byref(rd)))
+
+    def summary_finish(self) -> list:
+        """The eight counts: the reads of the classes known, reliable, unreliable, unrecognised, then their unique transcripts.  A read outside
+        the domain raises L2RError (rc=-1) naming the smallest such read and the kind."""
+        out = np.zeros(8, np.int64)
+        self._chk(self.lib.l2r_summary_finish(self.ctx, out.ctypes.data))
+        return [int(v) for v in out]
+
+    def summary_stats(self) -> dict:
+        """l2r_summary_stats: reads, exons, adds, route (0 device, 1 host), clusters, largest cluster, the form of k_sum_gather (0 thread, 1
+        wave), and with L2R_SORT_TIMING=1 device milliseconds per kernel group."""
+        out = np.zeros(len(SUMMARY_STAT_NAMES), np.float64)
+        self._chk(self.lib.l2r_summary_stats(self.ctx, out.ctypes.data, len(out)))
+        return {k: float(v) for k, v in zip(SUMMARY_STAT_NAMES, out)}
 
     def set_annotation_cache(self, directory) -> None:
         """Keep the annotation tables on disk under ``directory`` (None: off); see include/lr2rmats_hip.h."""

@@ -31,6 +31,7 @@
 #include "l2r_gtftext.hip.h"
 #include "l2r_readlist.hip.h"
 #include "l2r_detail.hip.h"
+#include "l2r_summary.hip.h"
 #include "l2r_plan.hip.h"
 #include "l2r_tables.hip.h"
 #include "l2r_nameorder.hip.h"
@@ -283,6 +284,50 @@ struct UniqState {
     double stats[UQS_N] = {0};                          // l2r_uniq_stats
 };
 
+// A device column that is appended to: reserve() keeps the n elements it holds (a copy on the context stream into a larger buffer, which
+// is waited for before the old one is released) and, where the larger buffer cannot be had, leaves the column as it was.
+template <typename T>
+struct AccBuf {
+    T *p = nullptr;
+    size_t cap = 0, n = 0;
+    AccBuf() = default;
+    AccBuf(const AccBuf &) = delete;
+    AccBuf &operator=(const AccBuf &) = delete;
+    ~AccBuf() { if (p) (void)hipFree(p); }
+    void clear() { n = 0; }
+    int reserve(hipStream_t stream, size_t want)
+    {
+        if (want <= cap) return 0;
+        T *q = nullptr;
+        size_t room = want > 2 * cap ? want : 2 * cap;
+        hipError_t e = hipMalloc((void **)&q, room * sizeof(T));
+        if (e != hipSuccess && room > want) { room = want; e = hipMalloc((void **)&q, room * sizeof(T)); }
+        if (e != hipSuccess) return fail(-2, "hipMalloc(%zu bytes): %s", room * sizeof(T), hipGetErrorString(e));
+        if (n) e = hipMemcpyAsync(q, p, n * sizeof(T), hipMemcpyDeviceToDevice, stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(stream);
+        if (e != hipSuccess) { (void)hipFree(q); return fail(-2, "growing a column of %zu elements: %s", n, hipGetErrorString(e)); }
+        if (p) (void)hipFree(p);
+        p = q; cap = room;
+        return 0;
+    }
+};
+
+// The read classes and unique counts of `update-gtf -y` (l2r_summary.hip.h): the merge parameters of l2r_summary_begin, the reads of every
+// l2r_summary_add since -- in HBM, or on the host where the route of the begin is the host's -- and what the kernels of l2r_summary_finish
+// leave.  `u` holds the permuted columns and the work of the merge kernels: a UniqState of this unit's own, so that a l2r_uniq_merge on
+// the same context keeps its results.
+struct SummaryState {
+    bool begun = false, on_host = false;
+    UniqPrm p{0, 0, 0, 0.0f};
+    int64_t n = 0, x = 0, adds = 0;                     // reads, exons, calls so far
+    AccBuf<int32_t> tid, xs, xe; AccBuf<uint32_t> info;
+    struct Host { std::vector<int32_t> tid, xs, xe; std::vector<uint32_t> info; } h;
+    DevBuf<uint8_t> cls; DevBuf<uint32_t> src_off, tile_cnt, dst_off, src, word;      // src_off, dst_off: n + 1, scanned in place; tile_cnt: 4 tiles + 1; word: SUMW_*
+    DevBuf<unsigned long long> bad;                     // the smallest read outside the domain << 4 | its kind
+    UniqState u;
+    double stats[SMS_N] = {0};                          // l2r_summary_stats
+};
+
 // The GTF block of `bam2gtf` / `unique-gtf` (l2r_gtftext.hip.h): the reference names, source string and form of l2r_gtftext_begin, the
 // transcripts of l2r_gtftext_rows, the selection of l2r_gtftext_blocks with what k_gtx_measure left per block, and the text of the last
 // l2r_gtftext_lines (in HBM, or on the host where the host route made it) until l2r_gtftext_out fetches it.  The route is read at
@@ -500,6 +545,7 @@ struct l2r_ctx {
     UniqState uniq;                         // `unique-gtf`
     GtxState gtx;                           // `bam2gtf`, `unique-gtf`: the GTF text
     DetailState detail;                     // `update-gtf -A`: the detail table
+    SummaryState summary;                   // `update-gtf -y`: read classes and unique counts
 };
 
 // A launch (or a group of launches) on the context stream
@@ -2939,6 +2985,51 @@ static void uniq_on_host(UniqState &m, const l2r_uniq_trans *t, const UniqPrm &p
     }
 }
 
+// The device part of merge_trans over N > 0 transcripts whose columns already lie in HBM, in m.tid, m.rev, m.ex_off, m.xs and m.xe
+// (l2r_uniq_merge uploads them, l2r_summary_finish gathers them there): the cluster cut, k_uniq_merge, k_uniq_take into m's buffers; the
+// counter block comes back in w.  The stage timer m.clk is the caller's to arm; ms_*: where the device milliseconds of the three groups
+// are added.  Where w[UQW_UNSORTED] is set -- (tid, start) descends somewhere -- nothing has been merged and the caller takes its exact host
+// routine.  The stream has been waited for on every path out.
+extern "C++" {
+static int uniq_device(l2r_ctx *c, UniqState &m, size_t N, const UniqPrm &p, const char *who, double *ms_cut, double *ms_merge, double *ms_take, uint32_t *w)
+{
+    const size_t n_tiles = (N + UNIQ_TILE - 1) / UNIQ_TILE;
+    int rc = 0;
+    if (m.rec.ensure(N) || m.tile_max.ensure(n_tiles) || m.head.ensure(N + 1) || m.first.ensure(N + 1) || m.len.ensure(N + 1) || m.word.ensure(UQW_N) ||
+        m.l_src.ensure(N) || m.l_start.ensure(N) || m.l_end.ensure(N) || m.l_cov.ensure(N) || m.uniq_of.ensure(N) || m.merged.ensure(N) ||
+        m.u_src.ensure(N) || m.u_start.ensure(N) || m.u_end.ensure(N) || m.u_cov.ensure(N)) rc = -2;
+    if (rc) { (void)hipStreamSynchronize(c->stream); return rc; }
+    HIP_TRY_AS(who, hipMemsetAsync(m.word.p, 0, UQW_N * sizeof(uint32_t), c->stream));
+    const UniqIn in{(int64_t)N, m.tid.p, m.rev.p, m.ex_off.p, m.xs.p, m.xe.p};
+    rc = m.clk.launch(c, ms_cut, [&] {
+        hipLaunchKernelGGL(k_uniq_heads, dim3((unsigned)n_tiles), dim3(UNIQ_TILE), 0, c->stream, in, m.rec.p, m.tile_max.p, m.word.p);
+        hipLaunchKernelGGL(k_uniq_pmax, dim3(1), dim3(1024), 0, c->stream, m.tile_max.p, (int64_t)n_tiles);
+        hipLaunchKernelGGL(k_uniq_cut, dim3((unsigned)n_tiles), dim3(UNIQ_TILE), 0, c->stream, (int64_t)N, (const int32_t *)m.tid.p, (const UniqRec *)m.rec.p,
+                           (const uint64_t *)m.tile_max.p, m.head.p);
+        scan_u32(c, m.head.p, (int64_t)N, m.word.p + UQW_CLUSTERS);
+        hipLaunchKernelGGL(k_uniq_firsts, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, c->stream, (int64_t)N, (const uint32_t *)m.head.p, m.first.p);
+    });
+    if ((rc = download_all(c, rc, {{w, m.word.p, UQW_N * sizeof(uint32_t)}}, who))) return rc;
+    if (w[UQW_UNSORTED]) return 0;
+    const uint32_t C = w[UQW_CLUSTERS];
+    if (C == 0 || (size_t)C > N) return fail(-2, "[%s] %u clusters of %zu transcripts", who, C, N);
+    const UniqList L{m.l_src.p, m.l_start.p, m.l_end.p, m.l_cov.p};
+    rc = m.clk.launch(c, ms_merge, [&] {
+        hipLaunchKernelGGL(k_uniq_merge, dim3((C + UNIQ_WAVES - 1) / UNIQ_WAVES), dim3(UNIQ_WAVES * 64), 0, c->stream, in, (const UniqRec *)m.rec.p, (const uint32_t *)m.first.p, C, p, L,
+                           m.len.p, m.merged.p, m.uniq_of.p, m.word.p);
+    });
+    if (!rc) rc = m.clk.launch(c, ms_take, [&] {
+        scan_u32(c, m.len.p, (int64_t)C, m.word.p + UQW_UNIQUE);
+        hipLaunchKernelGGL(k_uniq_take, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, c->stream, (int64_t)N, (const uint32_t *)m.head.p, (const uint32_t *)m.first.p,
+                           (const uint32_t *)m.len.p, L, m.uniq_of.p, m.u_src.p, m.u_start.p, m.u_end.p, m.u_cov.p);
+    });
+    if ((rc = download_all(c, rc, {{w, m.word.p, UQW_N * sizeof(uint32_t)}}, who))) return rc;
+    const uint64_t hits = (uint64_t)w[UQW_IDENT] + w[UQW_CONTAINED] + w[UQW_SINGLE];
+    if ((size_t)w[UQW_UNIQUE] > N || w[UQW_UNIQUE] < C || hits + w[UQW_UNIQUE] != N) return fail(-2, "[%s] %u entries and %llu hits of %zu offers", who, w[UQW_UNIQUE], (unsigned long long)hits, N);
+    return 0;
+}
+}
+
 int l2r_uniq_merge(l2r_ctx *c, const l2r_params *prm, const l2r_uniq_trans *t, int64_t *n_unique)
 {
     if (!c || !prm || !n_unique) return fail(-1, "[l2r_uniq_merge] null argument");
@@ -2957,48 +3048,19 @@ int l2r_uniq_merge(l2r_ctx *c, const l2r_params *prm, const l2r_uniq_trans *t, i
     HIP_TRY(hipSetDevice(c->device));
     int rc;
     if ((rc = m.clk.begin(env_on("L2R_SORT_TIMING"), c->check_stages))) return rc;
-    const size_t NX = (size_t)t->ex_off[N], n_tiles = (N + UNIQ_TILE - 1) / UNIQ_TILE;
+    const size_t NX = (size_t)t->ex_off[N];
     if ((rc = to_dev(c, m.tid, t->tid, N)) || (rc = to_dev(c, m.rev, t->rev, N)) || (rc = to_dev(c, m.ex_off, t->ex_off, N + 1)) ||
-        (rc = to_dev(c, m.xs, t->xs, NX)) || (rc = to_dev(c, m.xe, t->xe, NX)) ||
-        m.rec.ensure(N) || m.tile_max.ensure(n_tiles) || m.head.ensure(N + 1) || m.first.ensure(N + 1) || m.len.ensure(N + 1) || m.word.ensure(UQW_N) ||
-        m.l_src.ensure(N) || m.l_start.ensure(N) || m.l_end.ensure(N) || m.l_cov.ensure(N) || m.uniq_of.ensure(N) || m.merged.ensure(N) ||
-        m.u_src.ensure(N) || m.u_start.ensure(N) || m.u_end.ensure(N) || m.u_cov.ensure(N)) rc = rc ? rc : -2;
-    if (rc) { (void)hipStreamSynchronize(c->stream); return rc; }      // (the columns are the caller's)
-    HIP_TRY(hipMemsetAsync(m.word.p, 0, UQW_N * sizeof(uint32_t), c->stream));
-    const UniqIn in{(int64_t)N, m.tid.p, m.rev.p, m.ex_off.p, m.xs.p, m.xe.p};
-    rc = m.clk.launch(c, &m.stats[UQS_K_CUT], [&] {
-        hipLaunchKernelGGL(k_uniq_heads, dim3((unsigned)n_tiles), dim3(UNIQ_TILE), 0, c->stream, in, m.rec.p, m.tile_max.p, m.word.p);
-        hipLaunchKernelGGL(k_uniq_pmax, dim3(1), dim3(1024), 0, c->stream, m.tile_max.p, (int64_t)n_tiles);
-        hipLaunchKernelGGL(k_uniq_cut, dim3((unsigned)n_tiles), dim3(UNIQ_TILE), 0, c->stream, (int64_t)N, (const int32_t *)m.tid.p, (const UniqRec *)m.rec.p,
-                           (const uint64_t *)m.tile_max.p, m.head.p);
-        scan_u32(c, m.head.p, (int64_t)N, m.word.p + UQW_CLUSTERS);
-        hipLaunchKernelGGL(k_uniq_firsts, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, c->stream, (int64_t)N, (const uint32_t *)m.head.p, m.first.p);
-    });
+        (rc = to_dev(c, m.xs, t->xs, NX)) || (rc = to_dev(c, m.xe, t->xe, NX))) { (void)hipStreamSynchronize(c->stream); return rc; }      // (the columns are the caller's)
     uint32_t w[UQW_N] = {0};
-    if ((rc = download_all(c, rc, {{w, m.word.p, sizeof w}}, "l2r_uniq_merge"))) return rc;
+    if ((rc = uniq_device(c, m, N, p, "l2r_uniq_merge", &m.stats[UQS_K_CUT], &m.stats[UQS_K_MERGE], &m.stats[UQS_K_TAKE], w))) return rc;
     if (w[UQW_UNSORTED]) {                              // (tid, start) descends somewhere: the exact host routine
         for (int k = UQS_K_CUT; k < UQS_N; ++k) m.stats[k] = 0;
         uniq_on_host(m, t, p, false);
         *n_unique = m.n_unique;
         return 0;
     }
-    const uint32_t C = w[UQW_CLUSTERS];
-    if (C == 0 || (size_t)C > N) return fail(-2, "[l2r_uniq_merge] %u clusters of %zu transcripts", C, N);
-    const UniqList L{m.l_src.p, m.l_start.p, m.l_end.p, m.l_cov.p};
-    rc = m.clk.launch(c, &m.stats[UQS_K_MERGE], [&] {
-        hipLaunchKernelGGL(k_uniq_merge, dim3((C + UNIQ_WAVES - 1) / UNIQ_WAVES), dim3(UNIQ_WAVES * 64), 0, c->stream, in, (const UniqRec *)m.rec.p, (const uint32_t *)m.first.p, C, p, L,
-                           m.len.p, m.merged.p, m.uniq_of.p, m.word.p);
-    });
-    if (!rc) rc = m.clk.launch(c, &m.stats[UQS_K_TAKE], [&] {
-        scan_u32(c, m.len.p, (int64_t)C, m.word.p + UQW_UNIQUE);
-        hipLaunchKernelGGL(k_uniq_take, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, c->stream, (int64_t)N, (const uint32_t *)m.head.p, (const uint32_t *)m.first.p,
-                           (const uint32_t *)m.len.p, L, m.uniq_of.p, m.u_src.p, m.u_start.p, m.u_end.p, m.u_cov.p);
-    });
-    if ((rc = download_all(c, rc, {{w, m.word.p, sizeof w}}, "l2r_uniq_merge"))) return rc;
-    const uint64_t hits = (uint64_t)w[UQW_IDENT] + w[UQW_CONTAINED] + w[UQW_SINGLE];
-    if ((size_t)w[UQW_UNIQUE] > N || w[UQW_UNIQUE] < C || hits + w[UQW_UNIQUE] != N) return fail(-2, "[l2r_uniq_merge] %u entries and %llu hits of %zu offers", w[UQW_UNIQUE], (unsigned long long)hits, N);
     m.n_unique = (int64_t)w[UQW_UNIQUE];
-    m.stats[UQS_UNIQUE] = (double)w[UQW_UNIQUE]; m.stats[UQS_CLUSTERS] = (double)C; m.stats[UQS_LARGEST] = (double)w[UQW_LARGEST]; m.stats[UQS_ROUTE] = 0;
+    m.stats[UQS_UNIQUE] = (double)w[UQW_UNIQUE]; m.stats[UQS_CLUSTERS] = (double)w[UQW_CLUSTERS]; m.stats[UQS_LARGEST] = (double)w[UQW_LARGEST]; m.stats[UQS_ROUTE] = 0;
     m.stats[UQS_IDENT] = (double)w[UQW_IDENT]; m.stats[UQS_CONTAINED] = (double)w[UQW_CONTAINED]; m.stats[UQS_SINGLE] = (double)w[UQW_SINGLE]; m.stats[UQS_END_EXT] = (double)w[UQW_END_EXT];
     m.have = true;
     *n_unique = m.n_unique;
@@ -3027,6 +3089,179 @@ int l2r_uniq_out(l2r_ctx *c, uint8_t *merged, int32_t *uniq_of, int32_t *u_src, 
 }
 
 int l2r_uniq_stats(l2r_ctx *c, double *out, int n) { return stats_out(c ? c->uniq.stats : nullptr, UQS_N, out, n, "l2r_uniq_stats"); }
+
+// ---------------------------------------------------------------------------------------------- update-gtf -y: read classes and unique counts
+int l2r_summary_begin(l2r_ctx *c, const l2r_params *prm)
+{
+    if (!c || !prm) return fail(-1, "[l2r_summary_begin] null argument");
+    SummaryState &m = c->summary;
+    m.p = uniq_prm(prm);
+    m.on_host = route_is_host("L2R_SUMMARY_ROUTE");      // (tests, the comparator)
+    m.n = 0; m.x = 0; m.adds = 0;
+    m.tid.clear(); m.info.clear(); m.xs.clear(); m.xe.clear();
+    m.h = SummaryState::Host();
+    for (double &v : m.stats) v = 0;
+    m.stats[SMS_ROUTE] = m.on_host ? 1 : 0;
+    m.begun = true;
+    return 0;
+}
+
+// a buffer could not be had (the text of the failed allocation is in g_err): the stream waited for, -2 under the entry point's name
+static int summary_no_room(l2r_ctx *c, const char *who)
+{
+    const std::string why = g_err;
+    (void)hipStreamSynchronize(c->stream);
+    return fail(-2, "[%s] %s", who, why.c_str());
+}
+
+int l2r_summary_add(l2r_ctx *c, const l2r_summary_reads *r)
+{
+    if (!c || !r) return fail(-1, "[l2r_summary_add] null argument");
+    SummaryState &m = c->summary;
+    if (!m.begun) return fail(-1, "[l2r_summary_add] no l2r_summary_begin in front");
+    {   std::string msg;
+        if (summary_check_result(r->n, r->tid, r->res, msg)) return fail(-1, "%s", msg.c_str()); }
+    const size_t N = (size_t)r->n;
+    if (N == 0) { ++m.adds; m.stats[SMS_ADDS] = (double)m.adds; return 0; }
+    HIP_TRY(hipSetDevice(c->device));
+    int rc;
+    const bool run_res = !r->res;
+    if (run_res) {
+        if (!c->ran) return fail(-1, "[l2r_summary_add] no completed run on this context");
+        if ((rc = fetch_totals(c))) return rc;
+        if (!(c->want & L2R_WANT_RESULTS)) return fail(-1, "[l2r_summary_add] the last run kept no results (l2r_set_outputs without L2R_WANT_RESULTS)");
+        if (r->n != c->n_reads) return fail(-1, "[l2r_summary_add] %lld reads, the last run had %lld", (long long)r->n, (long long)c->n_reads);
+    }
+    const size_t X = run_res ? (size_t)c->h_totals[0] : (size_t)r->res->n_exons;
+    {   std::string msg;
+        if (summary_check_totals(m.n, m.x, r->n, (int64_t)X, msg)) return fail(-1, "%s", msg.c_str()); }
+    const size_t n0 = (size_t)m.n, x0 = (size_t)m.x;
+    if (m.on_host) {
+        SummaryState::Host &h = m.h;
+        try { h.tid.reserve(n0 + N); h.info.reserve(n0 + N); h.xs.reserve(x0 + X); h.xe.reserve(x0 + X); }
+        catch (const std::bad_alloc &) { return fail(-2, "[l2r_summary_add] no memory for %zu reads, %zu exons", n0 + N, x0 + X); }
+        if (run_res) {
+            std::vector<int64_t> off(N + 1); std::vector<uint8_t> f(X ? X : 1); std::vector<int32_t> ref(N);
+            h.info.resize(n0 + N); h.xs.resize(x0 + X); h.xe.resize(x0 + X);
+            l2r_result res{(int64_t)N, (int64_t)X, 0, off.data(), h.xs.data() + x0, h.xe.data() + x0, f.data(), h.info.data() + n0, ref.data()};
+            if ((rc = l2r_download(c, &res))) { h.info.resize(n0); h.xs.resize(x0); h.xe.resize(x0); return rc; }
+        } else {
+            h.info.insert(h.info.end(), r->res->info, r->res->info + N);
+            h.xs.insert(h.xs.end(), r->res->ex_start, r->res->ex_start + X); h.xe.insert(h.xe.end(), r->res->ex_end, r->res->ex_end + X);
+        }
+        h.tid.insert(h.tid.end(), r->tid, r->tid + N);
+    } else {
+        // room first: a failed allocation leaves the accumulators as they were
+        if (m.tid.reserve(c->stream, n0 + N) || m.info.reserve(c->stream, n0 + N) || m.xs.reserve(c->stream, x0 + X) || m.xe.reserve(c->stream, x0 + X)) return summary_no_room(c, "l2r_summary_add");
+        const hipMemcpyKind kind = run_res ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
+        const uint32_t *info = run_res ? c->info.p : r->res->info;
+        const int32_t *xs = run_res ? c->ex_start.p : r->res->ex_start, *xe = run_res ? c->ex_end.p : r->res->ex_end;
+        hipError_t e = hipMemcpyAsync(m.tid.p + n0, r->tid, N * 4, hipMemcpyHostToDevice, c->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(m.info.p + n0, info, N * 4, kind, c->stream);
+        if (e == hipSuccess && X) e = hipMemcpyAsync(m.xs.p + x0, xs, X * 4, kind, c->stream);
+        if (e == hipSuccess && X) e = hipMemcpyAsync(m.xe.p + x0, xe, X * 4, kind, c->stream);
+        const hipError_t sync = hipStreamSynchronize(c->stream);      // (the columns are the caller's)
+        if (e == hipSuccess) e = sync;
+        if (e != hipSuccess) return fail(-2, "[l2r_summary_add] %s", hipGetErrorString(e));
+        m.tid.n = m.info.n = n0 + N; m.xs.n = m.xe.n = x0 + X;
+    }
+    m.n += (int64_t)N; m.x += (int64_t)X; ++m.adds;
+    m.stats[SMS_READS] = (double)m.n; m.stats[SMS_EXONS] = (double)m.x; m.stats[SMS_ADDS] = (double)m.adds;
+    return 0;
+}
+
+extern "C++" {
+// summary_host over the host's copies of the accumulated reads (the checks first: -1 names the read)
+static int summary_on_host(SummaryState &m, const SummaryState::Host &h, bool checked, int64_t *counts)
+{
+    const size_t N = (size_t)m.n;
+    std::vector<int64_t> off(N + 1, 0);
+    for (size_t i = 0; i < N; ++i) off[i + 1] = off[i] + (int64_t)L2R_INFO_NEXON(h.info[i]);
+    if (off[N] != m.x) return fail(-2, "[l2r_summary_finish] the exon counts add up to %lld, %lld exons were added", (long long)off[N], (long long)m.x);
+    const SummaryReads r{m.n, h.tid.data(), h.info.data(), off.data(), h.xs.data(), h.xe.data()};
+    if (!checked) { std::string msg; if (summary_check(r, msg)) return fail(-1, "%s", msg.c_str()); }
+    summary_host(r, m.p, counts);
+    m.stats[SMS_ROUTE] = 1;
+    return 0;
+}
+
+// what a word of k_sum_class / k_sum_gather names: -1 and the text of the host route, or the device's inconsistency
+static int summary_bad_read(unsigned long long w, size_t N)
+{
+    const unsigned long long q = w >> 4; const int kind = (int)(w & 15ull);
+    if (q >= N || kind <= 0 || kind >= SUM_E_N) return fail(-2, "[l2r_summary_finish] the device names read %llu of %zu, kind %d", q, N, kind);
+    std::string msg; summary_read_fail(msg, (int64_t)q, kind);
+    return fail(-1, "%s", msg.c_str());
+}
+}
+
+int l2r_summary_finish(l2r_ctx *c, int64_t *counts)
+{
+    if (!c || !counts) return fail(-1, "[l2r_summary_finish] null argument");
+    SummaryState &m = c->summary;
+    if (!m.begun) return fail(-1, "[l2r_summary_finish] no l2r_summary_begin in front");
+    for (int k = 0; k < 2 * SUM_CLASSES; ++k) counts[k] = 0;
+    for (int k = SMS_CLUSTERS; k < SMS_N; ++k) m.stats[k] = 0;
+    const size_t N = (size_t)m.n, X = (size_t)m.x;
+    if (N == 0) return 0;
+    if (m.on_host) return summary_on_host(m, m.h, false, counts);
+    HIP_TRY(hipSetDevice(c->device));
+    UniqState &u = m.u;
+    int rc;
+    if ((rc = u.clk.begin(env_on("L2R_SORT_TIMING"), c->check_stages))) return rc;
+    const size_t n_tiles = (N + SUM_TILE - 1) / SUM_TILE;
+    if (m.cls.ensure(N) || m.src_off.ensure(N + 1) || m.tile_cnt.ensure(SUM_CLASSES * n_tiles + 1) || m.dst_off.ensure(N + 1) || m.src.ensure(N) || m.word.ensure(SUMW_N) || m.bad.ensure(1) ||
+        u.tid.ensure(N) || u.rev.ensure(N) || u.ex_off.ensure(N + 1) || u.xs.ensure(X ? X : 1) || u.xe.ensure(X ? X : 1)) return summary_no_room(c, "l2r_summary_finish");
+    HIP_TRY(hipMemsetAsync(m.bad.p, 0xff, sizeof(unsigned long long), c->stream));
+    HIP_TRY(hipMemsetAsync(m.word.p, 0, SUMW_N * sizeof(uint32_t), c->stream));
+    rc = u.clk.launch(c, &m.stats[SMS_K_CLASS], [&] {
+        hipLaunchKernelGGL(k_sum_class, dim3((unsigned)n_tiles), dim3(SUM_TILE), 0, c->stream, (int64_t)N, (const int32_t *)m.tid.p, (const uint32_t *)m.info.p, m.cls.p, m.src_off.p, m.tile_cnt.p,
+                           (int64_t)n_tiles, m.bad.p);
+        scan_u32(c, m.src_off.p, (int64_t)N, m.word.p + SUMW_EXONS);
+        scan_u32(c, m.tile_cnt.p, (int64_t)(SUM_CLASSES * n_tiles), m.word.p + SUMW_TILES);
+        hipLaunchKernelGGL(k_sum_place, dim3((unsigned)n_tiles), dim3(SUM_TILE), 0, c->stream, (int64_t)N, (const int32_t *)m.tid.p, (const uint32_t *)m.info.p, (const uint8_t *)m.cls.p,
+                           (const uint32_t *)m.tile_cnt.p, (int64_t)n_tiles, u.tid.p, u.rev.p, m.dst_off.p, m.src.p);
+        scan_u32(c, m.dst_off.p, (int64_t)N, m.word.p + SUMW_PLACED);
+    });
+    uint32_t w[SUMW_N] = {0};
+    unsigned long long bad = ~0ull;
+    // (a read k_sum_class has flagged is not reported yet: k_sum_gather may flag a smaller one, and neither harms it -- a read without
+    // exons copies nothing, a tid outside the domain is a key like any other; the totals below are what keeps its copies inside the arrays)
+    if ((rc = download_all(c, rc, {{w, m.word.p, sizeof w}}, "l2r_summary_finish"))) return rc;
+    if ((size_t)w[SUMW_TILES] != N || (size_t)w[SUMW_EXONS] != X || (size_t)w[SUMW_PLACED] != X)
+        return fail(-2, "[l2r_summary_finish] %u reads placed of %zu, %u and %u exons counted of %zu", w[SUMW_TILES], N, w[SUMW_EXONS], w[SUMW_PLACED], X);
+    const bool wave = wave_form((double)X / (double)N, "L2R_SUMMARY_WAVE");
+    m.stats[SMS_WAVE] = wave ? 1 : 0;
+    const SumGather g{(int64_t)N, m.src.p, m.src_off.p, m.dst_off.p, m.xs.p, m.xe.p, (uint32_t)X, u.ex_off.p, u.xs.p, u.xe.p, m.bad.p};
+    rc = u.clk.launch(c, &m.stats[SMS_K_GATHER], [&] {
+        const dim3 grid((unsigned)(((wave ? N * 64 : N) + 255) / 256));
+        if (wave) hipLaunchKernelGGL(k_sum_gather<true>, grid, dim3(256), 0, c->stream, g);
+        else hipLaunchKernelGGL(k_sum_gather<false>, grid, dim3(256), 0, c->stream, g);
+    });
+    if ((rc = download_all(c, rc, {{&bad, m.bad.p, sizeof bad}}, "l2r_summary_finish"))) return rc;
+    if (bad != ~0ull) return summary_bad_read(bad, N);
+    uint32_t uw[UQW_N] = {0};
+    if ((rc = uniq_device(c, u, N, m.p, "l2r_summary_finish", &m.stats[SMS_K_CUT], &m.stats[SMS_K_MERGE], &m.stats[SMS_K_TAKE], uw))) return rc;
+    if (uw[UQW_UNSORTED]) {                             // a class's (tid, start) descends somewhere: the accumulated columns fetched, the exact host routine
+        for (int k = SMS_K_CLASS; k < SMS_N; ++k) m.stats[k] = 0;
+        SummaryState::Host h;
+        h.tid.resize(N); h.info.resize(N); h.xs.resize(X ? X : 1); h.xe.resize(X ? X : 1);
+        if ((rc = download_all(c, 0, {{h.tid.data(), m.tid.p, N * 4}, {h.info.data(), m.info.p, N * 4}, {h.xs.data(), m.xs.p, X * 4}, {h.xe.data(), m.xe.p, X * 4}}, "l2r_summary_finish"))) return rc;
+        return summary_on_host(m, h, true, counts);
+    }
+    rc = u.clk.launch(c, &m.stats[SMS_K_TAKE], [&] {
+        hipLaunchKernelGGL(k_sum_count, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, c->stream, (int64_t)N, (const int32_t *)u.tid.p, (const uint8_t *)u.merged.p, m.word.p);
+    });
+    if ((rc = download_all(c, rc, {{w, m.word.p, sizeof w}}, "l2r_summary_finish"))) return rc;
+    uint64_t reads = 0, uniq = 0;
+    for (int k = 0; k < SUM_CLASSES; ++k) { reads += w[SUMW_READS + k]; uniq += w[SUMW_UNIQUE + k]; }
+    if (reads != N || uniq != uw[UQW_UNIQUE]) return fail(-2, "[l2r_summary_finish] %llu reads counted of %zu, %llu pushed offers of %u entries", (unsigned long long)reads, N, (unsigned long long)uniq, uw[UQW_UNIQUE]);
+    for (int k = 0; k < SUM_CLASSES; ++k) { counts[k] = (int64_t)w[SUMW_READS + k]; counts[SUM_CLASSES + k] = (int64_t)w[SUMW_UNIQUE + k]; }
+    m.stats[SMS_ROUTE] = 0; m.stats[SMS_CLUSTERS] = (double)uw[UQW_CLUSTERS]; m.stats[SMS_LARGEST] = (double)uw[UQW_LARGEST];
+    return 0;
+}
+
+int l2r_summary_stats(l2r_ctx *c, double *out, int n) { return stats_out(c ? c->summary.stats : nullptr, SMS_N, out, n, "l2r_summary_stats"); }
 
 }  // extern "C"
 

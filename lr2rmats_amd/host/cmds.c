@@ -359,7 +359,7 @@ int h_job_finish_part(h_job *j, int64_t lo, int64_t hi, const l2r_result *res, c
     o.out_gtf = open_part(j->out_path[0] ? j->out_path[0] : stdout_base, suffix);
     o.exon_bed = open_part(j->out_path[1], suffix); o.bam_gtf = open_part(j->out_path[2], suffix); o.bam_detail = open_part(j->out_path[3], suffix);
     o.known_gtf = open_part(j->out_path[4], suffix); o.novel_gtf = open_part(j->out_path[5], suffix); o.unrecog_gtf = open_part(j->out_path[6], suffix);
-    o.summary = NULL; o.summary_counts = counters; o.no_detail_header = !first_part;
+    o.summary = NULL; o.summary_counts = counters; o.no_detail_header = !first_part; o.class_counts = NULL;
     h_part_genes_free(&j->part_genes); o.part_genes = &j->part_genes;
     if (!o.out_gtf) h_fatal("update_gtf", "a partitioned run needs -o or a base path for the updated GTF");
     h_reads part = j->reads;                                   /* a view: per-read arrays shifted, string table shared */
@@ -403,6 +403,8 @@ static void *tail_part_main(void *arg)
     }
     o.out_gtf = fs[0]; o.exon_bed = fs[1]; o.bam_gtf = fs[2]; o.bam_detail = fs[3]; o.known_gtf = fs[4]; o.novel_gtf = fs[5]; o.unrecog_gtf = fs[6];
     o.summary = NULL; o.summary_counts = t->cnt; o.no_detail_header = !t->first; o.part_genes = &t->genes;
+    static const int64_t no_class_counts[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    if (o.class_counts) o.class_counts = no_class_counts;   /* the part runs none of the four merges; finish_threaded's total takes the engine's numbers once */
     h_reads part = *t->reads;
     part.n = t->hi - t->lo; part.tid += t->lo; part.pos += t->lo; part.rev += t->lo; part.qname += t->lo; part.cig_off += t->lo;
     if (part.tid_name) part.tid_name += t->lo;
@@ -561,6 +563,7 @@ static int finish_threaded(h_job *j, const h_reads *reads, const h_update_opts *
         const int32_t tid = parts[k].hi > parts[k].lo ? reads->tid[parts[k].lo] : 0;
         for (int q = 0; q < 2; ++q) total[gene_cnt[q]] -= gene_fix_join(&fix[q], tid, parts[k].genes.first_gids[q], parts[k].genes.n_first[q]);
     }
+    if (files->class_counts) h_summary_class_counters(total, files->class_counts);
     const double t_join = h_now() - t_w0;
     for (int q = 0; q < n_wr; ++q) pthread_join(wth[q], NULL);
     const double t_write = h_now() - t_w0;
@@ -967,9 +970,49 @@ static void lists_done(const char *who, lists_sink *d)
     d->ref_off = NULL; d->ref_names = NULL;
 }
 
+/* The read classes of summary.txt (-y) through the engine (l2r_summary_begin / _add / _finish, include/lr2rmats_hip.h): every engine
+ * shard's reads join the unit's accumulators while the shard's results still lie in HBM (res == NULL), and behind the last shard the
+ * four merges of the summary are made as one on the device.  The eight numbers reach the tail in h_update_opts.class_counts.
+ * L2R_SUMMARY_ROUTE=host: the engine's host routine; =off: the tail's own four lists.  A failure of the unit -- reads outside its domain
+ * (-1), memory (-2) -- does not end the run: the tail counts, and the route is reported as off.  L2R_TIMING=1: one line on stderr. */
+typedef struct {
+    int begun, failed, have;
+    int64_t counts[8];
+} summary_sink;
+
+static int summary_timing(void) { const char *tm = getenv("L2R_TIMING"); return tm && atoi(tm) != 0; }
+
+/* the stderr line of L2R_TIMING=1; st: l2r_summary_stats (reads, exons, adds, route, clusters, largest), k: the eight counts -- zeros where the tail counts */
+static void summary_line(const char *who, const char *route, const double *st, const int64_t *k)
+{
+    if (!summary_timing()) return;
+    fprintf(stderr, "[%s] summary classes: route %s, %lld reads in %lld adds, known %lld (%lld unique), reliable %lld (%lld unique), unreliable %lld (%lld unique), "
+            "unrecognised %lld (%lld unique), %lld clusters, largest %lld\n", who, route, (long long)st[0], (long long)st[2],
+            (long long)k[0], (long long)k[4], (long long)k[1], (long long)k[5], (long long)k[2], (long long)k[6], (long long)k[3], (long long)k[7], (long long)st[4], (long long)st[5]);
+}
+
+static void summary_shard(l2r_ctx *ctx, const l2r_params *prm, summary_sink *d, const int32_t *tid, int64_t n)
+{
+    if (d->failed) return;
+    if (!d->begun) { if (l2r_summary_begin(ctx, prm)) { d->failed = 1; return; } d->begun = 1; }
+    const l2r_summary_reads rd = { n, tid, NULL };
+    if (n > 0 && l2r_summary_add(ctx, &rd)) d->failed = 1;
+}
+
+static void summary_done(l2r_ctx *ctx, const char *who, const l2r_params *prm, summary_sink *d)
+{
+    if (!d->begun && !d->failed) summary_shard(ctx, prm, d, NULL, 0);      /* (no record) */
+    if (!d->failed && l2r_summary_finish(ctx, d->counts)) d->failed = 1;
+    d->have = !d->failed;
+    double st[7] = {0, 0, 0, 0, 0, 0, 0};
+    if (d->have) (void)l2r_summary_stats(ctx, st, 7);
+    else { if (summary_timing()) fprintf(stderr, "[%s] summary classes: the engine declined (%s)\n", who, l2r_last_error()); memset(d->counts, 0, sizeof d->counts); }
+    summary_line(who, !d->have ? "off" : st[3] != 0 ? "host" : "device", st, d->counts);
+}
+
 static void run_engine(const char *who, const l2r_params *prm, const l2r_annotation *a, const l2r_junctions *s,
                        const l2r_reads *r, h_result *out, int64_t **acc_read, detail_sink *detail /* NULL: none; only with acc_read == NULL */,
-                       lists_sink *lists /* likewise */)
+                       lists_sink *lists /* likewise */, summary_sink *summary /* likewise */)
 {
     int anno_set = 0;
     l2r_ctx *ctx = engine_take(who, &anno_set);
@@ -1012,6 +1055,7 @@ static void run_engine(const char *who, const l2r_params *prm, const l2r_annotat
         if (exons) for (int64_t k = 0; k <= add_rows; ++k) out->ex_off[rows + k] += exons;          /* shard-local -> global offsets */
         if (detail && !acc_read) detail_shard(ctx, who, detail, lo, hi, out);
         if (lists && !acc_read) lists_shard(ctx, who, lists, lo, hi, out);
+        if (summary && !acc_read) summary_shard(ctx, prm, summary, r->tid + lo, hi - lo);
         rows += add_rows; exons += add_ex;
         lo = hi;
     } while (lo < r->n_reads);
@@ -1025,6 +1069,7 @@ static void run_engine(const char *who, const l2r_params *prm, const l2r_annotat
         detail_done(who, detail);
     }
     if (lists && !acc_read) lists_done(who, lists);
+    if (summary && !acc_read) summary_done(ctx, who, prm, summary);
     h_stage_time("engine: upload, kernels, download");
     l2r_destroy(ctx);
     if ((detail || lists) && !acc_read) h_stage_time("engine: context destroyed");
@@ -1419,7 +1464,7 @@ static int update_gtf_multi(h_job *j, int n_gpus, int gathered)
                 off = (int64_t *)h_malloc((size_t)(hi - lo + 1) * 8);
                 for (int64_t i = 0; i <= hi - lo; ++i) off[i] = r.cig_off[lo + i] - r.cig_off[lo];
                 sub.cig_off = off; sub.first_read_index = lo;
-                run_engine("update_gtf", &prm, &a, &s, &sub, &out, NULL, NULL, NULL);
+                run_engine("update_gtf", &prm, &a, &s, &sub, &out, NULL, NULL, NULL, NULL);
             } else result_reserve(&out, 0, 0);
             l2r_result res = { out.n, out.n_ex, out.n_ex, out.ex_off, out.ex_start, out.ex_end, out.ex_flag, out.info, out.ref_tx };
             h_job_finish_part(j, lo, hi, &res, suffix, tmp_base, k == 0, cnt);
@@ -1562,7 +1607,13 @@ int h_cmd_update_gtf(int argc, char **argv)
         lists_sink lsink; memset(&lsink, 0, sizeof lsink);
         for (int k = 0; k < 4; ++k) lsink.out[k].fp = *list_fp[k];
         lsink.o = &j->o; lsink.chr = &j->chr; lsink.reads = &j->reads; lsink.anno = &j->anno; lsink.n_sj = s.n;
-        run_engine("update_gtf", &prm, &a, &s, &r, &out, NULL, by_engine ? &sink : NULL, lists_by_engine ? &lsink : NULL);
+        /* the read classes of summary.txt likewise (summary_shard): the tail runs none of its four merges; L2R_SUMMARY_ROUTE=off: it does */
+        const char *sr = getenv("L2R_SUMMARY_ROUTE");
+        const int summary_by_engine = j->o.summary && !(sr && !strcmp(sr, "off"));
+        summary_sink ssink; memset(&ssink, 0, sizeof ssink);
+        run_engine("update_gtf", &prm, &a, &s, &r, &out, NULL, by_engine ? &sink : NULL, lists_by_engine ? &lsink : NULL, summary_by_engine ? &ssink : NULL);
+        if (ssink.have) j->o.class_counts = ssink.counts;
+        else if (j->o.summary && !summary_by_engine) { const double st0[7] = {0, 0, 0, 0, 0, 0, 0}; summary_line("update_gtf", "off", st0, ssink.counts); }
         file_closer closer; memset(&closer, 0, sizeof closer);
         if (by_engine) files_close_start(&closer, &j->o.bam_detail);
         else if (j->o.bam_detail) { const char *tm = getenv("L2R_TIMING"); if (tm && atoi(tm) != 0) fprintf(stderr, "[update_gtf] detail text: route off, 0 rows, 0 bytes, 0 batches\n"); }
@@ -1574,7 +1625,7 @@ int h_cmd_update_gtf(int argc, char **argv)
         if (by_engine || lists_by_engine) h_stage_time("engine-written files closed");
     } else {
         int64_t *idx = NULL;
-        run_engine("update_gtf", &prm, &a, &s, &r, &out, &idx, NULL, NULL);
+        run_engine("update_gtf", &prm, &a, &s, &r, &out, &idx, NULL, NULL, NULL);
         l2r_result res = { out.n, out.n_ex, out.n_ex, out.ex_off, out.ex_start, out.ex_end, out.ex_flag, out.info, out.ref_tx };
         rc = h_job_finish_accepted(j, &res, idx);
         free(idx);
@@ -1603,7 +1654,7 @@ static void exons_only(const char *who, const char *fn, const l2r_params *prm, h
     int64_t zero_off = 0; a.tx_ex_off = &zero_off;
     l2r_junctions s; memset(&s, 0, sizeof s);
     l2r_reads r = { reads->n, reads->n_cig, reads->tid, reads->pos, reads->rev, reads->cig_off, reads->cig, 0, reads->cig_sum };
-    run_engine(who, prm, &a, &s, &r, out, NULL, NULL, NULL);
+    run_engine(who, prm, &a, &s, &r, out, NULL, NULL, NULL, NULL);
 }
 
 /* src/gtf.c:597-604 print_trans: gene_id + transcript_id only, exons always ascending */

@@ -240,6 +240,8 @@ typedef struct {
     int no_detail_header;        /* parts after the first of a partitioned run: detail.txt without its column line */
     int64_t *summary_counts;     /* non-NULL: the summary counters go here (H_N_SUMMARY values) instead of being printed */
     h_part_genes *part_genes;    /* non-NULL (parts of a partitioned run): filled for the caller's fix-up of the gene counters */
+    const int64_t *class_counts; /* non-NULL: the eight numbers of l2r_summary_finish -- the reads of the classes known, reliable, unreliable,
+                                  * unrecognised, then their unique transcripts; the tail then runs none of the four merges of the summary */
 } h_update_opts;
 
 /* Everything update_gtf() does after check_with_anno_trans/check_with_short_sj:
@@ -259,6 +261,8 @@ void h_list_rows(FILE *fp, const h_update_opts *o, const h_chroms *chr, const h_
                  int list, int64_t lo, int64_t hi);
 
 void h_write_summary_text(FILE *s, int anno_genes, int anno_tx, const int64_t *counters);
+/* the eight numbers of l2r_summary_finish into the summary counters 6 and 8-14 */
+void h_summary_class_counters(int64_t *counters, const int64_t *class_counts);
 
 /* The GTF text of a selection of blocks through the engine (l2r_gtftext_*: composed on the device, or by the engine's host routine with
  * L2R_GTX_ROUTE=host), written to fp batch by batch (L2R_GTX_BATCH blocks, default 1 Mi, and L2R_GTX_TEXT_MAX bytes, default 1 GiB).

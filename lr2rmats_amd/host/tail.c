@@ -444,6 +444,13 @@ void h_write_summary_text(FILE *s, int anno_genes, int anno_tx, const int64_t *k
     fprintf(s, "\n==================================\n");
 }
 
+void h_summary_class_counters(int64_t *k, const int64_t *cc)
+{
+    k[6] = cc[0]; k[8] = cc[4];                     /* known reads, unique */
+    k[9] = cc[1]; k[10] = cc[2]; k[11] = cc[5]; k[12] = cc[6];      /* novel: reliable, unreliable, their unique */
+    k[13] = cc[3]; k[14] = cc[7];                   /* unrecognised, unique */
+}
+
 static void summary_and_bed(const tail_ctx *c, const m_list *U)
 {
     /* src/update_gtf.c:421-587 print_trans_summary */
@@ -485,11 +492,18 @@ static void summary_and_bed(const tail_ctx *c, const m_list *U)
     }
     if (c->o->part_genes) { memset(c->o->part_genes, 0, sizeof *c->o->part_genes); part_genes_take(c->o->part_genes, 0, G, upd_genes); }
     if (c->o->summary || c->o->summary_counts) {
-        /* :496-528: classes of every input read + unique counts through merge_trans on fresh lists */
+        /* :496-528: classes of every input read + unique counts through merge_trans on fresh lists -- or, where the engine has made
+         * them (class_counts, l2r_summary_finish), the genes of the known reads alone */
+        const int by_engine = c->o->class_counts != NULL;
         int n_known = 0, n_rel = 0, n_unrel = 0, n_unrec = 0;
         m_list uk, ur, uu, un; memset(&uk, 0, sizeof uk); memset(&ur, 0, sizeof ur); memset(&uu, 0, sizeof uu); memset(&un, 0, sizeof un);
         for (int64_t i = 0; i < r->n; ++i) {
-            const uint32_t info = r->info[i]; const int64_t off = r->ex_off[i]; const int n = (int)L2R_INFO_NEXON(info);
+            const uint32_t info = r->info[i];
+            if (by_engine) {
+                if (info & L2R_INFO_KNOWN) add_gene(&G, &known_genes, &g_cap, c->reads->tid[i], gene_id_of(c, r->ref_tx[i]));
+                continue;
+            }
+            const int64_t off = r->ex_off[i]; const int n = (int)L2R_INFO_NEXON(info);
             m_cand t = { c->reads->tid[i], r->ex_start[off], r->ex_end[off + n - 1], n, (uint8_t)((info & L2R_INFO_REV) != 0), r->ex_start + off, r->ex_end + off, NULL };
             m_list *dst;
             if (info & L2R_INFO_KNOWN) { ++n_known; add_gene(&G, &known_genes, &g_cap, t.tid, gene_id_of(c, r->ref_tx[i])); dst = &uk; }
@@ -500,6 +514,7 @@ static void summary_and_bed(const tail_ctx *c, const m_list *U)
         if (c->o->part_genes) part_genes_take(c->o->part_genes, 1, G, known_genes);
         int64_t cnt[H_N_SUMMARY] = { upd_genes, U->n, partial, e_n, (int64_t)d_n + a_n, j_n, n_known, known_genes, uk.n,
                                      n_rel, n_unrel, ur.n, uu.n, n_unrec, un.n, 0 };
+        if (by_engine) h_summary_class_counters(cnt, c->o->class_counts);
         if (c->o->summary_counts) memcpy(c->o->summary_counts, cnt, sizeof cnt);
         if (c->o->summary) h_write_summary_text(c->o->summary, c->anno->gene_n, (int)c->anno->n_tx, cnt);
         m_free(&uk); m_free(&ur); m_free(&uu); m_free(&un);
