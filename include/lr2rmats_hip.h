@@ -766,6 +766,102 @@ int          l2r_detail_lines(l2r_ctx *ctx, int64_t first, int64_t max_rows, int
 int          l2r_detail_out(l2r_ctx *ctx, uint8_t *text, int64_t cap);
 int          l2r_detail_stats(l2r_ctx *ctx, double *out, int n);
 
+/* ---- the novel list of `update-gtf` (host/tail.c h_update_tail, summary_and_bed; src/update_gtf.c:181-295, :421-587, :939-964): the novel
+ * reads of a run merged into the list U behind the updated GTF, the kept novel exons, sites, junctions and genes behind `-E` and the
+ * "Updated information" block of `-y`.  The rule, stated here once, for runs in which no read is split.
+ * Offers.  Read i is an offer where FULL && !KNOWN && KNOWN_SITE and (!has_sj || SJ_PASS) -- read_route == T_NOVEL_WHOLE.  Its strand is
+ * L2R_INFO_REV, its chain and exon flags are the results'.  A read with FULL && !KNOWN && KNOWN_SITE, has_sj && !SJ_PASS and split
+ * (l2r_params.split_trans) set is split-route: such reads are counted, and where there is one l2r_novel_finish refuses (-3).
+ * List U.  The offers in input order go to ONE merge_trans list; the rule is l2r_uniq_merge's with -c, -d, -D, -f of l2r_params.  Entry e
+ * has src, the read that created it (global index: the reads added before + its place in its add), tid, rev and ref = ref_tx of src, its
+ * coverage cov, the chain of src with xs[0] and xe[n - 1] replaced by the widened start and end, and the flags of src.
+ * Novel items.  Over the entries in list order and j ascending, reading the entry's widened chain:
+ *     exon          (tid, xs[j], xe[j]) where f[j] & NOVEL_EXON; it carries cov, rev and a type: T for j == 0 or j == n - 1 where n > 1,
+ *                   I in between, S where n == 1
+ *     donor         (tid, xe[j]) where j < n - 1 and NOVEL_DON          acceptor   (tid, xs[j + 1]) where j < n - 1 and NOVEL_ACC
+ *     junction      (tid, xe[j], xs[j + 1]) where j < n - 1 and NOVEL_JUNC
+ *     gene          (tid, gene(ref)) per entry
+ *     known gene    (tid[i], gene(ref_tx[i])) of every read with KNOWN, whether FULL or not, in input order
+ * gene() is the ordinal of the gene-id string among the annotation's distinct gene-id strings (tx_gene[ref]); ref < 0 stands for the
+ * string `NA` and takes na_gene, which is the ordinal of an annotation gene called `NA` where there is one.
+ * Every list keeps the first item of every key, in the order of first appearance; a kept exon row takes the type and strand of the first
+ * item and score = the sum of cov over the key.  With tid not descending this is what the backward scans of summary_and_bed leave.
+ * The two gene lists then lose what add_gene's order of tests drops on top: it compares the gene BEFORE it stops at a smaller tid, so
+ * an item whose gene equals that of the newest kept row of a smaller tid is not kept either (one pass in list order; a row that goes
+ * takes no part later).  Seen from the lists: the same gene on two tids counts twice unless it was the newest gene when the first ended.
+ * BED line of a kept exon row: <ref>\t<start - 1>\t<end>\t<T|I|S>_exon\t<score>\t<+|->\n, numbers as %d (a start of 0 prints -1).
+ * Counts, in the order of h_write_summary_text: counts[0] genes, [1] entries, [2] 0, [3] exons, [4] donors + acceptors, [5] junctions,
+ * [6] 0 (not this unit's), [7] known genes.
+ *     l2r_novel_begin        -c, -d, -D, -f and -s of prm; has_sj; the reference names (as in l2r_bed_params); tx_gene[0, n_tx) and
+ *                            na_gene; the accumulators are emptied
+ *     l2r_novel_add          n reads with their tid and results.  res == NULL: the results of the context's last l2r_run where they lie
+ *                            in HBM (n = its reads); otherwise the arrays of an l2r_download, which are uploaded.  The offers' columns,
+ *                            chains and flags and the known reads' (tid, gene) are appended to accumulators in HBM, which grow by
+ *                            doubling.  n == 0 is fine.  -2: an allocation failed, the accumulators are as they were
+ *     l2r_novel_finish       merges, makes and keeps; counts[0..7] as above.  -3 where there are split-route reads (it says how many)
+ *     l2r_novel_entries_out  per entry src, start, end, cov; any pointer may be null
+ *     l2r_novel_rows_out     the kept rows of one list (L2R_NOVEL_EXON ..): tid, a, b -- exon (start, end), site (coordinate, 0),
+ *                            junction (donor, acceptor), gene (ordinal, 0) -- and for exons score and meta = type | rev << 2 (type 0 T,
+ *                            1 I, 2 S); any pointer may be null.  Tests and tools
+ *     l2r_novel_lines        one batch of text.  which = L2R_NOVEL_BED: kept exon rows from `first` while their count stays within
+ *                            max_rows and the sum of their bytes within max_bytes and below 2^32 - 64 -- always at least one.  Batches
+ *                            concatenated are the whole text.  which = L2R_NOVEL_GTF, behind l2r_novel_names: blocks (entries) of the
+ *                            updated GTF, cut and composed by l2r_gtftext_lines
+ *     l2r_novel_names        the updated GTF.  Entry e is the block of form L2R_GTX_READ with the overrides start, end and cov, g / G the
+ *                            gene id / gene name of annotation transcript ref (`NA` where ref < 0), t = tid_name[e], T = qname[e] -- the
+ *                            bytes print_merged writes for a whole entry.  The caller fetches src (l2r_novel_entries_out) and sends a
+ *                            names table for the entries alone.  The GTF-text unit (l2r_gtftext_*) is set up over the offers where
+ *                            they lie in HBM -- its rows are the accumulators' columns and chains, copied inside HBM, its blocks the
+ *                            entries -- and measures; *n_lines and *n_bytes are the totals.  It takes that unit's state: rows, blocks
+ *                            and text of an earlier l2r_gtftext_* call on the context are gone.  A caller that uses the read lists
+ *                            (l2r_gtftext_reads / _list) on the same context calls this behind the last of them and sets them up again
+ *                            afterwards.  qname / tid_name at or beyond names_len are refused (-4).  Under L2R_NOVEL_ROUTE=host the rows go
+ *                            through l2r_gtftext_rows, which reads L2R_GTX_ROUTE itself: the text is still composed by the kernels
+ *                            unless that is host as well.  The domain errors of a GTF block (a
+ *                            name of 255 bytes or more, ...) surface here with -1.  Needs src and the gene tables at the begin
+ *     l2r_novel_out          the text of the last l2r_novel_lines; cap < n_bytes fails and writes nothing
+ * Domain errors fail l2r_novel_finish with -1 and name the smallest read (global index) that has one, and of its kinds the first: a
+ * tid outside [0, n_ref), a read with no exon, ref at or beyond n_tx -- looked for in every read -- and a negative coordinate, looked for
+ * in the chains of the offers.  l2r_novel_add fails with -1 where the totals reach 2^31 reads or 2^32 - 64 exons, or where the arrays of
+ * res do not fit together.  A refusal leaves the unit usable: the next l2r_novel_begin starts afresh.
+ * On the device (csrc/l2r_novel.hip.h) where (tid, start) does not descend over the offers and tid does not descend over the known
+ * reads; other input is fetched and takes the exact host routine novel_host -- uniq_host and the literal backward scans -- as every input
+ * does under L2R_NOVEL_ROUTE=host (read at l2r_novel_begin: the engine then keeps host copies).  L2R_NOVEL_WAVE=0|1 forces the thread
+ * or the wave form of the chain copy.  The text buffer has 64 bytes of slack; with L2R_CHECK=1 they are filled with a pattern in front of
+ * the write kernel and looked at behind it.
+ * NOTE: route 0 does not mean that every kept row was made on the device alone.  The kernels keep the first item of every key of all six
+ * lists; the rows of the two GENE lists then come to the host (at most genes x chromosomes of them), where add_gene's last test is made,
+ * and l2r_novel_rows_out serves lists 4 and 5 from host memory on both routes.
+ * l2r_novel_stats: out[0] reads, [1] offers, [2] split-route reads, [3] known reads, [4] adds, [5] route (0 device, 1 host), [6] clusters,
+ * [7] offers of the largest cluster, [8] entries, [9] hits, [10] entries a hit has widened, [11..16] items and [17..22] kept rows of the
+ * six lists, [23] 1 where the wave form copied the chains of the last add, [24] 1 where the guard bytes are intact or were not checked;
+ * with L2R_SORT_TIMING=1 in the environment device milliseconds of [25] the selection (summed over the adds), [26] the merge, [27] the
+ * items, [28] the two sort stages, [29] heads, sums and compaction, [30] k_nov_bed_measure, and, summed over the batches, [31] the
+ * scans and [32] k_nov_bed_write; n = words of out (up to 33). */
+#define L2R_NOVEL_GTF 0
+#define L2R_NOVEL_BED 1
+#define L2R_NOVEL_EXON 0
+#define L2R_NOVEL_DON 1
+#define L2R_NOVEL_ACC 2
+#define L2R_NOVEL_JUNC 3
+#define L2R_NOVEL_GENE 4
+#define L2R_NOVEL_KNOWN_GENE 5
+typedef struct { int32_t n_ref; const int64_t *ref_off; const uint8_t *ref_names;          /* as l2r_bed_params */
+                 int64_t n_tx; const uint32_t *tx_gene; uint32_t na_gene; int32_t has_sj;
+                 int32_t src_len; const uint8_t *src;                       /* the updated GTF: the source string (NULL: no GTF text) ... */
+                 int64_t anno_names_len; const uint8_t *anno_names; const uint32_t *tx_gid, *tx_gname;      /* ... and the gene tables, as in l2r_gtx_anno */
+               } l2r_novel_params;
+typedef struct { int64_t names_len; const uint8_t *names; const uint32_t *qname, *tid_name /* may be NULL */; } l2r_novel_name_table;   /* per entry: byte offsets into names */
+int          l2r_novel_begin(l2r_ctx *ctx, const l2r_params *prm, const l2r_novel_params *np);
+int          l2r_novel_add(l2r_ctx *ctx, const l2r_summary_reads *reads);
+int          l2r_novel_finish(l2r_ctx *ctx, int64_t counts[8]);
+int          l2r_novel_entries_out(l2r_ctx *ctx, int32_t *src, int32_t *start, int32_t *end, int32_t *cov);
+int          l2r_novel_names(l2r_ctx *ctx, const l2r_novel_name_table *names, int64_t *n_lines, int64_t *n_bytes);
+int          l2r_novel_rows_out(l2r_ctx *ctx, int list, int32_t *tid, int32_t *a, int32_t *b, int32_t *score, uint8_t *meta);
+int          l2r_novel_lines(l2r_ctx *ctx, int which, int64_t first, int64_t max_rows, int64_t max_bytes, int64_t *n_taken, int64_t *n_bytes);
+int          l2r_novel_out(l2r_ctx *ctx, uint8_t *text, int64_t cap);
+int          l2r_novel_stats(l2r_ctx *ctx, double *out, int n);
+
 #ifdef __cplusplus
 }
 #endif

@@ -43,6 +43,7 @@ EXPORTS = [
     "l2r_gtftext_anno", "l2r_gtftext_reads", "l2r_gtftext_list", "l2r_gtftext_list_out",
     "l2r_detail_begin", "l2r_detail_rows", "l2r_detail_lines", "l2r_detail_out", "l2r_detail_stats",
     "l2r_summary_begin", "l2r_summary_add", "l2r_summary_finish", "l2r_summary_stats",
+    "l2r_novel_begin", "l2r_novel_add", "l2r_novel_finish", "l2r_novel_entries_out", "l2r_novel_names", "l2r_novel_rows_out", "l2r_novel_lines", "l2r_novel_out", "l2r_novel_stats",
 ]
 SJ_E_UNKNOWN_TID = -3
 
@@ -304,6 +305,15 @@ def load_library():
         lib.l2r_summary_add.argtypes = [C.c_void_p, C.c_void_p]
         lib.l2r_summary_finish.argtypes = [C.c_void_p, C.c_void_p]
         lib.l2r_summary_stats.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
+        lib.l2r_novel_begin.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        lib.l2r_novel_add.argtypes = [C.c_void_p, C.c_void_p]
+        lib.l2r_novel_finish.argtypes = [C.c_void_p, C.c_void_p]
+        lib.l2r_novel_names.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        lib.l2r_novel_entries_out.argtypes = [C.c_void_p] + [C.c_void_p] * 4
+        lib.l2r_novel_rows_out.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 5
+        lib.l2r_novel_lines.argtypes = [C.c_void_p, C.c_int, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p]
+        lib.l2r_novel_out.argtypes = [C.c_void_p, C.c_void_p, C.c_int64]
+        lib.l2r_novel_stats.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
         _lib = lib
     return _lib
 
@@ -468,6 +478,23 @@ SUMMARY_COUNT_NAMES = ["known", "reliable", "unreliable", "unrecognised"]
 
 class CSummaryReads(C.Structure):
     _fields_ = [("n", C.c_int64), ("tid", C.c_void_p), ("res", C.c_void_p)]
+
+
+NOVEL_LIST_NAMES = ["exons", "donors", "acceptors", "junctions", "genes", "known_genes"]
+NOVEL_STAT_NAMES = (["reads", "offers", "split_reads", "known_reads", "adds", "route", "clusters", "largest_cluster", "entries", "hits", "widened"] +
+                    ["items_" + k for k in NOVEL_LIST_NAMES] + ["kept_" + k for k in NOVEL_LIST_NAMES] +
+                    ["wave_form", "guard_intact", "selection", "merge", "items", "sort", "heads + sums + compaction", "k_nov_bed_measure", "k_scan_u32 (text)", "k_nov_bed_write"])
+NOVEL_GTF, NOVEL_BED = 0, 1
+
+
+class CNovelParams(C.Structure):
+    _fields_ = [("n_ref", C.c_int32), ("ref_off", C.c_void_p), ("ref_names", C.c_void_p), ("n_tx", C.c_int64), ("tx_gene", C.c_void_p), ("na_gene", C.c_uint32),
+                ("has_sj", C.c_int32), ("src_len", C.c_int32), ("src", C.c_void_p), ("anno_names_len", C.c_int64), ("anno_names", C.c_void_p), ("tx_gid", C.c_void_p),
+                ("tx_gname", C.c_void_p)]
+
+
+class CNovelNameTable(C.Structure):
+    _fields_ = [("names_len", C.c_int64), ("names", C.c_void_p), ("qname", C.c_void_p), ("tid_name", C.c_void_p)]
 
 
 FUSION_STAT_NAMES = ["wave_form", "k_fusion_seg", "k_fusion_select", "k_filter_score", "k_filter_select"]
@@ -1010,6 +1037,100 @@ class Engine:
         out = np.zeros(len(SUMMARY_STAT_NAMES), np.float64)
         self._chk(self.lib.l2r_summary_stats(self.ctx, out.ctypes.data, len(out)))
         return {k: float(v) for k, v in zip(SUMMARY_STAT_NAMES, out)}
+
+    # ---- the novel list of `update-gtf` (include/lr2rmats_hip.h: l2r_novel_begin / _add / _finish / _entries_out / _rows_out / _lines / _out / _stats)
+    def novel_begin(self, ref_names, tx_gene, na_gene, has_sj=0, split=0, force_strand=0, ss_dis=0, end_dis=0x7fffffff, frac=0.8, source=None, anno_names=b"", tx_gid=None,
+                    tx_gname=None) -> None:
+        """The reference names (byte strings, by tid), the gene ordinal of every annotation transcript and NA's, whether a junction table
+        was set, and -s, -c, -d, -D, -f as the command's; the accumulators are emptied.  ``source`` with the annotation's gene tables
+        (``anno_names``: NUL-terminated strings, ``tx_gid`` / ``tx_gname``: byte offsets per transcript): the updated GTF can be composed."""
+        off, blob = pack_names(ref_names)
+        keep = blob if blob.size else np.zeros(1, np.uint8)
+        tx_gene = np.ascontiguousarray(tx_gene, np.uint32)
+        prm = Params(3, 3, 50, int(ss_dis), int(end_dis), 5, int(split), 0, 1, int(force_strand), float(frac))
+        src = None if source is None else np.frombuffer(bytes(source) + b"\0", np.uint8)
+        an = np.frombuffer(bytes(anno_names) + b"\0", np.uint8)
+        gid = np.ascontiguousarray(tx_gid if tx_gid is not None else [], np.uint32)
+        gname = np.ascontiguousarray(tx_gname if tx_gname is not None else [], np.uint32)
+        np_ = CNovelParams(len(off) - 1, off.ctypes.data, keep.ctypes.data, int(tx_gene.shape[0]), tx_gene.ctypes.data if tx_gene.size else None, int(na_gene), int(has_sj),
+                           0 if source is None else len(bytes(source)), None if src is None else src.ctypes.data, len(bytes(anno_names)), an.ctypes.data,
+                           gid.ctypes.data if gid.size else None, gname.ctypes.data if gname.size else None)
+        self._chk(self.lib.l2r_novel_begin(self.ctx, C.byref(prm), C.byref(np_)))
+
+    def novel_add(self, tid, res=None, n=None) -> None:
+        """``tid`` of the reads and ``res``, a Result (the arrays of a download), which is uploaded; None: the results of the last run where
+        they lie in HBM (``n`` overrides the read count, which must equal the run's reads)."""
+        tid = np.ascontiguousarray(tid, np.int32)
+        n = int(tid.shape[0]) if n is None else int(n)
+        keep, cres = [], None
+        if res is not None:
+            keep = [np.ascontiguousarray(res.ex_off, np.int64), np.ascontiguousarray(res.ex_start, np.int32), np.ascontiguousarray(res.ex_end, np.int32),
+                    np.ascontiguousarray(res.ex_flag, np.uint8), np.ascontiguousarray(res.info, np.uint32), np.ascontiguousarray(res.ref_tx, np.int32)]
+            x = int(keep[0][-1]) if keep[0].size else 0
+            keep = [a if a.size else np.zeros(1, a.dtype) for a in keep]
+            cres = CResult(n, x, x, keep[0].ctypes.data_as(_i64p), keep[1].ctypes.data_as(_i32p), keep[2].ctypes.data_as(_i32p), keep[3].ctypes.data_as(_u8p),
+                           keep[4].ctypes.data_as(_u32p), keep[5].ctypes.data_as(_i32p))
+        rd = CSummaryReads(n, tid.ctypes.data if tid.size else None, None if cres is None else C.addressof(cres))
+        self._chk(self.lib.l2r_novel_add(self.ctx, C.byref(rd)))
+
+    def novel_finish(self) -> list:
+        """The eight counts in the order of summary.txt: genes, entries, 0, exons, sites, junctions, 0, known genes.  A read outside the
+        domain raises L2RError (rc=-1) naming the smallest such read and the kind; split-route reads raise rc=-3."""
+        out = np.zeros(8, np.int64)
+        self._chk(self.lib.l2r_novel_finish(self.ctx, out.ctypes.data))
+        return [int(v) for v in out]
+
+    def novel_entries(self) -> dict:
+        """src, start, end, cov of the entries of the last novel_finish."""
+        u = int(self.novel_stats()["entries"])
+        out = {k: np.zeros(u, np.int32) for k in ("src", "start", "end", "cov")}
+        self._chk(self.lib.l2r_novel_entries_out(self.ctx, *[out[k].ctypes.data if u else None for k in ("src", "start", "end", "cov")]))
+        return out
+
+    def novel_names(self, names, qname, tid_name=None):
+        """The names table (bytes: NUL-terminated strings) and per entry the byte offsets of its read name and, or None, its transcript id:
+        the updated GTF is measured; (lines, bytes)."""
+        tab = np.frombuffer(bytes(names) + b"\0", np.uint8)
+        q = np.ascontiguousarray(qname, np.uint32)
+        t = None if tid_name is None else np.ascontiguousarray(tid_name, np.uint32)
+        nt = CNovelNameTable(len(bytes(names)), tab.ctypes.data, q.ctypes.data if q.size else None, None if t is None or not t.size else t.ctypes.data)
+        nl, nb = C.c_int64(0), C.c_int64(0)
+        self._chk(self.lib.l2r_novel_names(self.ctx, C.byref(nt), C.byref(nl), C.byref(nb)))
+        return int(nl.value), int(nb.value)
+
+    def novel_rows(self, which: int) -> dict:
+        """The kept rows of list ``which`` (0 exons .. 5 known genes): tid, a, b, score, meta."""
+        r = int(self.novel_stats()["kept_" + NOVEL_LIST_NAMES[which]])
+        out = {k: np.zeros(r, np.int32) for k in ("tid", "a", "b", "score")}
+        out["meta"] = np.zeros(r, np.uint8)
+        self._chk(self.lib.l2r_novel_rows_out(self.ctx, int(which), *[out[k].ctypes.data if r else None for k in ("tid", "a", "b", "score", "meta")]))
+        return out
+
+    def novel_lines(self, which=NOVEL_BED, first=0, max_rows=1 << 20, max_bytes=1 << 30):
+        """One batch of text: (rows taken, its bytes)."""
+        take, nb = C.c_int64(0), C.c_int64(0)
+        self._chk(self.lib.l2r_novel_lines(self.ctx, int(which), int(first), int(max_rows), int(max_bytes), C.byref(take), C.byref(nb)))
+        buf = np.zeros(max(int(nb.value), 1), np.uint8)
+        self._chk(self.lib.l2r_novel_out(self.ctx, buf.ctypes.data, int(nb.value)))
+        return int(take.value), buf[:int(nb.value)].tobytes()
+
+    def novel_text(self, which=NOVEL_BED, max_rows=1 << 20, max_bytes=1 << 30) -> bytes:
+        """The whole text, batch by batch; empty where there is no row."""
+        n = int(self.novel_stats()["kept_exons" if which == NOVEL_BED else "entries"])
+        parts, first = [], 0
+        while first < n:
+            take, text = self.novel_lines(which, first, max_rows, max_bytes)
+            if take < 1:
+                raise L2RError("l2r_novel_lines took no row")
+            parts.append(text)
+            first += take
+        return b"".join(parts)
+
+    def novel_stats(self) -> dict:
+        """l2r_novel_stats: see include/lr2rmats_hip.h; with L2R_SORT_TIMING=1 device milliseconds per kernel group."""
+        out = np.zeros(len(NOVEL_STAT_NAMES), np.float64)
+        self._chk(self.lib.l2r_novel_stats(self.ctx, out.ctypes.data, len(out)))
+        return {k: float(v) for k, v in zip(NOVEL_STAT_NAMES, out)}
 
     def set_annotation_cache(self, directory) -> None:
         """Keep the annotation tables on disk under ``directory`` (None: off); see include/lr2rmats_hip.h."""

@@ -32,6 +32,7 @@
 #include "l2r_readlist.hip.h"
 #include "l2r_detail.hip.h"
 #include "l2r_summary.hip.h"
+#include "l2r_novel.hip.h"
 #include "l2r_plan.hip.h"
 #include "l2r_tables.hip.h"
 #include "l2r_nameorder.hip.h"
@@ -328,6 +329,35 @@ struct SummaryState {
     double stats[SMS_N] = {0};                          // l2r_summary_stats
 };
 
+// The novel list of `update-gtf` (l2r_novel.hip.h): the parameters of l2r_novel_begin, what the selection of every l2r_novel_add since
+// has appended -- in HBM, or in `h` where the route of the begin is the host's -- the work of an add and of l2r_novel_finish, and its
+// results until the next begin: the entries and kept rows in HBM (the two gene lists on the host, where add_gene's last test is made), or
+// all of them in `out` where novel_host made them.  `u` holds the work of the merge kernels, as in SummaryState.
+struct NovelState {
+    bool begun = false, on_host = false, finished = false, rows_on_host = false;
+    UniqPrm p{0, 0, 0, 0.0f};
+    NovelPrm np{0, 0, 0u, 0, 0};
+    RefNames ref;
+    std::vector<uint32_t> h_tx_gene; DevBuf<uint32_t> tx_gene;
+    int64_t n = 0, x = 0, adds = 0, split = 0;          // reads, their exons, calls, split-route reads so far
+    AccBuf<int32_t> o_tid, o_ref, o_read, xs, xe, k_tid; AccBuf<uint8_t> o_rev, f; AccBuf<uint32_t> o_nex, k_gene;
+    NovelAcc h;
+    DevBuf<int32_t> a_tid, a_ref, a_xs, a_xe; DevBuf<uint32_t> a_off, a_info, cnt_x, tile_cnt, aword; DevBuf<uint8_t> a_f, bits;     // one add; cnt_x: n + 1, tile_cnt: 2 tiles + 1, aword: NOVW_*
+    std::vector<uint32_t> off32;
+    DevBuf<unsigned long long> bad;                     // the smallest read outside the domain << 4 | its kind
+    UniqState u;
+    DevBuf<uint32_t> o_off, cnt, hi, ia, ib, icov, order1, order, head, first, grp, sum, fword; DevBuf<uint8_t> imeta;     // the finish; fword: NOVF_*
+    DevBuf<int32_t> e_src, r_tid, r_a, r_b, r_score; DevBuf<uint8_t> r_meta;
+    int64_t n_entries = 0, row0[NOV_LISTS + 1] = {0}, kept[NOV_LISTS] = {0};
+    NovelOut out;
+    DevBuf<uint32_t> len, off, tword; std::vector<uint32_t> h_len; TextOut text;    // the BED text
+    double tstats[12] = {0};                            // text_batch's slots
+    bool has_gtf = false, gtf_ready = false; int last_which = L2R_NOVEL_BED;       // the updated GTF: the source string and gene tables came with the begin; l2r_novel_names has set the GTF-text unit up
+    std::vector<uint8_t> h_src; GeneTables genes; int64_t anno_len = 0;
+    DevBuf<uint32_t> e_qname, e_tidname;
+    double stats[NVS_N] = {0};                          // l2r_novel_stats
+};
+
 // The GTF block of `bam2gtf` / `unique-gtf` (l2r_gtftext.hip.h): the reference names, source string and form of l2r_gtftext_begin, the
 // transcripts of l2r_gtftext_rows, the selection of l2r_gtftext_blocks with what k_gtx_measure left per block, and the text of the last
 // l2r_gtftext_lines (in HBM, or on the host where the host route made it) until l2r_gtftext_out fetches it.  The route is read at
@@ -546,6 +576,7 @@ struct l2r_ctx {
     GtxState gtx;                           // `bam2gtf`, `unique-gtf`: the GTF text
     DetailState detail;                     // `update-gtf -A`: the detail table
     SummaryState summary;                   // `update-gtf -y`: read classes and unique counts
+    NovelState novel;                       // `update-gtf`: the novel list, its kept items, the BED text
 };
 
 // A launch (or a group of launches) on the context stream
@@ -3904,6 +3935,507 @@ int l2r_detail_out(l2r_ctx *c, uint8_t *text, int64_t cap)
 }
 
 int l2r_detail_stats(l2r_ctx *c, double *out, int n) { return stats_out(c ? c->detail.stats : nullptr, DTS_N, out, n, "l2r_detail_stats"); }
+
+// ---------------------------------------------------------------------------------------------- update-gtf: the novel list, its kept items, the BED text
+constexpr int NOVC_TOTAL = NOVC_N;                      // NovelState::tword: k_nov_bed_write's counters, then the scan's total
+constexpr int NOVEL_E_ARG = -4;                         // arguments and order of calls of the text entry points
+
+int l2r_novel_begin(l2r_ctx *c, const l2r_params *prm, const l2r_novel_params *np)
+{
+    if (!c || !prm || !np) return fail(-1, "[l2r_novel_begin] null argument");
+    NovelState &m = c->novel;
+    m.begun = false; m.finished = false; m.text.reset();
+    {   std::string msg;
+        if (novel_check_begin(prm, np->n_ref, np->ref_off, np->ref_names, np->n_tx, np->tx_gene, msg)) return fail(-1, "%s", msg.c_str()); }
+    m.p = uniq_prm(prm);
+    m.np = NovelPrm{np->n_ref, np->n_tx, np->na_gene, np->has_sj != 0, prm->split_trans != 0};
+    m.ref.set(np->n_ref, np->ref_off, np->ref_names);
+    m.h_tx_gene.assign((size_t)np->n_tx + 1, 0u);
+    if (np->n_tx) memcpy(m.h_tx_gene.data(), np->tx_gene, (size_t)np->n_tx * 4);
+    m.has_gtf = false; m.gtf_ready = false; m.last_which = L2R_NOVEL_BED;
+    if (np->src) {
+        if (np->src_len < 0 || np->src_len > L2R_GTX_SRC_MAX) return fail(-1, "[l2r_novel_begin] a source string of %d bytes (at most %d)", np->src_len, L2R_GTX_SRC_MAX);
+        {   std::string msg;
+            if (text_check_genes(np->n_tx, np->anno_names_len, np->anno_names, np->tx_gid, np->tx_gname, msg, "l2r_novel_begin")) return fail(-1, "%s", msg.c_str()); }
+        m.h_src.assign(np->src, np->src + np->src_len);
+        m.genes.set(np->n_tx, np->anno_names_len, np->anno_names, np->tx_gid, np->tx_gname);
+        m.anno_len = np->anno_names_len;
+        m.has_gtf = true;
+    }
+    m.on_host = route_is_host("L2R_NOVEL_ROUTE");       // (tests, the comparator)
+    m.n = 0; m.x = 0; m.adds = 0; m.split = 0; m.n_entries = 0;
+    m.o_tid.clear(); m.o_ref.clear(); m.o_read.clear(); m.o_rev.clear(); m.o_nex.clear(); m.xs.clear(); m.xe.clear(); m.f.clear(); m.k_tid.clear(); m.k_gene.clear();
+    m.h = NovelAcc(); m.out = NovelOut(); m.h_len.clear();
+    for (double &v : m.stats) v = 0;
+    m.stats[NVS_ROUTE] = m.on_host ? 1 : 0; m.stats[NVS_GUARD] = 1;
+    HIP_TRY(hipSetDevice(c->device));
+    int rc;
+    if ((rc = m.ref.upload(c)) || (rc = put_dev(c, m.tx_gene, m.h_tx_gene)) || (m.has_gtf && (rc = m.genes.upload(c))) || m.bad.ensure(1) || m.aword.ensure(NOVW_N) || m.fword.ensure(NOVF_N)) { (void)hipStreamSynchronize(c->stream); return rc ? rc : -2; }
+    HIP_TRY(hipMemsetAsync(m.bad.p, 0xff, sizeof(unsigned long long), c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    m.begun = true;
+    return 0;
+}
+
+int l2r_novel_add(l2r_ctx *c, const l2r_summary_reads *r)
+{
+    if (!c || !r) return fail(-1, "[l2r_novel_add] null argument");
+    NovelState &m = c->novel;
+    if (!m.begun) return fail(-1, "[l2r_novel_add] no l2r_novel_begin in front");
+    {   std::string msg;
+        if (novel_check_result(r->n, r->tid, r->res, msg)) return fail(-1, "%s", msg.c_str()); }
+    m.finished = false; m.gtf_ready = false; m.text.reset();
+    const size_t N = (size_t)r->n;
+    if (N == 0) { ++m.adds; m.stats[NVS_ADDS] = (double)m.adds; return 0; }
+    HIP_TRY(hipSetDevice(c->device));
+    int rc;
+    const bool run_res = !r->res;
+    if (run_res) {
+        if (!c->ran) return fail(-1, "[l2r_novel_add] no completed run on this context");
+        if ((rc = fetch_totals(c))) return rc;
+        if (!(c->want & L2R_WANT_RESULTS)) return fail(-1, "[l2r_novel_add] the last run kept no results (l2r_set_outputs without L2R_WANT_RESULTS)");
+        if (r->n != c->n_reads) return fail(-1, "[l2r_novel_add] %lld reads, the last run had %lld", (long long)r->n, (long long)c->n_reads);
+    }
+    const size_t X = run_res ? (size_t)c->h_totals[0] : (size_t)r->res->n_exons;
+    {   std::string msg;
+        if (novel_check_totals(m.n, m.x, r->n, (int64_t)X, msg)) return fail(-1, "%s", msg.c_str()); }
+    if (m.on_host) {
+        NovelAcc &h = m.h;
+        const size_t o0 = h.o_tid.size(), x0 = h.xs.size(), k0 = h.k_tid.size();
+        const int64_t split0 = h.split, bad0 = h.bad; const int kind0 = h.bad_kind;
+        try {
+            if (run_res) {
+                std::vector<int64_t> off(N + 1); std::vector<int32_t> xs(X ? X : 1), xe(X ? X : 1), ref(N); std::vector<uint8_t> f(X ? X : 1); std::vector<uint32_t> info(N);
+                l2r_result res{(int64_t)N, (int64_t)X, 0, off.data(), xs.data(), xe.data(), f.data(), info.data(), ref.data()};
+                if ((rc = l2r_download(c, &res))) return rc;
+                novel_select(h, m.np, m.h_tx_gene.data(), (int64_t)N, r->tid, &res);
+            } else novel_select(h, m.np, m.h_tx_gene.data(), (int64_t)N, r->tid, r->res);
+        } catch (const std::bad_alloc &) {              // the accumulators as they were
+            h.o_tid.resize(o0); h.o_ref.resize(o0); h.o_read.resize(o0); h.o_rev.resize(o0); h.o_nex.resize(o0); h.xs.resize(x0); h.xe.resize(x0); h.f.resize(x0); h.k_tid.resize(k0); h.k_gene.resize(k0);
+            h.reads = m.n; h.split = split0; h.bad = bad0; h.bad_kind = kind0;
+            return fail(-2, "[l2r_novel_add] no memory for the offers of %zu reads", N);
+        }
+        m.split = h.split;
+        m.stats[NVS_OFFERS] = (double)h.o_tid.size(); m.stats[NVS_KNOWN] = (double)h.k_tid.size();
+    } else {
+        StageTimer &clk = m.u.clk;
+        if ((rc = clk.begin(env_on("L2R_SORT_TIMING"), c->check_stages))) return rc;
+        const size_t n_tiles = (N + NOV_TILE - 1) / NOV_TILE;
+        if ((rc = to_dev(c, m.a_tid, r->tid, N))) {}
+        else if (!run_res) {
+            m.off32.resize(N + 1);
+            for (size_t i = 0; i <= N; ++i) m.off32[i] = (uint32_t)r->res->ex_off[i];
+            if ((rc = put_dev(c, m.a_off, m.off32)) || (rc = to_dev(c, m.a_info, (const uint32_t *)r->res->info, N)) || (rc = to_dev(c, m.a_ref, (const int32_t *)r->res->ref_tx, N)) ||
+                (rc = to_dev(c, m.a_xs, (const int32_t *)r->res->ex_start, X)) || (rc = to_dev(c, m.a_xe, (const int32_t *)r->res->ex_end, X)) || (rc = to_dev(c, m.a_f, (const uint8_t *)r->res->ex_flag, X))) {}
+        }
+        if (!rc && (m.bits.ensure(N) || m.cnt_x.ensure(N + 1) || m.tile_cnt.ensure(2 * n_tiles + 1))) rc = -2;
+        if (rc) return summary_no_room(c, "l2r_novel_add");
+        HIP_TRY(hipMemsetAsync(m.aword.p, 0, NOVW_N * sizeof(uint32_t), c->stream));
+        NovSel s{};
+        s.n = (int64_t)N; s.read_base = m.n; s.tid = m.a_tid.p;
+        if (run_res) { s.info = c->info.p; s.ex_off = c->ex_off.p; s.ref_tx = c->ref_tx.p; s.xs = c->ex_start.p; s.xe = c->ex_end.p; s.f = c->ex_flag.p; }
+        else { s.info = m.a_info.p; s.ex_off = m.a_off.p; s.ref_tx = m.a_ref.p; s.xs = m.a_xs.p; s.xe = m.a_xe.p; s.f = m.a_f.p; }
+        s.src_exons = (uint32_t)X;
+        s.n_ref = m.np.n_ref; s.n_tx = m.np.n_tx; s.tx_gene = m.tx_gene.p; s.na_gene = m.np.na_gene; s.has_sj = m.np.has_sj; s.split = m.np.split;
+        s.bits = m.bits.p; s.cnt_x = m.cnt_x.p; s.tile_cnt = m.tile_cnt.p; s.n_tiles = (int64_t)n_tiles; s.word = m.aword.p; s.bad = m.bad.p;
+        rc = clk.launch(c, &m.stats[NVS_K_SELECT], [&] {
+            hipLaunchKernelGGL(k_nov_flag, dim3((unsigned)n_tiles), dim3(NOV_TILE), 0, c->stream, s);
+            scan_u32(c, m.cnt_x.p, (int64_t)N, m.aword.p + NOVW_EXONS);
+            scan_u32(c, m.tile_cnt.p, (int64_t)(2 * n_tiles), m.aword.p + NOVW_TILES);
+        });
+        uint32_t w[NOVW_N] = {0}, n_off = 0;
+        if ((rc = download_all(c, rc, {{w, m.aword.p, sizeof w}, {&n_off, m.tile_cnt.p + n_tiles, sizeof n_off}}, "l2r_novel_add"))) return rc;
+        if (n_off > w[NOVW_TILES] || (size_t)w[NOVW_TILES] > 2 * N || (size_t)w[NOVW_EXONS] > X)
+            return fail(-2, "[l2r_novel_add] %u offers and %u known reads of %zu reads, %u exons of %zu", n_off, w[NOVW_TILES] - n_off, N, w[NOVW_EXONS], X);
+        const size_t O = n_off, K = w[NOVW_TILES] - n_off, XO = w[NOVW_EXONS];
+        const size_t o0 = m.o_tid.n, k0 = m.k_tid.n, x0 = m.xs.n;
+        // room first: a failed allocation leaves the accumulators as they were
+        if (m.o_tid.reserve(c->stream, o0 + O) || m.o_ref.reserve(c->stream, o0 + O) || m.o_read.reserve(c->stream, o0 + O) || m.o_rev.reserve(c->stream, o0 + O) || m.o_nex.reserve(c->stream, o0 + O) ||
+            m.xs.reserve(c->stream, x0 + XO) || m.xe.reserve(c->stream, x0 + XO) || m.f.reserve(c->stream, x0 + XO) || m.k_tid.reserve(c->stream, k0 + K) || m.k_gene.reserve(c->stream, k0 + K))
+            return summary_no_room(c, "l2r_novel_add");
+        s.n_off = (uint32_t)O; s.n_known = (uint32_t)K; s.o0 = o0; s.k0 = k0; s.x0 = x0; s.o_room = o0 + O; s.k_room = k0 + K; s.x_room = x0 + XO;
+        s.o_tid = m.o_tid.p; s.o_ref = m.o_ref.p; s.o_read = m.o_read.p; s.o_rev = m.o_rev.p; s.o_nex = m.o_nex.p; s.a_xs = m.xs.p; s.a_xe = m.xe.p; s.a_f = m.f.p; s.k_tid = m.k_tid.p; s.k_gene = m.k_gene.p;
+        const bool wave = wave_form(O ? (double)XO / (double)O : 0.0, "L2R_NOVEL_WAVE");       // (exons per offer)
+        m.stats[NVS_WAVE] = wave ? 1 : 0;
+        rc = clk.launch(c, &m.stats[NVS_K_SELECT], [&] {
+            if (O + K) hipLaunchKernelGGL(k_nov_place, dim3((unsigned)n_tiles), dim3(NOV_TILE), 0, c->stream, s);
+            const dim3 grid((unsigned)(((wave ? N * 64 : N) + 255) / 256));
+            if (O && wave) hipLaunchKernelGGL(k_nov_chain<true>, grid, dim3(256), 0, c->stream, s);
+            else if (O) hipLaunchKernelGGL(k_nov_chain<false>, grid, dim3(256), 0, c->stream, s);
+        });
+        if ((rc = download_all(c, rc, {}, "l2r_novel_add"))) return rc;      // (the columns are the caller's)
+        m.o_tid.n = m.o_ref.n = m.o_read.n = m.o_rev.n = m.o_nex.n = o0 + O; m.xs.n = m.xe.n = m.f.n = x0 + XO; m.k_tid.n = m.k_gene.n = k0 + K;
+        m.split += (int64_t)w[NOVW_SPLIT];
+        m.stats[NVS_OFFERS] = (double)(o0 + O); m.stats[NVS_KNOWN] = (double)(k0 + K);
+    }
+    m.n += (int64_t)N; m.x += (int64_t)X; ++m.adds;
+    m.stats[NVS_READS] = (double)m.n; m.stats[NVS_SPLIT] = (double)m.split; m.stats[NVS_ADDS] = (double)m.adds;
+    return 0;
+}
+
+extern "C++" {
+// the lengths of the BED lines, the counts and the stats that both routes leave alike, from m.kept and m.out / the device's rows
+static void novel_done(NovelState &m, int64_t *counts)
+{
+    novel_counts(m.kept, m.n_entries, counts);
+    m.stats[NVS_ENTRIES] = (double)m.n_entries;
+    for (int l = 0; l < NOV_LISTS; ++l) m.stats[NVS_KEPT + l] = (double)m.kept[l];
+    m.finished = true;
+}
+
+// novel_host over the host's copy of the accumulators (the refusals first: -1 names the read, -3 counts the split-route reads)
+static int novel_on_host(NovelState &m, const NovelAcc &a, int64_t *counts)
+{
+    if (a.bad >= 0) { std::string msg; novel_read_fail(msg, a.bad, a.bad_kind); return fail(-1, "%s", msg.c_str()); }
+    if (a.split) return fail(-3, "[l2r_novel_finish] %lld split-route reads: their pieces enter the list without a place, the host tail merges it", (long long)a.split);
+    novel_host(a, m.p, m.h_tx_gene.data(), m.np.na_gene, m.out);
+    const NovelOut &o = m.out;
+    m.n_entries = (int64_t)o.e_src.size();
+    m.row0[0] = 0;
+    for (int l = 0; l < NOV_LISTS; ++l) { m.kept[l] = (int64_t)o.rows[l].tid.size(); m.row0[l + 1] = m.row0[l] + m.kept[l]; m.stats[NVS_ITEMS + l] = (double)o.items[l]; }
+    const NovelRows &E = o.rows[NOV_EXON];
+    m.h_len.resize(E.tid.size());
+    for (size_t q = 0; q < E.tid.size(); ++q) m.h_len[q] = novel_bed_bytes(m.ref.h_off.data(), E.tid[q], E.a[q], E.b[q], E.score[q]);
+    m.rows_on_host = true;
+    m.stats[NVS_ROUTE] = 1; m.stats[NVS_CLUSTERS] = (double)o.clusters; m.stats[NVS_LARGEST] = (double)o.largest;
+    m.stats[NVS_HITS] = (double)(o.u.hits[0] + o.u.hits[1] + o.u.hits[2]); m.stats[NVS_WIDENED] = (double)o.widened;
+    novel_done(m, counts);
+    return 0;
+}
+
+// the device's accumulators fetched, then novel_host (input that is not in order)
+static int novel_fetch_host(l2r_ctx *c, NovelState &m, int64_t *counts)
+{
+    for (int k = NVS_K_MERGE; k <= NVS_K_KEEP; ++k) m.stats[k] = 0;
+    m.h = NovelAcc();                                   // (kept: the updated GTF reads the chains from it)
+    NovelAcc &a = m.h;
+    const size_t O = m.o_tid.n, K = m.k_tid.n, X = m.xs.n;
+    try {
+        a.o_tid.resize(O); a.o_ref.resize(O); a.o_read.resize(O); a.o_rev.resize(O); a.o_nex.resize(O); a.xs.resize(X); a.xe.resize(X); a.f.resize(X); a.k_tid.resize(K); a.k_gene.resize(K);
+    } catch (const std::bad_alloc &) { return fail(-2, "[l2r_novel_finish] no memory for %zu offers", O); }
+    a.reads = m.n;
+    if (int rc = download_all(c, 0, {{a.o_tid.data(), m.o_tid.p, O * 4}, {a.o_ref.data(), m.o_ref.p, O * 4}, {a.o_read.data(), m.o_read.p, O * 4}, {a.o_rev.data(), m.o_rev.p, O}, {a.o_nex.data(), m.o_nex.p, O * 4},
+                                     {a.xs.data(), m.xs.p, X * 4}, {a.xe.data(), m.xe.p, X * 4}, {a.f.data(), m.f.p, X}, {a.k_tid.data(), m.k_tid.p, K * 4}, {a.k_gene.data(), m.k_gene.p, K * 4}}, "l2r_novel_finish")) return rc;
+    return novel_on_host(m, a, counts);
+}
+}
+
+int l2r_novel_finish(l2r_ctx *c, int64_t *counts)
+{
+    if (!c || !counts) return fail(-1, "[l2r_novel_finish] null argument");
+    NovelState &m = c->novel;
+    if (!m.begun) return fail(-1, "[l2r_novel_finish] no l2r_novel_begin in front");
+    for (int k = 0; k < 8; ++k) counts[k] = 0;
+    for (int k = NVS_CLUSTERS; k < NVS_WAVE; ++k) m.stats[k] = 0;
+    for (int k = NVS_K_MERGE; k < NVS_N; ++k) m.stats[k] = 0;
+    m.finished = false; m.gtf_ready = false; m.rows_on_host = false; m.text.reset(); m.out = NovelOut(); m.h_len.clear(); m.n_entries = 0;
+    for (int l = 0; l < NOV_LISTS; ++l) { m.kept[l] = 0; m.row0[l] = 0; }
+    m.row0[NOV_LISTS] = 0;
+    if (m.on_host) return novel_on_host(m, m.h, counts);
+    HIP_TRY(hipSetDevice(c->device));
+    int rc = 0;
+    StageTimer &clk = m.u.clk;
+    if ((rc = clk.begin(env_on("L2R_SORT_TIMING"), c->check_stages))) return rc;
+    {   unsigned long long bad = ~0ull;
+        if ((rc = download_all(c, 0, {{&bad, m.bad.p, sizeof bad}}, "l2r_novel_finish"))) return rc;
+        if (bad != ~0ull) {
+            const unsigned long long q = bad >> 4; const int kind = (int)(bad & 15ull);
+            if (q >= (unsigned long long)m.n || kind <= 0 || kind >= NOV_E_N) return fail(-2, "[l2r_novel_finish] the device names read %llu of %lld, kind %d", q, (long long)m.n, kind);
+            std::string msg; novel_read_fail(msg, (int64_t)q, kind);
+            return fail(-1, "%s", msg.c_str());
+        } }
+    if (m.split) return fail(-3, "[l2r_novel_finish] %lld split-route reads: their pieces enter the list without a place, the host tail merges it", (long long)m.split);
+    const size_t O = m.o_tid.n, K = m.k_tid.n, XO = m.xs.n;
+    UniqState &u = m.u;
+    uint32_t w[NOVF_N] = {0};
+    HIP_TRY(hipMemsetAsync(m.fword.p, 0, NOVF_N * sizeof(uint32_t), c->stream));
+    // ---- the merge
+    if (O) {
+        if (m.o_off.ensure(O + 1) || u.tid.ensure(O) || u.rev.ensure(O) || u.ex_off.ensure(O + 1) || u.xs.ensure(XO ? XO : 1) || u.xe.ensure(XO ? XO : 1)) return summary_no_room(c, "l2r_novel_finish");
+        HIP_TRY(hipMemcpyAsync(m.o_off.p, m.o_nex.p, O * 4, hipMemcpyDeviceToDevice, c->stream));
+        HIP_TRY(hipMemcpyAsync(u.tid.p, m.o_tid.p, O * 4, hipMemcpyDeviceToDevice, c->stream));
+        HIP_TRY(hipMemcpyAsync(u.rev.p, m.o_rev.p, O, hipMemcpyDeviceToDevice, c->stream));
+        if (XO) { HIP_TRY(hipMemcpyAsync(u.xs.p, m.xs.p, XO * 4, hipMemcpyDeviceToDevice, c->stream)); HIP_TRY(hipMemcpyAsync(u.xe.p, m.xe.p, XO * 4, hipMemcpyDeviceToDevice, c->stream)); }
+    }
+    rc = clk.launch(c, &m.stats[NVS_K_MERGE], [&] {
+        if (O) {
+            scan_u32(c, m.o_off.p, (int64_t)O, m.fword.p + NOVF_EXONS);
+            hipLaunchKernelGGL(k_nov_widen, dim3((unsigned)((O + 1 + 255) / 256)), dim3(256), 0, c->stream, (int64_t)O, (const uint32_t *)m.o_off.p, u.ex_off.p);
+        }
+        if (K > 1) hipLaunchKernelGGL(k_nov_descends, dim3((unsigned)((K + 255) / 256)), dim3(256), 0, c->stream, (int64_t)K, (const int32_t *)m.k_tid.p, m.fword.p);
+    });
+    if ((rc = download_all(c, rc, {{w, m.fword.p, sizeof w}}, "l2r_novel_finish"))) return rc;
+    if (O && (size_t)w[NOVF_EXONS] != XO) return fail(-2, "[l2r_novel_finish] the exon counts of the offers add up to %u, %zu exons were appended", w[NOVF_EXONS], XO);
+    if (w[NOVF_DESCENDS]) return novel_fetch_host(c, m, counts);
+    uint32_t uw[UQW_N] = {0};
+    if (O) {
+        if ((rc = uniq_device(c, u, O, m.p, "l2r_novel_finish", &m.stats[NVS_K_MERGE], &m.stats[NVS_K_MERGE], &m.stats[NVS_K_MERGE], uw))) return rc;
+        if (uw[UQW_UNSORTED]) return novel_fetch_host(c, m, counts);
+    }
+    const size_t U = uw[UQW_UNIQUE];
+    m.n_entries = (int64_t)U;
+    m.stats[NVS_ROUTE] = 0; m.stats[NVS_CLUSTERS] = (double)uw[UQW_CLUSTERS]; m.stats[NVS_LARGEST] = (double)uw[UQW_LARGEST];
+    m.stats[NVS_HITS] = (double)((uint64_t)uw[UQW_IDENT] + uw[UQW_CONTAINED] + uw[UQW_SINGLE]);
+    // ---- the items
+    NovItems t{};
+    t.n_entries = (uint32_t)U; t.n_offers = (uint32_t)O; t.n_exons = (uint32_t)XO; t.n_known = (uint32_t)K;
+    t.u_src = u.u_src.p; t.u_start = u.u_start.p; t.u_end = u.u_end.p; t.u_cov = u.u_cov.p;
+    t.o_tid = m.o_tid.p; t.o_ref = m.o_ref.p; t.o_read = m.o_read.p; t.o_rev = m.o_rev.p; t.o_nex = m.o_nex.p; t.o_off = m.o_off.p;
+    t.xs = m.xs.p; t.xe = m.xe.p; t.f = m.f.p; t.k_tid = m.k_tid.p; t.k_gene = m.k_gene.p; t.tx_gene = m.tx_gene.p; t.na_gene = m.np.na_gene; t.word = m.fword.p;
+    uint32_t start[NOV_LISTS + 1] = {0};                // where every list's items begin
+    if (U) {
+        const size_t n_cnt = (size_t)(NOV_GENE + 1) * U;
+        if (m.cnt.ensure(n_cnt + 1) || m.e_src.ensure(U)) return summary_no_room(c, "l2r_novel_finish");
+        t.cnt = m.cnt.p; t.e_src = m.e_src.p;
+        rc = clk.launch(c, &m.stats[NVS_K_ITEMS], [&] {
+            hipLaunchKernelGGL(k_nov_count, dim3((unsigned)((U + 255) / 256)), dim3(256), 0, c->stream, t);
+            scan_u32(c, m.cnt.p, (int64_t)n_cnt, m.fword.p + NOVF_ITEMS);
+        });
+        hipError_t e = hipSuccess;
+        for (int l = 1; l <= NOV_GENE && !rc && e == hipSuccess; ++l) e = hipMemcpyAsync(&start[l], m.cnt.p + (size_t)l * U, 4, hipMemcpyDeviceToHost, c->stream);
+        if (!rc && e != hipSuccess) rc = fail(-2, "[l2r_novel_finish] %s", hipGetErrorString(e));
+        if ((rc = download_all(c, rc, {{w, m.fword.p, sizeof w}}, "l2r_novel_finish"))) return rc;
+    }
+    const uint64_t n_items64 = (uint64_t)w[NOVF_ITEMS] + K;
+    if (n_items64 >= (uint64_t)NOV_MAX_ITEMS) return fail(-1, "[l2r_novel_finish] %llu items in the six lists (below 2^32 - 64)", (unsigned long long)n_items64);
+    const uint32_t n_items = (uint32_t)n_items64;
+    start[NOV_KNOWN_GENE] = w[NOVF_ITEMS]; start[NOV_LISTS] = n_items;
+    for (int l = 0; l < NOV_LISTS; ++l) {
+        if (start[l + 1] < start[l]) return fail(-2, "[l2r_novel_finish] the items of list %d begin at %u, those behind at %u", l, start[l], start[l + 1]);
+        m.stats[NVS_ITEMS + l] = (double)(start[l + 1] - start[l]);
+    }
+    m.stats[NVS_WIDENED] = (double)w[NOVF_WIDENED];
+    if (n_items == 0) { novel_done(m, counts); return 0; }
+    const size_t NI = n_items;
+    t.n_items = n_items; t.base_known = w[NOVF_ITEMS];
+    if (m.hi.ensure(NI) || m.ia.ensure(NI) || m.ib.ensure(NI) || m.icov.ensure(NI) || m.imeta.ensure(NI) || m.order1.ensure(NI) || m.order.ensure(NI) || m.head.ensure(NI + 1) || m.first.ensure(NI + 1) ||
+        m.grp.ensure(NI) || m.sum.ensure(NI)) return summary_no_room(c, "l2r_novel_finish");
+    t.hi = m.hi.p; t.a = m.ia.p; t.b = m.ib.p; t.cov = m.icov.p; t.meta = m.imeta.p;
+    HIP_TRY(hipMemsetAsync(m.hi.p, 0, NI * 4, c->stream)); HIP_TRY(hipMemsetAsync(m.ia.p, 0, NI * 4, c->stream)); HIP_TRY(hipMemsetAsync(m.ib.p, 0, NI * 4, c->stream));
+    HIP_TRY(hipMemsetAsync(m.icov.p, 0, NI * 4, c->stream)); HIP_TRY(hipMemsetAsync(m.imeta.p, 0, NI, c->stream));
+    HIP_TRY(hipMemsetAsync(m.first.p, 0, (NI + 1) * 4, c->stream)); HIP_TRY(hipMemsetAsync(m.sum.p, 0, NI * 4, c->stream));
+    if ((rc = clk.launch(c, &m.stats[NVS_K_ITEMS], [&] {
+            if (U) hipLaunchKernelGGL(k_nov_emit, dim3((unsigned)((U + 255) / 256)), dim3(256), 0, c->stream, t);
+            if (K) hipLaunchKernelGGL(k_nov_emit_known, dim3((unsigned)((K + 255) / 256)), dim3(256), 0, c->stream, t);
+        }))) { (void)hipStreamSynchronize(c->stream); return rc; }
+    // ---- the stable order by (list, tid, a, b): on b, then on the upper 64 bits read through the first order
+    {   double *const ms[3] = {&m.stats[NVS_K_SORT], &m.stats[NVS_K_SORT], &m.stats[NVS_K_SORT]};
+        const uint32_t *order1 = nullptr, *perm2 = nullptr;
+        int n_pass = 0;
+        if ((rc = order_by_keys(c, clk, NovLowKeyOf{m.ib.p}, n_items, ms[0], ms, &n_pass, nullptr, &order1))) { (void)hipStreamSynchronize(c->stream); return rc; }
+        if (order1) {                                   // (stage 2 runs in the same index columns)
+            HIP_TRY(hipMemcpyAsync(m.order1.p, order1, NI * sizeof(uint32_t), hipMemcpyDeviceToDevice, c->stream));
+            order1 = m.order1.p;
+        }
+        if ((rc = order_by_keys(c, clk, NovHighKeyOf{m.hi.p, m.ia.p, order1, n_items}, n_items, ms[0], ms, &n_pass, nullptr, &perm2))) { (void)hipStreamSynchronize(c->stream); return rc; }
+        if ((rc = clk.launch(c, &m.stats[NVS_K_SORT], [&] {
+                hipLaunchKernelGGL(k_gtf_compose, dim3((unsigned)((NI + GTF_THREADS - 1) / GTF_THREADS)), dim3(GTF_THREADS), 0, c->stream, order1, perm2, n_items, m.order.p);
+            }))) { (void)hipStreamSynchronize(c->stream); return rc; } }
+    // ---- the first item of every key, in item order
+    const NovKeys keys{n_items, m.order.p, m.hi.p, m.ia.p, m.ib.p};
+    const unsigned grid_i = (unsigned)((NI + 255) / 256);
+    rc = clk.launch(c, &m.stats[NVS_K_KEEP], [&] {
+        hipLaunchKernelGGL(k_nov_heads, dim3(grid_i), dim3(256), 0, c->stream, keys, m.head.p);
+        scan_u32(c, m.head.p, (int64_t)NI, m.fword.p + NOVF_GROUPS);
+        hipLaunchKernelGGL(k_nov_groups, dim3(grid_i), dim3(256), 0, c->stream, keys, (const uint32_t *)m.head.p, (const uint32_t *)m.icov.p, m.first.p, m.grp.p, m.sum.p);
+        scan_u32(c, m.first.p, (int64_t)NI, m.fword.p + NOVF_ROWS);
+    });
+    uint32_t row0[NOV_LISTS + 1] = {0};
+    {   hipError_t e = hipSuccess;
+        for (int l = 1; l < NOV_LISTS && !rc && e == hipSuccess; ++l) e = hipMemcpyAsync(&row0[l], m.first.p + start[l], 4, hipMemcpyDeviceToHost, c->stream);
+        if (!rc && e != hipSuccess) rc = fail(-2, "[l2r_novel_finish] %s", hipGetErrorString(e)); }
+    if ((rc = download_all(c, rc, {{w, m.fword.p, sizeof w}}, "l2r_novel_finish"))) return rc;
+    const size_t R = w[NOVF_ROWS];
+    row0[NOV_LISTS] = (uint32_t)R;
+    if (R == 0 || R > NI || w[NOVF_GROUPS] != R) return fail(-2, "[l2r_novel_finish] %u keys and %zu first items of %zu items", w[NOVF_GROUPS], R, NI);
+    for (int l = 0; l < NOV_LISTS; ++l) if (row0[l + 1] < row0[l]) return fail(-2, "[l2r_novel_finish] the rows of list %d begin at %u, those behind at %u", l, row0[l], row0[l + 1]);
+    if (m.r_tid.ensure(R) || m.r_a.ensure(R) || m.r_b.ensure(R) || m.r_score.ensure(R) || m.r_meta.ensure(R)) return summary_no_room(c, "l2r_novel_finish");
+    const size_t E = row0[NOV_EXON + 1] - row0[NOV_EXON], G0 = row0[NOV_GENE], NG = R - G0;
+    if (m.len.ensure(E ? E : 1)) return summary_no_room(c, "l2r_novel_finish");
+    const NovBed bed{(uint32_t)E, m.r_tid.p, m.r_a.p, m.r_b.p, m.r_score.p, m.r_meta.p, m.np.n_ref, m.ref.off.p, m.ref.names.p};
+    rc = clk.launch(c, &m.stats[NVS_K_KEEP], [&] {
+        hipLaunchKernelGGL(k_nov_keep, dim3(grid_i), dim3(256), 0, c->stream, keys, (const uint32_t *)m.first.p, (const uint32_t *)m.grp.p, (const uint32_t *)m.sum.p, (const uint8_t *)m.imeta.p, (uint32_t)R,
+                           NovRows{m.r_tid.p, m.r_a.p, m.r_b.p, m.r_score.p, m.r_meta.p});
+    });
+    if (!rc && E) rc = clk.launch(c, &m.stats[NVS_K_MEASURE], [&] { hipLaunchKernelGGL(k_nov_bed_measure, dim3((unsigned)((E + 255) / 256)), dim3(256), 0, c->stream, bed, m.len.p); });
+    // the gene rows come to the host, where add_gene's last test is made (novel_gene_rows); the lines' lengths for the cut
+    std::vector<int32_t> g_tid(NG ? NG : 1), g_a(NG ? NG : 1);
+    m.h_len.assign(E, 0u);
+    if ((rc = download_all(c, rc, {{g_tid.data(), m.r_tid.p + G0, NG * 4}, {g_a.data(), m.r_a.p + G0, NG * 4}, {m.h_len.data(), m.len.p, E * 4}}, "l2r_novel_finish"))) return rc;
+    for (int l = NOV_GENE; l < NOV_LISTS; ++l) {
+        NovelRows &g = m.out.rows[l];
+        const size_t lo = row0[l] - G0, hi = row0[l + 1] - G0;
+        g.tid.assign(g_tid.begin() + lo, g_tid.begin() + hi); g.a.assign(g_a.begin() + lo, g_a.begin() + hi);
+        g.b.assign(hi - lo, 0); g.score.assign(hi - lo, 0); g.meta.assign(hi - lo, 0);
+        novel_gene_rows(g);
+    }
+    for (int l = 0; l <= NOV_LISTS; ++l) m.row0[l] = (int64_t)row0[l];
+    for (int l = 0; l < NOV_GENE; ++l) m.kept[l] = (int64_t)(row0[l + 1] - row0[l]);
+    for (int l = NOV_GENE; l < NOV_LISTS; ++l) m.kept[l] = (int64_t)m.out.rows[l].tid.size();
+    novel_done(m, counts);
+    return 0;
+}
+
+int l2r_novel_entries_out(l2r_ctx *c, int32_t *src, int32_t *start, int32_t *end, int32_t *cov)
+{
+    if (!c) return fail(-1, "[l2r_novel_entries_out] null argument");
+    const NovelState &m = c->novel;
+    if (!m.finished) return fail(-1, "[l2r_novel_entries_out] no results: the last l2r_novel_finish failed, or none was made");
+    const size_t U = (size_t)m.n_entries;
+    if (U == 0) return 0;
+    if (m.rows_on_host) {
+        const NovelOut &o = m.out;
+        if (src) memcpy(src, o.e_src.data(), U * 4);
+        if (start) memcpy(start, o.e_start.data(), U * 4);
+        if (end) memcpy(end, o.e_end.data(), U * 4);
+        if (cov) memcpy(cov, o.e_cov.data(), U * 4);
+        return 0;
+    }
+    HIP_TRY(hipSetDevice(c->device));
+    return download_all(c, 0, {{src, m.e_src.p, src ? U * 4 : 0}, {start, m.u.u_start.p, start ? U * 4 : 0}, {end, m.u.u_end.p, end ? U * 4 : 0}, {cov, m.u.u_cov.p, cov ? U * 4 : 0}}, "l2r_novel_entries_out");
+}
+
+int l2r_novel_rows_out(l2r_ctx *c, int list, int32_t *tid, int32_t *a, int32_t *b, int32_t *score, uint8_t *meta)
+{
+    if (!c) return fail(-1, "[l2r_novel_rows_out] null argument");
+    const NovelState &m = c->novel;
+    if (!m.finished) return fail(-1, "[l2r_novel_rows_out] no results: the last l2r_novel_finish failed, or none was made");
+    if (list < 0 || list >= NOV_LISTS) return fail(-1, "[l2r_novel_rows_out] list %d (0 .. %d)", list, NOV_LISTS - 1);
+    const size_t R = (size_t)m.kept[list];
+    if (R == 0) return 0;
+    if (m.rows_on_host || list >= NOV_GENE) {
+        const NovelRows &r = m.out.rows[list];
+        if (tid) memcpy(tid, r.tid.data(), R * 4);
+        if (a) memcpy(a, r.a.data(), R * 4);
+        if (b) memcpy(b, r.b.data(), R * 4);
+        if (score) memcpy(score, r.score.data(), R * 4);
+        if (meta) memcpy(meta, r.meta.data(), R);
+        return 0;
+    }
+    HIP_TRY(hipSetDevice(c->device));
+    const size_t r0 = (size_t)m.row0[list];
+    return download_all(c, 0, {{tid, m.r_tid.p + r0, tid ? R * 4 : 0}, {a, m.r_a.p + r0, a ? R * 4 : 0}, {b, m.r_b.p + r0, b ? R * 4 : 0}, {score, m.r_score.p + r0, score ? R * 4 : 0},
+                               {meta, m.r_meta.p + r0, meta ? R : 0}}, "l2r_novel_rows_out");
+}
+
+int l2r_novel_lines(l2r_ctx *c, int which, int64_t first, int64_t max_rows, int64_t max_bytes, int64_t *n_taken, int64_t *n_bytes)
+{
+    if (!c || !n_taken || !n_bytes) return fail(NOVEL_E_ARG, "[l2r_novel_lines] null argument");
+    NovelState &m = c->novel;
+    m.text.reset();
+    *n_taken = 0; *n_bytes = 0;
+    if (!m.finished) return fail(NOVEL_E_ARG, "[l2r_novel_lines] no l2r_novel_finish in front, or it failed");
+    if (which == L2R_NOVEL_GTF) {
+        if (!m.gtf_ready) return fail(NOVEL_E_ARG, "[l2r_novel_lines] no l2r_novel_names in front, or it failed");
+        m.last_which = L2R_NOVEL_GTF;
+        return l2r_gtftext_lines(c, first, max_rows, max_bytes, n_taken, n_bytes);
+    }
+    m.last_which = L2R_NOVEL_BED;
+    if (which != L2R_NOVEL_BED) return fail(NOVEL_E_ARG, "[l2r_novel_lines] which = %d", which);
+    int64_t take = 0, sum = 0;
+    {   std::string msg;
+        if (novel_cut(m.h_len.data(), m.kept[NOV_EXON], first, max_rows, max_bytes, &take, &sum, msg)) return fail(NOVEL_E_ARG, "%s", msg.c_str()); }
+    static const TextBatch batch{"l2r_novel_lines", "L2R_SORT_TIMING", "lines would have left their place: k_nov_bed_measure and k_nov_bed_write disagree", NOV_BED_TILE, NOVC_TOTAL, NOVC_OUTSIDE, NOVC_DIRECT};
+    uint32_t w[NOVC_TOTAL + 1] = {0};
+    m.tstats[TXS_GUARD] = 1; m.tstats[TXS_K_SCAN] = 0; m.tstats[TXS_K_WRITE] = 0;
+    const NovBed bed{(uint32_t)m.kept[NOV_EXON], m.r_tid.p, m.r_a.p, m.r_b.p, m.r_score.p, m.r_meta.p, m.np.n_ref, m.ref.off.p, m.ref.names.p};
+    const int rc = text_batch(c, batch, m.text, m.u.clk, m.len, m.off, m.tword, m.tstats, m.rows_on_host, first, take, sum, w,
+        [&](std::vector<uint8_t> &text, std::string &) { novel_bed_host(m.out.rows[NOV_EXON], m.ref.h_off.data(), m.ref.h_names.data(), first, take, text); return 0; },
+        [&](unsigned n_tiles, uint8_t *text) {
+            hipLaunchKernelGGL(k_nov_bed_write, dim3(n_tiles), dim3(NOV_BED_TILE), 0, c->stream, bed, first, take, (const uint32_t *)m.off.p, text, m.tword.p);
+        });
+    m.stats[NVS_K_SCAN] += m.tstats[TXS_K_SCAN]; m.stats[NVS_K_WRITE] += m.tstats[TXS_K_WRITE];
+    if (m.tstats[TXS_GUARD] == 0) m.stats[NVS_GUARD] = 0;
+    if (rc) return rc;
+    *n_taken = take; *n_bytes = sum;
+    return 0;
+}
+
+// The updated GTF of the entries through the GTF-text unit (l2r_gtftext_*): the rows are the OFFERS -- the accumulators' columns and chains,
+// copied inside HBM -- the blocks the entries (sel = the entry's offer, with k_uniq_take's start, end and cov), and the names one table:
+// the annotation's, `NA`, the caller's.  g / G of an offer are those of its ref, t / T the entry's tid_name / qname.
+int l2r_novel_names(l2r_ctx *c, const l2r_novel_name_table *t, int64_t *n_lines, int64_t *n_bytes)
+{
+    if (!c || !t || !n_lines || !n_bytes) return fail(NOVEL_E_ARG, "[l2r_novel_names] null argument");
+    NovelState &m = c->novel;
+    m.gtf_ready = false;
+    *n_lines = 0; *n_bytes = 0;
+    if (!m.finished) return fail(NOVEL_E_ARG, "[l2r_novel_names] no l2r_novel_finish in front, or it failed");
+    if (!m.has_gtf) return fail(NOVEL_E_ARG, "[l2r_novel_names] l2r_novel_begin came without a source string and gene tables");
+    const size_t U = (size_t)m.n_entries, A = (size_t)m.anno_len, NL = (size_t)(t->names_len > 0 ? t->names_len : 0);
+    if (t->names_len < 0 || (uint64_t)A + 3 + NL > 0xffffffffull) return fail(NOVEL_E_ARG, "[l2r_novel_names] a names table of %lld bytes", (long long)t->names_len);
+    if (U && (!t->qname || (NL && !t->names))) return fail(NOVEL_E_ARG, "[l2r_novel_names] null column");
+    const uint32_t na = (uint32_t)A, base = (uint32_t)A + 3u;
+    const uint32_t *tid_name = t->tid_name ? t->tid_name : t->qname;
+    for (size_t e = 0; e < U; ++e)                      // (added to base below: an offset beyond the table would name another string, or wrap)
+        if ((size_t)t->qname[e] >= NL || (size_t)tid_name[e] >= NL) return fail(NOVEL_E_ARG, "[l2r_novel_names] entry %zu: a name id at or beyond names_len", e);
+    const l2r_gtx_params gp{m.np.n_ref, m.ref.h_off.data(), m.ref.h_names.data(), L2R_GTX_READ, (int32_t)m.h_src.size(), m.h_src.data()};
+    int rc;
+    if ((rc = l2r_gtftext_begin(c, &gp))) return rc;
+    std::vector<uint8_t> names(A + 3 + NL);
+    if (A) memcpy(names.data(), m.genes.h_names.data(), A);
+    names[A] = 'N'; names[A + 1] = 'A'; names[A + 2] = 0;
+    if (NL) memcpy(names.data() + base, t->names, NL);
+    std::vector<int32_t> sel(U ? U : 1), start(U ? U : 1), end(U ? U : 1), cov(U ? U : 1);
+    GtxState &g = c->gtx;
+    if (m.rows_on_host) {
+        const NovelAcc &a = m.h;
+        const size_t O = a.o_tid.size();
+        std::vector<int64_t> off;
+        (void)novel_trans(a, off);
+        std::vector<uint32_t> id[4];
+        for (auto &v : id) v.assign(O ? O : 1, na);
+        for (size_t e = 0; e < U; ++e) {
+            const size_t o = (size_t)m.out.u.u_src[e];
+            const int32_t ref = a.o_ref[o];
+            if (ref >= 0) { id[0][o] = m.genes.h_gid[(size_t)ref]; id[2][o] = m.genes.h_gname[(size_t)ref]; }
+            id[1][o] = base + tid_name[e]; id[3][o] = base + t->qname[e];
+            sel[e] = (int32_t)o; start[e] = m.out.e_start[e]; end[e] = m.out.e_end[e]; cov[e] = m.out.e_cov[e];
+        }
+        const l2r_gtx_rows rows{(int64_t)O, a.o_tid.data(), a.o_rev.data(), off.data(), a.xs.data(), a.xe.data(), (int64_t)names.size(), names.data(), id[0].data(), id[1].data(), id[2].data(), id[3].data()};
+        if (O && (rc = l2r_gtftext_rows(c, &rows))) return rc;
+        if (!O) { g.n = 0; g.names_len = 0; g.on_host = true; g.run_chains = false; g.have_rows = true; }
+    } else {
+        HIP_TRY(hipSetDevice(c->device));
+        const size_t O = m.o_tid.n, X = m.xs.n;
+        g.on_host = false; g.stats[GXS_ROUTE] = 0; g.run_chains = false;
+        g.n = (int64_t)O; g.names_len = (int64_t)names.size();
+        g.h_nex.assign(O, 0u);
+        if (g.tid.ensure(O ? O : 1) || g.rev.ensure(O ? O : 1) || g.ex_off.ensure(O + 1) || g.xs.ensure(X ? X : 1) || g.xe.ensure(X ? X : 1) || g.id[0].ensure(O ? O : 1) || g.id[1].ensure(O ? O : 1) ||
+            g.id[2].ensure(O ? O : 1) || g.id[3].ensure(O ? O : 1) || (rc = put_dev(c, g.names, names)) || (rc = to_dev(c, m.e_qname, t->qname, U)) || (rc = to_dev(c, m.e_tidname, tid_name, U)))
+            return summary_no_room(c, "l2r_novel_names");
+        hipError_t e = hipSuccess;
+        if (O) {
+            e = hipMemcpyAsync(g.tid.p, m.o_tid.p, O * 4, hipMemcpyDeviceToDevice, c->stream);
+            if (e == hipSuccess) e = hipMemcpyAsync(g.rev.p, m.o_rev.p, O, hipMemcpyDeviceToDevice, c->stream);
+            if (e == hipSuccess) e = hipMemcpyAsync(g.ex_off.p, m.u.ex_off.p, (O + 1) * 8, hipMemcpyDeviceToDevice, c->stream);
+            if (e == hipSuccess && X) e = hipMemcpyAsync(g.xs.p, m.xs.p, X * 4, hipMemcpyDeviceToDevice, c->stream);
+            if (e == hipSuccess && X) e = hipMemcpyAsync(g.xe.p, m.xe.p, X * 4, hipMemcpyDeviceToDevice, c->stream);
+            for (int k = 0; k < 4 && e == hipSuccess; ++k) e = hipMemsetAsync(g.id[k].p, 0, O * 4, c->stream);
+        }
+        if (e != hipSuccess) { (void)hipStreamSynchronize(c->stream); return fail(-2, "[l2r_novel_names] %s", hipGetErrorString(e)); }
+        if (U) hipLaunchKernelGGL(k_nov_gtf_ids, dim3((unsigned)((U + 255) / 256)), dim3(256), 0, c->stream, (uint32_t)U, (uint32_t)O, (const int32_t *)m.u.u_src.p, (const int32_t *)m.o_ref.p,
+                                  (const uint32_t *)m.genes.gid.p, (const uint32_t *)m.genes.gname.p, m.np.n_tx, na, base, (const uint32_t *)m.e_qname.p, (const uint32_t *)m.e_tidname.p,
+                                  g.id[0].p, g.id[1].p, g.id[2].p, g.id[3].p);
+        if ((rc = download_all(c, 0, {{g.h_nex.data(), m.o_nex.p, O * 4}, {sel.data(), m.u.u_src.p, U * 4}, {start.data(), m.u.u_start.p, U * 4}, {end.data(), m.u.u_end.p, U * 4}, {cov.data(), m.u.u_cov.p, U * 4}},
+                               "l2r_novel_names"))) return rc;
+        for (int k = 0; k < 4; ++k) g.id_p[k] = g.id[k].p;
+        g.have_rows = true;
+    }
+    const l2r_gtx_blocks blk{(int64_t)U, sel.data(), start.data(), end.data(), cov.data()};
+    if ((rc = l2r_gtftext_blocks(c, &blk, n_lines, n_bytes))) return rc;
+    m.gtf_ready = true;
+    return 0;
+}
+
+int l2r_novel_out(l2r_ctx *c, uint8_t *text, int64_t cap)
+{
+    if (!c) return fail(NOVEL_E_ARG, "[l2r_novel_out] null argument");
+    if (c->novel.last_which == L2R_NOVEL_GTF) return l2r_gtftext_out(c, text, cap);
+    return text_out(c, c->novel.text, text, cap, "l2r_novel_out", "l2r_novel_lines", NOVEL_E_ARG);
+}
+
+int l2r_novel_stats(l2r_ctx *c, double *out, int n) { return stats_out(c ? c->novel.stats : nullptr, NVS_N, out, n, "l2r_novel_stats"); }
 
 }  // extern "C"
 

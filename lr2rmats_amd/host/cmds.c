@@ -359,7 +359,7 @@ int h_job_finish_part(h_job *j, int64_t lo, int64_t hi, const l2r_result *res, c
     o.out_gtf = open_part(j->out_path[0] ? j->out_path[0] : stdout_base, suffix);
     o.exon_bed = open_part(j->out_path[1], suffix); o.bam_gtf = open_part(j->out_path[2], suffix); o.bam_detail = open_part(j->out_path[3], suffix);
     o.known_gtf = open_part(j->out_path[4], suffix); o.novel_gtf = open_part(j->out_path[5], suffix); o.unrecog_gtf = open_part(j->out_path[6], suffix);
-    o.summary = NULL; o.summary_counts = counters; o.no_detail_header = !first_part; o.class_counts = NULL;
+    o.summary = NULL; o.summary_counts = counters; o.no_detail_header = !first_part; o.class_counts = NULL; o.novel_counts = NULL;
     h_part_genes_free(&j->part_genes); o.part_genes = &j->part_genes;
     if (!o.out_gtf) h_fatal("update_gtf", "a partitioned run needs -o or a base path for the updated GTF");
     h_reads part = j->reads;                                   /* a view: per-read arrays shifted, string table shared */
@@ -405,6 +405,7 @@ static void *tail_part_main(void *arg)
     o.summary = NULL; o.summary_counts = t->cnt; o.no_detail_header = !t->first; o.part_genes = &t->genes;
     static const int64_t no_class_counts[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     if (o.class_counts) o.class_counts = no_class_counts;   /* the part runs none of the four merges; finish_threaded's total takes the engine's numbers once */
+    if (o.novel_counts) o.novel_counts = no_class_counts;   /* likewise: no U, no updated GTF, no BED, no gene lists in the part */
     h_reads part = *t->reads;
     part.n = t->hi - t->lo; part.tid += t->lo; part.pos += t->lo; part.rev += t->lo; part.qname += t->lo; part.cig_off += t->lo;
     if (part.tid_name) part.tid_name += t->lo;
@@ -564,6 +565,7 @@ static int finish_threaded(h_job *j, const h_reads *reads, const h_update_opts *
         for (int q = 0; q < 2; ++q) total[gene_cnt[q]] -= gene_fix_join(&fix[q], tid, parts[k].genes.first_gids[q], parts[k].genes.n_first[q]);
     }
     if (files->class_counts) h_summary_class_counters(total, files->class_counts);
+    if (files->novel_counts) h_summary_novel_counters(total, files->novel_counts);
     const double t_join = h_now() - t_w0;
     for (int q = 0; q < n_wr; ++q) pthread_join(wth[q], NULL);
     const double t_write = h_now() - t_w0;
@@ -1010,9 +1012,130 @@ static void summary_done(l2r_ctx *ctx, const char *who, const l2r_params *prm, s
     summary_line(who, !d->have ? "off" : st[3] != 0 ? "host" : "device", st, d->counts);
 }
 
+/* The novel list through the engine (l2r_novel_*, include/lr2rmats_hip.h): every engine shard's novel reads and known reads' genes join the
+ * unit's accumulators while the shard's results still lie in HBM (res == NULL); behind the last shard the list U is merged and its kept
+ * exons, sites, junctions and genes are made on the device, the caller's names of the entries go up, and the updated GTF (stdout or -o)
+ * and the -E file are written batch by batch -- L2R_NOVEL_BATCH blocks / rows (default 1 Mi) and L2R_NOVEL_TEXT_MAX bytes (default
+ * 1 GiB).  The seven counts reach the tail in h_update_opts.novel_counts; the tail, single or threaded, then neither merges U nor prints
+ * the updated GTF or the BED nor walks the known reads for genes.  Not with -s and a junction table (split pieces enter U without a
+ * place).  L2R_NOVEL_ROUTE=host: the engine's host routine; =off: the tail.  A refusal of the unit (-1, -2, -3, or a name outside the
+ * GTF block's domain) does not end the run: nothing has been written yet, the tail does it all and the line says route off.
+ * L2R_TIMING=1: one line on stderr. */
+typedef struct {
+    const h_update_opts *o; const h_chroms *chr; const h_reads *reads; const h_gtf *anno;
+    int has_sj, begun, failed, have;
+    int64_t counts[8], bytes, batches;
+    text_sink out_gtf, out_bed;
+} novel_sink;
+
+static void novel_line(const char *who, const char *route, const double *st, const int64_t *k, int64_t bytes, int64_t batches)
+{
+    if (!summary_timing()) return;
+    fprintf(stderr, "[%s] novel list: route %s, %lld reads in %lld adds, %lld offers, %lld entries (%lld hits), %lld exons, %lld sites, %lld junctions, %lld genes, %lld known genes, "
+            "%lld bytes, %lld batches, %lld clusters, largest %lld\n", who, route, (long long)st[0], (long long)st[4], (long long)st[1], (long long)k[1], (long long)st[9],
+            (long long)k[3], (long long)k[4], (long long)k[5], (long long)k[0], (long long)k[7], (long long)bytes, (long long)batches, (long long)st[6], (long long)st[7]);
+}
+
+static const h_gtf *g_gene_sort_anno;
+static int gene_sort_cmp(const void *x, const void *y)
+{
+    const h_gtf *g = g_gene_sort_anno;
+    return strcmp(h_str(&g->names, g->gid[*(const int64_t *)x]), h_str(&g->names, g->gid[*(const int64_t *)y]));
+}
+/* tx_gene[t]: the ordinal of transcript t's gene-id string among the annotation's distinct gene-id strings (in strcmp order); *na_gene: the
+ * ordinal of a gene called NA, or the number of distinct strings where there is none */
+static uint32_t *gene_ordinals(const h_gtf *g, uint32_t *na_gene)
+{
+    const int64_t T = g->n_tx;
+    int64_t *idx = (int64_t *)h_malloc((size_t)(T ? T : 1) * 8);
+    uint32_t *ord = (uint32_t *)h_malloc((size_t)(T ? T : 1) * 4);
+    for (int64_t t = 0; t < T; ++t) idx[t] = t;
+    g_gene_sort_anno = g;
+    qsort(idx, (size_t)T, sizeof idx[0], gene_sort_cmp);
+    uint32_t n = 0; int have_na = 0;
+    for (int64_t k = 0; k < T; ++k) {
+        const char *id = h_str(&g->names, g->gid[idx[k]]);
+        if (k > 0 && strcmp(id, h_str(&g->names, g->gid[idx[k - 1]])) != 0) ++n;
+        ord[idx[k]] = n;
+        if (!have_na && strcmp(id, "NA") == 0) { have_na = 1; *na_gene = n; }
+    }
+    if (!have_na) *na_gene = T ? n + 1 : 0;
+    free(idx);
+    return ord;
+}
+
+static void novel_shard(l2r_ctx *ctx, const l2r_params *prm, novel_sink *d, const int32_t *tid, int64_t n)
+{
+    if (d->failed) return;
+    if (!d->begun) {
+        int64_t *ref_off = NULL; uint8_t *ref_names = NULL;
+        ref_table(d->chr, &ref_off, &ref_names);
+        uint32_t na_gene = 0;
+        uint32_t *tx_gene = gene_ordinals(d->anno, &na_gene);
+        const l2r_novel_params np = { d->chr->n, ref_off, ref_names, d->anno->n_tx, tx_gene, na_gene, d->has_sj, (int32_t)strlen(d->o->source), (const uint8_t *)d->o->source,
+                                      (int64_t)d->anno->names.len, (const uint8_t *)d->anno->names.buf, d->anno->gid, d->anno->gname };
+        const int rc = l2r_novel_begin(ctx, prm, &np);
+        free(ref_off); free(ref_names); free(tx_gene);
+        if (rc) { d->failed = 1; return; }
+        d->begun = 1;
+    }
+    const l2r_summary_reads rd = { n, tid, NULL };
+    if (n > 0 && l2r_novel_add(ctx, &rd)) d->failed = 1;
+}
+
+/* the n items of one text (which: L2R_NOVEL_GTF blocks, L2R_NOVEL_BED rows), composed and written batch by batch */
+static void novel_batches(l2r_ctx *ctx, const char *who, novel_sink *d, int which, text_sink *s, int64_t n)
+{
+    const int64_t max_items = batch_env_count("L2R_NOVEL_BATCH", (int64_t)1 << 20), max_bytes = batch_env_count("L2R_NOVEL_TEXT_MAX", (int64_t)1 << 30);
+    for (int64_t first = 0; first < n;) {
+        int64_t take = 0, bytes = 0;
+        if (l2r_novel_lines(ctx, which, first, max_items, max_bytes, &take, &bytes) || take < 1) engine_fail(who);
+        if (bytes) {
+            if (l2r_novel_out(ctx, text_sink_room(s, bytes), bytes)) engine_fail(who);
+            text_sink_put(who, s, bytes);
+        }
+        ++d->batches; d->bytes += bytes; first += take;
+    }
+    text_sink_done(who, s);
+}
+
+static void novel_done(l2r_ctx *ctx, const char *who, const l2r_params *prm, novel_sink *d)
+{
+    double st[12] = {0};
+    if (!d->begun && !d->failed) novel_shard(ctx, prm, d, NULL, 0);          /* (no record) */
+    if (!d->failed && l2r_novel_finish(ctx, d->counts)) d->failed = 1;
+    if (!d->failed) {
+        /* the names of the entries alone: a table of their read names and transcript ids */
+        const int64_t U = d->counts[1];
+        int32_t *src = (int32_t *)h_malloc((size_t)(U ? U : 1) * 4);
+        uint32_t *qn = (uint32_t *)h_malloc((size_t)(U ? U : 1) * 4), *tn = (uint32_t *)h_malloc((size_t)(U ? U : 1) * 4);
+        h_strtab tab; memset(&tab, 0, sizeof tab);
+        if (l2r_novel_entries_out(ctx, src, NULL, NULL, NULL)) engine_fail(who);
+        for (int64_t e = 0; e < U; ++e) {
+            const int64_t i = src[e];
+            if (i < 0 || i >= d->reads->n) h_fatal(who, "entry %lld of the novel list names read %lld of %lld", (long long)e, (long long)i, (long long)d->reads->n);
+            qn[e] = h_str_add(&tab, h_str(&d->reads->names, d->reads->qname[i]));
+            tn[e] = d->reads->tid_name ? h_str_add(&tab, h_str(&d->reads->names, d->reads->tid_name[i])) : qn[e];
+        }
+        const l2r_novel_name_table nt = { (int64_t)tab.len, (const uint8_t *)tab.buf, qn, tn };
+        int64_t n_lines = 0, n_bytes = 0;
+        if (l2r_novel_names(ctx, &nt, &n_lines, &n_bytes)) d->failed = 1;       /* (a name outside the block's domain: nothing has been written) */
+        free(src); free(qn); free(tn); free(tab.buf);
+        if (!d->failed) {
+            (void)l2r_novel_stats(ctx, st, 12);
+            fflush(d->out_gtf.fp);
+            novel_batches(ctx, who, d, L2R_NOVEL_GTF, &d->out_gtf, U);
+            if (d->out_bed.fp) novel_batches(ctx, who, d, L2R_NOVEL_BED, &d->out_bed, d->counts[3]);
+        }
+    }
+    d->have = !d->failed;
+    if (!d->have) { if (summary_timing()) fprintf(stderr, "[%s] novel list: the engine declined (%s)\n", who, l2r_last_error()); memset(d->counts, 0, sizeof d->counts); }
+    novel_line(who, !d->have ? "off" : st[5] != 0 ? "host" : "device", st, d->counts, d->bytes, d->batches);
+}
+
 static void run_engine(const char *who, const l2r_params *prm, const l2r_annotation *a, const l2r_junctions *s,
                        const l2r_reads *r, h_result *out, int64_t **acc_read, detail_sink *detail /* NULL: none; only with acc_read == NULL */,
-                       lists_sink *lists /* likewise */, summary_sink *summary /* likewise */)
+                       lists_sink *lists /* likewise */, summary_sink *summary /* likewise */, novel_sink *novel /* likewise */)
 {
     int anno_set = 0;
     l2r_ctx *ctx = engine_take(who, &anno_set);
@@ -1056,6 +1179,7 @@ static void run_engine(const char *who, const l2r_params *prm, const l2r_annotat
         if (detail && !acc_read) detail_shard(ctx, who, detail, lo, hi, out);
         if (lists && !acc_read) lists_shard(ctx, who, lists, lo, hi, out);
         if (summary && !acc_read) summary_shard(ctx, prm, summary, r->tid + lo, hi - lo);
+        if (novel && !acc_read) novel_shard(ctx, prm, novel, r->tid + lo, hi - lo);
         rows += add_rows; exons += add_ex;
         lo = hi;
     } while (lo < r->n_reads);
@@ -1070,6 +1194,7 @@ static void run_engine(const char *who, const l2r_params *prm, const l2r_annotat
     }
     if (lists && !acc_read) lists_done(who, lists);
     if (summary && !acc_read) summary_done(ctx, who, prm, summary);
+    if (novel && !acc_read) novel_done(ctx, who, prm, novel);       /* (last: it takes the GTF-text unit's state over) */
     h_stage_time("engine: upload, kernels, download");
     l2r_destroy(ctx);
     if ((detail || lists) && !acc_read) h_stage_time("engine: context destroyed");
@@ -1464,7 +1589,7 @@ static int update_gtf_multi(h_job *j, int n_gpus, int gathered)
                 off = (int64_t *)h_malloc((size_t)(hi - lo + 1) * 8);
                 for (int64_t i = 0; i <= hi - lo; ++i) off[i] = r.cig_off[lo + i] - r.cig_off[lo];
                 sub.cig_off = off; sub.first_read_index = lo;
-                run_engine("update_gtf", &prm, &a, &s, &sub, &out, NULL, NULL, NULL, NULL);
+                run_engine("update_gtf", &prm, &a, &s, &sub, &out, NULL, NULL, NULL, NULL, NULL);
             } else result_reserve(&out, 0, 0);
             l2r_result res = { out.n, out.n_ex, out.n_ex, out.ex_off, out.ex_start, out.ex_end, out.ex_flag, out.info, out.ref_tx };
             h_job_finish_part(j, lo, hi, &res, suffix, tmp_base, k == 0, cnt);
@@ -1611,7 +1736,16 @@ int h_cmd_update_gtf(int argc, char **argv)
         const char *sr = getenv("L2R_SUMMARY_ROUTE");
         const int summary_by_engine = j->o.summary && !(sr && !strcmp(sr, "off"));
         summary_sink ssink; memset(&ssink, 0, sizeof ssink);
-        run_engine("update_gtf", &prm, &a, &s, &r, &out, NULL, by_engine ? &sink : NULL, lists_by_engine ? &lsink : NULL, summary_by_engine ? &ssink : NULL);
+        /* the novel list likewise (novel_shard): the tail merges no U and prints neither the updated GTF nor the BED; not with -s and a
+         * junction table; L2R_NOVEL_ROUTE=off: the tail */
+        const char *nr = getenv("L2R_NOVEL_ROUTE");
+        const int novel_by_engine = j->o.out_gtf && !(prm.split_trans && s.n > 0) && !(nr && !strcmp(nr, "off"));
+        novel_sink nsink; memset(&nsink, 0, sizeof nsink);
+        nsink.o = &j->o; nsink.chr = &j->chr; nsink.reads = &j->reads; nsink.anno = &j->anno; nsink.has_sj = s.n > 0;
+        nsink.out_gtf.fp = j->o.out_gtf; nsink.out_gtf.what = "the updated GTF"; nsink.out_bed.fp = j->o.exon_bed; nsink.out_bed.what = "the novel-exon BED";
+        run_engine("update_gtf", &prm, &a, &s, &r, &out, NULL, by_engine ? &sink : NULL, lists_by_engine ? &lsink : NULL, summary_by_engine ? &ssink : NULL, novel_by_engine ? &nsink : NULL);
+        if (nsink.have) j->o.novel_counts = nsink.counts;
+        else if (!novel_by_engine) { const double st0[12] = {0}; novel_line("update_gtf", "off", st0, nsink.counts, 0, 0); }
         if (ssink.have) j->o.class_counts = ssink.counts;
         else if (j->o.summary && !summary_by_engine) { const double st0[7] = {0, 0, 0, 0, 0, 0, 0}; summary_line("update_gtf", "off", st0, ssink.counts); }
         file_closer closer; memset(&closer, 0, sizeof closer);
@@ -1625,7 +1759,7 @@ int h_cmd_update_gtf(int argc, char **argv)
         if (by_engine || lists_by_engine) h_stage_time("engine-written files closed");
     } else {
         int64_t *idx = NULL;
-        run_engine("update_gtf", &prm, &a, &s, &r, &out, &idx, NULL, NULL, NULL);
+        run_engine("update_gtf", &prm, &a, &s, &r, &out, &idx, NULL, NULL, NULL, NULL);
         l2r_result res = { out.n, out.n_ex, out.n_ex, out.ex_off, out.ex_start, out.ex_end, out.ex_flag, out.info, out.ref_tx };
         rc = h_job_finish_accepted(j, &res, idx);
         free(idx);
@@ -1654,7 +1788,7 @@ static void exons_only(const char *who, const char *fn, const l2r_params *prm, h
     int64_t zero_off = 0; a.tx_ex_off = &zero_off;
     l2r_junctions s; memset(&s, 0, sizeof s);
     l2r_reads r = { reads->n, reads->n_cig, reads->tid, reads->pos, reads->rev, reads->cig_off, reads->cig, 0, reads->cig_sum };
-    run_engine(who, prm, &a, &s, &r, out, NULL, NULL, NULL, NULL);
+    run_engine(who, prm, &a, &s, &r, out, NULL, NULL, NULL, NULL, NULL);
 }
 
 /* src/gtf.c:597-604 print_trans: gene_id + transcript_id only, exons always ascending */

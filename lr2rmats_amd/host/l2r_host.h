@@ -242,6 +242,8 @@ typedef struct {
     h_part_genes *part_genes;    /* non-NULL (parts of a partitioned run): filled for the caller's fix-up of the gene counters */
     const int64_t *class_counts; /* non-NULL: the eight numbers of l2r_summary_finish -- the reads of the classes known, reliable, unreliable,
                                   * unrecognised, then their unique transcripts; the tail then runs none of the four merges of the summary */
+    const int64_t *novel_counts; /* non-NULL: the eight numbers of l2r_novel_finish, and the engine has written the updated GTF and the -E file: the
+                                  * tail then merges no list U, prints neither of the two and does not walk the known reads for genes */
 } h_update_opts;
 
 /* Everything update_gtf() does after check_with_anno_trans/check_with_short_sj:
@@ -263,6 +265,8 @@ void h_list_rows(FILE *fp, const h_update_opts *o, const h_chroms *chr, const h_
 void h_write_summary_text(FILE *s, int anno_genes, int anno_tx, const int64_t *counters);
 /* the eight numbers of l2r_summary_finish into the summary counters 6 and 8-14 */
 void h_summary_class_counters(int64_t *counters, const int64_t *class_counts);
+/* the eight numbers of l2r_novel_finish into the summary counters 0-5 and 7 */
+void h_summary_novel_counters(int64_t *counters, const int64_t *novel_counts);
 
 /* The GTF text of a selection of blocks through the engine (l2r_gtftext_*: composed on the device, or by the engine's host routine with
  * L2R_GTX_ROUTE=host), written to fp batch by batch (L2R_GTX_BATCH blocks, default 1 Mi, and L2R_GTX_TEXT_MAX bytes, default 1 GiB).

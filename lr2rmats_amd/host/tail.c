@@ -451,6 +451,11 @@ void h_summary_class_counters(int64_t *k, const int64_t *cc)
     k[13] = cc[3]; k[14] = cc[7];                   /* unrecognised, unique */
 }
 
+void h_summary_novel_counters(int64_t *k, const int64_t *nc)
+{
+    k[0] = nc[0]; k[1] = nc[1]; k[2] = nc[2]; k[3] = nc[3]; k[4] = nc[4]; k[5] = nc[5]; k[7] = nc[7];
+}
+
 static void summary_and_bed(const tail_ctx *c, const m_list *U)
 {
     /* src/update_gtf.c:421-587 print_trans_summary */
@@ -494,19 +499,20 @@ static void summary_and_bed(const tail_ctx *c, const m_list *U)
     if (c->o->summary || c->o->summary_counts) {
         /* :496-528: classes of every input read + unique counts through merge_trans on fresh lists -- or, where the engine has made
          * them (class_counts, l2r_summary_finish), the genes of the known reads alone */
-        const int by_engine = c->o->class_counts != NULL;
+        const int by_engine = c->o->class_counts != NULL, by_novel = c->o->novel_counts != NULL;      /* by_novel: U is empty, the known genes are the engine's */
         int n_known = 0, n_rel = 0, n_unrel = 0, n_unrec = 0;
         m_list uk, ur, uu, un; memset(&uk, 0, sizeof uk); memset(&ur, 0, sizeof ur); memset(&uu, 0, sizeof uu); memset(&un, 0, sizeof un);
         for (int64_t i = 0; i < r->n; ++i) {
             const uint32_t info = r->info[i];
             if (by_engine) {
+                if (by_novel) break;
                 if (info & L2R_INFO_KNOWN) add_gene(&G, &known_genes, &g_cap, c->reads->tid[i], gene_id_of(c, r->ref_tx[i]));
                 continue;
             }
             const int64_t off = r->ex_off[i]; const int n = (int)L2R_INFO_NEXON(info);
             m_cand t = { c->reads->tid[i], r->ex_start[off], r->ex_end[off + n - 1], n, (uint8_t)((info & L2R_INFO_REV) != 0), r->ex_start + off, r->ex_end + off, NULL };
             m_list *dst;
-            if (info & L2R_INFO_KNOWN) { ++n_known; add_gene(&G, &known_genes, &g_cap, t.tid, gene_id_of(c, r->ref_tx[i])); dst = &uk; }
+            if (info & L2R_INFO_KNOWN) { ++n_known; if (!by_novel) add_gene(&G, &known_genes, &g_cap, t.tid, gene_id_of(c, r->ref_tx[i])); dst = &uk; }
             else if (info & L2R_INFO_KNOWN_SITE) { if (info & L2R_INFO_UNREL) { ++n_unrel; dst = &uu; } else { ++n_rel; dst = &ur; } }
             else { ++n_unrec; dst = &un; }
             if (!m_merge(&t, dst, p)) m_push(dst, &t);
@@ -515,11 +521,12 @@ static void summary_and_bed(const tail_ctx *c, const m_list *U)
         int64_t cnt[H_N_SUMMARY] = { upd_genes, U->n, partial, e_n, (int64_t)d_n + a_n, j_n, n_known, known_genes, uk.n,
                                      n_rel, n_unrel, ur.n, uu.n, n_unrec, un.n, 0 };
         if (by_engine) h_summary_class_counters(cnt, c->o->class_counts);
+        if (by_novel) h_summary_novel_counters(cnt, c->o->novel_counts);
         if (c->o->summary_counts) memcpy(c->o->summary_counts, cnt, sizeof cnt);
         if (c->o->summary) h_write_summary_text(c->o->summary, c->anno->gene_n, (int)c->anno->n_tx, cnt);
         m_free(&uk); m_free(&ur); m_free(&uu); m_free(&un);
     }
-    if (c->o->exon_bed) {                                          /* :571-576 (BAM header names) */
+    if (c->o->exon_bed && !c->o->novel_counts) {                   /* :571-576 (BAM header names) */
         obuf o; ob_init(&o, c->o->exon_bed);
         for (int i = 0; i < e_n; ++i) {
             ob_s(&o, c->chr->name[E[i].tid]); ob_c(&o, '\t'); ob_i(&o, E[i].start - 1); ob_c(&o, '\t'); ob_i(&o, E[i].end); ob_c(&o, '\t');
@@ -540,6 +547,7 @@ void h_update_tail(const h_update_opts *o, const h_chroms *chr, const h_reads *r
     m_list U; memset(&U, 0, sizeof U);
     l_list K, N, X; memset(&K, 0, sizeof K); memset(&N, 0, sizeof N); memset(&X, 0, sizeof X);
     const int want_k = o->known_gtf != NULL, want_n = o->novel_gtf != NULL, want_x = o->unrecog_gtf != NULL;
+    const int by_novel = o->novel_counts != NULL;                 /* the engine has made U, the updated GTF and the BED (l2r_novel_*) */
 
     for (int64_t i = 0; i < res->n; ++i) {                         /* src/update_gtf.c:939-964 */
         const uint32_t info = res->info[i];
@@ -553,6 +561,7 @@ void h_update_tail(const h_update_opts *o, const h_chroms *chr, const h_reads *r
         const int32_t *xs = res->ex_start + off, *xe = res->ex_end + off; const uint8_t *xf = res->ex_flag + off;
         if (route == T_NOVEL_WHOLE) {
             if (want_n) l_push(&N, i, 0, n - 1, -1);
+            if (by_novel) continue;
             m_cand t = { reads->tid[i], xs[0], xe[n - 1], n, rev, xs, xe, xf };
             if (!m_merge(&t, &U, p)) {
                 m_ent *e = m_push(&U, &t);
@@ -582,7 +591,7 @@ void h_update_tail(const h_update_opts *o, const h_chroms *chr, const h_reads *r
         }
     }
 
-    print_merged(o->out_gtf, &c, &U);                              /* :1087 */
+    if (!by_novel) print_merged(o->out_gtf, &c, &U);               /* :1087 */
     if (o->bam_gtf) print_all_reads(o->bam_gtf, &c);
     if (o->bam_detail) print_detail(o->bam_detail, &c);
     if (want_k) print_ref_list(o->known_gtf, &c, &K);
